@@ -6,8 +6,8 @@
 
 A "step" is one pass of the hot path over the rank's shard: the GLS weight kernel over every node
 (inputs resident in HBM, output written in CSR position on the device) and, for N > 1, the one
-all-gather over RCCL that reassembles the (count, column, value) triplets on every rank.  For N > 1 the line
-also decomposes itself: `compute_only_Mnodes_s` (the kernels with no exchange), `exchange_ms` (the all-gather of one
+all-gather over RCCL that reassembles the (count, column, value) triplets on every rank.  For N > 1 and --full the
+line also decomposes itself: `compute_only_Mnodes_s` (the kernels with no exchange), `exchange_ms` (the all-gather of one
 step's values timed alone) and `apply_Mnodes_s` -- the sharded W . u (each rank applies its own row block, one
 all-gather of 8 B per node), which is what the reference's callers do with the matrix.
 
@@ -18,6 +18,11 @@ With N GPUs the box grows to 216 x 216 x 216 N cells (weak scaling; at N = 8 the
 side, and no rank ever holds the whole mesh.  `--edge-global G` instead fixes the WHOLE mesh at G^3 cells and splits its
 node planes over the ranks (strong scaling; BASELINE config [4] as SURVEY wrote it: --gpus 8 --edge-global 432).
 
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` then also writes what the last
+timed step computed (see dump_outputs).  Everything that takes runs of its own -- the IDW / LS context, every GLS kernel of
+the plan timed alone, the apply leg, end-to-end interpolate(), the device grid build, the other meshes of
+`baseline_configs`, the CPU baseline and, for N > 1, the decomposition of the step -- runs only with `--full`.
+
 Prints ONE JSON line on rank 0.  Besides the contract fields it carries
   roofline      of the dominant kernel, duration measured with HIP events on the launch stream.  GLS: bound "fp64":
                 `achieved` = ALGORITHMIC flops of the multifrontal formulation (tools/count_algorithmic_flops.py:
@@ -25,12 +30,12 @@ Prints ONE JSON line on rank 0.  Besides the contract fields it carries
                 kernel EXECUTES (ISA count) ride beside it as `executed_*`, the HBM figure -- algorithmic bytes of
                 SURVEY 8d / time against 8 TB/s -- as `hbm` / `hbm_frac`; IDW, LS: bound "hbm".  `traffic` from
                 profiles/traffic.json when a PMC run of exactly these kernel sources has been recorded, else null
-  cpu_baseline  our C restatement of the reference's method kernel (kind "port"; the reference itself never
+  cpu_baseline  (--full) our C restatement of the reference's method kernel (kind "port"; the reference itself never
                 travels to the GPU box) timed on this box's host cores on a bounded sample, with the container-measured
                 t_port / t_reference calibration beside it
   fp64          GLS is FP64-ALU-bound, not HBM-bound (SURVEY finding 2): executed and reference-equivalent
                 FLOP/s next to the 78.6 TFLOP/s vector peak.
-  baseline_configs  one row per single-GPU entry of BASELINE.json's `configs`.
+  baseline_configs  (--full) one row per single-GPU entry of BASELINE.json's `configs`.
 """
 import argparse
 import hashlib
@@ -105,6 +110,38 @@ def kernel_source_hash():
             h.update(f.encode())
             h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+# --dump-outputs: entries written per array at most (float64): 48 MB of CSR values + 12 MB of neumann_ws, under 64 MB in all
+DUMP_MAX_ENTRIES = {"weights": 6_000_000, "neumann_ws": 1_500_000}
+
+
+def dump_sample(t, k, seed):
+    """A 1-D device tensor as a float64 numpy array: whole when it has at most k entries, else a fixed seeded sample of at
+    most k of them in index order -- one entry drawn from each of the consecutive blocks of ceil(n / k) entries."""
+    import numpy as np
+    import torch
+    n = t.numel()
+    if n <= k:
+        return t.double().cpu().numpy()
+    stride = -(-n // k)
+    start = np.arange(0, n, stride, dtype=np.int64)
+    width = np.minimum(stride, n - start)
+    idx = start + (np.random.default_rng(seed).random(len(start)) * width).astype(np.int64)
+    return t[torch.from_numpy(idx).to(t.device)].double().cpu().numpy()
+
+
+def dump_outputs(directory, arrays):
+    """What the timed path handed its caller in the last step, as <directory>/<name>.npy: `weights` = the CSR values in
+    esup position (node p's row holds the weights of the cells around p, in esup order; for N > 1 the gathered matrix) and
+    `neumann_ws` = the Neumann weight per node.  The inputs are seeded, so two builds run with the same arguments can be
+    compared array for array."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for seed, (name, t) in enumerate(arrays.items()):
+        a = dump_sample(t, DUMP_MAX_ENTRIES[name], seed)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        print(f"bench.py: wrote {name}.npy ({a.size} of {t.numel()} entries, float64)", file=sys.stderr, flush=True)
 
 
 def cpu_model():
@@ -214,7 +251,16 @@ def main():
                     help="skip the end-to-end interpolate() timing (profiling runs: it launches the kernels in four pieces, which would dilute per-dispatch averages)")
     ap.add_argument("--check", action="store_true",
                     help="(small --edge only) rank 0 recomputes the whole mesh on its GPU and compares the gathered triplets")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: IDW / LS context, per-kernel rows, apply leg, end-to-end "
+                         "interpolate(), device grid build, baseline_configs, CPU baseline, multi-GPU decomposition "
+                         "(the --no-* options and --cpu-sample trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; a fixed seeded "
+                         "sample of an array too large for 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # the driver's shape `python bench.py --gpus N ...`: nothing has initialised the GPU in this process yet
@@ -277,7 +323,7 @@ def main():
         I = ninpol_amd.Interpolator(device=local_rank, num_threads=host_threads, grid_build=args.grid_build)
         I.load_mesh(mesh_obj=mesh)
         t_load = time.time() - t0
-        if not args.no_extras and args.grid_build == "host":
+        if args.full and not args.no_extras and args.grid_build == "host":
             # context: the same load_mesh with the connectivity built by HIP kernels on the GPU
             t0 = time.time()
             I2 = ninpol_amd.Interpolator(device=local_rank, grid_build="device")
@@ -297,9 +343,9 @@ def main():
     gls_counts = g.gls_plan() if args.method == "gls" else None
 
     stream = torch.cuda.current_stream()
-    if world == 1:
-        out = torch.empty(plan.nnz, dtype=torch.float64, device=dev)
-        nws = torch.empty(P_loc, dtype=torch.float64, device=dev)
+    if world == 1:   # zero-filled: --dump-outputs never writes what no step wrote
+        out = torch.zeros(plan.nnz, dtype=torch.float64, device=dev)
+        nws = torch.zeros(P_loc, dtype=torch.float64, device=dev)
 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
 
@@ -344,6 +390,16 @@ def main():
     else:
         total_nodes = n_owned
 
+    if args.dump_outputs:
+        # before anything else launches: the apply leg of --full writes nws again
+        if world > 1:
+            b_last = (splan.n_steps - 1) % 2
+            if rank == 0:
+                dump_outputs(args.dump_outputs, {"weights": torch.cat(splan.pieces(splan.vals[b_last], 0)),
+                                                 "neumann_ws": torch.cat(splan.pieces(splan.neumann[b_last], 1))})
+        else:
+            dump_outputs(args.dump_outputs, {"weights": out, "neumann_ws": nws})
+
     if world > 1:   # which device each rank really sits on
         dv = [None] * world
         dist.all_gather_object(dv, f"cuda:{torch.cuda.current_device()}")
@@ -372,7 +428,7 @@ def main():
         return dt / max(args.steps, 1) * 1e3
 
     decomposition = {}
-    if world > 1:
+    if args.full and world > 1:
         # (1) the kernels alone, no exchange; (2) one step's exchange alone (its buffers hold the last step's values);
         # (3) the sharded apply: W_block . u on the device + the all-gather of node values (ShardedPlan.apply_step)
         decomposition["compute_only_ms"] = timed_leg(lambda i: splan.step(exchange=False), lambda: None)
@@ -397,7 +453,7 @@ def main():
         splan.apply_step(u_loc)
         splan.drain_all()
         decomposition["apply_ms"] = timed_leg(lambda i: splan.apply_step(u_loc), splan.drain_all)
-    else:
+    elif args.full:
         u_loc = torch.from_numpy(np.ascontiguousarray(
             np.asarray(I.cells_data[I.variable_to_index["cells"]["u"]])[:g.n_elems].reshape(1, -1))).to(dev)
         node_vals = torch.empty((1, P_loc), dtype=torch.float64, device=dev)
@@ -497,11 +553,12 @@ def main():
             line["exchange_note"] = ("all-gather of one step's CSR values (8 B per entry" +
                                      (" + 8 B per row of neumann_ws" if splan.gather_neumann else "") +
                                      f"), timed alone: {splan.mx_nnz * 8 * (world - 1) / 1e9:.3f} GB received per GPU")
-        line["apply_Mnodes_s"] = round(total_nodes / decomposition["apply_ms"] / 1e3, 3)
-        line["apply_ms_per_step"] = round(decomposition["apply_ms"], 4)
-        line["apply_note"] = ("W . u for one cell field: weights + row-block apply on the device" +
-                              (f" + ONE all-gather of node values ({splan.mx_rows * 8 * (world - 1) / 1e6:.1f} MB received per GPU)"
-                               if world > 1 else "") + "; what the reference's callers do with the matrix (analytical.py:236)")
+        if "apply_ms" in decomposition:
+            line["apply_Mnodes_s"] = round(total_nodes / decomposition["apply_ms"] / 1e3, 3)
+            line["apply_ms_per_step"] = round(decomposition["apply_ms"], 4)
+            line["apply_note"] = ("W . u for one cell field: weights + row-block apply on the device" +
+                                  (f" + ONE all-gather of node values ({splan.mx_rows * 8 * (world - 1) / 1e6:.1f} MB received per GPU)"
+                                   if world > 1 else "") + "; what the reference's callers do with the matrix (analytical.py:236)")
         if t_load_dev is not None:
             line["setup_s"]["load_mesh_with_device_grid_build"] = round(t_load_dev, 2)
         if check is not None:
@@ -517,7 +574,7 @@ def main():
                             "note": "ref_equiv prices the node rate at the reference's dense dgels 44x25x8 = 74.8 kflop/node "
                                     "(SURVEY 8d); the multifrontal formulation needs 15.9 kflop/node (algorithmic) and the kernel "
                                     "executes 16.7 (the reflector scalars in all four lanes of a node, the quad sums), so ref_equiv may pass 1"}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # context: the two HBM-bound methods on the same grid, and end-to-end interpolate()
             for meth in ("idw", "ls"):
                 if meth == args.method:
@@ -631,7 +688,7 @@ def main():
                     del Io, mo
                     torch.cuda.empty_cache()
                 line["baseline_configs"] = rows
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.method, args.cpu_sample, args.jitter)
             except Exception as e:   # never lose the GPU line to the baseline leg

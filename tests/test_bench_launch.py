@@ -47,3 +47,25 @@ def test_direct_torchrun_form_still_checks_world_size():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-sample", "0"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and "does not match WORLD_SIZE" in r.stderr
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: a small array is written whole, a large one as the same seeded sample on every run, in index
+    order, and the caps keep the files under 64 MB in all."""
+    import numpy as np
+    import torch
+    b = _bench()
+    small = torch.arange(10, dtype=torch.float64)
+    np.testing.assert_array_equal(b.dump_sample(small, 100, 0), small.numpy())
+    big = torch.arange(1_000_003, dtype=torch.float64)
+    a = b.dump_sample(big, 1000, 0)
+    assert a.dtype == np.float64 and 0 < a.size <= 1000
+    np.testing.assert_array_equal(a, b.dump_sample(big, 1000, 0))
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < big.numel()
+    assert sum(8 * k for k in b.DUMP_MAX_ENTRIES.values()) <= 64_000_000
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr

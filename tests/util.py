@@ -7,6 +7,8 @@ import numpy as np
 from ninpol_amd import mesh as M
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# the reference's outputs on the meshes of test_port_matches_reference / test_edges_match_reference (not golden cases)
+REFERENCE_OUTPUTS_DIR = os.path.join(GOLDEN_DIR, "reference_outputs")
 GOLDEN_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
 
 GRID_ARRAYS = ("esup", "esup_ptr", "psup", "psup_ptr", "fsup", "fsup_ptr", "esuf", "esuf_ptr", "esuel",
