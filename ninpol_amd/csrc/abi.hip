@@ -675,22 +675,22 @@ int nin_fields_set(nin_grid *g, const double *permeability, const double *diff_m
 // cube nodes: the multifrontal kernel
 static int launch_hex8(DeviceGrid &d, const int32_t *nodes, const int32_t *desc, int32_t count, int add_neumann,
                        double *out, double *nws, hipStream_t stream) {
-    return launch_gls_hex8mf(d.v, nodes, desc, count, add_neumann, out, nws, d.gls_queue, stream);
+    return launch_gls_hex8mf(d.v, nodes, desc, count, add_neumann, out, nws, d.gls_queue + kGlsQueueHex8, stream);
 }
 
-// the one-wavefront multifrontal kernel, kind 0 / 1 / 2 (work counters: ints 5, 6, 7 of the queue block)
+// the one-wavefront multifrontal kernel, kind 0 / 1 / 2 (work counters: kGlsQueueMfw + kind)
 static int launch_mfw(DeviceGrid &d, const int32_t *nodes, const uint32_t *desc, int32_t count, int kind, int add_neumann,
                       double *out, double *nws, hipStream_t stream) {
-    return launch_gls_mfw(d.v, nodes, desc, count, kind, add_neumann, out, nws, d.gls_queue + 5 + kind, stream);
+    return launch_gls_mfw(d.v, nodes, desc, count, kind, add_neumann, out, nws, d.gls_queue + kGlsQueueMfw + kind, stream);
 }
 
 // one GLS size class: the block kernel with the system in LDS, or the wave kernel on global scratch
 static int launch_class(DeviceGrid &d, int c, const int32_t *nodes, int32_t count, int add_neumann, double *out,
                         double *nws, hipStream_t stream) {
     const auto &k = d.gls[c];
-    if (c < kGlsClasses - 1)   // work counter: ints 1..4 of the queue block (the hex8 kernel uses 0, 16, 32, ...)
+    if (c < kGlsClasses - 1)   // work counter: kGlsQueueBlock + c (device_grid.hpp)
         return launch_gls_block(d.v, nodes, count, k.waves, k.col_slots, k.lds_bytes, add_neumann, out, nws,
-                                d.gls_queue + 1 + c, stream);
+                                d.gls_queue + kGlsQueueBlock + c, stream);
     return launch_gls_class(d.v, nodes, count, 0, k.rows_per_lane, add_neumann, out, nws, d.gls_scratch,
                             d.gls_scratch_stride, d.gls_scratch_slots, stream);
 }
@@ -715,7 +715,7 @@ static int gls_side_begin(DeviceGrid &d, int add_neumann, double *out, double *n
     const auto &k = d.gls[kGlsClasses - 1];
     int rc = 0;
     if (ng > 0)
-        rc = launch_gls_mfg(d.v, d.mfg.nodes + bg, d.mfg_desc + (size_t)kMfgDescWords * bg, ng, add_neumann, out, nws, d.gls_queue + 16, d.mfg_tiles, d.mfg_slots, side);
+        rc = launch_gls_mfg(d.v, d.mfg.nodes + bg, d.mfg_desc + (size_t)kMfgDescWords * bg, ng, add_neumann, out, nws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, side);
     if (!rc && n > 0)
         rc = launch_gls_class(d.v, k.nodes ? k.nodes + b : nullptr, n, 0, k.rows_per_lane, add_neumann, out, nws, d.gls_scratch, d.gls_scratch_stride,
                               d.gls_scratch_slots, side);
@@ -747,10 +747,10 @@ static int launch_gls_but_cube(DeviceGrid &d, int add_neumann, double *out, doub
     for (int i = 0; i < 3 && !rc; ++i)
         if (on(9 + i)) rc = launch_gls_small(d.v, d.small[i].nodes, d.small[i].count, i, add_neumann, out, nws, stream);
     if (!rc && on(12)) rc = launch_gls_quad4(d.v, d.quad4.nodes, d.quad4_desc, d.quad4.count, add_neumann, out, nws, stream);
-    for (int i = 0; i < DeviceGrid::kMfxLists && !rc; ++i)   // (work counters: ints 8 .. 15; lists 6 and 7 -- the small class, (7, 12) -- are kernels 20 and 21 of the plan)
-        if (on(i < 6 ? 13 + i : 14 + i)) rc = launch_gls_mfx(d.v, d.mfx[i].nodes, d.mfx_desc[i], d.mfx[i].count, i, add_neumann, out, nws, d.gls_queue + 8 + i, stream);
-    if (!rc && on(19) && !d.side_pending)   // (work counter: int 16)
-        rc = launch_gls_mfg(d.v, d.mfg.nodes, d.mfg_desc, d.mfg.count, add_neumann, out, nws, d.gls_queue + 16, d.mfg_tiles, d.mfg_slots, stream);
+    for (int i = 0; i < DeviceGrid::kMfxLists && !rc; ++i)   // (work counters: kGlsQueueMfx + i; lists 6 and 7 -- the small class, (7, 12) -- are kernels 20 and 21 of the plan)
+        if (on(i < 6 ? 13 + i : 14 + i)) rc = launch_gls_mfx(d.v, d.mfx[i].nodes, d.mfx_desc[i], d.mfx[i].count, i, add_neumann, out, nws, d.gls_queue + kGlsQueueMfx + i, stream);
+    if (!rc && on(19) && !d.side_pending)   // (work counter: kGlsQueueMfg, off the cube-node kernel's lines)
+        rc = launch_gls_mfg(d.v, d.mfg.nodes, d.mfg_desc, d.mfg.count, add_neumann, out, nws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, stream);
     for (int c = 0; c < kGlsClasses && !rc; ++c) {
         if ((c == kGlsClasses - 1 && d.side_pending) || !on(c)) continue;
         rc = launch_class(d, c, d.gls[c].nodes, d.gls[c].count, add_neumann, out, nws, stream);
@@ -868,10 +868,10 @@ int nin_weights_device(nin_grid *g, int method, const int64_t *targets, int64_t 
         else if (method == NIN_METHOD_LS) rc = launch_ls(d.v, dl, cnt, 0, 0, dev_csr_data, dev_neumann_ws, stream);
         else if ((int)c == kGlsClasses) rc = launch_hex8(d, dl, ddesc, cnt, add_neumann, dev_csr_data, dev_neumann_ws, stream);
         else if ((int)c == kGlsClasses + 8 + DeviceGrid::kMfxLists)
-            rc = launch_gls_mfg(d.v, dl, dmfg, cnt, add_neumann, dev_csr_data, dev_neumann_ws, d.gls_queue + 16, d.mfg_tiles, d.mfg_slots, stream);
+            rc = launch_gls_mfg(d.v, dl, dmfg, cnt, add_neumann, dev_csr_data, dev_neumann_ws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, stream);
         else if ((int)c >= kGlsClasses + 8)
             rc = launch_gls_mfx(d.v, dl, dmfx + kMfxDescWords * (first[c] - first[kGlsClasses + 8]), cnt, (int)c - kGlsClasses - 8, add_neumann, dev_csr_data,
-                                dev_neumann_ws, d.gls_queue + 8 + ((int)c - kGlsClasses - 8), stream);
+                                dev_neumann_ws, d.gls_queue + kGlsQueueMfx + ((int)c - kGlsClasses - 8), stream);
         else if ((int)c == kGlsClasses + 7) rc = launch_gls_quad4(d.v, dl, dquad, cnt, add_neumann, dev_csr_data, dev_neumann_ws, stream);
         else if ((int)c >= kGlsClasses + 4) rc = launch_gls_small(d.v, dl, cnt, (int)c - kGlsClasses - 4, add_neumann, dev_csr_data, dev_neumann_ws, stream);
         else if ((int)c > kGlsClasses)
@@ -1014,12 +1014,12 @@ int weights_chunk(nin_grid *g, int method, int k, double *out, double *nws, hipS
                             d.chunk_off[kGlsClasses - 1][k + 1] - d.chunk_off[kGlsClasses - 1][k], d.chunk_off[lg][k], d.chunk_off[lg][k + 1] - d.chunk_off[lg][k]);
     {
         const int32_t b = d.chunk_off[kGlsClasses][k], n = d.chunk_off[kGlsClasses][k + 1] - b;
-        if (!rc && n > 0) rc = launch_gls_hex8mf(d.v, d.hex8.nodes + b, d.hex8_desc + 4 * (size_t)b, n, 1, out, nws, d.gls_queue, stream);
+        if (!rc && n > 0) rc = launch_gls_hex8mf(d.v, d.hex8.nodes + b, d.hex8_desc + 4 * (size_t)b, n, 1, out, nws, d.gls_queue + kGlsQueueHex8, stream);
     }
     for (int i = 0; i < 3 && !rc; ++i) {
         const int32_t b = d.chunk_off[kGlsClasses + 1 + i][k], n = d.chunk_off[kGlsClasses + 1 + i][k + 1] - b;
         if (n > 0) rc = launch_gls_mfw(d.v, d.mfw[i].nodes + b, d.mfw_desc[i] + (size_t)kMfwDescWords * b, n, i, 1, out, nws,
-                                       d.gls_queue + 5 + i, stream);
+                                       d.gls_queue + kGlsQueueMfw + i, stream);
     }
     for (int i = 0; i < 3 && !rc; ++i) {
         const int32_t b = d.chunk_off[kGlsClasses + 4 + i][k], n = d.chunk_off[kGlsClasses + 4 + i][k + 1] - b;
@@ -1031,19 +1031,19 @@ int weights_chunk(nin_grid *g, int method, int k, double *out, double *nws, hipS
     }
     for (int i = 0; i < DeviceGrid::kMfxLists && !rc; ++i) {
         const int32_t b = d.chunk_off[kGlsClasses + 8 + i][k], n = d.chunk_off[kGlsClasses + 8 + i][k + 1] - b;
-        if (n > 0) rc = launch_gls_mfx(d.v, d.mfx[i].nodes + b, d.mfx_desc[i] + (size_t)kMfxDescWords * b, n, i, 1, out, nws, d.gls_queue + 8 + i, stream);
+        if (n > 0) rc = launch_gls_mfx(d.v, d.mfx[i].nodes + b, d.mfx_desc[i] + (size_t)kMfxDescWords * b, n, i, 1, out, nws, d.gls_queue + kGlsQueueMfx + i, stream);
     }
     if (!rc && !d.side_pending) {
         constexpr int li = kGlsClasses + 8 + DeviceGrid::kMfxLists;
         const int32_t b = d.chunk_off[li][k], n = d.chunk_off[li][k + 1] - b;
-        if (n > 0) rc = launch_gls_mfg(d.v, d.mfg.nodes + b, d.mfg_desc + (size_t)kMfgDescWords * b, n, 1, out, nws, d.gls_queue + 16, d.mfg_tiles, d.mfg_slots, stream);
+        if (n > 0) rc = launch_gls_mfg(d.v, d.mfg.nodes + b, d.mfg_desc + (size_t)kMfgDescWords * b, n, 1, out, nws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, stream);
     }
     for (int c = 0; c < kGlsClasses && !rc; ++c) {
         const int32_t b = d.chunk_off[c][k], n = d.chunk_off[c][k + 1] - b;
         if (n <= 0) continue;
         const auto &kc = d.gls[c];
         if (c < kGlsClasses - 1)
-            rc = launch_gls_block(d.v, kc.nodes + b, n, kc.waves, kc.col_slots, kc.lds_bytes, 1, out, nws, d.gls_queue + 1 + c, stream);
+            rc = launch_gls_block(d.v, kc.nodes + b, n, kc.waves, kc.col_slots, kc.lds_bytes, 1, out, nws, d.gls_queue + kGlsQueueBlock + c, stream);
         else if (!d.side_pending)
             rc = launch_gls_class(d.v, kc.nodes + b, n, 0, kc.rows_per_lane, 1, out, nws, d.gls_scratch, d.gls_scratch_stride,
                                   d.gls_scratch_slots, stream);
@@ -1205,7 +1205,7 @@ int nin_apply_device(nin_grid *g, int method, const double *dev_u_cells, int32_t
         HIP_TRY(hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream));
         int rc = gls_side_begin(d, 1, d.apply_weights, dev_neumann_ws, stream, 0, d.gls[kGlsClasses - 1].count, 0, d.mfg.count);
         if (!rc) rc = launch_gls_hex8mf_apply(d.v, d.hex8.nodes, d.hex8_desc, d.hex8.count, 1, dev_u_cells, n_fields, dev_node_values,
-                                              dev_neumann_ws, d.gls_queue, stream);
+                                              dev_neumann_ws, d.gls_queue + kGlsQueueHex8, stream);
         if (!rc) rc = launch_gls_but_cube(d, 1, d.apply_weights, dev_neumann_ws, stream);
         if (!rc) rc = launch_apply_list(d.v, d.apply_weights, dev_u_cells, n_fields, dev_node_values, d.noncube_nodes, d.noncube_count, stream);
         if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));

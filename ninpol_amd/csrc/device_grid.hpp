@@ -34,8 +34,29 @@ struct GridView {  // passed to kernels by value
 #define NIN_HD
 #endif
 
-constexpr int kGlsQueueInts = 8 * 16;   // hex8 kernel: one work counter per XCD, each on its own 64-byte line
 constexpr int kGlsClasses = 5;  // four LDS budget classes (1 / 2 / 4 / 8 waves per node) + one global-scratch class
+// The GLS kernels' work counters: one block of kGlsQueueInts ints per grid, zeroed before every launch (and before every piece of
+// interpolate()'s pipeline).  The kernels of one launch run at the same time -- the side stream's under the main stream's -- so no
+// two of them may share an int:
+//   hex8 (kernels_gls_hex8mf.hip)      ints 0 + 16 * xcd   one per XCD, each on its own 64-byte line (a grid of fewer than
+//                                                          8 workgroups uses int 0 alone)
+//   block (kernels_gls_block.hip)      ints 1 .. 4         one per LDS class
+//   mfw (kernels_gls_mfw.hip)          ints 5 .. 7         one per kind
+//   mfx (kernels_gls_mfx.hip)          ints 8 .. 15        one per list
+//   mfg (kernels_gls_mfg.hip)          int 128             a 64-byte line of its own, past hex8's eight
+constexpr int kGlsQueueLine = 16;                 // ints per 64-byte line
+constexpr int kGlsQueueHex8 = 0, kGlsQueueHex8Lines = 8;
+constexpr int kGlsQueueBlock = 1;                 // + class (0 .. kGlsClasses - 2)
+constexpr int kGlsQueueMfw = 5;                   // + kind (0 .. 2)
+constexpr int kGlsQueueMfx = 8, kGlsQueueMfxLists = 8;   // + list (0 .. DeviceGrid::kMfxLists - 1)
+constexpr int kGlsQueueMfg = 8 * kGlsQueueLine;
+constexpr int kGlsQueueInts = 9 * kGlsQueueLine;
+static_assert(kGlsQueueBlock > kGlsQueueHex8 && kGlsQueueBlock + (kGlsClasses - 1) <= kGlsQueueMfw, "block counters overlap");
+static_assert(kGlsQueueMfw + 3 <= kGlsQueueMfx, "mfw counters overlap the mfx counters");
+static_assert(kGlsQueueMfx + kGlsQueueMfxLists <= kGlsQueueLine, "the block / mfw / mfx counters must stay between hex8's ints 0 and 16");
+static_assert(kGlsQueueMfg % kGlsQueueLine == 0 && kGlsQueueMfg / kGlsQueueLine >= kGlsQueueHex8 / kGlsQueueLine + kGlsQueueHex8Lines,
+              "the mfg counter must lie on none of hex8's eight lines");
+static_assert(kGlsQueueMfg < kGlsQueueInts, "the mfg counter lies outside the block");
 // LDS bytes a node's system may take in class c and the waves per node the block kernel runs it with
 // (16 / 5 / 2 / 1 workgroups per CU); the last class keeps its systems in global-memory scratch.
 NIN_HD inline int32_t gls_class_budget(int c) { return c == 0 ? 10240 : c == 1 ? 32768 : c == 2 ? 81920 : c == 3 ? 159744 : 0; }
@@ -86,6 +107,7 @@ struct DeviceGrid {
     // kernels_gls_mfx.hip (mfx_desc.hpp): interior nodes of unstructured meshes, up to 16 fronts + 21 dense cells, one list per size
     // class of the dense problem (6 x 10, 7 x 11, 8 x 13, 9 x 15, 10 x 16 tiles)
     static constexpr int kMfxLists = 8;   // (the sixth: boundary nodes, kernels_gls_mfx.hip's BND instantiation; the seventh: the small interior class (4, 7); the eighth: (7, 12))
+    static_assert(kMfxLists <= kGlsQueueMfxLists, "one work counter per mfx list");
     GlsClass mfx[kMfxLists];
     uint32_t *mfx_desc[kMfxLists] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [kMfxDescWords * mfx[c].count] descriptor words
     // kernels_gls_mfg.hip (mfg_desc.hpp): interior nodes beyond the wide kernel's registers (up to 32 fronts + 40 dense cells): the tiles
@@ -103,7 +125,7 @@ struct DeviceGrid {
     double *gls_scratch = nullptr;  // global-memory systems for the oversize class
     int64_t gls_scratch_stride = 0; // doubles per wave slot
     int32_t gls_scratch_slots = 0;
-    int32_t *gls_queue = nullptr;   // [kGlsQueueInts]
+    int32_t *gls_queue = nullptr;   // [kGlsQueueInts] the work counters (kGlsQueue* above)
     // buffers of nin_interpolate_csr_host / nin_csr_compact_host, allocated on first use and kept (0.65 + 0.98 GB at
     // 10 M cells; allocating and freeing them cost ~10 ms of every call)
     double *e2e_weights = nullptr, *e2e_nws = nullptr, *e2e_data = nullptr;

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
         const int32_t xcd = blockIdx.x & 7, per = (n_groups + 7) / 8;
         wg_lo = xcd * per;
         wg_end = (xcd + 1) * per < n_groups ? (xcd + 1) * per : n_groups;
-        q = queue + 16 * xcd;   // one counter per 64-byte line
+        q = queue + kGlsQueueLine * xcd;   // one counter per 64-byte line (device_grid.hpp: the counter block)
     } else {
         wg_lo = 0;
         wg_end = n_groups;

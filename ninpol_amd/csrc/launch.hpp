@@ -43,7 +43,8 @@ int launch_gls_block(const GridView &g, const int32_t *nodes, int32_t count, int
 const char *kernel_name_gls_block();
 // the multifrontal kernel for cube nodes (kernels_gls_hex8mf.hip): 4 lanes per node; `desc` = 4 descriptor words per
 // list entry (hex8_desc.hpp, filled by launch_hex8_desc);
-// `queue`: kGlsQueueInts zeroed device ints (one work counter per XCD, each on its own cache line)
+// `queue`: the grid's zeroed counter block + kGlsQueueHex8 (one work counter per XCD at queue + 16 * xcd, each on its own cache line:
+// ints kGlsQueueHex8 .. + 112 are the kernel's, device_grid.hpp)
 int launch_hex8_desc(const GridView &g, const int32_t *nodes, int32_t count, int32_t *desc, hipStream_t stream);
 int launch_gls_hex8mf(const GridView &g, const int32_t *nodes, const int32_t *desc, int32_t count, int add_neumann,
                       double *out, double *nws, int32_t *queue, hipStream_t stream);

@@ -320,6 +320,78 @@ def quad_tri_mesh_2d(nx, ny=None, jitter=0.0, seed=0):
     return Mesh(pts, [CellBlock("quad", quads), CellBlock("triangle", tris)])
 
 
+def composite_mesh(parts, interleave=True):
+    """The disjoint union of several meshes: one mesh whose connected components are the `parts`, so that every kernel a
+    part needs runs in the same launch.  Points are concatenated as they are (the parts may overlap in space: the grid is
+    built from connectivity alone); blocks of one cell type are merged into one block (cell_data_dict is keyed by type),
+    each holding the parts' cells in part order.  The blocks are ordered so that every part's cells keep their relative order
+    where the parts' own block orders allow it: a node's cells are then listed in the same order as in its part, and the
+    methods form the same sums (GLS on a mixed mesh is sensitive to the column order of its systems at ~1e-8).
+
+    interleave: global node ids follow each node's fractional position inside its own part (a stable merge on
+    (local id + 0.5) / n_part): every part keeps its own node order, and every quarter of the node range holds about a quarter of
+    every part -- interpolate() cuts each kernel's list by node range, and the parts' kernels then share every piece.  Without
+    it the parts' nodes follow one another.
+
+    The returned mesh carries `part_nodes` / `part_cells`: per part, the global id of each local node / cell.  Point and cell
+    data arrays that every part has are carried over, mapped the same way."""
+    n_pts = [int(p.points.shape[0]) for p in parts]
+    total = sum(n_pts)
+    if interleave:
+        key = np.concatenate([(np.arange(n) + 0.5) / n for n in n_pts])
+        order = np.argsort(key, kind="stable")          # ties: the lower part first
+        gid = np.empty(total, dtype=np.int64)
+        gid[order] = np.arange(total)
+    else:
+        gid = np.arange(total, dtype=np.int64)
+    part_nodes = np.split(gid, np.cumsum(n_pts)[:-1])
+    points = np.empty((total, 3))
+    points[gid] = np.concatenate([np.asarray(p.points, dtype=float) for p in parts])
+    # block order: every part's own block order wherever the parts agree on it (then each part's cells keep their relative
+    # order, and so does every node's list of cells); ties and conflicts go to the type that appears first
+    seen = []
+    for p in parts:
+        seen += [b.type for b in p.cells if b.type not in seen]
+    before = {t: set() for t in seen}
+    for p in parts:
+        order_p = [b.type for b in p.cells]
+        for k, t in enumerate(order_p):
+            before[t].update(u for u in order_p[:k] if u != t)
+    types = []
+    while len(types) < len(seen):
+        free = [t for t in seen if t not in types and before[t] <= set(types)]
+        types.append(free[0] if free else next(t for t in seen if t not in types))
+    part_cells = [np.empty(p.n_cells, dtype=np.int64) for p in parts]
+    blocks, pieces = [], []           # pieces: (part, first local cell, count) in global cell order
+    at = 0
+    for t in types:
+        data = []
+        for i, p in enumerate(parts):
+            first = 0
+            for b in p.cells:
+                if b.type == t:
+                    data.append(part_nodes[i][np.asarray(b.data)])
+                    part_cells[i][first:first + len(b)] = at + np.arange(len(b))
+                    pieces.append((i, first, len(b)))
+                    at += len(b)
+                first += len(b)
+        blocks.append(CellBlock(t, np.vstack(data)))
+    sizes = np.cumsum([0] + [len(b) for b in blocks])
+    cell_data = {}
+    for name in set.intersection(*(set(p.cell_data) for p in parts)):
+        flat = [np.concatenate(p.cell_data[name]) for p in parts]
+        merged = np.concatenate([flat[i][f:f + n] for i, f, n in pieces])
+        cell_data[name] = [merged[sizes[b]:sizes[b + 1]] for b in range(len(blocks))]
+    point_data = {}
+    for name in set.intersection(*(set(p.point_data) for p in parts)):
+        a = np.concatenate([np.asarray(p.point_data[name]) for p in parts])
+        point_data[name] = np.empty_like(a)
+        point_data[name][gid] = a
+    m = Mesh(points, blocks, point_data=point_data, cell_data=cell_data)
+    m.part_nodes, m.part_cells = part_nodes, part_cells
+    return m
+
+
 def _fix_tet_orientation(pts, tets):
     a, b, c, d = (pts[tets[:, i]] for i in range(4))
     vol = np.einsum("ij,ij->i", np.cross(b - a, c - a), d - a)

@@ -173,3 +173,40 @@ def csr_rowscaled_err(W, indptr, indices, data):
     scale[scale == 0] = 1.0
     d = np.where(np.isfinite(b), np.abs(np.nan_to_num(a) - np.nan_to_num(b)), 0.0)
     return float((d / scale[rows]).max())
+
+
+# ---- composite meshes (mesh.composite_mesh): a part's rows of the union, in the part's own layout ---------------------------
+
+def esup_csr(grid, w):
+    """a dense (n_points, MX_ELEMENTS_PER_POINT) weight table in esup layout (entry j of row p belongs to cell
+    esup[esup_ptr[p] + j]) as a scipy CSR (n_points, n_elems); explicit zeros are kept."""
+    import scipy.sparse as sp
+    ptr, esup = np.asarray(grid.esup_ptr), np.asarray(grid.esup)
+    cnt = np.diff(ptr)
+    rows = np.repeat(np.arange(len(cnt)), cnt)
+    local = np.arange(len(esup)) - np.repeat(ptr[:-1], cnt)
+    return sp.csr_matrix((np.asarray(w)[rows, local], esup, ptr), shape=(len(cnt), int(grid.n_elems)))
+
+
+def part_table(W, part_grid, nodes, cells):
+    """the rows of a composite mesh's weights W (scipy CSR over the composite's nodes and cells) that belong to one part, as a
+    dense table in the PART's esup layout: row p, entry j = W[nodes[p], cells[c]] with c = esup[esup_ptr[p] + j] of the part's
+    own grid.  (That the composite's cells around nodes[p] are exactly cells[...] of the part's is a grid property:
+    test_composite.py checks it.)"""
+    ptr, esup = np.asarray(part_grid.esup_ptr), np.asarray(part_grid.esup)
+    cnt = np.diff(ptr)
+    rows = np.repeat(np.arange(len(cnt)), cnt)
+    local = np.arange(len(esup)) - np.repeat(ptr[:-1], cnt)
+    W = W.tocsr()
+    W.sort_indices()
+    r, c = np.asarray(nodes)[rows], np.asarray(cells)[esup]
+    # position of column c in row r of W (columns sorted inside each row)
+    lo, hi = W.indptr[r], W.indptr[r + 1]
+    key = r.astype(np.int64) * (int(W.shape[1]) + 1) + c
+    flat = np.repeat(np.arange(W.shape[0], dtype=np.int64), np.diff(W.indptr)) * (int(W.shape[1]) + 1) + W.indices
+    pos = np.searchsorted(flat, key)
+    found = (pos < hi) & (pos >= lo)
+    found[found] = W.indices[pos[found]] == c[found]
+    out = np.zeros((len(cnt), int(part_grid.MX_ELEMENTS_PER_POINT)))
+    out[rows[found], local[found]] = W.data[pos[found]]
+    return out
