@@ -157,6 +157,30 @@ int nin_apply_device(nin_grid *g, int method, const double *dev_u_cells, int32_t
 int nin_apply_fields_host(nin_grid *g, int method, const double *u_cells, int32_t n_fields, double *node_values,
                           double *neumann_ws);
 
+/* ---- the adjoint: W^T v, and W . u on weights the caller holds -----------------------------------------------------------
+ * W is exactly the matrix nin_apply_* use and interpolate() returns, `+ neumann_ws[row]` of interpolator.pyx:618 included: the weights
+ * nin_weights_device(..., add_neumann = 1, ...) writes in esup / CSR position (entry j of node p at csr_data[esup_ptr[p] + j], column
+ * esup[esup_ptr[p] + j]).  With that W, <W u, v> = <u, W^T v>; the empty rows of Dirichlet nodes contribute nothing.  The reference's
+ * callers form W.T @ v in scipy on the host (no reference counterpart on the device).
+ *
+ * nin_spmv_device: node_values = W . u_cells for n_fields cell fields, u_cells [n_fields][n_elems] -> node_values [n_fields][n_points],
+ *   row-major (the layout of nin_apply_fields_host): the kernels nin_apply_device runs after its weights, without recomputing them.
+ * nin_spmv_transpose_device: cell_values[f][e] = sum over the nodes p of cell e of W[p, e] * node_values[f][p], node_values
+ *   [n_fields][n_points] -> cell_values [n_fields][n_elems].  Deterministic, no atomics: each cell sums its nodes' terms in ascending node
+ *   id (the order scipy's W.T @ v accumulates in); two calls agree bit for bit, and so do a batch of k fields and k single calls.  The
+ *   first call on a grid builds the cell-major index of the esup pattern on the device (4 (E+1) + 8 nnz_esup bytes of HBM, kept by the
+ *   grid until nin_grid_release_scratch) and synchronises `stream`; later calls are asynchronous on `stream`.
+ * Both take DEVICE pointers (dev_csr_data [nnz_esup]) and a hipStream_t `stream` (NULL = default); neither needs nin_fields_set.
+ * nin_apply_transpose_fields_host: the host-pointer counterpart of nin_apply_fields_host -- the weights of `method` (add_neumann = 1,
+ *   unfused) into the grid's apply buffer, then nin_spmv_transpose_device; node_values [n_fields][n_points] -> cell_values
+ *   [n_fields][n_elems]; synchronous.  NIN_ESTATE before nin_fields_set, or for GLS without permeability.
+ * All three: NIN_EINVAL for a NULL pointer or n_fields < 1, NIN_ENODEVICE for a grid that is not on a device. */
+int nin_spmv_device(nin_grid *g, const double *dev_csr_data, const double *dev_u_cells, int32_t n_fields, double *dev_node_values,
+                    void *stream);
+int nin_spmv_transpose_device(nin_grid *g, const double *dev_csr_data, const double *dev_node_values, int32_t n_fields,
+                              double *dev_cell_values, void *stream);
+int nin_apply_transpose_fields_host(nin_grid *g, int method, const double *node_values, int32_t n_fields, double *cell_values);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].
@@ -179,7 +203,7 @@ int nin_host_free(void *ptr);
 
 /* Give back the scratch a grid keeps between calls: the device buffers nin_interpolate_csr_host / nin_csr_compact_host /
  * nin_apply_* allocate on first use (weights, compacted triplets, counters: ~2.3 GB of HBM at 10 M cells, 8 x that at
- * 80 M) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
+ * 80 M), the transpose index of nin_spmv_transpose_device (~0.69 GB at 10 M hexahedra) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
  * weight table when interpolate() returns, interpolator.pyx:650-651.) */
 int nin_grid_release_scratch(nin_grid *g);
 

@@ -265,6 +265,47 @@ int locality_order(const DeviceGrid &d, int32_t *list, int32_t count, const int3
     (void)hipFree(keys); (void)hipFree(keys_out); (void)hipFree(list_out); (void)hipFree(tmp);
     return rc;
 }
+
+// a buffer of d.allocs given back before the grid goes
+void dev_release(DeviceGrid &d, void *p) {
+    if (!p) return;
+    auto it = std::find(d.allocs.begin(), d.allocs.end(), p);
+    if (it != d.allocs.end()) d.allocs.erase(it);
+    (void)hipFree(p);
+}
+
+// The cell-major index of the esup pattern (DeviceGrid::tr_*), built once per grid by the first transpose call: a stable radix sort
+// of the pairs (esup[j], j) by cell keeps ascending j -- hence ascending node id -- within each cell; cell_ptr and the node of each
+// position follow by binary search.  Synchronises `stream` (the sort's temporaries are freed before the call returns).
+int ensure_transpose_index(DeviceGrid &d, hipStream_t stream) {
+    if (d.tr_cell_ptr) return NIN_OK;
+    const int32_t E = d.v.n_elems, nnz = (int32_t)d.nnz_e;
+    int32_t *ptr = nullptr, *pos = nullptr, *node = nullptr, *cells_sorted = nullptr;
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+    int end_bit = 1;
+    while (end_bit < 31 && (int64_t{1} << end_bit) < (int64_t)E) ++end_bit;   // the cell ids fit in end_bit bits
+    int rc = dev_alloc(d, &ptr, (size_t)E + 1);
+    if (!rc) rc = dev_alloc(d, &pos, (size_t)nnz);
+    if (!rc) rc = dev_alloc(d, &node, (size_t)nnz);   // holds the sort's values 0 .. nnz-1 until cell_node overwrites it
+    auto step = [&](hipError_t e) { if (e != hipSuccess && rc == NIN_OK) rc = fail(NIN_EHIP, "transpose index: %s", hipGetErrorString(e)); return rc == NIN_OK; };
+    if (!rc && nnz > 0) {
+        if (step(hipMalloc((void **)&cells_sorted, (size_t)nnz * sizeof(int32_t))) &&
+            step(launch_iota(node, nnz, stream) ? hipErrorLaunchFailure : hipSuccess) &&
+            step(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d.v.esup, cells_sorted, node, pos, nnz, 0, end_bit, stream)) &&
+            step(hipMalloc(&tmp, tmp_bytes)) &&
+            step(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, d.v.esup, cells_sorted, node, pos, nnz, 0, end_bit, stream)))
+            (void)step(launch_transpose_index_fill(d.v, cells_sorted, nnz, ptr, pos, node, stream) ? hipErrorLaunchFailure : hipSuccess);
+        (void)step(hipStreamSynchronize(stream));
+    } else if (!rc) {
+        (void)step(launch_transpose_index_fill(d.v, nullptr, 0, ptr, pos, node, stream) ? hipErrorLaunchFailure : hipSuccess);
+        (void)step(hipStreamSynchronize(stream));
+    }
+    (void)hipFree(cells_sorted); (void)hipFree(tmp);
+    if (rc) { dev_release(d, ptr); dev_release(d, pos); dev_release(d, node); return rc; }
+    d.tr_cell_ptr = ptr; d.tr_cell_pos = pos; d.tr_cell_node = node;
+    return NIN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1161,25 +1202,23 @@ int nin_interpolate_csr_host(nin_grid *g, int method, int32_t *indptr, int32_t *
 }
 
 // Give the grid's call scratch back (the buffers nin_interpolate_csr_host / nin_csr_compact_host / nin_apply_* allocate
-// on first use and keep: ~2.3 GB of HBM at 10 M cells, + 10 MB of page-locked host memory); the next call allocates again.
+// on first use and keep: ~2.3 GB of HBM at 10 M cells, + 10 MB of page-locked host memory; the transpose index, 0.69 GB more);
+// the next call allocates again.
 int nin_grid_release_scratch(nin_grid *g) {
     if (!g) return fail(NIN_EINVAL, "NULL grid");
     DeviceGrid &d = g->d;
     if (d.device < 0) return NIN_OK;
     HIP_TRY(hipSetDevice(d.device));
     HIP_TRY(hipDeviceSynchronize());
-    void *scratch[] = {d.e2e_weights, d.e2e_nws, d.e2e_data, d.e2e_cnt, d.e2e_ptr, d.e2e_indices, d.e2e_tmp, d.apply_weights};
-    for (void *p : scratch) {
-        if (!p) continue;
-        auto it = std::find(d.allocs.begin(), d.allocs.end(), p);
-        if (it != d.allocs.end()) d.allocs.erase(it);
-        (void)hipFree(p);
-    }
+    void *scratch[] = {d.e2e_weights, d.e2e_nws, d.e2e_data, d.e2e_cnt, d.e2e_ptr, d.e2e_indices, d.e2e_tmp, d.apply_weights,
+                       d.tr_cell_ptr, d.tr_cell_pos, d.tr_cell_node};
+    for (void *p : scratch) dev_release(d, p);
     d.e2e_weights = d.e2e_nws = d.e2e_data = nullptr;
     d.e2e_cnt = d.e2e_ptr = d.e2e_indices = nullptr;
     d.e2e_tmp = nullptr;
     d.e2e_tmp_bytes = 0;
     d.apply_weights = nullptr;
+    d.tr_cell_ptr = d.tr_cell_pos = d.tr_cell_node = nullptr;
     if (d.flag_staging) { (void)hipHostFree(d.flag_staging); d.flag_staging = nullptr; }
     return NIN_OK;
 }
@@ -1247,6 +1286,69 @@ int nin_apply_fields_host(nin_grid *g, int method, const double *u_cells, int32_
 
 int nin_apply_host(nin_grid *g, int method, const double *u_cells, double *node_values, double *neumann_ws) {
     return nin_apply_fields_host(g, method, u_cells, 1, node_values, neumann_ws);
+}
+
+int nin_spmv_device(nin_grid *g, const double *dev_csr_data, const double *dev_u_cells, int32_t n_fields, double *dev_node_values,
+                    void *stream_) {
+    if (!g || !dev_csr_data || !dev_u_cells || !dev_node_values) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the kernels are HIP only");
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // the kernels nin_apply_device runs after its weights, on the caller's weights
+    const int rc = n_fields == 1 ? launch_apply(d.v, dev_csr_data, dev_u_cells, dev_node_values, (int32_t)g->h.mx_elems_per_point, d.nnz_e, stream)
+                                 : launch_apply_fields(d.v, dev_csr_data, dev_u_cells, n_fields, dev_node_values, (int32_t)g->h.mx_elems_per_point,
+                                                       d.nnz_e, stream);
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_spmv_transpose_device(nin_grid *g, const double *dev_csr_data, const double *dev_node_values, int32_t n_fields,
+                              double *dev_cell_values, void *stream_) {
+    if (!g || !dev_csr_data || !dev_node_values || !dev_cell_values) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the kernels are HIP only");
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = ensure_transpose_index(d, stream);
+    if (rc) return rc;
+    rc = launch_apply_transpose(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.tr_cell_node, d.v.dim == 2 ? 4 : 8, dev_csr_data, dev_node_values,
+                                n_fields, dev_cell_values, stream);
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_apply_transpose_fields_host(nin_grid *g, int method, const double *node_values, int32_t n_fields, double *cell_values) {
+    if (!g || !node_values || !cell_values) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the weight kernels are HIP only");
+    if (!d.fields_set) return fail(NIN_ESTATE, "nin_fields_set has not been called");
+    if (method != NIN_METHOD_GLS && method != NIN_METHOD_IDW && method != NIN_METHOD_LS) return fail(NIN_EINVAL, "unknown method %d", method);
+    if (method == NIN_METHOD_GLS && !d.have_perm) return fail(NIN_ESTATE, "GLS needs permeability and diff_mag");
+    HIP_TRY(hipSetDevice(d.device));
+    if (!d.apply_weights) {   // the weights of the last apply: one buffer per grid, allocated on first use
+        int rc = dev_alloc(d, &d.apply_weights, (size_t)std::max<int64_t>(d.nnz_e, 1));
+        if (rc) return rc;
+    }
+    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8;
+    double *dn = nullptr, *dv = nullptr, *dx = nullptr;
+    auto cleanup = [&]() { (void)hipFree(dn); (void)hipFree(dv); (void)hipFree(dx); };
+#define TRY_A(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(NIN_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
+    TRY_A(hipMalloc((void **)&dn, pb));
+    TRY_A(hipMalloc((void **)&dv, pb * n_fields));
+    TRY_A(hipMalloc((void **)&dx, eb * n_fields));
+    TRY_A(hipMemcpy(dv, node_values, pb * n_fields, hipMemcpyHostToDevice));
+    // the unfused weights (the fused cube-node apply writes no rows for cube nodes), with `+ neumann_ws[row]` as apply() uses them
+    int rc = nin_weights_device(g, method, nullptr, 0, 1, d.apply_weights, dn, nullptr);
+    if (!rc) rc = nin_spmv_transpose_device(g, d.apply_weights, dv, n_fields, dx, nullptr);
+    if (rc) { cleanup(); return rc; }
+    TRY_A(hipMemcpy(cell_values, dx, eb * n_fields, hipMemcpyDeviceToHost));
+#undef TRY_A
+    cleanup();
+    return NIN_OK;
 }
 
 int64_t nin_algorithmic_bytes(const nin_grid *g, int method) {

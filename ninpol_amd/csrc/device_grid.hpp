@@ -133,6 +133,10 @@ struct DeviceGrid {
     void *e2e_tmp = nullptr;
     size_t e2e_tmp_bytes = 0;
     double *apply_weights = nullptr;   // [nnz_e] weights of the last nin_apply_device (allocated on first use)
+    // the cell-major index of the esup pattern (the CSC of W's sparsity) for x = W^T v (nin_spmv_transpose_device): built on the
+    // device by the first transpose call, released with the scratch.  tr_cell_ptr [E+1]; tr_cell_pos [nnz_e] = the position in esup /
+    // csr_data of the pair (p, e); tr_cell_node [nnz_e] = p, ascending within a cell
+    int32_t *tr_cell_ptr = nullptr, *tr_cell_pos = nullptr, *tr_cell_node = nullptr;
     uint8_t *flag_staging = nullptr;   // page-locked [n_points]: nin_fields_set packs the node flags here and uploads from it
     void *copy_stream = nullptr, *copy_stream2 = nullptr;   // hipStream_t of the device-to-host copies that run under the kernels
     void *ev_weights = nullptr, *ev_scan = nullptr;   // hipEvent_t: weights written / row pointers scanned

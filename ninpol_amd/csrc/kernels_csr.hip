@@ -138,6 +138,103 @@ __global__ __launch_bounds__(256) void nin_apply_kernel(GridView g, const double
     }
 }
 
+// x[f][e] = sum_{p around e} W[p, e] * v[f][p]: the adjoint of nin_apply_kernel, through the cell-major index of the esup pattern
+// (DeviceGrid::tr_*: cell_ptr [E+1], cell_pos [nnz_e] = position of (p, e) in esup / data, cell_node [nnz_e] = p, ascending p within a
+// cell).  One lane per cell, the sum in ascending node id -- the order scipy's W.T @ v accumulates in -- with explicit fma, so that a
+// batch of fields and single calls agree bit for bit; no atomics.  The 64 cells of a wavefront own ONE contiguous run of cell_pos /
+// cell_node, copied HBM -> LDS cooperatively (whole lines) as nin_apply_kernel stages its rows; data[pos] and v[p] are gathered.
+// `cap`: the entries of LDS each wavefront owns (64 x the most nodes of a cell; a longer run is read straight from HBM).
+template <int NF>
+__global__ __launch_bounds__(256) void nin_apply_transpose_kernel(int32_t n_elems, int32_t n_points, const int32_t *__restrict__ cell_ptr,
+                                                                  const int32_t *__restrict__ cell_pos, const int32_t *__restrict__ cell_node,
+                                                                  const double *__restrict__ data, const double *__restrict__ v, int32_t k0,
+                                                                  int32_t k, double *__restrict__ x, int32_t cap) {
+    extern __shared__ int32_t tr_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t *const pl = tr_lds + (size_t)wave * 2 * cap;
+    int32_t *const nl = pl + cap;
+    const size_t E = (size_t)n_elems, P = (size_t)n_points;
+    const int32_t n_tiles = (n_elems + 63) / 64;
+    for (int32_t tile = blockIdx.x * 4 + wave; tile < n_tiles; tile += gridDim.x * 4) {
+        const int32_t e0 = tile * 64, e = e0 + lane, ee = e0 + 64 < n_elems ? e0 + 64 : n_elems;
+        const int32_t run_b = cell_ptr[e0], run_e = cell_ptr[ee], len = run_e - run_b;
+        const bool staged = len <= cap, live = e < n_elems;
+        if (staged) {
+            for (int32_t i = lane; i < len; i += 64) { pl[i] = cell_pos[run_b + i]; nl[i] = cell_node[run_b + i]; }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (live) {
+            const int32_t b = cell_ptr[e], end = cell_ptr[e + 1];
+            double acc[NF];
+#pragma unroll
+            for (int f = 0; f < NF; ++f) acc[f] = 0.0;
+            // eight entries at a time: their gathers of data and v are issued together, the sums stay in node order
+            int32_t q = b;
+            for (; q + 8 <= end; q += 8) {
+                double w8[8], v8[8][NF];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const size_t pos = (size_t)(staged ? pl[q + j - run_b] : cell_pos[q + j]);
+                    const size_t p = (size_t)(staged ? nl[q + j - run_b] : cell_node[q + j]);
+                    w8[j] = data[pos];
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) v8[j][f] = k0 + f < k ? v[(size_t)(k0 + f) * P + p] : 0.0;
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) acc[f] = __builtin_fma(w8[j], v8[j][f], acc[f]);
+                }
+            }
+            for (; q < end; ++q) {
+                const size_t pos = (size_t)(staged ? pl[q - run_b] : cell_pos[q]);
+                const size_t p = (size_t)(staged ? nl[q - run_b] : cell_node[q]);
+                const double w = data[pos];
+#pragma unroll
+                for (int f = 0; f < NF; ++f)
+                    if (k0 + f < k) acc[f] = __builtin_fma(w, v[(size_t)(k0 + f) * P + p], acc[f]);
+            }
+#pragma unroll
+            for (int f = 0; f < NF; ++f)
+                if (k0 + f < k) x[(size_t)(k0 + f) * E + e] = acc[f];
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// the cell-major index, after a stable sort of the pairs (esup[j], j) by cell: cell_ptr[e] = first i with sorted_cells[i] >= e
+__global__ __launch_bounds__(256) void nin_cell_ptr_kernel(const int32_t *__restrict__ sorted_cells, int32_t nnz, int32_t n_elems,
+                                                           int32_t *__restrict__ cell_ptr) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= n_elems; e += (int64_t)gridDim.x * blockDim.x) {
+        int32_t lo = 0, hi = nnz;
+        while (lo < hi) {
+            const int32_t mid = lo + ((hi - lo) >> 1);
+            if (sorted_cells[mid] < e) lo = mid + 1; else hi = mid;
+        }
+        cell_ptr[e] = lo;
+    }
+}
+
+// cell_node[i] = the row p of esup position cell_pos[i]: the last p with esup_ptr[p] <= cell_pos[i]
+__global__ __launch_bounds__(256) void nin_cell_node_kernel(const int32_t *__restrict__ esup_ptr, int32_t n_points,
+                                                            const int32_t *__restrict__ cell_pos, int32_t nnz, int32_t *__restrict__ cell_node) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t j = cell_pos[i];
+        int32_t lo = 0, hi = n_points;   // invariant: esup_ptr[lo] <= j and the answer lies in [lo, hi) (j < esup_ptr[n_points])
+        while (hi - lo > 1) {
+            const int32_t mid = lo + ((hi - lo) >> 1);
+            if (esup_ptr[mid] <= j) lo = mid; else hi = mid;
+        }
+        cell_node[i] = lo;
+    }
+}
+
+__global__ __launch_bounds__(256) void nin_iota_kernel(int32_t *__restrict__ dst, int32_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (int32_t)i;
+}
+
 // the listed nodes only: one lane per node, its row straight from HBM, every field in turn (sums in row order)
 __global__ __launch_bounds__(256) void nin_apply_list_kernel(GridView g, const double *__restrict__ data, const double *__restrict__ u,
                                                              int32_t k, double *__restrict__ values, const int32_t *__restrict__ list,
@@ -232,6 +329,45 @@ int launch_apply_fields(const GridView &g, const double *data, const double *u, 
         if (k - k0 >= 3) hipLaunchKernelGGL(nin_apply_kernel<4>, grid, dim3(256), lds, stream, g, data, u, k0, k, values, cap, tn);
         else if (k - k0 == 2) hipLaunchKernelGGL(nin_apply_kernel<2>, grid, dim3(256), lds, stream, g, data, u, k0, k, values, cap, tn);
         else hipLaunchKernelGGL(nin_apply_kernel<1>, grid, dim3(256), lds, stream, g, data, u, k0, k, values, cap, tn);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_iota(int32_t *dst, int32_t n, hipStream_t stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(nin_iota_kernel, dim3(grid_for(n)), dim3(256), 0, stream, dst, n);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_transpose_index_fill(const GridView &g, const int32_t *sorted_cells, int32_t nnz, int32_t *cell_ptr, const int32_t *cell_pos,
+                                int32_t *cell_node, hipStream_t stream) {
+    hipLaunchKernelGGL(nin_cell_ptr_kernel, dim3(grid_for((int64_t)g.n_elems + 1)), dim3(256), 0, stream, sorted_cells, nnz, g.n_elems, cell_ptr);
+    if (nnz > 0)
+        hipLaunchKernelGGL(nin_cell_node_kernel, dim3(grid_for(nnz)), dim3(256), 0, stream, g.esup_ptr, g.n_points, cell_pos, nnz, cell_node);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// k fields: four per pass over the index (the runs of a wavefront are staged once per pass), as launch_apply_fields
+int launch_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, int32_t mx_cell,
+                           const double *data, const double *v, int32_t k, double *x, hipStream_t stream) {
+    if (g.n_elems <= 0 || k <= 0) return 0;
+    const int32_t cap = 64 * (mx_cell > 0 ? mx_cell : 1);
+    const size_t lds = (size_t)cap * 4 * 2 * sizeof(int32_t);
+    const int64_t blocks = ((int64_t)(g.n_elems + 63) / 64 + 3) / 4;
+    const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks > 256 * 32 ? 256 * 32 : blocks));
+    if (allow_dynamic_lds<nin_apply_transpose_kernel<1>>(lds) || allow_dynamic_lds<nin_apply_transpose_kernel<2>>(lds) ||
+        allow_dynamic_lds<nin_apply_transpose_kernel<4>>(lds))
+        return -3;
+    for (int32_t k0 = 0; k0 < k; k0 += 4) {
+        if (k - k0 >= 3)
+            hipLaunchKernelGGL(nin_apply_transpose_kernel<4>, grid, dim3(256), lds, stream, g.n_elems, g.n_points, cell_ptr, cell_pos, cell_node,
+                               data, v, k0, k, x, cap);
+        else if (k - k0 == 2)
+            hipLaunchKernelGGL(nin_apply_transpose_kernel<2>, grid, dim3(256), lds, stream, g.n_elems, g.n_points, cell_ptr, cell_pos, cell_node,
+                               data, v, k0, k, x, cap);
+        else
+            hipLaunchKernelGGL(nin_apply_transpose_kernel<1>, grid, dim3(256), lds, stream, g.n_elems, g.n_points, cell_ptr, cell_pos, cell_node,
+                               data, v, k0, k, x, cap);
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

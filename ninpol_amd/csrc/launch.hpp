@@ -101,6 +101,16 @@ int launch_apply_list(const GridView &g, const double *data, const double *u, in
 int launch_apply_fields(const GridView &g, const double *data, const double *u, int32_t k, double *values, int32_t mx_row, int64_t nnz,
                         hipStream_t stream);
 
+// the adjoint, x = W^T v: the cell-major index of the esup pattern (DeviceGrid::tr_*) and k node fields v [k][n_points] ->
+// x [k][n_elems]; mx_cell = the most nodes of any cell (8 in 3-D, 4 in 2-D)
+int launch_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, int32_t mx_cell,
+                           const double *data, const double *v, int32_t k, double *x, hipStream_t stream);
+// building that index (abi.hip sorts the pairs (esup[j], j) by cell in between): dst[i] = i; then cell_ptr from the sorted cells and
+// cell_node from the sorted positions
+int launch_iota(int32_t *dst, int32_t n, hipStream_t stream);
+int launch_transpose_index_fill(const GridView &g, const int32_t *sorted_cells, int32_t nnz, int32_t *cell_ptr, const int32_t *cell_pos,
+                                int32_t *cell_node, hipStream_t stream);
+
 // GLS launch plan (grid_device.hip): size class of every node (255 = the hex8 kernel, 254 / 253 / 252 = the one-wavefront multifrontal kernel: two-coloured nodes large / small, general kind) and, per class, the
 // maxima of (bytes, rows, columns) as 3 * kGlsClasses unsigned 64-bit values; all DEVICE pointers
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)

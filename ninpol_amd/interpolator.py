@@ -490,9 +490,34 @@ class Interpolator:
         _lib.check(_lib.load().nin_apply_fields_host(g._h, _lib.METHOD_ID[method], _ptr(u), k, _ptr(out), _ptr(nws)))
         return out, nws
 
+    def apply_transpose(self, variable, method, values):
+        """The adjoint of `apply()`: node fields back to the cells, `W.T @ v` with the W that `apply()` uses and `interpolate()`
+        returns (the `+ neumann_ws[row]` of interpolator.pyx:618 included), on the device.  `values`: one node array (n_points,)
+        or k of them as (k, n_points); returns cell values shaped like `values` with n_elems in place of n_points.  Each cell
+        sums its nodes' terms in ascending node id (scipy's order), without atomics: results are bitwise reproducible."""
+        if not self.is_grid_initialized:
+            raise ValueError("Grid not initialized. Please load a mesh first.")
+        if method not in self.supported_methods:
+            raise ValueError(f"Method '{method}' not supported. Supported methods are: "
+                             f"{list(self.supported_methods.keys())}")
+        if variable not in self.variable_to_index["cells"]:
+            raise ValueError(f"Variable '{variable}' not found in cells data. "
+                             "Point -> Cell interpolation not supported yet.")
+        g = self.grid
+        v = np.ascontiguousarray(values, dtype=DTYPE_F)
+        if v.shape != (g.n_points,) and not (v.ndim == 2 and v.shape[0] >= 1 and v.shape[1] == g.n_points):
+            raise ValueError(f"values must have shape ({g.n_points},) or (k, {g.n_points}), not {v.shape}.")
+        if g.device < 0:
+            g.to_device(self.device)
+        _upload_fields(g, method, self.cells_data, self.points_data, self.variable_to_index, variable)
+        k = 1 if v.ndim == 1 else v.shape[0]
+        out = np.empty(g.n_elems if v.ndim == 1 else (k, g.n_elems), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_apply_transpose_fields_host(g._h, _lib.METHOD_ID[method], _ptr(v), k, _ptr(out)))
+        return out
+
     def release_scratch(self, pinned=True):
         """Give back what the object keeps between calls for speed: the grid's device scratch (weights, compacted
-        triplets: ~2.3 GB of HBM at 10 M cells) and, with pinned=True, the idle page-locked result buffers of the
+        triplets: ~2.3 GB of HBM at 10 M cells; the transpose index of apply_transpose(): 0.69 GB more) and, with pinned=True, the idle page-locked result buffers of the
         process-wide pool.  Results already returned stay valid."""
         if self.grid is not None:
             self.grid.release_scratch()
@@ -576,3 +601,15 @@ class DevicePlan:
         _lib.check(_lib.load().nin_apply_device(self.grid._h, self.method_id, ctypes.c_void_p(u_cells_ptr), int(n_fields),
                                                 ctypes.c_void_p(node_values_ptr), ctypes.c_void_p(neumann_ws_ptr),
                                                 ctypes.c_void_p(stream)))
+
+    def launch_spmv(self, weights_ptr, u_ptr, n_fields, values_ptr, stream=0):
+        """W . u on weights the caller holds (nin_spmv_device): weights [nnz_esup] as `launch(..., add_neumann=True)` writes
+        them, u [n_fields][n_elems] -> values [n_fields][n_points]; no weight kernel runs; asynchronous on `stream`."""
+        _lib.check(_lib.load().nin_spmv_device(self.grid._h, ctypes.c_void_p(weights_ptr), ctypes.c_void_p(u_ptr), int(n_fields),
+                                               ctypes.c_void_p(values_ptr), ctypes.c_void_p(stream)))
+
+    def launch_spmv_transpose(self, weights_ptr, values_ptr, n_fields, cells_ptr, stream=0):
+        """W^T . v on the same weights (nin_spmv_transpose_device): values [n_fields][n_points] -> cells [n_fields][n_elems];
+        asynchronous on `stream` (the first call on a grid builds the transpose index and synchronises)."""
+        _lib.check(_lib.load().nin_spmv_transpose_device(self.grid._h, ctypes.c_void_p(weights_ptr), ctypes.c_void_p(values_ptr),
+                                                         int(n_fields), ctypes.c_void_p(cells_ptr), ctypes.c_void_p(stream)))
