@@ -90,9 +90,12 @@ struct BackLoop<-1> {
 //     [slot][lane], no conflicts, no synchronisation -- until the panel and the face records are gone;
 //   * phase 2 forms each column's dot where it is used (the other wave fills the scalar chain's latency), with u and s in the
 //     LDS slots the fill entries have left;
-//   * the index levels of the next pass (list entry -> CSR row starts, coordinates -> cell / face ids) come in by LDS-DMA
-//     during this one (nothing in flight that the compiler could move or spill); geometry and permeability by plain loads at
-//     the top of the pass; a per-XCD work queue (the SIMD issues its older wave first: equal shares finish 4.0 / 5.85 ms apart).
+//   * the index levels of the next pass (list entry -> CSR row starts -> coordinates, cell / face ids) come in by LDS-DMA
+//     during this one (nothing in flight that the compiler could move or spill), one level at the top of the pass, after the
+//     face rows and at tile completion; its geometry and permeability by plain loads into registers ahead of phase-2 step 6,
+//     in flight until the top of the next pass (round 5: at the top of the pass itself, the wave waited ~3.3 k of its 23 - 24 k
+//     cycles for them).  A lane loads its own two cells only: the cell across face i is O_s of lane s of the quad, its K by
+//     DPP.  A per-XCD work queue (the SIMD issues its older wave first: equal shares finish 4.0 / 5.85 ms apart).
 // With two waves the SIMD is bound by instruction issue (FP64 at ~2.6 ns an instruction, everything else at ~1): every change
 // since the first version that fitted was a cut in instructions -- 4 159 -> 4 096 a pass, of them FP64 2 926 -> 2 426; executed
 // flops per node 20.5 k (kernel above) -> 16.7 k against 15.9 k algorithmic.  5.95 -> 4.8 .. 5.0 ms per launch at 216^3.
@@ -184,7 +187,12 @@ __device__ __forceinline__ void w2_column(const double (&P)[10][3], const double
 __device__ __forceinline__ void w2_dma(const void *gptr, uint32_t *row) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gptr, (__attribute__((address_space(3))) void *)row, 4, 0, 0);
 }
-__device__ __forceinline__ void w2_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// (a scheduling fence on both sides: the scheduler would otherwise move the arithmetic that is to cover the DMA behind the wait)
+__device__ __forceinline__ void w2_dma_wait() {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
 // level 0 of group `wg`: list entry and descriptor word (past the end: a clamped, valid entry -- never stored)
 __device__ __forceinline__ void w2_stage_a(const int32_t *nodes, const int32_t *desc, int32_t wg, int32_t count, int nd, int l,
                                            uint32_t *row_p, uint32_t *row_dsc) {
@@ -193,25 +201,61 @@ __device__ __forceinline__ void w2_stage_a(const int32_t *nodes, const int32_t *
     w2_dma(nodes + sel, row_p);
     w2_dma(desc + 4 * (size_t)sel + l, row_dsc);
 }
-// level 1: CSR row starts and the node's coordinates (as six dwords)
-__device__ __forceinline__ void w2_stage_b(const GridView &g, uint32_t p, uint32_t *rows_n) {
-    w2_dma(g.esup_ptr + p, rows_n);
-    w2_dma(g.fsup_ptr + p, rows_n + 64);
+// level 1: CSR row starts
+__device__ __forceinline__ void w2_stage_b(const GridView &g, uint32_t p, uint32_t *rows_b) {
+    w2_dma(g.esup_ptr + p, rows_b);
+    w2_dma(g.fsup_ptr + p, rows_b + 64);
+}
+// level 2: the node's coordinates (as six dwords, rows 2 .. 7), the lane's two cells (8, 9) and its three faces (10 .. 12)
+__device__ __forceinline__ void w2_stage_c(const GridView &g, uint32_t p, uint32_t eb, uint32_t fb, uint32_t dsc, uint32_t *rows_n) {
     const uint32_t *xw = reinterpret_cast<const uint32_t *>(g.coords) + 6 * (size_t)p;
 #pragma unroll
     for (int k = 0; k < 6; ++k) w2_dma(xw + k, rows_n + 64 * (2 + k));
-}
-// level 2: the lane's two cells, the cells across its three faces, the faces
-__device__ __forceinline__ void w2_stage_c(const GridView &g, uint32_t eb, uint32_t fb, uint32_t dsc, uint32_t *rows_n) {
     w2_dma(g.esup + eb + (dsc & 7), rows_n + 64 * 8);
     w2_dma(g.esup + eb + ((dsc >> 3) & 7), rows_n + 64 * 9);
 #pragma unroll
+    for (int i = 0; i < 3; ++i) w2_dma(g.fsup + fb + ((dsc >> (6 + 8 * i)) & 15), rows_n + 64 * (10 + i));
+}
+// level 3, in registers: geometry and permeability of the lane's own two cells and its three faces.  The cell across face i
+// of lane l is O_s, s = i (i < 3 - l) or i + 1 (hex8_desc.hpp) -- the cell lane s owns -- so its K and diff_mag come from lane
+// s by a quad permutation where they are used (w2_across), not from memory.
+struct W2Geo {
+    double Ke[9], dme, ce[3];      // E_l
+    double Ko[9], dmo, co[3];      // O_l
+    double fc[3][3];               // face centres
+    float fn[3][3];                // face normals
+    uint32_t flags;                // the node's
+};
+__device__ __forceinline__ void w2_stage_d(const GridView &g, const uint32_t *row_p, const uint32_t *rows_n, int lane, W2Geo &q) {
+    q.flags = g.flags[row_p[lane]];
+    const uint32_t ce = rows_n[64 * 8 + lane], co = rows_n[64 * 9 + lane];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { q.Ke[k] = g.perm[9 * (size_t)ce + k]; q.Ko[k] = g.perm[9 * (size_t)co + k]; }
+    q.dme = g.diff_mag[ce];
+    q.dmo = g.diff_mag[co];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) { q.ce[t] = g.centroids[3 * (size_t)ce + t]; q.co[t] = g.centroids[3 * (size_t)co + t]; }
+#pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const uint32_t w = dsc >> (6 + 8 * i);
-        w2_dma(g.esup + eb + ((w >> 4) & 7), rows_n + 64 * (10 + i));
-        w2_dma(g.fsup + fb + (w & 15), rows_n + 64 * (13 + i));
+        const uint32_t f = rows_n[64 * (10 + i) + lane];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) { q.fn[i][t] = g.face_normal[3 * (size_t)f + t]; q.fc[i][t] = g.face_center[3 * (size_t)f + t]; }
     }
 }
+// lane s(i, l) of the quad for face i: [0,0,0,1], [1,1,2,2], [2,3,3,3]
+template <int I>
+__device__ __forceinline__ double w2_across(double v) { return dpp_mov<I == 0 ? 0x40 : I == 1 ? 0xA5 : 0xFE>(v); }
+
+// Where the levels of the NEXT pass are requested (each waits for the one before with w2_dma_wait()): level 0 at the top of
+// the pass, 1 after the face rows (W2_B_LATE: after phase 1), 2 ahead of phase-2 step W2_C_STEP (0: at tile completion),
+// 3 ahead of step W2_D_STEP; level 3 is in flight from there to the top of the next pass.
+#ifndef W2_C_STEP
+#define W2_C_STEP 0
+#endif
+#ifndef W2_D_STEP
+#define W2_D_STEP 6
+#endif
+static_assert(W2_C_STEP >= 0 && W2_C_STEP < W2_D_STEP && W2_D_STEP <= 12, "level 2 before level 3, both in phase 2");
 
 #ifdef NIN_W2_TRACE
 __device__ unsigned long long nin_w2_trace[4096 * 4];   // per wave: start, end (s_memrealtime, 100 MHz), HW_ID, passes
@@ -230,13 +274,15 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
     const int l = lane & 3, nd = lane >> 2;
     double *const L = lds_all[wave] + lane;                   // slot k of this lane: L[64 k]
     double *const wbuf = lds_all[wave] + W2_SLOTS * 64;
-    // The index levels of the NEXT pass (list entry -> CSR row starts, coordinates -> cell / face ids) come in by LDS-DMA
+    // The index levels of the NEXT pass (list entry -> CSR row starts -> coordinates, cell / face ids) come in by LDS-DMA
     // (global_load_lds_dword: lane i's word lands at row[i]; no register is in flight, nothing the compiler could move or
-    // spill): rows of 64 dwords.  (p, dsc) have rows of their own; the others lie in parking slots 13 .. 20, which are free
-    // from the moment the tile is complete until the next pass parks again -- after it has read them.
+    // spill): rows of 64 dwords.  (p, dsc) have rows of their own; the CSR row starts land in the weights' staging, which is
+    // free until the weights; coordinates and ids in parking slots 13 .. 19, which are free from the moment the tile is
+    // complete until the next pass parks again -- after it has read them.
     uint32_t *const row_p = reinterpret_cast<uint32_t *>(lds_all[wave] + W2_SLOTS * 64 + NPW * 8);
     uint32_t *const row_dsc = row_p + 64;
-    uint32_t *const rows_n = reinterpret_cast<uint32_t *>(lds_all[wave] + 13 * 64);   // 0: eb, 1: fb, 2 .. 7: x_v, 8 .. 15: ids
+    uint32_t *const rows_b = reinterpret_cast<uint32_t *>(wbuf);                         // 0: eb, 1: fb
+    uint32_t *const rows_n = reinterpret_cast<uint32_t *>(lds_all[wave] + 13 * 64);   // 0: eb (copied), 2 .. 7: x_v, 8 .. 12: ids
 
     const int32_t n_groups = (count + NPW - 1) / NPW;
     // XCD x walks the x-th contiguous eighth of the node list; its waves pull consecutive 16-node groups off a per-XCD counter.
@@ -259,12 +305,19 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
     int32_t wg = wg_lo + __builtin_amdgcn_readfirstlane(ticket);
     if (lane == 0) ticket = atomicAdd(q, 1);
     int32_t wg_next = wg_lo + __builtin_amdgcn_readfirstlane(ticket);
-    // the first group's index levels, one after the other
+    // the first group's index levels and geometry, one after the other
+    W2Geo geo;
     w2_stage_a(nodes, desc, wg, count, nd, l, row_p, row_dsc);
     w2_dma_wait();
-    w2_stage_b(g, row_p[lane], rows_n);
+    w2_stage_b(g, row_p[lane], rows_b);
     w2_dma_wait();
-    w2_stage_c(g, rows_n[lane], rows_n[64 + lane], row_dsc[lane], rows_n);
+    {
+        const uint32_t eb0 = rows_b[lane];
+        rows_n[lane] = eb0;
+        w2_stage_c(g, row_p[lane], eb0, rows_b[64 + lane], row_dsc[lane], rows_n);
+    }
+    w2_dma_wait();
+    w2_stage_d(g, row_p, rows_n, lane, geo);
 #ifdef NIN_MF_STAMPS     // diagnostic build (tools/stamps_hex8mf.py): s_memtime at the phase boundaries of one pass
 #ifndef NIN_MF_STAMP_PASS
 #define NIN_MF_STAMP_PASS 8
@@ -280,7 +333,6 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
     unsigned trace_passes = 0;
 #endif
     while (wg < wg_end) {
-        if (lane == 0) ticket = atomicAdd(q, 1);              // names the group of the pass after the next
 #ifdef NIN_W2_TRACE
         ++trace_passes;
 #endif
@@ -289,52 +341,58 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
 #endif
         NIN_MF_STAMP();                                   // 0: top of the pass
         const bool valid = wg * NPW + nd < count;
-        w2_dma_wait();                                        // (the ids of this pass: requested in the middle of the last one)
-        const uint32_t p = row_p[lane], dsc = row_dsc[lane];
-        const uint32_t eb = rows_n[lane], fb = rows_n[64 + lane];
-        const bool is_neu = (g.flags[p] & 2) != 0;
+        // The geometry, requested in the middle of the last pass, is used at once.  Its wait comes FIRST, as a builtin the
+        // compiler sees: behind the loads issued below, the compiler's own wait for it would be a vmcnt(0) that also waits
+        // for them (the last pass's stores are in the count anyway).
+        __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0)
+#ifdef NIN_MF_STAMP_SPLIT   // (diagnostic build: stamp 1 = the geometry has landed; the back-substitution is not stamped)
+        NIN_MF_STAMP();
+#define NIN_MF_STAMP_BACK() do { } while (0)
+#else
+#define NIN_MF_STAMP_BACK() NIN_MF_STAMP()
+#endif
+        // (all of it landed during the last pass: p, dsc at its level-1 wait, x_v at its level-3 wait; eb was copied there)
+        const uint32_t p = row_p[lane], dsc = row_dsc[lane], eb = rows_n[lane];
         double xv[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) xv[k] = __hiloint2double((int)rows_n[64 * (3 + 2 * k) + lane], (int)rows_n[64 * (2 + 2 * k) + lane]);
-        uint32_t id[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) id[k] = rows_n[64 * (8 + k) + lane];
-        const uint32_t ce = id[0], co = id[1];
+        const bool is_neu = (geo.flags & 2) != 0;
+        __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0): read before level 0 of the next pass overwrites them
+        w2_stage_a(nodes, desc, wg_next, count, nd, l, row_p, row_dsc);   // next pass: list entry and descriptor
+        __builtin_amdgcn_sched_barrier(0);
 
         // ---- the front of E_l: rows 0 = cell row, 1 + 3 i + r = row r of face i; own columns in P ------------
         double P[10][3], de[3], dod[3], nb0[3][3], sav[3][2][3];
         {
-            double Ke[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) Ke[k] = g.perm[9 * (size_t)ce + k];
-            const double dme = g.diff_mag[ce];
+            const double dme = geo.dme;
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                de[t] = g.centroids[3 * (size_t)ce + t] - xv[t];      // gls.pyx:269-277
-                dod[t] = g.centroids[3 * (size_t)co + t] - xv[t];
+                de[t] = geo.ce[t] - xv[t];                    // gls.pyx:269-277
+                dod[t] = geo.co[t] - xv[t];
                 P[0][t] = de[t];
             }
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const uint32_t w = dsc >> (6 + 8 * i);
-                const uint32_t cn = id[2 + i], f = id[5 + i];
                 // B = [K N; T1; tau T2] (gls.pyx:293-321), row = [-B_a | +B_b] (gls.pyx:340-356)
-                const double N0 = (double)g.face_normal[3 * (size_t)f + 0], N1 = (double)g.face_normal[3 * (size_t)f + 1],
-                             N2 = (double)g.face_normal[3 * (size_t)f + 2];
-                const double T0 = xv[0] - g.face_center[3 * (size_t)f + 0], T1 = xv[1] - g.face_center[3 * (size_t)f + 1],
-                             T2 = xv[2] - g.face_center[3 * (size_t)f + 2];
+                const double N0 = (double)geo.fn[i][0], N1 = (double)geo.fn[i][1], N2 = (double)geo.fn[i][2];
+                const double T0 = xv[0] - geo.fc[i][0], T1 = xv[1] - geo.fc[i][1], T2 = xv[2] - geo.fc[i][2];
                 const double U0 = N1 * T2 - N2 * T1, U1 = N2 * T0 - N0 * T2, U2 = N0 * T1 - N1 * T0;
-                const double dmn = g.diff_mag[cn];
+                // the cell across the face: O_s of lane s(i, l)
+                auto across = [&](double v) { return i == 0 ? w2_across<0>(v) : i == 1 ? w2_across<1>(v) : w2_across<2>(v); };
+                const double dmn = across(geo.dmo);
                 double eta = 0.0;
                 eta = dme > eta ? dme : eta;
                 eta = dmn > eta ? dmn : eta;
                 const double tj = face_tau_sq(U0 * U0 + U1 * U1 + U2 * U2, eta);   // |T_sj2|^(-eta) without the square root
                 const bool side_a = ((w >> 7) & 1) != 0;
                 const double sg = side_a ? -1.0 : 1.0;
-                const double *Kn = g.perm + 9 * (size_t)cn;
+                double Kn[9];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) Kn[k] = across(geo.Ko[k]);
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
-                    P[1 + 3 * i][t] = sg * (Ke[t * 3 + 0] * N0 + Ke[t * 3 + 1] * N1 + Ke[t * 3 + 2] * N2);
+                    P[1 + 3 * i][t] = sg * (geo.Ke[t * 3 + 0] * N0 + geo.Ke[t * 3 + 1] * N1 + geo.Ke[t * 3 + 2] * N2);
                     nb0[i][t] = -sg * (Kn[t * 3 + 0] * N0 + Kn[t * 3 + 1] * N1 + Kn[t * 3 + 2] * N2);
                 }
                 sav[i][0][0] = sg * T0; sav[i][0][1] = sg * T1; sav[i][0][2] = sg * T2;
@@ -343,8 +401,20 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
                 for (int t = 0; t < 3; ++t) { P[2 + 3 * i][t] = sav[i][0][t]; P[3 + 3 * i][t] = sav[i][1][t]; }
             }
         }
-        NIN_MF_STAMP();                                   // 1: geometry in, face rows done
-        w2_stage_a(nodes, desc, wg_next, count, nd, l, row_p, row_dsc);   // next pass: list entry and descriptor
+        // (pinned: the face rows are what covers level 0; left alone the compiler sinks them behind the wait below)
+#pragma unroll
+        for (int r = 0; r < 10; ++r) { pin(P[r][0]); pin(P[r][1]); pin(P[r][2]); }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { pin(nb0[i][0]); pin(nb0[i][1]); pin(nb0[i][2]); }
+        NIN_MF_STAMP();                                   // 1: face rows done
+#ifndef W2_B_LATE
+        w2_dma_wait();
+        w2_stage_b(g, row_p[lane], rows_b);               // next pass: CSR row starts
+#endif
+        // the ticket that names the group of the pass after the next (read at the end of the pass); drawn here, behind a wait,
+        // so that no wait of the first part of the pass covers its round trip
+        if (lane == 0) ticket = atomicAdd(q, 1);
+        __builtin_amdgcn_sched_barrier(0);
         double C[NR][NC];
         double u[9], se, F1[7][2], F2[7][3];                  // u = z^T R_eo by face; fill entries of faces 1 and 2 (face 0: LDS)
         {
@@ -412,6 +482,10 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
             __builtin_amdgcn_sched_barrier(0);
         }
         NIN_MF_STAMP();                                   // 2: phase 1 done
+#ifdef W2_B_LATE
+        w2_dma_wait();
+        w2_stage_b(g, row_p[lane], rows_b);               // next pass: CSR row starts
+#endif
         // ---- the tile: odd slot 0 = F0 (lanes 0 .. 2); slot 1 = F1 (lanes 0, 1) or F0 (lane 3); slot 2 = F2 (lane 0) or F1
         //      (lanes 2, 3); slot 3 = F2 (lanes 1 .. 3); the slot a lane has no face on is zero.  The entries that waited in LDS
         //      come back; u and s take their place ------------------------------------------------------------------------------
@@ -448,20 +522,32 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
         // ---- phase 2: 32 x 12 over the quad ------------------------------------------------------------------
         double rinvq[3] = {0.0, 0.0, 0.0};
         NIN_MF_STAMP();                                   // 3: tile complete
-        w2_dma_wait();
-        w2_stage_b(g, row_p[lane], rows_n);               // next pass: CSR row starts, node coordinates
         __builtin_amdgcn_sched_barrier(0);
-        P2LeanLoop<0, 6>::run(C, rinvq, l);
-        NIN_MF_STAMP();                                   // 4: phase 2, steps 0-5
+        P2LeanLoop<0, W2_C_STEP>::run(C, rinvq, l);
         __builtin_amdgcn_sched_barrier(0);
         w2_dma_wait();
-        w2_stage_c(g, rows_n[lane], rows_n[64 + lane], row_dsc[lane], rows_n);   // next pass: cell and face ids
+        {   // next pass: coordinates, cell and face ids (the tile has left parking slots 13 .. 19); eb is kept for it in row 0
+            const uint32_t ebn = rows_b[lane];
+            rows_n[lane] = ebn;
+            w2_stage_c(g, row_p[lane], ebn, rows_b[64 + lane], row_dsc[lane], rows_n);
+        }
         __builtin_amdgcn_sched_barrier(0);
-        P2LeanLoop<6, 12>::run(C, rinvq, l);
+        P2LeanLoop<W2_C_STEP, W2_D_STEP>::run(C, rinvq, l);
+        NIN_MF_STAMP();                                   // 4: phase 2, steps 0 .. W2_D_STEP - 1
+        __builtin_amdgcn_sched_barrier(0);
+        w2_dma_wait();
+        // (the ticket is read here, where the wait has drained it: read at the end of the pass, its wait would be a vmcnt(0)
+        //  that drains the geometry below as well)
+        int32_t wg_after = wg_lo + __builtin_amdgcn_readfirstlane(ticket);
+        asm volatile("" : "+s"(wg_after));
+        __builtin_amdgcn_sched_barrier(0);
+        w2_stage_d(g, row_p, rows_n, lane, geo);          // next pass: geometry, in flight until its top
+        __builtin_amdgcn_sched_barrier(0);
+        P2LeanLoop<W2_D_STEP, 12>::run(C, rinvq, l);
         NIN_MF_STAMP();                                   // 5: phase 2 done
         double y[12], t3[3] = {C[0][12], C[1][12], C[2][12]};
         BackLoop<11>::run(C, rinvq, t3, y, l);
-        NIN_MF_STAMP();                                   // 6: back-substitution done
+        NIN_MF_STAMP_BACK();                              // 6: back-substitution done
         double tail = 0.0;
 #pragma unroll
         for (int r = 3; r < NR; ++r) tail = fma(C[r][12], C[r][12], tail);
@@ -513,7 +599,7 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
             for (int i = 0; i < 8; ++i) nws[nodes[i]] = (double)(stamps[i] - stamps[0]);   // (diagnostic build: clobbers neumann_ws of the first 8 listed nodes)
 #endif
         wg = wg_next;
-        wg_next = wg_lo + __builtin_amdgcn_readfirstlane(ticket);
+        wg_next = wg_after;
     }
     w2_dma_wait();   // nothing may still be on its way into this workgroup's LDS when the wave ends
 #ifdef NIN_W2_TRACE
