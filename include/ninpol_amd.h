@@ -96,6 +96,35 @@ int nin_device_count(int *count);
 int nin_grid_to_device(nin_grid *g, int device);
 int nin_grid_device(const nin_grid *g); /* device id or -1 */
 
+/* ---- moving meshes ---------------------------------------------------------------------------
+ * New node coordinates for a loaded grid whose connectivity stays: point_coords, centroids, faces_centers, normal_faces and
+ * faces_areas are made again (the reference's load_point_coords() + calculate_centroids() + calculate_normal_faces(),
+ * grid.pyx:661-809), bit for bit what a fresh nin_grid_create* of the moved mesh holds.  Nothing else changes: connectivity
+ * arrays, scalars, boundary flags, the resident permeability and Neumann flags, the GLS launch plan and the transpose index stay
+ * (the plan's node lists keep the locality order of the coordinates they were planned with: that order affects speed only, never a
+ * weight).  Weights computed before the update (a caller's csr_data buffers) are those of the old geometry.
+ *
+ * nin_grid_update_points: xyz is a HOST array [n_points][coords_dim]; synchronous.  On a grid that holds device arrays (built on a
+ * device, or after nin_grid_to_device) the coordinates are uploaded and the kernels of csrc/grid_update.hip run; on a host-only
+ * grid the host builder's geometry code runs again.  Both give the same bits.
+ * nin_grid_update_points_device: dev_xyz is a DEVICE array of the same shape on the grid's device, not overlapping any grid array;
+ * asynchronous on `stream` (hipStream_t): later launches on that stream -- the GLS side stream forks from it -- see the new
+ * geometry; work on other streams, and the host-synchronous entry points (nin_weights_host, nin_interpolate_csr_host,
+ * nin_apply_*_host: they run on the null stream), must be ordered behind `stream` by the caller.  NIN_ENODEVICE when
+ * nin_grid_device(g) is -1.
+ * Both: NIN_EINVAL for a NULL argument or a coords_dim other than the grid's.  The first update of a grid on a device puts inpoel,
+ * element_types, inpofa and a face-area array there (0.32 + 0.01 + 0.48 + 0.24 GB of HBM at 10 M hexahedra; a grid built on the device
+ * already has them) and is synchronous; they go with nin_grid_release_scratch and come back at the next update.  The host mirror
+ * does not go stale: nin_grid_array_copy of the five arrays after an update waits for it and fetches the new values on first use
+ * (nothing is copied back by the update itself). */
+int nin_grid_update_points(nin_grid *g, const double *xyz, int coords_dim);
+int nin_grid_update_points_device(nin_grid *g, const double *dev_xyz, int coords_dim, void *stream);
+/* Geometry updates the grid's device copy has seen since it was made (0 without one): a cheap way to tell that an update went
+ * through the device path. */
+int64_t nin_grid_geometry_updates(const nin_grid *g);
+/* 1 if the transpose index of nin_spmv_transpose_device is resident, else 0 (it survives an update of the points). */
+int nin_grid_has_transpose_index(const nin_grid *g);
+
 /* Per-call fields the plugins read from the data tables (idw.pyx:27-28, ls.pyx:27-28,
  * gls.pyx:47-59): permeability[E][3][3] row-major and diff_mag[E] (may be NULL for IDW / LS),
  * neumann_flag[P] (the points_data row, cast to integer like `.astype(int)`), neumann_val[P]
@@ -203,7 +232,7 @@ int nin_host_free(void *ptr);
 
 /* Give back the scratch a grid keeps between calls: the device buffers nin_interpolate_csr_host / nin_csr_compact_host /
  * nin_apply_* allocate on first use (weights, compacted triplets, counters: ~2.3 GB of HBM at 10 M cells, 8 x that at
- * 80 M), the transpose index of nin_spmv_transpose_device (~0.69 GB at 10 M hexahedra) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
+ * 80 M), the transpose index of nin_spmv_transpose_device (~0.69 GB at 10 M hexahedra), the connectivity copies of nin_grid_update_points* (~1.05 GB at 10 M hexahedra; kept while a grid built on the device still mirrors from them) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
  * weight table when interpolate() returns, interpolator.pyx:650-651.) */
 int nin_grid_release_scratch(nin_grid *g);
 

@@ -92,6 +92,7 @@ void dev_free_all(DeviceGrid &d) {
     if (d.flag_staging) (void)hipHostFree(d.flag_staging);
     if (d.ev_weights) (void)hipEventDestroy(static_cast<hipEvent_t>(d.ev_weights));
     if (d.ev_scan) (void)hipEventDestroy(static_cast<hipEvent_t>(d.ev_scan));
+    if (d.ev_geom) (void)hipEventDestroy(static_cast<hipEvent_t>(d.ev_geom));
     if (d.copy_stream) (void)hipStreamDestroy(static_cast<hipStream_t>(d.copy_stream));
     if (d.copy_stream2) (void)hipStreamDestroy(static_cast<hipStream_t>(d.copy_stream2));
     if (d.ev_fork) (void)hipEventDestroy(static_cast<hipEvent_t>(d.ev_fork));
@@ -132,6 +133,9 @@ unsigned array_bits(const std::string &name) {
 
 bool lookup_array(nin_grid *g, const std::string &name, ArrayRef *r) {
     HostGrid &h = g->h;
+    if ((array_bits(name) & A_GEOMETRY & ~h.have) && g->d.ev_geom) {   // geometry updated on the device: wait for the last update first
+        if (hipSetDevice(g->d.device) != hipSuccess || hipEventSynchronize(static_cast<hipEvent_t>(g->d.ev_geom)) != hipSuccess) return false;
+    }
     if (h.ensure(array_bits(name))) return false;   // a grid built on the device: bring the array over first
     auto I32 = [&](const std::vector<int32_t> &v) { *r = {NIN_I64, (int64_t)v.size(), 0, v.data()}; return true; };
     auto I64 = [&](const std::vector<int64_t> &v) { *r = {NIN_I64, (int64_t)v.size(), 1, v.data()}; return true; };
@@ -306,6 +310,109 @@ int ensure_transpose_index(DeviceGrid &d, hipStream_t stream) {
     d.tr_cell_ptr = ptr; d.tr_cell_pos = pos; d.tr_cell_node = node;
     return NIN_OK;
 }
+
+// ---- moving meshes: the geometry made again from new coordinates (grid_update.hip) ---------------------------------------------
+// The host mirror of a geometry that was updated on the device: the five arrays come back on first use (HostGrid::ensure), from
+// wherever the DeviceGrid holds them at that moment.  Installed by an update when the grid has no fetcher (a grid built on the
+// device still has its DeviceMirror, which reads the same buffers); HostGrid::ensure drops it once everything is on the host.
+struct GeometryMirror : LazyArrays {
+    const DeviceGrid *d;
+    explicit GeometryMirror(const DeviceGrid *dg) : d(dg) {}
+    template <class T>
+    static int get(std::vector<T> &dst, const T *src, size_t n, std::string *err) {
+        if (!src) { *err = "the device copy is gone"; return -3; }
+        dst.resize(n);
+        if (n && hipMemcpy(dst.data(), src, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) { *err = "hipMemcpy (device to host)"; return -3; }
+        return 0;
+    }
+    int fetch(HostGrid &h, unsigned which, std::string *err) override {
+        if (d->device < 0 || hipSetDevice(d->device) != hipSuccess) { *err = "the grid has no device copy"; return -3; }
+        const size_t P = (size_t)h.n_points, E = (size_t)h.n_elems, F = (size_t)h.n_faces;
+        int rc = 0;
+        if (!rc && (which & A_COORDS)) rc = get(h.coords, d->v.coords, P * 3, err);
+        if (!rc && (which & A_CENTROIDS)) rc = get(h.centroids, d->v.centroids, E * 3, err);
+        if (!rc && (which & A_FCENTERS)) rc = get(h.faces_centers, d->v.face_center, F * 3, err);
+        if (!rc && (which & A_NORMALS)) rc = get(h.normal_faces, d->v.face_normal, F * 3, err);
+        if (!rc && (which & A_AREAS)) rc = get(h.faces_areas, const_cast<const double *>(d->up_areas), F, err);
+        return rc;
+    }
+};
+
+// inpoel / etype / inpofa and the face-area array on the device (DeviceGrid::up_*): from the device builder's mirror if it still
+// holds them, else uploaded from the host arrays.  Synchronous.
+int ensure_update_inputs(nin_grid *g) {
+    DeviceGrid &d = g->d;
+    HostGrid &h = g->h;
+    if (d.up_inpoel) return NIN_OK;
+    LazyArrays::GeometryInputs gi;
+    if (h.lazy && h.lazy->lend_geometry_inputs(&gi)) {
+        for (void *q : {(void *)gi.inpoel, (void *)gi.etype, (void *)gi.inpofa, (void *)gi.areas}) d.allocs.push_back(q);
+        d.up_inpoel = gi.inpoel; d.up_etype = gi.etype; d.up_inpofa = gi.inpofa; d.up_areas = gi.areas;
+        return NIN_OK;
+    }
+    std::string err;
+    if (h.ensure(A_INPOEL | A_ETYPE | A_INPOFA, &err)) return fail(NIN_EHIP, "mirroring the connectivity: %s", err.c_str());
+    int32_t *inpoel = nullptr, *inpofa = nullptr;
+    int8_t *etype = nullptr;
+    double *areas = nullptr;
+    int rc = dev_alloc(d, &inpoel, h.inpoel.size());
+    if (!rc) rc = dev_alloc(d, &etype, h.etype.size());
+    if (!rc) rc = dev_alloc(d, &inpofa, h.inpofa.size());
+    if (!rc) rc = dev_alloc(d, &areas, (size_t)h.n_faces);
+    auto up = [&](void *dst, const void *src, size_t bytes) {
+        if (!rc && bytes && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = fail(NIN_EHIP, "uploading the connectivity failed");
+    };
+    up(inpoel, h.inpoel.data(), h.inpoel.size() * 4);
+    up(etype, h.etype.data(), h.etype.size());
+    up(inpofa, h.inpofa.data(), h.inpofa.size() * 4);
+    if (rc) { dev_release(d, inpoel); dev_release(d, etype); dev_release(d, inpofa); dev_release(d, areas); return rc; }
+    d.up_inpoel = inpoel; d.up_etype = etype; d.up_inpofa = inpofa; d.up_areas = areas;
+    return NIN_OK;
+}
+
+// xyz [P][cd] on the host (then stream = the null stream and the call waits) or on the grid's device
+int update_points_on_device(nin_grid *g, const double *xyz, bool on_host, int cd, hipStream_t stream) {
+    DeviceGrid &d = g->d;
+    HostGrid &h = g->h;
+    HIP_TRY(hipSetDevice(d.device));
+    int rc = ensure_update_inputs(g);
+    if (rc) return rc;
+    if (!d.ev_geom) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        d.ev_geom = e;
+    }
+    const size_t P = (size_t)h.n_points;
+    double *coords = const_cast<double *>(d.v.coords);
+    double *staged = nullptr;
+    if (on_host && cd == 3) {
+        HIP_TRY(hipMemcpy(coords, xyz, P * 24, hipMemcpyHostToDevice));
+    } else {
+        if (on_host) {
+            HIP_TRY(hipMalloc((void **)&staged, P * cd * sizeof(double)));
+            if (hipMemcpy(staged, xyz, P * cd * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(NIN_EHIP, "uploading the coordinates failed");
+        }
+        if (!rc && launch_update_coords(on_host ? staged : xyz, cd, (int64_t)P, coords, stream)) rc = fail(NIN_EHIP, "coordinate copy: %s", hipGetErrorString(hipGetLastError()));
+    }
+    uint64_t npoel8 = 0;
+    for (int t = 0; t < kNumElementTypes; ++t) npoel8 |= (uint64_t)(h.npoel[t] & 0xff) << (8 * t);
+    if (!rc && launch_update_geometry(d.v, npoel8, d.up_inpoel, d.up_etype, d.up_inpofa, const_cast<double *>(d.v.centroids),
+                                      const_cast<double *>(d.v.face_center), const_cast<float *>(d.v.face_normal), d.up_areas, stream))
+        rc = fail(NIN_EHIP, "geometry kernels: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc && d.v.centroids4 && launch_pad_centroids(d.v.centroids, h.n_elems, const_cast<double *>(d.v.centroids4), stream))
+        rc = fail(NIN_EHIP, "centroid padding kernel");
+    if (!rc && hipEventRecord(static_cast<hipEvent_t>(d.ev_geom), stream) != hipSuccess) rc = fail(NIN_EHIP, "hipEventRecord");
+    if (on_host || rc) {
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (e != hipSuccess && !rc) rc = fail(NIN_EHIP, "geometry update: %s", hipGetErrorString(e));
+    }
+    if (staged) (void)hipFree(staged);
+    // the host copies of the five arrays are the old mesh's from here on (also after a failure half way): fetched again on first use
+    h.have &= ~A_GEOMETRY;
+    if (!h.lazy) h.lazy.reset(new GeometryMirror(&g->d));
+    ++d.geom_updates;
+    return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -450,6 +557,29 @@ int nin_device_count(int *count) {
 // a grid built on the device holds its arrays there but has no launch plan yet: not "on the device" until to_device
 int nin_grid_device(const nin_grid *g) { return (g && !g->d.prebuilt) ? g->d.device : -1; }
 
+int nin_grid_update_points(nin_grid *g, const double *xyz, int coords_dim) {
+    if (!g || !xyz) return fail(NIN_EINVAL, "NULL argument");
+    if (coords_dim != g->coords_dim) return fail(NIN_EINVAL, "coords_dim %d is not the grid's (%d)", coords_dim, g->coords_dim);
+    // a grid that holds device arrays (a grid built on the device does before nin_grid_to_device too): the kernels
+    if (g->d.device >= 0) return update_points_on_device(g, xyz, true, coords_dim, nullptr);
+    try {
+        g->h.update_points(xyz, coords_dim);   // host-only: grid_host.cpp's own geometry code again
+    } catch (const std::bad_alloc &) {
+        return fail(NIN_ENOMEM, "out of host memory while updating the geometry");
+    }
+    return NIN_OK;
+}
+
+int nin_grid_update_points_device(nin_grid *g, const double *dev_xyz, int coords_dim, void *stream) {
+    if (!g || !dev_xyz) return fail(NIN_EINVAL, "NULL argument");
+    if (coords_dim != g->coords_dim) return fail(NIN_EINVAL, "coords_dim %d is not the grid's (%d)", coords_dim, g->coords_dim);
+    if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first, or nin_grid_update_points with a host array)");
+    return update_points_on_device(g, dev_xyz, false, coords_dim, static_cast<hipStream_t>(stream));
+}
+
+int64_t nin_grid_geometry_updates(const nin_grid *g) { return g ? g->d.geom_updates : 0; }
+int nin_grid_has_transpose_index(const nin_grid *g) { return g && g->d.tr_cell_ptr ? 1 : 0; }
+
 int nin_grid_to_device(nin_grid *g, int device) {
     if (!g) return fail(NIN_EINVAL, "NULL grid");
     int ndev = 0;
@@ -459,6 +589,7 @@ int nin_grid_to_device(nin_grid *g, int device) {
     const bool adopt = g->d.prebuilt && g->d.device == device;   // built on this device: the arrays are already there
     HostGrid &h = g->h;
     if (!adopt) {
+        if (g->d.ev_geom) (void)hipEventSynchronize(static_cast<hipEvent_t>(g->d.ev_geom));   // (a geometry update still in flight)
         std::string err;   // a device-built grid moving elsewhere: everything comes to the host before its HBM copy goes
         if (h.ensure(A_ALL, &err)) return fail(NIN_EHIP, "mirroring the device-built grid: %s", err.c_str());
         dev_free_all(g->d);
@@ -1220,6 +1351,16 @@ int nin_grid_release_scratch(nin_grid *g) {
     d.apply_weights = nullptr;
     d.tr_cell_ptr = d.tr_cell_pos = d.tr_cell_node = nullptr;
     if (d.flag_staging) { (void)hipHostFree(d.flag_staging); d.flag_staging = nullptr; }
+    // the connectivity copies of nin_grid_update_points*: kept while the device builder's mirror still fetches from them (they were its
+    // own before the first update: no HBM is held that the grid did not hold anyway)
+    if (d.up_inpoel && !(g->h.lazy && g->h.lazy->reads(d.up_inpoel))) {
+        std::string err;   // the face areas live nowhere else on the device: to the host first, if the host copy is the old mesh's
+        if (g->h.ensure(A_AREAS, &err)) return fail(NIN_EHIP, "mirroring faces_areas: %s", err.c_str());
+        dev_release(d, d.up_inpoel); dev_release(d, d.up_etype); dev_release(d, d.up_inpofa); dev_release(d, d.up_areas);
+        d.up_inpoel = d.up_inpofa = nullptr;
+        d.up_etype = nullptr;
+        d.up_areas = nullptr;
+    }
     return NIN_OK;
 }
 

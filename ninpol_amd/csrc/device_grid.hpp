@@ -137,6 +137,15 @@ struct DeviceGrid {
     // device by the first transpose call, released with the scratch.  tr_cell_ptr [E+1]; tr_cell_pos [nnz_e] = the position in esup /
     // csr_data of the pair (p, e); tr_cell_node [nnz_e] = p, ascending within a cell
     int32_t *tr_cell_ptr = nullptr, *tr_cell_pos = nullptr, *tr_cell_node = nullptr;
+    // what a geometry refresh (nin_grid_update_points*, grid_update.hip) reads next to the coordinates and the one array it writes that
+    // no weight kernel reads: inpoel [E][8], etype [E], inpofa [F][4], face areas [F].  Put here by the first update -- handed over by the
+    // device builder's mirror, or uploaded from the host arrays -- and given back with the scratch (0.32 + 0.01 + 0.48 + 0.24 GB at 10 M
+    // hexahedra); the next update brings them again.  geom_updates counts the updates; ev_geom (hipEvent_t) marks the last one's end.
+    int32_t *up_inpoel = nullptr, *up_inpofa = nullptr;
+    int8_t *up_etype = nullptr;
+    double *up_areas = nullptr;
+    int64_t geom_updates = 0;
+    void *ev_geom = nullptr;
     uint8_t *flag_staging = nullptr;   // page-locked [n_points]: nin_fields_set packs the node flags here and uploads from it
     void *copy_stream = nullptr, *copy_stream2 = nullptr;   // hipStream_t of the device-to-host copies that run under the kernels
     void *ev_weights = nullptr, *ev_scan = nullptr;   // hipEvent_t: weights written / row pointers scanned

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -367,6 +368,19 @@ struct DeviceMirror : LazyArrays {
         (void)hipSetDevice(device);
         for (void *p : owned) (void)hipFree(p);
     }
+    // the device copies a geometry refresh needs (nin_grid_update_points*): from now on they belong to the caller; fetch() goes on
+    // reading them, so the caller keeps them while reads() says so
+    bool lend_geometry_inputs(GeometryInputs *out) override {
+        void *lent[] = {inpoel, etype, inpofa, fa};
+        for (void *q : lent) {
+            auto it = std::find(owned.begin(), owned.end(), q);
+            if (it == owned.end()) return false;   // already lent
+        }
+        for (void *q : lent) owned.erase(std::find(owned.begin(), owned.end(), q));
+        *out = GeometryInputs{inpoel, etype, inpofa, fa};
+        return true;
+    }
+    bool reads(const void *p) const override { return p && (p == inpoel || p == etype || p == inpofa || p == fa); }
     int fetch(HostGrid &h, unsigned which, std::string *err) override {
         GB_TRY(hipSetDevice(device));
         int rc = 0;

@@ -63,6 +63,82 @@ inline bool elem_has_point(const int32_t *el, int n, int32_t p) {
 
 }  // namespace
 
+// [P][coords_dim] -> the grid's [P][3], zero-padded (inside an OpenMP team the caller set up)
+void HostGrid::load_coords(const double *xyz, int coords_dim) {
+    const int64_t P = n_points;
+    coords.assign((size_t)P * 3, 0.0);
+#pragma omp parallel for schedule(dynamic, 16384) num_threads(nin::host_team())
+    for (int64_t p = 0; p < P; ++p)
+        for (int k = 0; k < coords_dim && k < 3; ++k) coords[p * 3 + k] = xyz[p * coords_dim + k];
+}
+
+// centroids, face centres, float32 normals and areas from coords and the connectivity: the last step of build(), and all of
+// update_points()
+void HostGrid::compute_geometry() {
+    const int64_t E = n_elems, F = n_faces;
+    // ---- geometry (grid.pyx:669-809) -----------------------------------------------------------
+    centroids.assign((size_t)E * 3, 0.0);
+    const int d = (int)dim;
+#pragma omp parallel for schedule(dynamic, 16384) num_threads(nin::host_team())
+    for (int64_t e = 0; e < E; ++e) {
+        const int n = npoel[etype[e]];
+        for (int j = 0; j < n; ++j)
+            for (int k = 0; k < d; ++k) centroids[e * 3 + k] += coords[(int64_t)inpoel[e * 8 + j] * 3 + k] / (double)n;
+    }
+    faces_centers.assign((size_t)F * 3, 0.0);
+    normal_faces.assign((size_t)F * 3, 0.0f);
+    faces_areas.assign((size_t)F, 0.0);
+    const double *X = coords.data();
+#pragma omp parallel for schedule(dynamic, 16384) num_threads(nin::host_team())
+    for (int64_t f = 0; f < F; ++f) {
+        int npofa = 0;
+        for (int j = 0; j < kMaxPointsPerFace && inpofa[f * 4 + j] != -1; ++j) {
+            ++npofa;
+            for (int k = 0; k < d; ++k) faces_centers[f * 3 + k] += X[(int64_t)inpofa[f * 4 + j] * 3 + k];
+        }
+        for (int k = 0; k < d; ++k) faces_centers[f * 3 + k] /= (double)npofa;
+        const int64_t p1 = inpofa[f * 4 + 0], p2 = inpofa[f * 4 + 1];
+        if (d == 3) {
+            // float locals exactly as grid.pyx:732-736; the module is C++, so sqrt(float) is sqrtf
+            const int64_t p3 = inpofa[f * 4 + 2];
+            float v1x = (float)(X[p1 * 3 + 0] - X[p2 * 3 + 0]), v1y = (float)(X[p1 * 3 + 1] - X[p2 * 3 + 1]),
+                  v1z = (float)(X[p1 * 3 + 2] - X[p2 * 3 + 2]);
+            float v2x = (float)(X[p3 * 3 + 0] - X[p2 * 3 + 0]), v2y = (float)(X[p3 * 3 + 1] - X[p2 * 3 + 1]),
+                  v2z = (float)(X[p3 * 3 + 2] - X[p2 * 3 + 2]);
+            float nx = v1y * v2z - v1z * v2y, ny = v1z * v2x - v1x * v2z, nz = v1x * v2y - v1y * v2x;
+            float norm = fabsf(sqrtf(nx * nx + ny * ny + nz * nz));
+            normal_faces[f * 3 + 0] = nx / norm;
+            normal_faces[f * 3 + 1] = ny / norm;
+            normal_faces[f * 3 + 2] = nz / norm;
+            if (inpofa[f * 4 + 3] == -1) {
+                faces_areas[f] = (double)norm / 2.0;
+            } else {
+                const int64_t p4 = inpofa[f * 4 + 3];
+                v1x = (float)(X[p1 * 3 + 0] - X[p4 * 3 + 0]); v1y = (float)(X[p1 * 3 + 1] - X[p4 * 3 + 1]);
+                v1z = (float)(X[p1 * 3 + 2] - X[p4 * 3 + 2]);
+                v2x = (float)(X[p3 * 3 + 0] - X[p4 * 3 + 0]); v2y = (float)(X[p3 * 3 + 1] - X[p4 * 3 + 1]);
+                v2z = (float)(X[p3 * 3 + 2] - X[p4 * 3 + 2]);
+                nx = v1y * v2z - v1z * v2y; ny = v1z * v2x - v1x * v2z; nz = v1x * v2y - v1y * v2x;
+                faces_areas[f] = (double)(norm + sqrtf(nx * nx + ny * ny + nz * nz)) / 2.0;
+            }
+        } else {
+            float v1x = (float)(X[p1 * 3 + 0] - X[p2 * 3 + 0]), v1y = (float)(X[p1 * 3 + 1] - X[p2 * 3 + 1]);
+            float nx = -v1y, ny = v1x;
+            float norm = fabsf(sqrtf(nx * nx + ny * ny));
+            normal_faces[f * 3 + 0] = nx / norm;
+            normal_faces[f * 3 + 1] = ny / norm;
+            normal_faces[f * 3 + 2] = 0.0f;
+            faces_areas[f] = (double)norm;
+        }
+    }
+}
+
+void HostGrid::update_points(const double *xyz, int coords_dim) {
+    const ScopedTeam team(num_threads);
+    load_coords(xyz, coords_dim);
+    compute_geometry();
+}
+
 int HostGrid::build(const int64_t *connectivity, const int64_t *element_types, const double *xyz, int coords_dim) {
     const int64_t E = n_elems, P = n_points;
     const ScopedTeam team(num_threads);   // this build's OpenMP team (0: the CPUs this process may actually use); the process-wide default is not touched
@@ -91,10 +167,7 @@ int HostGrid::build(const int64_t *connectivity, const int64_t *element_types, c
     }
     if (bad) return -1;
 
-    coords.assign((size_t)P * 3, 0.0);
-#pragma omp parallel for schedule(dynamic, 16384) num_threads(nin::host_team())
-    for (int64_t p = 0; p < P; ++p)
-        for (int k = 0; k < coords_dim && k < 3; ++k) coords[p * 3 + k] = xyz[p * coords_dim + k];
+    load_coords(xyz, coords_dim);
 
     lap("ingest");
     // ---- esup (grid.pyx:233-267) ------------------------------------------------------------
@@ -296,61 +369,7 @@ int HostGrid::build(const int64_t *connectivity, const int64_t *element_types, c
             for (int k = 0; k < kMaxPointsPerFace && inpofa[f * 4 + k] != -1; ++k) boundary_points[inpofa[f * 4 + k]] = 1;
 
     lap("esuf");
-    // ---- geometry (grid.pyx:669-809) -----------------------------------------------------------
-    centroids.assign((size_t)E * 3, 0.0);
-    const int d = (int)dim;
-#pragma omp parallel for schedule(dynamic, 16384) num_threads(nin::host_team())
-    for (int64_t e = 0; e < E; ++e) {
-        const int n = npoel[etype[e]];
-        for (int j = 0; j < n; ++j)
-            for (int k = 0; k < d; ++k) centroids[e * 3 + k] += coords[(int64_t)inpoel[e * 8 + j] * 3 + k] / (double)n;
-    }
-    faces_centers.assign((size_t)F * 3, 0.0);
-    normal_faces.assign((size_t)F * 3, 0.0f);
-    faces_areas.assign((size_t)F, 0.0);
-    const double *X = coords.data();
-#pragma omp parallel for schedule(dynamic, 16384) num_threads(nin::host_team())
-    for (int64_t f = 0; f < F; ++f) {
-        int npofa = 0;
-        for (int j = 0; j < kMaxPointsPerFace && inpofa[f * 4 + j] != -1; ++j) {
-            ++npofa;
-            for (int k = 0; k < d; ++k) faces_centers[f * 3 + k] += X[(int64_t)inpofa[f * 4 + j] * 3 + k];
-        }
-        for (int k = 0; k < d; ++k) faces_centers[f * 3 + k] /= (double)npofa;
-        const int64_t p1 = inpofa[f * 4 + 0], p2 = inpofa[f * 4 + 1];
-        if (d == 3) {
-            // float locals exactly as grid.pyx:732-736; the module is C++, so sqrt(float) is sqrtf
-            const int64_t p3 = inpofa[f * 4 + 2];
-            float v1x = (float)(X[p1 * 3 + 0] - X[p2 * 3 + 0]), v1y = (float)(X[p1 * 3 + 1] - X[p2 * 3 + 1]),
-                  v1z = (float)(X[p1 * 3 + 2] - X[p2 * 3 + 2]);
-            float v2x = (float)(X[p3 * 3 + 0] - X[p2 * 3 + 0]), v2y = (float)(X[p3 * 3 + 1] - X[p2 * 3 + 1]),
-                  v2z = (float)(X[p3 * 3 + 2] - X[p2 * 3 + 2]);
-            float nx = v1y * v2z - v1z * v2y, ny = v1z * v2x - v1x * v2z, nz = v1x * v2y - v1y * v2x;
-            float norm = fabsf(sqrtf(nx * nx + ny * ny + nz * nz));
-            normal_faces[f * 3 + 0] = nx / norm;
-            normal_faces[f * 3 + 1] = ny / norm;
-            normal_faces[f * 3 + 2] = nz / norm;
-            if (inpofa[f * 4 + 3] == -1) {
-                faces_areas[f] = (double)norm / 2.0;
-            } else {
-                const int64_t p4 = inpofa[f * 4 + 3];
-                v1x = (float)(X[p1 * 3 + 0] - X[p4 * 3 + 0]); v1y = (float)(X[p1 * 3 + 1] - X[p4 * 3 + 1]);
-                v1z = (float)(X[p1 * 3 + 2] - X[p4 * 3 + 2]);
-                v2x = (float)(X[p3 * 3 + 0] - X[p4 * 3 + 0]); v2y = (float)(X[p3 * 3 + 1] - X[p4 * 3 + 1]);
-                v2z = (float)(X[p3 * 3 + 2] - X[p4 * 3 + 2]);
-                nx = v1y * v2z - v1z * v2y; ny = v1z * v2x - v1x * v2z; nz = v1x * v2y - v1y * v2x;
-                faces_areas[f] = (double)(norm + sqrtf(nx * nx + ny * ny + nz * nz)) / 2.0;
-            }
-        } else {
-            float v1x = (float)(X[p1 * 3 + 0] - X[p2 * 3 + 0]), v1y = (float)(X[p1 * 3 + 1] - X[p2 * 3 + 1]);
-            float nx = -v1y, ny = v1x;
-            float norm = fabsf(sqrtf(nx * nx + ny * ny));
-            normal_faces[f * 3 + 0] = nx / norm;
-            normal_faces[f * 3 + 1] = ny / norm;
-            normal_faces[f * 3 + 2] = 0.0f;
-            faces_areas[f] = (double)norm;
-        }
-    }
+    compute_geometry();
     lap("geometry");
     nnz_esup = (int64_t)esup.size();
     nnz_fsup = (int64_t)fsup.size();

@@ -26,7 +26,14 @@ struct HostGrid;
 struct LazyArrays {   // implemented by the device builder (grid_device.hip)
     virtual ~LazyArrays() {}
     virtual int fetch(HostGrid &h, unsigned which, std::string *err) = 0;   // 0 or a negative code
+    // A geometry refresh on the device (nin_grid_update_points*) reads inpoel / etype / inpofa and writes the face areas there.  A
+    // fetcher that holds device copies of the four hands their ownership to the caller (who frees them) and goes on reading them:
+    // see reads().  false: it has none.
+    struct GeometryInputs { int32_t *inpoel = nullptr; int8_t *etype = nullptr; int32_t *inpofa = nullptr; double *areas = nullptr; };
+    virtual bool lend_geometry_inputs(GeometryInputs *) { return false; }
+    virtual bool reads(const void *) const { return false; }   // does fetch() still read this device buffer?
 };
+constexpr unsigned A_GEOMETRY = A_COORDS | A_CENTROIDS | A_FCENTERS | A_NORMALS | A_AREAS;
 
 struct HostGrid {
     int64_t dim = 0, n_elems = 0, n_points = 0, n_faces = 0, n_edges = 0;
@@ -83,6 +90,10 @@ struct HostGrid {
     }
 
     int build(const int64_t *connectivity, const int64_t *element_types, const double *xyz, int coords_dim);
+    // the geometry of build() again from new coordinates [P][coords_dim] (every array must be on the host); connectivity untouched
+    void update_points(const double *xyz, int coords_dim);
+    void load_coords(const double *xyz, int coords_dim);   // the two steps of it, shared with build()
+    void compute_geometry();
     // used by the device builder (grid_device.hip) when it mirrors its int32 arrays into this object
     static void widen(const std::vector<int32_t> &src, std::vector<int64_t> &dst);
     void esuf_from_pairs(const std::vector<int32_t> &pairs);   // [F][2] (creator, neighbour or -1) -> esuf_ptr, esuf

@@ -118,6 +118,13 @@ int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStr
 int launch_classify(const GridView &g, int use_group, int force_global, uint8_t *node_class,
                     unsigned long long *class_max, hipStream_t stream);
 
+// grid_update.hip: a moving mesh's geometry from new coordinates (nin_grid_update_points*), all DEVICE pointers.  First the grid's
+// [P][3] coordinates from the caller's [P][coords_dim] (zero-padded), then centroids / face centres / float32 normals / areas from
+// g.coords and the [E][8] / [E] / [F][4] connectivity the builders made; npoel8 = points per cell of element type t in byte t
+int launch_update_coords(const double *dev_xyz, int coords_dim, int64_t n_points, double *coords, hipStream_t stream);
+int launch_update_geometry(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const int32_t *inpofa,
+                           double *centroids, double *face_center, float *face_normal, double *face_area, hipStream_t stream);
+
 const char *kernel_name_idw();
 const char *kernel_name_ls();
 const char *kernel_name_gls();

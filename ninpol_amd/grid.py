@@ -40,8 +40,9 @@ class Grid:
     element_types, logging=False, build_edges=False)  -- grid.pyx:47-53.
 
     Unlike the reference, the point coordinates are part of construction (`coords=`) and everything
-    -- connectivity, centroids, normals -- is built in one native call; `build()`,
-    `load_point_coords()` etc. are therefore no-ops kept for call-compatibility.
+    -- connectivity, centroids, normals -- is built in one native call; `build()`, `calculate_centroids()`,
+    `calculate_normal_faces()` and `load_point_coords()` without an argument are therefore no-ops kept for
+    call-compatibility.  `load_point_coords(coords)` moves the points of the built grid (a deforming mesh).
     """
 
     def __init__(self, dim, n_elems, n_points, npoel, nfael, lnofa, lpofa, nedel, lpoed, connectivity,
@@ -110,6 +111,44 @@ class Grid:
         return None
 
     def load_point_coords(self, coords=None):
+        """With coordinates: move the mesh (Interpolator.update_points does this).  `coords` has the shape the constructor saw,
+        (n_points, coords_dim): a host array, or a torch tensor on the grid's device.  The connectivity, the GLS launch plan and
+        everything else resident on the device stay; point_coords, centroids, faces_centers, normal_faces and faces_areas become
+        what a fresh Grid of the moved mesh holds, bit for bit (nin_grid_update_points / nin_grid_update_points_device).  A host
+        array is synchronous; a device tensor is asynchronous on torch's current stream and is not copied to the host.
+
+        Without coordinates: a no-op, like build() (reference-style call sequences load the coordinates at construction here)."""
+        if coords is None:
+            return None
+        L = _lib.load()
+        shape = (int(self.n_points), self._coords_dim)
+        if type(coords).__module__.split(".")[0] == "torch" and getattr(coords, "is_cuda", False):
+            import torch
+            if tuple(coords.shape) != shape:
+                raise ValueError(f"points must have shape {shape}, not {tuple(coords.shape)}.")
+            if coords.dtype != torch.float64:
+                raise ValueError(f"points on the device must be float64, not {coords.dtype}.")
+            if self.device < 0 or coords.device.index != self.device:
+                raise ValueError(f"points are on {coords.device}, the grid is on " +
+                                 (f"cuda:{self.device}" if self.device >= 0 else "no device (call to_device first)") + ".")
+            t = coords.detach().contiguous()
+            stream = torch.cuda.current_stream(coords.device).cuda_stream
+            rc = L.nin_grid_update_points_device(self._h, ctypes.c_void_p(t.data_ptr()), self._coords_dim, ctypes.c_void_p(stream))
+        else:
+            if type(coords).__module__.split(".")[0] == "torch":
+                coords = coords.detach().numpy()
+            try:
+                xyz = np.ascontiguousarray(coords, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"points cannot be converted to float64: {e}") from e
+            if xyz.shape != shape:
+                raise ValueError(f"points must have shape {shape}, not {xyz.shape}.")
+            rc = L.nin_grid_update_points(self._h, _ptr(xyz), self._coords_dim)
+        for name in ("point_coords", "centroids", "faces_centers", "normal_faces", "faces_areas"):
+            self._cache.pop(name, None)   # also after a failure: the native arrays may be half way
+        if rc == _lib.NIN_EINVAL:
+            raise ValueError(L.nin_last_error().decode())
+        _lib.check(rc)
         return None
 
     def calculate_centroids(self):
@@ -184,9 +223,19 @@ class Grid:
     def device(self):
         return int(_lib.load().nin_grid_device(self._h))
 
+    @property
+    def geometry_updates(self):
+        """How many times load_point_coords() moved the device copy of this grid (0: never, or the grid is host-only)."""
+        return int(_lib.load().nin_grid_geometry_updates(self._h))
+
+    @property
+    def has_transpose_index(self):
+        """Is the cell-major index of apply_transpose() resident on the device?  (It survives a move of the points.)"""
+        return bool(_lib.load().nin_grid_has_transpose_index(self._h))
+
     def release_scratch(self):
         """Free the device buffers interpolate() / apply() keep between calls (nin_grid_release_scratch: ~2.3 GB of HBM
-        at 10 M cells); the next call allocates them again."""
+        at 10 M cells; the connectivity copies of load_point_coords(): ~1 GB more); the next call allocates them again."""
         _lib.check(_lib.load().nin_grid_release_scratch(self._h))
 
     PLAN_KERNELS = ("block1", "block2", "block4", "block8", "scratch", "hex8", "mfw_large", "mfw_small", "mfw_general", "small4", "small8",

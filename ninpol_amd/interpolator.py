@@ -213,6 +213,20 @@ class Interpolator:
         self.grid = None
         self.points_coords = None
 
+    @property
+    def points_coords(self):
+        """The node coordinates as load_mesh() / update_points() last saw them (after an update from a device tensor: read
+        back from the grid on first use)."""
+        if self._points_coords is None and self._points_on_device:
+            self._points_coords = np.ascontiguousarray(self.grid.point_coords)
+            self._points_on_device = False
+        return self._points_coords
+
+    @points_coords.setter
+    def points_coords(self, value):
+        self._points_coords = value
+        self._points_on_device = False
+
     def _log(self, msg, kind="INFO"):
         if self.logging:
             print(f"[{kind:<5}] ({time.strftime('%H:%M:%S'):<8}) {msg}")
@@ -262,6 +276,31 @@ class Interpolator:
         self._log(f"Data loaded in {time.time() - t0:.2f} seconds")
         self.is_grid_initialized = True
         self._log(f"Mesh loaded successfully: {self.grid.n_points} points and {self.grid.n_elems} elements.")
+
+    def update_points(self, points):
+        """Move the mesh: new node coordinates, same connectivity (ALE and free-surface steps, mesh smoothing, shape optimisation).
+        `points`: an array of the shape load_mesh() saw, (n_points, 2 or 3) -- synchronous -- or a float64 torch tensor of that
+        shape on this Interpolator's device: then the geometry is recomputed from device memory, asynchronously on torch's current
+        stream, with no host copy; launches of a DevicePlan / CellToNode on that stream follow in order, the host-synchronous
+        methods (interpolate, apply, apply_transpose) need `torch.cuda.current_stream().synchronize()` first.
+
+        Afterwards every grid array and every result is bit for bit what a fresh load_mesh() of the moved mesh gives.  What stays:
+        the connectivity, the fields (permeability, Neumann flags), the GLS launch plan, the transpose index, all scratch.  What
+        does not follow by itself: weights already computed -- matrices returned earlier, the buffers a DevicePlan.launch wrote,
+        the weights a CellToNode holds (call its refresh()) -- and `mesh_obj.points`, which is the caller's."""
+        if not self.is_grid_initialized:
+            raise ValueError("Grid not initialized. Please load a mesh first.")
+        g = self.grid
+        on_device = type(points).__module__.split(".")[0] == "torch" and getattr(points, "is_cuda", False)
+        if on_device and g.device < 0:
+            g.to_device(self.device)
+        g.load_point_coords(points)
+        if on_device:
+            self._points_coords, self._points_on_device = None, True
+        else:
+            if type(points).__module__.split(".")[0] == "torch":
+                points = points.detach().numpy()
+            self.points_coords = np.ascontiguousarray(np.array(points, dtype=DTYPE_F))
 
     def load_arrays(self, points, cells, cell_data=None, point_data=None):
         """`load_mesh` from plain arrays, no meshio object.  `cells` is a list of
@@ -547,7 +586,10 @@ class DevicePlan:
     The Neumann flags and the permeability on the device belong to the grid, not to the plan: a launch first checks that
     the grid's resident flags are still this plan's variable (another plan, or interpolate() on another variable, may
     have replaced them) and re-uploads if not; `refresh()` re-reads the caller's tables unconditionally -- an in-place
-    edit of a table is only seen there, exactly as Interpolator.interpolate() sees it on every call."""
+    edit of a table is only seen there, exactly as Interpolator.interpolate() sees it on every call.
+
+    The geometry belongs to the grid too: after Interpolator.update_points() the next `launch` computes the weights of the moved
+    mesh (no refresh() is needed for that; what an earlier launch wrote into the caller's buffers stays what it was)."""
 
     def __init__(self, interp, variable, method):
         if not interp.is_grid_initialized:

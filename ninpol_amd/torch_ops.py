@@ -34,8 +34,10 @@ class CellToNode(torch.nn.Module):
 
     The weights are computed once, at construction, into `weights` (float64 [nnz_esup], esup / CSR position) with `neumann_ws`
     (float64 [n_points]) beside them; `refresh()` re-reads the Interpolator's tables and computes them again -- an in-place edit of
-    the permeability is seen there and only there (the contract of DevicePlan.refresh()).  Derivatives with respect to the
-    permeability or the Neumann values are not provided."""
+    the permeability is seen there and only there (the contract of DevicePlan.refresh()).  The same holds for a moved mesh: after
+    `interp.update_points(...)` the module goes on applying the weights of the old geometry until `refresh()`; nothing is
+    recomputed behind the caller's back.  Derivatives with respect to the permeability, the Neumann values or the node
+    coordinates are not provided."""
 
     def __init__(self, interp, variable, method):
         super().__init__()
@@ -58,7 +60,8 @@ class CellToNode(torch.nn.Module):
         self.weights, self.neumann_ws = w, nws
 
     def refresh(self):
-        """Upload the Interpolator's field tables as they are now and recompute the weights."""
+        """Upload the Interpolator's field tables as they are now and recompute the weights, from the grid's geometry as it is now
+        (on torch's current stream: behind an update_points() from a device tensor on the same stream)."""
         self.plan.refresh()
         self._compute_weights()
 
