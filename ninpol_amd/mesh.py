@@ -392,6 +392,106 @@ def composite_mesh(parts, interleave=True):
     return m
 
 
+# ------------------------------------------------------------------------------------------------
+# relabelling: the same mesh as an arbitrary mesher would number it
+# ------------------------------------------------------------------------------------------------
+
+def _cyclic(face):
+    """a face as the set of its cyclic rotations' canonical form: rotated so that its smallest vertex comes first"""
+    if len(face) == 2:          # an edge of a 2-D cell: the ordered pair is its orientation
+        return tuple(face)
+    k = face.index(min(face))
+    return tuple(face[k:] + face[:k])
+
+
+def _oriented_automorphisms(n, faces):
+    """Every permutation s of range(n) that maps each oriented face (v0, v1, ...) of `faces` onto an oriented face of `faces`
+    (same cyclic order, not reversed): the orientation-preserving symmetries of the cell's surface."""
+    from itertools import permutations
+    have = {_cyclic(list(f)) for f in faces}
+    return [s for s in permutations(range(n)) if all(_cyclic([s[v] for v in f]) in have for f in faces)]
+
+
+def _hexahedron_rotations():
+    """The 24 proper rotations of the cube (signed permutation matrices of determinant +1) acting on the corner coordinates
+    of the meshio hexahedron: s[v] = the corner that corner v is carried to."""
+    from itertools import permutations, product
+    corners = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]]) * 2 - 1
+    index = {tuple(c): v for v, c in enumerate(corners)}
+    out = []
+    for axes in permutations(range(3)):
+        for signs in product((1, -1), repeat=3):
+            R = np.zeros((3, 3), dtype=np.int64)
+            for r in range(3):
+                R[r, axes[r]] = signs[r]
+            if round(np.linalg.det(R)) == 1:
+                out.append(tuple(index[tuple(R @ c)] for c in corners))
+    return out
+
+
+_ROTATIONS = {}
+
+
+def cell_rotations(cell_type):
+    """(G, n) int64: the orientation-preserving symmetry group of a cell type in meshio vertex order, one permutation a row
+    (24 hexahedron, 12 tetra, 6 wedge, 4 pyramid, 4 quad, 3 triangle); data[:, row] is the same cell with its vertices listed
+    from another corner.  Derived, not typed in: the hexahedron's from the rotations of the cube, the others from the type's
+    face table (2-D types: their edges) in topology.py.  None for a type without faces (vertex, line)."""
+    if cell_type not in _ROTATIONS:
+        from .topology import ELEMENTS
+        e = ELEMENTS[cell_type]
+        faces = e["faces"] or (e["edges"] if cell_type in ("triangle", "quad") else [])
+        if cell_type == "hexahedron":
+            rows = _hexahedron_rotations()
+        elif faces:
+            rows = _oriented_automorphisms(e["number_of_points"], faces)
+        else:
+            rows = None
+        _ROTATIONS[cell_type] = None if rows is None else np.array(sorted(rows), dtype=np.int64)
+    return _ROTATIONS[cell_type]
+
+
+def relabel_mesh(mesh, seed, nodes=True, cells=True, rotate=True):
+    """The same mesh (geometry, topology, fields) under another labelling, as a mesher's file would bring it:
+
+    nodes:  a random permutation of the node ids (points, every point_data array, all connectivity);
+    cells:  a random permutation of the cells inside each block (connectivity and every cell_data array); blocks keep their
+            type and order;
+    rotate: per cell, a random element of cell_rotations(type): its vertices listed from another corner, orientation kept
+            (no reflections: the reference assumes positively oriented cells).
+
+    Attach fields BEFORE relabelling: they are carried over, so a Neumann plane and its seeded values mean the same nodes.
+    The returned mesh carries `new_node_of_old` (new id of each old node) and `old_cell_of_new` (old global cell id, block
+    order, of each new global cell), as composite_mesh carries part_nodes / part_cells."""
+    rng = np.random.default_rng(seed)
+    P = int(np.asarray(mesh.points).shape[0])
+    new_node_of_old = rng.permutation(P).astype(np.int64) if nodes else np.arange(P, dtype=np.int64)
+    points = np.empty_like(np.asarray(mesh.points))
+    points[new_node_of_old] = mesh.points
+    point_data = {}
+    for name, a in mesh.point_data.items():
+        a = np.asarray(a)
+        point_data[name] = np.empty_like(a)
+        point_data[name][new_node_of_old] = a
+    blocks, orders = [], []
+    for b in mesh.cells:
+        data = np.asarray(b.data)
+        n = len(data)
+        order = rng.permutation(n) if cells else np.arange(n)
+        data = data[order]
+        table = cell_rotations(b.type) if rotate else None
+        if table is not None and n:
+            data = np.take_along_axis(data, table[rng.integers(len(table), size=n)], axis=1)
+        blocks.append(CellBlock(b.type, new_node_of_old[data]))
+        orders.append(order)
+    cell_data = {name: [np.asarray(a)[o] for a, o in zip(per_block, orders)] for name, per_block in mesh.cell_data.items()}
+    first = np.cumsum([0] + [len(o) for o in orders])
+    m = Mesh(np.ascontiguousarray(points), blocks, point_data=point_data, cell_data=cell_data)
+    m.new_node_of_old = new_node_of_old
+    m.old_cell_of_new = np.concatenate([first[b] + o for b, o in enumerate(orders)]).astype(np.int64) if orders else np.zeros(0, dtype=np.int64)
+    return m
+
+
 def _fix_tet_orientation(pts, tets):
     a, b, c, d = (pts[tets[:, i]] for i in range(4))
     vol = np.einsum("ij,ij->i", np.cross(b - a, c - a), d - a)

@@ -1,5 +1,7 @@
 """Random meshes / fields / Neumann planes through the HIP path against the oracle (a fixed-seed slice of
-tools/fuzz_parity.py): every mesh family, both grid builders, all three methods, every GLS kernel."""
+tools/fuzz_parity.py): every mesh family, both grid builders, all three methods, every GLS kernel.  Cases 25 .. 39 draw a mesh the
+same way and relabel it (mesh.relabel_mesh) with a random non-empty subset of {nodes, cells, vertex rotation}: the oracle on the
+SAME relabelled mesh is the yardstick (the reference is not equivariant under cell reordering or vertex rotation)."""
 import numpy as np
 import pytest
 
@@ -9,10 +11,17 @@ from ninpol_amd import mesh as M
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("case", range(25))
+# cases 25 .. 39: the kind / lattice / grid-builder choices of these earlier cases (every family at least twice), fresh draws
+_RELABELLED = (0, 1, 2, 3, 4, 15, 16, 17, 21, 22, 7, 8, 9, 18, 23)
+
+
+@pytest.mark.parametrize("case", range(25 + len(_RELABELLED)))
 def test_fuzz_case(oracle_lib, case):
     import ninpol_amd
     rng = np.random.default_rng(7000 + case)
+    relabel = case >= 25
+    if relabel:
+        case = _RELABELLED[case - 25]
     kind = ["hex", "tet", "wedge", "mixed", "fan"][case % 5] if case < 15 else "delaunay" if case < 21 else "prisms"   # (cases 0 .. 14 are round 3's, unchanged)
     nx, ny, nz = (int(v) for v in rng.integers(3, 9, size=3))
     jit = float(rng.uniform(0.0, 0.2))
@@ -34,6 +43,11 @@ def test_fuzz_case(oracle_lib, case):
     plane = None if rng.random() < 0.3 else (int(rng.integers(0, 3)), float(rng.integers(0, 2)))
     perm = ["ALH", "LIN", "FAN"][int(rng.integers(0, 3))]    # FAN: cond(M_v) ~1e5, still inside 1e-10 at these sizes
     M.attach_fields(m, "u", perm=perm, neumann_plane=plane, seed=seed % 1000)
+    if relabel:
+        which = int(rng.integers(1, 8))                      # a non-empty subset of the three switches
+        nodes, cells, rotate = bool(which & 1), bool(which & 2), bool(which & 4)
+        m = M.relabel_mesh(m, seed=int(rng.integers(1 << 30)), nodes=nodes, cells=cells, rotate=rotate)
+        kind = f"{kind} relabelled nodes={nodes} cells={cells} rotate={rotate}"
     o = oracle_lib.OracleInterpolator("port", threads=4)
     o.load_mesh(m)
     I = ninpol_amd.Interpolator(grid_build=["host", "device"][case % 2])

@@ -47,6 +47,11 @@ def _meshes():
     yield "delaunay5_random_cloud", M.delaunay_tet_mesh(5, seed=6, lattice="random"), "LIN", (2, 0.0)
     yield "delaunay_prisms8", M.delaunay_wedge_mesh(8, 4, seed=1), "ALH", (2, 0.0)
     yield "delaunay_prisms7_random", M.delaunay_wedge_mesh(7, 3, seed=2, lattice="random"), "LIN", (0, 1.0)
+    # the same families under an arbitrary labelling (mesh.relabel_mesh: nodes, cells inside each block, vertex rotation)
+    yield "relabelled_hex9_jitter", M.relabel_mesh(M.hex_mesh(9, 8, 7, jitter=0.15, seed=4), seed=1), "ALH", (2, 0.0)
+    yield "relabelled_mixed844", M.relabel_mesh(M.mixed_mesh(8, 4, 4, jitter=0.1, seed=5), seed=2), "ALH", (2, 1.0)
+    yield "relabelled_delaunay5_random_cloud", M.relabel_mesh(M.delaunay_tet_mesh(5, seed=7, lattice="random"), seed=3), "ALH", (0, 1.0)
+    yield "relabelled_delaunay_prisms7_random", M.relabel_mesh(M.delaunay_wedge_mesh(7, 3, seed=8, lattice="random"), seed=4), "LIN", (1, 0.0)
 
 
 @pytest.mark.parametrize("name,mesh,perm,plane", list(_meshes()), ids=[m[0] for m in _meshes()])
