@@ -85,11 +85,13 @@ def build(force=False, verbose_resources=False):
 
 
 def build_tools():
-    """Stand-alone device test programs (tests/test_gpu_parity.py runs them on the GPU box): tools/_bin/test_xstrip."""
+    """Stand-alone device test programs (tests/test_gpu_parity.py and tests/test_gpu_face_tau.py run them on the GPU box):
+    tools/_bin/test_xstrip, tools/_bin/test_face_tau."""
     tools = os.path.join(os.path.dirname(HERE), "tools")
     os.makedirs(os.path.join(tools, "_bin"), exist_ok=True)
-    _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-I", CSRC, os.path.join(tools, "test_xstrip.hip"), "-o",
-          os.path.join(tools, "_bin", "test_xstrip")])
+    for name in ("test_xstrip", "test_face_tau"):
+        _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-I", CSRC, os.path.join(tools, name + ".hip"), "-o",
+              os.path.join(tools, "_bin", name)])
 
 
 if __name__ == "__main__":

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gls_tau_table.hpp"
+
 namespace nin {
 namespace glsmath {
 
@@ -108,6 +110,58 @@ __device__ __attribute__((noinline)) static double face_tau_t(double un, double 
 }
 __device__ __forceinline__ double face_tau(double un, double eta) { return face_tau_t<false>(un, eta); }
 __device__ __forceinline__ double face_tau_sq(double un2, double eta) { return face_tau_t<true>(un2, eta); }
+
+// The same tau from TABLES, 29 FP64 instructions a call where the series above has 50 (tools/proto_face_tau.py is the model,
+// operation for operation, and writes gls_tau_table.hpp).  u = 2^e m, interval i of 128 from m's top mantissa bits:
+//   log   f = fma(m, rc_i, -1) with the table's rc_i = fl(1 / c_i) -- no v_rcp_f64, no Newton steps -- |f| <= 2^-8, and
+//         log m = lc_i + f + f^2 g(f), lc_i = -log(rc_i) in two words, g of degree 3;  s = e LN2_HI + lh_i is exact, the rest of
+//         the logarithm is the small word w;
+//   pow   eta log u = yh + yl in two words (yl = the rounding of eta s, by fma, + eta w): with one word, the rounding of
+//         y = 55 (u = 1e-6, eta = 4) alone is 6e-15 on tau -- the series above has that error outside eta <= 1;
+//   exp   y = c (yh + yl), c = -1 or -1/2 (SQUARED) folded into the constants; k = rint(32 y / ln 2) from yh alone,
+//         rho = y - k ln2 / 32, |rho| <= ln2 / 64 + |c| eta 2^-8 (0.0265 at |c| eta = 4), exp(rho) = 1 + rho Q(rho), Q of degree
+//         5 fitted to |rho| <= 0.0275; tau = 2^(k >> 5) T_j (1 + rho Q), T_j = 2^(j / 32), j = k & 31.
+// Against numpy's pow over u in [1e-6, 1e2] (tests/test_face_tau_model.py): max relative error 2.2e-16 for eta in (0, 1],
+// 3.3e-16 for eta in (0, 4], mean 4.6e-17 (the series above: 1.8e-15 on (0, 1]).  Beyond |c| eta = 4 the fit of Q is left
+// behind gradually: 1e-15 at |c| eta = 8.
+// `tab` is a copy of kTauTab in LDS (tau_table_to_lds): the entries are chosen per lane, so they come by vector loads,
+// and from LDS they cost no memory traffic.  Both indices are masked: no input reads outside the table.  Out of line for the
+// same reason as the series.
+using lds_cdouble_ptr = const __attribute__((address_space(3))) double *;
+template <bool SQUARED>
+__device__ __attribute__((noinline)) static double face_tau_tab_t(double un, double eta, lds_cdouble_ptr tab) {
+    if (eta == 0.0) return 1.0;
+    constexpr double C = SQUARED ? -0.5 : -1.0;
+    constexpr double E0 = TAU_EX[0] * C, E1 = TAU_EX[1] * C * C, E2 = TAU_EX[2] * C * C * C, E3 = TAU_EX[3] * C * C * C * C,
+                     E4 = TAU_EX[4] * C * C * C * C * C, E5 = TAU_EX[5] * C * C * C * C * C * C;   // (powers of two: exact)
+    const double m = __builtin_amdgcn_frexp_mant(un);      // [0.5, 1)
+    const double ef = (double)__builtin_amdgcn_frexp_exp(un);
+    const int i = (__double2hiint(m) >> 13) & (TAU_LOG_N - 1);
+    const double f = fma(m, tab[i], -1.0);
+    const double f2 = f * f;
+    double g = fma(TAU_LG[3], f, TAU_LG[2]);
+    g = fma(g, f, TAU_LG[1]);
+    g = fma(g, f, TAU_LG[0]);
+    const double s = fma(ef, TAU_LN2_HI, tab[TAU_LOG_N + i]);
+    double t = fma(ef, TAU_LN2_LO, tab[2 * TAU_LOG_N + i]);
+    t = fma(f2, g, t);
+    const double w = f + t;
+    const double yh = eta * s;
+    const double yl = fma(eta, w, fma(eta, s, -yh));
+    const double k = rint(yh * (C * TAU_INV_L));
+    double r = fma(k, -(TAU_LN2_HI / TAU_EXP_N) / C, yh);
+    r = fma(k, -(TAU_LN2_LO / TAU_EXP_N) / C, r);
+    r = r + yl;                                            // rho = C r
+    double q = fma(E5, r, E4);
+    q = fma(q, r, E3); q = fma(q, r, E2); q = fma(q, r, E1); q = fma(q, r, E0);
+    const int ki = (int)k;
+    const double T = tab[3 * TAU_LOG_N + (ki & (TAU_EXP_N - 1))];
+    return __builtin_amdgcn_ldexp(fma(T * r, q, T), ki >> 5);
+}
+// the table into a workgroup's LDS, by all its threads; the caller synchronises the workgroup before the first call
+__device__ __forceinline__ void tau_table_to_lds(double *tab) {
+    for (int i = threadIdx.x; i < TAU_TAB_DOUBLES; i += blockDim.x) tab[i] = kTauTab[i];
+}
 
 // The panel of a front: three Householder steps on the front cell's own columns (10 rows: the cell row and the 3 x 3
 // rows of its faces).  v_k stays in P[k..9][k] (pivot entries included), R's off-diagonal entries in P[0][1], P[0][2],

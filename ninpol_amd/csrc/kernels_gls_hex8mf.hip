@@ -270,6 +270,13 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
                                                                 const double *__restrict__ u_cells, int32_t n_fields,
                                                                 double *__restrict__ values) {
     __shared__ double lds_all[4][W2_WAVE_DOUBLES];
+    // the tables of face_tau_tab_t, once per workgroup: 3 328 B beside the four waves' 77 824 -- 81 152 B a workgroup, 162 304 of
+    // the CU's 163 840 for the two that are resident (W2_WAVE_DOUBLES stays as it is; 1 536 B are left)
+    __shared__ double tau_tab[TAU_TAB_DOUBLES];
+    static_assert(2 * (sizeof(double) * (4 * W2_WAVE_DOUBLES + TAU_TAB_DOUBLES)) <= 160 * 1024, "two workgroups per CU");
+    tau_table_to_lds(tau_tab);
+    __syncthreads();
+    const lds_cdouble_ptr tau_lds = (lds_cdouble_ptr)tau_tab;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l = lane & 3, nd = lane >> 2;
     double *const L = lds_all[wave] + lane;                   // slot k of this lane: L[64 k]
@@ -384,7 +391,7 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
                 double eta = 0.0;
                 eta = dme > eta ? dme : eta;
                 eta = dmn > eta ? dmn : eta;
-                const double tj = face_tau_sq(U0 * U0 + U1 * U1 + U2 * U2, eta);   // |T_sj2|^(-eta) without the square root
+                const double tj = face_tau_tab_t<true>(U0 * U0 + U1 * U1 + U2 * U2, eta, tau_lds);   // |T_sj2|^(-eta) without the square root
                 const bool side_a = ((w >> 7) & 1) != 0;
                 const double sg = side_a ? -1.0 : 1.0;
                 double Kn[9];
@@ -636,7 +643,7 @@ int launch_gls_hex8mf(const GridView &g, const int32_t *nodes, const int32_t *de
     int64_t blocks = ((int64_t)count + 4 * NPW - 1) / (4 * NPW);
     const char *cap_env = getenv("NIN_W2_BLOCKS");   // (experiments)
     const int64_t cap2 = cap_env ? atoll(cap_env) : 512;
-    if (blocks > cap2) blocks = cap2;            // two 4-wave workgroups per CU are resident (256 registers, 74 KB of LDS each)
+    if (blocks > cap2) blocks = cap2;            // two 4-wave workgroups per CU are resident (256 registers, 79 KB of LDS each)
     if (blocks > 8) blocks &= ~(int64_t)7;
     if (getenv("NIN_DEBUG_OCCUPANCY") != nullptr) {
         int nb = -1;
