@@ -16,10 +16,12 @@
 #include "../../include/ninpol_amd.h"
 #include "device_grid.hpp"
 #include "grid_host.hpp"
+#include "hex8_desc.hpp"
 #include "launch.hpp"
 #include "mfw_desc.hpp"
 #include "mfg_desc.hpp"
 #include "mfx_desc.hpp"
+#include "quad4_desc.hpp"
 
 using namespace nin;
 
@@ -413,6 +415,143 @@ int update_points_on_device(nin_grid *g, const double *xyz, bool on_host, int cd
     ++d.geom_updates;
     return rc;
 }
+// ---- the GLS launch plan (gls_plan.hpp): the two functions that switch over the launcher family -------------------------------
+static_assert(kGlsDescHex8 == kHex8DescWords && kGlsDescQuad4 == kQuad4DescWords && kGlsDescMfw == kMfwDescWords &&
+                  kGlsDescMfx == kMfxDescWords && kGlsDescMfg == kMfgDescWords, "gls_plan.hpp's descriptor sizes are not the descriptor headers'");
+
+// the descriptors of `count` entries of a list of plan kernel k's nodes: gls_plan_row(k).desc_words words an entry
+int launch_plan_desc(const DeviceGrid &d, GlsKernel k, const int32_t *nodes, int32_t count, uint32_t *desc, hipStream_t stream) {
+    if (count <= 0) return 0;
+    switch (gls_plan_row(k).family) {
+        case GlsFamily::hex8: return launch_hex8_desc(d.v, nodes, count, reinterpret_cast<int32_t *>(desc), stream);
+        case GlsFamily::quad4: return launch_quad4_desc(d.v, nodes, count, reinterpret_cast<int32_t *>(desc), stream);
+        case GlsFamily::mfw: return launch_mfw_desc(d.v, nodes, count, desc, stream);
+        case GlsFamily::mfx: return launch_mfx_desc(d.v, nodes, count, desc, stream);
+        case GlsFamily::mfg: return launch_mfg_desc(d.v, nodes, count, desc, stream);
+        default: return 0;   // the kernel reads no descriptors
+    }
+}
+
+// plan kernel k on `count` entries of a list of its nodes and their descriptors (nodes == nullptr: the block / scratch kernels walk
+// 0 .. count - 1).  The block / scratch parameters are the plan's own list's; the work counter is the table's.
+int launch_plan_kernel(const DeviceGrid &d, GlsKernel k, const int32_t *nodes, const uint32_t *desc, int32_t count, int add_neumann,
+                       double *out, double *nws, hipStream_t stream) {
+    const GlsPlanRow r = gls_plan_row(k);
+    const DeviceGrid::GlsList &l = d.plan[k];
+    int32_t *queue = r.counter >= 0 ? d.gls_queue + r.counter : nullptr;
+    const int32_t *idesc = reinterpret_cast<const int32_t *>(desc);
+    switch (r.family) {
+        case GlsFamily::block: return launch_gls_block(d.v, nodes, count, l.waves, l.col_slots, l.lds_bytes, add_neumann, out, nws, queue, stream);
+        case GlsFamily::scratch:
+            return launch_gls_class(d.v, nodes, count, 0, l.rows_per_lane, add_neumann, out, nws, d.gls_scratch, d.gls_scratch_stride,
+                                    d.gls_scratch_slots, stream);
+        case GlsFamily::hex8: return launch_gls_hex8mf(d.v, nodes, idesc, count, add_neumann, out, nws, queue, stream);
+        case GlsFamily::mfw: return launch_gls_mfw(d.v, nodes, desc, count, r.sub, add_neumann, out, nws, queue, stream);
+        case GlsFamily::small: return launch_gls_small(d.v, nodes, count, r.sub, add_neumann, out, nws, stream);
+        case GlsFamily::quad4: return launch_gls_quad4(d.v, nodes, idesc, count, add_neumann, out, nws, stream);
+        case GlsFamily::mfx: return launch_gls_mfx(d.v, nodes, desc, count, r.sub, add_neumann, out, nws, queue, stream);
+        case GlsFamily::mfg: return launch_gls_mfg(d.v, nodes, desc, count, add_neumann, out, nws, queue, d.mfg_tiles, d.mfg_slots, stream);
+    }
+    return NIN_EINVAL;
+}
+
+// nin_grid_to_device's launch plan: the nodes binned by kernel (classified on the device), every list with its descriptors and its
+// cuts for interpolate()'s pipeline
+int build_gls_plan(nin_grid *g) {
+    DeviceGrid &d = g->d;
+    const int64_t P = g->h.n_points;
+    int rc;
+    g->node_class.assign((size_t)P, 0);
+    // debugging switches: keep nodes away from a kernel (gls_plan.hpp: GlsRoute)
+    auto unless = [](const char *name, int bit) { return getenv(name) == nullptr ? bit : 0; };
+    const int use_group = unless("NIN_GLS_NO_GROUP", kRouteHex8) | unless("NIN_GLS_NO_MFW", kRouteMfw) |
+                          unless("NIN_GLS_NO_MFW_GENERAL", kRouteMfwGeneral) | unless("NIN_GLS_NO_SMALL", kRouteSmall) |
+                          unless("NIN_GLS_NO_QUAD4", kRouteQuad4) | unless("NIN_GLS_NO_MFX", kRouteMfx) |
+                          unless("NIN_GLS_NO_MFX_7X12", kRouteMfx7x12) | unless("NIN_GLS_NO_MFX_SMALL", kRouteMfxSmall) |
+                          unless("NIN_GLS_NO_MFG", kRouteMfg) | (getenv("NIN_GLS_MFX_NO_BOUNDARY") != nullptr ? kRouteMfxNoBoundary : 0) |
+                          unless("NIN_GLS_MFW_GENERAL", kRouteMfxTakesGeneral);
+    const bool force_global = getenv("NIN_GLS_FORCE_GLOBAL") != nullptr;   // testing switch: systems in global scratch
+    int64_t need_max[kGlsClasses] = {0}, rows_max[kGlsClasses] = {0}, cols_max[kGlsClasses] = {0};
+    {
+        uint8_t *dcls = nullptr;
+        unsigned long long *dmax = nullptr, hmax[3 * kGlsClasses];
+        HIP_TRY(hipMalloc((void **)&dcls, (size_t)P));
+        if (hipMalloc((void **)&dmax, sizeof hmax) != hipSuccess) { (void)hipFree(dcls); return fail(NIN_ENOMEM, "hipMalloc"); }
+        hipError_t e1 = hipMemset(dmax, 0, sizeof hmax);
+        const int lrc = launch_classify(d.v, use_group, force_global, dcls, dmax, nullptr);
+        if (e1 == hipSuccess) e1 = hipMemcpy(g->node_class.data(), dcls, (size_t)P, hipMemcpyDeviceToHost);
+        if (e1 == hipSuccess) e1 = hipMemcpy(hmax, dmax, sizeof hmax, hipMemcpyDeviceToHost);
+        (void)hipFree(dcls); (void)hipFree(dmax);
+        if (lrc || e1 != hipSuccess) return fail(NIN_EHIP, "node classification: %s", hipGetErrorString(e1));
+        for (int c = 0; c < kGlsClasses; ++c) { need_max[c] = (int64_t)hmax[3 * c]; rows_max[c] = (int64_t)hmax[3 * c + 1]; cols_max[c] = (int64_t)hmax[3 * c + 2]; }
+    }
+    std::vector<int32_t> lists[kGlsPlanKernels];
+    {
+        int8_t kernel_of[256];
+        for (int c = 0; c < 256; ++c) kernel_of[c] = (int8_t)gls_class_kernel(c);
+        for (int64_t p = 0; p < P; ++p) {
+            const int k = kernel_of[g->node_class[p]];
+            if (k < 0) return fail(NIN_EHIP, "node classification: class byte %d belongs to no kernel", (int)g->node_class[p]);
+            lists[k].push_back((int32_t)p);
+        }
+        // every node the cube-node kernel does not take, ascending: what the fused apply leaves to the list kernel
+        std::vector<int32_t> rest;
+        rest.reserve((size_t)P - lists[gk::hex8].size());
+        for (int64_t p = 0; p < P; ++p)
+            if (g->node_class[p] != gls_class_byte(gk::hex8)) rest.push_back((int32_t)p);
+        d.noncube_count = (int32_t)rest.size();
+        const int32_t *lp = nullptr;
+        if (d.noncube_count && (rc = dev_upload(d, &lp, rest))) return rc;
+        d.noncube_nodes = lp;
+        d.noncube_nodes_ready = true;
+    }
+    for (int c = 0; c < kGlsClasses; ++c) {   // the block kernel's classes and the scratch class: plan kernels 0 .. kGlsClasses - 1
+        auto &k = d.plan[c];
+        k.lds_bytes = c == kGlsClasses - 1 ? 0 : (int32_t)need_max[c];
+        k.rows_per_lane = (int32_t)std::max<int64_t>(1, (rows_max[c] + 63) / 64);
+        k.waves = gls_class_waves(c);
+        k.col_slots = (int32_t)std::max<int64_t>(1, (cols_max[c] + 63) / 64);
+    }
+    // interpolate()'s pipeline: its pieces' node boundaries (multiples of 64 nodes)
+    constexpr int K = DeviceGrid::kE2eChunks;
+    for (int j = 0; j <= K; ++j) d.chunk_node[j] = j == K ? (int32_t)P : (int32_t)((P * j / K) & ~(int64_t)63);
+    // (NIN_GLS_LOCALITY_ORDER: "s<rows>" = strips of that many mesh rows, the default s16; "m" = Morton order; "off" = node order)
+    const char *lo_env = getenv("NIN_GLS_LOCALITY_ORDER");
+    const bool locality = !(lo_env && (lo_env[0] == 'o' || lo_env[0] == '0'));
+    for (int k = 0; k < kGlsPlanKernels; ++k) {
+        auto &l = d.plan[k];
+        l.count = (int32_t)lists[k].size();
+        // where the pieces' boundaries fall in the list (ascending here on the host; a list in locality order on the device is
+        // permuted inside the pieces only)
+        for (int j = 0; j <= K; ++j) l.chunk_off[j] = (int32_t)(std::lower_bound(lists[k].begin(), lists[k].end(), d.chunk_node[j]) - lists[k].begin());
+        if (!l.count) continue;
+        const int32_t *lp = nullptr;
+        if ((rc = dev_upload(d, &lp, lists[k]))) return rc;
+        l.nodes = const_cast<int32_t *>(lp);
+        if (k == gk::hex8 && locality && (rc = locality_order(d, l.nodes, l.count, d.chunk_node))) return rc;
+        if (const int words = gls_plan_row(k).desc_words) {   // one record per list entry
+            if ((rc = dev_alloc(d, &l.desc, (size_t)l.count * words))) return rc;
+            if (launch_plan_desc(d, GlsKernel(k), l.nodes, l.count, l.desc, nullptr)) return fail(NIN_EHIP, "descriptor kernel of plan kernel %d", k);
+        }
+    }
+    if (d.plan[gk::mfg_tiles].count) {   // one slot of tiles per resident wavefront
+        d.mfg_slots = std::min<int32_t>(d.plan[gk::mfg_tiles].count, kMfgResidentWaves);
+        if ((rc = dev_alloc(d, &d.mfg_tiles, (size_t)d.mfg_slots * kMfgSlotDoubles))) return rc;
+    }
+    d.gls_too_large = rows_max[gk::scratch] > 1024;
+    if ((rc = dev_alloc(d, &d.gls_queue, (size_t)kGlsQueueInts))) return rc;
+    if (d.plan[gk::scratch].count) {
+        d.gls_scratch_slots = std::min<int32_t>(d.plan[gk::scratch].count, 512);   // one per resident team (kernels_gls.hip)
+        d.gls_scratch_stride = need_max[gk::scratch] / 8;
+        if ((rc = dev_alloc(d, &d.gls_scratch, (size_t)d.gls_scratch_slots * d.gls_scratch_stride))) return rc;
+    }
+    const char *mn = getenv("NIN_E2E_MIN_NODES");                                // (tests: the pipeline on small meshes too)
+    d.chunkable = P >= (mn ? atoll(mn) : 64 * 1024) && P >= 64 * K && getenv("NIN_E2E_NO_PIPELINE") == nullptr;   // small meshes: one piece
+    // a single class holding every node in order needs no list: the kernel walks 0..P-1 directly
+    for (int c = 0; c < kGlsClasses; ++c)
+        if (d.plan[c].count == P) { d.plan[c].nodes = nullptr; d.chunkable = false; }
+    return NIN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -647,174 +786,7 @@ int nin_grid_to_device(nin_grid *g, int device) {
         if (launch_pad_centroids(v.centroids, E, c4, nullptr)) return fail(NIN_EHIP, "centroid padding kernel");
         v.centroids4 = c4;
     }
-    // ---- GLS launch plan: bin nodes by the size of their least-squares system (classified on the device) ----
-    g->node_class.assign((size_t)P, 0);
-    std::vector<std::vector<int32_t>> lists(kGlsClasses);
-    std::vector<int32_t> hex8_list, mfw_list[3], small_list[3], quad4_list, mfx_list[DeviceGrid::kMfxLists], mfg_list;
-    // debugging switches: keep nodes away from the hex8 kernel (bit 0) / the one-wavefront multifrontal kernel (bit 1)
-    const int use_group = (getenv("NIN_GLS_NO_GROUP") == nullptr ? 1 : 0) | (getenv("NIN_GLS_NO_MFW") == nullptr ? 2 : 0) |
-                          (getenv("NIN_GLS_NO_MFW_GENERAL") == nullptr ? 4 : 0) |   // (bit 2: the multifrontal kernel's general kind)
-                          (getenv("NIN_GLS_NO_SMALL") == nullptr ? 8 : 0) |         // (bit 3: the one-wavefront dense kernel for small nodes)
-                          (getenv("NIN_GLS_NO_QUAD4") == nullptr ? 16 : 0) |        // (bit 4: the two-lanes-per-node kernel for quad nodes)
-                          (getenv("NIN_GLS_NO_MFX") == nullptr ? 32 : 0) |          // (bit 5: the wide multifrontal kernel: unstructured meshes)
-                          (getenv("NIN_GLS_NO_MFX_7X12") == nullptr ? 1024 : 0) |    // (bit 10: ... its class (7, 12))
-                          (getenv("NIN_GLS_NO_MFX_SMALL") == nullptr ? 512 : 0) |    // (bit 9: ... its small class (4, 7) for interior nodes of 9 .. 14 cells)
-                          (getenv("NIN_GLS_NO_MFG") == nullptr ? 256 : 0) |          // (bit 8: the multifrontal kernel on global-memory tiles: nodes beyond the wide kernel)
-                          (getenv("NIN_GLS_MFX_NO_BOUNDARY") != nullptr ? 128 : 0) | // (bit 7: ... leaves the boundary nodes to the block kernel: round 3's route)
-                          (getenv("NIN_GLS_MFW_GENERAL") == nullptr ? 64 : 0);      // (bit 6: ... takes the general kind's nodes too -- the default
-                                                                                    //  since its dense phase runs straight-line per size class: 37 against
-                                                                                    //  38 ns a node on a Delaunay mesh, equal on the mixed mesh; NIN_GLS_MFW_GENERAL=1
-                                                                                    //  gives the nodes that fit back to kernels_gls_mfw.hip's general kind)
-    const bool force_global = getenv("NIN_GLS_FORCE_GLOBAL") != nullptr;   // testing switch: systems in global scratch
-    int64_t need_max[kGlsClasses] = {0}, rows_max[kGlsClasses] = {0}, cols_max[kGlsClasses] = {0};
-    {
-        uint8_t *dcls = nullptr;
-        unsigned long long *dmax = nullptr, hmax[3 * kGlsClasses];
-        HIP_TRY(hipMalloc((void **)&dcls, (size_t)P));
-        if (hipMalloc((void **)&dmax, sizeof hmax) != hipSuccess) { (void)hipFree(dcls); return fail(NIN_ENOMEM, "hipMalloc"); }
-        hipError_t e1 = hipMemset(dmax, 0, sizeof hmax);
-        const int lrc = launch_classify(d.v, use_group, force_global, dcls, dmax, nullptr);
-        if (e1 == hipSuccess) e1 = hipMemcpy(g->node_class.data(), dcls, (size_t)P, hipMemcpyDeviceToHost);
-        if (e1 == hipSuccess) e1 = hipMemcpy(hmax, dmax, sizeof hmax, hipMemcpyDeviceToHost);
-        (void)hipFree(dcls);
-        (void)hipFree(dmax);
-        if (lrc || e1 != hipSuccess) return fail(NIN_EHIP, "node classification: %s", hipGetErrorString(e1));
-        for (int c = 0; c < kGlsClasses; ++c) {
-            need_max[c] = (int64_t)hmax[3 * c]; rows_max[c] = (int64_t)hmax[3 * c + 1]; cols_max[c] = (int64_t)hmax[3 * c + 2];
-        }
-    }
-    for (int64_t p = 0; p < P; ++p) {
-        const uint8_t c = g->node_class[p];
-        if (c == 255) hex8_list.push_back((int32_t)p);
-        else if (c >= 252 && c <= 254) mfw_list[254 - c].push_back((int32_t)p);
-        else if (c >= 249 && c <= 251) small_list[c - 249].push_back((int32_t)p);
-        else if (c == 248) quad4_list.push_back((int32_t)p);
-        else if (c >= 243 && c <= 247) mfx_list[c - 243].push_back((int32_t)p);
-        else if (c == 242) mfx_list[5].push_back((int32_t)p);
-        else if (c == 240) mfx_list[6].push_back((int32_t)p);
-        else if (c == 239) mfx_list[7].push_back((int32_t)p);
-        else if (c == 241) mfg_list.push_back((int32_t)p);
-        else lists[c].push_back((int32_t)p);
-    }
-    for (int c = 0; c < kGlsClasses; ++c) {
-        auto &k = d.gls[c];
-        k.count = (int32_t)lists[c].size();
-        k.lds_bytes = c == kGlsClasses - 1 ? 0 : (int32_t)need_max[c];
-        k.rows_per_lane = (int32_t)std::max<int64_t>(1, (rows_max[c] + 63) / 64);
-        k.max_rows = (int32_t)rows_max[c];
-        k.max_cols = (int32_t)cols_max[c];
-        k.waves = gls_class_waves(c);
-        k.col_slots = (int32_t)std::max<int64_t>(1, (cols_max[c] + 63) / 64);
-        const int32_t *lp = nullptr;
-        if (k.count && (rc = dev_upload(d, &lp, lists[c]))) return rc;
-        k.nodes = const_cast<int32_t *>(lp);
-    }
-    {   // every node the cube-node kernel does not take, ascending: what the fused apply leaves to the list kernel
-        std::vector<int32_t> rest;
-        rest.reserve((size_t)P - hex8_list.size());
-        for (int64_t p = 0; p < P; ++p)
-            if (g->node_class[p] != 255) rest.push_back((int32_t)p);
-        d.noncube_count = (int32_t)rest.size();
-        const int32_t *lp = nullptr;
-        if (d.noncube_count && (rc = dev_upload(d, &lp, rest))) return rc;
-        d.noncube_nodes = lp;
-        d.noncube_nodes_ready = true;
-    }
-    // interpolate()'s pipeline: its pieces' node boundaries (multiples of 64 nodes)
-    {
-        constexpr int K = DeviceGrid::kE2eChunks;
-        for (int k = 0; k <= K; ++k) d.chunk_node[k] = k == K ? (int32_t)P : (int32_t)((P * k / K) & ~(int64_t)63);
-    }
-    // (NIN_GLS_LOCALITY_ORDER: "s<rows>" = strips of that many mesh rows, the default s16; "m" = Morton order; "off" = node order)
-    const char *lo_env = getenv("NIN_GLS_LOCALITY_ORDER");
-    const bool locality = !(lo_env && (lo_env[0] == 'o' || lo_env[0] == '0'));
-    {
-        d.hex8.count = (int32_t)hex8_list.size();
-        const int32_t *lp = nullptr;
-        if (d.hex8.count && (rc = dev_upload(d, &lp, hex8_list))) return rc;
-        d.hex8.nodes = const_cast<int32_t *>(lp);
-        if (d.hex8.count && locality && (rc = locality_order(d, d.hex8.nodes, d.hex8.count, d.chunk_node))) return rc;
-        if (d.hex8.count) {   // lane descriptors of the multifrontal kernel, one 16-byte record per list entry
-            if ((rc = dev_alloc(d, &d.hex8_desc, (size_t)d.hex8.count * 4))) return rc;
-            if (launch_hex8_desc(d.v, d.hex8.nodes, d.hex8.count, d.hex8_desc, nullptr)) return fail(NIN_EHIP, "hex8 descriptor kernel");
-        }
-    }
-    for (int i = 0; i < 3; ++i) {
-        d.mfw[i].count = (int32_t)mfw_list[i].size();
-        const int32_t *lp = nullptr;
-        if (d.mfw[i].count && (rc = dev_upload(d, &lp, mfw_list[i]))) return rc;
-        d.mfw[i].nodes = const_cast<int32_t *>(lp);
-        if (d.mfw[i].count) {   // descriptors of the one-wavefront multifrontal kernel, kMfwDescWords (40) words per list entry
-            if ((rc = dev_alloc(d, &d.mfw_desc[i], (size_t)d.mfw[i].count * kMfwDescWords))) return rc;
-            if (launch_mfw_desc(d.v, d.mfw[i].nodes, d.mfw[i].count, d.mfw_desc[i], nullptr)) return fail(NIN_EHIP, "mfw descriptor kernel");
-        }
-    }
-    for (int i = 0; i < DeviceGrid::kMfxLists; ++i) {
-        d.mfx[i].count = (int32_t)mfx_list[i].size();
-        const int32_t *lp = nullptr;
-        if (d.mfx[i].count && (rc = dev_upload(d, &lp, mfx_list[i]))) return rc;
-        d.mfx[i].nodes = const_cast<int32_t *>(lp);
-        if (d.mfx[i].count) {   // descriptors of the wide multifrontal kernel, kMfxDescWords (56) words per list entry
-            if ((rc = dev_alloc(d, &d.mfx_desc[i], (size_t)d.mfx[i].count * kMfxDescWords))) return rc;
-            if (launch_mfx_desc(d.v, d.mfx[i].nodes, d.mfx[i].count, d.mfx_desc[i], nullptr)) return fail(NIN_EHIP, "mfx descriptor kernel");
-        }
-    }
-    {
-        d.mfg.count = (int32_t)mfg_list.size();
-        const int32_t *lp = nullptr;
-        if (d.mfg.count && (rc = dev_upload(d, &lp, mfg_list))) return rc;
-        d.mfg.nodes = const_cast<int32_t *>(lp);
-        if (d.mfg.count) {   // descriptors, kMfgDescWords (124) words per list entry, and one slot of tiles per resident wavefront
-            if ((rc = dev_alloc(d, &d.mfg_desc, (size_t)d.mfg.count * kMfgDescWords))) return rc;
-            if (launch_mfg_desc(d.v, d.mfg.nodes, d.mfg.count, d.mfg_desc, nullptr)) return fail(NIN_EHIP, "mfg descriptor kernel");
-            d.mfg_slots = std::min<int32_t>(d.mfg.count, kMfgResidentWaves);
-            if ((rc = dev_alloc(d, &d.mfg_tiles, (size_t)d.mfg_slots * kMfgSlotDoubles))) return rc;
-        }
-    }
-    for (int i = 0; i < 3; ++i) {
-        d.small[i].count = (int32_t)small_list[i].size();
-        const int32_t *lp = nullptr;
-        if (d.small[i].count && (rc = dev_upload(d, &lp, small_list[i]))) return rc;
-        d.small[i].nodes = const_cast<int32_t *>(lp);
-    }
-    {
-        d.quad4.count = (int32_t)quad4_list.size();
-        const int32_t *lp = nullptr;
-        if (d.quad4.count && (rc = dev_upload(d, &lp, quad4_list))) return rc;
-        d.quad4.nodes = const_cast<int32_t *>(lp);
-        if (d.quad4.count) {
-            if ((rc = dev_alloc(d, &d.quad4_desc, (size_t)d.quad4.count * 2))) return rc;
-            if (launch_quad4_desc(d.v, d.quad4.nodes, d.quad4.count, d.quad4_desc, nullptr)) return fail(NIN_EHIP, "quad4 descriptor kernel");
-        }
-    }
-    d.gls_too_large = rows_max[kGlsClasses - 1] > 1024;
-    if ((rc = dev_alloc(d, &d.gls_queue, (size_t)kGlsQueueInts))) return rc;
-    if (d.gls[kGlsClasses - 1].count) {
-        d.gls_scratch_slots = std::min<int32_t>(d.gls[kGlsClasses - 1].count, 512);   // one per resident team (kernels_gls.hip)
-        d.gls_scratch_stride = need_max[kGlsClasses - 1] / 8;
-        if ((rc = dev_alloc(d, &d.gls_scratch, (size_t)d.gls_scratch_slots * d.gls_scratch_stride))) return rc;
-    }
-    // interpolate()'s pipeline: where the pieces' boundaries fall in every list (ascending here on the host; a list in locality
-    // order on the device is permuted inside the pieces only)
-    {
-        constexpr int K = DeviceGrid::kE2eChunks;
-        auto cut = [&](int li, const std::vector<int32_t> &v) {
-            for (int k = 0; k <= K; ++k)
-                d.chunk_off[li][k] = (int32_t)(std::lower_bound(v.begin(), v.end(), d.chunk_node[k]) - v.begin());
-        };
-        for (int c = 0; c < kGlsClasses; ++c) cut(c, lists[c]);
-        cut(kGlsClasses, hex8_list);
-        for (int i = 0; i < 3; ++i) cut(kGlsClasses + 1 + i, mfw_list[i]);
-        for (int i = 0; i < 3; ++i) cut(kGlsClasses + 4 + i, small_list[i]);
-        cut(kGlsClasses + 7, quad4_list);
-        for (int i = 0; i < DeviceGrid::kMfxLists; ++i) cut(kGlsClasses + 8 + i, mfx_list[i]);
-        cut(kGlsClasses + 8 + DeviceGrid::kMfxLists, mfg_list);
-        const char *mn = getenv("NIN_E2E_MIN_NODES");                                // (tests: the pipeline on small meshes too)
-        d.chunkable = P >= (mn ? atoll(mn) : 64 * 1024) && P >= 64 * K && getenv("NIN_E2E_NO_PIPELINE") == nullptr;   // small meshes: one piece
-    }
-    // a single class holding every node in order needs no list: the kernel walks 0..P-1 directly
-    for (int c = 0; c < kGlsClasses; ++c)
-        if (d.gls[c].count == P) { d.gls[c].nodes = nullptr; d.chunkable = false; }
+    if ((rc = build_gls_plan(g))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return NIN_OK;
 }
@@ -844,35 +816,37 @@ int nin_fields_set(nin_grid *g, const double *permeability, const double *diff_m
     return NIN_OK;
 }
 
-// cube nodes: the multifrontal kernel
-static int launch_hex8(DeviceGrid &d, const int32_t *nodes, const int32_t *desc, int32_t count, int add_neumann,
-                       double *out, double *nws, hipStream_t stream) {
-    return launch_gls_hex8mf(d.v, nodes, desc, count, add_neumann, out, nws, d.gls_queue + kGlsQueueHex8, stream);
+// ---- one launch of the plan: every walk over its kernels goes through the two arrays below ---------------------------------------
+// The long poles first, on the side stream when it is on (a node on global-memory tiles takes ~0.5 ms, one of the global-scratch class ~2 ms,
+// on a wavefront of its own); then kMainOrder, where the two come up again for a launch whose side stream did not take them.
+static constexpr GlsKernel kSideOrder[] = {gk::mfg_tiles, gk::scratch};
+static constexpr GlsKernel kMainOrder[] = {gk::hex8,     gk::mfw_large, gk::mfw_small, gk::mfw_general, gk::small4,       gk::small8,
+                                           gk::small12,  gk::quad4,     gk::mfx_6x10,  gk::mfx_7x11,    gk::mfx_8x13,     gk::mfx_9x15,
+                                           gk::mfx_10x16, gk::mfx_boundary, gk::mfx_4x7, gk::mfx_7x12,  gk::mfg_tiles,    gk::block1,
+                                           gk::block2,   gk::block4,    gk::block8,    gk::scratch};
+static constexpr bool main_order_is_complete() {
+    unsigned seen = 0;
+    for (GlsKernel k : kMainOrder) seen |= 1u << k;
+    return sizeof kMainOrder / sizeof kMainOrder[0] == kGlsPlanKernels && seen == (1u << kGlsPlanKernels) - 1;
+}
+static_assert(main_order_is_complete(), "kMainOrder must name every kernel of the plan once");
+static bool on_side_stream(GlsKernel k) { return std::find(std::begin(kSideOrder), std::end(kSideOrder), k) != std::end(kSideOrder); }
+
+// the entries of plan kernel k's list that lie in piece `piece` of interpolate()'s pipeline (piece < 0: the whole list)
+struct PlanRange { const int32_t *nodes; const uint32_t *desc; int32_t count; };
+static PlanRange plan_range(const DeviceGrid &d, GlsKernel k, int piece) {
+    const auto &l = d.plan[k];
+    const int32_t b = piece < 0 ? 0 : l.chunk_off[piece], n = (piece < 0 ? l.count : l.chunk_off[piece + 1]) - b;
+    return {l.nodes ? l.nodes + b : nullptr, l.desc ? l.desc + (size_t)gls_plan_row(k).desc_words * b : nullptr, n};
 }
 
-// the one-wavefront multifrontal kernel, kind 0 / 1 / 2 (work counters: kGlsQueueMfw + kind)
-static int launch_mfw(DeviceGrid &d, const int32_t *nodes, const uint32_t *desc, int32_t count, int kind, int add_neumann,
-                      double *out, double *nws, hipStream_t stream) {
-    return launch_gls_mfw(d.v, nodes, desc, count, kind, add_neumann, out, nws, d.gls_queue + kGlsQueueMfw + kind, stream);
-}
-
-// one GLS size class: the block kernel with the system in LDS, or the wave kernel on global scratch
-static int launch_class(DeviceGrid &d, int c, const int32_t *nodes, int32_t count, int add_neumann, double *out,
-                        double *nws, hipStream_t stream) {
-    const auto &k = d.gls[c];
-    if (c < kGlsClasses - 1)   // work counter: kGlsQueueBlock + c (device_grid.hpp)
-        return launch_gls_block(d.v, nodes, count, k.waves, k.col_slots, k.lds_bytes, add_neumann, out, nws,
-                                d.gls_queue + kGlsQueueBlock + c, stream);
-    return launch_gls_class(d.v, nodes, count, 0, k.rows_per_lane, add_neumann, out, nws, d.gls_scratch,
-                            d.gls_scratch_stride, d.gls_scratch_slots, stream);
-}
-
-// The long poles first, on the side stream: entries [b, b + n) of the global-scratch class's list and [bg, bg + ng) of kernels_gls_mfg.hip's
-// (a node on global-memory tiles takes ~0.5 ms on a wavefront of its own).  Ordered behind everything enqueued on `stream` so far (the
-// zeroed work counters, the caller's buffers) and joined by gls_side_end.  NIN_GLS_NO_SIDE_STREAM=1: off.
-static int gls_side_begin(DeviceGrid &d, int add_neumann, double *out, double *nws, hipStream_t stream, int32_t b, int32_t n, int32_t bg, int32_t ng) {
+// kSideOrder's kernels on the side stream: ordered behind everything enqueued on `stream` so far (the zeroed work counters, the
+// caller's buffers) and joined by gls_side_end.  NIN_GLS_NO_SIDE_STREAM=1: off.
+static int gls_side_begin(DeviceGrid &d, int piece, int add_neumann, double *out, double *nws, hipStream_t stream) {
     d.side_pending = false;
-    if ((n <= 0 && ng <= 0) || getenv("NIN_GLS_NO_SIDE_STREAM") != nullptr) return 0;
+    bool any = false;
+    for (GlsKernel k : kSideOrder) any = any || plan_range(d, k, piece).count > 0;
+    if (!any || getenv("NIN_GLS_NO_SIDE_STREAM") != nullptr) return 0;
     if (!d.side_stream) {
         hipStream_t s = nullptr;
         hipEvent_t a = nullptr, e = nullptr;
@@ -884,13 +858,11 @@ static int gls_side_begin(DeviceGrid &d, int add_neumann, double *out, double *n
     hipStream_t side = static_cast<hipStream_t>(d.side_stream);
     if (hipEventRecord(static_cast<hipEvent_t>(d.ev_fork), stream) != hipSuccess || hipStreamWaitEvent(side, static_cast<hipEvent_t>(d.ev_fork), 0) != hipSuccess)
         return -3;
-    const auto &k = d.gls[kGlsClasses - 1];
     int rc = 0;
-    if (ng > 0)
-        rc = launch_gls_mfg(d.v, d.mfg.nodes + bg, d.mfg_desc + (size_t)kMfgDescWords * bg, ng, add_neumann, out, nws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, side);
-    if (!rc && n > 0)
-        rc = launch_gls_class(d.v, k.nodes ? k.nodes + b : nullptr, n, 0, k.rows_per_lane, add_neumann, out, nws, d.gls_scratch, d.gls_scratch_stride,
-                              d.gls_scratch_slots, side);
+    for (GlsKernel k : kSideOrder) {
+        const PlanRange r = plan_range(d, k, piece);
+        if (!rc && r.count > 0) rc = launch_plan_kernel(d, k, r.nodes, r.desc, r.count, add_neumann, out, nws, side);
+    }
     if (!rc && hipEventRecord(static_cast<hipEvent_t>(d.ev_join), side) != hipSuccess) rc = -3;
     d.side_pending = rc == 0;
     return rc;
@@ -901,31 +873,22 @@ static int gls_side_end(DeviceGrid &d, hipStream_t stream) {
     return hipStreamWaitEvent(stream, static_cast<hipEvent_t>(d.ev_join), 0) == hipSuccess ? 0 : -3;
 }
 
-// NIN_GLS_ONLY=<k>: launch only kernel k of the plan, numbered as nin_gls_plan counts them (measurement: bench.py times the
-// kernels of a plan one by one; read at every launch)
+// NIN_GLS_ONLY=<k>: launch only kernel k of the plan (a GlsKernel: numbered as nin_gls_plan counts them; measurement: bench.py times
+// the kernels of a plan one by one; read at every launch)
 static int gls_only() {
     const char *e = getenv("NIN_GLS_ONLY");
     return e && *e ? atoi(e) : -1;
 }
 
-// every GLS kernel of the launch plan but the cube-node kernel, all their nodes (the work counters are zeroed by the caller; the
-// global-scratch class is left out if gls_side_begin took it)
-static int launch_gls_but_cube(DeviceGrid &d, int add_neumann, double *out, double *nws, hipStream_t stream) {
+// The plan's kernels on the main stream for one piece of the pipeline (piece < 0: all nodes), then the join with the side stream.  The
+// work counters are zeroed by the caller; what gls_side_begin took is left out.  cube = false: without the cube-node kernel (the fused
+// apply launches its own form of it); only >= 0: that kernel alone.
+static int gls_main(DeviceGrid &d, int piece, bool cube, int only, int add_neumann, double *out, double *nws, hipStream_t stream) {
     int rc = 0;
-    const int only = gls_only();
-    auto on = [&](int k) { return only < 0 || only == k; };
-    for (int i = 0; i < 3 && !rc; ++i)
-        if (on(6 + i)) rc = launch_mfw(d, d.mfw[i].nodes, d.mfw_desc[i], d.mfw[i].count, i, add_neumann, out, nws, stream);
-    for (int i = 0; i < 3 && !rc; ++i)
-        if (on(9 + i)) rc = launch_gls_small(d.v, d.small[i].nodes, d.small[i].count, i, add_neumann, out, nws, stream);
-    if (!rc && on(12)) rc = launch_gls_quad4(d.v, d.quad4.nodes, d.quad4_desc, d.quad4.count, add_neumann, out, nws, stream);
-    for (int i = 0; i < DeviceGrid::kMfxLists && !rc; ++i)   // (work counters: kGlsQueueMfx + i; lists 6 and 7 -- the small class, (7, 12) -- are kernels 20 and 21 of the plan)
-        if (on(i < 6 ? 13 + i : 14 + i)) rc = launch_gls_mfx(d.v, d.mfx[i].nodes, d.mfx_desc[i], d.mfx[i].count, i, add_neumann, out, nws, d.gls_queue + kGlsQueueMfx + i, stream);
-    if (!rc && on(19) && !d.side_pending)   // (work counter: kGlsQueueMfg, off the cube-node kernel's lines)
-        rc = launch_gls_mfg(d.v, d.mfg.nodes, d.mfg_desc, d.mfg.count, add_neumann, out, nws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, stream);
-    for (int c = 0; c < kGlsClasses && !rc; ++c) {
-        if ((c == kGlsClasses - 1 && d.side_pending) || !on(c)) continue;
-        rc = launch_class(d, c, d.gls[c].nodes, d.gls[c].count, add_neumann, out, nws, stream);
+    for (GlsKernel k : kMainOrder) {
+        if ((k == gk::hex8 && !cube) || (only >= 0 && only != k) || (d.side_pending && on_side_stream(k))) continue;
+        const PlanRange r = plan_range(d, k, piece);
+        if (!rc && r.count > 0) rc = launch_plan_kernel(d, k, r.nodes, r.desc, r.count, add_neumann, out, nws, stream);
     }
     if (!rc) rc = gls_side_end(d, stream);
     return rc;
@@ -954,10 +917,8 @@ int nin_weights_device(nin_grid *g, int method, const int64_t *targets, int64_t 
         else {
             HIP_TRY(hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream));   // the launches' work counters
             const int only = gls_only();
-            if (only < 0) rc = gls_side_begin(d, add_neumann, dev_csr_data, dev_neumann_ws, stream, 0, d.gls[kGlsClasses - 1].count, 0, d.mfg.count);
-            if (!rc && (only < 0 || only == 5))
-                rc = launch_hex8(d, d.hex8.nodes, d.hex8_desc, d.hex8.count, add_neumann, dev_csr_data, dev_neumann_ws, stream);
-            if (!rc) rc = launch_gls_but_cube(d, add_neumann, dev_csr_data, dev_neumann_ws, stream);
+            if (only < 0) rc = gls_side_begin(d, -1, add_neumann, dev_csr_data, dev_neumann_ws, stream);
+            if (!rc) rc = gls_main(d, -1, true, only, add_neumann, dev_csr_data, dev_neumann_ws, stream);
         }
         if (rc) return fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
         return NIN_OK;
@@ -968,88 +929,40 @@ int nin_weights_device(nin_grid *g, int method, const int64_t *targets, int64_t 
     HIP_TRY(hipMemsetAsync(dev_csr_data, 0, (size_t)d.nnz_e * 8, stream));
     HIP_TRY(hipMemsetAsync(dev_neumann_ws, 0, (size_t)P * 8, stream));
     if (n_targets == 0) return NIN_OK;
-    std::vector<std::vector<int32_t>> lists(method == NIN_METHOD_GLS ? kGlsClasses + 8 + DeviceGrid::kMfxLists + 1 : 1);
-    for (int64_t i = 0; i < n_targets; ++i) {
-        int c = method == NIN_METHOD_GLS ? g->node_class[targets[i]] : 0;
-        if (c == 255) c = kGlsClasses;   // the hex8 kernel's class
-        else if (c >= 252 && c <= 254) c = kGlsClasses + 1 + (254 - c);   // the one-wavefront multifrontal kernel, kind 0 / 1 / 2
-        else if (c >= 249 && c <= 251) c = kGlsClasses + 4 + (c - 249);   // the small-node kernel, kind 0 / 1 / 2
-        else if (c == 248) c = kGlsClasses + 7;                           // the quad-node kernel
-        else if (c >= 243 && c <= 247) c = kGlsClasses + 8 + (c - 243);   // the wide multifrontal kernel, by size class
-        else if (c == 242) c = kGlsClasses + 8 + 5;                       // ... its boundary nodes
-        else if (c == 240) c = kGlsClasses + 8 + 6;                       // ... its small interior class
-        else if (c == 239) c = kGlsClasses + 8 + 7;                       // ... its class (7, 12)
-        else if (c == 241) c = kGlsClasses + 8 + DeviceGrid::kMfxLists;   // the multifrontal kernel on global-memory tiles
-        lists[c].push_back((int32_t)targets[i]);
-    }
-    // one device buffer for all class lists, filled before the first launch: a per-class allocate / copy / free
+    const bool gls = method == NIN_METHOD_GLS;
+    std::vector<int32_t> lists[kGlsPlanKernels];   // the targets by plan kernel (IDW / LS: all in the first)
+    for (int64_t i = 0; i < n_targets; ++i) lists[gls ? gls_class_kernel(g->node_class[targets[i]]) : 0].push_back((int32_t)targets[i]);
+    // one device buffer for all lists and their descriptors, filled before the first launch: a per-list allocate / copy / free
     // cycle lets the allocator hand the same memory to the next list while the previous kernel still reads it
-    // (the pageable copy is not ordered behind that kernel)
+    // (the pageable copy is not ordered behind that kernel).  One descriptor launch per non-empty list, not per family: a few tiny launches more
     std::vector<int32_t> flat;
-    std::vector<size_t> first(lists.size() + 1, 0);
-    for (size_t c = 0; c < lists.size(); ++c) {
-        first[c] = flat.size();
-        flat.insert(flat.end(), lists[c].begin(), lists[c].end());
+    size_t first[kGlsPlanKernels], desc_first[kGlsPlanKernels], words = 0;   // where a list begins; where its descriptors begin, behind the lists
+    for (int k = 0; k < kGlsPlanKernels; ++k) {
+        first[k] = flat.size();
+        desc_first[k] = words;
+        flat.insert(flat.end(), lists[k].begin(), lists[k].end());
+        if (gls) words += lists[k].size() * (size_t)gls_plan_row(k).desc_words;
     }
-    first[lists.size()] = flat.size();
     int32_t *dl0 = nullptr;
-    const size_t n_hex8 = method == NIN_METHOD_GLS ? lists[kGlsClasses].size() : 0;   // + 4 descriptor words per cube node
-    const size_t n_mfw = method == NIN_METHOD_GLS ? lists[kGlsClasses + 1].size() + lists[kGlsClasses + 2].size() + lists[kGlsClasses + 3].size() : 0;   // + kMfwDescWords per node of the multifrontal kernel (the three lists are adjacent)
-    const size_t n_quad4 = method == NIN_METHOD_GLS ? lists[kGlsClasses + 7].size() : 0;   // + 2 descriptor words per quad node
-    size_t n_mfx = 0;                                                                      // + kMfxDescWords per node of the wide multifrontal kernel (its lists are adjacent)
-    if (method == NIN_METHOD_GLS)
-        for (int i = 0; i < DeviceGrid::kMfxLists; ++i) n_mfx += lists[kGlsClasses + 8 + i].size();
-    const size_t n_mfg = method == NIN_METHOD_GLS ? lists[kGlsClasses + 8 + DeviceGrid::kMfxLists].size() : 0;   // + kMfgDescWords per node of kernels_gls_mfg.hip
-    HIP_TRY(hipMalloc((void **)&dl0, (flat.size() + 4 * n_hex8 + kMfwDescWords * n_mfw + 2 * n_quad4 + kMfxDescWords * n_mfx + kMfgDescWords * n_mfg) * 4));
-    int32_t *ddesc = dl0 + flat.size();
-    uint32_t *dmfw = reinterpret_cast<uint32_t *>(ddesc + 4 * n_hex8);
-    int32_t *dquad = reinterpret_cast<int32_t *>(dmfw + kMfwDescWords * n_mfw);
-    uint32_t *dmfx = reinterpret_cast<uint32_t *>(dquad + 2 * n_quad4);
-    uint32_t *dmfg = dmfx + kMfxDescWords * n_mfx;
-    const hipError_t cp = hipMemcpy(dl0, flat.data(), flat.size() * 4, hipMemcpyHostToDevice);
-    if (cp != hipSuccess) { (void)hipFree(dl0); return fail(NIN_EHIP, "hipMemcpy: %s", hipGetErrorString(cp)); }
-    if (n_hex8 && launch_hex8_desc(d.v, dl0 + first[kGlsClasses], (int32_t)n_hex8, ddesc, stream)) {
-        (void)hipFree(dl0);
-        return fail(NIN_EHIP, "hex8 descriptor kernel");
-    }
-    if (n_mfw && launch_mfw_desc(d.v, dl0 + first[kGlsClasses + 1], (int32_t)n_mfw, dmfw, stream)) {
-        (void)hipFree(dl0);
-        return fail(NIN_EHIP, "mfw descriptor kernel");
-    }
-    if (n_quad4 && launch_quad4_desc(d.v, dl0 + first[kGlsClasses + 7], (int32_t)n_quad4, dquad, stream)) {
-        (void)hipFree(dl0);
-        return fail(NIN_EHIP, "quad4 descriptor kernel");
-    }
-    if (n_mfx && launch_mfx_desc(d.v, dl0 + first[kGlsClasses + 8], (int32_t)n_mfx, dmfx, stream)) {
-        (void)hipFree(dl0);
-        return fail(NIN_EHIP, "mfx descriptor kernel");
-    }
-    if (n_mfg && launch_mfg_desc(d.v, dl0 + first[kGlsClasses + 8 + DeviceGrid::kMfxLists], (int32_t)n_mfg, dmfg, stream)) {
-        (void)hipFree(dl0);
-        return fail(NIN_EHIP, "mfg descriptor kernel");
-    }
-    if (method == NIN_METHOD_GLS) {
-        const hipError_t qe = hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream);
-        if (qe != hipSuccess) { (void)hipFree(dl0); return fail(NIN_EHIP, "hipMemsetAsync: %s", hipGetErrorString(qe)); }
-    }
-    for (size_t c = 0; c < lists.size() && !rc; ++c) {
-        if (lists[c].empty()) continue;
-        const int32_t *dl = dl0 + first[c];
-        const int32_t cnt = (int32_t)lists[c].size();
-        if (method == NIN_METHOD_IDW) rc = launch_idw(d.v, dl, cnt, 0, 0, dev_csr_data, dev_neumann_ws, stream);
-        else if (method == NIN_METHOD_LS) rc = launch_ls(d.v, dl, cnt, 0, 0, dev_csr_data, dev_neumann_ws, stream);
-        else if ((int)c == kGlsClasses) rc = launch_hex8(d, dl, ddesc, cnt, add_neumann, dev_csr_data, dev_neumann_ws, stream);
-        else if ((int)c == kGlsClasses + 8 + DeviceGrid::kMfxLists)
-            rc = launch_gls_mfg(d.v, dl, dmfg, cnt, add_neumann, dev_csr_data, dev_neumann_ws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, stream);
-        else if ((int)c >= kGlsClasses + 8)
-            rc = launch_gls_mfx(d.v, dl, dmfx + kMfxDescWords * (first[c] - first[kGlsClasses + 8]), cnt, (int)c - kGlsClasses - 8, add_neumann, dev_csr_data,
-                                dev_neumann_ws, d.gls_queue + kGlsQueueMfx + ((int)c - kGlsClasses - 8), stream);
-        else if ((int)c == kGlsClasses + 7) rc = launch_gls_quad4(d.v, dl, dquad, cnt, add_neumann, dev_csr_data, dev_neumann_ws, stream);
-        else if ((int)c >= kGlsClasses + 4) rc = launch_gls_small(d.v, dl, cnt, (int)c - kGlsClasses - 4, add_neumann, dev_csr_data, dev_neumann_ws, stream);
-        else if ((int)c > kGlsClasses)
-            rc = launch_mfw(d, dl, dmfw + kMfwDescWords * (first[c] - first[kGlsClasses + 1]), cnt, (int)c - kGlsClasses - 1, add_neumann,
-                            dev_csr_data, dev_neumann_ws, stream);
-        else rc = launch_class(d, (int)c, dl, cnt, add_neumann, dev_csr_data, dev_neumann_ws, stream);
+    HIP_TRY(hipMalloc((void **)&dl0, (flat.size() + words) * 4));
+    hipError_t e = hipMemcpy(dl0, flat.data(), flat.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dl0); return fail(NIN_EHIP, "hipMemcpy: %s", hipGetErrorString(e)); }
+    uint32_t *ddesc = reinterpret_cast<uint32_t *>(dl0 + flat.size());
+    if (!gls) {
+        rc = method == NIN_METHOD_IDW ? launch_idw(d.v, dl0, (int32_t)flat.size(), 0, 0, dev_csr_data, dev_neumann_ws, stream)
+                                      : launch_ls(d.v, dl0, (int32_t)flat.size(), 0, 0, dev_csr_data, dev_neumann_ws, stream);
+    } else {
+        for (int k = 0; k < kGlsPlanKernels; ++k)
+            if (launch_plan_desc(d, GlsKernel(k), dl0 + first[k], (int32_t)lists[k].size(), ddesc + desc_first[k], stream)) {
+                (void)hipFree(dl0);
+                return fail(NIN_EHIP, "descriptor kernel of plan kernel %d", k);
+            }
+        e = hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream);
+        if (e != hipSuccess) { (void)hipFree(dl0); return fail(NIN_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e)); }
+        for (GlsKernel k : kMainOrder)   // (no side stream: every target's row is written by exactly one kernel, in any order)
+            if (!rc && !lists[k].empty())
+                rc = launch_plan_kernel(d, k, dl0 + first[k], ddesc + desc_first[k], (int32_t)lists[k].size(),
+                                        add_neumann, dev_csr_data, dev_neumann_ws, stream);
     }
     const hipError_t sy = hipStreamSynchronize(stream);   // the lists must outlive the kernels
     (void)hipFree(dl0);
@@ -1181,46 +1094,8 @@ int weights_chunk(nin_grid *g, int method, int k, double *out, double *nws, hipS
         return launch_rows_range(d.v, method == NIN_METHOD_LS ? 1 : 0, P, d.chunk_node[k], d.chunk_node[k + 1],
                                  (int32_t)g->h.mx_elems_per_point, d.nnz_e, out, nws, stream);
     HIP_TRY(hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream));   // the launches' work counters
-    constexpr int lg = kGlsClasses + 8 + DeviceGrid::kMfxLists;   // kernels_gls_mfg.hip's list
-    int rc = gls_side_begin(d, 1, out, nws, stream, d.chunk_off[kGlsClasses - 1][k],
-                            d.chunk_off[kGlsClasses - 1][k + 1] - d.chunk_off[kGlsClasses - 1][k], d.chunk_off[lg][k], d.chunk_off[lg][k + 1] - d.chunk_off[lg][k]);
-    {
-        const int32_t b = d.chunk_off[kGlsClasses][k], n = d.chunk_off[kGlsClasses][k + 1] - b;
-        if (!rc && n > 0) rc = launch_gls_hex8mf(d.v, d.hex8.nodes + b, d.hex8_desc + 4 * (size_t)b, n, 1, out, nws, d.gls_queue + kGlsQueueHex8, stream);
-    }
-    for (int i = 0; i < 3 && !rc; ++i) {
-        const int32_t b = d.chunk_off[kGlsClasses + 1 + i][k], n = d.chunk_off[kGlsClasses + 1 + i][k + 1] - b;
-        if (n > 0) rc = launch_gls_mfw(d.v, d.mfw[i].nodes + b, d.mfw_desc[i] + (size_t)kMfwDescWords * b, n, i, 1, out, nws,
-                                       d.gls_queue + kGlsQueueMfw + i, stream);
-    }
-    for (int i = 0; i < 3 && !rc; ++i) {
-        const int32_t b = d.chunk_off[kGlsClasses + 4 + i][k], n = d.chunk_off[kGlsClasses + 4 + i][k + 1] - b;
-        if (n > 0) rc = launch_gls_small(d.v, d.small[i].nodes + b, n, i, 1, out, nws, stream);
-    }
-    if (!rc) {
-        const int32_t b = d.chunk_off[kGlsClasses + 7][k], n = d.chunk_off[kGlsClasses + 7][k + 1] - b;
-        if (n > 0) rc = launch_gls_quad4(d.v, d.quad4.nodes + b, d.quad4_desc + 2 * (size_t)b, n, 1, out, nws, stream);
-    }
-    for (int i = 0; i < DeviceGrid::kMfxLists && !rc; ++i) {
-        const int32_t b = d.chunk_off[kGlsClasses + 8 + i][k], n = d.chunk_off[kGlsClasses + 8 + i][k + 1] - b;
-        if (n > 0) rc = launch_gls_mfx(d.v, d.mfx[i].nodes + b, d.mfx_desc[i] + (size_t)kMfxDescWords * b, n, i, 1, out, nws, d.gls_queue + kGlsQueueMfx + i, stream);
-    }
-    if (!rc && !d.side_pending) {
-        constexpr int li = kGlsClasses + 8 + DeviceGrid::kMfxLists;
-        const int32_t b = d.chunk_off[li][k], n = d.chunk_off[li][k + 1] - b;
-        if (n > 0) rc = launch_gls_mfg(d.v, d.mfg.nodes + b, d.mfg_desc + (size_t)kMfgDescWords * b, n, 1, out, nws, d.gls_queue + kGlsQueueMfg, d.mfg_tiles, d.mfg_slots, stream);
-    }
-    for (int c = 0; c < kGlsClasses && !rc; ++c) {
-        const int32_t b = d.chunk_off[c][k], n = d.chunk_off[c][k + 1] - b;
-        if (n <= 0) continue;
-        const auto &kc = d.gls[c];
-        if (c < kGlsClasses - 1)
-            rc = launch_gls_block(d.v, kc.nodes + b, n, kc.waves, kc.col_slots, kc.lds_bytes, 1, out, nws, d.gls_queue + kGlsQueueBlock + c, stream);
-        else if (!d.side_pending)
-            rc = launch_gls_class(d.v, kc.nodes + b, n, 0, kc.rows_per_lane, 1, out, nws, d.gls_scratch, d.gls_scratch_stride,
-                                  d.gls_scratch_slots, stream);
-    }
-    if (!rc) rc = gls_side_end(d, stream);
+    int rc = gls_side_begin(d, k, 1, out, nws, stream);
+    if (!rc) rc = gls_main(d, k, true, -1, 1, out, nws, stream);
     return rc ? fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError())) : NIN_OK;
 }
 
@@ -1378,15 +1253,16 @@ int nin_apply_device(nin_grid *g, int method, const double *dev_u_cells, int32_t
     }
     // GLS on a mesh with cube nodes: the cube-node kernel forms W . u itself (the 64 bytes of a node's row are neither written
     // nor read again); the other kernels write their rows as always and a list kernel applies those (NIN_APPLY_NO_FUSION: off)
-    if (method == NIN_METHOD_GLS && d.hex8.count > 0 && d.noncube_nodes_ready && getenv("NIN_APPLY_NO_FUSION") == nullptr) {
+    const DeviceGrid::GlsList &cube = d.plan[gk::hex8];
+    if (method == NIN_METHOD_GLS && cube.count > 0 && d.noncube_nodes_ready && getenv("NIN_APPLY_NO_FUSION") == nullptr) {
         if (!d.fields_set) return fail(NIN_ESTATE, "nin_fields_set has not been called");
         if (!d.have_perm) return fail(NIN_ESTATE, "GLS needs permeability and diff_mag");
         if (d.gls_too_large) return fail(NIN_ERANGE, "a node's GLS system has more than 1024 rows: beyond the fallback kernel");
         HIP_TRY(hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream));
-        int rc = gls_side_begin(d, 1, d.apply_weights, dev_neumann_ws, stream, 0, d.gls[kGlsClasses - 1].count, 0, d.mfg.count);
-        if (!rc) rc = launch_gls_hex8mf_apply(d.v, d.hex8.nodes, d.hex8_desc, d.hex8.count, 1, dev_u_cells, n_fields, dev_node_values,
-                                              dev_neumann_ws, d.gls_queue + kGlsQueueHex8, stream);
-        if (!rc) rc = launch_gls_but_cube(d, 1, d.apply_weights, dev_neumann_ws, stream);
+        int rc = gls_side_begin(d, -1, 1, d.apply_weights, dev_neumann_ws, stream);
+        if (!rc) rc = launch_gls_hex8mf_apply(d.v, cube.nodes, reinterpret_cast<const int32_t *>(cube.desc), cube.count, 1, dev_u_cells, n_fields,
+                                              dev_node_values, dev_neumann_ws, d.gls_queue + gls_plan_row(gk::hex8).counter, stream);
+        if (!rc) rc = gls_main(d, -1, false, gls_only(), 1, d.apply_weights, dev_neumann_ws, stream);
         if (!rc) rc = launch_apply_list(d.v, d.apply_weights, dev_u_cells, n_fields, dev_node_values, d.noncube_nodes, d.noncube_count, stream);
         if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
         return NIN_OK;
@@ -1565,27 +1441,24 @@ int nin_gls_plan_flops(nin_grid *g, double alg[22], double ref[22], int64_t comp
     if (!d.fields_set || !d.flag_staging) return fail(NIN_ESTATE, "nin_fields_set has not been called (the Neumann flags decide which boundary nodes are computed)");
     if (h.ensure(A_ESUP_PTR | A_ESUP | A_FSUP_PTR | A_FSUP | A_ESUF)) return fail(NIN_EHIP, "mirroring the connectivity failed");
     HIP_TRY(hipSetDevice(d.device));
-    for (int k = 0; k < 22; ++k) { alg[k] = ref[k] = 0.0; computed[k] = 0; }
+    for (int k = 0; k < kGlsPlanKernels; ++k) { alg[k] = ref[k] = 0.0; computed[k] = 0; }
     const int64_t P = h.n_points;
-    // (F, D, free faces) of the nodes of the multifrontal kernels: from their descriptors
+    // (F, D, free faces) of the nodes of the multifrontal kernels: the low 24 bits of the descriptor word the plan's table names
     std::vector<uint32_t> fdq((size_t)P, 0u);
-    auto read_desc = [&](const int32_t *nodes, const uint32_t *desc, int32_t count, int words, int word) -> int {
-        if (count <= 0) return 0;
-        std::vector<int32_t> hn((size_t)count);
-        std::vector<uint32_t> hd((size_t)count * words);
-        if (hipMemcpy(hn.data(), nodes, (size_t)count * 4, hipMemcpyDeviceToHost) != hipSuccess) return -3;
-        if (hipMemcpy(hd.data(), desc, hd.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -3;
-        for (int32_t i = 0; i < count; ++i) fdq[hn[i]] = hd[(size_t)i * words + word] & 0xFFFFFFu;   // (F, D, free faces: the low 24 bits of either kind's word)
-        return 0;
-    };
-    for (int i = 0; i < 3; ++i)
-        if (read_desc(d.mfw[i].nodes, d.mfw_desc[i], d.mfw[i].count, kMfwDescWords, 24)) return fail(NIN_EHIP, "reading the descriptors back failed");
-    for (int i = 0; i < DeviceGrid::kMfxLists; ++i)
-        if (read_desc(d.mfx[i].nodes, d.mfx_desc[i], d.mfx[i].count, kMfxDescWords, 0)) return fail(NIN_EHIP, "reading the descriptors back failed");
-    if (read_desc(d.mfg.nodes, d.mfg_desc, d.mfg.count, kMfgDescWords, 0)) return fail(NIN_EHIP, "reading the descriptors back failed");
+    for (int k = 0; k < kGlsPlanKernels; ++k) {
+        const GlsPlanRow row = gls_plan_row(k);
+        const auto &l = d.plan[k];
+        if (row.fdq_word < 0 || l.count <= 0) continue;
+        std::vector<int32_t> hn((size_t)l.count);
+        std::vector<uint32_t> hd((size_t)l.count * row.desc_words);
+        if (hipMemcpy(hn.data(), l.nodes, hn.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hd.data(), l.desc, hd.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(NIN_EHIP, "reading the descriptors back failed");
+        for (int32_t i = 0; i < l.count; ++i) fdq[hn[i]] = hd[(size_t)i * row.desc_words + row.fdq_word] & 0xFFFFFFu;
+    }
     for (int64_t p = 0; p < P; ++p) {
-        const int c = g->node_class[p];
-        const int k = c == 255 ? 5 : (c >= 252 && c <= 254) ? 6 + (254 - c) : (c >= 249 && c <= 251) ? 9 + (c - 249) : c == 248 ? 12 : (c >= 243 && c <= 247) ? 13 + (c - 243) : c == 242 ? 18 : c == 241 ? 19 : c == 240 ? 20 : c == 239 ? 21 : c;
+        const int k = gls_class_kernel(g->node_class[p]);
+        const GlsPlanRow row = gls_plan_row(k);
         const int fl = d.flag_staging[p];
         if ((fl & 1) && !(fl & 2)) continue;                   // a Dirichlet boundary node: the zero row, nothing computed (gls.pyx:165-166)
         const int64_t eb = h.esup_ptr[p], ne = h.esup_ptr[p + 1] - eb, fb = h.fsup_ptr[p], nf = h.fsup_ptr[p + 1] - fb;
@@ -1599,14 +1472,14 @@ int nin_gls_plan_flops(nin_grid *g, double alg[22], double ref[22], int64_t comp
         if (n_if == 0 || m < 3 * ne) continue;                 // outside the parity set: the zero row
         ++computed[k];
         ref[k] += dgels_flops((double)(ne + 3 * nf + n_nb), (double)(3 * ne + 1), (double)(ne + (n_nb ? 1 : 0)));
-        if (k == 5) alg[k] += multifrontal_flops(4, 4, 12, 0);
-        else if ((k >= 6 && k <= 8) || k >= 13) {
+        if (k == gk::hex8) alg[k] += multifrontal_flops(4, 4, 12, 0);
+        else if (row.fdq_word >= 0) {   // the multifrontal kernels with descriptors; all but the one-wavefront kernel take Neumann rows
             const uint32_t w = fdq[p];
-            alg[k] += multifrontal_flops(w & 255u, (w >> 8) & 255u, n_if, (w >> 16) & 255u, k >= 13 ? n_nb : 0);
-        } else if (k == 12) {
+            alg[k] += multifrontal_flops(w & 255u, (w >> 8) & 255u, n_if, (w >> 16) & 255u, row.family != GlsFamily::mfw ? n_nb : 0);
+        } else if (k == gk::quad4) {
             // two fronts of 8 rows (cell row, two internal faces, the Neumann row) x (3 | 6 | c), then 14 x 6 over the pair
             alg[k] += 52.0 * 4 + 15.0 * 4 + 2 * (hh_flops(8, 3, 3 + 6 + 1) + 9 + 36 + 6) + hh_flops(14, 6, 7) + 36 + 2 * 20 + 2 * 7 + 2 * 8 + 5;
-        } else if (k >= 1 && k <= 3) {
+        } else if (k >= gk::block2 && k <= gk::block8) {
             // the block kernel on more than one wavefront: fronts = the greedy independent set (esup order) of the cells with 1 .. 4
             // internal faces at the node that own no Neumann row; a front of a cell with f faces is (1 + 3 f) x (3 + 3 f + 1)
             const int n_c = (int)std::min<int64_t>(ne, 64);
@@ -1646,17 +1519,7 @@ int nin_gls_plan_flops(nin_grid *g, double alg[22], double ref[22], int64_t comp
 int nin_gls_plan(const nin_grid *g, int64_t counts[22]) {
     if (!g || !counts) return fail(NIN_EINVAL, "NULL argument");
     if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
-    for (int c = 0; c < kGlsClasses; ++c) counts[c] = g->d.gls[c].count;
-    counts[5] = g->d.hex8.count;
-    counts[6] = g->d.mfw[0].count;
-    counts[7] = g->d.mfw[1].count;
-    counts[8] = g->d.mfw[2].count;
-    for (int i = 0; i < 3; ++i) counts[9 + i] = g->d.small[i].count;
-    counts[12] = g->d.quad4.count;
-    for (int i = 0; i < 6; ++i) counts[13 + i] = g->d.mfx[i].count;
-    counts[19] = g->d.mfg.count;
-    counts[20] = g->d.mfx[6].count;
-    counts[21] = g->d.mfx[7].count;
+    for (int k = 0; k < kGlsPlanKernels; ++k) counts[k] = g->d.plan[k].count;
     return NIN_OK;
 }
 

@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "gls_plan.hpp"
+
 namespace nin {
 
 struct GridView {  // passed to kernels by value
@@ -28,35 +30,6 @@ struct GridView {  // passed to kernels by value
     const uint8_t *flags;      // [P]       bit0 boundary_points, bit1 neumann flag
 };
 
-#ifdef __HIPCC__
-#define NIN_HD __host__ __device__
-#else
-#define NIN_HD
-#endif
-
-constexpr int kGlsClasses = 5;  // four LDS budget classes (1 / 2 / 4 / 8 waves per node) + one global-scratch class
-// The GLS kernels' work counters: one block of kGlsQueueInts ints per grid, zeroed before every launch (and before every piece of
-// interpolate()'s pipeline).  The kernels of one launch run at the same time -- the side stream's under the main stream's -- so no
-// two of them may share an int:
-//   hex8 (kernels_gls_hex8mf.hip)      ints 0 + 16 * xcd   one per XCD, each on its own 64-byte line (a grid of fewer than
-//                                                          8 workgroups uses int 0 alone)
-//   block (kernels_gls_block.hip)      ints 1 .. 4         one per LDS class
-//   mfw (kernels_gls_mfw.hip)          ints 5 .. 7         one per kind
-//   mfx (kernels_gls_mfx.hip)          ints 8 .. 15        one per list
-//   mfg (kernels_gls_mfg.hip)          int 128             a 64-byte line of its own, past hex8's eight
-constexpr int kGlsQueueLine = 16;                 // ints per 64-byte line
-constexpr int kGlsQueueHex8 = 0, kGlsQueueHex8Lines = 8;
-constexpr int kGlsQueueBlock = 1;                 // + class (0 .. kGlsClasses - 2)
-constexpr int kGlsQueueMfw = 5;                   // + kind (0 .. 2)
-constexpr int kGlsQueueMfx = 8, kGlsQueueMfxLists = 8;   // + list (0 .. DeviceGrid::kMfxLists - 1)
-constexpr int kGlsQueueMfg = 8 * kGlsQueueLine;
-constexpr int kGlsQueueInts = 9 * kGlsQueueLine;
-static_assert(kGlsQueueBlock > kGlsQueueHex8 && kGlsQueueBlock + (kGlsClasses - 1) <= kGlsQueueMfw, "block counters overlap");
-static_assert(kGlsQueueMfw + 3 <= kGlsQueueMfx, "mfw counters overlap the mfx counters");
-static_assert(kGlsQueueMfx + kGlsQueueMfxLists <= kGlsQueueLine, "the block / mfw / mfx counters must stay between hex8's ints 0 and 16");
-static_assert(kGlsQueueMfg % kGlsQueueLine == 0 && kGlsQueueMfg / kGlsQueueLine >= kGlsQueueHex8 / kGlsQueueLine + kGlsQueueHex8Lines,
-              "the mfg counter must lie on none of hex8's eight lines");
-static_assert(kGlsQueueMfg < kGlsQueueInts, "the mfg counter lies outside the block");
 // LDS bytes a node's system may take in class c and the waves per node the block kernel runs it with
 // (16 / 5 / 2 / 1 workgroups per CU); the last class keeps its systems in global-memory scratch.
 NIN_HD inline int32_t gls_class_budget(int c) { return c == 0 ? 10240 : c == 1 ? 32768 : c == 2 ? 81920 : c == 3 ? 159744 : 0; }
@@ -90,42 +63,32 @@ struct DeviceGrid {
     bool prebuilt = false;  // arrays came from build_grid_on_device(): nin_grid_to_device adopts them, no upload
     std::vector<void *> allocs;  // everything hipMalloc'd, freed together
 
-    // GLS launch plan: nodes binned by the LDS bytes their least-squares system needs
-    struct GlsClass {
+    // interpolate()'s pipeline (abi.hip, interpolate_chunked): the node range is cut into kE2eChunks pieces at multiples of 64 nodes
+    static constexpr int kE2eChunks = 4;
+    int32_t chunk_node[kE2eChunks + 1] = {0, 0, 0, 0, 0};
+    bool chunkable = false;
+    // GLS launch plan: one node list per kernel of gls_plan.hpp, indexed by GlsKernel
+    struct GlsList {
         int32_t count = 0;
-        int32_t *nodes = nullptr;  // device list (ascending node ids)
+        int32_t *nodes = nullptr;  // device list (ascending node ids; the cube-node kernel's in locality order inside each piece)
+        uint32_t *desc = nullptr;  // [gls_plan_row(k).desc_words * count] descriptor words (the *_desc.hpp of the kernel), null: none
+        // every list is ascending, so a piece of the pipeline is a sub-range of it: chunk_off[j] .. chunk_off[j + 1]
+        int32_t chunk_off[kE2eChunks + 1] = {};
+        // the block kernel's classes (nodes binned by the LDS bytes their least-squares system needs) and the scratch class
         int32_t lds_bytes = 0;     // per node (workgroup)
         int32_t waves = 1;         // wavefronts per node
         int32_t col_slots = 1;     // ceil(max columns / 64)
         int32_t rows_per_lane = 1; // ceil(max rows / 64): the wave kernel of the scratch class
-        int32_t max_cells = 0, max_cols = 0, max_rows = 0;
-    } gls[kGlsClasses];
-    GlsClass hex8;  // cube nodes (8 cells, 12 internal faces, cube cell graph): kernels_gls_hex8mf.hip
-    int32_t *hex8_desc = nullptr;   // [4 * hex8.count] lane descriptors (hex8_desc.hpp)
-    GlsClass mfw[3];   // kernels_gls_mfw.hip (mfw_desc.hpp): two-coloured nodes large (Kuhn tetrahedra) / small (wedges), general kind
-    uint32_t *mfw_desc[3] = {nullptr, nullptr, nullptr};   // [kMfwDescWords * mfw[i].count] descriptor words
-    // kernels_gls_mfx.hip (mfx_desc.hpp): interior nodes of unstructured meshes, up to 16 fronts + 21 dense cells, one list per size
-    // class of the dense problem (6 x 10, 7 x 11, 8 x 13, 9 x 15, 10 x 16 tiles)
-    static constexpr int kMfxLists = 8;   // (the sixth: boundary nodes, kernels_gls_mfx.hip's BND instantiation; the seventh: the small interior class (4, 7); the eighth: (7, 12))
-    static_assert(kMfxLists <= kGlsQueueMfxLists, "one work counter per mfx list");
-    GlsClass mfx[kMfxLists];
-    uint32_t *mfx_desc[kMfxLists] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [kMfxDescWords * mfx[c].count] descriptor words
-    // kernels_gls_mfg.hip (mfg_desc.hpp): interior nodes beyond the wide kernel's registers (up to 32 fronts + 40 dense cells): the tiles
-    // of the dense problem in a global-memory slot per resident wavefront
-    GlsClass mfg;
-    uint32_t *mfg_desc = nullptr;   // [kMfgDescWords * mfg.count] descriptor words
-    double *mfg_tiles = nullptr;    // [mfg_slots][kMfgSlotDoubles]
+    } plan[kGlsPlanKernels];
+    double *mfg_tiles = nullptr;    // [mfg_slots][kMfgSlotDoubles]: kernels_gls_mfg.hip's dense problems, a global-memory slot per resident wavefront
     int32_t mfg_slots = 0;
     const int32_t *noncube_nodes = nullptr;   // every node the cube-node kernel does not take (the fused apply's list kernel)
     int32_t noncube_count = 0;
     bool noncube_nodes_ready = false;
-    GlsClass quad4;      // kernels_gls_quad4.hip: nodes inside a boundary face of a hexahedron mesh (4 cells, 4 + 4 faces)
-    int32_t *quad4_desc = nullptr;   // [2 * quad4.count] descriptor words
-    GlsClass small[3];   // kernels_gls_mfw.hip, nin_gls_small_kernel: nodes with at most 4 / 8 / 12 cells and 64 rows that no kernel above takes
     double *gls_scratch = nullptr;  // global-memory systems for the oversize class
     int64_t gls_scratch_stride = 0; // doubles per wave slot
     int32_t gls_scratch_slots = 0;
-    int32_t *gls_queue = nullptr;   // [kGlsQueueInts] the work counters (kGlsQueue* above)
+    int32_t *gls_queue = nullptr;   // [kGlsQueueInts] the work counters (gls_plan.hpp: kGlsQueue*)
     // buffers of nin_interpolate_csr_host / nin_csr_compact_host, allocated on first use and kept (0.65 + 0.98 GB at
     // 10 M cells; allocating and freeing them cost ~10 ms of every call)
     double *e2e_weights = nullptr, *e2e_nws = nullptr, *e2e_data = nullptr;
@@ -154,13 +117,6 @@ struct DeviceGrid {
     // and run under the other kernels (abi.hip: gls_side_begin / gls_side_end).
     void *side_stream = nullptr, *ev_fork = nullptr, *ev_join = nullptr;
     bool side_pending = false;
-    // interpolate()'s pipeline (abi.hip, interpolate_chunked): the node range is cut into kE2eChunks pieces at multiples of 64 nodes;
-    // every GLS list is ascending, so a piece is a sub-range of each: chunk_off[list][k] .. chunk_off[list][k + 1]
-    // (lists 0 .. kGlsClasses - 1: the block kernel's classes, then the cube-node kernel, the three mfw kinds, the three small kinds, the quad nodes, the wide multifrontal kernel's five size classes)
-    static constexpr int kE2eChunks = 4;
-    int32_t chunk_node[kE2eChunks + 1] = {0, 0, 0, 0, 0};
-    int32_t chunk_off[kGlsClasses + 8 + kMfxLists + 1][kE2eChunks + 1] = {};   // (the last: kernels_gls_mfg.hip's list)
-    bool chunkable = false;
     bool gls_too_large = false;     // some node's system has more rows than the scratch kernel handles (1024)
 };
 

@@ -577,53 +577,53 @@ __global__ void k_classify(GridView g, int use_group, int force_global, uint8_t 
     const int64_t ne = g.esup_ptr[p + 1] - g.esup_ptr[p], nf = g.fsup_ptr[p + 1] - g.fsup_ptr[p];
     int64_t nbf = 0;
     for (int32_t q = g.fsup_ptr[p]; q < g.fsup_ptr[p + 1]; ++q) nbf += g.face_cells[2 * (int64_t)g.fsup[q] + 1] == -1;
-    if ((use_group & 1) && ne == 8 && nf == 12 && nbf == 0 && g.dim == 3) {
+    if ((use_group & kRouteHex8) && ne == 8 && nf == 12 && nbf == 0 && g.dim == 3) {
         int32_t d[4];   // the hex8 kernel needs the cells to form the cube graph (hex8_desc.hpp)
-        if (hex8_descriptor(g, (int32_t)p, d)) { node_class[p] = 255; return; }
+        if (hex8_descriptor(g, (int32_t)p, d)) { node_class[p] = gls_class_byte(gk::hex8); return; }
     }
     // (general-kind nodes that fit the small-node kernel -- pyramid apexes: 7 cells, 43 rows -- are cheaper there: 26.64 -> 26.54 ms
     //  on BASELINE config [3])
-    const bool small_fits = (use_group & 8) && !force_global && g.dim == 3 && ne <= 12 && nf <= 48 && ne + 3 * nf <= 64;
-    if ((use_group & 2) && nbf == 0 && ne <= kMfwMaxCells) {
+    const bool small_fits = (use_group & kRouteSmall) && !force_global && g.dim == 3 && ne <= 12 && nf <= 48 && ne + 3 * nf <= 64;
+    if ((use_group & kRouteMfw) && nbf == 0 && ne <= kMfwMaxCells) {
         uint32_t w[kMfwDescWords];   // fronts of 3-face cells that share no face + dense cells (mfw_desc.hpp)
         const int kind = mfw_descriptor(g, (int32_t)p, w);
         if (kind == 1) {
             const int F = w[24] & 255, D = (w[24] >> 8) & 255;
-            node_class[p] = (F <= kMfwSmallFronts && D <= kMfwSmallDense) ? 253 : 254;
+            node_class[p] = (F <= kMfwSmallFronts && D <= kMfwSmallDense) ? gls_class_byte(gk::mfw_small) : gls_class_byte(gk::mfw_large);
             return;
         }
-        // (bit 6: the wide kernel takes the general kind's nodes too -- the default; NIN_GLS_MFW_GENERAL=1 clears it)
-        if (kind == 2 && (use_group & 4) && !small_fits && !(use_group & 64)) { node_class[p] = 252; return; }
+        // (kRouteMfxTakesGeneral: the wide kernel takes the general kind's nodes too -- the default; NIN_GLS_MFW_GENERAL=1 clears it)
+        if (kind == 2 && (use_group & kRouteMfwGeneral) && !small_fits && !(use_group & kRouteMfxTakesGeneral)) { node_class[p] = gls_class_byte(gk::mfw_general); return; }
     }
     // interior nodes of unstructured meshes: more cells than the kinds above hold, no two-colouring (kernels_gls_mfx.hip, mfx_desc.hpp)
     // (round 4: boundary nodes too -- computed only when the variable flags them Neumann; their boundary faces are one row each)
-    const bool small_fits_b = (use_group & 8) && !force_global && g.dim == 3 && ne <= 12 && nf <= 48 && ne + 3 * (nf - nbf) + nbf <= 64;
+    const bool small_fits_b = (use_group & kRouteSmall) && !force_global && g.dim == 3 && ne <= 12 && nf <= 48 && ne + 3 * (nf - nbf) + nbf <= 64;
     // (an interior node the small-node kernel could take -- at most 12 cells, 64 rows -- comes here too if it has at least 9 cells: with fronts
-    //  its dense problem is 43 x 19 where the small-node kernel sweeps 55 x 31: the wide kernel's small class, bit 9: NIN_GLS_NO_MFX_SMALL)
-    const bool small_class_candidate = (use_group & 512) && nbf == 0 && small_fits && ne >= 9;
-    if ((use_group & 32) && !force_global && ne <= kMfxMaxCells && (!(nbf == 0 ? small_fits : small_fits_b) || small_class_candidate) &&
-        (nbf == 0 || !(use_group & 128))) {
+    //  its dense problem is 43 x 19 where the small-node kernel sweeps 55 x 31: the wide kernel's small class, kRouteMfxSmall: NIN_GLS_NO_MFX_SMALL)
+    const bool small_class_candidate = (use_group & kRouteMfxSmall) && nbf == 0 && small_fits && ne >= 9;
+    if ((use_group & kRouteMfx) && !force_global && ne <= kMfxMaxCells && (!(nbf == 0 ? small_fits : small_fits_b) || small_class_candidate) &&
+        (nbf == 0 || !(use_group & kRouteMfxNoBoundary))) {
         uint32_t w[kMfxDescWords];
         const int k = mfx_descriptor(g, (int32_t)p, w);   // 1 + the size class of its dense problem, or kMfxSmallCode
-        if (k == kMfxSmallCode && (use_group & 512)) { node_class[p] = 240; return; }
-        if (k == kMfxMidCode && (use_group & 1024)) { node_class[p] = 239; return; }            // (bit 10: NIN_GLS_NO_MFX_7X12 clears it: class (8, 13))
-        if (k > 0 && nbf == 0 && !small_fits) { node_class[p] = (uint8_t)(243 + (k == kMfxSmallCode ? 1 : k == kMfxMidCode ? 3 : k) - 1); return; }
-        if (k > 0 && k <= 2 && nbf > 0) { node_class[p] = 242; return; }   // a boundary node that fits 7 x 11 tiles: the boundary instantiation's list
+        if (k == kMfxSmallCode && (use_group & kRouteMfxSmall)) { node_class[p] = gls_class_byte(gk::mfx_4x7); return; }
+        if (k == kMfxMidCode && (use_group & kRouteMfx7x12)) { node_class[p] = gls_class_byte(gk::mfx_7x12); return; }            // (NIN_GLS_NO_MFX_7X12 clears the bit: class (8, 13))
+        if (k > 0 && nbf == 0 && !small_fits) { node_class[p] = (uint8_t)(gls_class_byte(gk::mfx_6x10) + (k == kMfxSmallCode ? 1 : k == kMfxMidCode ? 3 : k) - 1); return; }
+        if (k > 0 && k <= 2 && nbf > 0) { node_class[p] = gls_class_byte(gk::mfx_boundary); return; }   // a boundary node that fits 7 x 11 tiles: the boundary instantiation's list
     }
     // interior nodes beyond the wide kernel's 16 fronts + 21 dense cells (a random point cloud's Delaunay mesh: 6 % of its nodes): the
-    // dense problem in global-memory tiles (kernels_gls_mfg.hip, mfg_desc.hpp; bit 8: NIN_GLS_NO_MFG clears it)
-    if ((use_group & 256) && (use_group & 32) && !force_global && nbf == 0 && ne > 12 && ne <= kMfgMaxCells) {
+    // dense problem in global-memory tiles (kernels_gls_mfg.hip, mfg_desc.hpp; kRouteMfg: NIN_GLS_NO_MFG clears it)
+    if ((use_group & kRouteMfg) && (use_group & kRouteMfx) && !force_global && nbf == 0 && ne > 12 && ne <= kMfgMaxCells) {
         uint32_t w[kMfgDescWords];
-        if (mfg_descriptor(g, (int32_t)p, w)) { node_class[p] = 241; return; }
+        if (mfg_descriptor(g, (int32_t)p, w)) { node_class[p] = gls_class_byte(gk::mfg_tiles); return; }
     }
     // nodes inside a boundary face of a hexahedron mesh: two lanes per node (kernels_gls_quad4.hip)
-    if ((use_group & 16) && !force_global && ne == 4 && nf == 8 && nbf == 4 && g.dim == 3) {
+    if ((use_group & kRouteQuad4) && !force_global && ne == 4 && nf == 8 && nbf == 4 && g.dim == 3) {
         int32_t d2[2];
-        if (quad4_descriptor(g, (int32_t)p, d2)) { node_class[p] = 248; return; }
+        if (quad4_descriptor(g, (int32_t)p, d2)) { node_class[p] = gls_class_byte(gk::quad4); return; }
     }
     // small nodes (in practice: boundary nodes): the one-wavefront dense kernel, lane = row (kernels_gls_mfw.hip, nin_gls_small_kernel)
-    if ((use_group & 8) && !force_global && g.dim == 3 && ne <= 12 && nf <= 48 && ne + 3 * (nf - nbf) + nbf <= 64) {
-        node_class[p] = ne <= 4 ? 249 : ne <= 8 ? 250 : 251;
+    if ((use_group & kRouteSmall) && !force_global && g.dim == 3 && ne <= 12 && nf <= 48 && ne + 3 * (nf - nbf) + nbf <= 64) {
+        node_class[p] = ne <= 4 ? gls_class_byte(gk::small4) : ne <= 8 ? gls_class_byte(gk::small8) : gls_class_byte(gk::small12);
         return;
     }
     int64_t bytes, rows, cols;

@@ -22,8 +22,10 @@
 
 namespace nin {
 
+constexpr int kHex8DescWords = 4;   // descriptor words per list entry (gls_plan.hpp holds the same figure; abi.hip asserts the match)
+
 #ifdef __HIPCC__
-__device__ inline bool hex8_descriptor(const GridView &g, int32_t p, int32_t d[4]) {
+__device__ inline bool hex8_descriptor(const GridView &g, int32_t p, int32_t d[kHex8DescWords]) {
     const int32_t eb = g.esup_ptr[p], fb = g.fsup_ptr[p];
     if (g.esup_ptr[p + 1] - eb != 8 || g.fsup_ptr[p + 1] - fb != 12 || g.dim != 3) return false;
     int32_t cells[8];

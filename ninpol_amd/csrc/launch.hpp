@@ -44,7 +44,7 @@ const char *kernel_name_gls_block();
 // the multifrontal kernel for cube nodes (kernels_gls_hex8mf.hip): 4 lanes per node; `desc` = 4 descriptor words per
 // list entry (hex8_desc.hpp, filled by launch_hex8_desc);
 // `queue`: the grid's zeroed counter block + kGlsQueueHex8 (one work counter per XCD at queue + 16 * xcd, each on its own cache line:
-// ints kGlsQueueHex8 .. + 112 are the kernel's, device_grid.hpp)
+// ints kGlsQueueHex8 .. + 112 are the kernel's, gls_plan.hpp)
 int launch_hex8_desc(const GridView &g, const int32_t *nodes, int32_t count, int32_t *desc, hipStream_t stream);
 int launch_gls_hex8mf(const GridView &g, const int32_t *nodes, const int32_t *desc, int32_t count, int add_neumann,
                       double *out, double *nws, int32_t *queue, hipStream_t stream);
@@ -111,10 +111,11 @@ int launch_iota(int32_t *dst, int32_t n, hipStream_t stream);
 int launch_transpose_index_fill(const GridView &g, const int32_t *sorted_cells, int32_t nnz, int32_t *cell_ptr, const int32_t *cell_pos,
                                 int32_t *cell_node, hipStream_t stream);
 
-// GLS launch plan (grid_device.hip): size class of every node (255 = the hex8 kernel, 254 / 253 / 252 = the one-wavefront multifrontal kernel: two-coloured nodes large / small, general kind) and, per class, the
-// maxima of (bytes, rows, columns) as 3 * kGlsClasses unsigned 64-bit values; all DEVICE pointers
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream);
+// GLS launch plan (grid_device.hip): the class byte of every node (gls_plan.hpp: gls_class_byte of the kernel that takes it; use_group =
+// the GlsRoute bits) and, per block / scratch class, the maxima of (bytes, rows, columns) as 3 * kGlsClasses unsigned 64-bit values; all
+// DEVICE pointers
 int launch_classify(const GridView &g, int use_group, int force_global, uint8_t *node_class,
                     unsigned long long *class_max, hipStream_t stream);
 

@@ -20,8 +20,10 @@
 
 namespace nin {
 
+constexpr int kQuad4DescWords = 2;   // descriptor words per list entry (gls_plan.hpp holds the same figure; abi.hip asserts the match)
+
 #ifdef __HIPCC__
-__device__ inline bool quad4_descriptor(const GridView &g, int32_t p, int32_t d[2]) {
+__device__ inline bool quad4_descriptor(const GridView &g, int32_t p, int32_t d[kQuad4DescWords]) {
     const int32_t eb = g.esup_ptr[p], fb = g.fsup_ptr[p];
     if (g.esup_ptr[p + 1] - eb != 4 || g.fsup_ptr[p + 1] - fb != 8 || g.dim != 3) return false;
     int32_t cells[4];

@@ -35,6 +35,22 @@ def test_abi_exports_every_declared_symbol(lib):
     assert lib.load().nin_version().decode().startswith("ninpol_amd")
 
 
+def test_plan_kernels_are_the_enum_of_gls_plan_hpp():
+    """Grid.PLAN_KERNELS names the kernels of csrc/gls_plan.hpp's GlsKernel, in its order (the C ABI exposes no names: the header
+    itself is parsed), and both have as many as the ABI's nin_gls_plan(counts[N]) prototype says."""
+    from ninpol_amd.grid import Grid
+    src = open(os.path.join(ROOT, "ninpol_amd", "csrc", "gls_plan.hpp")).read()
+    src = re.sub(r"//[^\n]*", "", src)
+    n_kernels = int(re.search(r"constexpr\s+int\s+kGlsPlanKernels\s*=\s*(\d+)\s*;", src).group(1))
+    body = re.search(r"enum\s+GlsKernel\s*:\s*int\s*\{(.*?)\}", src, flags=re.S).group(1)
+    names = [s.strip() for s in body.split(",") if s.strip()]
+    assert all(re.fullmatch(r"[A-Za-z_]\w*", s) for s in names), names   # no explicit values: the order is the numbering
+    header = open(os.path.join(ROOT, "include", "ninpol_amd.h")).read()
+    abi = re.search(r"int\s+nin_gls_plan\s*\(\s*const\s+nin_grid\s*\*\s*g\s*,\s*int64_t\s+counts\[(\d+)\]\s*\)", header)
+    assert len(Grid.PLAN_KERNELS) == n_kernels == int(abi.group(1)) == 22
+    assert tuple(names) == Grid.PLAN_KERNELS
+
+
 @pytest.mark.parametrize("case", util.GOLDEN_CASES)
 def test_host_grid_matches_golden(lib, case):
     import ninpol_amd
