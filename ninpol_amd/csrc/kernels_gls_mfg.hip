@@ -22,6 +22,7 @@
 // tools/stamps_mfg.py (a -DNIN_MFG_STAMPS build) gives one wavefront's cycles by phase: of ~435 k per node, 137 k apply finished panels
 // to the groups, 125 k are the panels' own steps (vector work), 72 k phase 1, 41 k the back substitution.
 // Same mathematics as dgels on the reference's matrix (gls.pyx:252-474): a Householder QR under a column / row order that exposes the zeros.
+// The descriptor words are decoded through MfgLayout (mf_graph.hpp), the struct mfg_desc.hpp's builder packs them with.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -325,7 +326,7 @@ __global__ __launch_bounds__(64, NIN_MFG_WAVES) void nin_gls_mfg_kernel(GridView
     const int lane = threadIdx.x;
     double *const yb = Lm + G_Y, *const wbuf = Lm + G_W;
     uint32_t *const dl = reinterpret_cast<uint32_t *>(Lm + G_DESC);
-    const uint8_t *const slotpos = reinterpret_cast<const uint8_t *>(dl + kMfgSlotTable);
+    const uint8_t *const slotpos = reinterpret_cast<const uint8_t *>(dl + MfgLayout::SlotTable);
     double *const slot = tiles + (size_t)blockIdx.x * kMfgSlotDoubles;
 
     auto ticket = [&]() -> int32_t {
@@ -363,8 +364,8 @@ __global__ __launch_bounds__(64, NIN_MFG_WAVES) void nin_gls_mfg_kernel(GridView
         for (int pass = 0; pass < 2; ++pass) {
             if (16 * pass < F) {                                 // (wave-uniform)
                 const int f = 16 * pass + fq;
-                const uint32_t wa = dl[kMfgW0 + f], wb = dl[kMfgW1 + f];
-                const uint32_t pe = wa & 63u, myslot = (wb >> (6 * my)) & 63u;
+                const uint32_t wa = dl[MfgLayout::W0 + f], wb = dl[MfgLayout::W1 + f];
+                const uint32_t pe = MfgLayout::cell_pos(wa), myslot = MfgLayout::slot(wb, my);
                 pe_[0] = pass == 0 ? pe : pe_[0];
                 pe_[1] = pass == 1 ? pe : pe_[1];
                 slot_[0] = pass == 0 ? myslot : slot_[0];
@@ -383,8 +384,8 @@ __global__ __launch_bounds__(64, NIN_MFG_WAVES) void nin_gls_mfg_kernel(GridView
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     // B = [K N; T1; tau T2] (gls.pyx:293-321), row = [-B_a | +B_b] (gls.pyx:340-356)
-                    const uint32_t fc = (uint32_t)g.fsup[fb + ((wa >> (6 + 7 * i)) & 127u)];
-                    const uint32_t cn = (uint32_t)g.esup[eb + slotpos[(wb >> (6 * i)) & 63u]];
+                    const uint32_t fc = (uint32_t)g.fsup[fb + MfgLayout::face_pos(wa, i)];
+                    const uint32_t cn = (uint32_t)g.esup[eb + slotpos[MfgLayout::slot(wb, i)]];
                     const double N0 = (double)g.face_normal[3 * (size_t)fc + 0], N1 = (double)g.face_normal[3 * (size_t)fc + 1],
                                  N2 = (double)g.face_normal[3 * (size_t)fc + 2];
                     const double T0 = xv0 - g.face_center[3 * (size_t)fc + 0], T1 = xv1 - g.face_center[3 * (size_t)fc + 1],
@@ -395,7 +396,7 @@ __global__ __launch_bounds__(64, NIN_MFG_WAVES) void nin_gls_mfg_kernel(GridView
                     eta = dme > eta ? dme : eta;
                     eta = dmn > eta ? dmn : eta;
                     const double tj = face_tau(sqrt(U0 * U0 + U1 * U1 + U2 * U2), eta);
-                    const double sg = ((wa >> (27 + i)) & 1u) ? -1.0 : 1.0;
+                    const double sg = MfgLayout::side_a(wa, i) ? -1.0 : 1.0;
                     const bool mine_ = jq > 0 && my == i;
                     const double s0[3] = {sg * T0, sg * T1, sg * T2}, s1[3] = {sg * (tj * U0), sg * (tj * U1), sg * (tj * U2)};
 #pragma unroll
@@ -449,9 +450,9 @@ __global__ __launch_bounds__(64, NIN_MFG_WAVES) void nin_gls_mfg_kernel(GridView
         }
         if (lane < nfree) {
             // a free face (both its cells dense): its three rows [-B_a | +B_b] (gls.pyx:293-356)
-            const uint32_t fw = dl[kMfgFree0 + lane];
-            const uint32_t fc = (uint32_t)g.fsup[fb + (fw & 127u)];
-            const int sa = (fw >> 7) & 63u, sbb = (fw >> 13) & 63u;
+            const uint32_t fw = dl[MfgLayout::Free0 + lane];
+            const uint32_t fc = (uint32_t)g.fsup[fb + MfgLayout::free_pos(fw)];
+            const int sa = MfgLayout::free_slot_a(fw), sbb = MfgLayout::free_slot_b(fw);
             const uint32_t ca_ = (uint32_t)g.esup[eb + slotpos[sa]], cb_ = (uint32_t)g.esup[eb + slotpos[sbb]];
             const double N0 = (double)g.face_normal[3 * (size_t)fc + 0], N1 = (double)g.face_normal[3 * (size_t)fc + 1],
                          N2 = (double)g.face_normal[3 * (size_t)fc + 2];

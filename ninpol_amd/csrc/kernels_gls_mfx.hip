@@ -14,6 +14,7 @@
 // two, so look-ahead between the panel factorisation and the trailing update buys nothing here.)  The smallest class, 60 tiles =
 // the Kuhn problem's size, runs at two wavefronts per SIMD.  Same mathematics as dgels on the reference's matrix: a Householder QR
 // under a column / row order that exposes the zeros.
+// The descriptor words are decoded through MfxLayout (mf_graph.hpp), the struct mfx_desc.hpp's builder packs them with.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -70,8 +71,8 @@ __device__ __forceinline__ double dense_phase(double *Rm, const uint32_t *dl, in
     // table is made once (lane f) and shuffled
     uint32_t tlo = 0u, thi = 0u;
     {
-        const uint32_t wbl = dl[kMfxW1 + (lane < kMfxMaxFronts ? lane : 0)];
-        const uint64_t t = (1ull << (2 * (wbl & 31u))) | (2ull << (2 * ((wbl >> 5) & 31u))) | (3ull << (2 * ((wbl >> 10) & 31u)));
+        const uint32_t wbl = dl[MfxLayout::W1 + (lane < kMfxMaxFronts ? lane : 0)];
+        const uint64_t t = (1ull << (2 * MfxLayout::slot(wbl, 0))) | (2ull << (2 * MfxLayout::slot(wbl, 1))) | (3ull << (2 * MfxLayout::slot(wbl, 2)));
         tlo = lane < F ? (uint32_t)t : 0u;
         thi = lane < F ? (uint32_t)(t >> 32) : 0u;
     }
@@ -86,8 +87,8 @@ __device__ __forceinline__ double dense_phase(double *Rm, const uint32_t *dl, in
         const bool cell = d >= 0 && d < D, fre = x >= 0 && x < 3 * nfree, bnd = BND && x >= 3 * nfree && x < 3 * nfree + nbnd;
         const int qf = fre ? (x * 43) >> 7 : bnd ? x - 2 * nfree : 0;     // (a boundary face's entry lies behind the free faces': nfree + (x - 3 nfree))
         const uint32_t flo = (uint32_t)__shfl((int)tlo, f), fhi = (uint32_t)__shfl((int)thi, f);
-        const uint32_t fw = dl[kMfxFree0 + qf];
-        const uint64_t qt = (1ull << (2 * ((fw >> 6) & 31u))) | (bnd ? 0ull : 2ull << (2 * ((fw >> 11) & 31u)));
+        const uint32_t fw = dl[MfxLayout::Free0 + qf];
+        const uint64_t qt = (1ull << (2 * MfxLayout::free_slot_a(fw))) | (bnd ? 0ull : 2ull << (2 * MfxLayout::free_slot_b(fw)));
         rtl[q] = fill ? flo : cell ? (d < 16 ? 1u << (2 * d) : 0u) : (fre || bnd) ? (uint32_t)qt : 0u;
         rth[q] = fill ? fhi : cell ? (d >= 16 ? 1u << (2 * (d - 16)) : 0u) : (fre || bnd) ? (uint32_t)(qt >> 32) : 0u;
         const bool have = row < nrows;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(64, (XDims<TQ, TCB>::WAVES)) void nin_gls_mfx_kerne
     const int lane = threadIdx.x;
     double *const yb = Rm + Dm::Y, *const wbuf = Rm + Dm::W;
     uint32_t *const dl = reinterpret_cast<uint32_t *>(Rm + Dm::DESC);
-    const uint8_t *const slotpos = reinterpret_cast<const uint8_t *>(dl + kMfxSlotTable);
+    const uint8_t *const slotpos = reinterpret_cast<const uint8_t *>(dl + MfxLayout::SlotTable);
     if (lane == 0) { Rm[Dm::Z] = 0.0; Rm[Dm::Z + 1] = 1.0; }
 
     auto ticket = [&]() -> int32_t {
@@ -162,11 +163,11 @@ __global__ __launch_bounds__(64, (XDims<TQ, TCB>::WAVES)) void nin_gls_mfx_kerne
         // phase 1 works with FOUR lanes per front: lane 4 f + j applies the front's reflectors to c (j = 0) or to the columns of
         // the front's neighbour j - 1; dense cell d's centroid is fetched by lane d
         const int fq = lane >> 2, jq = lane & 3;
-        const uint32_t wa = dl[kMfxW0 + fq], wb = dl[kMfxW1 + fq];
-        const uint32_t pe = wa & 63u;
+        const uint32_t wa = dl[MfxLayout::W0 + fq], wb = dl[MfxLayout::W1 + fq];
+        const uint32_t pe = MfxLayout::cell_pos(wa);
         const uint32_t po = slotpos[lane < kMfxMaxDense ? lane : 0];
         const int my = jq > 0 ? jq - 1 : 0;                      // this lane's face (the c lane computes face 0's neighbour side in vain)
-        const uint32_t myslot = (wb >> (5 * my)) & 31u;
+        const uint32_t myslot = MfxLayout::slot(wb, my);
         // ---- phase 1: the front of cell E_f (rows 0 = cell row, 1 + 3 i + r = row r of face i) ------------------------------
         // u: this lane's block of u = z^T R_ed (3 columns), or s = z . b_e in u[0] of the c lane
         double u[3], de[3], dod[3];
@@ -189,8 +190,8 @@ __global__ __launch_bounds__(64, (XDims<TQ, TCB>::WAVES)) void nin_gls_mfx_kerne
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 // B = [K N; T1; tau T2] (gls.pyx:293-321), row = [-B_a | +B_b] (gls.pyx:340-356)
-                const uint32_t f = (uint32_t)g.fsup[fb + ((wa >> (6 + 6 * i)) & 63u)];
-                const uint32_t cn = (uint32_t)g.esup[eb + slotpos[(wb >> (5 * i)) & 31u]];
+                const uint32_t f = (uint32_t)g.fsup[fb + MfxLayout::face_pos(wa, i)];
+                const uint32_t cn = (uint32_t)g.esup[eb + slotpos[MfxLayout::slot(wb, i)]];
                 const double N0 = (double)g.face_normal[3 * (size_t)f + 0], N1 = (double)g.face_normal[3 * (size_t)f + 1],
                              N2 = (double)g.face_normal[3 * (size_t)f + 2];
                 const double T0 = xv0 - g.face_center[3 * (size_t)f + 0], T1 = xv1 - g.face_center[3 * (size_t)f + 1],
@@ -201,7 +202,7 @@ __global__ __launch_bounds__(64, (XDims<TQ, TCB>::WAVES)) void nin_gls_mfx_kerne
                 eta = dme > eta ? dme : eta;
                 eta = dmn > eta ? dmn : eta;
                 const double tj = face_tau(sqrt(U0 * U0 + U1 * U1 + U2 * U2), eta);
-                const double sg = ((wa >> (24 + i)) & 1u) ? -1.0 : 1.0;
+                const double sg = MfxLayout::side_a(wa, i) ? -1.0 : 1.0;
                 const bool mine = jq > 0 && my == i;
                 const double s0[3] = {sg * T0, sg * T1, sg * T2}, s1[3] = {sg * (tj * U0), sg * (tj * U1), sg * (tj * U2)};
 #pragma unroll
@@ -241,9 +242,9 @@ __global__ __launch_bounds__(64, (XDims<TQ, TCB>::WAVES)) void nin_gls_mfx_kerne
         }
         if (lane < nfree) {
             // a free face (both its cells dense): its three rows [-B_a | +B_b] (gls.pyx:293-356) go straight into the dense problem
-            const uint32_t fw = dl[kMfxFree0 + lane];
-            const uint32_t f = (uint32_t)g.fsup[fb + (fw & 63u)];
-            const uint32_t ca_ = (uint32_t)g.esup[eb + slotpos[(fw >> 6) & 31u]], cb_ = (uint32_t)g.esup[eb + slotpos[(fw >> 11) & 31u]];
+            const uint32_t fw = dl[MfxLayout::Free0 + lane];
+            const uint32_t f = (uint32_t)g.fsup[fb + MfxLayout::free_pos(fw)];
+            const uint32_t ca_ = (uint32_t)g.esup[eb + slotpos[MfxLayout::free_slot_a(fw)]], cb_ = (uint32_t)g.esup[eb + slotpos[MfxLayout::free_slot_b(fw)]];
             const double N0 = (double)g.face_normal[3 * (size_t)f + 0], N1 = (double)g.face_normal[3 * (size_t)f + 1],
                          N2 = (double)g.face_normal[3 * (size_t)f + 2];
             const double T0 = xv0 - g.face_center[3 * (size_t)f + 0], T1 = xv1 - g.face_center[3 * (size_t)f + 1],
@@ -271,9 +272,9 @@ __global__ __launch_bounds__(64, (XDims<TQ, TCB>::WAVES)) void nin_gls_mfx_kerne
         } else if (BND && lane < nfree + nbnd) {
             // a boundary face of a Neumann node: ONE row, -(K N) on its cell's columns (gls.pyx:394-416; the right-hand side it carries
             // in the reference sits in a column the last-row identity never reads)
-            const uint32_t fw = dl[kMfxFree0 + lane];
-            const uint32_t f = (uint32_t)g.fsup[fb + (fw & 63u)];
-            const uint32_t ca_ = (uint32_t)g.esup[eb + slotpos[(fw >> 6) & 31u]];
+            const uint32_t fw = dl[MfxLayout::Free0 + lane];
+            const uint32_t f = (uint32_t)g.fsup[fb + MfxLayout::free_pos(fw)];
+            const uint32_t ca_ = (uint32_t)g.esup[eb + slotpos[MfxLayout::free_slot_a(fw)]];
             const double N0 = (double)g.face_normal[3 * (size_t)f + 0], N1 = (double)g.face_normal[3 * (size_t)f + 1],
                          N2 = (double)g.face_normal[3 * (size_t)f + 2];
             const double *Ka = g.perm + 9 * (size_t)ca_;

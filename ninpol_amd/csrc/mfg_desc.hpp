@@ -14,15 +14,13 @@
 //   word 65 .. 74     esup position of dense slot d, one byte each (slots in esup order)
 //   word 75 + q       free face q: fsup position (7 bits) | dense slot of its first cell << 7 | of its second cell << 13
 #pragma once
-#include <cstdint>
-
-#include "device_grid.hpp"
+#include "mf_graph.hpp"
 
 namespace nin {
 
 constexpr int kMfgMaxFronts = 32, kMfgMaxDense = 40, kMfgMaxFree = 48, kMfgDescWords = 124;
 constexpr int kMfgMaxRows = 256, kMfgMaxCells = 64, kMfgMaxFaces = 127;
-constexpr int kMfgW0 = 1, kMfgW1 = 33, kMfgSlotTable = 65, kMfgFree0 = 75;
+using MfgLayout = MfLayout<kMfgMaxFronts, kMfgMaxDense, kMfgMaxFree, kMfgMaxRows, kMfgDescWords, 75, 7, 6, 27>;   // mf_graph.hpp
 constexpr int kMfgRowTiles = 16, kMfgColBlocks = 32;                   // tiles of 16 rows x 4 columns: 256 x 128
 constexpr int kMfgSlotDoubles = (kMfgRowTiles * kMfgColBlocks + 2 * kMfgColBlocks) * 64;   // one node's tiles + two auxiliary tiles per panel: 288 KB of global scratch
 constexpr int kMfgResidentWaves = 4 * 256;                             // slots at most: one wavefront per SIMD (288 MB)
@@ -88,8 +86,8 @@ __device__ inline int mfg_descriptor(const GridView &g, int32_t p, uint32_t w[kM
     for (int k = 0; k < kMfgDescWords; ++k) w[k] = 0u;
     w[0] = (uint32_t)F | ((uint32_t)D << 8) | ((uint32_t)nfree << 16);
     for (int i = 0; i < ne; ++i) {
-        if ((best >> i) & 1ull) w[kMfgW0 + rank[i]] |= (uint32_t)i;
-        else w[kMfgSlotTable + (rank[i] >> 2)] |= (uint32_t)i << (8 * (rank[i] & 3));
+        if ((best >> i) & 1ull) w[MfgLayout::W0 + rank[i]] |= (uint32_t)i;
+        else w[MfgLayout::SlotTable + (rank[i] >> 2)] |= (uint32_t)i << (8 * (rank[i] & 3));
     }
     uint8_t nface[kMfgMaxFronts];
     for (int f = 0; f < kMfgMaxFronts; ++f) nface[f] = 0;
@@ -98,13 +96,13 @@ __device__ inline int mfg_descriptor(const GridView &g, int32_t p, uint32_t w[kM
         const int ia = fa[fi], ib = fbb[fi];
         const bool a_front = ((best >> ia) & 1ull) != 0, b_front = ((best >> ib) & 1ull) != 0;
         if (!a_front && !b_front) {
-            w[kMfgFree0 + q++] = (uint32_t)fi | ((uint32_t)rank[ia] << 7) | ((uint32_t)rank[ib] << 13);
+            w[MfgLayout::Free0 + q++] = MfgLayout::pack_free(fi, rank[ia], rank[ib]);
             continue;
         }
         const int fc = a_front ? ia : ib, oc = a_front ? ib : ia;
         const int f = rank[fc], k = nface[f]++;
-        w[kMfgW0 + f] |= ((uint32_t)fi << (6 + 7 * k)) | ((a_front ? 1u : 0u) << (27 + k));
-        w[kMfgW1 + f] |= (uint32_t)rank[oc] << (6 * k);
+        w[MfgLayout::W0 + f] |= MfgLayout::pack_face(fi, k, a_front);
+        w[MfgLayout::W1 + f] |= MfgLayout::pack_slot(rank[oc], k);
     }
     return 1;
 }

@@ -19,15 +19,13 @@
 //                     then the boundary faces: fsup position | dense slot of its cell << 6 | bit 31  (free + boundary faces <= 16)
 // Fronts and dense cells are numbered in esup order, free and boundary faces in fsup order.
 #pragma once
-#include <cstdint>
-
-#include "device_grid.hpp"
+#include "mf_graph.hpp"
 
 namespace nin {
 
 constexpr int kMfxMaxFronts = 16, kMfxMaxDense = 21, kMfxMaxFree = 16, kMfxDescWords = 56;
 constexpr int kMfxMaxRows = 160, kMfxMaxCells = kMfxMaxFronts + kMfxMaxDense, kMfxMaxFaces = 63;
-constexpr int kMfxW0 = 1, kMfxW1 = 17, kMfxSlotTable = 33, kMfxFree0 = 39;
+using MfxLayout = MfLayout<kMfxMaxFronts, kMfxMaxDense, kMfxMaxFree, kMfxMaxRows, kMfxDescWords, 39, 6, 5, 24>;   // mf_graph.hpp
 // Size classes of the dense problem (kernels_gls_mfx.hip: one instantiation and one list of the launch plan each): rows <= 16 TQ,
 // pivot columns nc = 3 D < 4 TCB for (TQ, TCB) = (6, 10), (7, 11), (8, 13), (9, 15), (10, 16)
 constexpr int kMfxClasses = 5;
@@ -139,8 +137,8 @@ __device__ inline int mfx_descriptor(const GridView &g, int32_t p, uint32_t w[kM
     for (int k = 0; k < kMfxDescWords; ++k) w[k] = 0u;
     w[0] = (uint32_t)F | ((uint32_t)D << 8) | ((uint32_t)nfree << 16) | ((uint32_t)nbnd << 24);
     for (int i = 0; i < ne; ++i) {
-        if ((best >> i) & 1ull) w[kMfxW0 + rank[i]] |= (uint32_t)i;
-        else w[kMfxSlotTable + (rank[i] >> 2)] |= (uint32_t)i << (8 * (rank[i] & 3));
+        if ((best >> i) & 1ull) w[MfxLayout::W0 + rank[i]] |= (uint32_t)i;
+        else w[MfxLayout::SlotTable + (rank[i] >> 2)] |= (uint32_t)i << (8 * (rank[i] & 3));
     }
     int nface[kMfxMaxFronts];
     for (int f = 0; f < kMfxMaxFronts; ++f) nface[f] = 0;
@@ -148,18 +146,18 @@ __device__ inline int mfx_descriptor(const GridView &g, int32_t p, uint32_t w[kM
     for (int fi = 0; fi < G.nf; ++fi) {
         const int ia = G.fa[fi], ib = G.fbb[fi];
         if (ib == 0xFF) {                                  // boundary face: behind the free faces
-            w[kMfxFree0 + qb++] = (uint32_t)fi | ((uint32_t)rank[ia] << 6) | 0x80000000u;
+            w[MfxLayout::Free0 + qb++] = MfxLayout::pack_boundary(fi, rank[ia]);
             continue;
         }
         const bool a_front = ((best >> ia) & 1ull) != 0, b_front = ((best >> ib) & 1ull) != 0;
         if (!a_front && !b_front) {
-            w[kMfxFree0 + q++] = (uint32_t)fi | ((uint32_t)rank[ia] << 6) | ((uint32_t)rank[ib] << 11);
+            w[MfxLayout::Free0 + q++] = MfxLayout::pack_free(fi, rank[ia], rank[ib]);
             continue;
         }
         const int fc = a_front ? ia : ib, oc = a_front ? ib : ia;
         const int f = rank[fc], k = nface[f]++;
-        w[kMfxW0 + f] |= ((uint32_t)fi << (6 + 6 * k)) | ((a_front ? 1u : 0u) << (24 + k));
-        w[kMfxW1 + f] |= (uint32_t)rank[oc] << (5 * k);
+        w[MfxLayout::W0 + f] |= MfxLayout::pack_face(fi, k, a_front);
+        w[MfxLayout::W1 + f] |= MfxLayout::pack_slot(rank[oc], k);
     }
     if (mfx_fits_small(F, D, nfree, nbnd)) return kMfxSmallCode;
     const int cls = mfx_size_class(F, D, nfree, nbnd);

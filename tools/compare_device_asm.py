@@ -4,7 +4,8 @@
 Compiles every kernel unit (kernels_*.hip, grid_update.hip, grid_device.hip; or the ones named) of ninpol_amd/csrc and of OTHER_CSRC
 (another checkout's csrc directory) to device-only gfx950 assembly with the unit's own flags from build.UNITS, the way count_fp64.py
 does, and compares the instruction streams kernel by kernel after stripping comments, the compiler ident, file-path lines and the
-compilation-unit id (a hash of the source path).
+compilation-unit id (a hash of the source path).  The metadata block at the end of a unit (every kernel's register and scratch
+figures) is compared as an entry of its own, "(metadata)".
 One line per unit; exit status 1 if any differs.  No GPU needed."""
 import os
 import re
@@ -28,8 +29,8 @@ def kernels(csrc, unit, extra, tmp):
         if not line.strip() or re.match(r"\s*\.(ident|file)\b", line) or csrc in line or "__hip_cuid_" in line:
             continue
         m = re.match(r"^(_Z\w+):", line)
-        if m:
-            name = m.group(1)
+        if m or line.strip() == ".amdgpu_metadata":        # (the unit's metadata follows the last kernel: its own entry, not that kernel's)
+            name = m.group(1) if m else "(metadata)"
             out[name] = []
         out[name].append(line)
     return out
@@ -45,7 +46,7 @@ def main():
             a, b = kernels(CSRC, unit, extra, ta), kernels(other, unit, extra, tb)
             diff = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
             bad += bool(diff)
-            print(f"{unit}: {len(a) - 1} symbols, {sum(map(len, a.values()))} lines: " +
+            print(f"{unit}: {sum(k.startswith('_Z') for k in a)} symbols, {sum(map(len, a.values()))} lines: " +
                   ("identical" if not diff else "DIFFERENT in " + ", ".join(k or "(preamble)" for k in diff)), flush=True)
     return 1 if bad else 0
 
