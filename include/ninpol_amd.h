@@ -133,6 +133,29 @@ int nin_grid_has_transpose_index(const nin_grid *g);
 int nin_fields_set(nin_grid *g, const double *permeability, const double *diff_mag,
                    const double *neumann_flag, const double *neumann_val);
 
+/* ---- changing permeability ---------------------------------------------------------------------
+ * The permeability of a grid on a device replaced from DEVICE memory (nonlinear diffusion, mobility times absolute permeability
+ * under Picard / Newton iteration: K changes every step and already lives on the GPU).  Nothing crosses the host.
+ *
+ * nin_fields_set_permeability_device: dev_permeability is a DEVICE array [n_elems][3][3] row-major on the grid's device, at any
+ * 8-byte aligned address (at a 16-byte aligned one it is read in 16-byte pieces, else in 8-byte pieces: same result), dev_scale a DEVICE
+ * array [n_elems] or NULL; neither overlaps a grid array.
+ * The resident table becomes permeability[e][k] (dev_scale NULL) or dev_scale[e] * permeability[e][k] (one multiplication, rounded
+ * once) and the resident diff_mag what nin_diff_mag makes of that table, bit for bit (csrc/fields_update.hip).  Asynchronous on
+ * `stream` (hipStream_t), with the ordering rules of nin_grid_update_points_device: later launches on that stream see the new K;
+ * work on other streams, and the host-synchronous entry points (nin_weights_host, nin_interpolate_csr_host, nin_apply_*_host: they
+ * run on the null stream), must be ordered behind `stream` by the caller.  Needs no prior nin_fields_set and leaves the Neumann
+ * flags as they are; GLS finds its permeability set afterwards.  A later nin_fields_set with a permeability replaces the table again.
+ * NIN_EINVAL for a NULL grid or dev_permeability, NIN_ENODEVICE when nin_grid_device(g) is -1.
+ * nin_fields_get_permeability: the resident tables copied to HOST arrays permeability [n_elems][9] and diff_mag [n_elems] (either
+ * may be NULL); host-synchronous, waits for everything enqueued on the device first.  NIN_EINVAL for a NULL grid, NIN_ENODEVICE as
+ * above, NIN_ESTATE when no permeability is resident. */
+int nin_fields_set_permeability_device(nin_grid *g, const double *dev_permeability, const double *dev_scale, void *stream);
+int nin_fields_get_permeability(nin_grid *g, double *permeability, double *diff_mag);
+/* Permeability updates from device memory the grid's device copy has seen since it was made (0 without one): the sibling of
+ * nin_grid_geometry_updates -- a cheap way to tell which path an update took. */
+int64_t nin_grid_field_updates(const nin_grid *g);
+
 /* ---- the hot path -------------------------------------------------------------------------
  * Replaces supported_methods[method](grid, ..., target_points, weights, neumann_ws)
  * (interpolator.pyx:657-665 -> idw.pyx:14-84, ls.pyx:21-135, gls.pyx:38-474).

@@ -23,6 +23,7 @@ EXPORTS = (
     "nin_algorithmic_bytes", "nin_kernel_name", "nin_gls_plan", "nin_gls_plan_flops", "nin_host_alloc", "nin_host_free", "nin_hash64",
     "nin_grid_release_scratch",
     "nin_grid_update_points", "nin_grid_update_points_device", "nin_grid_geometry_updates", "nin_grid_has_transpose_index",
+    "nin_fields_set_permeability_device", "nin_fields_get_permeability", "nin_grid_field_updates",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -88,6 +89,10 @@ def load():
     L.nin_grid_geometry_updates.argtypes = [vp]
     L.nin_grid_geometry_updates.restype = i64
     L.nin_grid_has_transpose_index.argtypes = [vp]
+    L.nin_fields_set_permeability_device.argtypes = [vp, vp, vp, vp]
+    L.nin_fields_get_permeability.argtypes = [vp, vp, vp]
+    L.nin_grid_field_updates.argtypes = [vp]
+    L.nin_grid_field_updates.restype = i64
     L.nin_exchange_create.argtypes = [i32, i32, i32, ctypes.c_size_t, ctypes.POINTER(vp)]
     L.nin_exchange_destroy.argtypes = [vp]
     L.nin_exchange_destroy.restype = None

@@ -38,6 +38,8 @@ UNITS = [
     ("grid_device.hip", "hipcc", ["-ffp-contract=off"]),
     # geometry refresh of a moving mesh: the same arithmetic as grid_device.hip's geometry kernels, the same flag
     ("grid_update.hip", "hipcc", ["-ffp-contract=off"]),
+    # permeability from device memory: diff_mag must be pack_host.cpp's value bit for bit, so no contraction here either
+    ("fields_update.hip", "hipcc", ["-ffp-contract=off"]),
     ("abi.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),

@@ -816,6 +816,34 @@ int nin_fields_set(nin_grid *g, const double *permeability, const double *diff_m
     return NIN_OK;
 }
 
+int nin_fields_set_permeability_device(nin_grid *g, const double *dev_permeability, const double *dev_scale, void *stream) {
+    if (!g || !dev_permeability) return fail(NIN_EINVAL, "NULL argument");
+    if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first, or nin_fields_set with host arrays)");
+    DeviceGrid &d = g->d;
+    HIP_TRY(hipSetDevice(d.device));
+    const hipError_t e = launch_update_permeability(d.v.n_elems, dev_permeability, dev_scale, const_cast<double *>(d.v.perm),
+                                                    const_cast<double *>(d.v.diff_mag), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(NIN_EHIP, "permeability kernel: %s", hipGetErrorString(e));
+    d.have_perm = true;
+    ++d.field_updates;
+    return NIN_OK;
+}
+
+int nin_fields_get_permeability(nin_grid *g, double *permeability, double *diff_mag) {
+    if (!g) return fail(NIN_EINVAL, "NULL grid");
+    if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
+    DeviceGrid &d = g->d;
+    if (!d.have_perm) return fail(NIN_ESTATE, "no permeability is resident (nin_fields_set or nin_fields_set_permeability_device first)");
+    HIP_TRY(hipSetDevice(d.device));
+    HIP_TRY(hipDeviceSynchronize());   // an update may still be in flight on any stream
+    const size_t E = (size_t)g->h.n_elems;
+    if (permeability) HIP_TRY(hipMemcpy(permeability, d.v.perm, E * 9 * 8, hipMemcpyDeviceToHost));
+    if (diff_mag) HIP_TRY(hipMemcpy(diff_mag, d.v.diff_mag, E * 8, hipMemcpyDeviceToHost));
+    return NIN_OK;
+}
+
+int64_t nin_grid_field_updates(const nin_grid *g) { return g ? g->d.field_updates : 0; }
+
 // ---- one launch of the plan: every walk over its kernels goes through the two arrays below ---------------------------------------
 // The long poles first, on the side stream when it is on (a node on global-memory tiles takes ~0.5 ms, one of the global-scratch class ~2 ms,
 // on a wavefront of its own); then kMainOrder, where the two come up again for a launch whose side stream did not take them.

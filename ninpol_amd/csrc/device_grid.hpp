@@ -109,6 +109,7 @@ struct DeviceGrid {
     double *up_areas = nullptr;
     int64_t geom_updates = 0;
     void *ev_geom = nullptr;
+    int64_t field_updates = 0;   // permeability updates from device memory (nin_fields_set_permeability_device, fields_update.hip)
     uint8_t *flag_staging = nullptr;   // page-locked [n_points]: nin_fields_set packs the node flags here and uploads from it
     void *copy_stream = nullptr, *copy_stream2 = nullptr;   // hipStream_t of the device-to-host copies that run under the kernels
     void *ev_weights = nullptr, *ev_scan = nullptr;   // hipEvent_t: weights written / row pointers scanned

@@ -126,6 +126,12 @@ int launch_update_coords(const double *dev_xyz, int coords_dim, int64_t n_points
 int launch_update_geometry(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const int32_t *inpofa,
                            double *centroids, double *face_center, float *face_normal, double *face_area, hipStream_t stream);
 
+// fields_update.hip: the grid's perm [E][9] and diff_mag [E] from a caller's K [E][9] and an optional scale [E] (null: none), all
+// DEVICE pointers; perm from hipMalloc (16-byte aligned), dev_K at any multiple of 8 bytes, neither overlapping the outputs.  Returns
+// the launch's own error (read once: hipGetLastError clears it)
+hipError_t launch_update_permeability(int32_t n_elems, const double *dev_K, const double *dev_scale, double *perm, double *diff_mag,
+                                      hipStream_t stream);
+
 const char *kernel_name_idw();
 const char *kernel_name_ls();
 const char *kernel_name_gls();

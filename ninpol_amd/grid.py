@@ -77,6 +77,9 @@ class Grid:
         self._cache = {}
         self._perm_key = None   # fingerprint of the permeability table resident on the device (interpolator.py)
         self._fields_variable = None   # the variable whose Neumann flags are resident (DevicePlan.ensure_current)
+        # True from load_permeability_device() until a host table is uploaded over it, or read back into the host rows
+        # (Interpolator.permeability_on_device)
+        self._perm_from_device = False
         self._h = ctypes.c_void_p()
         L = _lib.load()
         if build_device is None:   # the native OpenMP builder (csrc/grid_host.cpp)
@@ -216,8 +219,37 @@ class Grid:
     def to_device(self, device=0):
         self._perm_key = None   # a fresh device copy holds no fields
         self._fields_variable = None   # ... and nobody's Neumann flags: every DevicePlan re-uploads at its next launch
+        self._perm_from_device = False
         _lib.check(_lib.load().nin_grid_to_device(self._h, int(device)))
         return self
+
+    def load_permeability_device(self, K, scale=None):
+        """The resident permeability from torch tensors on the grid's device (nin_fields_set_permeability_device): K float64,
+        contiguous, n_elems * 9 values; scale None or float64 contiguous (n_elems,).  Asynchronous on torch's current stream; the
+        arguments are checked by Interpolator.update_permeability, which is the public way in."""
+        import torch
+        stream = torch.cuda.current_stream(K.device).cuda_stream
+        _lib.check(_lib.load().nin_fields_set_permeability_device(
+            self._h, ctypes.c_void_p(K.data_ptr()), None if scale is None else ctypes.c_void_p(scale.data_ptr()), ctypes.c_void_p(stream)))
+        self._perm_from_device = True
+
+    def fetch_permeability(self):
+        """(permeability (n_elems, 9), diff_mag (n_elems,)) as resident on the device (nin_fields_get_permeability: waits for the
+        device); None when the grid is on no device or holds no permeability there."""
+        if self.device < 0:
+            return None
+        E = int(self.n_elems)
+        perm, dmag = np.empty((E, 9), dtype=np.float64), np.empty(E, dtype=np.float64)
+        rc = _lib.load().nin_fields_get_permeability(self._h, _ptr(perm), _ptr(dmag))
+        if rc == _lib.NIN_ESTATE:
+            return None
+        _lib.check(rc)
+        return perm, dmag
+
+    @property
+    def field_updates(self):
+        """How many times the permeability of this grid's device copy was replaced from device memory (0: never, or host-only)."""
+        return int(_lib.load().nin_grid_field_updates(self._h))
 
     @property
     def device(self):

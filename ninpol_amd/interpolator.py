@@ -101,6 +101,7 @@ class _TableCheck:
     def upload(self, flag):
         _lib.check(_lib.load().nin_fields_set(self.grid._h, _ptr(self.perm), _ptr(self.dmag), _ptr(flag), None))
         self.grid._perm_key = self.key
+        self.grid._perm_from_device = False
 
 
 def _upload_fields(grid, method, cells_data, points_data, variable_to_index, variable, device=0, always_perm=False,
@@ -135,6 +136,8 @@ def _upload_fields(grid, method, cells_data, points_data, variable_to_index, var
     _lib.check(L.nin_fields_set(grid._h, _ptr(perm), _ptr(dmag), _ptr(flag), _ptr(nval)))
     if key is not None:
         grid._perm_key = key
+    if perm is not None:
+        grid._perm_from_device = False   # the host table went over whatever a device update had left
     # the flags on the device belong to the GRID, not to a plan: remember whose they are (DevicePlan.ensure_current)
     grid._fields_variable = variable
     if check is not None:
@@ -301,6 +304,113 @@ class Interpolator:
             if type(points).__module__.split(".")[0] == "torch":
                 points = points.detach().numpy()
             self.points_coords = np.ascontiguousarray(np.array(points, dtype=DTYPE_F))
+
+    # ---- changing permeability ---------------------------------------------------------------------
+    def _perm_rows(self):
+        """The `permeability` and `diff_mag` rows of cells_data as _upload_fields reads them (views: same addresses, same hash)."""
+        if not self.is_grid_initialized:
+            raise ValueError("Grid not initialized. Please load a mesh first.")
+        v2i = self.variable_to_index["cells"]
+        if "permeability" not in v2i or "diff_mag" not in v2i:
+            raise ValueError("Variable 'permeability' not found in cells data: load a mesh that carries it.")
+        E = self.grid.n_elems
+        cd = np.asarray(self.cells_data)
+        return cd[v2i["permeability"]][:E * 9], cd[v2i["diff_mag"]][:E]
+
+    def update_permeability(self, K, scale=None):
+        """Replace the permeability of the loaded mesh: K of shape (n_elems, 3, 3) or (n_elems, 9), optionally times a per-cell
+        factor `scale` of shape (n_elems,) (mobility times absolute permeability: one multiplication per entry, rounded once).
+        diff_mag follows.  Connectivity, geometry, Neumann flags and the GLS launch plan stay.
+
+        A numpy array (or a CPU torch tensor): the `permeability` and `diff_mag` rows of `cells_data` are rewritten in place -- what a
+        fresh load_mesh() of the mesh with that K holds, bit for bit -- and the next interpolate() / apply() / DevicePlan.refresh()
+        finds the table changed and uploads it, as after any in-place edit.  Works without a GPU.
+
+        A float64 torch tensor on this Interpolator's device (`scale`, if given, one too): the resident table is rewritten from device
+        memory by a kernel on torch's current stream -- no host copy, no synchronisation.  Launches of a DevicePlan / CellToNode
+        (recompute_weights()) on that stream follow in order; the host-synchronous methods (interpolate, apply, apply_transpose)
+        need `torch.cuda.current_stream().synchronize()` first.  The `cells_data` rows are NOT touched: fetch_permeability() brings
+        the device's values back.  Precedence: the device copy stays resident, through any number of interpolate() / refresh()
+        calls, until the CONTENTS of the host rows change; an in-place edit of `cells_data` made afterwards wins at the next call
+        that reads the tables, exactly as an edit always did."""
+        perm_row, dmag_row = self._perm_rows()
+        g = self.grid
+        E = g.n_elems
+        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
+        if is_torch(K) and getattr(K, "is_cuda", False):
+            import torch
+            where = torch.device("cuda", self.device)
+
+            def checked(t, name, shapes):
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError(f"{name} must be a torch.Tensor on {where} when K is, not {type(t).__name__}")
+                if t.dtype != torch.float64:
+                    raise TypeError(f"{name} must be float64, not {t.dtype} (no silent cast)")
+                if t.device != where:
+                    raise ValueError(f"{name} must be on {where}, not {t.device}")
+                if tuple(t.shape) not in shapes:
+                    raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {tuple(t.shape)}")
+                return t.detach().contiguous()
+
+            Kd = checked(K, "K", ((E, 3, 3), (E, 9)))
+            sd = None if scale is None else checked(scale, "scale", ((E,),))
+            if g.device < 0:
+                g.to_device(self.device)
+            if g._perm_key is None:
+                # the host table was never uploaded to this device copy: it counts as seen from here on, or the next call would
+                # upload it over the device's K (its first hash finds nothing to compare with)
+                g._perm_key = (_table_key(perm_row), _table_key(dmag_row))
+            g.load_permeability_device(Kd, sd)
+            return
+        if is_torch(K):
+            K = K.detach().numpy()
+        if scale is not None and is_torch(scale):
+            if getattr(scale, "is_cuda", False):
+                raise ValueError(f"scale must be on the host when K is, not {scale.device}")
+            scale = scale.detach().numpy()
+
+        def checked(a, name, shapes):
+            try:
+                a = np.asarray(a)
+                if a.dtype.kind == "f" and a.dtype != DTYPE_F:
+                    raise TypeError(f"{name} must be float64, not {a.dtype} (no silent cast)")
+                a = np.ascontiguousarray(a, dtype=DTYPE_F)
+            except ValueError as e:
+                raise ValueError(f"{name} cannot be converted to float64: {e}") from e
+            if a.shape not in shapes:
+                raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {a.shape}")
+            return a
+
+        K9 = checked(K, "K", ((E, 3, 3), (E, 9))).reshape(E, 9)
+        if scale is not None:
+            K9 = checked(scale, "scale", ((E,),))[:, None] * K9
+        perm_row[:] = K9.reshape(-1)
+        dmag_row[:] = self.compute_diffusion_magnitude(K9)
+        g._perm_from_device = False  # the host rows are the newer ones now: the next call that reads the tables uploads them
+
+    def fetch_permeability(self):
+        """The permeability resident on the device read back into the `permeability` and `diff_mag` rows of `cells_data` (after
+        update_permeability() from device tensors the rows still hold the older values); waits for the device.  The rows then ARE
+        the resident table and are recorded as such: the next call uploads nothing.  Returns K as (n_elems, 3, 3).  With nothing
+        resident on a device the rows are returned as they are."""
+        perm_row, dmag_row = self._perm_rows()
+        g = self.grid
+        got = g.fetch_permeability()
+        if got is not None:
+            perm_row[:] = got[0].reshape(-1)
+            dmag_row[:] = got[1]
+            g._perm_key = (_table_key(perm_row), _table_key(dmag_row))
+            g._perm_from_device = False
+        return np.array(perm_row).reshape(g.n_elems, 3, 3)
+
+    @property
+    def permeability_on_device(self):
+        """True while the permeability resident on the device came from update_permeability() with device tensors and is newer than
+        the `cells_data` rows: until fetch_permeability(), a host-side update_permeability(), or the call that finds the host rows
+        edited and uploads them.  It reports what has HAPPENED: an in-place edit of the rows that no call has read yet -- made
+        before or after the device update -- does not show here until the next call that reads the tables uploads it."""
+        g = self.grid
+        return g is not None and g._perm_from_device
 
     def load_arrays(self, points, cells, cell_data=None, point_data=None):
         """`load_mesh` from plain arrays, no meshio object.  `cells` is a list of
@@ -589,7 +699,12 @@ class DevicePlan:
     edit of a table is only seen there, exactly as Interpolator.interpolate() sees it on every call.
 
     The geometry belongs to the grid too: after Interpolator.update_points() the next `launch` computes the weights of the moved
-    mesh (no refresh() is needed for that; what an earlier launch wrote into the caller's buffers stays what it was)."""
+    mesh (no refresh() is needed for that; what an earlier launch wrote into the caller's buffers stays what it was).
+
+    So does a permeability that changes on the device: after Interpolator.update_permeability() with device tensors the next
+    `launch` on the same stream computes with the new K -- `launch` never re-reads a table, so a time loop of update_permeability(K_dev)
+    and launch(...) touches no host memory and never synchronises.  `refresh()` leaves that K resident as long as the contents of the
+    host table are what they were (the precedence rule of update_permeability)."""
 
     def __init__(self, interp, variable, method):
         if not interp.is_grid_initialized:

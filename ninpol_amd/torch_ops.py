@@ -36,8 +36,10 @@ class CellToNode(torch.nn.Module):
     (float64 [n_points]) beside them; `refresh()` re-reads the Interpolator's tables and computes them again -- an in-place edit of
     the permeability is seen there and only there (the contract of DevicePlan.refresh()).  The same holds for a moved mesh: after
     `interp.update_points(...)` the module goes on applying the weights of the old geometry until `refresh()`; nothing is
-    recomputed behind the caller's back.  Derivatives with respect to the permeability, the Neumann values or the node
-    coordinates are not provided."""
+    recomputed behind the caller's back.  A permeability that lives on the device reaches the module through
+    `interp.update_permeability(K_dev)` followed by `recompute_weights()`: the weight kernels run again on torch's current stream
+    from whatever is resident -- geometry and permeability -- with no table re-read, no hash and no synchronisation.  Derivatives
+    with respect to the permeability, the Neumann values or the node coordinates are not provided."""
 
     def __init__(self, interp, variable, method):
         super().__init__()
@@ -63,6 +65,12 @@ class CellToNode(torch.nn.Module):
         """Upload the Interpolator's field tables as they are now and recompute the weights, from the grid's geometry as it is now
         (on torch's current stream: behind an update_points() from a device tensor on the same stream)."""
         self.plan.refresh()
+        self._compute_weights()
+
+    def recompute_weights(self):
+        """Compute the weights again from what is resident on the device NOW -- after interp.update_permeability() or
+        update_points() with device tensors on the same stream -- without reading the Interpolator's tables (refresh() does that).
+        Asynchronous on torch's current stream; outputs computed before keep the weights of their forward pass in backward."""
         self._compute_weights()
 
     def _spmv(self, weights, u):
