@@ -156,6 +156,43 @@ int nin_fields_get_permeability(nin_grid *g, double *permeability, double *diff_
  * nin_grid_geometry_updates -- a cheap way to tell which path an update took. */
 int64_t nin_grid_field_updates(const nin_grid *g);
 
+/* ---- local permeability updates: recompute only the rows that changed ---------------------------------------------------
+ * A GLS row of node n reads the permeability of the cells around n only, so a change to cell e can move the rows of the vertices of e
+ * and no others.  The grid keeps a DIRTY SET of nodes on the device: a scatter writes a subset of cells and marks their vertices, a
+ * dirty launch recomputes exactly the marked rows IN PLACE in the caller's buffers.  Contract: if the caller's buffers held a full
+ * result as of the last clear, they hold, after a dirty launch, what a full launch would write now, bit for bit.  The set does not
+ * record why a node is dirty: IDW and LS recompute their marked rows too (and get the same bits).  All calls that touch the set of one
+ * grid belong on ONE stream (or are ordered by the caller).
+ *
+ * nin_fields_scatter_permeability_device: dev_cell_ids [n] cell ids (int32, or int64 when ids_are_int64 != 0), dev_permeability [n][9]
+ *   and dev_scale [n] or NULL, all DEVICE arrays on the grid's device.  Cell dev_cell_ids[i] of the resident table becomes row i
+ *   (times dev_scale[i]: one multiplication, rounded once), its diff_mag what nin_diff_mag makes of that row, bit for bit; the vertices
+ *   of the cell are marked.  Every id is checked on the device before any access: an id outside [0, n_elems) writes nothing and is
+ *   counted; the next nin_weights_dirty_device reports the count.  Duplicate ids with identical rows are fine; with different rows one
+ *   of them wins, and which one is unspecified.  Asynchronous on `stream`, no host copy (the first call on a grid brings the
+ *   cell -> vertex table to the device and synchronises, as the first nin_grid_update_points* does).  Counts in
+ *   nin_grid_field_updates.  n == 0 is a no-op.  NIN_ESTATE when no permeability is resident to patch.
+ * nin_weights_dirty_device: the marked nodes are binned by kernel on the device (ascending node id per kernel), the counts and the
+ *   refused-id counter come back in one 128-byte copy -- the ONLY synchronisation of the call (of `stream`) -- and the weight kernels run on
+ *   the lists.  Rows outside the set are not touched and nothing is zeroed.  clear != 0: the set is empty afterwards.  *n_recomputed
+ *   (may be NULL): the number of rows recomputed.  If ids were refused since the last dirty launch: NIN_EINVAL with the count in
+ *   nin_last_error(), nothing is launched, the set is kept and the counter starts again from zero.
+ *   "Everything is dirty" after nin_grid_to_device, a nin_fields_set with a permeability, nin_fields_set_permeability_device,
+ *   nin_grid_update_points* and nin_grid_dirty_reset(g, 1, ...): then the call is the ordinary full launch (and, with clear, ends that
+ *   state).  nin_weights_device never touches the set: two buffers may be served from one grid (clear = 0 for all but the last).
+ * nin_grid_dirty_nodes: the number of marked nodes; -1 when everything is dirty; 0 for a grid on no device.  A diagnostic: it waits for
+ *   the WHOLE device (a scatter may be in flight on any stream) and works on the null stream, so it stalls every stream of the
+ *   process -- not for a time loop (nin_weights_dirty_device returns the count of the rows it recomputed without that).
+ * nin_grid_dirty_reset: all_dirty = 0 empties the set -- "the caller's buffers hold a full result as of now" -- and forgets refused ids;
+ *   all_dirty != 0 marks everything (the Python layer does so when the Neumann flags of another variable are uploaded).  Asynchronous
+ *   on `stream`. */
+int nin_fields_scatter_permeability_device(nin_grid *g, const void *dev_cell_ids, int ids_are_int64, int64_t n,
+                                           const double *dev_permeability, const double *dev_scale, void *stream);
+int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *dev_csr_data, double *dev_neumann_ws, void *stream,
+                             int clear, int64_t *n_recomputed);
+int64_t nin_grid_dirty_nodes(nin_grid *g);
+int nin_grid_dirty_reset(nin_grid *g, int all_dirty, void *stream);
+
 /* ---- the hot path -------------------------------------------------------------------------
  * Replaces supported_methods[method](grid, ..., target_points, weights, neumann_ws)
  * (interpolator.pyx:657-665 -> idw.pyx:14-84, ls.pyx:21-135, gls.pyx:38-474).

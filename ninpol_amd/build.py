@@ -40,6 +40,8 @@ UNITS = [
     ("grid_update.hip", "hipcc", ["-ffp-contract=off"]),
     # permeability from device memory: diff_mag must be pack_host.cpp's value bit for bit, so no contraction here either
     ("fields_update.hip", "hipcc", ["-ffp-contract=off"]),
+    # local permeability updates: the scatter's diff_mag is the same expression under the same flag
+    ("fields_scatter.hip", "hipcc", ["-ffp-contract=off"]),
     ("abi.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),

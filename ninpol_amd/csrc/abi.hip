@@ -372,6 +372,13 @@ int ensure_update_inputs(nin_grid *g) {
     return NIN_OK;
 }
 
+// the points per cell of the element types, one byte each (grid_update.hip, fields_scatter.hip)
+uint64_t pack_npoel8(const HostGrid &h) {
+    uint64_t npoel8 = 0;
+    for (int t = 0; t < kNumElementTypes; ++t) npoel8 |= (uint64_t)(h.npoel[t] & 0xff) << (8 * t);
+    return npoel8;
+}
+
 // xyz [P][cd] on the host (then stream = the null stream and the call waits) or on the grid's device
 int update_points_on_device(nin_grid *g, const double *xyz, bool on_host, int cd, hipStream_t stream) {
     DeviceGrid &d = g->d;
@@ -396,8 +403,7 @@ int update_points_on_device(nin_grid *g, const double *xyz, bool on_host, int cd
         }
         if (!rc && launch_update_coords(on_host ? staged : xyz, cd, (int64_t)P, coords, stream)) rc = fail(NIN_EHIP, "coordinate copy: %s", hipGetErrorString(hipGetLastError()));
     }
-    uint64_t npoel8 = 0;
-    for (int t = 0; t < kNumElementTypes; ++t) npoel8 |= (uint64_t)(h.npoel[t] & 0xff) << (8 * t);
+    const uint64_t npoel8 = pack_npoel8(h);
     if (!rc && launch_update_geometry(d.v, npoel8, d.up_inpoel, d.up_etype, d.up_inpofa, const_cast<double *>(d.v.centroids),
                                       const_cast<double *>(d.v.face_center), const_cast<float *>(d.v.face_normal), d.up_areas, stream))
         rc = fail(NIN_EHIP, "geometry kernels: %s", hipGetErrorString(hipGetLastError()));
@@ -413,6 +419,7 @@ int update_points_on_device(nin_grid *g, const double *xyz, bool on_host, int cd
     h.have &= ~A_GEOMETRY;
     if (!h.lazy) h.lazy.reset(new GeometryMirror(&g->d));
     ++d.geom_updates;
+    d.all_dirty = true;   // every row reads the geometry
     return rc;
 }
 // ---- the GLS launch plan (gls_plan.hpp): the two functions that switch over the launcher family -------------------------------
@@ -473,15 +480,16 @@ int build_gls_plan(nin_grid *g) {
     const bool force_global = getenv("NIN_GLS_FORCE_GLOBAL") != nullptr;   // testing switch: systems in global scratch
     int64_t need_max[kGlsClasses] = {0}, rows_max[kGlsClasses] = {0}, cols_max[kGlsClasses] = {0};
     {
-        uint8_t *dcls = nullptr;
+        uint8_t *dcls = nullptr;   // stays resident (P bytes): a dirty launch bins its nodes on the device (fields_scatter.hip)
         unsigned long long *dmax = nullptr, hmax[3 * kGlsClasses];
-        HIP_TRY(hipMalloc((void **)&dcls, (size_t)P));
-        if (hipMalloc((void **)&dmax, sizeof hmax) != hipSuccess) { (void)hipFree(dcls); return fail(NIN_ENOMEM, "hipMalloc"); }
+        if ((rc = dev_alloc(d, &dcls, (size_t)P))) return rc;
+        d.node_class = dcls;
+        if (hipMalloc((void **)&dmax, sizeof hmax) != hipSuccess) return fail(NIN_ENOMEM, "hipMalloc");
         hipError_t e1 = hipMemset(dmax, 0, sizeof hmax);
         const int lrc = launch_classify(d.v, use_group, force_global, dcls, dmax, nullptr);
         if (e1 == hipSuccess) e1 = hipMemcpy(g->node_class.data(), dcls, (size_t)P, hipMemcpyDeviceToHost);
         if (e1 == hipSuccess) e1 = hipMemcpy(hmax, dmax, sizeof hmax, hipMemcpyDeviceToHost);
-        (void)hipFree(dcls); (void)hipFree(dmax);
+        (void)hipFree(dmax);
         if (lrc || e1 != hipSuccess) return fail(NIN_EHIP, "node classification: %s", hipGetErrorString(e1));
         for (int c = 0; c < kGlsClasses; ++c) { need_max[c] = (int64_t)hmax[3 * c]; rows_max[c] = (int64_t)hmax[3 * c + 1]; cols_max[c] = (int64_t)hmax[3 * c + 2]; }
     }
@@ -811,6 +819,7 @@ int nin_fields_set(nin_grid *g, const double *permeability, const double *diff_m
         HIP_TRY(hipMemcpy(const_cast<double *>(d.v.perm), permeability, (size_t)E * 9 * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(const_cast<double *>(d.v.diff_mag), diff_mag, (size_t)E * 8, hipMemcpyHostToDevice));
         d.have_perm = true;
+        d.all_dirty = true;   // a full table: no record of which cells it changed
     }
     d.fields_set = true;
     return NIN_OK;
@@ -825,6 +834,7 @@ int nin_fields_set_permeability_device(nin_grid *g, const double *dev_permeabili
                                                     const_cast<double *>(d.v.diff_mag), static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(NIN_EHIP, "permeability kernel: %s", hipGetErrorString(e));
     d.have_perm = true;
+    d.all_dirty = true;
     ++d.field_updates;
     return NIN_OK;
 }
@@ -996,6 +1006,192 @@ int nin_weights_device(nin_grid *g, int method, const int64_t *targets, int64_t 
     (void)hipFree(dl0);
     if (sy != hipSuccess) return fail(NIN_EHIP, "target kernels: %s", hipGetErrorString(sy));
     if (rc) return fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+// ---- local permeability updates (fields_scatter.hip) ---------------------------------------------------------------
+namespace {
+
+// the marks and their header block: state of the grid from the first scatter on (P + 128 bytes)
+int ensure_dirty_state(DeviceGrid &d, int64_t P) {
+    if (d.dirty) return NIN_OK;
+    uint8_t *marks = nullptr;
+    int32_t *hdr = nullptr;
+    int rc = dev_alloc(d, &marks, (size_t)P);
+    if (!rc) rc = dev_alloc(d, &hdr, (size_t)kDirtyHdrInts);
+    if (!rc && (hipMemset(marks, 0, (size_t)P) != hipSuccess || hipMemset(hdr, 0, kDirtyHdrInts * sizeof(int32_t)) != hipSuccess))
+        rc = fail(NIN_EHIP, "zeroing the dirty set failed");
+    if (rc) { dev_release(d, marks); dev_release(d, hdr); return rc; }
+    d.dirty = marks; d.dirty_hdr = hdr;
+    return NIN_OK;
+}
+
+// a scratch buffer of the dirty launch with room for `count` elements: kept while it is large enough (hipFree waits for the device)
+extern "C++" {
+template <class T>
+int grow(DeviceGrid &d, T **buf, size_t *have, size_t count) {
+    if (*buf && *have >= count) return NIN_OK;
+    dev_release(d, *buf);
+    *buf = nullptr;
+    *have = 0;
+    const int rc = dev_alloc(d, buf, count);
+    if (!rc) *have = count;
+    return rc;
+}
+}
+
+// NIN_TIMING=1: HIP events on the launch's stream around its three phases -- compaction + read-back, descriptor kernels, weight
+// kernels -- and one line on stderr; the call then waits for its kernels (tools/time_update_fields.py --local reads the lines)
+struct DirtyLaps {
+    bool on = getenv("NIN_TIMING") != nullptr;
+    hipStream_t stream;
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit DirtyLaps(hipStream_t s) : stream(s) {}
+    ~DirtyLaps() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    void mark(int i) { if (on && !e[i] && hipEventCreate(&e[i]) == hipSuccess) (void)hipEventRecord(e[i], stream); }
+    void report(int64_t n) {
+        if (!on || !e[0] || !e[1] || !e[2] || !e[3] || hipEventSynchronize(e[3]) != hipSuccess) return;
+        float ms[3] = {0.f, 0.f, 0.f};
+        for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms[i], e[i], e[i + 1]);
+        fprintf(stderr, "[nin_dirty] nodes %lld compact+readback %.4f descriptors %.4f weights %.4f ms\n", (long long)n, ms[0], ms[1], ms[2]);
+    }
+};
+
+}  // namespace
+
+int nin_fields_scatter_permeability_device(nin_grid *g, const void *dev_cell_ids, int ids_are_int64, int64_t n, const double *dev_permeability,
+                                           const double *dev_scale, void *stream) {
+    if (!g) return fail(NIN_EINVAL, "NULL grid");
+    if (n < 0) return fail(NIN_EINVAL, "negative n");
+    if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
+    if (n == 0) return NIN_OK;
+    if (!dev_cell_ids || !dev_permeability) return fail(NIN_EINVAL, "NULL argument");
+    DeviceGrid &d = g->d;
+    if (!d.have_perm) return fail(NIN_ESTATE, "no permeability is resident to patch (nin_fields_set or nin_fields_set_permeability_device first)");
+    HIP_TRY(hipSetDevice(d.device));
+    int rc = ensure_update_inputs(g);   // inpoel / etype on the device: the first call brings them (synchronous), as the first update of the points does
+    if (!rc) rc = ensure_dirty_state(d, g->h.n_points);
+    if (rc) return rc;
+    rc = launch_scatter_permeability(d.v, pack_npoel8(g->h), d.up_inpoel, d.up_etype, dev_cell_ids, ids_are_int64, n, dev_permeability, dev_scale,
+                                     d.dirty, d.dirty_hdr + kDirtyHdrRejected, static_cast<hipStream_t>(stream));
+    if (rc) return fail(rc, "scatter kernel: %s", hipGetErrorString(hipGetLastError()));
+    ++d.field_updates;
+    return NIN_OK;
+}
+
+int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *dev_csr_data, double *dev_neumann_ws, void *stream_, int clear,
+                             int64_t *n_recomputed) {
+    if (n_recomputed) *n_recomputed = 0;
+    if (!g || !dev_csr_data || !dev_neumann_ws) return fail(NIN_EINVAL, "NULL argument");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the weight kernels are HIP only");
+    if (!d.fields_set) return fail(NIN_ESTATE, "nin_fields_set has not been called");
+    if (method != NIN_METHOD_GLS && method != NIN_METHOD_IDW && method != NIN_METHOD_LS) return fail(NIN_EINVAL, "unknown method %d", method);
+    const bool gls = method == NIN_METHOD_GLS;
+    if (gls && !d.have_perm) return fail(NIN_ESTATE, "GLS needs permeability and diff_mag");
+    if (gls && d.gls_too_large)
+        return fail(NIN_ERANGE, "a node's GLS system has more than 1024 rows (more than ~100 cells around one node): beyond the fallback kernel");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(d.device));
+    const int32_t P = (int32_t)g->h.n_points;
+    int32_t hdr[kDirtyHdrInts] = {0};
+    int rc = NIN_OK;
+    DirtyLaps laps(stream);   // NIN_TIMING=1: the call's three phases on stderr
+    laps.mark(0);
+    if (d.dirty) {   // (no scatter yet: no marks, no refused ids)
+        if (!d.all_dirty) {
+            const size_t ints = 2 * dirty_compact_hist_ints(P);   // the histogram and its scan
+            size_t tmp_bytes = 0;
+            if (dirty_compact_tmp_bytes(P, &tmp_bytes)) return fail(NIN_EHIP, "sizing the scan of the dirty set failed");
+            // both sized by the mesh alone: allocated by the first dirty launch (and again after nin_grid_release_scratch)
+            if (!d.dirty_hist && (rc = dev_alloc(d, &d.dirty_hist, ints))) return rc;
+            if (!d.dirty_lists && (rc = dev_alloc(d, &d.dirty_lists, (size_t)P))) return rc;
+            if ((rc = grow(d, reinterpret_cast<char **>(&d.dirty_tmp), &d.dirty_tmp_bytes, std::max<size_t>(tmp_bytes, 16)))) return rc;
+            if (launch_dirty_compact(P, gls ? 0 : 1, clear, d.dirty, d.node_class, d.dirty_hdr + kDirtyHdrRejected, d.dirty_hist,
+                                     d.dirty_hist + ints / 2, d.dirty_tmp, d.dirty_tmp_bytes, d.dirty_lists, d.dirty_hdr, stream))
+                return fail(NIN_EHIP, "compacting the dirty set: %s", hipGetErrorString(hipGetLastError()));
+        }
+        // the one synchronisation of the call: the lists' offsets and the refused-id counter, 128 bytes
+        HIP_TRY(hipMemcpyAsync(hdr, d.dirty_hdr, sizeof hdr, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (hdr[kDirtyHdrRejected] != 0) {   // the marks are as they were (the fill pass clears nothing while the counter is set)
+            HIP_TRY(hipMemsetAsync(d.dirty_hdr + kDirtyHdrRejected, 0, sizeof(int32_t), stream));
+            return fail(NIN_EINVAL, "%d cell ids outside [0, %lld) were given to nin_fields_scatter_permeability_device and written nowhere; "
+                        "nothing was launched, the dirty set is kept", (int)hdr[kDirtyHdrRejected], (long long)g->h.n_elems);
+        }
+    }
+    if (d.all_dirty) {   // the ordinary full launch
+        if ((rc = nin_weights_device(g, method, nullptr, 0, add_neumann, dev_csr_data, dev_neumann_ws, stream_))) return rc;
+        if (clear) {
+            if (d.dirty) HIP_TRY(hipMemsetAsync(d.dirty, 0, (size_t)P, stream));
+            d.all_dirty = false;
+        }
+        if (n_recomputed) *n_recomputed = P;
+        return NIN_OK;
+    }
+    const int32_t *off = hdr + kDirtyHdrOffsets;
+    const int32_t total = off[kGlsPlanKernels];
+    if (total < 0 || total > P) return fail(NIN_EHIP, "the dirty set's lists hold %d nodes of %d", (int)total, (int)P);
+    if (n_recomputed) *n_recomputed = total;
+    if (total == 0) return NIN_OK;
+    if (!gls) {   // one list
+        laps.mark(1); laps.mark(2);
+        rc = method == NIN_METHOD_IDW ? launch_idw(d.v, d.dirty_lists, total, 0, 0, dev_csr_data, dev_neumann_ws, stream)
+                                      : launch_ls(d.v, d.dirty_lists, total, 0, 0, dev_csr_data, dev_neumann_ws, stream);
+        if (rc) return fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        laps.mark(3);
+        laps.report(total);
+        return NIN_OK;
+    }
+    size_t desc_first[kGlsPlanKernels], words = 0;
+    for (int k = 0; k < kGlsPlanKernels; ++k) {
+        if (off[k + 1] < off[k]) return fail(NIN_EHIP, "the dirty set's lists are out of order");
+        desc_first[k] = words;
+        words += (size_t)(off[k + 1] - off[k]) * (size_t)gls_plan_row(k).desc_words;
+    }
+    if (words > d.dirty_desc_words && (rc = grow(d, &d.dirty_desc, &d.dirty_desc_words, words + words / 2))) return rc;
+    laps.mark(1);
+    for (int k = 0; k < kGlsPlanKernels; ++k)
+        if (launch_plan_desc(d, GlsKernel(k), d.dirty_lists + off[k], off[k + 1] - off[k], d.dirty_desc + desc_first[k], stream))
+            return fail(NIN_EHIP, "descriptor kernel of plan kernel %d", k);
+    HIP_TRY(hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream));   // the launches' work counters
+    laps.mark(2);
+    for (GlsKernel k : kMainOrder)   // (no side stream: every listed row is written by exactly one kernel, in any order)
+        if (!rc && off[k + 1] > off[k])
+            rc = launch_plan_kernel(d, k, d.dirty_lists + off[k], d.dirty_desc + desc_first[k], off[k + 1] - off[k], add_neumann, dev_csr_data,
+                                    dev_neumann_ws, stream);
+    if (rc) return fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    laps.mark(3);
+    laps.report(total);
+    return NIN_OK;
+}
+
+int64_t nin_grid_dirty_nodes(nin_grid *g) {
+    if (!g || g->d.device < 0 || g->d.prebuilt) return 0;
+    DeviceGrid &d = g->d;
+    if (d.all_dirty) return -1;
+    if (!d.dirty) return 0;
+    int32_t n = 0;
+    if (hipSetDevice(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||   // a scatter may be in flight on any stream
+        hipMemset(d.dirty_hdr + kDirtyHdrCount, 0, sizeof(int32_t)) != hipSuccess ||
+        launch_dirty_count((int32_t)g->h.n_points, d.dirty, d.dirty_hdr + kDirtyHdrCount, nullptr) ||
+        hipMemcpy(&n, d.dirty_hdr + kDirtyHdrCount, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)fail(NIN_EHIP, "counting the dirty nodes: %s", hipGetErrorString(hipGetLastError()));
+        return -2;
+    }
+    return n;
+}
+
+int nin_grid_dirty_reset(nin_grid *g, int all_dirty, void *stream) {
+    if (!g) return fail(NIN_EINVAL, "NULL grid");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
+    HIP_TRY(hipSetDevice(d.device));
+    if (!all_dirty && d.dirty) {   // the marks and the refused-id counter
+        HIP_TRY(hipMemsetAsync(d.dirty, 0, (size_t)g->h.n_points, static_cast<hipStream_t>(stream)));
+        HIP_TRY(hipMemsetAsync(d.dirty_hdr + kDirtyHdrRejected, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
+    }
+    d.all_dirty = all_dirty != 0;
     return NIN_OK;
 }
 
@@ -1253,6 +1449,12 @@ int nin_grid_release_scratch(nin_grid *g) {
     d.e2e_tmp_bytes = 0;
     d.apply_weights = nullptr;
     d.tr_cell_ptr = d.tr_cell_pos = d.tr_cell_node = nullptr;
+    // a dirty launch's lists, histogram, scan temporary and descriptors (the marks themselves and their header are state: they stay)
+    for (void *p : {(void *)d.dirty_lists, (void *)d.dirty_hist, d.dirty_tmp, (void *)d.dirty_desc}) dev_release(d, p);
+    d.dirty_lists = d.dirty_hist = nullptr;
+    d.dirty_tmp = nullptr;
+    d.dirty_desc = nullptr;
+    d.dirty_tmp_bytes = d.dirty_desc_words = 0;
     if (d.flag_staging) { (void)hipHostFree(d.flag_staging); d.flag_staging = nullptr; }
     // the connectivity copies of nin_grid_update_points*: kept while the device builder's mirror still fetches from them (they were its
     // own before the first update: no HBM is held that the grid did not hold anyway)

@@ -110,6 +110,21 @@ struct DeviceGrid {
     int64_t geom_updates = 0;
     void *ev_geom = nullptr;
     int64_t field_updates = 0;   // permeability updates from device memory (nin_fields_set_permeability_device, fields_update.hip)
+    // Local permeability updates (fields_scatter.hip).  node_class: the class bytes k_classify wrote, kept ([P]).  The dirty
+    // set: dirty [P] (1 = the node's row may have moved since the last clear) and dirty_hdr [kDirtyHdrInts] (launch.hpp), allocated by the
+    // first scatter and kept -- they are state, not scratch; all_dirty: everything is (a full nin_fields_set, a full permeability update,
+    // moved points: the marks are not looked at until a dirty launch clears the flag).  Scratch of a dirty launch, grown on demand, reused
+    // across calls and given back with the rest: the flat list buffer [P], the block histogram and its scan, the scan's temporary, the
+    // descriptors of the listed nodes.
+    const uint8_t *node_class = nullptr;
+    uint8_t *dirty = nullptr;
+    int32_t *dirty_hdr = nullptr;
+    bool all_dirty = true;
+    int32_t *dirty_lists = nullptr, *dirty_hist = nullptr;
+    void *dirty_tmp = nullptr;
+    size_t dirty_tmp_bytes = 0;
+    uint32_t *dirty_desc = nullptr;
+    size_t dirty_desc_words = 0;
     uint8_t *flag_staging = nullptr;   // page-locked [n_points]: nin_fields_set packs the node flags here and uploads from it
     void *copy_stream = nullptr, *copy_stream2 = nullptr;   // hipStream_t of the device-to-host copies that run under the kernels
     void *ev_weights = nullptr, *ev_scan = nullptr;   // hipEvent_t: weights written / row pointers scanned

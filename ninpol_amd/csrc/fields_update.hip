@@ -27,6 +27,7 @@
 
 #include <cstdint>
 
+#include "diff_mag.hpp"
 #include "launch.hpp"
 
 namespace nin {
@@ -35,13 +36,6 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int RUN = 9 * TPB;   // doubles of a workgroup's cells
-
-// the host's expression (pack_host.cpp: nin_diff_mag), operation for operation
-__device__ __forceinline__ double diff_mag_of(double k0, double k4, double k8) {
-    const double tr = (k0 + k4) + k8;
-    const double x = 1 - (3 * 1.0 / tr);
-    return x * x;
-}
 
 template <bool SCALED, bool ALIGNED16>
 __global__ __launch_bounds__(TPB) void nin_update_perm_kernel(int32_t E, const double *__restrict__ K, const double *__restrict__ scale,

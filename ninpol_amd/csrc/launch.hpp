@@ -132,6 +132,27 @@ int launch_update_geometry(const GridView &g, uint64_t npoel8, const int32_t *in
 hipError_t launch_update_permeability(int32_t n_elems, const double *dev_K, const double *dev_scale, double *perm, double *diff_mag,
                                       hipStream_t stream);
 
+// fields_scatter.hip: local permeability updates, all DEVICE pointers.
+// The header block of the dirty set (DeviceGrid::dirty_hdr): where each plan kernel's list begins in the flat list buffer
+// ([kGlsPlanKernels]: the total), the ids refused by scatters since the last dirty launch, and the cell of nin_grid_dirty_nodes
+constexpr int kDirtyHdrOffsets = 0, kDirtyHdrRejected = kGlsPlanKernels + 2, kDirtyHdrCount = kGlsPlanKernels + 3, kDirtyHdrInts = 32;
+static_assert(kDirtyHdrCount < kDirtyHdrInts, "the dirty set's header block is too small for the plan");
+// perm / diff_mag of the cells dev_ids[0 .. n) (int32, or int64 when ids_are_int64) from dev_K [n][9] and dev_scale [n] (null: none), and
+// dirty[v] = 1 for their vertices (inpoel [E][8], etype [E], npoel8 as launch_update_geometry); an id outside [0, n_elems) writes nothing
+// and adds one to *rejected
+int launch_scatter_permeability(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const void *dev_ids,
+                                int ids_are_int64, int64_t n, const double *dev_K, const double *dev_scale, uint8_t *dirty, int32_t *rejected,
+                                hipStream_t stream);
+// the marked nodes binned by plan kernel (single != 0: one list, IDW / LS) into `lists` [n_points], ascending node ids, list k at
+// hdr[kDirtyHdrOffsets + k] .. hdr[kDirtyHdrOffsets + k + 1]; hist / scanned: dirty_compact_hist_ints() ints each, tmp: the scan's
+// (dirty_compact_tmp_bytes).  clear != 0: the marks are cleared as they are read, unless *rejected is non-zero
+size_t dirty_compact_hist_ints(int32_t n_points);
+int dirty_compact_tmp_bytes(int32_t n_points, size_t *bytes);
+int launch_dirty_compact(int32_t n_points, int single, int clear, uint8_t *dirty, const uint8_t *node_class, const int32_t *rejected,
+                         int32_t *hist, int32_t *scanned, void *tmp, size_t tmp_bytes, int32_t *lists, int32_t *hdr, hipStream_t stream);
+// *out += the number of marked nodes
+int launch_dirty_count(int32_t n_points, const uint8_t *dirty, int32_t *out, hipStream_t stream);
+
 const char *kernel_name_idw();
 const char *kernel_name_ls();
 const char *kernel_name_gls();

@@ -233,6 +233,37 @@ class Grid:
             self._h, ctypes.c_void_p(K.data_ptr()), None if scale is None else ctypes.c_void_p(scale.data_ptr()), ctypes.c_void_p(stream)))
         self._perm_from_device = True
 
+    def scatter_permeability_device(self, cells, K, scale=None):
+        """Rows of the resident permeability from torch tensors on the grid's device (nin_fields_scatter_permeability_device):
+        cells int32 / int64 (m,), K float64 contiguous m * 9 values, scale None or float64 (m,).  The vertices of the cells join the
+        dirty set.  Asynchronous on torch's current stream; the arguments are checked by Interpolator.update_permeability, which is
+        the public way in."""
+        import torch
+        stream = torch.cuda.current_stream(K.device).cuda_stream
+        _lib.check(_lib.load().nin_fields_scatter_permeability_device(
+            self._h, ctypes.c_void_p(cells.data_ptr()), int(cells.dtype == torch.int64), int(cells.numel()), ctypes.c_void_p(K.data_ptr()),
+            None if scale is None else ctypes.c_void_p(scale.data_ptr()), ctypes.c_void_p(stream)))
+
+    @property
+    def dirty_nodes(self):
+        """How many nodes' weights may have moved since the last clear (nin_grid_dirty_nodes: waits for the device): the vertices of
+        the cells that update_permeability(cells=...) rewrote.  -1: every node -- after the grid went to the device, a full
+        permeability update, moved points, or the Neumann flags of another variable.  0 for a grid on no device.  A diagnostic: it
+        waits for the whole device and so stalls every stream -- not for a time loop (launch_dirty returns its count)."""
+        n = int(_lib.load().nin_grid_dirty_nodes(self._h))
+        if n < -1:
+            _lib.check(_lib.NIN_EHIP)
+        return n
+
+    def clear_dirty(self, stream=0):
+        """Empty the dirty set: the caller's weight buffers hold a full result as of now (nin_grid_dirty_reset; asynchronous on
+        `stream`).  DevicePlan.launch_dirty(clear=True) does the same behind its launch."""
+        _lib.check(_lib.load().nin_grid_dirty_reset(self._h, 0, ctypes.c_void_p(stream)))
+
+    def mark_all_dirty(self, stream=0):
+        """Every node is dirty: the next DevicePlan.launch_dirty is a full launch."""
+        _lib.check(_lib.load().nin_grid_dirty_reset(self._h, 1, ctypes.c_void_p(stream)))
+
     def fetch_permeability(self):
         """(permeability (n_elems, 9), diff_mag (n_elems,)) as resident on the device (nin_fields_get_permeability: waits for the
         device); None when the grid is on no device or holds no permeability there."""

@@ -139,6 +139,8 @@ def _upload_fields(grid, method, cells_data, points_data, variable_to_index, var
     if perm is not None:
         grid._perm_from_device = False   # the host table went over whatever a device update had left
     # the flags on the device belong to the GRID, not to a plan: remember whose they are (DevicePlan.ensure_current)
+    if grid._fields_variable is not None and grid._fields_variable != variable:
+        grid.mark_all_dirty()   # other flags: any row may differ from what a caller's buffers hold (DevicePlan.launch_dirty)
     grid._fields_variable = variable
     if check is not None:
         check.flag = flag
@@ -317,7 +319,7 @@ class Interpolator:
         cd = np.asarray(self.cells_data)
         return cd[v2i["permeability"]][:E * 9], cd[v2i["diff_mag"]][:E]
 
-    def update_permeability(self, K, scale=None):
+    def update_permeability(self, K, scale=None, cells=None):
         """Replace the permeability of the loaded mesh: K of shape (n_elems, 3, 3) or (n_elems, 9), optionally times a per-cell
         factor `scale` of shape (n_elems,) (mobility times absolute permeability: one multiplication per entry, rounded once).
         diff_mag follows.  Connectivity, geometry, Neumann flags and the GLS launch plan stay.
@@ -332,8 +334,25 @@ class Interpolator:
         need `torch.cuda.current_stream().synchronize()` first.  The `cells_data` rows are NOT touched: fetch_permeability() brings
         the device's values back.  Precedence: the device copy stays resident, through any number of interpolate() / refresh()
         calls, until the CONTENTS of the host rows change; an in-place edit of `cells_data` made afterwards wins at the next call
-        that reads the tables, exactly as an edit always did."""
+        that reads the tables, exactly as an edit always did.
+
+        `cells` (1-D integer ids in [0, n_elems), m of them): only those cells change; K is then (m, 3, 3) or (m, 9) and `scale` (m,),
+        row i for cell cells[i].  Duplicate ids with identical rows are fine; with different rows one of them wins, and which one is
+        unspecified.  The nodes whose weights can move -- the vertices of those cells -- join the grid's dirty set (Grid.dirty_nodes),
+        and DevicePlan.launch_dirty() recomputes exactly their rows.
+        `cells` a torch tensor (int32 / int64) on this Interpolator's device, K and scale float64 tensors there: the rows are scattered
+        into the resident table by a kernel on torch's current stream, with the rules of the device path above (no host copy, the
+        `cells_data` rows are not touched, fetch_permeability() brings the patched table back).  Ids are checked on the device: one
+        outside [0, n_elems) writes nothing, and the next launch_dirty() raises with the count.
+        `cells` a numpy array (or a list), K numpy: the rows of `cells_data` are rewritten in place for those cells; ids are checked
+        here (ValueError).  Works without a GPU.  If the grid is on a device and its resident table is the host rows' (not a newer
+        device copy), the same rows also go through the scatter (needs torch; synchronous), so the resident table and the dirty set
+        follow and the next call uploads nothing; otherwise the edit is found and uploaded whole by the next call that reads the
+        tables, as any in-place edit is -- and then every node is dirty.
+        Host and device arguments cannot be mixed (TypeError)."""
         perm_row, dmag_row = self._perm_rows()
+        if cells is not None:
+            return self._update_permeability_cells(K, scale, cells, perm_row, dmag_row)
         g = self.grid
         E = g.n_elems
         is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
@@ -387,6 +406,103 @@ class Interpolator:
         perm_row[:] = K9.reshape(-1)
         dmag_row[:] = self.compute_diffusion_magnitude(K9)
         g._perm_from_device = False  # the host rows are the newer ones now: the next call that reads the tables uploads them
+
+    def _update_permeability_cells(self, K, scale, cells, perm_row, dmag_row):
+        g = self.grid
+        E = g.n_elems
+        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
+        on_gpu = lambda a: is_torch(a) and getattr(a, "is_cuda", False)
+        if on_gpu(cells):
+            import torch
+            where = torch.device("cuda", self.device)
+            if cells.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"cells must be int32 or int64, not {cells.dtype} (no silent cast)")
+            if cells.device != where:
+                raise ValueError(f"cells must be on {where}, not {cells.device}")
+            if cells.dim() != 1:
+                raise ValueError(f"cells must have shape (m,), not {tuple(cells.shape)}")
+            m = int(cells.shape[0])
+
+            def checked(t, name, shapes):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                    raise TypeError(f"{name} must be a torch.Tensor on {where} when cells is, not " +
+                                    (f"one on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__))
+                if t.dtype != torch.float64:
+                    raise TypeError(f"{name} must be float64, not {t.dtype} (no silent cast)")
+                if t.device != where:
+                    raise ValueError(f"{name} must be on {where}, not {t.device}")
+                if tuple(t.shape) not in shapes:
+                    raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {tuple(t.shape)}")
+                return t.detach().contiguous()
+
+            Kd = checked(K, "K", ((m, 3, 3), (m, 9)))
+            sd = None if scale is None else checked(scale, "scale", ((m,),))
+            cd = cells.detach().contiguous()
+            if g.device < 0:
+                g.to_device(self.device)
+            if g._perm_key is None:
+                # nothing was ever uploaded to this device copy: the host table goes over first (through the device path: the same
+                # bits), and counts as seen from here on (see update_permeability)
+                g._perm_key = (_table_key(perm_row), _table_key(dmag_row))
+                g.load_permeability_device(torch.from_numpy(np.ascontiguousarray(perm_row)).to(where))
+            g.scatter_permeability_device(cd, Kd, sd)
+            g._perm_from_device = True
+            return
+        if on_gpu(K) or on_gpu(scale):
+            raise TypeError("K and scale must be on the host when cells is (a numpy array), not on " +
+                            str((K if on_gpu(K) else scale).device))
+        if is_torch(cells):
+            cells = cells.detach().numpy()
+        if is_torch(K):
+            K = K.detach().numpy()
+        if scale is not None and is_torch(scale):
+            scale = scale.detach().numpy()
+        ids = np.asarray(cells)
+        if ids.dtype.kind not in "iu":
+            raise TypeError(f"cells must be integers, not {ids.dtype} (no silent cast)")
+        if ids.ndim != 1:
+            raise ValueError(f"cells must have shape (m,), not {ids.shape}")
+        ids = ids.astype(np.int64)
+        m = len(ids)
+        bad = (ids < 0) | (ids >= E)
+        if bad.any():
+            raise ValueError(f"cells must lie in [0, {E}): {int(bad.sum())} of {m} do not (the first: {int(ids[bad][0])})")
+
+        def checked(a, name, shapes):
+            try:
+                a = np.asarray(a)
+                if a.dtype.kind == "f" and a.dtype != DTYPE_F:
+                    raise TypeError(f"{name} must be float64, not {a.dtype} (no silent cast)")
+                a = np.ascontiguousarray(a, dtype=DTYPE_F)
+            except ValueError as e:
+                raise ValueError(f"{name} cannot be converted to float64: {e}") from e
+            if a.shape not in shapes:
+                raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {a.shape}")
+            return a
+
+        K9 = checked(K, "K", ((m, 3, 3), (m, 9))).reshape(m, 9)
+        if scale is not None:
+            K9 = checked(scale, "scale", ((m,),))[:, None] * K9
+        if m == 0:
+            return
+        # is the resident table the host rows as they are NOW?  Only then can the device follow row by row
+        in_step = (g.device >= 0 and g._perm_key is not None and not g._perm_from_device and
+                   g._perm_key == (_table_key(perm_row), _table_key(dmag_row)))
+        perm_row.reshape(E, 9)[ids] = K9
+        dmag_row[ids] = self.compute_diffusion_magnitude(K9)
+        if in_step:
+            try:
+                import torch
+            except ImportError:
+                in_step = False
+        if in_step:
+            where = torch.device("cuda", g.device)
+            with torch.cuda.device(where):
+                g.scatter_permeability_device(torch.from_numpy(ids).to(where), torch.from_numpy(K9).to(where))
+                torch.cuda.current_stream(where).synchronize()
+            g._perm_key = (_table_key(perm_row), _table_key(dmag_row))   # the rows ARE the resident table: nothing to upload
+        else:
+            g._perm_from_device = False   # the host rows are the newer ones now: the next call that reads the tables uploads them
 
     def fetch_permeability(self):
         """The permeability resident on the device read back into the `permeability` and `diff_mag` rows of `cells_data` (after
@@ -750,6 +866,22 @@ class DevicePlan:
         _lib.check(_lib.load().nin_weights_device(self.grid._h, self.method_id, None, 0, int(bool(add_neumann)),
                                                   ctypes.c_void_p(csr_data_ptr), ctypes.c_void_p(neumann_ws_ptr),
                                                   ctypes.c_void_p(stream)))
+
+    def launch_dirty(self, csr_data_ptr, neumann_ws_ptr, stream=0, add_neumann=True, clear=True):
+        """Recompute, IN PLACE, the rows of the grid's dirty nodes only (nin_weights_dirty_device) -- after
+        Interpolator.update_permeability(cells=...) the vertices of the rewritten cells -- and return how many that were.  If the
+        buffers held a full result as of the last clear (Grid.clear_dirty() after a full launch(), or an earlier launch_dirty with
+        clear=True), they hold afterwards what launch() would write now, bit for bit; no other row is touched.  The call reads 128
+        bytes back (how many nodes each kernel gets) and so waits for `stream` once; everything else is asynchronous on it.
+        clear=False keeps the set (a second buffer follows).  While every node is dirty (Grid.dirty_nodes == -1) this is launch().
+        Raises if cell ids outside the mesh were scattered since the last call: nothing is launched, the set is kept, and the next
+        call goes through."""
+        self.ensure_current()
+        n = ctypes.c_int64(0)
+        _lib.check(_lib.load().nin_weights_dirty_device(self.grid._h, self.method_id, int(bool(add_neumann)), ctypes.c_void_p(csr_data_ptr),
+                                                        ctypes.c_void_p(neumann_ws_ptr), ctypes.c_void_p(stream), int(bool(clear)),
+                                                        ctypes.byref(n)))
+        return int(n.value)
 
     def launch_apply(self, u_cells_ptr, n_fields, node_values_ptr, neumann_ws_ptr, stream=0):
         """W . u on the device for n_fields cell fields (nin_apply_device): u [n_fields][n_elems] ->

@@ -67,11 +67,21 @@ class CellToNode(torch.nn.Module):
         self.plan.refresh()
         self._compute_weights()
 
-    def recompute_weights(self):
+    def recompute_weights(self, dirty_only=False):
         """Compute the weights again from what is resident on the device NOW -- after interp.update_permeability() or
         update_points() with device tensors on the same stream -- without reading the Interpolator's tables (refresh() does that).
-        Asynchronous on torch's current stream; outputs computed before keep the weights of their forward pass in backward."""
-        self._compute_weights()
+        Asynchronous on torch's current stream; outputs computed before keep the weights of their forward pass in backward.
+
+        dirty_only=True: only the rows of the grid's dirty nodes (after interp.update_permeability(cells=...): the vertices of those
+        cells) are computed, into CLONES of `weights` / `neumann_ws` that then replace them (DevicePlan.launch_dirty: reads the sizes
+        of its lists back, so it waits for the stream once), and the set is cleared.  While every node is dirty -- as it is until
+        the first clear after the grid went to the device -- the call is a full launch; from then on only the marked rows run.  The
+        set belongs to the grid: one module (or one DevicePlan buffer) per grid can be kept current this way."""
+        if not dirty_only:
+            return self._compute_weights()
+        w, nws = self.weights.clone(), self.neumann_ws.clone()
+        self.plan.launch_dirty(w.data_ptr(), nws.data_ptr(), self._stream(), add_neumann=True, clear=True)
+        self.weights, self.neumann_ws = w, nws
 
     def _spmv(self, weights, u):
         k = 1 if u.dim() == 1 else u.shape[0]

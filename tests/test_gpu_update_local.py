@@ -1,0 +1,483 @@
+"""Local permeability updates on the device: Interpolator.update_permeability(cells=...) scatters rows into the resident table and marks
+the vertices of those cells; DevicePlan.launch_dirty recomputes exactly the marked rows in place (csrc/fields_scatter.hip).  The
+yardstick throughout is a FRESH Interpolator loaded with a mesh that carries the patched K; comparisons are bit for bit
+(np.array_equal); GLS is also held to the oracle on the patched mesh within the suite's bars."""
+import numpy as np
+import pytest
+
+import util
+import test_gpu_update_fields as UF
+from ninpol_amd import mesh as M
+
+pytestmark = pytest.mark.gpu
+
+METHODS = UF.METHODS
+PLANE = UF.PLANE
+same, on_device, with_K, _loaded = UF.same, UF.on_device, UF.with_K, UF._loaded
+FULL, KEPT = -7.0, -9.0      # sentinels: "never written by the full launch", "not written by the dirty launch"
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def ids_on_device(ids, dtype=np.int64):
+    return _torch().from_numpy(np.ascontiguousarray(ids, dtype=dtype)).cuda()
+
+
+def verts_of(inpoel, cells):
+    """the distinct vertices of `cells`, from the host connectivity ((E, 8), -1 padded)"""
+    v = np.asarray(inpoel)[np.asarray(cells, dtype=np.int64)].reshape(-1)
+    return np.unique(v[v >= 0])
+
+
+def stream():
+    return _torch().cuda.current_stream().cuda_stream
+
+
+# ---- 1. the scatter kernel's corners -----------------------------------------------------------------------------------------------
+CORNERS = {"60_cells": lambda: M.hex_mesh(5, 4, 3), "4096_cells": lambda: M.hex_mesh(16)}
+CASES = ("m0", "m1", "m63", "m64", "m65", "all_shuffled", "duplicates")
+
+
+@pytest.fixture(scope="module", params=sorted(CORNERS))
+def corner(request):
+    mesh = M.attach_fields(CORNERS[request.param](), "u", perm="LIN", neumann_plane=PLANE, seed=2)
+    I = _loaded(mesh)
+    E = int(I.grid.n_elems)
+    assert E == int(request.param.split("_")[0])
+    I.update_permeability(on_device(UF.K_of(mesh, "LIN", 2)))      # the table is resident; everything is dirty
+    assert I.grid.dirty_nodes == -1
+    return {"I": I, "E": E, "inpoel": np.array(I.grid.inpoel), "table": UF.K_of(mesh, "LIN", 2).copy()}
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_scatter_corners(corner, case):
+    I, E, table = corner["I"], corner["E"], corner["table"]
+    rng = np.random.default_rng(len(case) + E)
+    if case == "all_shuffled":
+        ids = rng.permutation(E)
+    elif case == "duplicates":
+        ids = np.tile(rng.choice(E, size=20, replace=False), 2)
+    else:   # m distinct cells; on the 60-cell mesh m = 63 .. 65 repeats a few (with equal rows, as below)
+        m = int(case[1:])
+        order = rng.permutation(E)
+        ids = np.concatenate([order[:min(m, E)], order[:max(m - E, 0)]])
+    m = len(ids)
+    combos = [(scaled, dt, as_33) for scaled in (False, True) for dt in (np.int32, np.int64) for as_33 in (False, True)]
+    for j, (scaled, dt, as_33) in enumerate(combos):
+        A = rng.uniform(-0.3, 0.3, (E, 3, 3))
+        K = (A @ A.transpose(0, 2, 1) + (1.0 + j) * np.eye(3)).reshape(E, 9)[ids]     # a row per CELL: duplicate ids carry equal rows
+        scale = rng.uniform(0.1, 10.0, E)[ids] if scaled else None
+        table[ids] = scale[:, None] * K if scaled else K           # the host's arithmetic: numpy's product
+        I.grid.clear_dirty()
+        n0 = I.grid.field_updates
+        I.update_permeability(on_device(K.reshape(m, 3, 3) if as_33 else K), scale=None if scale is None else on_device(scale),
+                              cells=ids_on_device(ids, dt))
+        what = (case, scaled, dt.__name__, as_33)
+        assert I.grid.field_updates == n0 + (1 if m else 0) and I.permeability_on_device, what
+        got = I.grid.fetch_permeability()
+        assert same(got[0], table), (what, "perm")
+        assert same(got[1], I.compute_diffusion_magnitude(table)), (what, "diff_mag")
+        assert I.grid.dirty_nodes == len(verts_of(corner["inpoel"], ids)), what
+    assert same(I.fetch_permeability().reshape(E, 9), table)
+    assert same(UF.rows(I)[0], table.reshape(-1)) and same(UF.rows(I)[1], I.compute_diffusion_magnitude(table))
+
+
+# ---- 2 .. 5: every kernel of the plan, in place ------------------------------------------------------------------------------------
+def _composite(perm, seed0):
+    parts = UF._parts() + [M.delaunay_tet_mesh(6, lattice="random", seed=4)]
+    for i, p in enumerate(parts):
+        M.attach_fields(p, "u", perm=perm, neumann_plane=PLANE, seed=seed0 + i)
+    return M.composite_mesh(parts)
+
+
+def _buffers(plan, fill):
+    torch = _torch()
+    return (torch.full((plan.nnz,), fill, dtype=torch.float64, device="cuda"),
+            torch.full((plan.n_points,), fill, dtype=torch.float64, device="cuda"))
+
+
+def _host(bufs):
+    _torch().cuda.synchronize()
+    return bufs[0].cpu().numpy(), bufs[1].cpu().numpy()
+
+
+class Ctx:
+    """a mesh with K0, a second table K1, the host connectivity, the owner kernel of every node and fresh launches on demand"""
+
+    def __init__(self, mesh, K1):
+        from ninpol_amd.interpolator import DevicePlan
+        self.mesh, self.K1 = mesh, K1
+        self.K0 = np.ascontiguousarray(np.concatenate(mesh.cell_data["permeability"]))
+        I = _loaded(mesh)
+        dp = DevicePlan(I, "u", "gls")
+        g = I.grid
+        self.E, self.P = int(g.n_elems), int(g.n_points)
+        self.inpoel = np.array(g.inpoel)
+        self.esup, self.esup_ptr = np.array(g.esup), np.array(g.esup_ptr)
+        self.rows = np.repeat(np.arange(self.P), np.diff(self.esup_ptr))
+        self.plan = dict(g.gls_plan())
+        # NIN_GLS_ONLY=<k>: the rows kernel k writes, launched alone into NaN-filled buffers
+        self.owner = np.full(self.P, -1)
+        with pytest.MonkeyPatch.context() as mp:
+            for k, name in enumerate(g.PLAN_KERNELS):
+                if not self.plan[name]:
+                    continue
+                mp.setenv("NIN_GLS_ONLY", str(k))
+                b = _buffers(dp, np.nan)
+                dp.launch(b[0].data_ptr(), b[1].data_ptr(), stream())
+                mine = np.flatnonzero(~np.isnan(_host(b)[1]))
+                assert len(mine) == self.plan[name] and (self.owner[mine] == -1).all(), name
+                self.owner[mine] = k
+        assert (self.owner >= 0).all()
+        self._fresh = {}
+
+    def fresh(self, K, meth, add_neumann, tag):
+        """csr_data and neumann_ws of a DevicePlan.launch of a fresh Interpolator on the mesh carrying K"""
+        key = (tag, meth, add_neumann)
+        if key not in self._fresh:
+            from ninpol_amd.interpolator import DevicePlan
+            plan = DevicePlan(_loaded(with_K(self.mesh, K)), "u", meth)
+            b = _buffers(plan, FULL)
+            plan.launch(b[0].data_ptr(), b[1].data_ptr(), stream(), add_neumann=add_neumann)
+            self._fresh[key] = _host(b)
+        return self._fresh[key]
+
+    def cell_sets(self):
+        """(a) one cell, (b) ~3 % of the cells with a vertex in every non-empty plan kernel, (c) all cells"""
+        rng = np.random.default_rng(31)
+        b = [int(self.esup[self.esup_ptr[np.flatnonzero(self.owner == k)[0]]]) for k in sorted(set(self.owner.tolist()))]
+        extra = rng.choice(self.E, size=max(self.E * 3 // 100 - len(b), 1), replace=False)
+        b = rng.permutation(np.unique(np.concatenate([np.array(b, dtype=np.int64), extra])))
+        hit = set(self.owner[verts_of(self.inpoel, b)].tolist())
+        assert hit == set(self.owner.tolist()), "a plan kernel without a dirty node"
+        return {"a": np.array([self.E // 2]), "b": b, "c": rng.permutation(self.E)}
+
+
+@pytest.fixture(scope="module")
+def C():
+    mesh = _composite("LIN", 20)
+    K1 = np.ascontiguousarray(np.concatenate(_composite("ALH", 40).cell_data["permeability"]))
+    c = Ctx(mesh, K1)
+    p = c.plan
+    assert p["hex8"] > 0 and p["mfw_large"] + p["mfw_small"] > 0, p                                   # cube, two-coloured
+    assert sum(n for k, n in p.items() if k.startswith("mfx_")) > 0 and p["mfg_tiles"] > 0, p          # wide, tiles in global memory
+    assert p["quad4"] > 0 and p["small4"] + p["small8"] + p["small12"] > 0, p                          # quad, small
+    assert sum(n for k, n in p.items() if k.startswith("block")) > 0, p                                # block
+    return c
+
+
+def _start(c, meth, add_neumann):
+    """a fresh Interpolator with K0, one full launch into sentinel-filled buffers, a second pair of buffers holding the same result,
+    and the set cleared: both pairs hold a full result as of now"""
+    torch = _torch()
+    from ninpol_amd.interpolator import DevicePlan
+    I = _loaded(c.mesh)
+    plan = DevicePlan(I, "u", meth)
+    marked = _buffers(plan, FULL)
+    assert I.grid.dirty_nodes == -1
+    plan.launch(marked[0].data_ptr(), marked[1].data_ptr(), stream(), add_neumann=add_neumann)
+    assert I.grid.dirty_nodes == -1                                        # a full launch leaves the set alone
+    clean = (marked[0].clone(), marked[1].clone())
+    I.grid.clear_dirty(stream())
+    assert I.grid.dirty_nodes == 0
+    w0, n0 = c.fresh(c.K0, meth, add_neumann, "K0")
+    assert same(_host(marked)[0], w0) and same(_host(marked)[1], n0)
+    return I, plan, marked, clean
+
+
+def _one_set(c, I, plan, marked, clean, cells, K_now, tag, meth, add_neumann):
+    """scatter K1's rows of `cells`; the dirty launch into `marked` (whose other rows hold a second sentinel) keeps the set, the one
+    into `clean` clears it"""
+    torch = _torch()
+    I.update_permeability(on_device(c.K1[cells]), cells=ids_on_device(cells))
+    K_now[cells] = c.K1[cells]
+    dirty = verts_of(c.inpoel, cells)
+    assert I.grid.dirty_nodes == len(dirty), tag
+    on = np.zeros(c.P, dtype=bool)
+    on[dirty] = True
+    on_rows = on[c.rows]
+    marked[0][torch.from_numpy(~on_rows).cuda()] = KEPT
+    marked[1][torch.from_numpy(~on).cuda()] = KEPT
+    n = plan.launch_dirty(marked[0].data_ptr(), marked[1].data_ptr(), stream(), add_neumann=add_neumann, clear=False)
+    assert n == len(dirty) and I.grid.dirty_nodes == len(dirty), tag
+    n = plan.launch_dirty(clean[0].data_ptr(), clean[1].data_ptr(), stream(), add_neumann=add_neumann, clear=True)
+    assert n == len(dirty) and I.grid.dirty_nodes == 0, tag
+    fw, fn = c.fresh(K_now, meth, add_neumann, tag)
+    w, nws = _host(marked)
+    assert same(w[on_rows], fw[on_rows]) and same(nws[on], fn[on]), (tag, "dirty rows")
+    assert (w[~on_rows] == KEPT).all() and (nws[~on] == KEPT).all(), (tag, "a row outside the set was written")
+    w, nws = _host(clean)
+    assert same(w, fw) and same(nws, fn), (tag, "the whole buffer: a row outside the marked set depended on the changed cells")
+    marked[0].copy_(clean[0])
+    marked[1].copy_(clean[1])
+    return w, nws
+
+
+def _oracle_check(oracle_lib, c, K, w, nws, what):
+    import scipy.sparse as sp
+    o = oracle_lib.OracleInterpolator("port", threads=8)
+    o.load_mesh(with_K(c.mesh, K))
+    Wo, nwo = o.interpolate("u", "gls")
+    W = sp.csr_matrix((w, c.esup.astype(Wo.indices.dtype), c.esup_ptr.astype(Wo.indptr.dtype)), shape=(c.P, c.E))
+    W.eliminate_zeros()
+    err = util.csr_rowscaled_err(W, Wo.indptr, Wo.indices, Wo.data)
+    el = util.csr_elementwise_err(W, Wo.indptr, Wo.indices, Wo.data)
+    print(f"{what}: GLS after a local update vs oracle on the patched mesh: row-scaled {err:.3e}, element-wise {el:.3e}")
+    assert err <= util.WEIGHT_RTOL
+    assert el <= util.ELEMENTWISE_RTOL_GLS
+    assert util.rowscaled_err(nws, nwo) <= util.WEIGHT_RTOL
+
+
+@pytest.mark.parametrize("add_neumann", (True, False), ids=("add_neumann", "plain"))
+@pytest.mark.parametrize("meth", METHODS)
+def test_every_kernel_in_place(C, oracle_lib, meth, add_neumann):
+    I, plan, marked, clean = _start(C, meth, add_neumann)
+    sets = C.cell_sets()
+    K_now = C.K0.copy()
+    for name in ("a", "b", "c"):
+        w, nws = _one_set(C, I, plan, marked, clean, sets[name], K_now, name, meth, add_neumann)
+        if name == "b" and meth == "gls" and add_neumann:
+            _oracle_check(oracle_lib, C, K_now, w, nws, "composite")
+    assert same(K_now, C.K1)
+    if meth == "gls":
+        assert not same(w, C.fresh(C.K0, meth, add_neumann, "K0")[0])                        # K matters to GLS
+    assert same(I.grid.fetch_permeability()[0], C.K1)
+
+
+# ---- 3. a relabelled mesh -------------------------------------------------------------------------------------------------------------
+def test_relabelled_mesh(C, oracle_lib):
+    mesh = M.relabel_mesh(C.mesh, 5)
+    c = Ctx(mesh, UF.K_of(mesh, "ALH", 61))
+    I, plan, marked, clean = _start(c, "gls", True)
+    K_now = c.K0.copy()
+    w, nws = _one_set(c, I, plan, marked, clean, c.cell_sets()["b"], K_now, "b", "gls", True)
+    _oracle_check(oracle_lib, c, K_now, w, nws, "relabelled composite")
+
+
+# ---- 4. accumulation and flags -------------------------------------------------------------------------------------------------------
+def test_accumulation_and_the_all_dirty_flag(C):
+    torch = _torch()
+    I, plan, marked, clean = _start(C, "gls", True)
+    sets = C.cell_sets()
+    one, two = sets["b"][: len(sets["b"]) // 2], sets["b"][len(sets["b"]) // 3:]               # overlapping
+    K_now = C.K0.copy()
+    I.update_permeability(on_device(C.K1[one]), cells=ids_on_device(one, np.int32))
+    I.update_permeability(on_device(C.K1[two]), cells=ids_on_device(two))
+    K_now[sets["b"]] = C.K1[sets["b"]]
+    union = verts_of(C.inpoel, sets["b"])
+    assert I.grid.dirty_nodes == len(union)
+    # a full launch leaves the set alone
+    other = _buffers(plan, FULL)
+    plan.launch(other[0].data_ptr(), other[1].data_ptr(), stream())
+    assert I.grid.dirty_nodes == len(union)
+    fw, fn = C.fresh(K_now, "gls", True, "b_only")
+    assert same(_host(other)[0], fw)
+    # clear=False serves two buffers in turn
+    assert plan.launch_dirty(marked[0].data_ptr(), marked[1].data_ptr(), stream(), clear=False) == len(union)
+    assert I.grid.dirty_nodes == len(union)
+    assert plan.launch_dirty(clean[0].data_ptr(), clean[1].data_ptr(), stream()) == len(union)
+    assert I.grid.dirty_nodes == 0
+    for b in (marked, clean):
+        assert same(_host(b)[0], fw) and same(_host(b)[1], fn)
+    assert plan.launch_dirty(clean[0].data_ptr(), clean[1].data_ptr(), stream()) == 0          # nothing to do
+    assert same(_host(clean)[0], fw)
+    # a full update from the device: everything is dirty, and the next dirty launch is a full launch
+    I.update_permeability(on_device(C.K1))
+    assert I.grid.dirty_nodes == -1
+    stale = _buffers(plan, KEPT)
+    assert plan.launch_dirty(stale[0].data_ptr(), stale[1].data_ptr(), stream()) == C.P
+    assert I.grid.dirty_nodes == 0
+    f1 = C.fresh(C.K1, "gls", True, "c")
+    assert same(_host(stale)[0], f1[0]) and same(_host(stale)[1], f1[1])
+    # moved points: the same
+    X = np.asarray(C.mesh.points, dtype=np.float64).copy()
+    I.update_points(on_device(X))
+    assert I.grid.dirty_nodes == -1
+    stale = _buffers(plan, KEPT)
+    assert plan.launch_dirty(stale[0].data_ptr(), stale[1].data_ptr(), stream(), clear=False) == C.P
+    assert I.grid.dirty_nodes == -1                                                           # kept: a second buffer may follow
+    assert same(_host(stale)[0], f1[0]) and same(_host(stale)[1], f1[1])
+    I.grid.clear_dirty()
+    assert I.grid.dirty_nodes == 0
+
+
+# ---- 5. a loop without the host ------------------------------------------------------------------------------------------------------
+def test_loop_without_the_host(C):
+    torch = _torch()
+    I, plan, marked, clean = _start(C, "gls", True)
+    cen = M.cell_centroids(C.mesh)
+    lo, hi = cen.min(axis=0), cen.max(axis=0)
+    rng = np.random.default_rng(77)
+    K_now = C.K0.copy()
+    steps = []
+    for s in range(10):   # a box a third of the mesh wide, moving along x
+        a = lo[0] + (hi[0] - lo[0]) * (s / 12.0)
+        cells = np.flatnonzero((cen[:, 0] >= a) & (cen[:, 0] <= a + (hi[0] - lo[0]) / 3.0) & (cen[:, 1] <= lo[1] + 0.6 * (hi[1] - lo[1])))
+        assert len(cells) > 0
+        rows = rng.uniform(0.5, 2.0, (len(cells), 1)) * C.K1[cells]
+        K_now[cells] = rows
+        steps.append((ids_on_device(cells), on_device(rows)))
+    # the host tables are poison from here on: nothing in the loop may read them
+    v2i = I.variable_to_index["cells"]
+    I.cells_data[v2i["permeability"], :] = np.nan
+    I.cells_data[v2i["diff_mag"], :] = np.nan
+    torch.cuda.synchronize()
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        for ids, rows in steps:
+            I.update_permeability(rows, cells=ids)
+            assert plan.launch_dirty(clean[0].data_ptr(), clean[1].data_ptr(), st.cuda_stream) > 0
+    st.synchronize()
+    assert I.grid.dirty_nodes == 0 and I.permeability_on_device
+    fw, fn = C.fresh(K_now, "gls", True, "loop")
+    assert same(_host(clean)[0], fw) and same(_host(clean)[1], fn)
+    assert not same(fw, C.fresh(C.K0, "gls", True, "K0")[0])
+
+
+# ---- 6. CellToNode.recompute_weights(dirty_only=True) ----------------------------------------------------------------------------------
+def test_cell_to_node_dirty_only(monkeypatch):
+    torch = _torch()
+    from ninpol_amd.torch_ops import CellToNode
+    monkeypatch.setenv("NIN_APPLY_NO_FUSION", "1")
+    small = M.attach_fields(M.mixed_mesh(4, 3, 3, jitter=0.1, seed=2), "u", perm="LIN", neumann_plane=PLANE, seed=3)
+    I = _loaded(small)
+    E = int(I.grid.n_elems)
+    K0, K1 = UF.K_of(small, "LIN", 3), UF.K_of(small, "ALH", 8)
+    cells = np.random.default_rng(4).choice(E, size=E // 5, replace=False)
+    K_new = K0.copy()
+    K_new[cells] = K1[cells]
+    op = CellToNode(I, "u", "gls")
+    I.grid.clear_dirty()                                   # op.weights is a full result as of now
+    u = torch.from_numpy(np.random.default_rng(17).uniform(0.5, 1.5, E)).cuda().requires_grad_(True)
+    g_out = torch.from_numpy(np.random.default_rng(18).uniform(-1.0, 1.0, I.grid.n_points)).cuda()
+    y_old = op(u)
+    old_weights = op.weights
+    I.update_permeability(on_device(K1[cells]), cells=ids_on_device(cells))
+    assert same(op(u).detach().cpu().numpy(), y_old.detach().cpu().numpy())      # nothing recomputes behind the caller's back
+    op.recompute_weights(dirty_only=True)
+    assert I.grid.dirty_nodes == 0 and op.weights is not old_weights
+    fresh_op = CellToNode(_loaded(with_K(small, K_new)), "u", "gls")
+    assert same(op.weights.cpu().numpy(), fresh_op.weights.cpu().numpy())
+    assert same(op.neumann_ws.cpu().numpy(), fresh_op.neumann_ws.cpu().numpy())
+    assert not same(op.weights.cpu().numpy(), old_weights.cpu().numpy())
+    u2 = u.detach().clone().requires_grad_(True)
+    uf = u.detach().clone().requires_grad_(True)
+    y_new, y_fresh = op(u2), fresh_op(uf)
+    assert same(y_new.detach().cpu().numpy(), y_fresh.detach().cpu().numpy())
+    y_new.backward(g_out)
+    y_fresh.backward(g_out)
+    assert same(u2.grad.cpu().numpy(), uf.grad.cpu().numpy())
+    # an output computed before the update keeps its old weights in backward
+    y_old.backward(g_out)
+    old_op = CellToNode(_loaded(small), "u", "gls")
+    uo = u.detach().clone().requires_grad_(True)
+    old_op(uo).backward(g_out)
+    assert same(u.grad.cpu().numpy(), uo.grad.cpu().numpy())
+    assert not same(u.grad.cpu().numpy(), u2.grad.cpu().numpy())
+
+
+# ---- 7. errors -------------------------------------------------------------------------------------------------------------------------
+def test_ids_outside_the_mesh(C):
+    from ninpol_amd._lib import NinpolError
+    I, plan, marked, clean = _start(C, "gls", True)
+    good = C.cell_sets()["b"][:40]
+    ids = np.concatenate([good[:20], [C.E], good[20:], [-1]])
+    rows = np.concatenate([C.K1[good[:20]], np.full((1, 9), 5.0), C.K1[good[20:]], np.full((1, 9), 6.0)])
+    K_now = C.K0.copy()
+    K_now[good] = C.K1[good]
+    dirty = verts_of(C.inpoel, good)
+    for dt in (np.int64, np.int32):
+        I.update_permeability(on_device(rows), cells=ids_on_device(ids, dt))
+        probe = _buffers(plan, KEPT)
+        with pytest.raises(NinpolError, match=r"\b2 cell ids outside"):
+            plan.launch_dirty(probe[0].data_ptr(), probe[1].data_ptr(), stream())
+        assert same(I.grid.fetch_permeability()[0], K_now), "the valid rows were written, and nothing else"
+        assert I.grid.dirty_nodes == len(dirty), "the set is kept"
+        assert (_host(probe)[0] == KEPT).all() and (_host(probe)[1] == KEPT).all(), "nothing was launched"
+        assert plan.launch_dirty(clean[0].data_ptr(), clean[1].data_ptr(), stream(), clear=(dt is np.int32)) == len(dirty)
+    assert I.grid.dirty_nodes == 0
+    fw, fn = C.fresh(K_now, "gls", True, "errors")
+    assert same(_host(clean)[0], fw) and same(_host(clean)[1], fn)
+
+
+def test_input_errors():
+    torch = _torch()
+    small = M.attach_fields(M.mixed_mesh(4, 3, 3, jitter=0.1, seed=2), "u", perm="LIN", neumann_plane=PLANE, seed=3)
+    I = _loaded(small)
+    E = int(I.grid.n_elems)
+    K = on_device(UF.K_of(small, "ALH", 8)[:5])
+    ids = ids_on_device(np.arange(5))
+    scale = on_device(np.ones(5))
+    host_rows = UF.rows(I)
+    with pytest.raises(TypeError, match="int32 or int64"):
+        I.update_permeability(K, cells=ids.to(torch.int16))
+    with pytest.raises(TypeError, match="int32 or int64"):
+        I.update_permeability(K, cells=ids.double())
+    with pytest.raises(TypeError, match="float64"):
+        I.update_permeability(K.float(), cells=ids)
+    with pytest.raises(TypeError, match="float64"):
+        I.update_permeability(K, scale=scale.float(), cells=ids)
+    with pytest.raises(ValueError, match="shape"):
+        I.update_permeability(K, cells=ids.reshape(5, 1))
+    with pytest.raises(ValueError, match="shape"):
+        I.update_permeability(K[:4], cells=ids)
+    with pytest.raises(ValueError, match="shape"):
+        I.update_permeability(K.reshape(5, 9, 1), cells=ids)
+    with pytest.raises(ValueError, match="shape"):
+        I.update_permeability(K, scale=scale[:4], cells=ids)
+    # mixed host / device arguments
+    with pytest.raises(TypeError, match="K must be"):
+        I.update_permeability(K.cpu().numpy(), cells=ids)
+    with pytest.raises(TypeError, match="K must be"):
+        I.update_permeability(K.cpu(), cells=ids)
+    with pytest.raises(TypeError, match="scale must be"):
+        I.update_permeability(K, scale=np.ones(5), cells=ids)
+    with pytest.raises(TypeError, match="on the host"):
+        I.update_permeability(K, cells=np.arange(5))
+    with pytest.raises(TypeError, match="on the host"):
+        I.update_permeability(K.cpu().numpy(), scale=scale, cells=np.arange(5))
+    import ninpol_amd
+    if torch.cuda.device_count() > 1:
+        with pytest.raises(ValueError, match="must be on cuda:0"):
+            I.update_permeability(K, cells=ids.to(torch.device("cuda", 1)))
+    else:       # one GPU visible: an Interpolator made for another device sees these tensors on the wrong one
+        J = ninpol_amd.Interpolator(device=1)
+        J.load_mesh(mesh_obj=small)
+        with pytest.raises(ValueError, match="must be on cuda:1"):
+            J.update_permeability(K, cells=ids)
+        assert J.grid.device == -1
+    assert I.grid.device == -1 and not I.permeability_on_device              # every refusal came before any side effect
+    assert same(UF.rows(I)[0], host_rows[0])
+
+
+def test_numpy_cells_follow_on_the_device(C):
+    """the host path on a grid whose resident table is the host rows': rows, resident copy and dirty set move together, and the next
+    call uploads nothing"""
+    I, plan, marked, clean = _start(C, "gls", True)
+    cells = C.cell_sets()["b"]
+    key0, n0 = I.grid._perm_key, I.grid.field_updates
+    I.update_permeability(C.K1[cells], cells=cells)
+    K_now = C.K0.copy()
+    K_now[cells] = C.K1[cells]
+    assert same(UF.rows(I)[0], K_now.reshape(-1)) and not I.permeability_on_device
+    assert I.grid.field_updates == n0 + 1 and I.grid._perm_key != key0
+    assert I.grid.dirty_nodes == len(verts_of(C.inpoel, cells))
+    assert same(I.grid.fetch_permeability()[0], K_now)
+    key1 = I.grid._perm_key
+    plan.refresh()                                                            # finds the table current: no upload, the set survives
+    assert I.grid._perm_key == key1 and I.grid.dirty_nodes == len(verts_of(C.inpoel, cells))
+    plan.launch_dirty(clean[0].data_ptr(), clean[1].data_ptr(), stream())
+    fw, fn = C.fresh(K_now, "gls", True, "b_only")
+    assert same(_host(clean)[0], fw) and same(_host(clean)[1], fn)
+    # behind a device-owned copy the host path is an edit like any other: the next call uploads the rows, and everything is dirty
+    I.update_permeability(on_device(C.K1))
+    I.update_permeability(C.K0[cells], cells=cells)
+    assert not I.permeability_on_device
+    plan.refresh()
+    assert I.grid.dirty_nodes == -1
+    K_host = K_now.copy()
+    K_host[cells] = C.K0[cells]
+    assert same(K_host, C.K0) and same(I.grid.fetch_permeability()[0], C.K0)

@@ -8,7 +8,13 @@ Per mesh (the 216^3 hexahedron mesh by default), GLS:
        K at a 16-byte aligned address and at an odd multiple of 8, with and without `scale`; with the bytes the update must move
        (72 in + 80 out per cell, + 8 with a scale) against the 6.29 TB/s copy rate DESIGN uses;
   and the launch alone, for scale.
---profile: only WARMUP + REPS device updates (for a rocprofv3 run around this script)."""
+--profile: only WARMUP + REPS device updates (for a rocprofv3 run around this script).
+--local FRACTION [FRACTION ...]: instead of (a) .. (c), the LOCAL step against the full step, calls interleaved in one session: the cells
+  inside a box at the middle of the mesh that holds that fraction of it; update_permeability(K_box, cells=box) + launch_dirty against
+  update_permeability(K) + launch, HIP events around each pair, median of REPS; and the scatter alone.  launch_dirty waits for the
+  stream once (it reads the lists' sizes back), so its events span that wait.  The split of the dirty launch into compaction +
+  read-back, descriptor kernels and weight kernels comes from the library's own HIP events around the three phases (NIN_TIMING=1 makes
+  nin_weights_dirty_device print them on stderr): REPS more local steps in the same session, median of each."""
 import os
 import sys
 import time
@@ -21,7 +27,8 @@ import ninpol_amd
 from ninpol_amd import mesh as M
 
 CASES = {"hex216": lambda: M.hex_mesh(216, jitter=0.15), "hex64": lambda: M.hex_mesh(64, jitter=0.15),
-         "del54": lambda: M.delaunay_tet_mesh(54, seed=0), "del20": lambda: M.delaunay_tet_mesh(20, seed=0)}
+         "del54": lambda: M.delaunay_tet_mesh(54, seed=0), "del20": lambda: M.delaunay_tet_mesh(20, seed=0),
+         "kuhn40": lambda: M.tet_mesh(40, jitter=0.1), "kuhn12": lambda: M.tet_mesh(12, jitter=0.1)}
 WARMUP, REPS, HOST_REPS = 5, 30, 5
 COPY_RATE = 6.29e12
 
@@ -47,8 +54,101 @@ def odd_view(t):
     return v
 
 
+def box_cells(mesh, fraction):
+    """the cells whose centroid lies in a box around the middle of the mesh that holds `fraction` of its volume"""
+    cen = M.cell_centroids(mesh)
+    lo, hi = cen.min(axis=0), cen.max(axis=0)
+    half = 0.5 * (hi - lo) * fraction ** (1.0 / 3.0)
+    mid = 0.5 * (lo + hi)
+    return np.flatnonzero(np.all(np.abs(cen - mid) <= half, axis=1)).astype(np.int64)
+
+
+def dirty_split(run, n):
+    """medians of the three phases nin_weights_dirty_device reports under NIN_TIMING=1 (stderr is read back through a file)"""
+    import re
+    import tempfile
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile(mode="w+") as tmp:
+        os.dup2(tmp.fileno(), 2)
+        os.environ["NIN_TIMING"] = "1"
+        try:
+            for i in range(n):
+                run(i)
+            torch.cuda.synchronize()
+        finally:
+            del os.environ["NIN_TIMING"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        rows = [tuple(map(float, m.groups())) for m in
+                re.finditer(r"\[nin_dirty\] nodes \d+ compact\+readback (\S+) descriptors (\S+) weights (\S+) ms", tmp.read())]
+    if len(rows) != n:   # (a launch with an empty set, or one that found everything dirty, reports no phases)
+        return [float("nan")] * 3
+    return [float(np.median([r[k] for r in rows])) for k in range(3)]
+
+
+def local_leg(name, mesh, I, plan, step, st, fractions, profile_only):
+    g = I.grid
+    E = int(g.n_elems)
+    v2i = I.variable_to_index["cells"]
+    K0 = np.array(I.cells_data[v2i["permeability"]][:E * 9]).reshape(E, 9)
+    k_full = [torch.from_numpy(K0).cuda(), torch.from_numpy(1.5 * K0).cuda()]
+    w = torch.empty(plan.nnz, dtype=torch.float64, device="cuda")
+    nws = torch.empty(int(g.n_points), dtype=torch.float64, device="cuda")
+    full = lambda i: (I.update_permeability(k_full[i & 1]), step())
+    for f in fractions:
+        cells = box_cells(mesh, f)
+        if len(cells) == 0:
+            print(f"{name}: --local {f:g}: the box holds no cell centroid of this mesh: skipped", flush=True)
+            continue
+        ids = torch.from_numpy(cells).cuda()
+        k_box = [k_full[0][ids].contiguous(), k_full[1][ids].contiguous()]
+        scatter = lambda i: I.update_permeability(k_box[i & 1], cells=ids)
+        dirty = lambda: plan.launch_dirty(w.data_ptr(), nws.data_ptr(), st.cuda_stream)
+        full(0)
+        plan.launch(w.data_ptr(), nws.data_ptr(), st.cuda_stream)
+        g.clear_dirty(st.cuda_stream)
+        n = 0
+        for i in range(WARMUP):
+            scatter(i)
+            n = dirty()
+        torch.cuda.synchronize()
+        if profile_only:
+            for i in range(REPS):
+                scatter(i)
+                dirty()
+            torch.cuda.synchronize()
+            continue
+        t_local, t_full, t_scatter, t_dirty = [], [], [], []
+        for i in range(REPS):   # interleaved: one local step, one full step
+            t_local.append(events_ms(lambda: (scatter(i), dirty()), st, 1)[0])
+            t_full.append(events_ms(lambda: full(i), st, 1)[0])
+            g.clear_dirty(st.cuda_stream)   # (the full update marked everything; w is not looked at)
+            t_scatter.append(events_ms(lambda: scatter(i), st, 1)[0])
+            t_dirty.append(events_ms(dirty, st, 1)[0])
+        med = lambda a: float(np.median(a))
+        split = dirty_split(lambda i: (scatter(i), dirty()), REPS)
+        print(f"{name}: --local {f:g}: {len(cells)} cells ({100.0 * len(cells) / E:.2f} %), {n} dirty nodes of {int(g.n_points)}: "
+              f"local step median {med(t_local):.3f} ms (min {min(t_local):.3f}, max {max(t_local):.3f}) = scatter {med(t_scatter):.3f} + "
+              f"launch_dirty {med(t_dirty):.3f}; full step median {med(t_full):.3f} ms (min {min(t_full):.3f}, max {max(t_full):.3f}) over {REPS}; "
+              f"full / local = {med(t_full) / med(t_local):.2f}", flush=True)
+        print(f"{name}: --local {f:g}: split of the local step, medians over {REPS}: scatter {med(t_scatter):.3f} ms, compaction + read-back "
+              f"{split[0]:.3f} ms, descriptor kernels {split[1]:.3f} ms, weight kernels {split[2]:.3f} ms", flush=True)
+
+
 def main():
-    names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["hex216"]
+    args = sys.argv[1:]
+    fractions = []
+    if "--local" in args:
+        j = args.index("--local") + 1
+        while j < len(args) and not args[j].startswith("--") and args[j] not in CASES:
+            fractions.append(float(args[j]))
+            j += 1
+        if not fractions:
+            raise SystemExit("--local needs at least one fraction, e.g. --local 0.001 0.01 0.1")
+        args = args[:args.index("--local")] + args[j:]
+    names = [a for a in args if not a.startswith("--")] or ["hex216"]
     profile_only = "--profile" in sys.argv
     if not torch.cuda.is_available():
         raise SystemExit("time_update_fields.py needs a GPU")
@@ -75,6 +175,11 @@ def main():
         s_dev = torch.from_numpy(scale_h).cuda()
         print(f"{name}: P={P} E={E}; K is {E * 72 / 1e9:.3f} GB", flush=True)
         upd = lambda i, K=k_dev, s=None: I.update_permeability(K[i & 1], scale=s)
+        if fractions:
+            local_leg(name, m, I, plan, step, st, fractions, profile_only)
+            I.release_scratch()
+            del plan, I
+            continue
         if profile_only:
             for i in range(WARMUP + REPS):
                 upd(i)
