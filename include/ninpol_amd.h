@@ -178,7 +178,7 @@ int64_t nin_grid_field_updates(const nin_grid *g);
  *   (may be NULL): the number of rows recomputed.  If ids were refused since the last dirty launch: NIN_EINVAL with the count in
  *   nin_last_error(), nothing is launched, the set is kept and the counter starts again from zero.
  *   "Everything is dirty" after nin_grid_to_device, a nin_fields_set with a permeability, nin_fields_set_permeability_device,
- *   nin_grid_update_points* and nin_grid_dirty_reset(g, 1, ...): then the call is the ordinary full launch (and, with clear, ends that
+ *   the whole-mesh nin_grid_update_points* and nin_grid_dirty_reset(g, 1, ...): then the call is the ordinary full launch (and, with clear, ends that
  *   state).  nin_weights_device never touches the set: two buffers may be served from one grid (clear = 0 for all but the last).
  * nin_grid_dirty_nodes: the number of marked nodes; -1 when everything is dirty; 0 for a grid on no device.  A diagnostic: it waits for
  *   the WHOLE device (a scatter may be in flight on any stream) and works on the null stream, so it stalls every stream of the
@@ -192,6 +192,32 @@ int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *d
                              int clear, int64_t *n_recomputed);
 int64_t nin_grid_dirty_nodes(nin_grid *g);
 int nin_grid_dirty_reset(nin_grid *g, int all_dirty, void *stream);
+
+/* ---- local mesh motion: move a subset of nodes, recompute only their rows -------------------------------------------------
+ * A row of node v reads coords[v], the centroids of the cells around v and the centres and normals of the faces around v.  Moving node p
+ * changes coords[p], the centroids of the cells around p and the centre, normal and area of the faces around p, and every such face lies
+ * in such a cell: the rows that can move are those of the vertices of the cells around the moved nodes, and no others.  These calls
+ * write the new coordinates, make the geometry of those cells and faces again -- bit for bit what the whole-mesh nin_grid_update_points*
+ * writes there, and it would change nothing elsewhere -- and mark those vertices in the dirty set of the block above (GLS, IDW and LS
+ * alike: every method reads the geometry); nin_weights_dirty_device then recomputes exactly the marked rows.  They do NOT make
+ * everything dirty.  Connectivity, fields, the GLS launch plan and all scratch stay, as for nin_grid_update_points*.
+ *
+ * nin_grid_scatter_points_device: dev_node_ids [n] node ids (int32, or int64 when ids_are_int64 != 0) and dev_xyz [n][coords_dim], row i
+ *   for node dev_node_ids[i], DEVICE arrays on the grid's device; coords_dim as at construction (columns beyond it stay zero).  Every id
+ *   is checked on the device before any access: an id outside [0, n_points) moves nothing, marks nothing and is counted in the counter
+ *   of nin_fields_scatter_permeability_device; the next nin_weights_dirty_device reports the count.  Duplicate ids with identical rows
+ *   are fine; with different rows one of them wins, which one is unspecified, and the geometry is that of the coordinates that ended up
+ *   in the grid.  Asynchronous on `stream` with the ordering rules of nin_grid_update_points_device (the first call on a grid brings the
+ *   connectivity to the device and allocates the dirty set, and synchronises); host reads of the five geometry arrays wait for the
+ *   update and fetch them again.  Counts in nin_grid_geometry_updates.  n == 0 is a no-op.  NIN_EINVAL for a NULL argument or a
+ *   coords_dim that is not the grid's, NIN_ENODEVICE when nin_grid_device(g) is -1.
+ * nin_grid_scatter_points: HOST arrays, int64 ids.  The ids are checked here: NIN_EINVAL with the count in nin_last_error() if any lies
+ *   outside [0, n_points), and nothing is moved.  A grid that holds device arrays: ids and rows are staged, the same kernels run, the
+ *   call waits.  A host-only grid: the host coordinates are patched and the host builder's geometry code runs over the mesh (there is
+ *   no dirty set without a device). */
+int nin_grid_scatter_points_device(nin_grid *g, const void *dev_node_ids, int ids_are_int64, int64_t n, const double *dev_xyz,
+                                   int coords_dim, void *stream);
+int nin_grid_scatter_points(nin_grid *g, const int64_t *node_ids, int64_t n, const double *xyz, int coords_dim);
 
 /* ---- the hot path -------------------------------------------------------------------------
  * Replaces supported_methods[method](grid, ..., target_points, weights, neumann_ws)

@@ -38,6 +38,8 @@ UNITS = [
     ("grid_device.hip", "hipcc", ["-ffp-contract=off"]),
     # geometry refresh of a moving mesh: the same arithmetic as grid_device.hip's geometry kernels, the same flag
     ("grid_update.hip", "hipcc", ["-ffp-contract=off"]),
+    # local mesh motion: the cells and faces around the moved nodes get grid_update.hip's arithmetic (geom_math.hpp) under the same flag
+    ("grid_scatter.hip", "hipcc", ["-ffp-contract=off"]),
     # permeability from device memory: diff_mag must be pack_host.cpp's value bit for bit, so no contraction here either
     ("fields_update.hip", "hipcc", ["-ffp-contract=off"]),
     # local permeability updates: the scatter's diff_mag is the same expression under the same flag

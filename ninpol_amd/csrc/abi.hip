@@ -350,6 +350,7 @@ int ensure_update_inputs(nin_grid *g) {
     if (h.lazy && h.lazy->lend_geometry_inputs(&gi)) {
         for (void *q : {(void *)gi.inpoel, (void *)gi.etype, (void *)gi.inpofa, (void *)gi.areas}) d.allocs.push_back(q);
         d.up_inpoel = gi.inpoel; d.up_etype = gi.etype; d.up_inpofa = gi.inpofa; d.up_areas = gi.areas;
+        d.up_areas_valid = true;   // the builder's own
         return NIN_OK;
     }
     std::string err;
@@ -369,6 +370,7 @@ int ensure_update_inputs(nin_grid *g) {
     up(inpofa, h.inpofa.data(), h.inpofa.size() * 4);
     if (rc) { dev_release(d, inpoel); dev_release(d, etype); dev_release(d, inpofa); dev_release(d, areas); return rc; }
     d.up_inpoel = inpoel; d.up_etype = etype; d.up_inpofa = inpofa; d.up_areas = areas;
+    d.up_areas_valid = false;   // room only: a whole-mesh update writes every area, a local one uploads the host's first
     return NIN_OK;
 }
 
@@ -419,6 +421,7 @@ int update_points_on_device(nin_grid *g, const double *xyz, bool on_host, int cd
     h.have &= ~A_GEOMETRY;
     if (!h.lazy) h.lazy.reset(new GeometryMirror(&g->d));
     ++d.geom_updates;
+    d.up_areas_valid = true;
     d.all_dirty = true;   // every row reads the geometry
     return rc;
 }
@@ -1075,7 +1078,102 @@ int nin_fields_scatter_permeability_device(nin_grid *g, const void *dev_cell_ids
     rc = launch_scatter_permeability(d.v, pack_npoel8(g->h), d.up_inpoel, d.up_etype, dev_cell_ids, ids_are_int64, n, dev_permeability, dev_scale,
                                      d.dirty, d.dirty_hdr + kDirtyHdrRejected, static_cast<hipStream_t>(stream));
     if (rc) return fail(rc, "scatter kernel: %s", hipGetErrorString(hipGetLastError()));
+    d.scattered_cells = true;
     ++d.field_updates;
+    return NIN_OK;
+}
+
+// ---- local mesh motion (grid_scatter.hip) ---------------------------------------------------------------------------
+namespace {
+
+// ids [n] (int32 / int64) and xyz [n][cd] on the host (then int64 ids, stream = the null stream and the call waits) or on the grid's device
+int scatter_points_on_device(nin_grid *g, const void *ids, int ids_are_int64, int64_t n, const double *xyz, bool on_host, int cd,
+                             hipStream_t stream) {
+    DeviceGrid &d = g->d;
+    HostGrid &h = g->h;
+    HIP_TRY(hipSetDevice(d.device));
+    int rc = ensure_update_inputs(g);   // the first call brings the connectivity (synchronous), as the first nin_grid_update_points* does
+    if (!rc) rc = ensure_dirty_state(d, h.n_points);
+    if (rc) return rc;
+    if (!d.up_areas_valid) {
+        // the device's face areas are room only (no whole-mesh update wrote them yet): the kernels below write the faces around the
+        // moved nodes, the others come from the host, which still holds them (only a geometry update on the device makes them stale)
+        std::string err;
+        if (h.ensure(A_AREAS, &err)) return fail(NIN_EHIP, "mirroring faces_areas: %s", err.c_str());
+        if (h.n_faces > 0) HIP_TRY(hipMemcpy(d.up_areas, h.faces_areas.data(), (size_t)h.n_faces * sizeof(double), hipMemcpyHostToDevice));
+        d.up_areas_valid = true;
+    }
+    if (!d.ev_geom) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        d.ev_geom = e;
+    }
+    void *staged_ids = nullptr;
+    double *staged_xyz = nullptr;
+    if (on_host) {
+        const size_t ib = (size_t)n * sizeof(int64_t), xb = (size_t)n * cd * sizeof(double);
+        HIP_TRY(hipMalloc(&staged_ids, ib));
+        if (hipMalloc((void **)&staged_xyz, xb) != hipSuccess) rc = fail(NIN_ENOMEM, "hipMalloc(%zu bytes) for the moved rows", xb);
+        if (!rc && (hipMemcpy(staged_ids, ids, ib, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(staged_xyz, xyz, xb, hipMemcpyHostToDevice) != hipSuccess))
+            rc = fail(NIN_EHIP, "uploading the moved nodes failed");
+        if (rc) { (void)hipFree(staged_ids); (void)hipFree(staged_xyz); return rc; }   // nothing was launched: the geometry is as it was
+        ids = staged_ids; xyz = staged_xyz;
+    }
+    if (launch_scatter_points(d.v, pack_npoel8(h), d.up_inpoel, d.up_etype, d.up_inpofa, ids, ids_are_int64, n, xyz, cd, d.up_areas, d.dirty,
+                              d.dirty_hdr + kDirtyHdrRejected, stream))
+        rc = fail(NIN_EHIP, "local geometry kernels: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc && hipEventRecord(static_cast<hipEvent_t>(d.ev_geom), stream) != hipSuccess) rc = fail(NIN_EHIP, "hipEventRecord");
+    if (on_host || rc) {
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (e != hipSuccess && !rc) rc = fail(NIN_EHIP, "local geometry update: %s", hipGetErrorString(e));
+    }
+    if (staged_ids) (void)hipFree(staged_ids);
+    if (staged_xyz) (void)hipFree(staged_xyz);
+    // the host copies of the five arrays are the old mesh's from here on (also after a failure half way): fetched again on first use
+    h.have &= ~A_GEOMETRY;
+    if (!h.lazy) h.lazy.reset(new GeometryMirror(&g->d));
+    ++d.geom_updates;
+    d.scattered_nodes = true;
+    return rc;   // all_dirty stays as it is: the kernels marked the rows that can move
+}
+
+}  // namespace
+
+int nin_grid_scatter_points_device(nin_grid *g, const void *dev_node_ids, int ids_are_int64, int64_t n, const double *dev_xyz, int coords_dim,
+                                   void *stream) {
+    if (!g) return fail(NIN_EINVAL, "NULL grid");
+    if (n < 0) return fail(NIN_EINVAL, "negative n");
+    if (coords_dim != g->coords_dim) return fail(NIN_EINVAL, "coords_dim %d is not the grid's (%d)", coords_dim, g->coords_dim);
+    if (g->d.device < 0 || g->d.prebuilt)
+        return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first, or nin_grid_scatter_points with host arrays)");
+    if (n == 0) return NIN_OK;
+    if (!dev_node_ids || !dev_xyz) return fail(NIN_EINVAL, "NULL argument");
+    return scatter_points_on_device(g, dev_node_ids, ids_are_int64, n, dev_xyz, false, coords_dim, static_cast<hipStream_t>(stream));
+}
+
+int nin_grid_scatter_points(nin_grid *g, const int64_t *node_ids, int64_t n, const double *xyz, int coords_dim) {
+    if (!g) return fail(NIN_EINVAL, "NULL grid");
+    if (n < 0) return fail(NIN_EINVAL, "negative n");
+    if (coords_dim != g->coords_dim) return fail(NIN_EINVAL, "coords_dim %d is not the grid's (%d)", coords_dim, g->coords_dim);
+    if (n == 0) return NIN_OK;
+    if (!node_ids || !xyz) return fail(NIN_EINVAL, "NULL argument");
+    HostGrid &h = g->h;
+    int64_t bad = 0, first = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (node_ids[i] < 0 || node_ids[i] >= h.n_points) { if (!bad++) first = node_ids[i]; }
+    if (bad) return fail(NIN_EINVAL, "%lld of %lld node ids lie outside [0, %lld) (the first: %lld); nothing was moved", (long long)bad, (long long)n,
+                         (long long)h.n_points, (long long)first);
+    // a grid that holds device arrays (a grid built on the device does before nin_grid_to_device too): the kernels
+    if (g->d.device >= 0) return scatter_points_on_device(g, node_ids, 1, n, xyz, true, coords_dim, nullptr);
+    try {   // host-only: the coordinates patched, then grid_host.cpp's own geometry code over the whole mesh (no dirty set without a device)
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < coords_dim && k < 3; ++k) h.coords[(size_t)node_ids[i] * 3 + k] = xyz[i * coords_dim + k];
+        const std::vector<double> moved(h.coords);
+        h.update_points(moved.data(), 3);
+    } catch (const std::bad_alloc &) {
+        return fail(NIN_ENOMEM, "out of host memory while updating the geometry");
+    }
     return NIN_OK;
 }
 
@@ -1116,9 +1214,20 @@ int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *d
         HIP_TRY(hipStreamSynchronize(stream));
         if (hdr[kDirtyHdrRejected] != 0) {   // the marks are as they were (the fill pass clears nothing while the counter is set)
             HIP_TRY(hipMemsetAsync(d.dirty_hdr + kDirtyHdrRejected, 0, sizeof(int32_t), stream));
-            return fail(NIN_EINVAL, "%d cell ids outside [0, %lld) were given to nin_fields_scatter_permeability_device and written nowhere; "
-                        "nothing was launched, the dirty set is kept", (int)hdr[kDirtyHdrRejected], (long long)g->h.n_elems);
+            // one counter for both scatters: what was called since the last dirty launch says whose ids they can be
+            const bool cells = d.scattered_cells || !d.scattered_nodes, nodes = d.scattered_nodes;
+            d.scattered_cells = d.scattered_nodes = false;
+            char who[160];
+            if (cells && nodes)
+                snprintf(who, sizeof who, "cell ids outside [0, %lld) or node ids outside [0, %lld) were given to the local updates",
+                         (long long)g->h.n_elems, (long long)g->h.n_points);
+            else if (nodes)
+                snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_grid_scatter_points_device", (long long)g->h.n_points);
+            else
+                snprintf(who, sizeof who, "cell ids outside [0, %lld) were given to nin_fields_scatter_permeability_device", (long long)g->h.n_elems);
+            return fail(NIN_EINVAL, "%d %s and written nowhere; nothing was launched, the dirty set is kept", (int)hdr[kDirtyHdrRejected], who);
         }
+        d.scattered_cells = d.scattered_nodes = false;
     }
     if (d.all_dirty) {   // the ordinary full launch
         if ((rc = nin_weights_device(g, method, nullptr, 0, add_neumann, dev_csr_data, dev_neumann_ws, stream_))) return rc;
@@ -1465,6 +1574,7 @@ int nin_grid_release_scratch(nin_grid *g) {
         d.up_inpoel = d.up_inpofa = nullptr;
         d.up_etype = nullptr;
         d.up_areas = nullptr;
+        d.up_areas_valid = false;
     }
     return NIN_OK;
 }

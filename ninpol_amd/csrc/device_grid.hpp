@@ -107,19 +107,24 @@ struct DeviceGrid {
     int32_t *up_inpoel = nullptr, *up_inpofa = nullptr;
     int8_t *up_etype = nullptr;
     double *up_areas = nullptr;
+    bool up_areas_valid = false;   // up_areas holds the mesh's areas (the builder's, or a whole-mesh update's), not just room for them
     int64_t geom_updates = 0;
     void *ev_geom = nullptr;
     int64_t field_updates = 0;   // permeability updates from device memory (nin_fields_set_permeability_device, fields_update.hip)
     // Local permeability updates (fields_scatter.hip).  node_class: the class bytes k_classify wrote, kept ([P]).  The dirty
     // set: dirty [P] (1 = the node's row may have moved since the last clear) and dirty_hdr [kDirtyHdrInts] (launch.hpp), allocated by the
     // first scatter and kept -- they are state, not scratch; all_dirty: everything is (a full nin_fields_set, a full permeability update,
-    // moved points: the marks are not looked at until a dirty launch clears the flag).  Scratch of a dirty launch, grown on demand, reused
-    // across calls and given back with the rest: the flat list buffer [P], the block histogram and its scan, the scan's temporary, the
+    // the whole mesh's points moved: the marks are not looked at until a dirty launch clears the flag).  A local move of the points
+    // (grid_scatter.hip) marks nodes in the same set.  Scratch of a dirty launch, grown on demand, reused across calls and
+    // given back with the rest: the flat list buffer [P], the block histogram and its scan, the scan's temporary, the
     // descriptors of the listed nodes.
     const uint8_t *node_class = nullptr;
     uint8_t *dirty = nullptr;
     int32_t *dirty_hdr = nullptr;
     bool all_dirty = true;
+    // which of the two scatters (fields_scatter.hip's cells, grid_scatter.hip's nodes) ran since the last dirty launch: they share the
+    // refused-id counter, and the error that reports it names the ids they can have been
+    bool scattered_cells = false, scattered_nodes = false;
     int32_t *dirty_lists = nullptr, *dirty_hist = nullptr;
     void *dirty_tmp = nullptr;
     size_t dirty_tmp_bytes = 0;

@@ -10,9 +10,8 @@
 // indices in, 1.6 GB of records out, the coordinates mostly from the L2), so what matters is the shape of the accesses:
 //   * one thread per cell / face; its index row is one aligned 32-byte (two dwordx4) / 16-byte (one dwordx4) load, so a wavefront
 //     reads 2 KiB / 1 KiB of contiguous indices;
-//   * the -1 padding of a row costs no divergent region: a padded slot loads the row's first point again (a valid address, the
-//     line is already there) and contributes a selected +0.0.  The running sums start at +0.0 and therefore never hold -0.0, so
-//     adding +0.0 leaves every bit alone;
+//   * the -1 padding of a row costs no divergent region (geom_math.hpp, which holds the per-cell and per-face arithmetic: the local
+//     update of grid_scatter.hip compiles the same expressions);
 //   * the 24-byte [..][3] double records and the 12-byte float normals of a workgroup go through LDS and leave as whole 16-byte
 //     pieces per lane (a wavefront stores 1 KiB of contiguous bytes per instruction instead of 64 eight-byte pieces 24 bytes apart);
 //     a workgroup's first record sits at 256 * 24 (or * 12) bytes times the block index: 16-byte aligned.
@@ -24,6 +23,7 @@
 
 #include <cstdint>
 
+#include "geom_math.hpp"
 #include "launch.hpp"
 
 namespace nin {
@@ -66,21 +66,8 @@ __global__ __launch_bounds__(TPB) void nin_update_cells_kernel(int32_t E, int d,
     __shared__ __attribute__((aligned(16))) double s[3 * TPB];
     const int32_t e0 = (int32_t)blockIdx.x * TPB;
     const int32_t e = min(e0 + (int32_t)threadIdx.x, E - 1);   // lanes past the end redo the last cell; their records are not stored
-    const int4 a = inpoel[2 * (int64_t)e], b = inpoel[2 * (int64_t)e + 1];
-    const int32_t q[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const int n = (int)((npoel8 >> (8 * (etype[e] & 7))) & 0xff);
-    const double dn = (double)n;
-    double c[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {   // divide-then-add, vertex order (grid.pyx:699-704)
-        const bool on = j < n;
-        const int64_t p = min(max(on ? q[j] : q[0], 0), P - 1);   // (the builders checked every index; the clamp keeps a damaged row inside the array)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double x = X[p * 3 + k];
-            c[k] += (on && k < d) ? x / dn : 0.0;
-        }
-    }
+    double c[3];
+    cell_centroid_of(inpoel[2 * (int64_t)e], inpoel[2 * (int64_t)e + 1], npoel_of(npoel8, etype[e]), d, P, X, c);   // geom_math.hpp
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[3 * threadIdx.x + k] = c[k];
     __syncthreads();
@@ -95,49 +82,11 @@ __global__ __launch_bounds__(TPB) void nin_update_faces_kernel(int32_t F, int d,
     __shared__ __attribute__((aligned(16))) float sn[3 * TPB];
     const int32_t f0 = (int32_t)blockIdx.x * TPB;
     const int32_t f = min(f0 + (int32_t)threadIdx.x, F - 1);
-    const int4 r = inpofa[f];
-    // the face's points end at the first -1 (at least two are there); a slot past the end reads the first point again
-    const int32_t p1 = min(max(r.x, 0), P - 1);
-    const bool on1 = r.y != -1, on2 = on1 && r.z != -1, on3 = on2 && r.w != -1;
-    const int32_t q[4] = {p1, on1 ? min(r.y, P - 1) : p1, on2 ? min(r.z, P - 1) : p1, on3 ? min(r.w, P - 1) : p1};
-    const bool on[4] = {true, on1, on2, on3};
-    const int npofa = 1 + (int)on1 + (int)on2 + (int)on3;
-    double x[4][3];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[j][k] = X[(int64_t)q[j] * 3 + k];
-    double c[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)   // sum, then divide (grid.pyx:716-727)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] += (on[j] && k < d) ? x[j][k] : 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        if (k < d) c[k] /= (double)npofa;
+    double c[3], area;
+    float nx, ny, nz;
+    face_geometry_of<DIM3>(inpofa[f], d, P, X, c, nx, ny, nz, area);   // geom_math.hpp
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[3 * threadIdx.x + k] = c[k];
-    float nx, ny, nz;
-    double area;
-    if (DIM3) {
-        // float locals exactly as grid.pyx:732-736 (k_faces_geometry); points 1, 2, 3 of the row, and 4 where there is one
-        float v1x = (float)(x[0][0] - x[1][0]), v1y = (float)(x[0][1] - x[1][1]), v1z = (float)(x[0][2] - x[1][2]);
-        float v2x = (float)(x[2][0] - x[1][0]), v2y = (float)(x[2][1] - x[1][1]), v2z = (float)(x[2][2] - x[1][2]);
-        nx = v1y * v2z - v1z * v2y; ny = v1z * v2x - v1x * v2z; nz = v1x * v2y - v1y * v2x;
-        const float norm = fabsf(sqrtf(nx * nx + ny * ny + nz * nz));
-        nx = nx / norm; ny = ny / norm; nz = nz / norm;
-        v1x = (float)(x[0][0] - x[3][0]); v1y = (float)(x[0][1] - x[3][1]); v1z = (float)(x[0][2] - x[3][2]);
-        v2x = (float)(x[2][0] - x[3][0]); v2y = (float)(x[2][1] - x[3][1]); v2z = (float)(x[2][2] - x[3][2]);
-        const float mx = v1y * v2z - v1z * v2y, my = v1z * v2x - v1x * v2z, mz = v1x * v2y - v1y * v2x;
-        const double quad = (double)(norm + sqrtf(mx * mx + my * my + mz * mz)) / 2.0, tri = (double)norm / 2.0;
-        area = on3 ? quad : tri;
-    } else {
-        const float v1x = (float)(x[0][0] - x[1][0]), v1y = (float)(x[0][1] - x[1][1]);
-        nx = -v1y; ny = v1x;
-        const float norm = fabsf(sqrtf(nx * nx + ny * ny));
-        nx = nx / norm; ny = ny / norm; nz = 0.0f;
-        area = (double)norm;
-    }
     sn[3 * threadIdx.x + 0] = nx; sn[3 * threadIdx.x + 1] = ny; sn[3 * threadIdx.x + 2] = nz;
     if (f0 + (int32_t)threadIdx.x < F) fa[f] = area;
     __syncthreads();

@@ -143,6 +143,14 @@ static_assert(kDirtyHdrCount < kDirtyHdrInts, "the dirty set's header block is t
 int launch_scatter_permeability(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const void *dev_ids,
                                 int ids_are_int64, int64_t n, const double *dev_K, const double *dev_scale, uint8_t *dirty, int32_t *rejected,
                                 hipStream_t stream);
+// grid_scatter.hip: local mesh motion, all DEVICE pointers.  coords[dev_ids[i]] = dev_xyz[i] ([n][coords_dim], zero-padded to three
+// columns) for the ids (int32, or int64 when ids_are_int64) inside [0, n_points) -- one outside writes nothing and adds one to *rejected
+// -- then, in a second kernel behind it, the centroids (g.centroids, and g.centroids4 where it is not null) of the cells around those
+// nodes, the centres, normals and areas of the faces around them (launch_update_geometry's arithmetic and arrays), and dirty[v] = 1 for
+// the vertices of those cells
+int launch_scatter_points(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const int32_t *inpofa,
+                          const void *dev_ids, int ids_are_int64, int64_t n, const double *dev_xyz, int coords_dim, double *face_area,
+                          uint8_t *dirty, int32_t *rejected, hipStream_t stream);
 // the marked nodes binned by plan kernel (single != 0: one list, IDW / LS) into `lists` [n_points], ascending node ids, list k at
 // hdr[kDirtyHdrOffsets + k] .. hdr[kDirtyHdrOffsets + k + 1]; hist / scanned: dirty_compact_hist_ints() ints each, tmp: the scan's
 // (dirty_compact_tmp_bytes).  clear != 0: the marks are cleared as they are read, unless *rejected is non-zero

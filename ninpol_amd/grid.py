@@ -154,6 +154,27 @@ class Grid:
         _lib.check(rc)
         return None
 
+    def scatter_point_coords(self, nodes, rows):
+        """Move a subset of the nodes (nin_grid_scatter_points_device / nin_grid_scatter_points): row i of `rows` (m, coords_dim) float64 is
+        the new position of node nodes[i].  torch tensors on the grid's device (nodes int32 / int64): asynchronous on torch's current
+        stream, ids checked on the device.  numpy arrays (nodes int64, contiguous): synchronous, ids checked here (ValueError); on a grid
+        without a device copy the host builder's geometry code runs.  On a device the geometry around the nodes is made again and the
+        vertices of the cells around them join the dirty set.  The arguments are checked by Interpolator.update_points, which is the
+        public way in."""
+        L = _lib.load()
+        if type(rows).__module__.split(".")[0] == "torch":
+            import torch
+            stream = torch.cuda.current_stream(rows.device).cuda_stream
+            rc = L.nin_grid_scatter_points_device(self._h, ctypes.c_void_p(nodes.data_ptr()), int(nodes.dtype == torch.int64), int(nodes.numel()),
+                                                  ctypes.c_void_p(rows.data_ptr()), self._coords_dim, ctypes.c_void_p(stream))
+        else:
+            rc = L.nin_grid_scatter_points(self._h, _ptr(nodes), int(len(nodes)), _ptr(rows), self._coords_dim)
+        for name in ("point_coords", "centroids", "faces_centers", "normal_faces", "faces_areas"):
+            self._cache.pop(name, None)   # also after a failure: the native arrays may be half way
+        if rc == _lib.NIN_EINVAL:
+            raise ValueError(L.nin_last_error().decode())
+        _lib.check(rc)
+
     def calculate_centroids(self):
         return None
 
@@ -247,8 +268,9 @@ class Grid:
     @property
     def dirty_nodes(self):
         """How many nodes' weights may have moved since the last clear (nin_grid_dirty_nodes: waits for the device): the vertices of
-        the cells that update_permeability(cells=...) rewrote.  -1: every node -- after the grid went to the device, a full
-        permeability update, moved points, or the Neumann flags of another variable.  0 for a grid on no device.  A diagnostic: it
+        the cells that update_permeability(cells=...) rewrote and of the cells around the nodes that update_points(nodes=...) moved.
+        -1: every node -- after the grid went to the device, a full permeability update, a whole-mesh update_points(), or the Neumann
+        flags of another variable.  0 for a grid on no device.  A diagnostic: it
         waits for the whole device and so stalls every stream -- not for a time loop (launch_dirty returns its count)."""
         n = int(_lib.load().nin_grid_dirty_nodes(self._h))
         if n < -1:
@@ -288,7 +310,8 @@ class Grid:
 
     @property
     def geometry_updates(self):
-        """How many times load_point_coords() moved the device copy of this grid (0: never, or the grid is host-only)."""
+        """How many times load_point_coords() or scatter_point_coords() moved the device copy of this grid (0: never, or the grid is
+        host-only)."""
         return int(_lib.load().nin_grid_geometry_updates(self._h))
 
     @property

@@ -282,7 +282,7 @@ class Interpolator:
         self.is_grid_initialized = True
         self._log(f"Mesh loaded successfully: {self.grid.n_points} points and {self.grid.n_elems} elements.")
 
-    def update_points(self, points):
+    def update_points(self, points, nodes=None):
         """Move the mesh: new node coordinates, same connectivity (ALE and free-surface steps, mesh smoothing, shape optimisation).
         `points`: an array of the shape load_mesh() saw, (n_points, 2 or 3) -- synchronous -- or a float64 torch tensor of that
         shape on this Interpolator's device: then the geometry is recomputed from device memory, asynchronously on torch's current
@@ -292,9 +292,26 @@ class Interpolator:
         Afterwards every grid array and every result is bit for bit what a fresh load_mesh() of the moved mesh gives.  What stays:
         the connectivity, the fields (permeability, Neumann flags), the GLS launch plan, the transpose index, all scratch.  What
         does not follow by itself: weights already computed -- matrices returned earlier, the buffers a DevicePlan.launch wrote,
-        the weights a CellToNode holds (call its refresh()) -- and `mesh_obj.points`, which is the caller's."""
+        the weights a CellToNode holds (call its refresh()) -- and `mesh_obj.points`, which is the caller's.
+
+        `nodes` (1-D integer ids in [0, n_points), m of them): only those nodes move; `points` is then (m, coords_dim), row i the new
+        position of node nodes[i] (coords_dim: the columns load_mesh() saw).  Duplicate ids with identical rows are fine; with
+        different rows one of them wins, and which one is unspecified.  Only the geometry around the moved nodes is made again -- the
+        result is the same bits -- and the whole mesh is NOT marked dirty: the nodes whose weights can move, the vertices of the cells
+        around the moved nodes, join the grid's dirty set (Grid.dirty_nodes), and DevicePlan.launch_dirty() and
+        CellToNode.recompute_weights(dirty_only=True) recompute exactly those rows (the whole-mesh form above makes every node dirty).
+        `nodes` a torch tensor (int32 / int64) on this Interpolator's device, `points` a float64 tensor there: asynchronous on torch's
+        current stream with the rules of the device path above; `points_coords` is read back from the grid on first use.  Ids are
+        checked on the device: one outside [0, n_points) moves nothing and marks nothing, and the next launch_dirty() raises with the
+        count.
+        `nodes` a numpy array (or a list), `points` numpy: `points_coords` is patched in place; ids are checked here (ValueError);
+        synchronous.  On a grid that is on a device the same kernels run and the dirty set follows; a grid on no device recomputes its
+        host geometry (works without a GPU; there is no dirty set then: the first upload makes every node dirty anyway).
+        Host and device arguments cannot be mixed (TypeError)."""
         if not self.is_grid_initialized:
             raise ValueError("Grid not initialized. Please load a mesh first.")
+        if nodes is not None:
+            return self._update_points_nodes(points, nodes)
         g = self.grid
         on_device = type(points).__module__.split(".")[0] == "torch" and getattr(points, "is_cuda", False)
         if on_device and g.device < 0:
@@ -306,6 +323,68 @@ class Interpolator:
             if type(points).__module__.split(".")[0] == "torch":
                 points = points.detach().numpy()
             self.points_coords = np.ascontiguousarray(np.array(points, dtype=DTYPE_F))
+
+    def _update_points_nodes(self, rows, nodes):
+        g = self.grid
+        P, cd = int(g.n_points), g._coords_dim
+        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
+        on_gpu = lambda a: is_torch(a) and getattr(a, "is_cuda", False)
+        if on_gpu(nodes):
+            import torch
+            where = torch.device("cuda", self.device)
+            if nodes.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"nodes must be int32 or int64, not {nodes.dtype} (no silent cast)")
+            if nodes.device != where:
+                raise ValueError(f"nodes must be on {where}, not {nodes.device}")
+            if nodes.dim() != 1:
+                raise ValueError(f"nodes must have shape (m,), not {tuple(nodes.shape)}")
+            m = int(nodes.shape[0])
+            if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
+                raise TypeError(f"points must be a torch.Tensor on {where} when nodes is, not " +
+                                (f"one on {rows.device}" if isinstance(rows, torch.Tensor) else type(rows).__name__))
+            if rows.dtype != torch.float64:
+                raise TypeError(f"points must be float64, not {rows.dtype} (no silent cast)")
+            if rows.device != where:
+                raise ValueError(f"points must be on {where}, not {rows.device}")
+            if tuple(rows.shape) != (m, cd):
+                raise ValueError(f"points must have shape {(m, cd)}, not {tuple(rows.shape)}")
+            if m == 0:
+                return
+            if g.device < 0:
+                g.to_device(self.device)
+            g.scatter_point_coords(nodes.detach().contiguous(), rows.detach().contiguous())
+            self._points_coords, self._points_on_device = None, True
+            return
+        if on_gpu(rows):
+            raise TypeError(f"points must be on the host when nodes is (a numpy array), not on {rows.device}")
+        if is_torch(nodes):
+            nodes = nodes.detach().numpy()
+        if is_torch(rows):
+            rows = rows.detach().numpy()
+        ids = np.asarray(nodes)
+        if ids.dtype.kind not in "iu":
+            raise TypeError(f"nodes must be integers, not {ids.dtype} (no silent cast)")
+        if ids.ndim != 1:
+            raise ValueError(f"nodes must have shape (m,), not {ids.shape}")
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        m = len(ids)
+        bad = (ids < 0) | (ids >= P)
+        if bad.any():
+            raise ValueError(f"nodes must lie in [0, {P}): {int(bad.sum())} of {m} do not (the first: {int(ids[bad][0])})")
+        try:
+            X = np.asarray(rows)
+            if X.dtype.kind == "f" and X.dtype != DTYPE_F:
+                raise TypeError(f"points must be float64, not {X.dtype} (no silent cast)")
+            X = np.ascontiguousarray(X, dtype=DTYPE_F)
+        except ValueError as e:
+            raise ValueError(f"points cannot be converted to float64: {e}") from e
+        if X.shape != (m, cd):
+            raise ValueError(f"points must have shape {(m, cd)}, not {X.shape}")
+        if m == 0:
+            return
+        pc = self.points_coords           # (after a device update: read back from the grid first)
+        g.scatter_point_coords(ids, X)
+        pc[ids] = X                       # duplicate ids with different rows: numpy keeps the last, the device an unspecified one
 
     # ---- changing permeability ---------------------------------------------------------------------
     def _perm_rows(self):

@@ -73,7 +73,8 @@ class CellToNode(torch.nn.Module):
         Asynchronous on torch's current stream; outputs computed before keep the weights of their forward pass in backward.
 
         dirty_only=True: only the rows of the grid's dirty nodes (after interp.update_permeability(cells=...): the vertices of those
-        cells) are computed, into CLONES of `weights` / `neumann_ws` that then replace them (DevicePlan.launch_dirty: reads the sizes
+        cells; after interp.update_points(rows, nodes=...): the vertices of the cells around the moved nodes -- the same set serves
+        both, and nothing here had to change for local mesh motion) are computed, into CLONES of `weights` / `neumann_ws` that then replace them (DevicePlan.launch_dirty: reads the sizes
         of its lists back, so it waits for the stream once), and the set is cleared.  While every node is dirty -- as it is until
         the first clear after the grid went to the device -- the call is a full launch; from then on only the marked rows run.  The
         set belongs to the grid: one module (or one DevicePlan buffer) per grid can be kept current this way."""

@@ -8,7 +8,12 @@ Per mesh (a 216^3 hexahedron mesh and an unstructured Delaunay tetrahedron mesh 
          6.29 TB/s copy rate DESIGN uses;
   (b)    the host-pointer update end to end (upload + kernels + synchronise), host clock, median of REPS;
   (c)    a GLS weights step before and after an update, interleaved in the same process: medians and their difference.
---profile: only WARMUP + REPS device-pointer updates (for a rocprofv3 run around this script)."""
+--profile: only WARMUP + REPS device-pointer updates (for a rocprofv3 run around this script).
+--local FRACTION [FRACTION ...]: instead of (a) .. (c), the LOCAL step against the full step, calls interleaved in one session, for two
+  sets of moved nodes that each hold that fraction of the mesh's nodes: a contiguous slab under the top of the mesh (a free-surface
+  layer) and a random subset.  update_points(rows, nodes=ids) + launch_dirty against update_points(X) + launch, HIP events around each
+  pair, WARMUP local steps first, medians (with minimum and maximum) of REPS; and the scatter and the dirty launch alone.
+  launch_dirty waits for the stream once (it reads the lists' sizes back), so its events span that wait."""
 import os
 import sys
 import time
@@ -21,7 +26,8 @@ import ninpol_amd
 from ninpol_amd import mesh as M
 
 CASES = {"hex216": lambda: M.hex_mesh(216, jitter=0.15), "hex64": lambda: M.hex_mesh(64, jitter=0.15),
-         "del54": lambda: M.delaunay_tet_mesh(54, seed=0), "del20": lambda: M.delaunay_tet_mesh(20, seed=0)}
+         "del54": lambda: M.delaunay_tet_mesh(54, seed=0), "del20": lambda: M.delaunay_tet_mesh(20, seed=0),
+         "kuhn40": lambda: M.tet_mesh(40, jitter=0.1), "kuhn12": lambda: M.tet_mesh(12, jitter=0.1)}
 WARMUP, REPS = 5, 30
 COPY_RATE = 6.29e12
 
@@ -46,8 +52,62 @@ def events_ms(run, stream, n):
     return out
 
 
+def moved_sets(X, fraction, seed=0):
+    """{label: node ids}: `fraction` of the nodes as the slab of highest z (a free-surface layer: contiguous in space) and as a random
+    subset"""
+    P = len(X)
+    m = max(int(round(fraction * P)), 1)
+    slab = np.argsort(X[:, 2], kind="stable")[P - m:]
+    return {"slab": np.sort(slab).astype(np.int64), "random": np.sort(np.random.default_rng(seed).choice(P, size=m, replace=False)).astype(np.int64)}
+
+
+def local_leg(name, I, plan, st, X, fractions):
+    g = I.grid
+    P = int(g.n_points)
+    w = torch.empty(plan.nnz, dtype=torch.float64, device="cuda")
+    nws = torch.empty(P, dtype=torch.float64, device="cuda")
+    x_full = [torch.from_numpy(X[0]).cuda(), torch.from_numpy(X[1]).cuda()]
+    step = lambda: plan.launch(w.data_ptr(), nws.data_ptr(), st.cuda_stream)
+    dirty = lambda: plan.launch_dirty(w.data_ptr(), nws.data_ptr(), st.cuda_stream)
+    full = lambda i: (I.update_points(x_full[i & 1]), step())
+    med = lambda a: float(np.median(a))
+    for f in fractions:
+        for label, nodes in moved_sets(X[0], f).items():
+            ids = torch.from_numpy(nodes).cuda()
+            rows = [x_full[0][ids].contiguous(), x_full[1][ids].contiguous()]
+            scatter = lambda i: I.update_points(rows[i & 1], nodes=ids)
+            full(0)
+            g.clear_dirty(st.cuda_stream)   # w holds a full result of X[0] as of now
+            n = 0
+            for i in range(WARMUP):
+                scatter(i + 1)
+                n = dirty()
+            torch.cuda.synchronize()
+            t_local, t_full, t_scatter, t_dirty = [], [], [], []
+            for i in range(REPS):   # interleaved: one local step, one full step
+                t_local.append(events_ms(lambda: (scatter(i), dirty()), st, 1)[0])
+                t_full.append(events_ms(lambda: full(i), st, 1)[0])
+                g.clear_dirty(st.cuda_stream)   # (the full update marked everything; w is not looked at)
+                t_scatter.append(events_ms(lambda: scatter(i + 1), st, 1)[0])
+                t_dirty.append(events_ms(dirty, st, 1)[0])
+            print(f"{name}: --local {f:g} {label}: {len(nodes)} nodes ({100.0 * len(nodes) / P:.2f} %), {n} dirty nodes of {P}: "
+                  f"local step median {med(t_local):.3f} ms (min {min(t_local):.3f}, max {max(t_local):.3f}) = scatter {med(t_scatter):.3f} + "
+                  f"launch_dirty {med(t_dirty):.3f}; full step median {med(t_full):.3f} ms (min {min(t_full):.3f}, max {max(t_full):.3f}) "
+                  f"over {REPS}; full / local = {med(t_full) / med(t_local):.2f}", flush=True)
+
+
 def main():
-    names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["hex216", "del54"]
+    args = sys.argv[1:]
+    fractions = []
+    if "--local" in args:
+        j = args.index("--local") + 1
+        while j < len(args) and not args[j].startswith("--") and args[j] not in CASES:
+            fractions.append(float(args[j]))
+            j += 1
+        if not fractions:
+            raise SystemExit("--local needs at least one fraction, e.g. --local 0.001 0.01 0.1")
+        args = args[:args.index("--local")] + args[j:]
+    names = [a for a in args if not a.startswith("--")] or ["hex216", "del54"]
     profile_only = "--profile" in sys.argv
     if not torch.cuda.is_available():
         raise SystemExit("time_update.py needs a GPU")
@@ -72,6 +132,11 @@ def main():
         print(f"{name}: P={P} E={E} F={F}; load_mesh(grid_build='device') {t_load * 1e3:.1f} ms (mesh tables and field packing included) + "
               f"plan build {t_plan * 1e3:.1f} ms", flush=True)
         plan = I.device_plan("u", "gls")
+        if fractions:
+            local_leg(name, I, plan, st, (X1, X2), fractions)
+            I.release_scratch()
+            del plan, I
+            continue
         w = torch.empty(plan.nnz, dtype=torch.float64, device="cuda")
         nws = torch.empty(P, dtype=torch.float64, device="cuda")
         step = lambda: plan.launch(w.data_ptr(), nws.data_ptr(), st.cuda_stream)
