@@ -129,7 +129,9 @@ int nin_grid_has_transpose_index(const nin_grid *g);
  * gls.pyx:47-59): permeability[E][3][3] row-major and diff_mag[E] (may be NULL for IDW / LS),
  * neumann_flag[P] (the points_data row, cast to integer like `.astype(int)`), neumann_val[P]
  * (may be NULL for IDW / LS).  Host pointers; uploaded to the grid's device.  permeability / diff_mag NULL leaves
- * the copies already on the device in place (they belong to the mesh, not to the variable). */
+ * the copies already on the device in place (they belong to the mesh, not to the variable).  neumann_flag NULL leaves the
+ * flags already on the device in place (an earlier call's, or nin_fields_set_flags_device's); before any flags are resident
+ * it is NIN_EINVAL: every method needs them. */
 int nin_fields_set(nin_grid *g, const double *permeability, const double *diff_mag,
                    const double *neumann_flag, const double *neumann_val);
 
@@ -174,7 +176,8 @@ int64_t nin_grid_field_updates(const nin_grid *g);
  *   nin_grid_field_updates.  n == 0 is a no-op.  NIN_ESTATE when no permeability is resident to patch.
  * nin_weights_dirty_device: the marked nodes are binned by kernel on the device (ascending node id per kernel), the counts and the
  *   refused-id counter come back in one 128-byte copy -- the ONLY synchronisation of the call (of `stream`) -- and the weight kernels run on
- *   the lists.  Rows outside the set are not touched and nothing is zeroed.  clear != 0: the set is empty afterwards.  *n_recomputed
+ *   the lists.  Rows outside the set are not touched and nothing is zeroed; a row IN the set is written by its kernel whether it is computed or
+ *   the zero row of a Dirichlet node.  clear != 0: the set is empty afterwards.  *n_recomputed
  *   (may be NULL): the number of rows recomputed.  If ids were refused since the last dirty launch: NIN_EINVAL with the count in
  *   nin_last_error(), nothing is launched, the set is kept and the counter starts again from zero.
  *   "Everything is dirty" after nin_grid_to_device, a nin_fields_set with a permeability, nin_fields_set_permeability_device,
@@ -218,6 +221,47 @@ int nin_grid_dirty_reset(nin_grid *g, int all_dirty, void *stream);
 int nin_grid_scatter_points_device(nin_grid *g, const void *dev_node_ids, int ids_are_int64, int64_t n, const double *dev_xyz,
                                    int coords_dim, void *stream);
 int nin_grid_scatter_points(nin_grid *g, const int64_t *node_ids, int64_t n, const double *xyz, int coords_dim);
+
+/* ---- changing boundary conditions: Neumann flags from device memory -------------------------------------------------------
+ * Which boundary nodes are computed and which get the zero row -- a boundary that switches between Dirichlet and Neumann, wells that
+ * open and close, two variables with different Neumann sets served in turn -- changed where the flags already live.  Nothing crosses
+ * the host.  The resident flag byte of a node is bit0 = boundary point (the mesh's, on the device since nin_grid_to_device, never
+ * changed here) and bit1 = Neumann; these calls rewrite bit1.  A value is SET when, as float64, (long long)x != 0 -- truncation toward
+ * zero, the rule of nin_fields_set (`.astype(int)`): 0.5, -0.5 and 1e-300 are not set, -1.0, 2.0 and 255.0 are; NaN and values of
+ * magnitude >= 2^63 are outside the contract (the host's cast is undefined for them, and so is the result here) -- or, as one byte per
+ * value (flags_are_bytes != 0: bool / uint8), when it is non-zero.
+ * The flag of node n is read by row n of the weights and by no other (gls.pyx:165-214, idw.pyx:62-63, ls.pyx:58-59), so both setters
+ * mark, in the dirty set of the blocks above, exactly the nodes whose Neumann bit CHANGED: an update that rewrites equal values marks
+ * nothing.  nin_weights_dirty_device then writes those rows in place -- a node that became Dirichlet gets the zero row and
+ * neumann_ws = 0 of a full launch.  Neither setter makes everything dirty, and while everything is dirty neither marks (no marks are
+ * needed then); neumann_val is not part of the state (nin_fields_set ignores it too).  The GLS launch plan does not depend on the
+ * flags and stays.
+ *
+ * nin_fields_set_flags_device: dev_flags is a DEVICE array [n_points] on the grid's device, float64 or one byte per node, at any
+ *   address its type allows (bytes at an 8-byte aligned address are read eight at a time: same result), not overlapping a grid array.  One streaming pass; a byte is written only where it changes.  Needs no prior nin_fields_set: the methods find their
+ *   fields set afterwards (GLS still needs a permeability).
+ * nin_fields_scatter_flags_device: dev_node_ids [n] node ids (int32, or int64 when ids_are_int64 != 0) and dev_flags [n], value i for
+ *   node dev_node_ids[i], DEVICE arrays on the grid's device.  Every id is checked on the device before any access: an id outside
+ *   [0, n_points) writes nothing, marks nothing and is counted in the counter of nin_fields_scatter_permeability_device; the next
+ *   nin_weights_dirty_device reports the count and names this call.  Duplicate ids with equal values are fine; with different values
+ *   one of them wins, which one is unspecified, and the node is marked if its bit ends up different from what it was before the call.
+ *   n == 0 is a no-op.  NIN_ESTATE when no flags are resident yet to patch.
+ * Both: asynchronous on `stream` (hipStream_t) with the ordering rules of nin_fields_set_permeability_device -- later launches on that
+ *   stream see the new flags; work on other streams, and the host-synchronous entry points (they run on the null stream), must be
+ *   ordered behind `stream` by the caller; calls that touch the dirty set of one grid belong on one stream.  The first call on a grid
+ *   allocates the dirty set and may synchronise once.  Both count in nin_grid_flag_updates.  NIN_EINVAL for a NULL argument or a
+ *   negative n, NIN_ENODEVICE when nin_grid_device(g) is -1.  A later nin_fields_set with a neumann_flag replaces the flags again (and
+ *   marks nothing: its caller decides what is dirty).
+ * nin_fields_get_flags: the resident Neumann bits copied to a HOST array neumann [n_points], 0 or 1 each; host-synchronous, waits for
+ *   everything enqueued on the device first.  NIN_EINVAL for a NULL argument, NIN_ENODEVICE as above, NIN_ESTATE when no flags are
+ *   resident.
+ * nin_grid_flag_updates: flag updates from device memory the grid's device copy has seen since it was made (0 without one): the
+ *   sibling of nin_grid_field_updates. */
+int nin_fields_set_flags_device(nin_grid *g, const void *dev_flags, int flags_are_bytes, void *stream);
+int nin_fields_scatter_flags_device(nin_grid *g, const void *dev_node_ids, int ids_are_int64, int64_t n,
+                                    const void *dev_flags, int flags_are_bytes, void *stream);
+int nin_fields_get_flags(nin_grid *g, uint8_t *neumann /* [n_points], 0 or 1 */);
+int64_t nin_grid_flag_updates(const nin_grid *g);
 
 /* ---- the hot path -------------------------------------------------------------------------
  * Replaces supported_methods[method](grid, ..., target_points, weights, neumann_ws)

@@ -26,6 +26,7 @@ EXPORTS = (
     "nin_fields_set_permeability_device", "nin_fields_get_permeability", "nin_grid_field_updates",
     "nin_fields_scatter_permeability_device", "nin_weights_dirty_device", "nin_grid_dirty_nodes", "nin_grid_dirty_reset",
     "nin_grid_scatter_points_device", "nin_grid_scatter_points",
+    "nin_fields_set_flags_device", "nin_fields_scatter_flags_device", "nin_fields_get_flags", "nin_grid_flag_updates",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -98,6 +99,11 @@ def load():
     L.nin_fields_scatter_permeability_device.argtypes = [vp, vp, i32, i64, vp, vp, vp]
     L.nin_grid_scatter_points_device.argtypes = [vp, vp, i32, i64, vp, i32, vp]
     L.nin_grid_scatter_points.argtypes = [vp, vp, i64, vp, i32]
+    L.nin_fields_set_flags_device.argtypes = [vp, vp, i32, vp]
+    L.nin_fields_scatter_flags_device.argtypes = [vp, vp, i32, i64, vp, i32, vp]
+    L.nin_fields_get_flags.argtypes = [vp, vp]
+    L.nin_grid_flag_updates.argtypes = [vp]
+    L.nin_grid_flag_updates.restype = i64
     L.nin_weights_dirty_device.argtypes = [vp, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i64)]
     L.nin_grid_dirty_nodes.argtypes = [vp]
     L.nin_grid_dirty_nodes.restype = i64

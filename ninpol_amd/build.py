@@ -44,6 +44,8 @@ UNITS = [
     ("fields_update.hip", "hipcc", ["-ffp-contract=off"]),
     # local permeability updates: the scatter's diff_mag is the same expression under the same flag
     ("fields_scatter.hip", "hipcc", ["-ffp-contract=off"]),
+    # Neumann flags from device memory: integer work on bytes, one float64 -> integer cast; nothing to contract
+    ("flags_update.hip", "hipcc", []),
     ("abi.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),

@@ -808,16 +808,20 @@ int nin_fields_set(nin_grid *g, const double *permeability, const double *diff_m
     if (!g) return fail(NIN_EINVAL, "NULL grid");
     if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
     if (g->h.ensure(A_BPOINTS)) return fail(NIN_EHIP, "mirroring boundary_points failed");
-    if (!neumann_flag) return fail(NIN_EINVAL, "neumann_flag is required by every method");
+    // NULL keeps the flags that are resident (nin_fields_set_flags_device put them there, or an earlier call), as a NULL permeability keeps the table
+    if (!neumann_flag && !g->d.fields_set) return fail(NIN_EINVAL, "neumann_flag is required by every method");
     HIP_TRY(hipSetDevice(g->d.device));
     HostGrid &h = g->h;
     DeviceGrid &d = g->d;
     const int64_t P = h.n_points, E = h.n_elems;
-    // packed by the host's OpenMP team (pack_host.cpp) into a page-locked staging buffer the grid keeps: 82 MB of float64
-    // flags in, 10 MB out at 10 M nodes -- the serial loop + pageable copy this replaces took ~15 ms of every interpolate()
-    if (!d.flag_staging) HIP_TRY(hipHostMalloc((void **)&d.flag_staging, (size_t)std::max<int64_t>(P, 1), hipHostMallocDefault));
-    pack_node_flags(neumann_flag, h.boundary_points.data(), P, d.flag_staging);
-    HIP_TRY(hipMemcpy(const_cast<uint8_t *>(d.v.flags), d.flag_staging, (size_t)P, hipMemcpyHostToDevice));
+    if (neumann_flag) {
+        // packed by the host's OpenMP team (pack_host.cpp) into a page-locked staging buffer the grid keeps: 82 MB of float64
+        // flags in, 10 MB out at 10 M nodes -- the serial loop + pageable copy this replaces took ~15 ms of every interpolate()
+        if (!d.flag_staging) HIP_TRY(hipHostMalloc((void **)&d.flag_staging, (size_t)std::max<int64_t>(P, 1), hipHostMallocDefault));
+        pack_node_flags(neumann_flag, h.boundary_points.data(), P, d.flag_staging);
+        HIP_TRY(hipMemcpy(const_cast<uint8_t *>(d.v.flags), d.flag_staging, (size_t)P, hipMemcpyHostToDevice));
+        d.flags_host_stale = false;
+    }
     if (permeability && diff_mag) {   // NULL keeps what is resident (0.8 GB at 10 M cells: callers upload it once per mesh)
         HIP_TRY(hipMemcpy(const_cast<double *>(d.v.perm), permeability, (size_t)E * 9 * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(const_cast<double *>(d.v.diff_mag), diff_mag, (size_t)E * 8, hipMemcpyHostToDevice));
@@ -1083,6 +1087,73 @@ int nin_fields_scatter_permeability_device(nin_grid *g, const void *dev_cell_ids
     return NIN_OK;
 }
 
+// ---- Neumann flags from device memory (flags_update.hip) -------------------------------------------------------------
+int nin_fields_set_flags_device(nin_grid *g, const void *dev_flags, int flags_are_bytes, void *stream) {
+    if (!g || !dev_flags) return fail(NIN_EINVAL, "NULL argument");
+    if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first, or nin_fields_set with host arrays)");
+    DeviceGrid &d = g->d;
+    HIP_TRY(hipSetDevice(d.device));
+    int rc = ensure_dirty_state(d, g->h.n_points);
+    if (rc) return rc;
+    // while everything is dirty no marks are needed; afterwards only the nodes whose byte changes are marked
+    rc = launch_set_flags(d.v.n_points, dev_flags, flags_are_bytes, const_cast<uint8_t *>(d.v.flags), d.all_dirty ? nullptr : d.dirty,
+                          static_cast<hipStream_t>(stream));
+    if (rc) return fail(rc, "flag kernel: %s", hipGetErrorString(hipGetLastError()));
+    d.fields_set = true;
+    d.flags_host_stale = true;
+    ++d.flag_updates;
+    return NIN_OK;
+}
+
+int nin_fields_scatter_flags_device(nin_grid *g, const void *dev_node_ids, int ids_are_int64, int64_t n, const void *dev_flags,
+                                    int flags_are_bytes, void *stream) {
+    if (!g) return fail(NIN_EINVAL, "NULL grid");
+    if (n < 0) return fail(NIN_EINVAL, "negative n");
+    if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
+    if (n == 0) return NIN_OK;
+    if (!dev_node_ids || !dev_flags) return fail(NIN_EINVAL, "NULL argument");
+    DeviceGrid &d = g->d;
+    if (!d.fields_set) return fail(NIN_ESTATE, "no Neumann flags are resident to patch (nin_fields_set or nin_fields_set_flags_device first)");
+    HIP_TRY(hipSetDevice(d.device));
+    int rc = ensure_dirty_state(d, g->h.n_points);
+    if (rc) return rc;
+    rc = launch_scatter_flags(d.v.n_points, dev_node_ids, ids_are_int64, n, dev_flags, flags_are_bytes, const_cast<uint8_t *>(d.v.flags),
+                              d.all_dirty ? nullptr : d.dirty, d.dirty_hdr + kDirtyHdrRejected, static_cast<hipStream_t>(stream));
+    if (rc) return fail(rc, "flag scatter kernel: %s", hipGetErrorString(hipGetLastError()));
+    d.scattered_flags = true;
+    d.flags_host_stale = true;
+    ++d.flag_updates;
+    return NIN_OK;
+}
+
+// the host's copy of the resident flag bytes (flag_staging), brought up to date; waits for the device when it has to fetch
+static int fetch_flag_bytes(nin_grid *g) {
+    DeviceGrid &d = g->d;
+    if (d.flag_staging && !d.flags_host_stale) return NIN_OK;
+    const size_t P = (size_t)g->h.n_points;
+    if (!d.flag_staging) HIP_TRY(hipHostMalloc((void **)&d.flag_staging, std::max<size_t>(P, 1), hipHostMallocDefault));
+    HIP_TRY(hipDeviceSynchronize());   // an update may still be in flight on any stream
+    HIP_TRY(hipMemcpy(d.flag_staging, d.v.flags, P, hipMemcpyDeviceToHost));
+    d.flags_host_stale = false;
+    return NIN_OK;
+}
+
+int nin_fields_get_flags(nin_grid *g, uint8_t *neumann) {
+    if (!g || !neumann) return fail(NIN_EINVAL, "NULL argument");
+    if (g->d.device < 0 || g->d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
+    DeviceGrid &d = g->d;
+    if (!d.fields_set) return fail(NIN_ESTATE, "no Neumann flags are resident (nin_fields_set or nin_fields_set_flags_device first)");
+    HIP_TRY(hipSetDevice(d.device));
+    d.flags_host_stale = true;   // host-synchronous by contract: wait for the device and read what is there now
+    const int rc = fetch_flag_bytes(g);
+    if (rc) return rc;
+    const int64_t P = g->h.n_points;
+    for (int64_t p = 0; p < P; ++p) neumann[p] = (uint8_t)((d.flag_staging[p] >> 1) & 1);
+    return NIN_OK;
+}
+
+int64_t nin_grid_flag_updates(const nin_grid *g) { return g ? g->d.flag_updates : 0; }
+
 // ---- local mesh motion (grid_scatter.hip) ---------------------------------------------------------------------------
 namespace {
 
@@ -1214,20 +1285,25 @@ int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *d
         HIP_TRY(hipStreamSynchronize(stream));
         if (hdr[kDirtyHdrRejected] != 0) {   // the marks are as they were (the fill pass clears nothing while the counter is set)
             HIP_TRY(hipMemsetAsync(d.dirty_hdr + kDirtyHdrRejected, 0, sizeof(int32_t), stream));
-            // one counter for both scatters: what was called since the last dirty launch says whose ids they can be
-            const bool cells = d.scattered_cells || !d.scattered_nodes, nodes = d.scattered_nodes;
-            d.scattered_cells = d.scattered_nodes = false;
-            char who[160];
-            if (cells && nodes)
-                snprintf(who, sizeof who, "cell ids outside [0, %lld) or node ids outside [0, %lld) were given to the local updates",
-                         (long long)g->h.n_elems, (long long)g->h.n_points);
+            // one counter for the three scatters: what was called since the last dirty launch says whose ids they can be
+            const bool nodes = d.scattered_nodes, flags = d.scattered_flags, cells = d.scattered_cells || !(nodes || flags);
+            d.scattered_cells = d.scattered_nodes = d.scattered_flags = false;
+            char who[240];
+            if (cells && (nodes || flags))
+                snprintf(who, sizeof who, "cell ids outside [0, %lld) or node ids outside [0, %lld) were given to the local updates%s",
+                         (long long)g->h.n_elems, (long long)g->h.n_points, flags ? " (nin_fields_scatter_flags_device among them)" : "");
+            else if (nodes && flags)
+                snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_grid_scatter_points_device or nin_fields_scatter_flags_device",
+                         (long long)g->h.n_points);
+            else if (flags)
+                snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_fields_scatter_flags_device", (long long)g->h.n_points);
             else if (nodes)
                 snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_grid_scatter_points_device", (long long)g->h.n_points);
             else
                 snprintf(who, sizeof who, "cell ids outside [0, %lld) were given to nin_fields_scatter_permeability_device", (long long)g->h.n_elems);
             return fail(NIN_EINVAL, "%d %s and written nowhere; nothing was launched, the dirty set is kept", (int)hdr[kDirtyHdrRejected], who);
         }
-        d.scattered_cells = d.scattered_nodes = false;
+        d.scattered_cells = d.scattered_nodes = d.scattered_flags = false;
     }
     if (d.all_dirty) {   // the ordinary full launch
         if ((rc = nin_weights_device(g, method, nullptr, 0, add_neumann, dev_csr_data, dev_neumann_ws, stream_))) return rc;
@@ -1778,9 +1854,14 @@ int nin_gls_plan_flops(nin_grid *g, double alg[22], double ref[22], int64_t comp
     DeviceGrid &d = g->d;
     HostGrid &h = g->h;
     if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
-    if (!d.fields_set || !d.flag_staging) return fail(NIN_ESTATE, "nin_fields_set has not been called (the Neumann flags decide which boundary nodes are computed)");
+    if (!d.fields_set || (!d.flag_staging && !d.flags_host_stale))
+        return fail(NIN_ESTATE, "nin_fields_set has not been called (the Neumann flags decide which boundary nodes are computed)");
     if (h.ensure(A_ESUP_PTR | A_ESUP | A_FSUP_PTR | A_FSUP | A_ESUF)) return fail(NIN_EHIP, "mirroring the connectivity failed");
     HIP_TRY(hipSetDevice(d.device));
+    {   // after an update of the flags from device memory the host's copy of the bytes is fetched again (waits for the device)
+        const int frc = fetch_flag_bytes(g);
+        if (frc) return frc;
+    }
     for (int k = 0; k < kGlsPlanKernels; ++k) { alg[k] = ref[k] = 0.0; computed[k] = 0; }
     const int64_t P = h.n_points;
     // (F, D, free faces) of the nodes of the multifrontal kernels: the low 24 bits of the descriptor word the plan's table names

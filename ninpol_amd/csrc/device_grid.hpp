@@ -122,9 +122,13 @@ struct DeviceGrid {
     uint8_t *dirty = nullptr;
     int32_t *dirty_hdr = nullptr;
     bool all_dirty = true;
-    // which of the two scatters (fields_scatter.hip's cells, grid_scatter.hip's nodes) ran since the last dirty launch: they share the
-    // refused-id counter, and the error that reports it names the ids they can have been
-    bool scattered_cells = false, scattered_nodes = false;
+    // which of the three scatters (fields_scatter.hip's cells, grid_scatter.hip's nodes, flags_update.hip's flags) ran since the last
+    // dirty launch: they share the refused-id counter, and the error that reports it names the ids they can have been
+    bool scattered_cells = false, scattered_nodes = false, scattered_flags = false;
+    // Neumann flags from device memory (flags_update.hip): flag_updates counts the updates; flags_host_stale: flag_staging,
+    // the host's copy of the resident bytes, is older than the device's (fetched again by whoever reads it)
+    int64_t flag_updates = 0;
+    bool flags_host_stale = false;
     int32_t *dirty_lists = nullptr, *dirty_hist = nullptr;
     void *dirty_tmp = nullptr;
     size_t dirty_tmp_bytes = 0;

@@ -151,6 +151,14 @@ int launch_scatter_permeability(const GridView &g, uint64_t npoel8, const int32_
 int launch_scatter_points(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const int32_t *inpofa,
                           const void *dev_ids, int ids_are_int64, int64_t n, const double *dev_xyz, int coords_dim, double *face_area,
                           uint8_t *dirty, int32_t *rejected, hipStream_t stream);
+// flags_update.hip: the Neumann bit of the resident flag bytes (flags [P]: bit0 boundary point, kept; bit1 Neumann) from DEVICE memory.
+// dev_flags: float64 (set when (long long)x != 0, the host packer's rule) or, flags_are_bytes != 0, one byte per value (set when
+// non-zero).  A byte is written only where it changes, and where it does dirty[p] = 1 (dirty null: no marks).  launch_set_flags: all
+// n_points nodes from dev_flags [n_points]; launch_scatter_flags: the nodes dev_ids[0 .. n) (int32, or int64 when ids_are_int64) from
+// dev_flags [n] -- an id outside [0, n_points) writes nothing, marks nothing and adds one to *rejected
+int launch_set_flags(int32_t n_points, const void *dev_flags, int flags_are_bytes, uint8_t *flags, uint8_t *dirty, hipStream_t stream);
+int launch_scatter_flags(int32_t n_points, const void *dev_ids, int ids_are_int64, int64_t n, const void *dev_flags, int flags_are_bytes,
+                         uint8_t *flags, uint8_t *dirty, int32_t *rejected, hipStream_t stream);
 // the marked nodes binned by plan kernel (single != 0: one list, IDW / LS) into `lists` [n_points], ascending node ids, list k at
 // hdr[kDirtyHdrOffsets + k] .. hdr[kDirtyHdrOffsets + k + 1]; hist / scanned: dirty_compact_hist_ints() ints each, tmp: the scan's
 // (dirty_compact_tmp_bytes).  clear != 0: the marks are cleared as they are read, unless *rejected is non-zero

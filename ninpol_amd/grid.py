@@ -80,6 +80,10 @@ class Grid:
         # True from load_permeability_device() until a host table is uploaded over it, or read back into the host rows
         # (Interpolator.permeability_on_device)
         self._perm_from_device = False
+        # True from load_flags_device() / scatter_flags_device() until a host row is uploaded over the flags, or they are read back into
+        # the host row (Interpolator.neumann_flags_on_device); _flags_key: the fingerprint of that host row at the device update
+        self._flags_from_device = False
+        self._flags_key = None
         self._h = ctypes.c_void_p()
         L = _lib.load()
         if build_device is None:   # the native OpenMP builder (csrc/grid_host.cpp)
@@ -241,6 +245,8 @@ class Grid:
         self._perm_key = None   # a fresh device copy holds no fields
         self._fields_variable = None   # ... and nobody's Neumann flags: every DevicePlan re-uploads at its next launch
         self._perm_from_device = False
+        self._flags_from_device = False
+        self._flags_key = None
         _lib.check(_lib.load().nin_grid_to_device(self._h, int(device)))
         return self
 
@@ -265,12 +271,52 @@ class Grid:
             self._h, ctypes.c_void_p(cells.data_ptr()), int(cells.dtype == torch.int64), int(cells.numel()), ctypes.c_void_p(K.data_ptr()),
             None if scale is None else ctypes.c_void_p(scale.data_ptr()), ctypes.c_void_p(stream)))
 
+    def load_flags_device(self, flags):
+        """The resident Neumann flags from a torch tensor on the grid's device (nin_fields_set_flags_device): float64, bool or uint8,
+        contiguous, (n_points,).  The nodes whose bit changes join the dirty set (none while every node is dirty).  Asynchronous on torch's
+        current stream; the arguments are checked by Interpolator.update_neumann_flags, which is the public way in."""
+        import torch
+        stream = torch.cuda.current_stream(flags.device).cuda_stream
+        _lib.check(_lib.load().nin_fields_set_flags_device(self._h, ctypes.c_void_p(flags.data_ptr()), int(flags.dtype != torch.float64),
+                                                           ctypes.c_void_p(stream)))
+        self._flags_from_device = True
+
+    def scatter_flags_device(self, nodes, flags):
+        """Neumann flags of a subset of the nodes from torch tensors on the grid's device (nin_fields_scatter_flags_device): nodes int32 /
+        int64 (m,), flags float64, bool or uint8 (m,), value i for node nodes[i].  Ids are checked on the device; the nodes whose bit changes
+        join the dirty set.  Asynchronous on torch's current stream; the arguments are checked by Interpolator.update_neumann_flags, which
+        is the public way in."""
+        import torch
+        stream = torch.cuda.current_stream(flags.device).cuda_stream
+        _lib.check(_lib.load().nin_fields_scatter_flags_device(
+            self._h, ctypes.c_void_p(nodes.data_ptr()), int(nodes.dtype == torch.int64), int(nodes.numel()), ctypes.c_void_p(flags.data_ptr()),
+            int(flags.dtype != torch.float64), ctypes.c_void_p(stream)))
+        self._flags_from_device = True
+
+    def fetch_flags(self):
+        """The Neumann bits resident on the device as a uint8 array (n_points,) of 0 / 1 (nin_fields_get_flags: waits for the device); None
+        when the grid is on no device or holds no flags there."""
+        if self.device < 0:
+            return None
+        out = np.empty(int(self.n_points), dtype=np.uint8)
+        rc = _lib.load().nin_fields_get_flags(self._h, _ptr(out))
+        if rc == _lib.NIN_ESTATE:
+            return None
+        _lib.check(rc)
+        return out
+
+    @property
+    def flag_updates(self):
+        """How many times the Neumann flags of this grid's device copy were rewritten from device memory (0: never, or host-only)."""
+        return int(_lib.load().nin_grid_flag_updates(self._h))
+
     @property
     def dirty_nodes(self):
         """How many nodes' weights may have moved since the last clear (nin_grid_dirty_nodes: waits for the device): the vertices of
-        the cells that update_permeability(cells=...) rewrote and of the cells around the nodes that update_points(nodes=...) moved.
+        the cells that update_permeability(cells=...) rewrote and of the cells around the nodes that update_points(nodes=...) moved, and the
+        nodes whose Neumann bit update_neumann_flags() changed.
         -1: every node -- after the grid went to the device, a full permeability update, a whole-mesh update_points(), or the Neumann
-        flags of another variable.  0 for a grid on no device.  A diagnostic: it
+        flags of another variable uploaded from the host.  0 for a grid on no device.  A diagnostic: it
         waits for the whole device and so stalls every stream -- not for a time loop (launch_dirty returns its count)."""
         n = int(_lib.load().nin_grid_dirty_nodes(self._h))
         if n < -1:

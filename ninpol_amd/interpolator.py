@@ -99,6 +99,7 @@ class _TableCheck:
         return self.key != self.grid._perm_key
 
     def upload(self, flag):
+        # flag None: the flags resident on the device stay (_upload_fields found a device copy that is still the newer one)
         _lib.check(_lib.load().nin_fields_set(self.grid._h, _ptr(self.perm), _ptr(self.dmag), _ptr(flag), None))
         self.grid._perm_key = self.key
         self.grid._perm_from_device = False
@@ -116,6 +117,14 @@ def _upload_fields(grid, method, cells_data, points_data, variable_to_index, var
     P, E = grid.n_points, grid.n_elems
     v2i = variable_to_index
     flag = np.ascontiguousarray(np.asarray(points_data)[v2i["points"]["neumann_flag_" + variable]][:P], dtype=DTYPE_F)
+    host_over_device = False
+    if grid._flags_from_device:
+        # flags written from the device (Interpolator.update_neumann_flags) stay resident while the CONTENTS of this variable's host
+        # row are what they were at that update; an in-place edit of the row, or another variable, wins -- the permeability's rule
+        if grid._fields_variable == variable and grid._flags_key == _table_key(flag):
+            flag = None
+        else:
+            grid._flags_from_device, grid._flags_key, host_over_device = False, None, True
     perm = dmag = nval = None
     key = None
     check = None
@@ -139,7 +148,7 @@ def _upload_fields(grid, method, cells_data, points_data, variable_to_index, var
     if perm is not None:
         grid._perm_from_device = False   # the host table went over whatever a device update had left
     # the flags on the device belong to the GRID, not to a plan: remember whose they are (DevicePlan.ensure_current)
-    if grid._fields_variable is not None and grid._fields_variable != variable:
+    if host_over_device or (grid._fields_variable is not None and grid._fields_variable != variable):
         grid.mark_all_dirty()   # other flags: any row may differ from what a caller's buffers hold (DevicePlan.launch_dirty)
     grid._fields_variable = variable
     if check is not None:
@@ -607,6 +616,177 @@ class Interpolator:
         g = self.grid
         return g is not None and g._perm_from_device
 
+    # ---- changing boundary conditions ----------------------------------------------------------------
+    def _flag_row(self, variable):
+        """The `neumann_flag_<variable>` row of points_data as _upload_fields reads it (a view: same address, same hash)."""
+        if not self.is_grid_initialized:
+            raise ValueError("Grid not initialized. Please load a mesh first.")
+        name = "neumann_flag_" + str(variable)
+        if name not in self.variable_to_index["points"]:
+            raise ValueError(f"Variable '{name}' not found in points data.")
+        return np.asarray(self.points_data)[self.variable_to_index["points"][name]][:self.grid.n_points]
+
+    def update_neumann_flags(self, variable, flags, nodes=None):
+        """Change the boundary condition of `variable`: which nodes carry its Neumann flag (a boundary that switches between Dirichlet
+        and Neumann, wells that open and close, two variables with different Neumann sets served in turn).  `flags` has shape
+        (n_points,); a value is SET when, as an integer, it is not zero -- `.astype(int)`, truncation toward zero, as everywhere else:
+        0.5 and -0.5 are not set -- or, for bool / uint8, when it is non-zero.  Connectivity, geometry, permeability and the GLS launch
+        plan stay; Neumann VALUES are not part of the weights and are not touched.
+
+        The flag of node n is read by row n only, so exactly the nodes whose bit CHANGES join the grid's dirty set (Grid.dirty_nodes), and
+        DevicePlan.launch_dirty() / CellToNode.recompute_weights(dirty_only=True) recompute exactly those rows -- a node that became
+        Dirichlet gets its zero row.  An update that rewrites equal values marks nothing.
+
+        A torch tensor (float64, bool or uint8) on this Interpolator's device: the resident flags are rewritten by a kernel on torch's
+        current stream -- no host copy, no synchronisation, `points_data` is NOT touched (fetch_neumann_flags() brings the bits back).
+        `variable` may differ from the one whose flags are resident: the grid then holds `variable`'s flags, and only the nodes whose
+        bit differs are dirty -- switching a weight buffer from u to v costs the differing rows, not a full launch.  Precedence as for
+        update_permeability(): the device copy stays resident through refresh() / interpolate() / apply() / apply_transpose() until the
+        CONTENTS of the host row change; an in-place edit of the row made afterwards wins at the next call that reads the tables (and
+        then every node is dirty).  The host-synchronous methods need `torch.cuda.current_stream().synchronize()` first.
+
+        `nodes` (1-D integer ids in [0, n_points), m of them): only those nodes change; `flags` is then (m,), value i for node nodes[i].
+        Duplicate ids with equal values are fine; with different values one of them wins, and which one is unspecified.
+        `nodes` a torch tensor (int32 / int64) on this Interpolator's device, `flags` a tensor there: scattered by a kernel on torch's
+        current stream with the rules above.  `variable` must be the one whose flags are resident (ValueError: the other rows would
+        belong to a different variable; with nothing resident yet its host row goes over first).  Ids are checked on the device: one
+        outside [0, n_points) writes nothing and marks nothing, and the next launch_dirty() raises with the count.
+
+        numpy arrays or lists (float64, integers or bool): the `neumann_flag_<variable>` row of `points_data` is rewritten in place with
+        the values as given -- what a fresh load_mesh() of the mesh with those flags holds.  Works without a GPU; ids are checked here
+        (ValueError).  If the grid is on a device and the resident flags are this variable's host row (not a newer device copy, not
+        another variable's), the same values also go through the kernels (needs torch; synchronous), so the resident flags and the dirty
+        set follow; otherwise the next call that reads the tables uploads the row, as after any in-place edit.
+        Host and device arguments cannot be mixed (TypeError)."""
+        row = self._flag_row(variable)
+        g = self.grid
+        P = int(g.n_points)
+        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
+        on_gpu = lambda a: is_torch(a) and getattr(a, "is_cuda", False)
+        if on_gpu(flags) or on_gpu(nodes):
+            import torch
+            where = torch.device("cuda", self.device)
+            if not on_gpu(flags):
+                raise TypeError(f"flags must be a torch.Tensor on {where} when nodes is, not " +
+                                (f"one on {flags.device}" if is_torch(flags) else type(flags).__name__))
+            if nodes is not None and not on_gpu(nodes):
+                raise TypeError(f"nodes must be a torch.Tensor on {where} when flags is, not " +
+                                (f"one on {nodes.device}" if is_torch(nodes) else type(nodes).__name__))
+            if flags.dtype not in (torch.float64, torch.bool, torch.uint8):
+                raise TypeError(f"flags must be float64, bool or uint8, not {flags.dtype} (no silent cast)")
+            if flags.device != where:
+                raise ValueError(f"flags must be on {where}, not {flags.device}")
+            if nodes is None:
+                if tuple(flags.shape) != (P,):
+                    raise ValueError(f"flags must have shape {(P,)}, not {tuple(flags.shape)}")
+                if g.device < 0:
+                    g.to_device(self.device)
+                # the host row is hashed at the FIRST device update behind a host upload, not at every step of a time loop: an in-place
+                # edit of the row made between two device updates is still found by the next call that reads the tables
+                hashed = g._flags_from_device and g._fields_variable == variable and g._flags_key is not None
+                g.load_flags_device(flags.detach().contiguous())
+                g._fields_variable = variable          # only the nodes whose bit differs were marked: no mark_all_dirty()
+                if not hashed:
+                    g._flags_key = _table_key(row)
+                return
+            if nodes.dtype not in (torch.int32, torch.int64):
+                raise TypeError(f"nodes must be int32 or int64, not {nodes.dtype} (no silent cast)")
+            if nodes.device != where:
+                raise ValueError(f"nodes must be on {where}, not {nodes.device}")
+            if nodes.dim() != 1:
+                raise ValueError(f"nodes must have shape (m,), not {tuple(nodes.shape)}")
+            m = int(nodes.shape[0])
+            if tuple(flags.shape) != (m,):
+                raise ValueError(f"flags must have shape {(m,)}, not {tuple(flags.shape)}")
+            if g.device >= 0 and g._fields_variable is not None and g._fields_variable != variable:
+                raise ValueError(f"the flags resident on the device are those of '{g._fields_variable}', not of '{variable}': a subset of "
+                                 "nodes can only be patched into its own variable (pass the whole array to switch)")
+            if m == 0:
+                return
+            if g.device < 0:
+                g.to_device(self.device)
+            if g._fields_variable is None:
+                # nothing is resident on this device copy yet: the host row goes over first (through the device path: the same bits)
+                g.load_flags_device(torch.from_numpy(np.ascontiguousarray(row, dtype=DTYPE_F)).to(where))
+                g._fields_variable = variable
+            hashed = g._flags_from_device and g._flags_key is not None
+            g.scatter_flags_device(nodes.detach().contiguous(), flags.detach().contiguous())
+            if not hashed:
+                g._flags_key = _table_key(row)
+            return
+        if is_torch(flags):
+            flags = flags.detach().numpy()
+        if nodes is not None and is_torch(nodes):
+            nodes = nodes.detach().numpy()
+        try:
+            F = np.asarray(flags)
+            if F.dtype.kind not in "fiub" or (F.dtype.kind == "f" and F.dtype != DTYPE_F):
+                raise TypeError(f"flags must be float64, integers or bool, not {F.dtype} (no silent cast)")
+            F = np.ascontiguousarray(F, dtype=DTYPE_F)
+        except ValueError as e:
+            raise ValueError(f"flags cannot be converted to float64: {e}") from e
+        ids = None
+        if nodes is not None:
+            ids = np.asarray(nodes)
+            if ids.dtype.kind not in "iu" and ids.size:
+                raise TypeError(f"nodes must be integers, not {ids.dtype} (no silent cast)")
+            if ids.ndim != 1:
+                raise ValueError(f"nodes must have shape (m,), not {ids.shape}")
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            bad = (ids < 0) | (ids >= P)
+            if bad.any():
+                raise ValueError(f"nodes must lie in [0, {P}): {int(bad.sum())} of {len(ids)} do not (the first: {int(ids[bad][0])})")
+        shape = (P,) if ids is None else (len(ids),)
+        if F.shape != shape:
+            raise ValueError(f"flags must have shape {shape}, not {F.shape}")
+        if F.size == 0:
+            return
+        if ids is None:
+            row[:] = F
+        else:
+            row[ids] = F                  # duplicate ids with different values: numpy keeps the last, the device an unspecified one
+        # is what is resident this variable's host row (not a newer device copy, not another variable's)?  Then the device follows
+        in_step = g.device >= 0 and g._fields_variable == variable and not g._flags_from_device
+        if in_step:
+            try:
+                import torch
+            except ImportError:
+                in_step = False
+        if in_step:
+            where = torch.device("cuda", g.device)
+            with torch.cuda.device(where):
+                if ids is None:
+                    g.load_flags_device(torch.from_numpy(F).to(where))
+                else:
+                    g.scatter_flags_device(torch.from_numpy(ids).to(where), torch.from_numpy(F).to(where))
+                torch.cuda.current_stream(where).synchronize()
+            g._flags_from_device = False  # the row IS what is resident
+
+    def fetch_neumann_flags(self, variable):
+        """The Neumann bits resident on the device read back into the `neumann_flag_<variable>` row of `points_data` as 0.0 / 1.0 (after
+        update_neumann_flags() from device tensors the row still holds the older values); waits for the device.  The row then IS what is
+        resident and is recorded as such.  `variable` must be the one whose flags are resident (ValueError).  Returns the row (a copy).
+        With nothing resident on a device the row is returned as it is."""
+        row = self._flag_row(variable)
+        g = self.grid
+        if g.device >= 0 and g._fields_variable is not None:
+            if g._fields_variable != variable:
+                raise ValueError(f"the flags resident on the device are those of '{g._fields_variable}', not of '{variable}'")
+            got = g.fetch_flags()
+            if got is not None:
+                row[:] = got
+                g._flags_from_device, g._flags_key = False, None
+        return np.array(row)
+
+    @property
+    def neumann_flags_on_device(self):
+        """True while the Neumann flags resident on the device came from update_neumann_flags() with device tensors and are newer than
+        the `points_data` row: until fetch_neumann_flags(), or the call that finds the host row edited (or another variable asked for)
+        and uploads it.  Like permeability_on_device it reports what has HAPPENED: an in-place edit of the row that no call has read
+        yet does not show here."""
+        g = self.grid
+        return g is not None and g._flags_from_device
+
     def load_arrays(self, points, cells, cell_data=None, point_data=None):
         """`load_mesh` from plain arrays, no meshio object.  `cells` is a list of
         (type name, (n, nodes per cell) int array) blocks in meshio's vertex order -- one block per type, as the
@@ -899,7 +1079,11 @@ class DevicePlan:
     So does a permeability that changes on the device: after Interpolator.update_permeability() with device tensors the next
     `launch` on the same stream computes with the new K -- `launch` never re-reads a table, so a time loop of update_permeability(K_dev)
     and launch(...) touches no host memory and never synchronises.  `refresh()` leaves that K resident as long as the contents of the
-    host table are what they were (the precedence rule of update_permeability)."""
+    host table are what they were (the precedence rule of update_permeability).
+
+    And so do Neumann flags that change on the device: Interpolator.update_neumann_flags() with device tensors rewrites the grid's flags
+    and marks the nodes whose bit changed; launch_dirty() recomputes those rows.  After a whole-array update for ANOTHER variable the
+    grid holds that variable's flags: a plan of the first variable re-uploads its own at its next launch (ensure_current)."""
 
     def __init__(self, interp, variable, method):
         if not interp.is_grid_initialized:
@@ -936,7 +1120,8 @@ class DevicePlan:
             self.refresh()
 
     def any_neumann_flag(self):
-        """Does any node carry neumann_flag_<variable>?  (neumann_ws is identically zero otherwise.)"""
+        """Does any node carry neumann_flag_<variable>?  (neumann_ws is identically zero otherwise.)  It reads the HOST row: after
+        Interpolator.update_neumann_flags() with device tensors it answers for the host row until fetch_neumann_flags()."""
         row = self._v2i["points"]["neumann_flag_" + self.variable]
         return bool(np.any(np.asarray(self._points_data)[row][:self.n_points].astype(np.int64) != 0))
 
@@ -953,8 +1138,8 @@ class DevicePlan:
         clear=True), they hold afterwards what launch() would write now, bit for bit; no other row is touched.  The call reads 128
         bytes back (how many nodes each kernel gets) and so waits for `stream` once; everything else is asynchronous on it.
         clear=False keeps the set (a second buffer follows).  While every node is dirty (Grid.dirty_nodes == -1) this is launch().
-        Raises if cell ids outside the mesh were scattered since the last call: nothing is launched, the set is kept, and the next
-        call goes through."""
+        Raises if cell or node ids outside the mesh were scattered since the last call (update_permeability(cells=), update_points(nodes=),
+        update_neumann_flags(nodes=)): nothing is launched, the set is kept, and the next call goes through."""
         self.ensure_current()
         n = ctypes.c_int64(0)
         _lib.check(_lib.load().nin_weights_dirty_device(self.grid._h, self.method_id, int(bool(add_neumann)), ctypes.c_void_p(csr_data_ptr),
