@@ -301,6 +301,59 @@ int nin_csr_compact_host(nin_grid *g, const double *dev_csr_data, int32_t *indpt
 int nin_interpolate_csr_host(nin_grid *g, int method, int32_t *indptr, int32_t *indices, double *data,
                              int64_t *nnz_out, double *neumann_ws);
 
+/* ---- a host matrix kept current: only the dirty rows cross PCIe -----------------------------------------------------------
+ * nin_interpolate_csr_host runs every row and sends the whole matrix on every call.  A caller in a time loop -- a few cells' K edited,
+ * a boundary layer moved, some flags flipped, and the scipy matrix needed again -- keeps a nin_hostmatrix instead: it owns device
+ * buffers of its own (weights [nnz_esup], neumann_ws [n_points], surviving entries per row [n_points]; NOT the grid's call scratch,
+ * which any nin_interpolate_csr_host overwrites), and after the local updates of the blocks above only the rows of the grid's dirty
+ * set are recomputed (nin_weights_dirty_device into those buffers), counted, packed, transferred and patched into the caller's
+ * arrays.  The result is bit for bit what nin_interpolate_csr_host returns for the mesh as it is now.  The caller owns the host arrays
+ * (indptr [n_points + 1], indices and data with room for nnz_esup entries, neumann_ws [n_points]; page-locked for speed) and passes
+ * them to every call.  One consumer per grid, as for nin_weights_dirty_device with clear != 0: the dirty set is the grid's.
+ *
+ * nin_hostmatrix_create: the device buffers; `method` is fixed.  NIN_ENODEVICE when nin_grid_device(g) is -1.
+ * nin_hostmatrix_full: all rows (add_neumann = 1) into the matrix's buffers, then the count / scan / compaction of
+ *   nin_csr_compact_host into the host arrays; *nnz_out = surviving entries.  Clears the grid's dirty set (marks, every-node flag and the
+ *   counter of refused ids).  Host-synchronous on `stream`.  Also the second half of an update that found every node dirty (below).
+ * nin_hostmatrix_update: the first half of an update.  *n_rows = the rows recomputed, 0 with an empty set (nothing is touched then).
+ *   While every node is dirty the full launch runs, *n_entries = -1, and the caller finishes with nin_hostmatrix_full (which then does
+ *   not launch again).  Otherwise the dirty rows are recomputed in the matrix's buffers, two kernels over the launch's list and one
+ *   scan count and pack them -- what survives is `!= 0.0`: NaNs stay, +-0 go, the rule of nin_csr_compact_host -- 8 bytes come back
+ *   (*n_entries = the packed entries, *n_changed = the rows whose count of surviving entries differs from what the matrix held), and
+ *   the pack leaves for page-locked staging buffers on the grid's copy streams.  The call waits for `stream` twice: once inside
+ *   nin_weights_dirty_device, once for those 8 bytes.  `clear` as there.  If ids were refused since the last call: NIN_EINVAL with
+ *   nin_weights_dirty_device's text, nothing was launched, matrix and dirty set are as they were.
+ * nin_hostmatrix_patch: the second half: waits for the transfers and patches the rows into the caller's arrays (nin_csr_patch_rows
+ *   below).  *n_changed == 0: out_* NULL, the arrays are patched in place.  Otherwise out_indptr [n_points + 1], out_indices and out_data
+ *   (room for nnz_esup entries; not overlapping the old arrays) receive the new matrix; neumann_ws is always patched in place.
+ *   NIN_ESTATE when no update is waiting.  After a failure of either half every node counts as dirty.
+ * nin_hostmatrix_destroy: gives the device and staging buffers back (waits for the device).
+ * NIN_TIMING=1: the phases of an update on stderr ("[nin_hostmatrix] dirty launch | count + pack | D2H | host patch"), each waiting
+ *   for its work. */
+typedef struct nin_hostmatrix nin_hostmatrix;
+int nin_hostmatrix_create(nin_grid *g, int method, nin_hostmatrix **out);
+int nin_hostmatrix_full(nin_hostmatrix *m, int32_t *indptr, int32_t *indices, double *data, double *neumann_ws, int64_t *nnz_out,
+                        void *stream);
+int nin_hostmatrix_update(nin_hostmatrix *m, int clear, void *stream, int64_t *n_rows, int64_t *n_changed, int64_t *n_entries);
+int nin_hostmatrix_patch(nin_hostmatrix *m, const int32_t *indptr, int32_t *indices, double *data, double *neumann_ws,
+                         int32_t *out_indptr, int32_t *out_indices, double *out_data);
+void nin_hostmatrix_destroy(nin_hostmatrix *m);
+
+/* m rows of a CSR matrix replaced, on the host (OpenMP, no device involved): row nodes[i] becomes the counts[i] entries
+ * pack_indices / pack_data [off[i] .. off[i + 1]) and neumann_ws[nodes[i]] = pack_nws[i].  The matrix is indptr [P + 1], indices, data;
+ * `nodes` are distinct rows in any order, off [m + 1] the exclusive prefix sum of counts.
+ *   out_* all NULL: every counts[i] must equal the row's length, and indices, data and neumann_ws are overwritten in place (the indices
+ *     too: equal counts do not imply an equal pattern).
+ *   out_* all given (not overlapping the inputs): out_indptr [P + 1] = the prefix sum of the patched row lengths, out_indices / out_data =
+ *     the rows in order, unchanged ones copied from the old arrays, listed ones from the pack; neumann_ws is patched in place.
+ * NIN_EINVAL, with every array as it was: a NULL argument (out_* aside) or only some of out_*, a negative P or m, a node outside
+ * [0, P), a node listed twice, a negative count, off[0] != 0 or off[i + 1] - off[i] != counts[i], and -- in place -- a count that is not
+ * the row's length.  NIN_ERANGE: the new matrix has more entries than int32 holds (out_indptr is then undefined).  Sets no
+ * nin_last_error() text. */
+int nin_csr_patch_rows(int64_t P, const int32_t *indptr, int32_t *indices, double *data, double *neumann_ws, int64_t m,
+                       const int32_t *nodes, const int32_t *counts, const int32_t *off, const int32_t *pack_indices,
+                       const double *pack_data, const double *pack_nws, int32_t *out_indptr, int32_t *out_indices, double *out_data);
+
 /* Interpolate a cell field to the nodes without materialising the matrix on the host: weights for all nodes (with the
  * `+ neumann_ws[row]` of interpolator.pyx:618), then node_values = W . u_cells on the device -- what the reference's
  * callers compute next as `weights.dot(u)` (tests/utils/analytical.py:236).  Host pointers: u_cells [n_elems],

@@ -27,6 +27,8 @@ EXPORTS = (
     "nin_fields_scatter_permeability_device", "nin_weights_dirty_device", "nin_grid_dirty_nodes", "nin_grid_dirty_reset",
     "nin_grid_scatter_points_device", "nin_grid_scatter_points",
     "nin_fields_set_flags_device", "nin_fields_scatter_flags_device", "nin_fields_get_flags", "nin_grid_flag_updates",
+    "nin_hostmatrix_create", "nin_hostmatrix_full", "nin_hostmatrix_update", "nin_hostmatrix_patch", "nin_hostmatrix_destroy",
+    "nin_csr_patch_rows",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -108,6 +110,13 @@ def load():
     L.nin_grid_dirty_nodes.argtypes = [vp]
     L.nin_grid_dirty_nodes.restype = i64
     L.nin_grid_dirty_reset.argtypes = [vp, i32, vp]
+    L.nin_hostmatrix_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
+    L.nin_hostmatrix_full.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp]
+    L.nin_hostmatrix_update.argtypes = [vp, i32, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.nin_hostmatrix_patch.argtypes = [vp] * 8
+    L.nin_hostmatrix_destroy.argtypes = [vp]
+    L.nin_hostmatrix_destroy.restype = None
+    L.nin_csr_patch_rows.argtypes = [i64, vp, vp, vp, vp, i64] + [vp] * 9
     L.nin_exchange_create.argtypes = [i32, i32, i32, ctypes.c_size_t, ctypes.POINTER(vp)]
     L.nin_exchange_destroy.argtypes = [vp]
     L.nin_exchange_destroy.restype = None

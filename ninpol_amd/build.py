@@ -34,6 +34,9 @@ UNITS = [
     ("kernels_gls_mfg.hip", "hipcc", []),
     ("kernels_gls_quad4.hip", "hipcc", []),
     ("kernels_csr.hip", "hipcc", []),
+    # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
+    ("csr_dirty.hip", "hipcc", []),
+    ("csr_patch.cpp", "g++", ["-fopenmp"]),
     # device-side grid build: no contraction, like grid_host.cpp (float32 normals must match the reference)
     ("grid_device.hip", "hipcc", ["-ffp-contract=off"]),
     # geometry refresh of a moving mesh: the same arithmetic as grid_device.hip's geometry kernels, the same flag

@@ -1616,6 +1616,252 @@ int nin_interpolate_csr_host(nin_grid *g, int method, int32_t *indptr, int32_t *
     return rc;
 }
 
+// ---- a host matrix kept current: only the dirty rows cross PCIe (csr_dirty.hip, csr_patch.cpp) ----------------------
+struct nin_hostmatrix {
+    nin_grid *g = nullptr;
+    int method = 0;
+    int device = -1;                // the grid's, as it was at creation: nin_hostmatrix_destroy does not look at the grid, which may be gone
+    // the matrix's own device state: weights in esup position, neumann_ws, surviving entries per row (not the grid's e2e_* scratch,
+    // which any interpolate() overwrites)
+    double *weights = nullptr, *nws = nullptr;
+    int32_t *cnt = nullptr;
+    bool weights_current = false;   // nin_hostmatrix_update found every node dirty and ran the full launch: nin_hostmatrix_full finishes it
+    // scratch of an update, sized by the dirty list and grown on demand: per listed row (pack_off has two more: the total and the
+    // counter of rows whose count changed, read back together) and per packed entry; the same again page-locked on the host
+    size_t rows_cap = 0, entries_cap = 0, h_rows_cap = 0, h_entries_cap = 0;
+    int32_t *pack_cnt = nullptr, *pack_off = nullptr, *pack_node = nullptr, *pack_indices = nullptr;
+    double *pack_nws = nullptr, *pack_data = nullptr;
+    void *scan_tmp = nullptr;
+    size_t scan_tmp_bytes = 0;
+    int32_t *h_cnt = nullptr, *h_off = nullptr, *h_node = nullptr, *h_indices = nullptr;
+    double *h_nws = nullptr, *h_data = nullptr;
+    int64_t pending_rows = -1;      // rows of the last update whose pack is on its way to the host (nin_hostmatrix_patch takes them)
+};
+
+namespace {
+
+struct HmLaps {   // NIN_TIMING=1: the phases of one update on stderr; each lap then waits for the work it names
+    bool on = getenv("NIN_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char *what, std::initializer_list<hipStream_t> wait_for) {
+        if (!on) return;
+        for (hipStream_t s : wait_for) (void)hipStreamSynchronize(s);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[nin_hostmatrix] %-14s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+        t = now;
+    }
+};
+
+extern "C++" {
+template <class T>
+int hm_grow(T **buf, size_t count, bool on_host) {
+    if (*buf) (void)(on_host ? hipHostFree(*buf) : hipFree(*buf));
+    *buf = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    const hipError_t e = on_host ? hipHostMalloc((void **)buf, bytes, hipHostMallocDefault) : hipMalloc((void **)buf, bytes);
+    return e == hipSuccess ? NIN_OK : fail(NIN_ENOMEM, "%s(%zu bytes): %s", on_host ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+}
+}
+
+// room for `rows` listed rows and `entries` packed entries, on the device or in page-locked host memory (half as much again: a time
+// loop's dirty set wobbles).  Growing frees first, which waits for the device: nothing of an earlier update is in flight by then.
+int hm_reserve(nin_hostmatrix *m, size_t rows, size_t entries, bool on_host) {
+    size_t &rc_ = on_host ? m->h_rows_cap : m->rows_cap, &ec_ = on_host ? m->h_entries_cap : m->entries_cap;
+    int rc = NIN_OK;
+    if (rows > rc_) {
+        const size_t n = rows + rows / 2;
+        rc_ = 0;
+        if (!rc) rc = hm_grow(on_host ? &m->h_cnt : &m->pack_cnt, n + 1, on_host);
+        if (!rc) rc = hm_grow(on_host ? &m->h_off : &m->pack_off, n + 2, on_host);
+        if (!rc) rc = hm_grow(on_host ? &m->h_node : &m->pack_node, n, on_host);
+        if (!rc) rc = hm_grow(on_host ? &m->h_nws : &m->pack_nws, n, on_host);
+        if (rc) return rc;
+        rc_ = n;
+    }
+    if (entries > ec_ || !(on_host ? m->h_data : m->pack_data)) {
+        const size_t n = entries + entries / 2;
+        ec_ = 0;
+        if (!rc) rc = hm_grow(on_host ? &m->h_indices : &m->pack_indices, n, on_host);
+        if (!rc) rc = hm_grow(on_host ? &m->h_data : &m->pack_data, n, on_host);
+        if (rc) return rc;
+        ec_ = n;
+    }
+    return NIN_OK;
+}
+
+}  // namespace
+
+int nin_hostmatrix_create(nin_grid *g, int method, nin_hostmatrix **out) {
+    if (!g || !out) return fail(NIN_EINVAL, "NULL argument");
+    *out = nullptr;
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
+    if (method != NIN_METHOD_GLS && method != NIN_METHOD_IDW && method != NIN_METHOD_LS) return fail(NIN_EINVAL, "unknown method %d", method);
+    HIP_TRY(hipSetDevice(d.device));
+    nin_hostmatrix *m = new (std::nothrow) nin_hostmatrix();
+    if (!m) return fail(NIN_ENOMEM, "out of host memory");
+    m->g = g;
+    m->method = method;
+    m->device = d.device;
+    int rc = hm_grow(&m->weights, (size_t)d.nnz_e, false);
+    if (!rc) rc = hm_grow(&m->nws, (size_t)g->h.n_points, false);
+    if (!rc) rc = hm_grow(&m->cnt, (size_t)g->h.n_points, false);
+    if (rc) { nin_hostmatrix_destroy(m); return rc; }
+    *out = m;
+    return NIN_OK;
+}
+
+void nin_hostmatrix_destroy(nin_hostmatrix *m) {
+    if (!m) return;
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    for (void *p : {(void *)m->weights, (void *)m->nws, (void *)m->cnt, (void *)m->pack_cnt, (void *)m->pack_off, (void *)m->pack_node,
+                    (void *)m->pack_indices, (void *)m->pack_nws, (void *)m->pack_data, m->scan_tmp})
+        if (p) (void)hipFree(p);   // (waits for the device)
+    for (void *p : {(void *)m->h_cnt, (void *)m->h_off, (void *)m->h_node, (void *)m->h_indices, (void *)m->h_nws, (void *)m->h_data})
+        if (p) (void)hipHostFree(p);
+    delete m;
+}
+
+int nin_hostmatrix_full(nin_hostmatrix *m, int32_t *indptr, int32_t *indices, double *data, double *neumann_ws, int64_t *nnz_out,
+                        void *stream_) {
+    if (!m || !indptr || !indices || !data || !neumann_ws || !nnz_out) return fail(NIN_EINVAL, "NULL argument");
+    nin_grid *g = m->g;
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the weight kernels are HIP only");
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = NIN_OK;
+    if (!m->weights_current) {   // (else nin_hostmatrix_update has run the launch and cleared the set)
+        if ((rc = nin_weights_device(g, m->method, nullptr, 0, 1, m->weights, m->nws, stream_))) return rc;
+        if ((rc = nin_grid_dirty_reset(g, 0, stream_))) return rc;
+    }
+    m->weights_current = false;
+    m->pending_rows = -1;
+    // the existing finish: count, scan and compaction in the grid's scratch, the transfers under them; the row counts stay with the matrix
+    rc = csr_compact_pipelined(g, m->weights, m->nws, indptr, indices, data, nnz_out, neumann_ws, stream);
+    if (!rc) {
+        const hipError_t e = hipMemcpyAsync(m->cnt, d.e2e_cnt, (size_t)g->h.n_points * sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
+        if (e != hipSuccess) rc = fail(NIN_EHIP, "keeping the row counts: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess && !rc) rc = fail(NIN_EHIP, "full run of the host matrix: %s", hipGetErrorString(e));
+    if (rc) d.all_dirty = true;   // the matrix holds no full result: the next update starts over
+    return rc;
+}
+
+int nin_hostmatrix_update(nin_hostmatrix *m, int clear, void *stream_, int64_t *n_rows, int64_t *n_changed, int64_t *n_entries) {
+    if (!m || !n_rows || !n_changed || !n_entries) return fail(NIN_EINVAL, "NULL argument");
+    *n_rows = *n_changed = *n_entries = 0;
+    nin_grid *g = m->g;
+    DeviceGrid &d = g->d;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (m->pending_rows >= 0) {   // an update nobody patched in: its copies must not be in flight when the staging buffers are reused
+        (void)hipStreamSynchronize(static_cast<hipStream_t>(d.copy_stream));
+        (void)hipStreamSynchronize(static_cast<hipStream_t>(d.copy_stream2));
+        m->pending_rows = -1;
+        d.all_dirty = true;       // ... and the host's arrays missed those rows
+    }
+    const bool full = d.all_dirty;
+    HmLaps L;
+    int64_t n = 0;
+    // refused ids: nothing is launched, the matrix and the set stay as they are (nin_weights_dirty_device's contract)
+    int rc = nin_weights_dirty_device(g, m->method, 1, m->weights, m->nws, stream_, clear, &n);
+    if (rc) return rc;
+    *n_rows = n;
+    if (full) {   // every row was launched: the ordinary finish follows (nin_hostmatrix_full)
+        m->weights_current = true;
+        *n_entries = -1;
+        return NIN_OK;
+    }
+    if (n == 0) return NIN_OK;
+    L.lap("dirty launch", {stream});
+    const int32_t total = (int32_t)n;
+    // what the rows of the list can hold at most: the pack's size is not known on the host before the kernels that fill it are enqueued
+    const size_t bound = (size_t)std::min<int64_t>(n * std::max<int64_t>(g->h.mx_elems_per_point, 1), d.nnz_e);
+    size_t tmp_bytes = 0;
+    int32_t back[2] = {0, 0};   // pack_off[total] = the packed entries, pack_off[total + 1] = the rows whose count changed
+    auto step = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && !rc) rc = fail(NIN_EHIP, "%s: %s", what, hipGetErrorString(e));
+        return rc == NIN_OK;
+    };
+    rc = hm_reserve(m, (size_t)total, bound, false);
+    if (!rc) rc = e2e_streams(d);
+    if (!rc && !d.copy_stream2) {
+        hipStream_t s2 = nullptr;
+        if (step(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking), "hipStreamCreate")) d.copy_stream2 = s2;
+    }
+    hipStream_t cs = static_cast<hipStream_t>(d.copy_stream), cs2 = static_cast<hipStream_t>(d.copy_stream2);
+    hipEvent_t ev_scan = static_cast<hipEvent_t>(d.ev_scan), ev_pack = static_cast<hipEvent_t>(d.ev_weights);
+    if (!rc && step(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, m->pack_cnt, m->pack_off, total + 1, stream), "sizing the scan") &&
+        tmp_bytes > m->scan_tmp_bytes) {
+        m->scan_tmp_bytes = 0;
+        if (!(rc = hm_grow(reinterpret_cast<char **>(&m->scan_tmp), std::max<size_t>(tmp_bytes, 16), false))) m->scan_tmp_bytes = std::max<size_t>(tmp_bytes, 16);
+    }
+    if (!rc) {
+        (void)(step(hipMemsetAsync(m->pack_cnt + total, 0, sizeof(int32_t), stream), "hipMemsetAsync") &&
+               step(hipMemsetAsync(m->pack_off + total + 1, 0, sizeof(int32_t), stream), "hipMemsetAsync"));
+        if (!rc && launch_dirty_row_nnz(d.v, m->weights, d.dirty_lists, total, m->pack_cnt, m->cnt, m->pack_off + total + 1, stream))
+            rc = fail(NIN_EHIP, "row count kernel: %s", hipGetErrorString(hipGetLastError()));
+        size_t tb = m->scan_tmp_bytes;
+        // the sizes leave on the copy stream as soon as the scan is done, under the pack kernel: the call's second and last wait
+        (void)(step(hipcub::DeviceScan::ExclusiveSum(m->scan_tmp, tb, m->pack_cnt, m->pack_off, total + 1, stream), "scan of the row counts") &&
+               step(hipEventRecord(ev_scan, stream), "hipEventRecord") && step(hipStreamWaitEvent(cs, ev_scan, 0), "hipStreamWaitEvent") &&
+               step(hipMemcpyAsync(back, m->pack_off + total, sizeof back, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync"));
+        if (!rc && launch_dirty_pack(d.v, m->weights, m->nws, d.dirty_lists, total, m->pack_off, m->pack_node, m->pack_nws, m->pack_indices,
+                                     m->pack_data, stream))
+            rc = fail(NIN_EHIP, "pack kernel: %s", hipGetErrorString(hipGetLastError()));
+        (void)(step(hipEventRecord(ev_pack, stream), "hipEventRecord") && step(hipStreamSynchronize(cs), "reading the pack's size back"));
+    }
+    if (!rc && (back[0] < 0 || (size_t)back[0] > bound || back[1] < 0 || back[1] > total))
+        rc = fail(NIN_EHIP, "the pack holds %d entries (room for %zu) and %d changed rows of %d", (int)back[0], bound, (int)back[1], (int)total);
+    L.lap("count + pack", {stream});
+    if (!rc) rc = hm_reserve(m, (size_t)total, (size_t)back[0], true);
+    if (!rc) {
+        const size_t rows = (size_t)total, ents = (size_t)back[0];
+        (void)(step(hipStreamWaitEvent(cs, ev_pack, 0), "hipStreamWaitEvent") && step(hipStreamWaitEvent(cs2, ev_pack, 0), "hipStreamWaitEvent") &&
+               step(hipMemcpyAsync(m->h_node, m->pack_node, rows * 4, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync") &&
+               step(hipMemcpyAsync(m->h_cnt, m->pack_cnt, rows * 4, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync") &&
+               step(hipMemcpyAsync(m->h_off, m->pack_off, (rows + 1) * 4, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync") &&
+               step(hipMemcpyAsync(m->h_nws, m->pack_nws, rows * 8, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync"));
+        if (!rc && ents)   // two copy queues, as interpolate()'s pipeline: the index and the value stream each keep a DMA engine busy
+            (void)(step(hipMemcpyAsync(m->h_data, m->pack_data, ents * 8, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync") &&
+                   step(hipMemcpyAsync(m->h_indices, m->pack_indices, ents * 4, hipMemcpyDeviceToHost, cs2), "hipMemcpyAsync"));
+    }
+    if (rc) {   // rows were rewritten on the device that the host will not get: everything counts as dirty again
+        (void)hipStreamSynchronize(stream); (void)hipStreamSynchronize(cs);
+        if (cs2) (void)hipStreamSynchronize(cs2);
+        d.all_dirty = true;
+        return rc;
+    }
+    L.lap("D2H", {cs, cs2});
+    m->pending_rows = total;
+    *n_changed = back[1];
+    *n_entries = back[0];
+    return NIN_OK;
+}
+
+int nin_hostmatrix_patch(nin_hostmatrix *m, const int32_t *indptr, int32_t *indices, double *data, double *neumann_ws, int32_t *out_indptr,
+                         int32_t *out_indices, double *out_data) {
+    if (!m || !indptr || !indices || !data || !neumann_ws) return fail(NIN_EINVAL, "NULL argument");
+    if (m->pending_rows < 0) return fail(NIN_ESTATE, "no update is waiting to be patched in (nin_hostmatrix_update first)");
+    DeviceGrid &d = m->g->d;
+    HIP_TRY(hipSetDevice(d.device));
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(d.copy_stream)));
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(d.copy_stream2)));
+    HmLaps L;
+    const int64_t rows = m->pending_rows;
+    m->pending_rows = -1;
+    const int rc = nin_csr_patch_rows(m->g->h.n_points, indptr, indices, data, neumann_ws, rows, m->h_node, m->h_cnt, m->h_off, m->h_indices,
+                                      m->h_data, m->h_nws, out_indptr, out_indices, out_data);
+    L.lap("host patch", {});
+    if (rc) {
+        d.all_dirty = true;   // the device is ahead of the host's arrays
+        return fail(rc, rc == NIN_ERANGE ? "the patched matrix has more entries than int32 indices hold"
+                                         : "the packed rows do not fit the matrix they are patched into (out_* missing for a new structure, or other arrays)");
+    }
+    return NIN_OK;
+}
+
 // Give the grid's call scratch back (the buffers nin_interpolate_csr_host / nin_csr_compact_host / nin_apply_* allocate
 // on first use and keep: ~2.3 GB of HBM at 10 M cells, + 10 MB of page-locked host memory; the transpose index, 0.69 GB more);
 // the next call allocates again.

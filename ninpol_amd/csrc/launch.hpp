@@ -169,6 +169,16 @@ int launch_dirty_compact(int32_t n_points, int single, int clear, uint8_t *dirty
 // *out += the number of marked nodes
 int launch_dirty_count(int32_t n_points, const uint8_t *dirty, int32_t *out, hipStream_t stream);
 
+// csr_dirty.hip: the rows of a dirty launch's list (`list` [total]: unique node ids in any order) counted and packed, all DEVICE
+// pointers; `data` / `nws` as the weight kernels wrote them (esup position).  launch_dirty_row_nnz: pack_cnt[i] = entries != 0.0 of the
+// row of list[i]; cnt [n_points], the resident count of every row, follows, and *changed += the rows whose count moved.
+// launch_dirty_pack, behind the exclusive scan pack_off of pack_cnt: row i's surviving (column, value) pairs at pack_off[i] of
+// pack_indices / pack_data (room for pack_off[total] entries), pack_node[i] = list[i], pack_nws[i] = nws[list[i]]
+int launch_dirty_row_nnz(const GridView &g, const double *data, const int32_t *list, int32_t total, int32_t *pack_cnt, int32_t *cnt,
+                         int32_t *changed, hipStream_t stream);
+int launch_dirty_pack(const GridView &g, const double *data, const double *nws, const int32_t *list, int32_t total, const int32_t *pack_off,
+                      int32_t *pack_node, double *pack_nws, int32_t *pack_indices, double *pack_data, hipStream_t stream);
+
 const char *kernel_name_idw();
 const char *kernel_name_ls();
 const char *kernel_name_gls();

@@ -1147,6 +1147,12 @@ class DevicePlan:
                                                         ctypes.byref(n)))
         return int(n.value)
 
+    def host_matrix(self, stream=0):
+        """The matrix of Interpolator.interpolate(variable, method) on the host, kept current by this plan: a HostMatrix.  A full run
+        now (host-synchronous on `stream`) into buffers the HostMatrix owns; its update() then recomputes, transfers and patches only
+        the grid's dirty rows.  Clears the grid's dirty set -- one consumer per grid, the contract of launch_dirty(clear=True)."""
+        return HostMatrix(self, stream)
+
     def launch_apply(self, u_cells_ptr, n_fields, node_values_ptr, neumann_ws_ptr, stream=0):
         """W . u on the device for n_fields cell fields (nin_apply_device): u [n_fields][n_elems] ->
         node_values [n_fields][n_points], weights computed once; asynchronous on `stream`."""
@@ -1166,3 +1172,112 @@ class DevicePlan:
         asynchronous on `stream` (the first call on a grid builds the transpose index and synchronises)."""
         _lib.check(_lib.load().nin_spmv_transpose_device(self.grid._h, ctypes.c_void_p(weights_ptr), ctypes.c_void_p(values_ptr),
                                                          int(n_fields), ctypes.c_void_p(cells_ptr), ctypes.c_void_p(stream)))
+
+
+class HostMatrix:
+    """`W, neumann = Interpolator.interpolate(variable, method)` as an object that stays current: `M.W` (scipy csr_matrix, n_points x
+    n_elems, int32 indices) and `M.neumann` (n_points,) in page-locked host memory.  After Interpolator.update_permeability(cells=),
+    update_points(nodes=) or update_neumann_flags(nodes=) -- numpy or device arguments -- `M.update()` recomputes the grid's dirty rows on
+    the device, brings only those rows over PCIe and patches them in; afterwards indptr, indices, data and neumann are bit for bit what
+    interpolate() of a fresh load_mesh() of the mesh as it is now returns.
+
+    Like DevicePlan.launch_dirty it computes from what is resident on the device (plan.refresh() re-reads the tables and makes every node
+    dirty), and the dirty set is the grid's: one HostMatrix (or one launch_dirty consumer) per grid.  Its device buffers -- weights, neumann_ws
+    and row counts -- are its own: interpolate() / apply() calls in between do not disturb it.  Made by DevicePlan.host_matrix()."""
+
+    def __init__(self, plan, stream=0):
+        g = plan.grid
+        if max(g.nnz_esup, g.n_elems, g.n_points) >= np.iinfo(np.int32).max:
+            raise ValueError("this mesh needs int64 indices: a HostMatrix holds int32 ones (use interpolate())")
+        if plan.method == "gls" and g.dim == 2:
+            import warnings
+            warnings.warn("GLS on a 2-D mesh: the reference's result there is undefined (rank-deficient system); "
+                          "values will not match ninpol's", RuntimeWarning, stacklevel=3)
+        self.plan = plan
+        self.W = self.neumann = None
+        self.structure_changed = False
+        self._h = None
+        self._full(stream)
+        self.structure_changed = False
+
+    @staticmethod
+    def _empty(n, dtype):
+        return (np.empty if os.environ.get("NINPOL_AMD_NO_PINNED") else _pinned.empty)(n, dtype=dtype)
+
+    def _full(self, stream):
+        """every row: the full launch (unless update() has just run it) and the ordinary count / scan / compaction"""
+        L = _lib.load()
+        g = self.plan.grid
+        P, E = g.n_points, g.n_elems
+        self.plan.ensure_current()
+        moved = self._h is None          # new buffers: whoever holds the old arrays keeps the old matrix
+        if moved:
+            h = ctypes.c_void_p()
+            _lib.check(L.nin_hostmatrix_create(g._h, self.plan.method_id, ctypes.byref(h)))
+            self._h = h
+            self._indices, self._data = self._empty(g.nnz_esup, np.int32), self._empty(g.nnz_esup, DTYPE_F)
+            self.neumann = self._empty(P, DTYPE_F)
+        indptr = self._empty(P + 1, np.int32)
+        nnz = ctypes.c_int64(0)
+        _lib.check(L.nin_hostmatrix_full(self._h, _ptr(indptr), _ptr(self._indices), _ptr(self._data), _ptr(self.neumann),
+                                         ctypes.byref(nnz), ctypes.c_void_p(stream)))
+        if not moved and np.array_equal(indptr, self.W.indptr):
+            self.structure_changed = False      # same row lengths: the arrays of M.W were rewritten where they are
+        else:
+            self.W = _wrap_csr(self._data[:nnz.value], self._indices[:nnz.value], indptr, (P, E))
+            self.structure_changed = True
+
+    def update(self, clear=True, stream=0):
+        """Bring M.W and M.neumann up to date with the grid's dirty rows and return how many rows that were (0: nothing was touched).
+        `structure_changed` says what happened to the objects: False -- no dirty row's count of surviving entries changed, and indptr,
+        indices, data were patched in place (the same arrays: references to M.W stay valid; indices are rewritten too, equal counts do not
+        imply an equal pattern); True -- M.W is a new matrix over new arrays (a flag flipped to Dirichlet empties a row, for example); after a
+        patch, arrays handed out before keep the old matrix (after a full run they share M's buffers and hold the new entries).  An entry survives when it is `!= 0.0` (NaNs stay, +-0 go), as in interpolate().
+        While every node is dirty (Grid.dirty_nodes == -1: a whole-array update, plan.refresh() after an edit, the first call after
+        release()) this is the full run, rewritten in place when the row lengths allow.  Host-synchronous on `stream`; `clear` as
+        launch_dirty's.  Raises what launch_dirty raises if ids outside the mesh were scattered since the last call: M and the dirty set
+        stay as they are, and the next update() goes through."""
+        L = _lib.load()
+        g = self.plan.grid
+        if self._h is None:
+            self._full(stream)
+            return int(g.n_points)
+        self.plan.ensure_current()
+        n, changed, entries = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(L.nin_hostmatrix_update(self._h, int(bool(clear)), ctypes.c_void_p(stream), ctypes.byref(n), ctypes.byref(changed),
+                                           ctypes.byref(entries)))
+        if entries.value < 0:            # every node was dirty
+            self._full(stream)
+            return int(n.value)
+        self.structure_changed = False
+        if n.value == 0:
+            return 0
+        W = self.W
+        if changed.value == 0:
+            _lib.check(L.nin_hostmatrix_patch(self._h, _ptr(W.indptr), _ptr(self._indices), _ptr(self._data), _ptr(self.neumann),
+                                              None, None, None))
+            return int(n.value)
+        P = g.n_points
+        indptr = self._empty(P + 1, np.int32)
+        indices, data = self._empty(g.nnz_esup, np.int32), self._empty(g.nnz_esup, DTYPE_F)
+        _lib.check(L.nin_hostmatrix_patch(self._h, _ptr(W.indptr), _ptr(self._indices), _ptr(self._data), _ptr(self.neumann),
+                                          _ptr(indptr), _ptr(indices), _ptr(data)))
+        nnz = int(indptr[P])
+        self._indices, self._data = indices, data
+        self.W = _wrap_csr(data[:nnz], indices[:nnz], indptr, (P, g.n_elems))
+        self.structure_changed = True
+        return int(n.value)
+
+    def release(self):
+        """Give the device buffers and the page-locked staging back.  M.W and M.neumann stay valid as they are; the next update() allocates
+        again and is a full run."""
+        if self._h is not None:
+            _lib.load().nin_hostmatrix_destroy(self._h)
+            self._h = None
+        self._indices = self._data = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:       # interpreter shutdown
+            pass
