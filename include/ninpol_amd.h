@@ -393,6 +393,45 @@ int nin_spmv_transpose_device(nin_grid *g, const double *dev_csr_data, const dou
                               double *dev_cell_values, void *stream);
 int nin_apply_transpose_fields_host(nin_grid *g, int method, const double *node_values, int32_t n_fields, double *cell_values);
 
+/* ---- the GLS weights differentiated with respect to the permeability ---------------------------------------------------------
+ * The GLS weights are a function of the resident permeability K (and of diff_mag = (1 - 3 / tr K)^2, which the table derives from
+ * it).  Given the gradient of a scalar L with respect to the STORED weights -- the entries nin_weights_device(NIN_METHOD_GLS, ...,
+ * add_neumann, ...) writes, esup / CSR position -- these calls return dL/dK.  IDW and LS do not depend on K.  The reference has no
+ * counterpart (its callers would difference the whole computation).  All pointers are DEVICE pointers, `stream` a hipStream_t.
+ *
+ * nin_gls_weights_backward_device: dev_grad_csr [nnz_esup] = dL/d csr_data; dev_grad_neumann_ws [n_points] = dL/d neumann_ws, or
+ *   NULL (none); add_neumann as in the forward call whose weights were differentiated.  Writes dev_grad_perm [n_elems][9] = dL/dK
+ *   (row-major 3 x 3 per cell) with diff_mag held fixed and dev_grad_diff_mag [n_elems] = dL/d diff_mag; with dev_grad_diff_mag
+ *   NULL the chain through the table's diff_mag is folded into the diagonal of dev_grad_perm, which is then dL/dK altogether.
+ *   Nodes the forward gives the zero row (Dirichlet boundary nodes, too few rows, a singular or non-finite system) contribute
+ *   nothing.  It differentiates at what is resident NOW: geometry, flags, K.  One node per workgroup, a dense Householder QR kept
+ *   for two least-squares solves; per (node, cell) pair ten values go to a contribution buffer, and every cell then sums its nodes'
+ *   in ascending node id: deterministic, no atomics, two calls agree bit for bit.
+ *   The first call on a grid bins the nodes by system size, allocates the contribution buffer -- 80 bytes per entry of esup: 6.4 GB
+ *   at 216^3 hexahedra -- and the scratch slots of the systems that do not fit a CU's LDS, builds the transpose index of
+ *   nin_spmv_transpose_device if it is not there, and synchronises `stream`; later calls are asynchronous on it.  All of it is kept
+ *   by the grid until nin_grid_release_scratch.  NIN_ESTATE before nin_fields_set or without permeability, NIN_ENODEVICE for a grid
+ *   that is not on a device, NIN_EINVAL for a NULL grid, dev_grad_csr or dev_grad_perm.
+ *   The environment variable NIN_GLS_ADJ_FORCE_GLOBAL (read when the bins are made) sends every node through the global-scratch
+ *   class: a testing switch.  NIN_GLS_ADJ_ONLY=<bin> (read at every call) launches only that bin's kernel before the gather:
+ *   per-bin timing, the other nodes' slots keep what they held.
+ * nin_sddmm_device: the sampled product dev_grad_csr[pos] = sum_f node_values[f][p] * u_cells[f][esup[pos]] for every entry pos of
+ *   every row p -- the gradient of <node_values, W u_cells> with respect to the stored weights; u_cells [n_fields][n_elems],
+ *   node_values [n_fields][n_points].  Asynchronous on `stream`; needs no fields.  NIN_EINVAL for a NULL pointer or n_fields < 1,
+ *   NIN_ENODEVICE as above.
+ * nin_gls_permeability_gradient_host: the host-pointer counterpart, the sibling of nin_apply_transpose_fields_host -- grad_permeability
+ *   [n_elems][9] = d <node_values, W cell_values> / dK for the W of nin_apply_* (add_neumann = 1), the diff_mag chain folded;
+ *   node_values [n_fields][n_points], cell_values [n_fields][n_elems]; synchronous.  Errors as the two calls it makes.
+ * nin_gls_adjoint_plan: nodes per bin of the adjoint kernel -- the LDS classes of one, two and four wavefronts per node, then the
+ *   global-scratch class (diagnostics and tests).  Makes the bins if they are not there (synchronous). */
+int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
+                                    double *dev_grad_perm, double *dev_grad_diff_mag, void *stream);
+int nin_sddmm_device(nin_grid *g, const double *dev_u_cells, const double *dev_node_values, int32_t n_fields, double *dev_grad_csr,
+                     void *stream);
+int nin_gls_permeability_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields,
+                                       double *grad_permeability);
+int nin_gls_adjoint_plan(nin_grid *g, int64_t counts[4]);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].
@@ -415,7 +454,7 @@ int nin_host_free(void *ptr);
 
 /* Give back the scratch a grid keeps between calls: the device buffers nin_interpolate_csr_host / nin_csr_compact_host /
  * nin_apply_* allocate on first use (weights, compacted triplets, counters: ~2.3 GB of HBM at 10 M cells, 8 x that at
- * 80 M), the transpose index of nin_spmv_transpose_device (~0.69 GB at 10 M hexahedra), the connectivity copies of nin_grid_update_points* (~1.05 GB at 10 M hexahedra; kept while a grid built on the device still mirrors from them) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
+ * 80 M), the transpose index of nin_spmv_transpose_device (~0.69 GB at 10 M hexahedra), the bins, contribution buffer and scratch slots of nin_gls_weights_backward_device (6.4 GB at 10 M hexahedra), the connectivity copies of nin_grid_update_points* (~1.05 GB at 10 M hexahedra; kept while a grid built on the device still mirrors from them) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
  * weight table when interpolate() returns, interpolator.pyx:650-651.) */
 int nin_grid_release_scratch(nin_grid *g);
 

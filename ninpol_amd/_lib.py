@@ -29,6 +29,7 @@ EXPORTS = (
     "nin_fields_set_flags_device", "nin_fields_scatter_flags_device", "nin_fields_get_flags", "nin_grid_flag_updates",
     "nin_hostmatrix_create", "nin_hostmatrix_full", "nin_hostmatrix_update", "nin_hostmatrix_patch", "nin_hostmatrix_destroy",
     "nin_csr_patch_rows",
+    "nin_gls_weights_backward_device", "nin_sddmm_device", "nin_gls_adjoint_plan", "nin_gls_permeability_gradient_host",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -76,6 +77,10 @@ def load():
     L.nin_spmv_device.argtypes = [vp, vp, vp, i32, vp, vp]
     L.nin_spmv_transpose_device.argtypes = [vp, vp, vp, i32, vp, vp]
     L.nin_apply_transpose_fields_host.argtypes = [vp, i32, vp, i32, vp]
+    L.nin_gls_weights_backward_device.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.nin_sddmm_device.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.nin_gls_adjoint_plan.argtypes = [vp, vp]
+    L.nin_gls_permeability_gradient_host.argtypes = [vp, vp, vp, i32, vp]
     L.nin_pack_connectivity.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     L.nin_pack_table_row.argtypes = [vp, i64, i64, i64, vp]
     L.nin_diff_mag.argtypes = [vp, i64, vp]

@@ -33,6 +33,8 @@ UNITS = [
     ("kernels_gls_mfx.hip", "hipcc", []),
     ("kernels_gls_mfg.hip", "hipcc", []),
     ("kernels_gls_quad4.hip", "hipcc", []),
+    # the GLS weights differentiated with respect to the permeability: a dense QR per node kept for two solves, and the gather
+    ("kernels_gls_adjoint.hip", "hipcc", []),
     ("kernels_csr.hip", "hipcc", []),
     # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
     ("csr_dirty.hip", "hipcc", []),

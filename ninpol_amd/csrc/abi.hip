@@ -15,6 +15,7 @@
 
 #include "../../include/ninpol_amd.h"
 #include "device_grid.hpp"
+#include "gls_adjoint.hpp"
 #include "grid_host.hpp"
 #include "hex8_desc.hpp"
 #include "launch.hpp"
@@ -1865,6 +1866,7 @@ int nin_hostmatrix_patch(nin_hostmatrix *m, const int32_t *indptr, int32_t *indi
 // Give the grid's call scratch back (the buffers nin_interpolate_csr_host / nin_csr_compact_host / nin_apply_* allocate
 // on first use and keep: ~2.3 GB of HBM at 10 M cells, + 10 MB of page-locked host memory; the transpose index, 0.69 GB more);
 // the next call allocates again.
+static void release_adjoint_state(DeviceGrid &d);   // (with the adjoint, below)
 int nin_grid_release_scratch(nin_grid *g) {
     if (!g) return fail(NIN_EINVAL, "NULL grid");
     DeviceGrid &d = g->d;
@@ -1880,6 +1882,7 @@ int nin_grid_release_scratch(nin_grid *g) {
     d.e2e_tmp_bytes = 0;
     d.apply_weights = nullptr;
     d.tr_cell_ptr = d.tr_cell_pos = d.tr_cell_node = nullptr;
+    release_adjoint_state(d);   // the GLS adjoint's bins, contribution buffer and scratch slots
     // a dirty launch's lists, histogram, scan temporary and descriptors (the marks themselves and their header are state: they stay)
     for (void *p : {(void *)d.dirty_lists, (void *)d.dirty_hist, d.dirty_tmp, (void *)d.dirty_desc}) dev_release(d, p);
     d.dirty_lists = d.dirty_hist = nullptr;
@@ -2180,6 +2183,137 @@ int nin_gls_plan_flops(nin_grid *g, double alg[22], double ref[22], int64_t comp
             alg[k] += dense_flops(ne, n_if, n_nb);             // small-node kernel, block kernel on one wavefront, global scratch
         }
     }
+    return NIN_OK;
+}
+
+// ---- the GLS adjoint: dL/dK from dL/d(stored weights) (kernels_gls_adjoint.hip) ---------------------------------------
+static void release_adjoint_state(DeviceGrid &d) {
+    for (auto &b : d.adj_bin) { dev_release(d, b.nodes); b = DeviceGrid::AdjBin{}; }
+    dev_release(d, d.adj_contrib);
+    dev_release(d, d.adj_scratch);
+    d.adj_contrib = d.adj_scratch = nullptr;
+    d.adj_scratch_stride = 0;
+    d.adj_scratch_slots = 0;
+    d.adj_ready = false;
+}
+
+// The bins, the contribution buffer and the scratch slots, on first use.  Synchronises `stream` (one device-to-host copy of 8 bytes a node).
+static int ensure_adjoint_state(DeviceGrid &d, hipStream_t stream) {
+    if (d.adj_ready) return NIN_OK;
+    const int32_t P = d.v.n_points;
+    const bool force_global = getenv("NIN_GLS_ADJ_FORCE_GLOBAL") != nullptr;   // testing switch: every system in global scratch
+    std::vector<int64_t> bytes((size_t)std::max(P, 1));
+    {
+        int64_t *dev_bytes = nullptr;
+        HIP_TRY(hipMalloc((void **)&dev_bytes, bytes.size() * sizeof(int64_t)));
+        hipError_t e = launch_adjoint_bytes(d.v, dev_bytes, stream) ? hipErrorLaunchFailure : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e == hipSuccess && P > 0) e = hipMemcpy(bytes.data(), dev_bytes, (size_t)P * sizeof(int64_t), hipMemcpyDeviceToHost);
+        (void)hipFree(dev_bytes);
+        if (e != hipSuccess) return fail(NIN_EHIP, "adjoint bins: %s", hipGetErrorString(e));
+    }
+    std::vector<int32_t> lists[kAdjBins];
+    int64_t mx[kAdjBins] = {};
+    for (int32_t p = 0; p < P; ++p) {
+        const int b = adj_node_bin(bytes[p], force_global);
+        lists[b].push_back(p);
+        mx[b] = std::max(mx[b], bytes[p]);
+    }
+    int rc = NIN_OK;
+    for (int b = 0; b < kAdjBins && !rc; ++b) {
+        DeviceGrid::AdjBin &bin = d.adj_bin[b];
+        bin.count = (int32_t)lists[b].size();
+        bin.bytes = mx[b];
+        if (bin.count == 0) continue;
+        rc = dev_alloc(d, &bin.nodes, lists[b].size());
+        if (!rc && hipMemcpy(bin.nodes, lists[b].data(), lists[b].size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(NIN_EHIP, "adjoint bins: upload failed");
+    }
+    if (!rc) rc = dev_alloc(d, &d.adj_contrib, (size_t)std::max<int64_t>(d.nnz_e, 1) * 10);
+    if (!rc && d.adj_bin[kAdjBins - 1].count > 0) {
+        d.adj_scratch_slots = std::min<int32_t>(d.adj_bin[kAdjBins - 1].count, 256);
+        d.adj_scratch_stride = mx[kAdjBins - 1] / 8;
+        rc = dev_alloc(d, &d.adj_scratch, (size_t)d.adj_scratch_slots * (size_t)d.adj_scratch_stride);
+    }
+    if (rc) { release_adjoint_state(d); return rc; }
+    d.adj_ready = true;
+    return NIN_OK;
+}
+
+int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
+                                    double *dev_grad_perm, double *dev_grad_diff_mag, void *stream_) {
+    if (!g || !dev_grad_csr || !dev_grad_perm) return fail(NIN_EINVAL, "NULL argument");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the kernels are HIP only");
+    if (!d.fields_set) return fail(NIN_ESTATE, "nin_fields_set has not been called");
+    if (!d.have_perm) return fail(NIN_ESTATE, "GLS needs permeability and diff_mag");
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = ensure_adjoint_state(d, stream);
+    if (!rc) rc = ensure_transpose_index(d, stream);
+    if (rc) return rc;
+    const char *only_env = getenv("NIN_GLS_ADJ_ONLY");   // per-bin timing (tools/time_adjoint.py): launch only that bin; read at every call
+    const int only = only_env ? atoi(only_env) : -1;
+    for (int b = 0; b < kAdjBins && !rc; ++b) {
+        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
+        if (only >= 0 && b != only) continue;
+        rc = launch_gls_adjoint(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, dev_grad_csr, dev_grad_neumann_ws, d.adj_contrib,
+                                d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots, stream);
+    }
+    if (!rc) rc = launch_adjoint_gather(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.adj_contrib, dev_grad_perm, dev_grad_diff_mag, stream);
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_sddmm_device(nin_grid *g, const double *dev_u_cells, const double *dev_node_values, int32_t n_fields, double *dev_grad_csr,
+                     void *stream_) {
+    if (!g || !dev_u_cells || !dev_node_values || !dev_grad_csr) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the kernels are HIP only");
+    HIP_TRY(hipSetDevice(d.device));
+    const int rc = launch_sddmm(d.v, dev_u_cells, dev_node_values, n_fields, dev_grad_csr, static_cast<hipStream_t>(stream_));
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_gls_permeability_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields,
+                                       double *grad_permeability) {
+    if (!g || !node_values || !cell_values || !grad_permeability) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device: the kernels are HIP only");
+    if (!d.fields_set) return fail(NIN_ESTATE, "nin_fields_set has not been called");
+    if (!d.have_perm) return fail(NIN_ESTATE, "GLS needs permeability and diff_mag");
+    HIP_TRY(hipSetDevice(d.device));
+    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8;
+    double *dv = nullptr, *du = nullptr, *dg = nullptr, *dk = nullptr;
+    auto cleanup = [&]() { (void)hipFree(dv); (void)hipFree(du); (void)hipFree(dg); (void)hipFree(dk); };
+#define TRY_A(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(NIN_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); } } while (0)
+    TRY_A(hipMalloc((void **)&dv, pb * n_fields));
+    TRY_A(hipMalloc((void **)&du, eb * n_fields));
+    TRY_A(hipMalloc((void **)&dg, (size_t)std::max<int64_t>(d.nnz_e, 1) * 8));
+    TRY_A(hipMalloc((void **)&dk, std::max<size_t>(eb, 8) * 9));
+    TRY_A(hipMemcpy(dv, node_values, pb * n_fields, hipMemcpyHostToDevice));
+    TRY_A(hipMemcpy(du, cell_values, eb * n_fields, hipMemcpyHostToDevice));
+    // W as apply() uses it (`+ neumann_ws[row]` included): add_neumann = 1, nothing flows through neumann_ws itself
+    int rc = nin_sddmm_device(g, du, dv, n_fields, dg, nullptr);
+    if (!rc) rc = nin_gls_weights_backward_device(g, 1, dg, nullptr, dk, nullptr, nullptr);
+    if (rc) { cleanup(); return rc; }
+    TRY_A(hipMemcpy(grad_permeability, dk, eb * 9, hipMemcpyDeviceToHost));
+#undef TRY_A
+    cleanup();
+    return NIN_OK;
+}
+
+int nin_gls_adjoint_plan(nin_grid *g, int64_t counts[4]) {
+    if (!g || !counts) return fail(NIN_EINVAL, "NULL argument");
+    DeviceGrid &d = g->d;
+    if (d.device < 0 || d.prebuilt) return fail(NIN_ENODEVICE, "grid is not on a device (call nin_grid_to_device first)");
+    HIP_TRY(hipSetDevice(d.device));
+    const int rc = ensure_adjoint_state(d, nullptr);
+    if (rc) return rc;
+    for (int b = 0; b < kAdjBins; ++b) counts[b] = d.adj_bin[b].count;
     return NIN_OK;
 }
 

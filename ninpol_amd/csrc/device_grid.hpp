@@ -100,6 +100,19 @@ struct DeviceGrid {
     // device by the first transpose call, released with the scratch.  tr_cell_ptr [E+1]; tr_cell_pos [nnz_e] = the position in esup /
     // csr_data of the pair (p, e); tr_cell_node [nnz_e] = p, ascending within a cell
     int32_t *tr_cell_ptr = nullptr, *tr_cell_pos = nullptr, *tr_cell_node = nullptr;
+    // the GLS adjoint (nin_gls_weights_backward_device, kernels_gls_adjoint.hip): the node list of every bin (gls_adjoint.hpp) with the
+    // largest slot among its nodes, the contribution buffer [nnz_e][10] (80 bytes per entry of esup: 6.4 GB at 216^3 hexahedra) and the
+    // global-scratch bin's slots; built by the first call, kept until nin_grid_release_scratch.  The bins depend on the connectivity
+    // alone.  The kernels take their nodes by a static stride: no work counter, and no line of gls_queue
+    struct AdjBin {
+        int32_t count = 0;
+        int32_t *nodes = nullptr;
+        int64_t bytes = 0;
+    } adj_bin[4];
+    bool adj_ready = false;
+    double *adj_contrib = nullptr, *adj_scratch = nullptr;
+    int64_t adj_scratch_stride = 0;   // doubles per slot
+    int32_t adj_scratch_slots = 0;
     // what a geometry refresh (nin_grid_update_points*, grid_update.hip) reads next to the coordinates and the one array it writes that
     // no weight kernel reads: inpoel [E][8], etype [E], inpofa [F][4], face areas [F].  Put here by the first update -- handed over by the
     // device builder's mirror, or uploaded from the host arrays -- and given back with the scratch (0.32 + 0.01 + 0.48 + 0.24 GB at 10 M

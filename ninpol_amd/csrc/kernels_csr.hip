@@ -251,6 +251,21 @@ __global__ __launch_bounds__(256) void nin_apply_list_kernel(GridView g, const d
     }
 }
 
+// the sampled product: one lane per node, entry by entry of its row, the fields summed in ascending order
+__global__ __launch_bounds__(256) void nin_sddmm_kernel(GridView g, const double *__restrict__ u, const double *__restrict__ v, int32_t k,
+                                                        double *__restrict__ grad) {
+    const size_t E = (size_t)g.n_elems, P = (size_t)g.n_points;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < g.n_points; p += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t b = g.esup_ptr[p], e = g.esup_ptr[p + 1];
+        for (int32_t q = b; q < e; ++q) {
+            const size_t c = (size_t)g.esup[q];
+            double acc = 0.0;
+            for (int32_t f = 0; f < k; ++f) acc += v[(size_t)f * P + p] * u[(size_t)f * E + c];
+            grad[q] = acc;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void nin_pad_centroids_kernel(const double *__restrict__ src, int64_t n, double *__restrict__ dst) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
         dst[4 * e + 0] = src[3 * e + 0]; dst[4 * e + 1] = src[3 * e + 1]; dst[4 * e + 2] = src[3 * e + 2]; dst[4 * e + 3] = 0.0;
@@ -285,6 +300,12 @@ int launch_compact(const GridView &g, const double *data, const int32_t *new_ptr
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream) {
     if (n_elems <= 0) return 0;
     hipLaunchKernelGGL(nin_pad_centroids_kernel, dim3(grid_for(n_elems)), dim3(256), 0, stream, src, n_elems, dst);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_sddmm(const GridView &g, const double *u, const double *v, int32_t k, double *grad, hipStream_t stream) {
+    if (g.n_points <= 0) return 0;
+    hipLaunchKernelGGL(nin_sddmm_kernel, dim3(grid_for(g.n_points)), dim3(256), 0, stream, g, u, v, k, grad);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

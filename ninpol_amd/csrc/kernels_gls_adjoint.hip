@@ -1,0 +1,438 @@
+// kernels_gls_adjoint.hip -- the GLS weights differentiated with respect to the permeability, gfx950.
+//
+// Notation of kernels_gls.hip's header: M is the node's m x n system, n = 3 n_e + 1, A its first n - 1 columns, c its last (1 on the
+// n_e cell rows).  Forward:  y = argmin |c - A y|,  r = c - A y,  rho = r.r,  w_i = r_i / rho on the cell rows; the stored entry is
+// d_i = w_i + nws, nws = w_{ne-1} on a Neumann node (when add_neumann), else 0.  Backward, given ghat_i = dL/dd_i:
+//   g     = ghat on the cell rows, 0 elsewhere; on a Neumann node g_{ne-1} += sum_j ghat_j (add_neumann) + dL/dneumann_ws[p] (if given)
+//   rbar  = g / rho - 2 (g.r) r / rho^2
+//   s     = argmin |rbar - A s|,  q = rbar - A s          (a second least-squares solve with the SAME factorisation)
+//   Abar  = -q y^T - r s^T                                 (only the entries of the K.N and tau.T2 rows are ever formed)
+// K enters A through the K.N row of an internal face (-(K_a N) on cell a's columns, +(K_b N) on cell b's), through the -(K_0 N) row of
+// a Neumann boundary face, and through eta = max(0, diff_mag_a, diff_mag_b) in tau = |T2|^(-eta) of the tau.T2 row.
+//
+// nin_gls_adjoint_kernel: one node per WORKGROUP of TW wavefronts, the dense formulation of kernels_gls.hip -- rows across the lanes
+// (row r in lane r % 64), column-major, Householder reflectors kept in place (v_k below the diagonal, R on and above it: the two
+// triangular solves need R, which the forward kernel never reads again).  Every wavefront forms reflector k from the pivot column,
+// wavefront w applies it to every TW-th group of four trailing columns, one barrier per reflector; the tail (two back substitutions,
+// three applications of Q) is wavefront 0's.  The system lives in LDS (LDS = true: the classes of 1, 2 and 4 wavefronts) or in a
+// global-memory scratch slot per workgroup (the systems that do not fit one CU's LDS), as nin_gls_team_kernel keeps it.  The assembly
+// is the forward's, expression for expression (gls_device_math.hpp's face_tau; K . N row by row).
+//
+// Contributions: lane i of the workgroup owns cell i of the node and walks the node's faces in fsup order; the ten values of the pair
+// (node, cell) -- Kbar[9] and etabar -- are summed in that fixed order and written to contrib[esup position][10].  nin_adjoint_gather_kernel
+// then sums, for every cell, the slots of its nodes in ascending node id through the cell-major index of the transpose (DeviceGrid::tr_*).
+// No atomics anywhere: two calls agree bit for bit.
+#include <hip/hip_runtime.h>
+
+#include "device_grid.hpp"
+#include "gls_adjoint.hpp"
+#include "gls_device_math.hpp"
+#include "launch.hpp"
+
+namespace nin {
+
+namespace {
+
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+// Sum over the 64 lanes, result in every lane.  All 64 lanes must be active.
+__device__ __forceinline__ double wave_sum(double v) {
+    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
+    v += dpp_mov<0x141>(v);  // row_half_mirror
+    v += dpp_mov<0x140>(v);  // row_mirror  -> every lane holds its 16-lane row sum
+    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+
+// Orders this wave's LDS / scratch traffic: a lane may read what another lane of the wave wrote.
+template <bool LDS>
+__device__ __forceinline__ void wave_sync() {
+    if (LDS) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+
+__device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+constexpr int JB = 4;  // columns updated together (independent reductions in flight)
+
+// z <- H_k z for the reflector in column k (v_k = 1, v_i = A[i, k] below it; tk = 0: the identity).  A lane touches only its own rows
+// of z (i % 64 == lane): no ordering is needed between successive reflectors.
+__device__ __forceinline__ void reflect(const double *A, int ld, int m, int k, double tk, double *z, int lane) {
+    if (tk == 0.0) return;   // uniform
+    const double *col = A + (size_t)k * ld;
+    double s = 0.0;
+    for (int i = k + lane; i < m; i += 64) s += (i == k ? 1.0 : col[i]) * z[i];
+    s = wave_sum(s) * tk;
+    for (int i = k + lane; i < m; i += 64) z[i] -= s * (i == k ? 1.0 : col[i]);
+}
+
+// x <- R^-1 x for the upper triangle in A's first nc columns, in place, by columns (one wavefront)
+template <bool LDS>
+__device__ __forceinline__ void back_substitute(const double *A, int ld, int nc, double *x, int lane) {
+    for (int k = nc - 1; k >= 0; --k) {
+        const double *col = A + (size_t)k * ld;
+        const double xk = x[k] / col[k];   // every lane reads the same two words
+        wave_sync<LDS>();                  // ... before the owner of x[k] replaces it
+        for (int i = lane; i <= k; i += 64) x[i] = i == k ? xk : x[i] - xk * col[i];
+        wave_sync<LDS>();
+    }
+}
+
+template <int TW, bool LDS>
+__global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, const int32_t *__restrict__ nodes, int32_t count, int add_neumann,
+                                                                 const double *__restrict__ grad_csr, const double *__restrict__ grad_nws,
+                                                                 double *__restrict__ contrib, double *scratch, long long scratch_stride) {
+    extern __shared__ double smem[];
+    const int tid = threadIdx.x, nthr = 64 * TW;
+    const int lane = tid & 63;
+    const int wave = ufirst(tid >> 6);
+    double *const base = LDS ? smem : scratch + (size_t)blockIdx.x * scratch_stride;
+
+    for (int32_t idx = blockIdx.x; idx < count; idx += gridDim.x) {
+        const int32_t p = ufirst(nodes[idx]);
+        const int32_t eb = ufirst(g.esup_ptr[p]), ne = ufirst(g.esup_ptr[p + 1]) - eb;
+        const int32_t fb = ufirst(g.fsup_ptr[p]), nf = ufirst(g.fsup_ptr[p + 1]) - fb;
+        const int fl = ufirst((int)g.flags[p]);
+        const bool is_neu = (fl & 2) != 0;
+
+        int n_if = 0;   // internal faces of the node; every wave counts them itself
+        for (int f0 = 0; f0 < nf; f0 += 64) {
+            const int fi = f0 + lane;
+            const bool internal = fi < nf && g.face_cells[2 * (size_t)g.fsup[fb + fi] + 1] >= 0;
+            n_if += __popcll(__ballot(internal));
+        }
+        const int n_bf = nf - n_if;
+        const int n = 3 * ne + 1;                              // columns, the last one is c
+        const int m = ne + 3 * n_if + (is_neu ? n_bf : 0);     // rows actually populated
+        // the forward's zero rows (kernels_gls.hip): nothing depends on K there
+        if (((fl & 1) && !is_neu) || n_if == 0 || m < n - 1) {
+            for (int i = tid; i < 10 * ne; i += nthr) contrib[10 * (size_t)eb + i] = 0.0;
+            continue;
+        }
+        const int ld = m;
+        // the slot: A [ld * n] | tau [n] | y [n] | s [n] | r [m] | q [m] | cells [ne], frow [nf], fia [nf], fib [nf] (int32)
+        double *A = base;
+        double *tau = A + (size_t)ld * n;
+        double *y = tau + n, *sv = y + n, *rv = sv + n, *qv = rv + m;
+        int32_t *cells = reinterpret_cast<int32_t *>(qv + m);
+        int32_t *frow = cells + ne, *fia = frow + nf, *fib = fia + nf;
+
+        for (int i = tid; i < ne; i += nthr) cells[i] = g.esup[eb + i];
+        for (int i = tid; i < ld * n; i += nthr) A[i] = 0.0;
+        __syncthreads();
+        const double xv0 = g.coords[3 * (size_t)p + 0], xv1 = g.coords[3 * (size_t)p + 1], xv2 = g.coords[3 * (size_t)p + 2];
+        if (wave == 0) {   // assembly, as kernels_gls.hip: a lane per cell / face
+            for (int i = lane; i < ne; i += 64) {
+                const size_t c = (size_t)cells[i];
+                A[i + (size_t)(3 * i + 0) * ld] = g.centroids[3 * c + 0] - xv0;
+                A[i + (size_t)(3 * i + 1) * ld] = g.centroids[3 * c + 1] - xv1;
+                A[i + (size_t)(3 * i + 2) * ld] = g.centroids[3 * c + 2] - xv2;
+                A[i + (size_t)(n - 1) * ld] = 1.0;
+            }
+            int if_base = 0, bf_base = 0;
+            for (int f0 = 0; f0 < nf; f0 += 64) {
+                const int fi = f0 + lane;
+                const bool valid = fi < nf;
+                const size_t f = valid ? (size_t)g.fsup[fb + fi] : 0;
+                const int ca = valid ? g.face_cells[2 * f] : 0, cb = valid ? g.face_cells[2 * f + 1] : -1;
+                const bool internal = valid && cb >= 0;
+                const bool bface = valid && cb < 0;
+                const unsigned long long mi = __ballot(internal), mb = __ballot(bface);
+                const unsigned long long below = (1ull << lane) - 1ull;
+                int Ia = 0, Ib = 0;
+                if (valid)
+                    for (int q = 0; q < ne; ++q) {
+                        const int cq = cells[q];
+                        Ia = cq == ca ? q : Ia;
+                        Ib = cq == cb ? q : Ib;
+                    }
+                if (internal) {
+                    const int row = ne + 3 * (if_base + __popcll(mi & below));
+                    const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
+                    const double T0 = xv0 - g.face_center[3 * f + 0], T1 = xv1 - g.face_center[3 * f + 1],
+                                 T2 = xv2 - g.face_center[3 * f + 2];
+                    const double U0 = N1 * T2 - N2 * T1, U1 = N2 * T0 - N0 * T2, U2 = N0 * T1 - N1 * T0;
+                    const double da = g.diff_mag[ca], db = g.diff_mag[cb];
+                    double eta = 0.0;
+                    eta = da > eta ? da : eta;
+                    eta = db > eta ? db : eta;
+                    const double tj = glsmath::face_tau(sqrt(U0 * U0 + U1 * U1 + U2 * U2), eta);
+                    const double *Ka = g.perm + 9 * (size_t)ca, *Kb = g.perm + 9 * (size_t)cb;
+                    double *ra = A + row + (size_t)(3 * Ia) * ld, *rb = A + row + (size_t)(3 * Ib) * ld;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const double nLa = Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2;  // row c of K . N
+                        const double nLb = Kb[c * 3 + 0] * N0 + Kb[c * 3 + 1] * N1 + Kb[c * 3 + 2] * N2;
+                        const double t1 = c == 0 ? T0 : (c == 1 ? T1 : T2);
+                        const double u = tj * (c == 0 ? U0 : (c == 1 ? U1 : U2));
+                        ra[(size_t)c * ld + 0] = -nLa; rb[(size_t)c * ld + 0] = nLb;
+                        ra[(size_t)c * ld + 1] = -t1;  rb[(size_t)c * ld + 1] = t1;
+                        ra[(size_t)c * ld + 2] = -u;   rb[(size_t)c * ld + 2] = u;
+                    }
+                    frow[fi] = row; fia[fi] = Ia; fib[fi] = Ib;
+                } else if (bface && is_neu) {
+                    const int row = ne + 3 * n_if + bf_base + __popcll(mb & below);
+                    const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
+                    const double *Ka = g.perm + 9 * (size_t)ca;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        A[row + (size_t)(3 * Ia + c) * ld] = -(Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2);
+                    frow[fi] = row; fia[fi] = Ia; fib[fi] = -1;
+                } else if (valid) {
+                    frow[fi] = -1; fia[fi] = Ia; fib[fi] = -1;
+                }
+                if_base += __popcll(mi);
+                bf_base += __popcll(mb);
+            }
+        }
+        __syncthreads();
+
+        // ---- Householder QR of the first n-1 columns, applied to the last one as it goes (kernels_gls.hip); R stays: beta on the
+        //      diagonal, row k of the trailing columns above it ----------------------------------------------------------------
+        bool singular = false;
+        for (int k = 0; k < n - 1; ++k) {
+            const double *ck = A + (size_t)k * ld;
+            double ss = 0.0;
+            for (int r = k + 1 + lane; r < m; r += 64) ss += ck[r] * ck[r];
+            ss = wave_sum(ss);
+            const double alpha = ck[k];
+            double tk = 0.0, sc = 0.0, beta = alpha;
+            if (ss != 0.0) {  // dlarfg: beta = -sign(alpha) |(alpha, x)|, tau = (beta-alpha)/beta, v = x/(alpha-beta)
+                beta = -copysign(sqrt(alpha * alpha + ss), alpha);
+                tk = (beta - alpha) / beta;
+                sc = 1.0 / (alpha - beta);
+            } else {
+                singular = singular || (alpha == 0.0);
+            }
+            if (tk != 0.0) {
+                for (int j0 = k + 1 + JB * wave; j0 < n; j0 += JB * TW) {
+                    double s[JB];
+                    double *cj[JB];
+#pragma unroll
+                    for (int jj = 0; jj < JB; ++jj) {
+                        s[jj] = 0.0;
+                        cj[jj] = A + (size_t)(j0 + jj < n ? j0 + jj : j0) * ld;   // (a column past the end: read j0 again, never written)
+                    }
+                    for (int r = k + lane; r < m; r += 64) {
+                        const double v = r == k ? 1.0 : ck[r] * sc;
+#pragma unroll
+                        for (int jj = 0; jj < JB; ++jj) s[jj] += v * cj[jj][r];
+                    }
+#pragma unroll
+                    for (int jj = 0; jj < JB; ++jj) s[jj] = wave_sum(s[jj]) * tk;
+                    for (int r = k + lane; r < m; r += 64) {
+                        const double v = r == k ? 1.0 : ck[r] * sc;
+#pragma unroll
+                        for (int jj = 0; jj < JB; ++jj)
+                            if (j0 + jj < n) cj[jj][r] -= s[jj] * v;
+                    }
+                }
+            }
+            __syncthreads();   // every wave has read the pivot column: v_k and beta may replace it (nobody reads column k again before the tail)
+            if (wave == 0) {
+                double *wk = A + (size_t)k * ld;
+                if (tk != 0.0)
+                    for (int r = k + 1 + lane; r < m; r += 64) wk[r] *= sc;
+                if (lane == 0) { tau[k] = tk; wk[k] = beta; }
+            }
+        }
+        __syncthreads();
+
+        if (wave == 0) {
+            const double *ct = A + (size_t)(n - 1) * ld;   // Q^T c
+            // rho = |(Q^T c)(n-1:m)|^2;  r = Q [0; (Q^T c)(n-1:m)];  y = R^-1 (Q^T c)(0:n-1)
+            double rho = 0.0;
+            for (int i = lane; i < m; i += 64) {
+                const double z = i >= n - 1 ? ct[i] : 0.0;
+                rv[i] = z;
+                rho += z * z;
+                if (i < n - 1) y[i] = ct[i];
+            }
+            rho = wave_sum(rho);
+            for (int k = n - 2; k >= 0; --k) reflect(A, ld, m, k, tau[k], rv, lane);
+            wave_sync<LDS>();
+            back_substitute<LDS>(A, ld, n - 1, y, lane);
+            // the forward's last zero-row rule: a singular system, or a result that is not finite
+            bool ok = !singular && rho > 0.0;
+            {
+                bool fin = true;
+                for (int i = lane; i < ne; i += 64) fin = fin && isfinite(rv[i] / rho);
+                ok = ok && __ballot(!fin) == 0ull;
+            }
+            // g and rbar (into q)
+            double gsum = 0.0;
+            for (int i = lane; i < ne; i += 64) gsum += grad_csr[eb + i];
+            gsum = wave_sum(gsum);
+            const double extra = is_neu ? (add_neumann ? gsum : 0.0) + (grad_nws ? grad_nws[p] : 0.0) : 0.0;
+            double gr = 0.0;
+            for (int i = lane; i < ne; i += 64) gr += (grad_csr[eb + i] + (i == ne - 1 ? extra : 0.0)) * rv[i];
+            gr = wave_sum(gr);
+            const double irho = 1.0 / rho, c2 = 2.0 * gr * irho * irho;
+            for (int i = lane; i < m; i += 64) {
+                const double gi = i < ne ? grad_csr[eb + i] + (i == ne - 1 ? extra : 0.0) : 0.0;
+                qv[i] = gi * irho - c2 * rv[i];
+            }
+            // s = R^-1 (Q^T rbar)(0:n-1);  q = Q [0; (Q^T rbar)(n-1:m)]
+            for (int k = 0; k < n - 1; ++k) reflect(A, ld, m, k, tau[k], qv, lane);
+            for (int i = lane; i < n - 1; i += 64) { sv[i] = qv[i]; qv[i] = 0.0; }
+            for (int k = n - 2; k >= 0; --k) reflect(A, ld, m, k, tau[k], qv, lane);
+            wave_sync<LDS>();
+            back_substitute<LDS>(A, ld, n - 1, sv, lane);
+            if (lane == 0) tau[0] = ok ? 1.0 : 0.0;   // (tau is done with: its first word carries the verdict to the other waves)
+        }
+        __syncthreads();
+
+        // ---- contributions: thread i = cell i of the node, the node's faces in fsup order ------------------------------------
+        const bool ok = tau[0] != 0.0;
+        for (int i = tid; i < ne; i += nthr) {
+            double kb[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, etab = 0.0;
+            for (int fi = 0; ok && fi < nf; ++fi) {
+                const int t = frow[fi], Ia = fia[fi], Ib = fib[fi];
+                if (t < 0 || (Ia != i && Ib != i)) continue;
+                const size_t f = (size_t)g.fsup[fb + fi];
+                const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
+                // Abar(t, 3 i + c) = -q_t y_(3i+c) - r_t s_(3i+c); on cell a's columns the row holds -(K_a N), on b's +(K_b N)
+                const double sign = Ia == i ? -1.0 : 1.0;
+                const double qt = qv[t], rt = rv[t];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double ab = sign * (-(qt * y[3 * i + c]) - rt * sv[3 * i + c]);
+                    kb[3 * c + 0] += ab * N0;
+                    kb[3 * c + 1] += ab * N1;
+                    kb[3 * c + 2] += ab * N2;
+                }
+                if (Ib < 0) continue;   // a Neumann boundary face: no tau row
+                const double da = g.diff_mag[cells[Ia]], db = g.diff_mag[cells[Ib]];
+                const int pick = db > da ? Ib : (da > 0.0 ? Ia : -1);   // the cell the forward's max() takes eta from
+                if (pick != i) continue;
+                const double T0 = xv0 - g.face_center[3 * f + 0], T1 = xv1 - g.face_center[3 * f + 1], T2 = xv2 - g.face_center[3 * f + 2];
+                const double U0 = N1 * T2 - N2 * T1, U1 = N2 * T0 - N0 * T2, U2 = N0 * T1 - N1 * T0;
+                const double un = sqrt(U0 * U0 + U1 * U1 + U2 * U2);
+                const double eta = db > da ? db : da;
+                const double tj = glsmath::face_tau(un, eta);
+                const double q2 = qv[t + 2], r2 = rv[t + 2];
+                double dot = 0.0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double abb = -(q2 * y[3 * Ib + c]) - r2 * sv[3 * Ib + c], aba = -(q2 * y[3 * Ia + c]) - r2 * sv[3 * Ia + c];
+                    dot += (abb - aba) * (c == 0 ? U0 : (c == 1 ? U1 : U2));
+                }
+                etab += dot * (-log(un) * tj);   // d tau / d eta = -ln|T2| tau
+            }
+            double *o = contrib + 10 * (size_t)(eb + i);
+#pragma unroll
+            for (int c = 0; c < 9; ++c) o[c] = kb[c];
+            o[9] = etab;
+        }
+        __syncthreads();   // (the slot is the next node's)
+    }
+}
+
+// thread p: the bytes of node p's slot (gls_adjoint.hpp), from the node's shape alone -- the Neumann flag may change, the bin may not
+__global__ __launch_bounds__(256) void nin_adjoint_bytes_kernel(GridView g, int64_t *__restrict__ bytes) {
+    const int32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= g.n_points) return;
+    const int32_t ne = g.esup_ptr[p + 1] - g.esup_ptr[p];
+    const int32_t fb = g.fsup_ptr[p], nf = g.fsup_ptr[p + 1] - fb;
+    int nbf = 0;
+    for (int i = 0; i < nf; ++i) nbf += g.face_cells[2 * (size_t)g.fsup[fb + i] + 1] < 0;
+    bytes[p] = adj_node_bytes(ne, nf, nbf);
+}
+
+// thread e: cell e sums the slots of its nodes, ascending node id (the order of cell_pos within a cell)
+__global__ __launch_bounds__(256) void nin_adjoint_gather_kernel(int32_t n_elems, const int32_t *__restrict__ cell_ptr, const int32_t *__restrict__ cell_pos,
+                                                                const double *__restrict__ contrib, const double *__restrict__ perm,
+                                                                double *__restrict__ grad_perm, double *__restrict__ grad_dm) {
+    const int32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_elems) return;
+    double acc[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int32_t j = cell_ptr[e]; j < cell_ptr[e + 1]; ++j) {
+        const double *c = contrib + 10 * (size_t)cell_pos[j];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) acc[k] += c[k];
+    }
+    if (grad_dm) {
+        grad_dm[e] = acc[9];
+    } else {   // diff_mag = (1 - 3 / tr K)^2 (diff_mag.hpp): d diff_mag / d K_dd = 2 (1 - 3 / tr) 3 / tr^2 on the three diagonal entries
+        const double *K = perm + 9 * (size_t)e;
+        const double tr = (K[0] + K[4]) + K[8];
+        const double t = acc[9] * (2.0 * (1.0 - 3.0 / tr) * 3.0 / (tr * tr));
+        acc[0] += t; acc[4] += t; acc[8] += t;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) grad_perm[9 * (size_t)e + k] = acc[k];
+}
+
+template <int TW, bool LDS>
+int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const double *grad_csr,
+               const double *grad_nws, double *contrib, double *scratch, int64_t stride, int32_t slots, hipStream_t stream) {
+    auto kern = nin_gls_adjoint_kernel<TW, LDS>;
+    int64_t blocks;
+    size_t lds = 0;
+    if (LDS) {
+        lds = (size_t)bytes;
+        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS>>(lds)) return -3;
+        int64_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : (int64_t)lds);
+        if (per_cu > 32 / TW) per_cu = 32 / TW;
+        if (per_cu < 1) per_cu = 1;
+        blocks = 256 * per_cu * 2;
+    } else {
+        blocks = slots;   // one scratch slot per workgroup
+    }
+    if (blocks > count) blocks = count;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * TW), lds, stream, g, nodes, count, add_neumann, grad_csr, grad_nws, contrib,
+                       scratch, (long long)stride);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace
+
+int launch_adjoint_bytes(const GridView &g, int64_t *bytes, hipStream_t stream) {
+    if (g.n_points <= 0) return 0;
+    hipLaunchKernelGGL(nin_adjoint_bytes_kernel, dim3((unsigned)((g.n_points + 255) / 256)), dim3(256), 0, stream, g, bytes);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const double *grad_csr,
+                       const double *grad_nws, double *contrib, double *scratch, int64_t scratch_stride, int32_t scratch_slots,
+                       hipStream_t stream) {
+    if (count <= 0) return 0;
+    switch (bin) {
+        case 0: return launch_bin<1, true>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, nullptr, 0, 0, stream);
+        case 1: return launch_bin<2, true>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, nullptr, 0, 0, stream);
+        case 2: return launch_bin<4, true>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, nullptr, 0, 0, stream);
+        case 3:
+            if (!scratch || scratch_slots < 1 || scratch_stride * 8 < bytes) return -1;
+            return launch_bin<8, false>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, scratch, scratch_stride, scratch_slots, stream);
+    }
+    return -1;
+}
+
+int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,
+                          double *grad_diff_mag, hipStream_t stream) {
+    if (g.n_elems <= 0) return 0;
+    hipLaunchKernelGGL(nin_adjoint_gather_kernel, dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems, cell_ptr, cell_pos,
+                       contrib, g.perm, grad_perm, grad_diff_mag);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace nin

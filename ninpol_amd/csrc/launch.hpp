@@ -111,6 +111,24 @@ int launch_iota(int32_t *dst, int32_t n, hipStream_t stream);
 int launch_transpose_index_fill(const GridView &g, const int32_t *sorted_cells, int32_t nnz, int32_t *cell_ptr, const int32_t *cell_pos,
                                 int32_t *cell_node, hipStream_t stream);
 
+// the sampled product (kernels_csr.hip): grad[pos] = sum_f v[f][p] u[f][esup[pos]] for every entry pos of every row p -- the gradient of
+// <v, W u> with respect to the stored weights; u [k][n_elems], v [k][n_points], grad [nnz_esup]
+int launch_sddmm(const GridView &g, const double *u, const double *v, int32_t k, double *grad, hipStream_t stream);
+
+// the GLS adjoint (kernels_gls_adjoint.hip, gls_adjoint.hpp), all DEVICE pointers.
+// launch_adjoint_bytes: bytes[p] = adj_node_bytes of node p.
+// launch_gls_adjoint: the nodes of one bin (`bytes`: the largest slot among them; bin 3: `scratch` holds scratch_slots slots of
+//   scratch_stride doubles); grad_csr [nnz_esup] = dL/d stored weights, grad_nws [n_points] = dL/d neumann_ws or null; writes the ten
+//   values (Kbar[9], etabar) of every (node, cell) pair of the listed nodes to contrib [nnz_esup][10].
+// launch_adjoint_gather: grad_perm [E][9] (and grad_diff_mag [E]; null: its term folded into the diagonal of grad_perm through the
+//   resident g.perm) = per cell the sum of its nodes' slots, ascending node id, through the transpose index (cell_ptr, cell_pos)
+int launch_adjoint_bytes(const GridView &g, int64_t *bytes, hipStream_t stream);
+int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const double *grad_csr,
+                       const double *grad_nws, double *contrib, double *scratch, int64_t scratch_stride, int32_t scratch_slots,
+                       hipStream_t stream);
+int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,
+                          double *grad_diff_mag, hipStream_t stream);
+
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream);
 // GLS launch plan (grid_device.hip): the class byte of every node (gls_plan.hpp: gls_class_byte of the kernel that takes it; use_group =

@@ -370,6 +370,15 @@ class Grid:
         at 10 M cells; the connectivity copies of load_point_coords(): ~1 GB more); the next call allocates them again."""
         _lib.check(_lib.load().nin_grid_release_scratch(self._h))
 
+    ADJOINT_BINS = ("lds1", "lds2", "lds4", "global")
+
+    def gls_adjoint_plan(self):
+        """Nodes per bin of the GLS adjoint kernel on the device copy (nin_gls_adjoint_plan): the LDS classes of one, two and four
+        wavefronts per node, then the systems kept in global-memory scratch.  Makes the bins if they are not there yet."""
+        counts = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.load().nin_gls_adjoint_plan(self._h, counts.ctypes.data_as(ctypes.c_void_p)))
+        return dict(zip(self.ADJOINT_BINS, counts.tolist()))
+
     PLAN_KERNELS = ("block1", "block2", "block4", "block8", "scratch", "hex8", "mfw_large", "mfw_small", "mfw_general", "small4", "small8",
                     "small12", "quad4", "mfx_6x10", "mfx_7x11", "mfx_8x13", "mfx_9x15", "mfx_10x16", "mfx_boundary", "mfg_tiles", "mfx_4x7", "mfx_7x12")
 

@@ -1039,6 +1039,39 @@ class Interpolator:
         _lib.check(_lib.load().nin_apply_transpose_fields_host(g._h, _lib.METHOD_ID[method], _ptr(v), k, _ptr(out)))
         return out
 
+    def permeability_gradient(self, variable, node_values, cell_values=None):
+        """The derivative of `<v, W u>` with respect to the permeability, for the GLS matrix W that `apply(variable, "gls")` uses (the
+        `+ neumann_ws[row]` included): `node_values` = v, one node array (n_points,) or k of them as (k, n_points); `cell_values` = u,
+        shaped alike with n_elems (default: the cell variable `variable` itself, for every v).  Returns (n_elems, 3, 3): the gradient
+        with respect to the resident permeability table, the chain through diff_mag = (1 - 3 / tr K)^2 folded in.  On the device, the
+        sibling of apply_transpose(): host-synchronous, numpy in and out; deterministic.  Nodes whose row is zero (Dirichlet nodes)
+        contribute nothing; the Neumann values and the coordinates are not differentiated."""
+        if not self.is_grid_initialized:
+            raise ValueError("Grid not initialized. Please load a mesh first.")
+        if variable not in self.variable_to_index["cells"]:
+            raise ValueError(f"Variable '{variable}' not found in cells data. "
+                             "Point -> Cell interpolation not supported yet.")
+        self._perm_rows()   # (ValueError without a permeability)
+        g = self.grid
+        v = np.ascontiguousarray(node_values, dtype=DTYPE_F)
+        if v.shape != (g.n_points,) and not (v.ndim == 2 and v.shape[0] >= 1 and v.shape[1] == g.n_points):
+            raise ValueError(f"node_values must have shape ({g.n_points},) or (k, {g.n_points}), not {v.shape}.")
+        k = 1 if v.ndim == 1 else v.shape[0]
+        if cell_values is None:
+            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
+            u = np.ascontiguousarray(np.broadcast_to(u, (k, g.n_elems)), dtype=DTYPE_F)
+        else:
+            u = np.ascontiguousarray(cell_values, dtype=DTYPE_F)
+            if u.shape != v.shape[:-1] + (g.n_elems,):
+                raise ValueError(f"cell_values must have shape {v.shape[:-1] + (g.n_elems,)} beside node_values of shape {v.shape}, "
+                                 f"not {u.shape}.")
+        if g.device < 0:
+            g.to_device(self.device)
+        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        out = np.empty((g.n_elems, 3, 3), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_permeability_gradient_host(g._h, _ptr(v), _ptr(u), k, _ptr(out)))
+        return out
+
     def release_scratch(self, pinned=True):
         """Give back what the object keeps between calls for speed: the grid's device scratch (weights, compacted
         triplets: ~2.3 GB of HBM at 10 M cells; the transpose index of apply_transpose(): 0.69 GB more) and, with pinned=True, the idle page-locked result buffers of the
@@ -1172,6 +1205,27 @@ class DevicePlan:
         asynchronous on `stream` (the first call on a grid builds the transpose index and synchronises)."""
         _lib.check(_lib.load().nin_spmv_transpose_device(self.grid._h, ctypes.c_void_p(weights_ptr), ctypes.c_void_p(values_ptr),
                                                          int(n_fields), ctypes.c_void_p(cells_ptr), ctypes.c_void_p(stream)))
+
+
+    def launch_sddmm(self, u_ptr, values_ptr, n_fields, grad_csr_ptr, stream=0):
+        """The sampled product (nin_sddmm_device): grad_csr[pos] = sum_f values[f][p] * u[f][esup[pos]] over the entries of every row p
+        -- the gradient of <values, W u> with respect to weights in esup position; u [n_fields][n_elems], values
+        [n_fields][n_points], grad_csr [nnz_esup]; asynchronous on `stream`."""
+        _lib.check(_lib.load().nin_sddmm_device(self.grid._h, ctypes.c_void_p(u_ptr), ctypes.c_void_p(values_ptr), int(n_fields),
+                                                ctypes.c_void_p(grad_csr_ptr), ctypes.c_void_p(stream)))
+
+    def launch_weights_backward(self, grad_csr_ptr, grad_perm_ptr, grad_diff_mag_ptr=0, grad_neumann_ws_ptr=0, stream=0, add_neumann=True):
+        """The GLS weights differentiated with respect to the permeability (nin_gls_weights_backward_device): grad_csr [nnz_esup] =
+        dL/d csr_data of a `launch(..., add_neumann)` (grad_neumann_ws [n_points] = dL/d neumann_ws, 0: none) -> grad_perm
+        [n_elems][9] = dL/dK at what is resident now.  With grad_diff_mag [n_elems] the table's diff_mag counts as an independent
+        input and gets its own gradient; with 0 its chain is folded into grad_perm.  Asynchronous on `stream` after the first call on
+        a grid (which makes the bins and buffers -- 80 bytes per entry of esup -- and synchronises).  Only GLS depends on K."""
+        if self.method != "gls":
+            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: launch_weights_backward is GLS only")
+        self.ensure_current()
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_weights_backward_device(self.grid._h, int(bool(add_neumann)), vp(grad_csr_ptr), vp(grad_neumann_ws_ptr),
+                                                               vp(grad_perm_ptr), vp(grad_diff_mag_ptr), ctypes.c_void_p(stream)))
 
 
 class HostMatrix:

@@ -1,5 +1,7 @@
 """torch autograd for the interpolation operator: `CellToNode(interp, variable, method)(u)` is `W . u` on the device, and its
-backward pass is `W^T . grad` (nin_spmv_device / nin_spmv_transpose_device), both on torch's current stream.
+backward pass is `W^T . grad` (nin_spmv_device / nin_spmv_transpose_device), both on torch's current stream.  `CellToNode(...)(u, K)`
+also makes the GLS weights a function of the permeability tensor K: its backward pass returns dL/dK through the sampled product
+(nin_sddmm_device) and the adjoint of the weight kernels (nin_gls_weights_backward_device).
 
 Not imported by `ninpol_amd/__init__.py`: importing the package loads nothing native and does not import torch.  This module
 imports torch, and opens its device, before the native library loads ("A process that also uses a PyTorch-ROCm
@@ -13,19 +15,84 @@ from .interpolator import DevicePlan  # noqa: E402  (after torch has the device)
 
 
 class _CellToNodeFn(torch.autograd.Function):
-    """u [k][n_elems] -> W u [k][n_points]; backward W^T g.  The weights travel with the graph: a later refresh() of the module
-    does not change the gradient of an output computed before it."""
+    """u [k][n_elems] -> W u [k][n_points]; backward W^T g for u and, when the weights themselves require a gradient (they are the
+    output of _GlsWeightsFn), the sampled product g u^T on W's pattern for them.  The weights travel with the graph: a later
+    refresh() of the module does not change the gradient of an output computed before it."""
 
     @staticmethod
     def forward(ctx, u, op, weights):
         ctx.op, ctx.weights = op, weights
+        ctx.u = u if ctx.needs_input_grad[2] else None
         return op._spmv(weights, u)
 
     @staticmethod
     def backward(ctx, grad):
-        if not ctx.needs_input_grad[0]:
+        gu = gw = None
+        if ctx.needs_input_grad[0]:
+            gu = ctx.op._spmv_transpose(ctx.weights, grad.contiguous())
+        if ctx.needs_input_grad[2]:
+            gw = ctx.op._sddmm(ctx.u, grad.contiguous())
+        return gu, None, gw
+
+
+class _GlsWeightsFn(torch.autograd.Function):
+    """K [n_elems][3][3] (or [n_elems][9]), scale [n_elems] or None -> the stored GLS weights [nnz_esup] and neumann_ws [n_points] of the
+    permeability scale * K, which becomes the grid's resident table (Interpolator.update_permeability).  Backward reads what is
+    resident -- geometry, flags, permeability -- so it refuses to run once any of them was updated after the forward pass: it would
+    differentiate at another point."""
+
+    @staticmethod
+    def forward(ctx, K, scale, op):
+        op.plan.interp.update_permeability(K.detach(), None if scale is None else scale.detach())
+        w, nws = op._launch_weights()
+        ctx.op, ctx.stamp = op, op._stamp()
+        ctx.save_for_backward(K, scale)
+        ctx.set_materialize_grads(False)
+        return w, nws
+
+    @staticmethod
+    def backward(ctx, gw, gnws):
+        K, scale = ctx.saved_tensors
+        op = ctx.op
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return None, None, None
-        return ctx.op._spmv_transpose(ctx.weights, grad.contiguous()), None, None
+        now = op._stamp()
+        if now != ctx.stamp:
+            names = ("field_updates", "geometry_updates", "flag_updates")
+            moved = ", ".join(f"{n} {a} -> {b}" for n, a, b in zip(names, ctx.stamp, now) if a != b)
+            raise RuntimeError("the grid's resident permeability, geometry or Neumann flags were updated after the forward pass "
+                               f"({moved}): the gradient with respect to K would be taken at another point.  Run backward() before "
+                               "the next update, or the forward pass again.")
+        E = op.n_elems
+        gperm = torch.empty((E, 9), dtype=torch.float64, device=op.device)
+        if gw is None:
+            gw = torch.zeros(op.plan.nnz, dtype=torch.float64, device=op.device)
+        gw = gw.contiguous()
+        gnws = None if gnws is None else gnws.contiguous()
+        op.plan.launch_weights_backward(gw.data_ptr(), gperm.data_ptr(), 0, 0 if gnws is None else gnws.data_ptr(), op._stream(),
+                                        add_neumann=True)
+        # perm = scale * K, entry by entry
+        gK = gscale = None
+        if ctx.needs_input_grad[0]:
+            gK = (gperm if scale is None else gperm * scale[:, None]).reshape(K.shape)
+        if scale is not None and ctx.needs_input_grad[1]:
+            gscale = (K.reshape(E, 9) * gperm).sum(dim=1)
+        return gK, gscale, None
+
+
+class _ConstantWeightsFn(torch.autograd.Function):
+    """IDW / LS: the weights do not depend on the permeability -- K and scale get zeros"""
+
+    @staticmethod
+    def forward(ctx, K, scale, weights):
+        ctx.save_for_backward(K, scale)
+        return weights.detach().clone()
+
+    @staticmethod
+    def backward(ctx, gw):
+        K, scale = ctx.saved_tensors
+        return (torch.zeros_like(K) if ctx.needs_input_grad[0] else None,
+                torch.zeros_like(scale) if scale is not None and ctx.needs_input_grad[1] else None, None)
 
 
 class CellToNode(torch.nn.Module):
@@ -38,8 +105,10 @@ class CellToNode(torch.nn.Module):
     `interp.update_points(...)` the module goes on applying the weights of the old geometry until `refresh()`; nothing is
     recomputed behind the caller's back.  A permeability that lives on the device reaches the module through
     `interp.update_permeability(K_dev)` followed by `recompute_weights()`: the weight kernels run again on torch's current stream
-    from whatever is resident -- geometry and permeability -- with no table re-read, no hash and no synchronisation.  Derivatives
-    with respect to the permeability, the Neumann values or the node coordinates are not provided."""
+    from whatever is resident -- geometry and permeability -- with no table re-read, no hash and no synchronisation.
+
+    The derivative with respect to the permeability comes through `forward(u, K, scale)` (GLS; see there) or `weights_of(K, scale)`.
+    Derivatives with respect to the Neumann values or the node coordinates are not provided."""
 
     def __init__(self, interp, variable, method):
         super().__init__()
@@ -54,12 +123,19 @@ class CellToNode(torch.nn.Module):
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _compute_weights(self):
+    def _launch_weights(self):
         w = torch.empty(self.plan.nnz, dtype=torch.float64, device=self.device)
         nws = torch.empty(self.n_points, dtype=torch.float64, device=self.device)
         self.plan.launch(w.data_ptr(), nws.data_ptr(), self._stream(), add_neumann=True)
+        return w, nws
+
+    def _compute_weights(self):
         # new tensors, not an in-place update: outputs computed before a refresh() keep the weights of their forward pass
-        self.weights, self.neumann_ws = w, nws
+        self.weights, self.neumann_ws = self._launch_weights()
+
+    def _stamp(self):
+        g = self.plan.grid
+        return (g.field_updates, g.geometry_updates, g.flag_updates)
 
     def refresh(self):
         """Upload the Interpolator's field tables as they are now and recompute the weights, from the grid's geometry as it is now
@@ -96,8 +172,41 @@ class CellToNode(torch.nn.Module):
         self.plan.launch_spmv_transpose(weights.data_ptr(), v.data_ptr(), k, out.data_ptr(), self._stream())
         return out
 
-    def forward(self, u):
-        """u: float64 (n_elems,) or (k, n_elems) on the plan's device -> node values (n_points,) or (k, n_points)."""
+    def _sddmm(self, u, v):
+        k = 1 if u.dim() == 1 else u.shape[0]
+        out = torch.empty(self.plan.nnz, dtype=torch.float64, device=self.device)
+        self.plan.launch_sddmm(u.data_ptr(), v.data_ptr(), k, out.data_ptr(), self._stream())
+        return out
+
+    def weights_of(self, K, scale=None):
+        """The stored weights [nnz_esup] (esup / CSR position, `+ neumann_ws[row]` included) and neumann_ws [n_points] as differentiable
+        functions of the permeability: K float64 (n_elems, 3, 3) or (n_elems, 9) on the plan's device, optionally times the per-cell
+        factor `scale` (n_elems,) -- the arguments, and the checks, of Interpolator.update_permeability with device tensors, which is
+        what runs first: scale * K becomes the grid's resident permeability (the module's own `weights` stay what they were).  Fresh
+        tensors on torch's current stream.  GLS: backward gives dL/dK = scale * dL/dperm and dL/dscale = sum(K * dL/dperm) through
+        DevicePlan.launch_weights_backward, which reads the resident geometry, flags and permeability -- so backward raises
+        RuntimeError if Grid.field_updates, geometry_updates or flag_updates moved after this call (another weights_of /
+        forward(u, K) included): run each backward before the next update.  IDW / LS: the module's weights, and zeros for K."""
+        if not isinstance(K, torch.Tensor):
+            raise TypeError(f"K must be a torch.Tensor on {self.device}, not {type(K).__name__}")
+        if K.device != self.device:
+            raise ValueError(f"K must be on {self.device}, not {K.device}")
+        if self.plan.method != "gls":
+            for t, name, shapes in ((K, "K", ((self.n_elems, 3, 3), (self.n_elems, 9))), (scale, "scale", ((self.n_elems,),))):
+                if t is None:
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                    raise TypeError(f"{name} must be a float64 torch.Tensor (no silent cast)")
+                if t.device != self.device or tuple(t.shape) not in shapes:
+                    raise ValueError(f"{name} must be on {self.device} with shape {' or '.join(map(str, shapes))}")
+            return _ConstantWeightsFn.apply(K, scale, self.weights), self.neumann_ws
+        return _GlsWeightsFn.apply(K, scale, self)
+
+    def forward(self, u, K=None, scale=None):
+        """u: float64 (n_elems,) or (k, n_elems) on the plan's device -> node values (n_points,) or (k, n_points).
+
+        With K (and optionally scale; see weights_of): the weights are first computed from the permeability scale * K, and the
+        result is differentiable in u, K and scale.  Without K nothing changes: the module's weights are applied."""
         if not isinstance(u, torch.Tensor):
             raise TypeError(f"u must be a torch.Tensor, not {type(u).__name__}")
         if u.dtype != torch.float64:
@@ -106,4 +215,9 @@ class CellToNode(torch.nn.Module):
             raise ValueError(f"u must be on {self.device}, not {u.device}")
         if tuple(u.shape) != (self.n_elems,) and not (u.dim() == 2 and u.shape[0] >= 1 and u.shape[1] == self.n_elems):
             raise ValueError(f"u must have shape ({self.n_elems},) or (k, {self.n_elems}), not {tuple(u.shape)}")
-        return _CellToNodeFn.apply(u.contiguous(), self, self.weights)
+        if K is None:
+            if scale is not None:
+                raise ValueError("scale needs K")
+            return _CellToNodeFn.apply(u.contiguous(), self, self.weights)
+        weights, _ = self.weights_of(K, scale)
+        return _CellToNodeFn.apply(u.contiguous(), self, weights)
