@@ -99,6 +99,8 @@ struct BackLoop<-1> {
 // With two waves the SIMD is bound by instruction issue (FP64 at ~2.6 ns an instruction, everything else at ~1): every change
 // since the first version that fitted was a cut in instructions -- 4 159 -> 4 096 a pass, of them FP64 2 926 -> 2 426; executed
 // flops per node 20.5 k (kernel above) -> 16.7 k against 15.9 k algorithmic.  5.95 -> 4.8 .. 5.0 ms per launch at 216^3.
+// (Round 12: 16.5 k with phase-1 columns that never form their rows 0 .. 2, -1.2 %.  Not every cut of FP64 pays: adds traded for
+//  selects in phase 2 were 2.2 % slower, multiplications traded for sign-bit flips in the face rows gave nothing -- DESIGN 4.3.)
 // Same arithmetic as the kernel above up to the order of a few sums: results differ by rounding only.
 #ifdef NIN_W2_FENCE_COLUMNS
 #define NIN_W2_COLUMN_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -153,9 +155,12 @@ struct P2LeanLoop<KEND, KEND> {
 //   w0 = -g0 (v0 . b),  w1 = -g1 (v1 . b + w0 v1 . v0),  w2 = -g2 (v2 . b + w0 v2 . v0 + w1 v2 . v1)
 // -- 45 operations a column against 54 for the three reflectors one after the other.  v_k = P[k .. 9][k] (pivot entries
 // included).  Out: u = z^T (rows 0 .. 2), the seven fill entries (rows 3 .. 9).  R0 < 0: the column c = e_0.
+// Rows 0 .. 2 are needed as u only, and they are (entry rows 0 .. 2) + V_top (w0, w1, w2), V_top the reflectors' top 3 x 3 block:
+// with q = V_top^T z (once per node, the caller's) u = z . (entry rows 0 .. 2) + q . w and the three rows are never formed --
+// 3 operations a column (5 for face 0, whose rows 1, 2 lie in the top block) where forming them and the dot took 9 (round 12).
 template <int R0>
 __device__ __forceinline__ void w2_column(const double (&P)[10][3], const double (&g3)[3], const double (&cc)[3], const double (&z)[3],
-                                          const double (&b)[3], double &u_out, double (&fill)[7]) {
+                                          const double (&q)[3], const double (&b)[3], double &u_out, double (&fill)[7]) {
     double w0, w1, w2;
     if (R0 < 0) {
         w0 = -(g3[0] * P[0][0]);
@@ -168,18 +173,17 @@ __device__ __forceinline__ void w2_column(const double (&P)[10][3], const double
                                     : fma(P[R0 + 2][2], b[2], P[R0 + 1][2] * b[1]);     // (R0 = 1: row 1 lies above v2)
         w2 = -(g3[2] * fma(w1, cc[2], fma(w0, cc[1], d2)));
     }
-    double B[10];
+    double ub;                                                // z . (entry rows 0 .. 2) + q0 w0
+    if (R0 < 0) ub = fma(q[0], w0, z[0]);
+    else if (R0 == 1) ub = fma(q[0], w0, fma(z[2], b[1], z[1] * b[0]));
+    else ub = q[0] * w0;
+    u_out = fma(q[2], w2, fma(q[1], w1, ub));
 #pragma unroll
-    for (int r = 0; r < 10; ++r) {
+    for (int r = 3; r < 10; ++r) {
         const bool own = R0 >= 0 && r >= R0 && r < R0 + 3;
-        double v = own ? fma(w0, P[r][0], b[own ? r - R0 : 0]) : (R0 < 0 && r == 0) ? fma(w0, P[0][0], 1.0) : w0 * P[r][0];
-        if (r >= 1) v = fma(w1, P[r][1], v);
-        if (r >= 2) v = fma(w2, P[r][2], v);
-        B[r] = v;
+        const double v = own ? fma(w0, P[r][0], b[own ? r - R0 : 0]) : w0 * P[r][0];
+        fill[r - 3] = fma(w2, P[r][2], fma(w1, P[r][1], v));
     }
-    u_out = fma(z[2], B[2], fma(z[1], B[1], z[0] * B[0]));
-#pragma unroll
-    for (int r = 0; r < 7; ++r) fill[r] = B[3 + r];
 }
 
 // LDS-DMA of one dword per lane (lane i's word lands at row[i]); the compiler does not order LDS reads behind it: every
@@ -437,10 +441,15 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
             for (int r = 2; r < 10; ++r) cc[0] = fma(P[r][1], P[r][0], cc[0]);
 #pragma unroll
             for (int r = 3; r < 10; ++r) { cc[1] = fma(P[r][2], P[r][0], cc[1]); cc[2] = fma(P[r][2], P[r][1], cc[2]); }
+            // q = V_top^T z: what the columns' rows 0 .. 2 add to u (w2_column)
+            double q3[3];
+            q3[0] = fma(z[2], P[2][0], fma(z[1], P[1][0], z[0] * P[0][0]));
+            q3[1] = fma(z[2], P[2][1], z[1] * P[1][1]);
+            q3[2] = z[2] * P[2][2];
             {
                 const double none[3] = {0.0, 0.0, 0.0};
                 double fill[7];
-                w2_column<-1>(P, g3, cc, z, none, se, fill);   // c = e_0 on entry: only the cell row carries a 1
+                w2_column<-1>(P, g3, cc, z, q3, none, se, fill);   // c = e_0 on entry: only the cell row carries a 1
                 pin(se);
 #pragma unroll
                 for (int r = 0; r < 7; ++r) L[64 * r] = fill[r];                            // slots 0 .. 6: column c
@@ -453,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
             for (int t = 0; t < 3; ++t) {                                                    // face 0: rows 1 .. 3
                 const double b[3] = {nb0[0][t], -sav[0][0][t], -sav[0][1][t]};
                 double fill[7];
-                w2_column<1>(P, g3, cc, z, b, u[t], fill);
+                w2_column<1>(P, g3, cc, z, q3, b, u[t], fill);
                 pin(u[t]);
 #pragma unroll
                 for (int r = 0; r < 7; ++r) L[64 * (7 + 7 * t + r)] = fill[r];               // slots 7 .. 27: F0
@@ -464,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
             for (int t = 0; t < 3; ++t) {                                                    // face 1: rows 4 .. 6
                 const double b[3] = {nb0[1][t], -sav[1][0][t], -sav[1][1][t]};
                 double fill[7];
-                w2_column<4>(P, g3, cc, z, b, u[3 + t], fill);
+                w2_column<4>(P, g3, cc, z, q3, b, u[3 + t], fill);
                 pin(u[3 + t]);
                 if (t == 0) {
 #pragma unroll
@@ -480,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
             for (int t = 0; t < 3; ++t) {                                                    // face 2: rows 7 .. 9
                 const double b[3] = {nb0[2][t], -sav[2][0][t], -sav[2][1][t]};
                 double fill[7];
-                w2_column<7>(P, g3, cc, z, b, u[6 + t], fill);
+                w2_column<7>(P, g3, cc, z, q3, b, u[6 + t], fill);
                 pin(u[6 + t]);
 #pragma unroll
                 for (int r = 0; r < 7; ++r) F2[r][t] = fill[r];
