@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from . import topology as T
+from ._args import is_torch, on_gpu
 
 _SCALARS = ("dim", "n_elems", "n_points", "n_faces", "n_edges", "MX_ELEMENTS_PER_POINT",
             "MX_POINTS_PER_POINT", "MX_ELEMENTS_PER_FACE", "MX_FACES_PER_POINT")
@@ -23,6 +24,22 @@ _ARRAYS = ("esup", "esup_ptr", "psup", "psup_ptr", "fsup", "fsup_ptr", "esuf", "
 
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _dev_ptr(t):
+    """the address of a torch tensor's data (None stays None: an optional argument of the C entry point)"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _dev_ids(t):
+    """the three arguments of a C entry point that reads ids (int32 / int64) from the device: address, 64-bit?, how many"""
+    return ctypes.c_void_p(t.data_ptr()), int(t.element_size() == 8), int(t.numel())
+
+
+def _stream_of(t):
+    """torch's current stream on the tensor's device: where the *_device methods of Grid launch"""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 class _PlanCounts(dict):
@@ -75,15 +92,7 @@ class Grid:
         self.logging = bool(logging)
         self.build_edges = bool(build_edges)
         self._cache = {}
-        self._perm_key = None   # fingerprint of the permeability table resident on the device (interpolator.py)
-        self._fields_variable = None   # the variable whose Neumann flags are resident (DevicePlan.ensure_current)
-        # True from load_permeability_device() until a host table is uploaded over it, or read back into the host rows
-        # (Interpolator.permeability_on_device)
-        self._perm_from_device = False
-        # True from load_flags_device() / scatter_flags_device() until a host row is uploaded over the flags, or they are read back into
-        # the host row (Interpolator.neumann_flags_on_device); _flags_key: the fingerprint of that host row at the device update
-        self._flags_from_device = False
-        self._flags_key = None
+        self._no_fields_resident()
         self._h = ctypes.c_void_p()
         L = _lib.load()
         if build_device is None:   # the native OpenMP builder (csrc/grid_host.cpp)
@@ -129,7 +138,7 @@ class Grid:
             return None
         L = _lib.load()
         shape = (int(self.n_points), self._coords_dim)
-        if type(coords).__module__.split(".")[0] == "torch" and getattr(coords, "is_cuda", False):
+        if on_gpu(coords):
             import torch
             if tuple(coords.shape) != shape:
                 raise ValueError(f"points must have shape {shape}, not {tuple(coords.shape)}.")
@@ -139,10 +148,9 @@ class Grid:
                 raise ValueError(f"points are on {coords.device}, the grid is on " +
                                  (f"cuda:{self.device}" if self.device >= 0 else "no device (call to_device first)") + ".")
             t = coords.detach().contiguous()
-            stream = torch.cuda.current_stream(coords.device).cuda_stream
-            rc = L.nin_grid_update_points_device(self._h, ctypes.c_void_p(t.data_ptr()), self._coords_dim, ctypes.c_void_p(stream))
+            rc = L.nin_grid_update_points_device(self._h, _dev_ptr(t), self._coords_dim, _stream_of(t))
         else:
-            if type(coords).__module__.split(".")[0] == "torch":
+            if is_torch(coords):
                 coords = coords.detach().numpy()
             try:
                 xyz = np.ascontiguousarray(coords, dtype=np.float64)
@@ -151,12 +159,16 @@ class Grid:
             if xyz.shape != shape:
                 raise ValueError(f"points must have shape {shape}, not {xyz.shape}.")
             rc = L.nin_grid_update_points(self._h, _ptr(xyz), self._coords_dim)
+        self._points_moved(rc)
+        return None
+
+    def _points_moved(self, rc):
+        """behind a native call that moved points: the cached geometry goes, its return code is raised"""
         for name in ("point_coords", "centroids", "faces_centers", "normal_faces", "faces_areas"):
             self._cache.pop(name, None)   # also after a failure: the native arrays may be half way
         if rc == _lib.NIN_EINVAL:
-            raise ValueError(L.nin_last_error().decode())
+            raise ValueError(_lib.load().nin_last_error().decode())
         _lib.check(rc)
-        return None
 
     def scatter_point_coords(self, nodes, rows):
         """Move a subset of the nodes (nin_grid_scatter_points_device / nin_grid_scatter_points): row i of `rows` (m, coords_dim) float64 is
@@ -166,18 +178,11 @@ class Grid:
         vertices of the cells around them join the dirty set.  The arguments are checked by Interpolator.update_points, which is the
         public way in."""
         L = _lib.load()
-        if type(rows).__module__.split(".")[0] == "torch":
-            import torch
-            stream = torch.cuda.current_stream(rows.device).cuda_stream
-            rc = L.nin_grid_scatter_points_device(self._h, ctypes.c_void_p(nodes.data_ptr()), int(nodes.dtype == torch.int64), int(nodes.numel()),
-                                                  ctypes.c_void_p(rows.data_ptr()), self._coords_dim, ctypes.c_void_p(stream))
+        if is_torch(rows):
+            rc = L.nin_grid_scatter_points_device(self._h, *_dev_ids(nodes), _dev_ptr(rows), self._coords_dim, _stream_of(rows))
         else:
             rc = L.nin_grid_scatter_points(self._h, _ptr(nodes), int(len(nodes)), _ptr(rows), self._coords_dim)
-        for name in ("point_coords", "centroids", "faces_centers", "normal_faces", "faces_areas"):
-            self._cache.pop(name, None)   # also after a failure: the native arrays may be half way
-        if rc == _lib.NIN_EINVAL:
-            raise ValueError(L.nin_last_error().decode())
-        _lib.check(rc)
+        self._points_moved(rc)
 
     def calculate_centroids(self):
         return None
@@ -242,56 +247,115 @@ class Grid:
 
     # -- device ------------------------------------------------------------------------------------
     def to_device(self, device=0):
-        self._perm_key = None   # a fresh device copy holds no fields
-        self._fields_variable = None   # ... and nobody's Neumann flags: every DevicePlan re-uploads at its next launch
-        self._perm_from_device = False
-        self._flags_from_device = False
-        self._flags_key = None
+        self._no_fields_resident()
         _lib.check(_lib.load().nin_grid_to_device(self._h, int(device)))
         return self
+
+    # -- whose are the fields resident on the device? ------------------------------------------------------------------------------------
+    # The record is six fields.  Only the methods below assign them, each named for the event it records; the Interpolator reads them.
+    #   _perm_key               fingerprint (interpolator.py: _perm_keys) of the host permeability / diff_mag rows as they were when the
+    #                           resident table was last theirs, or was written over them; None: no permeability on this device copy yet
+    #   _perm_from_device       the resident table was written from device memory and is newer than the host rows
+    #                           (Interpolator.permeability_on_device)
+    #   _perm_edited_last_call  interpolate() found the host table edited at its last call: the next one hashes before it launches
+    #   _fields_variable        the variable whose Neumann flags are resident (DevicePlan.ensure_current); None: nobody's
+    #   _flags_from_device      the resident flags were written from device memory and are newer than that variable's host row
+    #                           (Interpolator.neumann_flags_on_device)
+    #   _flags_key              only while _flags_from_device: the fingerprint of that host row at the first device update behind a host upload
+    # The rule: a device copy stays until the CONTENTS of the host rows change; an in-place edit of the host rows wins at the next call
+    # that reads the tables -- it is found there, by its fingerprint, and is then a host upload; another variable's flags make every node
+    # dirty.  What each event does ("-": stays as it is):
+    #
+    #   permeability                                      method                       _perm_key        _perm_from_device
+    #   new Grid, to_device()                             _no_fields_resident          None             False    (_perm_edited_last_call too)
+    #   host upload                                       host_permeability_resident   the rows'        False
+    #   whole-table device update, device scatter         permeability_from_device     - (the rows'     True
+    #                                                                                    if it was None)
+    #   host rows patched in step (the device followed)   host_permeability_resident   the rows'        False (it was)
+    #   host rows edited (the device did not follow)      host_permeability_edited     -                False
+    #   fetch                                             host_permeability_resident   the rows'        False
+    #   interpolate() compared the fingerprints           permeability_edit_seen       -                -        (_perm_edited_last_call)
+    #
+    #   Neumann flags                                     method                       _fields_variable _flags_from_device  _flags_key
+    #   new Grid, to_device()                             _no_fields_resident          None             False               None
+    #   host upload: every call that reads the tables,    host_flags_uploaded          the variable     False               None
+    #     unless a device copy is still current                                        (every node dirty if a device copy or another variable's flags went)
+    #   whole-array device update (another variable's     flags_from_device            the variable     True                the row's, unless kept from
+    #     too: the differing nodes are dirty), scatter                                                                      an earlier device update
+    #   host row patched in step (the device followed)    (nothing to record: the row still is what is resident)
+    #   host row edited (the device did not follow)       (nothing to record: found by its fingerprint, or uploaded anyway)
+    #   fetch                                             flags_fetched                -                False               None
+    #
+    # Who records: the *_device methods further down only launch.  Their caller knows which event the launch was -- a device update, or
+    # host values sent through the device path -- and records it afterwards, so a launch that raises records nothing.
+    def _no_fields_resident(self):
+        """a fresh device copy holds no fields and nobody's Neumann flags: every DevicePlan re-uploads at its next launch"""
+        self._perm_key = self._fields_variable = self._flags_key = None
+        self._perm_from_device = self._flags_from_device = self._perm_edited_last_call = False
+
+    def host_permeability_resident(self, key):
+        """the resident table IS the host rows (fingerprint `key`): they were uploaded, followed row by row, or fetched into"""
+        self._perm_key, self._perm_from_device = key, False
+
+    def host_permeability_edited(self):
+        """the host rows are the newer ones now: the next call that reads the tables uploads them"""
+        self._perm_from_device = False
+
+    def permeability_from_device(self, fingerprint, *host_rows):
+        """the resident table was written from device memory.  fingerprint(*host_rows) is only asked for when no permeability went to this
+        device copy before: the host table then counts as seen from here on, or the next call would upload it over the device's K (its
+        first hash finds nothing to compare with)"""
+        if self._perm_key is None:
+            self._perm_key = fingerprint(*host_rows)
+        self._perm_from_device = True
+
+    def permeability_edit_seen(self, edited):
+        """interpolate() found the host table edited at this call (True) or still the resident one (False)"""
+        self._perm_edited_last_call = edited
+
+    def host_flags_uploaded(self, variable):
+        """`variable`'s host row went over whatever flags were resident"""
+        if self._flags_from_device or self._fields_variable not in (None, variable):
+            self.mark_all_dirty()   # other flags: any row may differ from what a caller's buffers hold (DevicePlan.launch_dirty)
+        self._fields_variable, self._flags_from_device, self._flags_key = variable, False, None
+
+    def flags_from_device(self, variable, fingerprint, host_row):
+        """the resident flags, now `variable`'s, were written from device memory.  fingerprint(host_row), of the variable's host row, is
+        asked for at the FIRST device update behind a host upload, not at every step of a time loop: an in-place edit of the row made
+        between two device updates is still found by the next call that reads the tables"""
+        if not (self._flags_from_device and self._fields_variable == variable and self._flags_key is not None):
+            self._flags_key = fingerprint(host_row)
+        self._fields_variable, self._flags_from_device = variable, True
+
+    def flags_fetched(self):
+        """the resident flags were read back into the host row: the row IS what is resident"""
+        self._flags_from_device, self._flags_key = False, None
 
     def load_permeability_device(self, K, scale=None):
         """The resident permeability from torch tensors on the grid's device (nin_fields_set_permeability_device): K float64,
         contiguous, n_elems * 9 values; scale None or float64 contiguous (n_elems,).  Asynchronous on torch's current stream; the
         arguments are checked by Interpolator.update_permeability, which is the public way in."""
-        import torch
-        stream = torch.cuda.current_stream(K.device).cuda_stream
-        _lib.check(_lib.load().nin_fields_set_permeability_device(
-            self._h, ctypes.c_void_p(K.data_ptr()), None if scale is None else ctypes.c_void_p(scale.data_ptr()), ctypes.c_void_p(stream)))
-        self._perm_from_device = True
+        _lib.check(_lib.load().nin_fields_set_permeability_device(self._h, _dev_ptr(K), _dev_ptr(scale), _stream_of(K)))
 
     def scatter_permeability_device(self, cells, K, scale=None):
         """Rows of the resident permeability from torch tensors on the grid's device (nin_fields_scatter_permeability_device):
         cells int32 / int64 (m,), K float64 contiguous m * 9 values, scale None or float64 (m,).  The vertices of the cells join the
         dirty set.  Asynchronous on torch's current stream; the arguments are checked by Interpolator.update_permeability, which is
         the public way in."""
-        import torch
-        stream = torch.cuda.current_stream(K.device).cuda_stream
-        _lib.check(_lib.load().nin_fields_scatter_permeability_device(
-            self._h, ctypes.c_void_p(cells.data_ptr()), int(cells.dtype == torch.int64), int(cells.numel()), ctypes.c_void_p(K.data_ptr()),
-            None if scale is None else ctypes.c_void_p(scale.data_ptr()), ctypes.c_void_p(stream)))
+        _lib.check(_lib.load().nin_fields_scatter_permeability_device(self._h, *_dev_ids(cells), _dev_ptr(K), _dev_ptr(scale), _stream_of(K)))
 
     def load_flags_device(self, flags):
         """The resident Neumann flags from a torch tensor on the grid's device (nin_fields_set_flags_device): float64, bool or uint8,
         contiguous, (n_points,).  The nodes whose bit changes join the dirty set (none while every node is dirty).  Asynchronous on torch's
         current stream; the arguments are checked by Interpolator.update_neumann_flags, which is the public way in."""
-        import torch
-        stream = torch.cuda.current_stream(flags.device).cuda_stream
-        _lib.check(_lib.load().nin_fields_set_flags_device(self._h, ctypes.c_void_p(flags.data_ptr()), int(flags.dtype != torch.float64),
-                                                           ctypes.c_void_p(stream)))
-        self._flags_from_device = True
+        _lib.check(_lib.load().nin_fields_set_flags_device(self._h, _dev_ptr(flags), int(flags.element_size() == 1), _stream_of(flags)))
 
     def scatter_flags_device(self, nodes, flags):
         """Neumann flags of a subset of the nodes from torch tensors on the grid's device (nin_fields_scatter_flags_device): nodes int32 /
         int64 (m,), flags float64, bool or uint8 (m,), value i for node nodes[i].  Ids are checked on the device; the nodes whose bit changes
         join the dirty set.  Asynchronous on torch's current stream; the arguments are checked by Interpolator.update_neumann_flags, which
         is the public way in."""
-        import torch
-        stream = torch.cuda.current_stream(flags.device).cuda_stream
-        _lib.check(_lib.load().nin_fields_scatter_flags_device(
-            self._h, ctypes.c_void_p(nodes.data_ptr()), int(nodes.dtype == torch.int64), int(nodes.numel()), ctypes.c_void_p(flags.data_ptr()),
-            int(flags.dtype != torch.float64), ctypes.c_void_p(stream)))
-        self._flags_from_device = True
+        _lib.check(_lib.load().nin_fields_scatter_flags_device(self._h, *_dev_ids(nodes), _dev_ptr(flags), int(flags.element_size() == 1), _stream_of(flags)))
 
     def fetch_flags(self):
         """The Neumann bits resident on the device as a uint8 array (n_points,) of 0 / 1 (nin_fields_get_flags: waits for the device); None

@@ -14,6 +14,7 @@ import time
 import numpy as np
 import scipy.sparse as sp
 
+from . import _args as A
 from . import _lib
 from . import topology as T
 from .grid import Grid
@@ -77,6 +78,34 @@ def _table_key(a):
     return (a.__array_interface__["data"][0], a.size, h.value)
 
 
+def _perm_keys(perm, dmag):
+    """The fingerprint Grid._perm_key holds: the permeability's and the diff_mag's."""
+    return (_table_key(perm), _table_key(dmag))
+
+
+def _set_fields(grid, perm, dmag, flag, nval, key):
+    """nin_fields_set (a None keeps what is resident), and its record: a host table (fingerprint `key`) went over whatever a device update
+    had left."""
+    _lib.check(_lib.load().nin_fields_set(grid._h, _ptr(perm), _ptr(dmag), _ptr(flag), _ptr(nval)))
+    if perm is not None:
+        grid.host_permeability_resident(key)
+
+
+def _follow_on_device(grid, launch, *arrays):
+    """Host arrays given while the grid is on a device, and what is resident there are the host rows: the same values through `launch`
+    (one of Grid's *_device methods) on the grid's device, and wait -- the resident copy and the dirty set follow.  Needs torch: False
+    without it, and the rows then count as edited."""
+    try:
+        import torch
+    except ImportError:
+        return False
+    where = torch.device("cuda", grid.device)
+    with torch.cuda.device(where):
+        launch(*[torch.from_numpy(a).to(where) for a in arrays])
+        torch.cuda.current_stream(where).synchronize()
+    return True
+
+
 class _TableCheck:
     """Is the permeability / diff_mag resident on the device still the caller's?  The answer is a hash of all 0.8 GB of the
     two tables (10 M cells: 3-5 ms on the host's OpenMP team); it is computed on a thread WHILE the kernels already run with the
@@ -89,7 +118,7 @@ class _TableCheck:
         self._t.start()
 
     def _hash(self):
-        self.key = (_table_key(self.perm), _table_key(self.dmag))
+        self.key = _perm_keys(self.perm, self.dmag)
 
     def join(self):
         self._t.join()
@@ -100,9 +129,7 @@ class _TableCheck:
 
     def upload(self, flag):
         # flag None: the flags resident on the device stay (_upload_fields found a device copy that is still the newer one)
-        _lib.check(_lib.load().nin_fields_set(self.grid._h, _ptr(self.perm), _ptr(self.dmag), _ptr(flag), None))
-        self.grid._perm_key = self.key
-        self.grid._perm_from_device = False
+        _set_fields(self.grid, self.perm, self.dmag, flag, None, self.key)
 
 
 def _upload_fields(grid, method, cells_data, points_data, variable_to_index, variable, device=0, always_perm=False,
@@ -111,20 +138,15 @@ def _upload_fields(grid, method, cells_data, points_data, variable_to_index, var
     name is a KeyError there too) and hand them to the device.  always_perm: upload permeability / diff_mag whenever
     the mesh has them (a DevicePlan serves any method afterwards).  speculate: when a permeability is resident already,
     upload the flags only and return a _TableCheck (the caller launches at once and asks it afterwards); else None."""
-    L = _lib.load()
     if grid.device < 0:   # the GPU its Interpolator was built for (a bare Grid handed to a plugin: device 0)
         grid.to_device(getattr(grid, "preferred_device", device))
     P, E = grid.n_points, grid.n_elems
     v2i = variable_to_index
     flag = np.ascontiguousarray(np.asarray(points_data)[v2i["points"]["neumann_flag_" + variable]][:P], dtype=DTYPE_F)
-    host_over_device = False
-    if grid._flags_from_device:
-        # flags written from the device (Interpolator.update_neumann_flags) stay resident while the CONTENTS of this variable's host
-        # row are what they were at that update; an in-place edit of the row, or another variable, wins -- the permeability's rule
-        if grid._fields_variable == variable and grid._flags_key == _table_key(flag):
-            flag = None
-        else:
-            grid._flags_from_device, grid._flags_key, host_over_device = False, None, True
+    # flags written from the device (Interpolator.update_neumann_flags) stay resident while the CONTENTS of this variable's host
+    # row are what they were at that update; an in-place edit of the row, or another variable, wins -- the permeability's rule
+    if grid._flags_from_device and grid._fields_variable == variable and grid._flags_key == _table_key(flag):
+        flag = None
     perm = dmag = nval = None
     key = None
     check = None
@@ -134,23 +156,18 @@ def _upload_fields(grid, method, cells_data, points_data, variable_to_index, var
         dmag = np.ascontiguousarray(cd[v2i["cells"]["diff_mag"]][:E], dtype=DTYPE_F)
         if method == "gls":
             nval = np.ascontiguousarray(np.asarray(points_data)[v2i["points"]["neumann_" + variable]][:P], dtype=DTYPE_F)
-        if speculate and getattr(grid, "_perm_key", None) is not None:
+        if speculate and grid._perm_key is not None:
             check = _TableCheck(grid, perm, dmag)
             perm = dmag = None
         else:
             # permeability and diff_mag belong to the mesh: 0.8 GB at 10 M cells, uploaded once per table contents
-            key = (_table_key(perm), _table_key(dmag))
-            if getattr(grid, "_perm_key", None) == key and grid.device >= 0:
+            key = _perm_keys(perm, dmag)
+            if grid._perm_key == key and grid.device >= 0:
                 perm = dmag = None
-    _lib.check(L.nin_fields_set(grid._h, _ptr(perm), _ptr(dmag), _ptr(flag), _ptr(nval)))
-    if key is not None:
-        grid._perm_key = key
-    if perm is not None:
-        grid._perm_from_device = False   # the host table went over whatever a device update had left
-    # the flags on the device belong to the GRID, not to a plan: remember whose they are (DevicePlan.ensure_current)
-    if host_over_device or (grid._fields_variable is not None and grid._fields_variable != variable):
-        grid.mark_all_dirty()   # other flags: any row may differ from what a caller's buffers hold (DevicePlan.launch_dirty)
-    grid._fields_variable = variable
+    _set_fields(grid, perm, dmag, flag, nval, key)
+    if flag is not None:
+        # the flags on the device belong to the GRID, not to a plan: it remembers whose they are (DevicePlan.ensure_current)
+        grid.host_flags_uploaded(variable)
     if check is not None:
         check.flag = flag
     return check
@@ -245,6 +262,19 @@ class Interpolator:
         if self.logging:
             print(f"[{kind:<5}] ({time.strftime('%H:%M:%S'):<8}) {msg}")
 
+    _NOT_ASKED = object()
+
+    def _check_call(self, method=_NOT_ASKED, variable=_NOT_ASKED):
+        """What an entry point asks first: a mesh is loaded, `method` is known, `variable` is a cell variable (the last two if given)."""
+        if not self.is_grid_initialized:
+            raise ValueError("Grid not initialized. Please load a mesh first.")
+        if method is not self._NOT_ASKED and method not in self.supported_methods:
+            raise ValueError(f"Method '{method}' not supported. Supported methods are: "
+                             f"{list(self.supported_methods.keys())}")
+        if variable is not self._NOT_ASKED and variable not in self.variable_to_index["cells"]:
+            raise ValueError(f"Variable '{variable}' not found in cells data. "
+                             "Point -> Cell interpolation not supported yet.")
+
     def is_cached(self, filename):
         """The reference's pickle cache (interpolator.pyx:93-111) is not kept: nothing is ever cached."""
         return None
@@ -317,79 +347,37 @@ class Interpolator:
         synchronous.  On a grid that is on a device the same kernels run and the dirty set follows; a grid on no device recomputes its
         host geometry (works without a GPU; there is no dirty set then: the first upload makes every node dirty anyway).
         Host and device arguments cannot be mixed (TypeError)."""
-        if not self.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
+        self._check_call()
         if nodes is not None:
             return self._update_points_nodes(points, nodes)
         g = self.grid
-        on_device = type(points).__module__.split(".")[0] == "torch" and getattr(points, "is_cuda", False)
+        on_device = A.on_gpu(points)
         if on_device and g.device < 0:
             g.to_device(self.device)
         g.load_point_coords(points)
         if on_device:
             self._points_coords, self._points_on_device = None, True
         else:
-            if type(points).__module__.split(".")[0] == "torch":
-                points = points.detach().numpy()
-            self.points_coords = np.ascontiguousarray(np.array(points, dtype=DTYPE_F))
+            self.points_coords = np.ascontiguousarray(np.array(A.to_host(points), dtype=DTYPE_F))
 
     def _update_points_nodes(self, rows, nodes):
         g = self.grid
-        P, cd = int(g.n_points), g._coords_dim
-        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
-        on_gpu = lambda a: is_torch(a) and getattr(a, "is_cuda", False)
-        if on_gpu(nodes):
-            import torch
-            where = torch.device("cuda", self.device)
-            if nodes.dtype not in (torch.int32, torch.int64):
-                raise TypeError(f"nodes must be int32 or int64, not {nodes.dtype} (no silent cast)")
-            if nodes.device != where:
-                raise ValueError(f"nodes must be on {where}, not {nodes.device}")
-            if nodes.dim() != 1:
-                raise ValueError(f"nodes must have shape (m,), not {tuple(nodes.shape)}")
-            m = int(nodes.shape[0])
-            if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
-                raise TypeError(f"points must be a torch.Tensor on {where} when nodes is, not " +
-                                (f"one on {rows.device}" if isinstance(rows, torch.Tensor) else type(rows).__name__))
-            if rows.dtype != torch.float64:
-                raise TypeError(f"points must be float64, not {rows.dtype} (no silent cast)")
-            if rows.device != where:
-                raise ValueError(f"points must be on {where}, not {rows.device}")
-            if tuple(rows.shape) != (m, cd):
-                raise ValueError(f"points must have shape {(m, cd)}, not {tuple(rows.shape)}")
+        cd = g._coords_dim
+        if A.on_gpu(nodes):
+            m = A.device_ids(nodes, "nodes", self.device)
+            rows = A.device_tensor(rows, "points", self.device, "nodes", ((m, cd),))
             if m == 0:
                 return
             if g.device < 0:
                 g.to_device(self.device)
-            g.scatter_point_coords(nodes.detach().contiguous(), rows.detach().contiguous())
+            g.scatter_point_coords(nodes.detach().contiguous(), rows)
             self._points_coords, self._points_on_device = None, True
             return
-        if on_gpu(rows):
+        if A.on_gpu(rows):
             raise TypeError(f"points must be on the host when nodes is (a numpy array), not on {rows.device}")
-        if is_torch(nodes):
-            nodes = nodes.detach().numpy()
-        if is_torch(rows):
-            rows = rows.detach().numpy()
-        ids = np.asarray(nodes)
-        if ids.dtype.kind not in "iu":
-            raise TypeError(f"nodes must be integers, not {ids.dtype} (no silent cast)")
-        if ids.ndim != 1:
-            raise ValueError(f"nodes must have shape (m,), not {ids.shape}")
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        m = len(ids)
-        bad = (ids < 0) | (ids >= P)
-        if bad.any():
-            raise ValueError(f"nodes must lie in [0, {P}): {int(bad.sum())} of {m} do not (the first: {int(ids[bad][0])})")
-        try:
-            X = np.asarray(rows)
-            if X.dtype.kind == "f" and X.dtype != DTYPE_F:
-                raise TypeError(f"points must be float64, not {X.dtype} (no silent cast)")
-            X = np.ascontiguousarray(X, dtype=DTYPE_F)
-        except ValueError as e:
-            raise ValueError(f"points cannot be converted to float64: {e}") from e
-        if X.shape != (m, cd):
-            raise ValueError(f"points must have shape {(m, cd)}, not {X.shape}")
-        if m == 0:
+        ids = A.host_ids(A.to_host(nodes), "nodes", int(g.n_points))
+        X = A.host_float64(A.to_host(rows), "points", ((len(ids), cd),))
+        if len(ids) == 0:
             return
         pc = self.points_coords           # (after a device update: read back from the grid first)
         g.scatter_point_coords(ids, X)
@@ -398,8 +386,7 @@ class Interpolator:
     # ---- changing permeability ---------------------------------------------------------------------
     def _perm_rows(self):
         """The `permeability` and `diff_mag` rows of cells_data as _upload_fields reads them (views: same addresses, same hash)."""
-        if not self.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
+        self._check_call()
         v2i = self.variable_to_index["cells"]
         if "permeability" not in v2i or "diff_mag" not in v2i:
             raise ValueError("Variable 'permeability' not found in cells data: load a mesh that carries it.")
@@ -443,154 +430,59 @@ class Interpolator:
             return self._update_permeability_cells(K, scale, cells, perm_row, dmag_row)
         g = self.grid
         E = g.n_elems
-        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
-        if is_torch(K) and getattr(K, "is_cuda", False):
-            import torch
-            where = torch.device("cuda", self.device)
-
-            def checked(t, name, shapes):
-                if not isinstance(t, torch.Tensor):
-                    raise TypeError(f"{name} must be a torch.Tensor on {where} when K is, not {type(t).__name__}")
-                if t.dtype != torch.float64:
-                    raise TypeError(f"{name} must be float64, not {t.dtype} (no silent cast)")
-                if t.device != where:
-                    raise ValueError(f"{name} must be on {where}, not {t.device}")
-                if tuple(t.shape) not in shapes:
-                    raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {tuple(t.shape)}")
-                return t.detach().contiguous()
-
-            Kd = checked(K, "K", ((E, 3, 3), (E, 9)))
-            sd = None if scale is None else checked(scale, "scale", ((E,),))
+        if A.on_gpu(K):
+            Kd = A.device_tensor(K, "K", self.device, "K", ((E, 3, 3), (E, 9)), cpu_tensor_passes=True)
+            sd = None if scale is None else A.device_tensor(scale, "scale", self.device, "K", ((E,),), cpu_tensor_passes=True)
             if g.device < 0:
                 g.to_device(self.device)
-            if g._perm_key is None:
-                # the host table was never uploaded to this device copy: it counts as seen from here on, or the next call would
-                # upload it over the device's K (its first hash finds nothing to compare with)
-                g._perm_key = (_table_key(perm_row), _table_key(dmag_row))
             g.load_permeability_device(Kd, sd)
+            g.permeability_from_device(_perm_keys, perm_row, dmag_row)
             return
-        if is_torch(K):
-            K = K.detach().numpy()
-        if scale is not None and is_torch(scale):
-            if getattr(scale, "is_cuda", False):
-                raise ValueError(f"scale must be on the host when K is, not {scale.device}")
-            scale = scale.detach().numpy()
-
-        def checked(a, name, shapes):
-            try:
-                a = np.asarray(a)
-                if a.dtype.kind == "f" and a.dtype != DTYPE_F:
-                    raise TypeError(f"{name} must be float64, not {a.dtype} (no silent cast)")
-                a = np.ascontiguousarray(a, dtype=DTYPE_F)
-            except ValueError as e:
-                raise ValueError(f"{name} cannot be converted to float64: {e}") from e
-            if a.shape not in shapes:
-                raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {a.shape}")
-            return a
-
-        K9 = checked(K, "K", ((E, 3, 3), (E, 9))).reshape(E, 9)
+        if A.on_gpu(scale):
+            raise ValueError(f"scale must be on the host when K is, not {scale.device}")
+        K9 = A.host_float64(A.to_host(K), "K", ((E, 3, 3), (E, 9))).reshape(E, 9)
         if scale is not None:
-            K9 = checked(scale, "scale", ((E,),))[:, None] * K9
+            K9 = A.host_float64(A.to_host(scale), "scale", ((E,),))[:, None] * K9
         perm_row[:] = K9.reshape(-1)
         dmag_row[:] = self.compute_diffusion_magnitude(K9)
-        g._perm_from_device = False  # the host rows are the newer ones now: the next call that reads the tables uploads them
+        g.host_permeability_edited()
 
     def _update_permeability_cells(self, K, scale, cells, perm_row, dmag_row):
         g = self.grid
-        E = g.n_elems
-        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
-        on_gpu = lambda a: is_torch(a) and getattr(a, "is_cuda", False)
-        if on_gpu(cells):
-            import torch
-            where = torch.device("cuda", self.device)
-            if cells.dtype not in (torch.int32, torch.int64):
-                raise TypeError(f"cells must be int32 or int64, not {cells.dtype} (no silent cast)")
-            if cells.device != where:
-                raise ValueError(f"cells must be on {where}, not {cells.device}")
-            if cells.dim() != 1:
-                raise ValueError(f"cells must have shape (m,), not {tuple(cells.shape)}")
-            m = int(cells.shape[0])
-
-            def checked(t, name, shapes):
-                if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                    raise TypeError(f"{name} must be a torch.Tensor on {where} when cells is, not " +
-                                    (f"one on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__))
-                if t.dtype != torch.float64:
-                    raise TypeError(f"{name} must be float64, not {t.dtype} (no silent cast)")
-                if t.device != where:
-                    raise ValueError(f"{name} must be on {where}, not {t.device}")
-                if tuple(t.shape) not in shapes:
-                    raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {tuple(t.shape)}")
-                return t.detach().contiguous()
-
-            Kd = checked(K, "K", ((m, 3, 3), (m, 9)))
-            sd = None if scale is None else checked(scale, "scale", ((m,),))
+        if A.on_gpu(cells):
+            m = A.device_ids(cells, "cells", self.device)
+            Kd = A.device_tensor(K, "K", self.device, "cells", ((m, 3, 3), (m, 9)))
+            sd = None if scale is None else A.device_tensor(scale, "scale", self.device, "cells", ((m,),))
             cd = cells.detach().contiguous()
             if g.device < 0:
                 g.to_device(self.device)
             if g._perm_key is None:
-                # nothing was ever uploaded to this device copy: the host table goes over first (through the device path: the same
-                # bits), and counts as seen from here on (see update_permeability)
-                g._perm_key = (_table_key(perm_row), _table_key(dmag_row))
-                g.load_permeability_device(torch.from_numpy(np.ascontiguousarray(perm_row)).to(where))
+                # nothing was ever uploaded to this device copy: the host table goes over first (through the device path: the same bits)
+                import torch
+                g.load_permeability_device(torch.from_numpy(np.ascontiguousarray(perm_row)).to(f"cuda:{self.device}"))
             g.scatter_permeability_device(cd, Kd, sd)
-            g._perm_from_device = True
+            g.permeability_from_device(_perm_keys, perm_row, dmag_row)
             return
-        if on_gpu(K) or on_gpu(scale):
+        if A.on_gpu(K) or A.on_gpu(scale):
             raise TypeError("K and scale must be on the host when cells is (a numpy array), not on " +
-                            str((K if on_gpu(K) else scale).device))
-        if is_torch(cells):
-            cells = cells.detach().numpy()
-        if is_torch(K):
-            K = K.detach().numpy()
-        if scale is not None and is_torch(scale):
-            scale = scale.detach().numpy()
-        ids = np.asarray(cells)
-        if ids.dtype.kind not in "iu":
-            raise TypeError(f"cells must be integers, not {ids.dtype} (no silent cast)")
-        if ids.ndim != 1:
-            raise ValueError(f"cells must have shape (m,), not {ids.shape}")
-        ids = ids.astype(np.int64)
+                            str((K if A.on_gpu(K) else scale).device))
+        E = g.n_elems
+        ids = A.host_ids(A.to_host(cells), "cells", E)
         m = len(ids)
-        bad = (ids < 0) | (ids >= E)
-        if bad.any():
-            raise ValueError(f"cells must lie in [0, {E}): {int(bad.sum())} of {m} do not (the first: {int(ids[bad][0])})")
-
-        def checked(a, name, shapes):
-            try:
-                a = np.asarray(a)
-                if a.dtype.kind == "f" and a.dtype != DTYPE_F:
-                    raise TypeError(f"{name} must be float64, not {a.dtype} (no silent cast)")
-                a = np.ascontiguousarray(a, dtype=DTYPE_F)
-            except ValueError as e:
-                raise ValueError(f"{name} cannot be converted to float64: {e}") from e
-            if a.shape not in shapes:
-                raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, not {a.shape}")
-            return a
-
-        K9 = checked(K, "K", ((m, 3, 3), (m, 9))).reshape(m, 9)
+        K9 = A.host_float64(A.to_host(K), "K", ((m, 3, 3), (m, 9))).reshape(m, 9)
         if scale is not None:
-            K9 = checked(scale, "scale", ((m,),))[:, None] * K9
+            K9 = A.host_float64(A.to_host(scale), "scale", ((m,),))[:, None] * K9
         if m == 0:
             return
         # is the resident table the host rows as they are NOW?  Only then can the device follow row by row
         in_step = (g.device >= 0 and g._perm_key is not None and not g._perm_from_device and
-                   g._perm_key == (_table_key(perm_row), _table_key(dmag_row)))
+                   g._perm_key == _perm_keys(perm_row, dmag_row))
         perm_row.reshape(E, 9)[ids] = K9
         dmag_row[ids] = self.compute_diffusion_magnitude(K9)
-        if in_step:
-            try:
-                import torch
-            except ImportError:
-                in_step = False
-        if in_step:
-            where = torch.device("cuda", g.device)
-            with torch.cuda.device(where):
-                g.scatter_permeability_device(torch.from_numpy(ids).to(where), torch.from_numpy(K9).to(where))
-                torch.cuda.current_stream(where).synchronize()
-            g._perm_key = (_table_key(perm_row), _table_key(dmag_row))   # the rows ARE the resident table: nothing to upload
+        if in_step and _follow_on_device(g, g.scatter_permeability_device, ids, K9):
+            g.host_permeability_resident(_perm_keys(perm_row, dmag_row))   # the rows ARE the resident table: nothing to upload
         else:
-            g._perm_from_device = False   # the host rows are the newer ones now: the next call that reads the tables uploads them
+            g.host_permeability_edited()
 
     def fetch_permeability(self):
         """The permeability resident on the device read back into the `permeability` and `diff_mag` rows of `cells_data` (after
@@ -603,8 +495,7 @@ class Interpolator:
         if got is not None:
             perm_row[:] = got[0].reshape(-1)
             dmag_row[:] = got[1]
-            g._perm_key = (_table_key(perm_row), _table_key(dmag_row))
-            g._perm_from_device = False
+            g.host_permeability_resident(_perm_keys(perm_row, dmag_row))
         return np.array(perm_row).reshape(g.n_elems, 3, 3)
 
     @property
@@ -619,8 +510,7 @@ class Interpolator:
     # ---- changing boundary conditions ----------------------------------------------------------------
     def _flag_row(self, variable):
         """The `neumann_flag_<variable>` row of points_data as _upload_fields reads it (a view: same address, same hash)."""
-        if not self.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
+        self._check_call()
         name = "neumann_flag_" + str(variable)
         if name not in self.variable_to_index["points"]:
             raise ValueError(f"Variable '{name}' not found in points data.")
@@ -660,44 +550,21 @@ class Interpolator:
         Host and device arguments cannot be mixed (TypeError)."""
         row = self._flag_row(variable)
         g = self.grid
-        P = int(g.n_points)
-        is_torch = lambda a: type(a).__module__.split(".")[0] == "torch"
-        on_gpu = lambda a: is_torch(a) and getattr(a, "is_cuda", False)
-        if on_gpu(flags) or on_gpu(nodes):
-            import torch
-            where = torch.device("cuda", self.device)
-            if not on_gpu(flags):
-                raise TypeError(f"flags must be a torch.Tensor on {where} when nodes is, not " +
-                                (f"one on {flags.device}" if is_torch(flags) else type(flags).__name__))
-            if nodes is not None and not on_gpu(nodes):
-                raise TypeError(f"nodes must be a torch.Tensor on {where} when flags is, not " +
-                                (f"one on {nodes.device}" if is_torch(nodes) else type(nodes).__name__))
-            if flags.dtype not in (torch.float64, torch.bool, torch.uint8):
-                raise TypeError(f"flags must be float64, bool or uint8, not {flags.dtype} (no silent cast)")
-            if flags.device != where:
-                raise ValueError(f"flags must be on {where}, not {flags.device}")
+        P = len(row)                      # (n_points)
+        if A.on_gpu(flags) or A.on_gpu(nodes):
+            A.require_device_tensor(flags, "flags", self.device, "nodes")
+            if nodes is not None:
+                A.require_device_tensor(nodes, "nodes", self.device, "flags")
+            Fd = A.device_tensor(flags, "flags", self.device, "nodes", also=("bool", "uint8"))
             if nodes is None:
-                if tuple(flags.shape) != (P,):
-                    raise ValueError(f"flags must have shape {(P,)}, not {tuple(flags.shape)}")
+                A.check_shape(Fd.shape, "flags", ((P,),))
                 if g.device < 0:
                     g.to_device(self.device)
-                # the host row is hashed at the FIRST device update behind a host upload, not at every step of a time loop: an in-place
-                # edit of the row made between two device updates is still found by the next call that reads the tables
-                hashed = g._flags_from_device and g._fields_variable == variable and g._flags_key is not None
-                g.load_flags_device(flags.detach().contiguous())
-                g._fields_variable = variable          # only the nodes whose bit differs were marked: no mark_all_dirty()
-                if not hashed:
-                    g._flags_key = _table_key(row)
+                g.load_flags_device(Fd)
+                g.flags_from_device(variable, _table_key, row)   # only the nodes whose bit differs were marked: no mark_all_dirty()
                 return
-            if nodes.dtype not in (torch.int32, torch.int64):
-                raise TypeError(f"nodes must be int32 or int64, not {nodes.dtype} (no silent cast)")
-            if nodes.device != where:
-                raise ValueError(f"nodes must be on {where}, not {nodes.device}")
-            if nodes.dim() != 1:
-                raise ValueError(f"nodes must have shape (m,), not {tuple(nodes.shape)}")
-            m = int(nodes.shape[0])
-            if tuple(flags.shape) != (m,):
-                raise ValueError(f"flags must have shape {(m,)}, not {tuple(flags.shape)}")
+            m = A.device_ids(nodes, "nodes", self.device)
+            A.check_shape(Fd.shape, "flags", ((m,),))
             if g.device >= 0 and g._fields_variable is not None and g._fields_variable != variable:
                 raise ValueError(f"the flags resident on the device are those of '{g._fields_variable}', not of '{variable}': a subset of "
                                  "nodes can only be patched into its own variable (pass the whole array to switch)")
@@ -707,60 +574,27 @@ class Interpolator:
                 g.to_device(self.device)
             if g._fields_variable is None:
                 # nothing is resident on this device copy yet: the host row goes over first (through the device path: the same bits)
-                g.load_flags_device(torch.from_numpy(np.ascontiguousarray(row, dtype=DTYPE_F)).to(where))
-                g._fields_variable = variable
-            hashed = g._flags_from_device and g._flags_key is not None
-            g.scatter_flags_device(nodes.detach().contiguous(), flags.detach().contiguous())
-            if not hashed:
-                g._flags_key = _table_key(row)
+                import torch
+                g.load_flags_device(torch.from_numpy(np.ascontiguousarray(row, dtype=DTYPE_F)).to(f"cuda:{self.device}"))
+            g.scatter_flags_device(nodes.detach().contiguous(), Fd)
+            g.flags_from_device(variable, _table_key, row)
             return
-        if is_torch(flags):
-            flags = flags.detach().numpy()
-        if nodes is not None and is_torch(nodes):
-            nodes = nodes.detach().numpy()
-        try:
-            F = np.asarray(flags)
-            if F.dtype.kind not in "fiub" or (F.dtype.kind == "f" and F.dtype != DTYPE_F):
-                raise TypeError(f"flags must be float64, integers or bool, not {F.dtype} (no silent cast)")
-            F = np.ascontiguousarray(F, dtype=DTYPE_F)
-        except ValueError as e:
-            raise ValueError(f"flags cannot be converted to float64: {e}") from e
-        ids = None
-        if nodes is not None:
-            ids = np.asarray(nodes)
-            if ids.dtype.kind not in "iu" and ids.size:
-                raise TypeError(f"nodes must be integers, not {ids.dtype} (no silent cast)")
-            if ids.ndim != 1:
-                raise ValueError(f"nodes must have shape (m,), not {ids.shape}")
-            ids = np.ascontiguousarray(ids, dtype=np.int64)
-            bad = (ids < 0) | (ids >= P)
-            if bad.any():
-                raise ValueError(f"nodes must lie in [0, {P}): {int(bad.sum())} of {len(ids)} do not (the first: {int(ids[bad][0])})")
-        shape = (P,) if ids is None else (len(ids),)
-        if F.shape != shape:
-            raise ValueError(f"flags must have shape {shape}, not {F.shape}")
+        F = A.host_float64(A.to_host(flags), "flags", numbers_only=True)
+        ids = None if nodes is None else A.host_ids(A.to_host(nodes), "nodes", P, empty_of_any_dtype=True)
+        A.check_shape(F.shape, "flags", ((P,) if ids is None else (len(ids),),))
         if F.size == 0:
             return
         if ids is None:
             row[:] = F
         else:
             row[ids] = F                  # duplicate ids with different values: numpy keeps the last, the device an unspecified one
-        # is what is resident this variable's host row (not a newer device copy, not another variable's)?  Then the device follows
-        in_step = g.device >= 0 and g._fields_variable == variable and not g._flags_from_device
-        if in_step:
-            try:
-                import torch
-            except ImportError:
-                in_step = False
-        if in_step:
-            where = torch.device("cuda", g.device)
-            with torch.cuda.device(where):
-                if ids is None:
-                    g.load_flags_device(torch.from_numpy(F).to(where))
-                else:
-                    g.scatter_flags_device(torch.from_numpy(ids).to(where), torch.from_numpy(F).to(where))
-                torch.cuda.current_stream(where).synchronize()
-            g._flags_from_device = False  # the row IS what is resident
+        # is what is resident this variable's host row (not a newer device copy, not another variable's)?  Then the device follows, and
+        # the row still IS what is resident: nothing to record
+        if g.device >= 0 and g._fields_variable == variable and not g._flags_from_device:
+            if ids is None:
+                _follow_on_device(g, g.load_flags_device, F)
+            else:
+                _follow_on_device(g, g.scatter_flags_device, ids, F)
 
     def fetch_neumann_flags(self, variable):
         """The Neumann bits resident on the device read back into the `neumann_flag_<variable>` row of `points_data` as 0.0 / 1.0 (after
@@ -775,7 +609,7 @@ class Interpolator:
             got = g.fetch_flags()
             if got is not None:
                 row[:] = got
-                g._flags_from_device, g._flags_key = False, None
+                g.flags_fetched()
         return np.array(row)
 
     @property
@@ -915,16 +749,9 @@ class Interpolator:
 
     # ---- interpolate, interpolator.pyx:549-629 ---------------------------------------------------
     def interpolate(self, variable, method, target_points=np.array([], dtype=DTYPE_I)):
-        if not self.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
-        if method not in self.supported_methods:
-            raise ValueError(f"Method '{method}' not supported. Supported methods are: "
-                             f"{list(self.supported_methods.keys())}")
+        self._check_call(method, variable)
         target_points = np.asarray(target_points, dtype=DTYPE_I)
         every_node = len(target_points) == 0    # interpolator.pyx:557-558: an empty list means all nodes
-        if variable not in self.variable_to_index["cells"]:
-            raise ValueError(f"Variable '{variable}' not found in cells data. "
-                             "Point -> Cell interpolation not supported yet.")
         if self.cells_data_dimensions[self.variable_to_index["cells"][variable]] > 1:
             raise ValueError(f"Variable '{variable}' has more than one dimension. Vector data not supported yet.")
         self._log(f"Interpolating variable '{variable}' using method '{method}'")
@@ -948,24 +775,24 @@ class Interpolator:
             # Speculation is adaptive (advisor, round 3): a caller who edits K before every call (nonlinear / time loops) would pay a
             # wasted run each time -- after a stale check the next calls hash first, and speculation comes back once a call has
             # found the resident table still current.
-            speculate = not getattr(g, "_perm_edited_last_call", False)
-            key_before = getattr(g, "_perm_key", None)
-            check = _upload_fields(g, method, self.cells_data, self.points_data, self.variable_to_index, variable, speculate=speculate)
+            key_before = g._perm_key
+            check = _upload_fields(g, method, self.cells_data, self.points_data, self.variable_to_index, variable,
+                                   speculate=not g._perm_edited_last_call)
             try:
                 indptr, indices, data, nws = _native_interpolate(g, method)
             except BaseException:
                 if check is not None:
                     check.join()                         # never leave the hash thread behind
                 raise
-            if check is not None and check.stale():      # the caller's permeability is not the resident one: again, with it
-                del indptr, indices, data, nws
-                check.upload(check.flag)
-                indptr, indices, data, nws = _native_interpolate(g, method)
-                g._perm_edited_last_call = True
-            elif check is not None:
-                g._perm_edited_last_call = False
-            else:                                        # hashed first: was the table edited since the last call?
-                g._perm_edited_last_call = key_before is not None and getattr(g, "_perm_key", None) != key_before
+            if check is None:                            # hashed first: was the table edited since the last call?
+                edited = key_before is not None and g._perm_key != key_before
+            else:
+                edited = check.stale()
+                if edited:                               # the caller's permeability is not the resident one: again, with it
+                    del indptr, indices, data, nws
+                    check.upload(check.flag)
+                    indptr, indices, data, nws = _native_interpolate(g, method)
+            g.permeability_edit_seen(edited)
             self._log(f"Interpolation done in {time.time() - t0:.2f} seconds")
             return _wrap_csr(data, indices, indptr, (P, E)), nws
         csr, nws = _run_weights(g, method, self.cells_data, self.points_data, self.variable_to_index, variable,
@@ -991,14 +818,7 @@ class Interpolator:
         the cell variable `variable` itself -- or k of them as (k, n_elems): the weights (which depend on `variable`
         only through its Neumann flags) are computed once and applied to every field.  Returns (node_values,
         neumann_ws), node_values shaped like `values` with n_points in place of n_elems; Dirichlet rows are 0."""
-        if not self.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
-        if method not in self.supported_methods:
-            raise ValueError(f"Method '{method}' not supported. Supported methods are: "
-                             f"{list(self.supported_methods.keys())}")
-        if variable not in self.variable_to_index["cells"]:
-            raise ValueError(f"Variable '{variable}' not found in cells data. "
-                             "Point -> Cell interpolation not supported yet.")
+        self._check_call(method, variable)
         g = self.grid
         if g.device < 0:
             g.to_device(self.device)
@@ -1019,14 +839,7 @@ class Interpolator:
         returns (the `+ neumann_ws[row]` of interpolator.pyx:618 included), on the device.  `values`: one node array (n_points,)
         or k of them as (k, n_points); returns cell values shaped like `values` with n_elems in place of n_points.  Each cell
         sums its nodes' terms in ascending node id (scipy's order), without atomics: results are bitwise reproducible."""
-        if not self.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
-        if method not in self.supported_methods:
-            raise ValueError(f"Method '{method}' not supported. Supported methods are: "
-                             f"{list(self.supported_methods.keys())}")
-        if variable not in self.variable_to_index["cells"]:
-            raise ValueError(f"Variable '{variable}' not found in cells data. "
-                             "Point -> Cell interpolation not supported yet.")
+        self._check_call(method, variable)
         g = self.grid
         v = np.ascontiguousarray(values, dtype=DTYPE_F)
         if v.shape != (g.n_points,) and not (v.ndim == 2 and v.shape[0] >= 1 and v.shape[1] == g.n_points):
@@ -1046,11 +859,7 @@ class Interpolator:
         with respect to the resident permeability table, the chain through diff_mag = (1 - 3 / tr K)^2 folded in.  On the device, the
         sibling of apply_transpose(): host-synchronous, numpy in and out; deterministic.  Nodes whose row is zero (Dirichlet nodes)
         contribute nothing; the Neumann values and the coordinates are not differentiated."""
-        if not self.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
-        if variable not in self.variable_to_index["cells"]:
-            raise ValueError(f"Variable '{variable}' not found in cells data. "
-                             "Point -> Cell interpolation not supported yet.")
+        self._check_call(variable=variable)
         self._perm_rows()   # (ValueError without a permeability)
         g = self.grid
         v = np.ascontiguousarray(node_values, dtype=DTYPE_F)
@@ -1119,11 +928,7 @@ class DevicePlan:
     grid holds that variable's flags: a plan of the first variable re-uploads its own at its next launch (ensure_current)."""
 
     def __init__(self, interp, variable, method):
-        if not interp.is_grid_initialized:
-            raise ValueError("Grid not initialized. Please load a mesh first.")
-        if method not in interp.supported_methods:
-            raise ValueError(f"Method '{method}' not supported. Supported methods are: "
-                             f"{list(interp.supported_methods.keys())}")
+        interp._check_call(method)
         self.interp = interp
         self.variable = variable
         self.grid = g = interp.grid
@@ -1149,7 +954,7 @@ class DevicePlan:
                        device=self._device, always_perm=True)
 
     def ensure_current(self):
-        if getattr(self.grid, "_fields_variable", None) != self.variable:
+        if self.grid._fields_variable != self.variable:
             self.refresh()
 
     def any_neumann_flag(self):

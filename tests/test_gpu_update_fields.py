@@ -387,6 +387,10 @@ def test_input_errors_on_the_device_path(small):
         I.update_permeability(K, scale=torch.from_numpy(scale))            # a CPU tensor
     with pytest.raises((TypeError, ValueError), match="scale must be"):
         I.update_permeability(K, scale=scale)                               # a numpy array
+    # as found, not as designed: a CPU tensor beside a device K is a ValueError here (the device check refuses it) and a TypeError in the
+    # cells= form (tests/test_gpu_update_local.py)
+    with pytest.raises(ValueError, match="scale must be on cuda:0, not cpu"):
+        I.update_permeability(K, scale=torch.from_numpy(scale))
     with pytest.raises(ValueError, match="shape"):
         I.update_permeability(K[:-1])
     with pytest.raises(ValueError, match="shape"):

@@ -435,6 +435,10 @@ def test_input_errors():
         I.update_permeability(K.cpu(), cells=ids)
     with pytest.raises(TypeError, match="scale must be"):
         I.update_permeability(K, scale=np.ones(5), cells=ids)
+    # as found, not as designed: a CPU tensor beside device cells is a TypeError here and a ValueError in the whole-table form
+    # (tests/test_gpu_update_fields.py)
+    with pytest.raises(TypeError, match="scale must be a torch.Tensor on cuda:0 when cells is, not one on cpu"):
+        I.update_permeability(K, scale=scale.cpu(), cells=ids)
     with pytest.raises(TypeError, match="on the host"):
         I.update_permeability(K, cells=np.arange(5))
     with pytest.raises(TypeError, match="on the host"):

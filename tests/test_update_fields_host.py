@@ -173,3 +173,8 @@ def test_python_argument_checks(lib):
     assert np.array_equal(rows(I)[0], before[0]) and np.array_equal(rows(I)[1], before[1]), "a refused call changed the table"
     I.update_permeability(good.tolist())                         # anything numpy converts to float64 without narrowing
     assert np.array_equal(rows(I)[0], good.reshape(-1))
+    # as found, not as designed: a complex K is taken, with numpy's warning, and its imaginary part dropped (update_neumann_flags
+    # refuses complex flags with a TypeError)
+    with pytest.warns(Warning, match="discards the imaginary part"):
+        I.update_permeability(2.0 * good + 1j)
+    assert np.array_equal(rows(I)[0], 2.0 * good.reshape(-1))

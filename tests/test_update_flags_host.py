@@ -193,6 +193,9 @@ def test_validation_errors_leave_the_row_unchanged(lib):
         I.update_neumann_flags("u", ok.astype(np.float32), nodes=[0, 1, 2])
     with pytest.raises(ValueError):
         I.update_neumann_flags("u", [[1.0, 2.0], [1.0]])
+    # as found, not as designed: an empty LIST of ids (numpy makes `[]` float64) is taken here and changes nothing; update_points and
+    # update_permeability refuse it with a TypeError
+    assert I.update_neumann_flags("u", [], nodes=[]) is None
     assert np.array_equal(np.asarray(I.points_data), before), "a refused call changed the table"
 
 

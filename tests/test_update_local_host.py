@@ -90,6 +90,9 @@ def test_host_id_validation_and_argument_checks(lib):
         I.update_permeability(K.astype(np.float32), cells=[0, 1, 2])
     with pytest.raises(TypeError, match="float64"):
         I.update_permeability(K, scale=np.ones(3, dtype=np.float32), cells=[0, 1, 2])
+    # as found, not as designed: an empty LIST of ids is refused (numpy makes `[]` float64); update_neumann_flags takes it
+    with pytest.raises(TypeError, match="cells must be integers, not float64"):
+        I.update_permeability(np.zeros((0, 9)), cells=[])
     assert np.array_equal(rows(I)[0], before[0]) and np.array_equal(rows(I)[1], before[1]), "a refused call changed the table"
     import ninpol_amd
     with pytest.raises(ValueError, match="Grid not initialized. Please load a mesh first."):

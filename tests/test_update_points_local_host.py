@@ -181,6 +181,9 @@ def test_host_id_validation_and_argument_checks(lib):
             I.update_points(bad_rows, nodes=[0, 1, 2])
     with pytest.raises(TypeError, match="float64"):
         I.update_points(rows.astype(np.float32), nodes=[0, 1, 2])
+    # as found, not as designed: an empty LIST of ids is refused (numpy makes `[]` float64); update_neumann_flags takes it
+    with pytest.raises(TypeError, match="nodes must be integers, not float64"):
+        I.update_points(np.zeros((0, 3)), nodes=[])
     for k in GEOMETRY:
         assert np.array_equal(getattr(I.grid, k), before[k]), ("a refused call changed the grid", k)
     assert np.array_equal(I.points_coords, X0)
