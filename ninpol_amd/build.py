@@ -51,7 +51,12 @@ UNITS = [
     ("fields_scatter.hip", "hipcc", ["-ffp-contract=off"]),
     # Neumann flags from device memory: integer work on bytes, one float64 -> integer cast; nothing to contract
     ("flags_update.hip", "hipcc", []),
-    ("abi.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    # the C ABI's host code by area (abi_internal.hpp is what the five share); only abi_plan.hip has a kernel, the locality keys
+    ("abi_grid.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_plan.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_update.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_csr.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_apply.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),
 ]

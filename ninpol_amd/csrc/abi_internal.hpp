@@ -1,0 +1,170 @@
+// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply.hip;
+// exchange.hip takes the error setter): the grid behind the handle, the text of nin_last_error(), the preconditions of the entry
+// points, device memory owned by the grid or by one call, and the functions of one unit that another calls.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "../../include/ninpol_amd.h"
+#include "device_grid.hpp"
+#include "grid_host.hpp"
+#include "launch.hpp"
+
+struct nin_grid {
+    nin::HostGrid h;
+    nin::DeviceGrid d;
+    std::vector<uint8_t> node_class;  // GLS size class of every node (host copy, for target subsets)
+    int coords_dim = 3;
+};
+
+#pragma GCC visibility push(hidden)   // between the library's own units: none of this is a dynamic symbol
+namespace nin {
+
+// sets what nin_last_error() returns (per thread) and hands `code` back (abi_grid.hip)
+int fail(int code, const char *fmt, ...);
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return nin::fail(NIN_EHIP, "%s: %s", #expr, hipGetErrorString(e_));  \
+    } while (0)
+
+// ---- preconditions ---------------------------------------------------------------------------------------------------------------
+// The grid is on a device, with its launch plan; NIN_ENODEVICE and "grid is not on a device" + hint otherwise.  plan = false: a grid
+// built on the device that nin_grid_to_device has not adopted yet passes too -- the form four host-side entry points have always
+// had (nin_weights_host, nin_csr_compact_host, nin_interpolate_csr_host, nin_apply_fields_host); what they call refuses such a grid.
+constexpr const char *kHintToDevice = " (call nin_grid_to_device first)";
+constexpr const char *kHintWeights = ": the weight kernels are HIP only";
+constexpr const char *kHintKernels = ": the kernels are HIP only";
+int on_device(const nin_grid *g, const char *hint, bool plan = true);
+// a weight launch can go: Neumann flags resident, method known, GLS has its permeability and (size) no system beyond the scratch kernel
+int weights_ready(const DeviceGrid &d, int method, bool size = true);
+
+// ---- device memory ---------------------------------------------------------------------------------------------------------------
+template <class T>
+int dev_alloc(DeviceGrid &d, T **ptr, size_t count) {
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(NIN_ENOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
+    d.allocs.push_back(p);
+    *ptr = static_cast<T *>(p);
+    return 0;
+}
+
+template <class T>
+int dev_upload(DeviceGrid &d, const T **ptr, const std::vector<T> &src) {
+    T *p = nullptr;
+    int rc = dev_alloc(d, &p, src.size());
+    if (rc) return rc;
+    if (!src.empty()) HIP_TRY(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    *ptr = p;
+    return 0;
+}
+
+// a buffer of d.allocs given back before the grid goes (hipFree waits for the device); the pointer is cleared
+template <class T>
+void dev_release(DeviceGrid &d, T *&p) {
+    if (!p) return;
+    auto it = std::find(d.allocs.begin(), d.allocs.end(), (void *)p);
+    if (it != d.allocs.end()) d.allocs.erase(it);
+    (void)hipFree((void *)p);
+    p = nullptr;
+}
+
+// a scratch buffer of the grid with room for `count` elements: kept while it is large enough
+template <class T>
+int grow(DeviceGrid &d, T **buf, size_t *have, size_t count) {
+    if (*buf && *have >= count) return NIN_OK;
+    dev_release(d, *buf);
+    *have = 0;
+    const int rc = dev_alloc(d, buf, count);
+    if (!rc) *have = count;
+    return rc;
+}
+
+// A hipMalloc'd buffer that lives as long as one call: freed when the owner goes out of scope (hipFree waits for the device).  It
+// stands where the plain pointer stood -- converts to it, and & gives the pointer's address -- so an allocation reads, and HIP_TRY
+// words its error, as before.
+template <class T>
+struct DevTmp {
+    T *p = nullptr;
+    DevTmp() = default;
+    DevTmp(DevTmp &&o) noexcept : p(o.p) { o.p = nullptr; }
+    ~DevTmp() { if (p) (void)hipFree(p); }
+    operator T *() const { return p; }
+    T **operator&() { return &p; }
+};
+
+// A stream (non-blocking) or an event (no timing) of the grid, made by the first call that needs it and never earlier: the streams a
+// process has open share its hardware queues
+inline int lazy_stream(void *&slot) {
+    if (slot) return NIN_OK;
+    hipStream_t s;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    slot = s;
+    return NIN_OK;
+}
+inline int lazy_event(void *&slot) {
+    if (slot) return NIN_OK;
+    hipEvent_t e;
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    slot = e;
+    return NIN_OK;
+}
+
+// NIN_TIMING=1: host-side laps of one call on stderr as "[tag] name ms", the name padded to `width`; a lap first waits for the
+// streams it is given, so that it times the work it names
+struct Laps {
+    const char *tag;
+    int width;
+    bool on = getenv("NIN_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char *what, std::initializer_list<hipStream_t> wait_for = {}) {
+        if (!on) return;
+        for (hipStream_t s : wait_for) (void)hipStreamSynchronize(s);
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[%s] %-*s %.3f ms\n", tag, width, what, std::chrono::duration<double, std::milli>(now - t).count());
+        t = now;
+    }
+};
+
+// NIN_TIMING=1: HIP events on the launch's stream around its three phases -- compaction + read-back, descriptor kernels, weight
+// kernels -- and one line on stderr; the call then waits for its kernels (tools/time_update_fields.py --local reads the lines)
+struct DirtyLaps {
+    bool on = getenv("NIN_TIMING") != nullptr;
+    hipStream_t stream;
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit DirtyLaps(hipStream_t s) : stream(s) {}
+    ~DirtyLaps() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    void mark(int i) { if (on && !e[i] && hipEventCreate(&e[i]) == hipSuccess) (void)hipEventRecord(e[i], stream); }
+    void report(int64_t n) {
+        if (!on || !e[0] || !e[1] || !e[2] || !e[3] || hipEventSynchronize(e[3]) != hipSuccess) return;
+        float ms[3] = {0.f, 0.f, 0.f};
+        for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms[i], e[i], e[i + 1]);
+        fprintf(stderr, "[nin_dirty] nodes %lld compact+readback %.4f descriptors %.4f weights %.4f ms\n", (long long)n, ms[0], ms[1], ms[2]);
+    }
+};
+
+// ---- one unit's functions that another calls ---------------------------------------------------------------------------------------
+// abi_plan.hip: the launch plan of nin_grid_to_device; the walk over its kernels (work counters zeroed by the caller); the plan's
+// kernels on lists of their own nodes
+int build_gls_plan(nin_grid *g);
+int gls_only();
+int gls_side_begin(DeviceGrid &d, int piece, int add_neumann, double *out, double *nws, hipStream_t stream);
+int gls_main(DeviceGrid &d, int piece, bool cube, int only, int add_neumann, double *out, double *nws, hipStream_t stream);
+int launch_lists(DeviceGrid &d, int method, const int32_t *lists, const int32_t *off, uint32_t *desc, const size_t *desc_first,
+                 int add_neumann, double *out, double *nws, hipStream_t stream, DirtyLaps *laps);
+// abi_update.hip: the host's copy of the resident flag bytes (flag_staging), brought up to date
+int fetch_flag_bytes(nin_grid *g);
+// abi_apply.hip: the adjoint's bins, contribution buffer and scratch slots given back
+void release_adjoint_state(DeviceGrid &d);
+
+}  // namespace nin
+#pragma GCC visibility pop

@@ -63,7 +63,7 @@ struct DeviceGrid {
     bool prebuilt = false;  // arrays came from build_grid_on_device(): nin_grid_to_device adopts them, no upload
     std::vector<void *> allocs;  // everything hipMalloc'd, freed together
 
-    // interpolate()'s pipeline (abi.hip, interpolate_chunked): the node range is cut into kE2eChunks pieces at multiples of 64 nodes
+    // interpolate()'s pipeline (abi_csr.hip, interpolate_chunked): the node range is cut into kE2eChunks pieces at multiples of 64 nodes
     static constexpr int kE2eChunks = 4;
     int32_t chunk_node[kE2eChunks + 1] = {0, 0, 0, 0, 0};
     bool chunkable = false;
@@ -152,7 +152,7 @@ struct DeviceGrid {
     void *ev_weights = nullptr, *ev_scan = nullptr;   // hipEvent_t: weights written / row pointers scanned
     // The long pole of a GLS launch plan: the few nodes of the global-scratch class (more cells than any in-register / in-LDS kernel
     // holds: ~0.03 % of a Delaunay mesh) take ~2 ms EACH on a wavefront of their own.  They start first, on a stream of their own,
-    // and run under the other kernels (abi.hip: gls_side_begin / gls_side_end).
+    // and run under the other kernels (abi_plan.hip: gls_side_begin / gls_side_end).
     void *side_stream = nullptr, *ev_fork = nullptr, *ev_join = nullptr;
     bool side_pending = false;
     bool gls_too_large = false;     // some node's system has more rows than the scratch kernel handles (1024)

@@ -18,11 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ninpol_amd.h"
-
-namespace nin {
-int abi_fail(int code, const char *fmt, ...);   // abi.hip: sets nin_last_error()
-}
+#include "abi_internal.hpp"   // nin::fail: sets nin_last_error()
 
 struct nin_exchange {
     int device = -1, rank = 0, world = 1;
@@ -38,23 +34,23 @@ struct nin_exchange {
 #define X_TRY(expr)                                                                                         \
     do {                                                                                                    \
         hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return nin::abi_fail(NIN_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
+        if (e_ != hipSuccess) return nin::fail(NIN_EHIP, "%s: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
 
 extern "C" {
 
 int nin_exchange_create(int device, int rank, int world, size_t slot_bytes, nin_exchange **out) {
-    if (!out || world < 1 || rank < 0 || rank >= world || slot_bytes == 0) return nin::abi_fail(NIN_EINVAL, "bad argument");
+    if (!out || world < 1 || rank < 0 || rank >= world || slot_bytes == 0) return nin::fail(NIN_EINVAL, "bad argument");
     *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return nin::abi_fail(NIN_ENODEVICE, "no HIP device %d", device);
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return nin::fail(NIN_ENODEVICE, "no HIP device %d", device);
     X_TRY(hipSetDevice(device));
     auto *x = new nin_exchange();
     x->device = device; x->rank = rank; x->world = world;
     x->slot_bytes = (slot_bytes + 255) & ~(size_t)255;
     if (hipMalloc((void **)&x->buffer, x->slot_bytes * world) != hipSuccess) {
         delete x;
-        return nin::abi_fail(NIN_ENOMEM, "hipMalloc of the gathered buffer (%zu bytes)", slot_bytes * world);
+        return nin::fail(NIN_ENOMEM, "hipMalloc of the gathered buffer (%zu bytes)", slot_bytes * world);
     }
     x->remote.assign(world, nullptr);
     x->remote[rank] = x->buffer;
@@ -64,12 +60,12 @@ int nin_exchange_create(int device, int rank, int world, size_t slot_bytes, nin_
         if (hipStreamCreateWithFlags(&x->streams[p], hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&x->done[p], hipEventDisableTiming) != hipSuccess) {
             nin_exchange_destroy(x);
-            return nin::abi_fail(NIN_EHIP, "stream / event creation failed");
+            return nin::fail(NIN_EHIP, "stream / event creation failed");
         }
     }
     if (hipEventCreateWithFlags(&x->ready, hipEventDisableTiming) != hipSuccess) {
         nin_exchange_destroy(x);
-        return nin::abi_fail(NIN_EHIP, "event creation failed");
+        return nin::fail(NIN_EHIP, "event creation failed");
     }
     x->connected = world == 1;
     *out = x;
@@ -90,7 +86,7 @@ void nin_exchange_destroy(nin_exchange *x) {
 }
 
 int nin_exchange_handle(nin_exchange *x, void *handle64) {
-    if (!x || !handle64) return nin::abi_fail(NIN_EINVAL, "NULL argument");
+    if (!x || !handle64) return nin::fail(NIN_EINVAL, "NULL argument");
     static_assert(sizeof(hipIpcMemHandle_t) == NIN_EXCHANGE_HANDLE_BYTES, "handle size");
     X_TRY(hipSetDevice(x->device));
     hipIpcMemHandle_t h;
@@ -100,7 +96,7 @@ int nin_exchange_handle(nin_exchange *x, void *handle64) {
 }
 
 int nin_exchange_connect(nin_exchange *x, const void *all_handles) {
-    if (!x || (!all_handles && x->world > 1)) return nin::abi_fail(NIN_EINVAL, "NULL argument");
+    if (!x || (!all_handles && x->world > 1)) return nin::fail(NIN_EINVAL, "NULL argument");
     if (x->connected) return NIN_OK;
     X_TRY(hipSetDevice(x->device));
     const char *hs = static_cast<const char *>(all_handles);
@@ -110,7 +106,7 @@ int nin_exchange_connect(nin_exchange *x, const void *all_handles) {
         std::memcpy(&h, hs + (size_t)p * NIN_EXCHANGE_HANDLE_BYTES, sizeof h);
         void *ptr = nullptr;
         const hipError_t e = hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess);
-        if (e != hipSuccess) return nin::abi_fail(NIN_EHIP, "hipIpcOpenMemHandle of rank %d's buffer: %s", p, hipGetErrorString(e));
+        if (e != hipSuccess) return nin::fail(NIN_EHIP, "hipIpcOpenMemHandle of rank %d's buffer: %s", p, hipGetErrorString(e));
         x->remote[p] = static_cast<char *>(ptr);
     }
     x->connected = true;
@@ -118,9 +114,9 @@ int nin_exchange_connect(nin_exchange *x, const void *all_handles) {
 }
 
 int nin_exchange_push(nin_exchange *x, const void *dev_src, size_t bytes, size_t offset, void *stream_) {
-    if (!x || !dev_src) return nin::abi_fail(NIN_EINVAL, "NULL argument");
-    if (!x->connected) return nin::abi_fail(NIN_ESTATE, "nin_exchange_connect has not been called");
-    if (offset + bytes > x->slot_bytes) return nin::abi_fail(NIN_ERANGE, "%zu bytes at offset %zu do not fit the slot (%zu)", bytes, offset, x->slot_bytes);
+    if (!x || !dev_src) return nin::fail(NIN_EINVAL, "NULL argument");
+    if (!x->connected) return nin::fail(NIN_ESTATE, "nin_exchange_connect has not been called");
+    if (offset + bytes > x->slot_bytes) return nin::fail(NIN_ERANGE, "%zu bytes at offset %zu do not fit the slot (%zu)", bytes, offset, x->slot_bytes);
     if (bytes == 0) return NIN_OK;
     X_TRY(hipSetDevice(x->device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -136,7 +132,7 @@ int nin_exchange_push(nin_exchange *x, const void *dev_src, size_t bytes, size_t
 }
 
 int nin_exchange_wait_sent(nin_exchange *x, void *stream_, int host_wait) {
-    if (!x) return nin::abi_fail(NIN_EINVAL, "NULL argument");
+    if (!x) return nin::fail(NIN_EINVAL, "NULL argument");
     X_TRY(hipSetDevice(x->device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     for (int p = 0; p < x->world; ++p) {

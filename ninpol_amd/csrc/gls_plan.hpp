@@ -3,7 +3,7 @@
 // A node is given to exactly one GLS kernel when the grid goes to the device (grid_device.hip: k_classify writes one class byte per
 // node).  Everything the host needs to route a node -- the kernel's public index, its launcher family, the class byte, the size of its
 // descriptors, its work counter -- is one row of gls_plan_row() below.  A new kernel costs one enumerator, one row, one case in
-// abi.hip's launch_plan_kernel and, if it has descriptors, one in launch_plan_desc.
+// abi_plan.hip's launch_plan_kernel and, if it has descriptors, one in launch_plan_desc.
 #pragma once
 #include <cstdint>
 
@@ -36,7 +36,7 @@ enum GlsKernel : int {
 }  // namespace gk
 using gk::GlsKernel;
 
-// which launcher takes the list (abi.hip: launch_plan_kernel / launch_plan_desc switch over this)
+// which launcher takes the list (abi_plan.hip: launch_plan_kernel / launch_plan_desc switch over this)
 enum class GlsFamily : uint8_t {
     block,    // kernels_gls_block.hip: one node per workgroup, system in LDS; sub = the LDS class
     scratch,  // kernels_gls.hip: the wave kernel on global-memory scratch
@@ -78,7 +78,7 @@ struct GlsPlanRow {
     int16_t fdq_word;     // the descriptor word whose low 24 bits are (F, D, free faces), for nin_gls_plan_flops; -1: none
     int16_t counter;      // the kernel's work counter: an offset into gls_queue; -1: the kernel takes none
 };
-// (the descriptor sizes are mfw_desc / mfx_desc / mfg_desc.hpp's kM*DescWords: those headers include this one, abi.hip asserts the match)
+// (the descriptor sizes are mfw_desc / mfx_desc / mfg_desc.hpp's kM*DescWords: those headers include this one, abi_plan.hip asserts the match)
 constexpr int kGlsDescHex8 = 4, kGlsDescQuad4 = 2, kGlsDescMfw = 40, kGlsDescMfx = 56, kGlsDescMfg = 124;
 
 NIN_HD constexpr GlsPlanRow gls_plan_row(int k) {

@@ -22,7 +22,7 @@
 
 namespace nin {
 
-constexpr int kHex8DescWords = 4;   // descriptor words per list entry (gls_plan.hpp holds the same figure; abi.hip asserts the match)
+constexpr int kHex8DescWords = 4;   // descriptor words per list entry (gls_plan.hpp holds the same figure; abi_plan.hip asserts the match)
 
 #ifdef __HIPCC__
 __device__ inline bool hex8_descriptor(const GridView &g, int32_t p, int32_t d[kHex8DescWords]) {

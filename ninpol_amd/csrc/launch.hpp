@@ -105,7 +105,7 @@ int launch_apply_fields(const GridView &g, const double *data, const double *u, 
 // x [k][n_elems]; mx_cell = the most nodes of any cell (8 in 3-D, 4 in 2-D)
 int launch_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, int32_t mx_cell,
                            const double *data, const double *v, int32_t k, double *x, hipStream_t stream);
-// building that index (abi.hip sorts the pairs (esup[j], j) by cell in between): dst[i] = i; then cell_ptr from the sorted cells and
+// building that index (abi_apply.hip sorts the pairs (esup[j], j) by cell in between): dst[i] = i; then cell_ptr from the sorted cells and
 // cell_node from the sorted positions
 int launch_iota(int32_t *dst, int32_t n, hipStream_t stream);
 int launch_transpose_index_fill(const GridView &g, const int32_t *sorted_cells, int32_t nnz, int32_t *cell_ptr, const int32_t *cell_pos,

@@ -20,7 +20,7 @@
 
 namespace nin {
 
-constexpr int kQuad4DescWords = 2;   // descriptor words per list entry (gls_plan.hpp holds the same figure; abi.hip asserts the match)
+constexpr int kQuad4DescWords = 2;   // descriptor words per list entry (gls_plan.hpp holds the same figure; abi_plan.hip asserts the match)
 
 #ifdef __HIPCC__
 __device__ inline bool quad4_descriptor(const GridView &g, int32_t p, int32_t d[kQuad4DescWords]) {

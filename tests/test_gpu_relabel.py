@@ -205,7 +205,7 @@ _NODE_ONLY = [("hex20_jitter_neu", ()), ("hex20_jitter_neu", ("NIN_GLS_NO_GROUP"
 @pytest.mark.parametrize("name,switches", _NODE_ONLY, ids=[n + ("_" + "_".join(s) if s else "") for n, s in _NODE_ONLY])
 def test_gpu_node_only_relabelling_is_bit_identical(monkeypatch, name, switches):
     """Renumbering the nodes alone leaves every node's cells, faces and their order as they were (the oracle is bit-identical
-    there: tests/test_relabel.py), and a node's arithmetic does not depend on its neighbours in the list (abi.hip): the LS and
+    there: tests/test_relabel.py), and a node's arithmetic does not depend on its neighbours in the list (abi_plan.hip): the LS and
     GLS tables and neumann_ws of the node-relabelled mesh, rows mapped back, equal those of the original bit for bit -- through
     the cube-node kernel and, with it switched off, the one-wavefront kernel; the mixed mesh; the random cloud (wide kernel,
     tiles in global memory) and unstructured prisms.  IDW to its bar (1e-14).  The launch plan is the same key by key."""

@@ -10,8 +10,12 @@ the first child that fails, faults or times out nothing further is started.
 Meshes (small: a few seconds each): jittered hexahedra, a mixed mesh, wedges and a random-cloud Delaunay mesh; the composite of the nine
 parts of tests/test_gpu_composite.py (between them all 22 plan kernels have nodes); and a random-cloud Delaunay mesh WITH a Neumann plane,
 for which mfx_boundary must have nodes and neumann_ws non-zero entries -- otherwise the boundary-face rows are never computed.
-Routes per mesh: nin_weights_host over all nodes and over a shuffled subset, interpolate() pipelined (NIN_E2E_MIN_NODES=512), apply()
-fused and unfused.  On the composite mesh the all-nodes route runs again under each switch of SWITCHES.
+Routes per mesh: nin_weights_host over all nodes and over a shuffled subset (GLS, IDW and LS), interpolate() pipelined
+(NIN_E2E_MIN_NODES=512), apply() fused and unfused, apply_transpose() with 3 fields, permeability_gradient().  On the meshes of LOCAL a
+scatter of permeability, of points and of Neumann flags (device tensors), each followed by the dirty launch -- weights and neumann_ws
+after each -- and by HostMatrix.update(), whose matrix must in the end be a fresh interpolate()'s in the same child.  On the composite
+mesh the all-nodes route runs again under each switch of SWITCHES (NIN_GLS_NO_SMALL is among them because only without the small-node
+kernels does the one-wavefront block kernel, block1, get nodes on these meshes).
 Exit status 1 if an array or a plan differs, or if one of the plan kernels has no nodes on any mesh.  Needs a GPU; reads nothing
 outside the repository."""
 import json
@@ -22,8 +26,9 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_SECONDS = 240
-SWITCHES = ("NIN_MFW_LANE_COLUMNS", "NIN_MFW_NO_STRIPS", "NIN_MFW_SMALL_STRIPS", "NIN_GLS_MFW_GENERAL", "NIN_GLS_NO_MFX")
+SWITCHES = ("NIN_MFW_LANE_COLUMNS", "NIN_MFW_NO_STRIPS", "NIN_MFW_SMALL_STRIPS", "NIN_GLS_MFW_GENERAL", "NIN_GLS_NO_MFX", "NIN_GLS_NO_SMALL")
 PLANE = (2, 0.0)
+LOCAL = ("mixed", "delaunay_neumann")
 
 
 def _composite(M):
@@ -50,6 +55,46 @@ MESHES = {
 }
 
 
+def local_routes(I, A):
+    """scatter K, points and flags from device tensors; after each the dirty launch into full buffers and the host matrix's update"""
+    import numpy as np
+    import torch
+    from ninpol_amd.interpolator import DevicePlan
+    g = I.grid
+    P, E = int(g.n_points), int(g.n_elems)
+    rng = np.random.default_rng(11)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    plan = DevicePlan(I, "u", "gls")
+    s = torch.cuda.current_stream().cuda_stream
+    hm = plan.host_matrix(s)                                   # a full run; clears the dirty set
+    csr, nws = torch.zeros(plan.nnz, dtype=torch.float64, device="cuda"), torch.zeros(P, dtype=torch.float64, device="cuda")
+    plan.launch(csr.data_ptr(), nws.data_ptr(), s)
+    cells, nodes = rng.choice(E, 5, replace=False), rng.choice(P, 7, replace=False)
+    on_plane = np.flatnonzero(np.asarray(I.points_coords)[:, PLANE[0]] == PLANE[1])
+    flagged = on_plane[:6] if len(on_plane) else nodes
+    row = I.variable_to_index["points"]["neumann_flag_u"]
+    steps = {
+        "perm": lambda: I.update_permeability(dev(rng.uniform(0.5, 2.0, (5, 1, 1)) * np.eye(3)), cells=dev(cells)),
+        "points": lambda: I.update_points(dev(np.asarray(I.points_coords)[nodes] + rng.uniform(-1e-3, 1e-3, (7, 3))), nodes=dev(nodes)),
+        "flags": lambda: I.update_neumann_flags("u", dev(1.0 - np.asarray(I.points_data)[row][flagged]), nodes=dev(flagged)),
+    }
+    for name, step in steps.items():
+        step()
+        A[f"local.{name}.rows"] = np.array(plan.launch_dirty(csr.data_ptr(), nws.data_ptr(), s, clear=False))
+        torch.cuda.current_stream().synchronize()
+        A[f"local.{name}.csr"], A[f"local.{name}.nws"] = csr.cpu().numpy(), nws.cpu().numpy()
+        A[f"local.{name}.hm_rows"] = np.array(hm.update(stream=s))
+        W = hm.W
+        A[f"local.{name}.hm_data"], A[f"local.{name}.hm_indices"], A[f"local.{name}.hm_indptr"] = W.data.copy(), W.indices.copy(), W.indptr.copy()
+        A[f"local.{name}.hm_nws"] = np.array(hm.neumann)
+        assert A[f"local.{name}.rows"] > 0 and A[f"local.{name}.hm_rows"] == A[f"local.{name}.rows"], name
+    torch.cuda.current_stream().synchronize()
+    W, n = I.interpolate("u", "gls")                           # the mesh as it is now, every row
+    for got, ref in ((hm.W.data, W.data), (hm.W.indices, W.indices), (hm.W.indptr, W.indptr), (hm.neumann, n)):
+        assert np.array_equal(np.asarray(got), np.asarray(ref)), "the host matrix is not a fresh interpolate()'s"
+    A["local.interp.data"], A["local.interp.nws"] = W.data, n
+
+
 def child(mesh_name, route_set, out):
     """route_set: 'routes' (all of them) or the name of a switch (the all-nodes route under it)"""
     import numpy as np
@@ -58,6 +103,9 @@ def child(mesh_name, route_set, out):
     else:
         os.environ[route_set] = "1"
     sys.path.insert(0, ROOT)
+    if mesh_name in LOCAL and route_set == "routes":
+        import torch                                           # (torch's own HIP runtime has to open the device before the library's does)
+        torch.cuda.init()
     import ninpol_amd
     from ninpol_amd import mesh as M
     from ninpol_amd.interpolator import _run_weights
@@ -65,18 +113,27 @@ def child(mesh_name, route_set, out):
     I.load_mesh(mesh_obj=MESHES[mesh_name](M))
     P = int(I.grid.n_points)
 
-    def weights(targets):
-        return _run_weights(I.grid, "gls", I.cells_data, I.points_data, I.variable_to_index, "u", np.asarray(targets, dtype=np.int64), False)
+    def weights(targets, meth="gls"):
+        return _run_weights(I.grid, meth, I.cells_data, I.points_data, I.variable_to_index, "u", np.asarray(targets, dtype=np.int64), False)
 
     A = {}
     A["all.csr"], A["all.nws"] = weights(())
     if route_set == "routes":
-        A["targets.csr"], A["targets.nws"] = weights(np.random.default_rng(5).permutation(P)[:max(1, P // 3)])
+        subset = np.random.default_rng(5).permutation(P)[:max(1, P // 3)]
+        A["targets.csr"], A["targets.nws"] = weights(subset)
+        for meth in ("idw", "ls"):
+            A[f"{meth}.all.csr"], A[f"{meth}.all.nws"] = weights((), meth)
+            A[f"{meth}.targets.csr"], A[f"{meth}.targets.nws"] = weights(subset, meth)
         W, A["interp.nws"] = I.interpolate("u", "gls")
         A["interp.data"], A["interp.indices"], A["interp.indptr"] = W.data, W.indices, W.indptr
         A["apply_fused.v"], A["apply_fused.nws"] = I.apply("u", "gls", values=np.random.default_rng(6).random((3, int(I.grid.n_elems))))
         os.environ["NIN_APPLY_NO_FUSION"] = "1"                # (the library reads this switch at every apply call)
         A["apply_unfused.v"], A["apply_unfused.nws"] = I.apply("u", "gls", values=np.random.default_rng(6).random((3, int(I.grid.n_elems))))
+        v3 = np.random.default_rng(8).random((3, P))
+        A["apply_transpose.x"] = I.apply_transpose("u", "gls", v3)
+        A["perm_gradient.g"] = I.permeability_gradient("u", v3)
+        if mesh_name in LOCAL:
+            local_routes(I, A)
     plan = {k: int(v) for k, v in I.grid.gls_plan().items()}
     np.savez(out, __plan__=np.array(json.dumps(plan)), __kernels__=np.array(json.dumps(list(I.grid.PLAN_KERNELS))),
              **{k: np.asarray(v) for k, v in A.items()})
@@ -116,7 +173,8 @@ def main():
             for k in sorted(set(a.files) | set(b.files)):
                 if k.startswith("__"):
                     continue
-                same = k in a.files and k in b.files and np.array_equal(a[k], b[k])
+                same = k in a.files and k in b.files and (np.array_equal(a[k], b[k]) or   # (rows of NaNs, LS on wedges: the same bytes)
+                                                          (a[k].shape == b[k].shape and a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes()))
                 bad += not same
                 lines.append((f"{label}.{k}", str(b[k].shape) if k in b.files else "missing", "equal" if same else "DIFFERENT",
                               int(np.count_nonzero(b[k])) if k in b.files else 0))
