@@ -800,16 +800,16 @@ __global__ __launch_bounds__(256, (DM <= 4 ? 4 : DM <= 8 ? 3 : 2)) void nin_gls_
             }
             wave_lds_sync();
             // ---- lane r builds row r: two cell slots (Ia, Ib) carry three entries each, c = 1 on the cell rows ---------------
-            double b[NP], a_unused[NP], ca_unused = 0.0, cbv = 0.0, dod[3] = {0.0, 0.0, 0.0};
-            {
-                int Ra = -1, Rb = -1;                             // the two cell slots of THIS lane's row
-                double va[3] = {0.0, 0.0, 0.0}, vb[3] = {0.0, 0.0, 0.0};
+            // (twice: before the factorisation, and again for the refinement behind it -- the face records stay in LDS, and the six
+            //  entries need not live in registers across the sweep)
+            auto build_row = [&](int &Ra, int &Rb, double (&va)[3], double (&vb)[3]) {
+                Ra = -1; Rb = -1;                                 // the two cell slots of THIS lane's row
+#pragma unroll
+                for (int t = 0; t < 3; ++t) { va[t] = 0.0; vb[t] = 0.0; }
                 if (lane < ne) {                                   // gls.pyx:269-281
                     const size_t c = (size_t)mycell;
                     va[0] = g.centroids[3 * c + 0] - xv0; va[1] = g.centroids[3 * c + 1] - xv1; va[2] = g.centroids[3 * c + 2] - xv2;
-                    dod[0] = va[0]; dod[1] = va[1]; dod[2] = va[2];
                     Ra = lane;
-                    cbv = 1.0;
                 } else if (lane < ne + 3 * n_if) {                 // gls.pyx:340-356: [-B_a | +B_b], B = [K N; T; tau U]
                     const int x = lane - ne, q = (x * 43) >> 7, k = x - 3 * q;
                     const double *fr = frec + Dm::FREC * q;
@@ -825,6 +825,12 @@ __global__ __launch_bounds__(256, (DM <= 4 ? 4 : DM <= 8 ? 3 : 2)) void nin_gls_
 #pragma unroll
                     for (int t = 0; t < 3; ++t) va[t] = fr[t];
                 }
+            };
+            double b[NP], a_unused[NP], ca_unused = 0.0, cbv = lane < ne ? 1.0 : 0.0;
+            {
+                int Ra, Rb;
+                double va[3], vb[3];
+                build_row(Ra, Rb, va, vb);
 #pragma unroll
                 for (int sl = 0; sl < DM; ++sl) {
 #pragma unroll
@@ -836,12 +842,12 @@ __global__ __launch_bounds__(256, (DM <= 4 ? 4 : DM <= 8 ? 3 : 2)) void nin_gls_
             for (int k = 0; k < ne; ++k) rows_block<NP, false>(a_unused, b, ca_unused, cbv, h, k, nc, lane, Rm, RP);
             if (lane < nc) Rm[lane * RP + nc] = cbv;
             const double cbl = lane >= nc ? cbv : 0.0;
-            const double rr = wave_allsum(cbl * cbl);
+            const double rr = wave_allsum(cbl * cbl);             // |(Q^T c)(nc:m)|^2: > 0 for a system with a solution row
             wave_lds_sync();
-            {
-                const int li = lane < nc ? lane : 0;
-                double ct = lane < nc ? Rm[li * RP + nc] : 0.0;
-                const double ri = fast_rcp(Rm[li * RP + li]);
+            const int li = lane < nc ? lane : 0;
+            const double ri = fast_rcp(Rm[li * RP + li]);
+            // R x = ct by columns, lane = row of R: this lane's entry of x
+            auto solve_upper = [&](double ct) {
                 const double *Rl = Rm + li * RP;
                 int kb = (nc - 1) & ~3;
                 double c4[4], n4[4];
@@ -861,13 +867,53 @@ __global__ __launch_bounds__(256, (DM <= 4 ? 4 : DM <= 8 ? 3 : 2)) void nin_gls_
 #pragma unroll
                     for (int j = 0; j < 4; ++j) c4[j] = n4[j];
                 }
-                if (lane < nc) yb[lane] = ct * ri;
+                return ct * ri;
+            };
+            {
+                const double y = solve_upper(lane < nc ? Rm[li * RP + nc] : 0.0);
+                if (lane < nc) yb[lane] = y;
             }
             wave_lds_sync();
+            // ---- the residual of c on EVERY row, refined once ---------------------------------------------------------------------
+            // The weights are r_i / (r . r), r = c - A y (its cell rows: 1 - d_i . y_i).  Formed from y alone, r inherits y's error
+            // cond(A) eps |A| |y| -- against entries of r that are SMALL where c lies almost in the span of the other columns (a mesh
+            // of size 1e3: |r| ~ 1e-4, four digits cancel in 1 - d . y), and r . r taken from the tail of Q^T c carries the sweep's
+            // error besides.  One step of the corrected semi-normal equations removes both: r' = r - A dy with R^T R dy = A^T r
+            // (the error of r lies in the span of A; dy projects it out again), r . r from r' itself.  Measured against the 80-bit
+            // solution (tests/test_gpu_gls_exact.py): no further from it than the reference's dgels on every case, where the
+            // unrefined form was up to 260 x further.
             {
-                const int ld = lane < ne ? lane : 0;
-                const double ro = 1.0 - fma(dod[2], yb[3 * ld + 2], fma(dod[1], yb[3 * ld + 1], dod[0] * yb[3 * ld]));
-                double w = ro * fast_rcp(rr);
+                int Ra, Rb;
+                double va[3], vb[3];
+                build_row(Ra, Rb, va, vb);
+                auto row_dot = [&](const double *x) {              // this lane's row of A times x[0 .. nc)
+                    const int ia = Ra >= 0 ? 3 * Ra : 0, ib = Rb >= 0 ? 3 * Rb : 0;
+                    const double sa = fma(va[2], x[ia + 2], fma(va[1], x[ia + 1], va[0] * x[ia]));
+                    return fma(vb[2], x[ib + 2], fma(vb[1], x[ib + 1], fma(vb[0], x[ib], sa)));   // (no cell in a slot: its entries are 0)
+                };
+                double res = (lane < ne ? 1.0 : 0.0) - row_dot(yb);
+                double sj = 0.0;                                   // lane j < nc: (A^T r)_j
+                for (int q = 0; q < ne; ++q) {
+                    const bool ina = Ra == q, inb = Rb == q;
+                    const double tot = reduce4((ina ? va[0] : inb ? vb[0] : 0.0) * res, (ina ? va[1] : inb ? vb[1] : 0.0) * res,
+                                               (ina ? va[2] : inb ? vb[2] : 0.0) * res, 0.0);
+                    const double s0 = rl64(tot, kReduce4Lane[0]), s1 = rl64(tot, kReduce4Lane[1]), s2 = rl64(tot, kReduce4Lane[2]);
+                    sj = lane == 3 * q ? s0 : lane == 3 * q + 1 ? s1 : lane == 3 * q + 2 ? s2 : sj;
+                }
+                // R^T z = A^T r by rows of R: lane j subtracts R(k, j) z_k for every k < j
+                double ct = sj;
+                for (int k = 0; k < nc; ++k) {
+                    const double zk = rl64(ct * ri, k);
+                    const double rkj = (lane > k && lane < nc) ? Rm[k * RP + lane] : 0.0;
+                    ct = fma(-zk, rkj, ct);
+                }
+                const double dy = solve_upper(lane < nc ? ct * ri : 0.0);
+                wave_lds_sync();                                   // (every lane has read y)
+                if (lane < nc) yb[lane] = dy;
+                wave_lds_sync();
+                res -= row_dot(yb);
+                const double r2 = wave_allsum(res * res);
+                double w = res * fast_rcp(r2);
                 w = (rr > 0.0 && __builtin_isfinite(w)) ? w : 0.0;
                 if (lane < ne) wbuf[lane] = w;
             }

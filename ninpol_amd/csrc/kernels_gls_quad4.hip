@@ -9,10 +9,14 @@
 // form a 4-cycle (quad4_desc.hpp): two even cells that share no face, two odd ones, each even cell adjacent to BOTH odd cells.
 //   phase 1  lane e eliminates E_e in its front: cell row, 3 + 3 rows of its two internal faces, its Neumann row -- 8 rows x
 //            (3 own | 3 + 3 odd | c); three reflectors, the columns through the reflectors' mutual products as in the
-//            cube-node kernel; 3 rows of R folded into z, u, s, 5 fill rows left;
+//            cube-node kernel; 5 fill rows left (the 3 rows of R are not kept: nothing reads them);
 //   phase 2  14 x 6 over the pair: per lane its 5 fill rows, the cell row and the Neumann row of O_e; row-distributed
 //            Householder, one DPP stage per reduction, pivot rows dealt round-robin;
-//   then     back-substitution, r_i = 1 - d_i . y_i, weights r_i / (r . r); neumann_ws = the LAST cell's weight (gls.pyx:470-472).
+//   then     the residual of c, r = Q [0; tail of Q^T c]: the reflectors of phase 2, then of phase 1, applied backwards to the
+//            tail; weights r_i / (r . r); neumann_ws = the LAST cell's weight (gls.pyx:470-472).  (Until round 14: back-substitution
+//            and r_i = 1 - d_i . y_i -- four digits cancel there where c lies almost in the span of the other columns, a mesh of
+//            size 1e3, and y's error cond(A) eps is what is left: up to 35 x the reference's distance from the 80-bit solution,
+//            tests/test_gpu_gls_exact.py.  The back-application is backward stable and needs no y at all.)
 // Dirichlet nodes of the list (gls.pyx:165-166) get their zero row; a pass without a computed node does nothing else.
 #include <hip/hip_runtime.h>
 
@@ -37,15 +41,14 @@ template <int L>
 __device__ __forceinline__ double pair_bcast(double v) { return dpp_mov<L | (L << 2) | ((2 + L) << 4) | ((2 + L) << 6)>(v); }
 
 // The panel of an 8-row front (rows 0 = cell row, 1-3 / 4-6 = the two internal faces, 7 = the Neumann row): three Householder
-// steps on the own columns; v_k stays in P[k..7][k] (pivot entries included); g[k] the reflectors' scalars; z = R_ee^-T d
-__device__ __forceinline__ void quad_panel(double (&P)[8][3], const double (&d)[3], double (&g)[3], double (&z)[3]) {
-    double rinv[3];
+// steps on the own columns; v_k stays in P[k..7][k] (pivot entries included); g[k] the reflectors' scalars
+__device__ __forceinline__ void quad_panel(double (&P)[8][3], double (&g)[3]) {
     {
         double ss = 0.0;
 #pragma unroll
         for (int r = 1; r < 8; ++r) ss = fma(P[r][0], P[r][0], ss);
         const House h = house_unguarded(P[0][0], ss);
-        g[0] = h.g; rinv[0] = h.rinv;
+        g[0] = h.g;
         double d1 = h.vp * P[0][1], d2 = h.vp * P[0][2];
 #pragma unroll
         for (int r = 1; r < 8; ++r) { d1 = fma(P[r][0], P[r][1], d1); d2 = fma(P[r][0], P[r][2], d2); }
@@ -59,7 +62,7 @@ __device__ __forceinline__ void quad_panel(double (&P)[8][3], const double (&d)[
 #pragma unroll
         for (int r = 2; r < 8; ++r) ss = fma(P[r][1], P[r][1], ss);
         const House h = house_unguarded(P[1][1], ss);
-        g[1] = h.g; rinv[1] = h.rinv;
+        g[1] = h.g;
         double d2 = h.vp * P[1][2];
 #pragma unroll
         for (int r = 2; r < 8; ++r) d2 = fma(P[r][1], P[r][2], d2);
@@ -73,20 +76,18 @@ __device__ __forceinline__ void quad_panel(double (&P)[8][3], const double (&d)[
 #pragma unroll
         for (int r = 3; r < 8; ++r) ss = fma(P[r][2], P[r][2], ss);
         const House h = house_unguarded(P[2][2], ss);
-        g[2] = h.g; rinv[2] = h.rinv;
+        g[2] = h.g;
         P[2][2] = h.vp;
     }
-    z[0] = d[0] * rinv[0];
-    z[1] = fma(-P[0][1], z[0], d[1]) * rinv[1];
-    z[2] = fma(-P[1][2], z[1], fma(-P[0][2], z[0], d[2])) * rinv[2];
 }
 
 // The three reflectors on a column that enters with one face's three entries (rows R0 .. R0 + 2; R0 < 0: the column c = e_0)
 // and zeros elsewhere, through the reflectors' mutual products cc = (v1 . v0, v2 . v0, v2 . v1) -- w2_column of
-// kernels_gls_hex8mf.hip on 8 rows.  Out: u = z^T (rows 0 .. 2), the five fill entries (rows 3 .. 7).
+// kernels_gls_hex8mf.hip on 8 rows.  Out: the five fill entries (rows 3 .. 7); rows 0 .. 2, the column's part of R, are needed by
+// nobody: the weights come from the residual, which the reflectors give back without R.
 template <int R0>
-__device__ __forceinline__ void quad_column(const double (&P)[8][3], const double (&g3)[3], const double (&cc)[3], const double (&z)[3],
-                                            const double (&b)[3], double &u_out, double (&fill)[5]) {
+__device__ __forceinline__ void quad_column(const double (&P)[8][3], const double (&g3)[3], const double (&cc)[3], const double (&b)[3],
+                                            double (&fill)[5]) {
     double w0, w1, w2;
     if (R0 < 0) {
         w0 = -(g3[0] * P[0][0]);
@@ -99,23 +100,17 @@ __device__ __forceinline__ void quad_column(const double (&P)[8][3], const doubl
                                     : fma(P[R0 + 2][2], b[2], P[R0 + 1][2] * b[1]);     // (R0 = 1: row 1 lies above v2)
         w2 = -(g3[2] * fma(w1, cc[2], fma(w0, cc[1], d2)));
     }
-    double B[8];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
+    for (int r = 3; r < 8; ++r) {
         const bool own = R0 >= 0 && r >= R0 && r < R0 + 3;
-        double v = own ? fma(w0, P[r][0], b[own ? r - R0 : 0]) : (R0 < 0 && r == 0) ? fma(w0, P[0][0], 1.0) : w0 * P[r][0];
-        if (r >= 1) v = fma(w1, P[r][1], v);
-        if (r >= 2) v = fma(w2, P[r][2], v);
-        B[r] = v;
+        const double v = own ? fma(w0, P[r][0], b[own ? r - R0 : 0]) : w0 * P[r][0];
+        fill[r - 3] = fma(w2, P[r][2], fma(w1, P[r][1], v));
     }
-    u_out = fma(z[2], B[2], fma(z[1], B[1], z[0] * B[0]));
-#pragma unroll
-    for (int r = 0; r < 5; ++r) fill[r] = B[3 + r];
 }
 
 // Phase 2, step K: pivot = local row Q = K / 2 of lane LAM = K % 2 (p2_step_lean of kernels_gls_hex8mf.hip on a pair)
 template <int K>
-__device__ __forceinline__ void quad_p2_step(double (&C)[QR][QC], double (&rinvq)[3], int e) {
+__device__ __forceinline__ void quad_p2_step(double (&C)[QR][QC], double (&gq)[6], double (&vpq)[6], int e) {
     constexpr int Q = K / 2, LAM = K % 2;
     const bool is_piv = (e == LAM);
     const double xq = (e > LAM) ? C[Q][K] : 0.0;
@@ -125,7 +120,8 @@ __device__ __forceinline__ void quad_p2_step(double (&C)[QR][QC], double (&rinvq
     ss = pair_sum(ss);
     const double alpha = pair_bcast<LAM>(C[Q][K]);
     const House h = house_unguarded(alpha, ss);
-    rinvq[Q] = is_piv ? h.rinv : rinvq[Q];
+    gq[K] = h.g;                                               // (the pair's two lanes hold the same scalars)
+    vpq[K] = h.vp;
     const double vq = is_piv ? h.vp : xq;
 #pragma unroll
     for (int j = K + 1; j < QC; ++j) {
@@ -140,31 +136,35 @@ __device__ __forceinline__ void quad_p2_step(double (&C)[QR][QC], double (&rinvq
 }
 template <int K, int KEND>
 struct QuadP2 {
-    static __device__ __forceinline__ void run(double (&C)[QR][QC], double (&rinvq)[3], int e) {
-        quad_p2_step<K>(C, rinvq, e);
-        QuadP2<K + 1, KEND>::run(C, rinvq, e);
+    static __device__ __forceinline__ void run(double (&C)[QR][QC], double (&gq)[6], double (&vpq)[6], int e) {
+        quad_p2_step<K>(C, gq, vpq, e);
+        QuadP2<K + 1, KEND>::run(C, gq, vpq, e);
     }
 };
 template <int KEND>
 struct QuadP2<KEND, KEND> {
-    static __device__ __forceinline__ void run(double (&)[QR][QC], double (&)[3], int) {}
+    static __device__ __forceinline__ void run(double (&)[QR][QC], double (&)[6], double (&)[6], int) {}
 };
-// back-substitution by columns: row K of R lives in lane K % 2, local row K / 2 (entries C[Q][j], j > K; right-hand side t[Q])
+// Reflector K of phase 2 once more, on a vector t over the pair's 14 rows (v_K is still in column K of C: nothing below a pivot is
+// written after its step; the pivot entry is vpq[K]); K = 5 first: t <- H_0 .. H_5 t
 template <int K>
-struct QuadBack {
-    static __device__ __forceinline__ void run(const double (&C)[QR][QC], const double (&rinvq)[3], double (&t)[3], double (&y)[6], int e) {
+struct QuadP2Back {
+    static __device__ __forceinline__ void run(const double (&C)[QR][QC], const double (&gq)[6], const double (&vpq)[6], double (&t)[QR], int e) {
         constexpr int Q = K / 2, LAM = K % 2;
-        const double yk = pair_bcast<LAM>(t[Q] * rinvq[Q]);
-        y[K] = yk;
+        const double vq = (e == LAM) ? vpq[K] : (e > LAM) ? C[Q][K] : 0.0;
+        double a = vq * t[Q];
 #pragma unroll
-        for (int q = 0; q < Q; ++q) t[q] = fma(-C[q][K], yk, t[q]);
-        if (LAM > 0) t[Q] = fma((e < LAM) ? -C[Q][K] : 0.0, yk, t[Q]);
-        QuadBack<K - 1>::run(C, rinvq, t, y, e);
+        for (int r = Q + 1; r < QR; ++r) a = fma(C[r][K], t[r], a);
+        const double w = -(gq[K] * pair_sum(a));
+        t[Q] = fma(w, vq, t[Q]);
+#pragma unroll
+        for (int r = Q + 1; r < QR; ++r) t[r] = fma(w, C[r][K], t[r]);
+        QuadP2Back<K - 1>::run(C, gq, vpq, t, e);
     }
 };
 template <>
-struct QuadBack<-1> {
-    static __device__ __forceinline__ void run(const double (&)[QR][QC], const double (&)[3], double (&)[3], double (&)[6], int) {}
+struct QuadP2Back<-1> {
+    static __device__ __forceinline__ void run(const double (&)[QR][QC], const double (&)[6], const double (&)[6], double (&)[QR], int) {}
 };
 
 __global__ __launch_bounds__(256) void nin_gls_quad4_kernel(GridView g, const int32_t *__restrict__ nodes,
@@ -246,10 +246,10 @@ __global__ __launch_bounds__(256) void nin_gls_quad4_kernel(GridView g, const in
 #pragma unroll
             for (int t = 0; t < 3; ++t) P[7][t] = -mneu * (Ke[t * 3 + 0] * N0 + Ke[t * 3 + 1] * N1 + Ke[t * 3 + 2] * N2);   // gls.pyx:394-416
         }
-        double C[QR][QC], u[6], se;
+        double C[QR][QC], g3[3];
         {
-            double g3[3], z[3], cc[3];
-            quad_panel(P, de, g3, z);
+            double cc[3];
+            quad_panel(P, g3);
             cc[0] = P[1][1] * P[1][0];
             cc[1] = P[2][2] * P[2][0];
             cc[2] = P[2][2] * P[2][1];
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void nin_gls_quad4_kernel(GridView g, const in
             {
                 const double none[3] = {0.0, 0.0, 0.0};
                 double fill[5];
-                quad_column<-1>(P, g3, cc, z, none, se, fill);   // c = e_0 on entry
+                quad_column<-1>(P, g3, cc, none, fill);   // c = e_0 on entry
 #pragma unroll
                 for (int r = 0; r < 5; ++r) C[r][6] = fill[r];
             }
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void nin_gls_quad4_kernel(GridView g, const in
             for (int t = 0; t < 3; ++t) {                        // odd slot 0 <- face A: rows 1 .. 3
                 const double b[3] = {nb[0][0][t], nb[0][1][t], nb[0][2][t]};
                 double fill[5];
-                quad_column<1>(P, g3, cc, z, b, u[t], fill);
+                quad_column<1>(P, g3, cc, b, fill);
 #pragma unroll
                 for (int r = 0; r < 5; ++r) C[r][t] = fill[r];
             }
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void nin_gls_quad4_kernel(GridView g, const in
             for (int t = 0; t < 3; ++t) {                        // odd slot 1 <- face B: rows 4 .. 6
                 const double b[3] = {nb[1][0][t], nb[1][1][t], nb[1][2][t]};
                 double fill[5];
-                quad_column<4>(P, g3, cc, z, b, u[3 + t], fill);
+                quad_column<4>(P, g3, cc, b, fill);
 #pragma unroll
                 for (int r = 0; r < 5; ++r) C[r][3 + t] = fill[r];
             }
@@ -299,19 +299,29 @@ __global__ __launch_bounds__(256) void nin_gls_quad4_kernel(GridView g, const in
             C[6][6] = 0.0;
         }
         // ---- phase 2: 14 x 6 over the pair ---------------------------------------------------------------------------------
-        double rinvq[3] = {0.0, 0.0, 0.0};
-        QuadP2<0, 6>::run(C, rinvq, e);
-        double y[6], t3[3] = {C[0][6], C[1][6], C[2][6]};
-        QuadBack<5>::run(C, rinvq, t3, y, e);
-        double tail = 0.0;
+        double gq[6], vpq[6];
+        QuadP2<0, 6>::run(C, gq, vpq, e);
+        // ---- the residual r = Q [0; tail]: rows 0 .. 2 of either lane were pivot rows, the tail of Q^T c sits in rows 3 .. 6 ----
+        double tail = 0.0, t7[QR];
+#pragma unroll
+        for (int r = 0; r < QR; ++r) t7[r] = r < 3 ? 0.0 : C[r][6];
 #pragma unroll
         for (int r = 3; r < QR; ++r) tail = fma(C[r][6], C[r][6], tail);
         const double rr = pair_sum(tail);                        // r . r = |(Q^T c)(12:20)|^2
-        double re = 1.0 - se;                                    // r_e = 1 - d_e . y_e = 1 - z . b_e + u . y_odd
+        QuadP2Back<5>::run(C, gq, vpq, t7, e);
+        const double ro = t7[5];                                 // the cell row of O_e
+        // phase 1 backwards on the front of E_e: rows 0 .. 2 were its pivot rows, rows 3 .. 7 are the five fill rows (t7[0 .. 4])
+        double x8[8] = {0.0, 0.0, 0.0, t7[0], t7[1], t7[2], t7[3], t7[4]};
 #pragma unroll
-        for (int j = 0; j < 6; ++j) re = fma(u[j], y[j], re);
-        const double d0 = fma(dod[2], y[2], fma(dod[1], y[1], dod[0] * y[0])), d1 = fma(dod[2], y[5], fma(dod[1], y[4], dod[0] * y[3]));
-        const double ro = 1.0 - (e == 0 ? d0 : d1);
+        for (int k = 2; k >= 0; --k) {
+            double a = 0.0;
+#pragma unroll
+            for (int r = k; r < 8; ++r) a = fma(P[r][k], x8[r], a);
+            const double w = -(g3[k] * a);
+#pragma unroll
+            for (int r = k; r < 8; ++r) x8[r] = fma(w, P[r][k], x8[r]);
+        }
+        const double re = x8[0];                                 // the cell row of E_e
         const double rri = fast_rcp(rr);
         double we = re * rri, wo = ro * rri;
         const bool ok = computed && rr > 0.0;                    // (rank-deficient system or NaN from a zero column: the zero row)

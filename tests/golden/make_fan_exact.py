@@ -22,69 +22,7 @@ import numpy as np  # noqa: E402
 import ninpol_oracle as O  # noqa: E402
 from ninpol_amd import mesh as M  # noqa: E402
 
-LD = np.longdouble
-
-
-def system(p, G, perm, dmag, flag):
-    """M_v as the reference assembles it (gls.pyx:252-416), float64 arithmetic in the reference's operation order;
-    returns (M, n_elem) -- the weights are row n-1 of pinv(M) restricted to the cell rows."""
-    cells = G.esup[G.esup_ptr[p]:G.esup_ptr[p + 1]]
-    faces = G.fsup[G.fsup_ptr[p]:G.fsup_ptr[p + 1]]
-    loc = {int(c): i for i, c in enumerate(cells)}
-    ne, nf = len(cells), len(faces)
-    bfaces = [f for f in faces if G.boundary_faces[f] == 1]
-    m = ne + 3 * nf + len(bfaces)
-    Mi = np.zeros((m, 3 * ne + 1))
-    xv = G.point_coords[p]
-    for e, c in enumerate(cells):
-        Mi[e, 3 * e:3 * e + 3] = G.centroids[c] - xv
-        Mi[e, -1] = 1.0
-    row = ne
-    for f in faces:
-        a, b = G.esuf_ptr[f], G.esuf_ptr[f + 1]
-        if b - a < 2:
-            continue
-        ca, cb = int(G.esuf[a]), int(G.esuf[a + 1])
-        N = G.normal_faces[f]
-        T = xv - G.faces_centers[f]
-        U = np.array([N[1] * T[2] - N[2] * T[1], N[2] * T[0] - N[0] * T[2], N[0] * T[1] - N[1] * T[0]])
-        eta = max(0.0, dmag[ca], dmag[cb])
-        tau = np.sqrt(U[0] * U[0] + U[1] * U[1] + U[2] * U[2]) ** (-eta)
-        Ka, Kb = perm[ca].reshape(3, 3), perm[cb].reshape(3, 3)
-        kna = np.array([Ka[r, 0] * N[0] + Ka[r, 1] * N[1] + Ka[r, 2] * N[2] for r in range(3)])
-        knb = np.array([Kb[r, 0] * N[0] + Kb[r, 1] * N[1] + Kb[r, 2] * N[2] for r in range(3)])
-        for k, (va, vb) in enumerate(((kna, knb), (T, T), (tau * U, tau * U))):
-            Mi[row + k, 3 * loc[ca]:3 * loc[ca] + 3] = -va
-            Mi[row + k, 3 * loc[cb]:3 * loc[cb] + 3] = vb
-        row += 3
-    if flag[p]:
-        start = ne + 3 * nf
-        for i, f in enumerate(bfaces):
-            c0 = int(G.esuf[G.esuf_ptr[f]])
-            K0 = perm[c0].reshape(3, 3)
-            N = G.normal_faces[f]
-            Mi[start + i, 3 * loc[c0]:3 * loc[c0] + 3] = [-(K0[r, 0] * N[0] + K0[r, 1] * N[1] + K0[r, 2] * N[2]) for r in range(3)]
-    return Mi, ne
-
-
-def last_row_of_pinv(Mi, ne):
-    """Row n-1 of the least-squares solution of M X = [I_ne; 0] in extended precision (Householder QR, full column rank)."""
-    A = Mi.astype(LD)
-    m, n = A.shape
-    B = np.zeros((m, ne), dtype=LD)
-    B[:ne, :ne] = np.eye(ne, dtype=LD)
-    for k in range(n):
-        x = A[k:, k].copy()
-        nx = np.sqrt((x * x).sum())
-        if nx == 0:
-            raise ZeroDivisionError("rank deficient")
-        beta = -np.copysign(nx, x[0])
-        v = x.copy()
-        v[0] -= beta
-        g = LD(1) / (v * v).sum() * 2
-        A[k:, k:] -= np.outer(v, g * (v @ A[k:, k:]))
-        B[k:, :] -= np.outer(v, g * (v @ B[k:, :]))
-    return np.asarray(B[n - 1, :] / A[n - 1, n - 1], dtype=np.float64)   # back-substitution's first step IS row n-1
+from gls_exact import last_row_of_pinv, system  # noqa: E402  (tests/gls_exact.py: the solver the GPU tests use is the one that made this pin)
 
 
 def main():

@@ -34,11 +34,7 @@ def _loaded(mesh, **kw):
     return I
 
 
-def _layout(grid):
-    ptr = np.asarray(grid.esup_ptr)
-    cnt = np.diff(ptr)
-    rows = np.repeat(np.arange(len(cnt)), cnt)
-    return rows, np.arange(int(ptr[-1])) - np.repeat(ptr[:-1], cnt)
+_layout = util.esup_layout
 
 
 def _dense(grid, csr):
@@ -95,46 +91,15 @@ def C(oracle_lib):
             "I": I, "full": full, "plan": I.grid.gls_plan(), "part_plans": [g.gls_plan() for g, _ in alone]}
 
 
-def _torch_launch(plan, fill, add_neumann=False, out=None):
-    import torch
-    if out is None:
-        out = (torch.full((plan.nnz,), fill, dtype=torch.float64, device="cuda"),
-               torch.full((plan.n_points,), fill, dtype=torch.float64, device="cuda"))
-    plan.launch(out[0].data_ptr(), out[1].data_ptr(), torch.cuda.current_stream().cuda_stream, add_neumann=add_neumann)
-    return out
-
-
-def _host(out):
-    import torch
-    torch.cuda.synchronize()
-    return out[0].cpu().numpy(), out[1].cpu().numpy()
+_torch_launch, _host = util.torch_launch, util.torch_to_host
 
 
 @pytest.fixture(scope="module")
 def owners(C):
     """NIN_GLS_ONLY=<k>: the rows each kernel of the plan writes (launched alone into NaN-filled buffers)"""
-    I, plan = C["I"], C["plan"]
-    rows, _ = _layout(I.grid)
-    dp = I.device_plan("u", "gls")
     csr, nws = C["full"]["gls"]
-    assert not np.isnan(csr).any() and not np.isnan(nws).any()   # (a NaN in the buffer below means: not written)
-    got = {}
-    with pytest.MonkeyPatch.context() as mp:
-        for k, name in enumerate(I.grid.PLAN_KERNELS):
-            if not plan[name]:
-                continue
-            mp.setenv("NIN_GLS_ONLY", str(k))
-            a, n = _host(_torch_launch(dp, np.nan))
-            row_nan = np.zeros(C["P"], dtype=bool)
-            np.logical_or.at(row_nan, rows, np.isnan(a))
-            row_all = np.ones(C["P"], dtype=bool)
-            np.logical_and.at(row_all, rows, np.isnan(a))
-            assert np.array_equal(row_nan, row_all), (name, "rows written in part")
-            assert np.array_equal(row_nan, np.isnan(n)), (name, "neumann_ws and the row disagree")
-            mine = np.flatnonzero(~row_nan)
-            sel = ~row_nan[rows]
-            got[name] = (mine, a[sel], n[mine])
-    return got
+    assert not np.isnan(csr).any() and not np.isnan(nws).any()   # (a NaN in the owners' buffers means: not written)
+    return util.gls_kernel_owners(C["I"], C["plan"])
 
 
 def test_plan_holds_every_kernel_and_is_the_sum_of_the_parts(C):

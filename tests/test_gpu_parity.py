@@ -681,23 +681,7 @@ def test_gpu_gls_degenerate_set(oracle_lib, kind):
     assert util.rowscaled_err(nw[regular], no[regular]) <= util.WEIGHT_RTOL
 
 
-# every way a node can reach a GLS kernel: name -> environment switches (read when the launch plan is built)
-_GLS_ROUTES = {
-    "default": (),                                                        # cube-node kernel / mfw strips (two-coloured) / the wide kernel / small, quad, block for the boundary
-    "no_cube_kernel": ("NIN_GLS_NO_GROUP",),                              # cube nodes -> mfw small instantiation
-    "mfw_lane_columns": ("NIN_GLS_NO_GROUP", "NIN_MFW_LANE_COLUMNS"),     # the mfw kernel's first form
-    "mfw_row_lanes": ("NIN_MFW_NO_STRIPS",),                              # its second form (round 2's default) where the strip form runs now
-    "mfw_small_strips": ("NIN_GLS_NO_GROUP", "NIN_MFW_SMALL_STRIPS"),     # the strip form in the small instantiation (wedge / cube nodes)
-    "general_kind": ("NIN_GLS_MFW_GENERAL",),                             # nodes that are not two-coloured: kernels_gls_mfw.hip's general kind where it fits (round 3's default)
-    "no_general_kind": ("NIN_GLS_NO_MFW_GENERAL", "NIN_GLS_NO_MFX"),      # ... -> block kernel
-    "wide_for_two_coloured": ("NIN_GLS_NO_MFW",),                         # Kuhn / wedge nodes through the wide kernel (small ones: the small-node kernel)
-    "no_quad_kernel": ("NIN_GLS_NO_QUAD4",),                              # nodes inside a boundary face -> small-node kernel
-    "no_small_kernel": ("NIN_GLS_NO_SMALL", "NIN_GLS_NO_QUAD4"),          # boundary nodes -> block kernel (round 2's route)
-    "small_where_it_fits": ("NIN_GLS_NO_GROUP", "NIN_GLS_NO_MFW"),        # the small-node kernel for every node of <= 12 cells and <= 64 rows
-    "no_boundary_in_wide": ("NIN_GLS_MFX_NO_BOUNDARY",),                  # boundary nodes beyond the small-node kernel -> block kernel (round 3's route)
-    "block_only": ("NIN_GLS_NO_GROUP", "NIN_GLS_NO_MFW", "NIN_GLS_NO_MFX", "NIN_GLS_NO_SMALL", "NIN_GLS_NO_QUAD4"),   # block kernel, 1 / 2 / 4 / 8 wavefronts per node
-    "global_scratch": ("NIN_GLS_NO_GROUP", "NIN_GLS_NO_MFW", "NIN_GLS_FORCE_GLOBAL"),   # the wave kernel
-}
+_GLS_ROUTES = util.GLS_ROUTES   # every way a node can reach a GLS kernel: name -> environment switches
 
 
 @pytest.mark.parametrize("kind", ["hex", "tet", "wedge", "mixed"])
