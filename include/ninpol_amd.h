@@ -78,7 +78,8 @@ int nin_grid_create_on_device(int64_t dim, int64_t n_elems, int64_t n_points,
                               nin_grid **out);
 
 /* Readonly attributes of Grid (grid.pxd:128-187).  Scalars: dim n_elems n_points n_faces n_edges
- * MX_ELEMENTS_PER_POINT MX_POINTS_PER_POINT MX_ELEMENTS_PER_FACE MX_FACES_PER_POINT.  Unknown -> -1. */
+ * MX_ELEMENTS_PER_POINT MX_POINTS_PER_POINT MX_ELEMENTS_PER_FACE MX_FACES_PER_POINT; of the library's own: coords_dim nnz_esup
+ * nnz_fsup gls_adjoint_contrib_bytes (the GLS adjoint's contribution buffer as allocated now, 0: not there).  Unknown -> -1. */
 int64_t nin_grid_scalar(const nin_grid *g, const char *name);
 
 /* Number of elements of array `name` and its dtype code; arrays: esup esup_ptr psup psup_ptr fsup
@@ -423,7 +424,30 @@ int nin_apply_transpose_fields_host(nin_grid *g, int method, const double *node_
  *   [n_elems][9] = d <node_values, W cell_values> / dK for the W of nin_apply_* (add_neumann = 1), the diff_mag chain folded;
  *   node_values [n_fields][n_points], cell_values [n_fields][n_elems]; synchronous.  Errors as the two calls it makes.
  * nin_gls_adjoint_plan: nodes per bin of the adjoint kernel -- the LDS classes of one, two and four wavefronts per node, then the
- *   global-scratch class (diagnostics and tests).  Makes the bins if they are not there (synchronous). */
+ *   global-scratch class (diagnostics and tests).  Makes the bins if they are not there (synchronous).
+ *
+ * The forward derivative, for Newton-Krylov, Gauss-Newton and forward-mode AD: the change of the stored weights along a direction dK.
+ * nin_gls_weights_tangent_device: dev_tangent_perm [n_tangents][n_elems][9] = the directions dK (row-major 3 x 3 per cell);
+ *   dev_tangent_diff_mag [n_tangents][n_elems] = the directions of diff_mag as an independent input, or NULL: folded,
+ *   d diff_mag_e = 2 (1 - 3 / tr K_e) 3 / tr K_e^2 tr dK_e from the resident K.  Writes dev_tangent_csr [n_tangents][nnz_esup] =
+ *   (d csr_data / dK) . dK in esup / CSR position, for the csr_data of nin_weights_device(NIN_METHOD_GLS, ..., add_neumann, ...) at
+ *   what is resident NOW, and dev_tangent_neumann_ws [n_tangents][n_points] = the same for neumann_ws (NULL: not wanted).  Every
+ *   entry of both is written: zeros for the nodes the forward gives the zero row, and for neumann_ws of the nodes that are not
+ *   Neumann nodes.  The adjoint's kernel in its tangent mode: the same assembly and the same Householder QR, factored once per node
+ *   for all n_tangents directions; per direction one application of Q^T, one forward substitution with R^T and one application of
+ *   Q, written straight into CSR position -- no contribution buffer, no gather, no transpose index, no atomics; two calls agree bit
+ *   for bit, and a batch equals its directions one by one.  With the backward call's dL/dK = Kbar:
+ *   <grad_csr, tangent_csr> + <grad_neumann_ws, tangent_neumann_ws> = <Kbar, dK>.
+ *   The first of the backward, tangent and plan calls on a grid bins the nodes and allocates the scratch slots (and synchronises
+ *   `stream`); the 80 bytes per entry of the contribution buffer are allocated by the first BACKWARD call only
+ *   (nin_grid_scalar "gls_adjoint_contrib_bytes": what is allocated now).  Later calls are asynchronous on `stream`.  Errors as
+ *   nin_gls_weights_backward_device; NIN_EINVAL also for n_tangents < 1.  NIN_GLS_ADJ_FORCE_GLOBAL and NIN_GLS_ADJ_ONLY as there
+ *   (with NIN_GLS_ADJ_ONLY the other bins' rows are not written).
+ * nin_gls_permeability_tangent_host: the host-pointer counterpart, the sibling of nin_gls_permeability_gradient_host -- direction f
+ *   meets field f: node_values[f] = dW_f . cell_values[f] with dW_f the tangent of the W of nin_apply_* (add_neumann = 1, the
+ *   diff_mag chain folded) along tangent_permeability[f], and neumann_ws[f] the tangent of neumann_ws; tangent_permeability
+ *   [n_fields][n_elems][9], cell_values [n_fields][n_elems], node_values and neumann_ws [n_fields][n_points]; synchronous.  Errors
+ *   as the calls it makes (the tangent, then nin_spmv_device). */
 int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
                                     double *dev_grad_perm, double *dev_grad_diff_mag, void *stream);
 int nin_sddmm_device(nin_grid *g, const double *dev_u_cells, const double *dev_node_values, int32_t n_fields, double *dev_grad_csr,
@@ -431,6 +455,11 @@ int nin_sddmm_device(nin_grid *g, const double *dev_u_cells, const double *dev_n
 int nin_gls_permeability_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields,
                                        double *grad_permeability);
 int nin_gls_adjoint_plan(nin_grid *g, int64_t counts[4]);
+int nin_gls_weights_tangent_device(nin_grid *g, int add_neumann, int32_t n_tangents, const double *dev_tangent_perm,
+                                   const double *dev_tangent_diff_mag, double *dev_tangent_csr, double *dev_tangent_neumann_ws,
+                                   void *stream);
+int nin_gls_permeability_tangent_host(nin_grid *g, const double *tangent_permeability, const double *cell_values, int32_t n_fields,
+                                      double *node_values, double *neumann_ws);
 
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,

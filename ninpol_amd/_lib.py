@@ -30,6 +30,7 @@ EXPORTS = (
     "nin_hostmatrix_create", "nin_hostmatrix_full", "nin_hostmatrix_update", "nin_hostmatrix_patch", "nin_hostmatrix_destroy",
     "nin_csr_patch_rows",
     "nin_gls_weights_backward_device", "nin_sddmm_device", "nin_gls_adjoint_plan", "nin_gls_permeability_gradient_host",
+    "nin_gls_weights_tangent_device", "nin_gls_permeability_tangent_host",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -81,6 +82,8 @@ def load():
     L.nin_sddmm_device.argtypes = [vp, vp, vp, i32, vp, vp]
     L.nin_gls_adjoint_plan.argtypes = [vp, vp]
     L.nin_gls_permeability_gradient_host.argtypes = [vp, vp, vp, i32, vp]
+    L.nin_gls_weights_tangent_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.nin_gls_permeability_tangent_host.argtypes = [vp, vp, vp, i32, vp, vp]
     L.nin_pack_connectivity.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     L.nin_pack_table_row.argtypes = [vp, i64, i64, i64, vp]
     L.nin_diff_mag.argtypes = [vp, i64, vp]

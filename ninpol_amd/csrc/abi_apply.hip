@@ -1,4 +1,4 @@
-// abi_apply.hip -- the C ABI, part 5: W u, W^T v with the cell-major index behind it, and the GLS adjoint.
+// abi_apply.hip -- the C ABI, part 5: W u, W^T v with the cell-major index behind it, the GLS adjoint and the GLS tangent.
 #include <hipcub/hipcub.hpp>
 
 #include "abi_internal.hpp"
@@ -171,8 +171,9 @@ void nin::release_adjoint_state(DeviceGrid &d) {
     d.adj_ready = false;
 }
 
-// The bins, the contribution buffer and the scratch slots, on first use.  Synchronises `stream` (one device-to-host copy of 8 bytes a node).
-static int ensure_adjoint_state(DeviceGrid &d, hipStream_t stream) {
+// The bins and the scratch slots, made by whichever of the backward, tangent and plan calls comes first.  Synchronises `stream` (one
+// device-to-host copy of 8 bytes a node).
+static int ensure_adjoint_bins(DeviceGrid &d, hipStream_t stream) {
     if (d.adj_ready) return NIN_OK;
     const int32_t P = d.v.n_points;
     const bool force_global = getenv("NIN_GLS_ADJ_FORCE_GLOBAL") != nullptr;   // testing switch: every system in global scratch
@@ -202,7 +203,6 @@ static int ensure_adjoint_state(DeviceGrid &d, hipStream_t stream) {
         if (!rc && hipMemcpy(bin.nodes, lists[b].data(), lists[b].size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(NIN_EHIP, "adjoint bins: upload failed");
     }
-    if (!rc) rc = dev_alloc(d, &d.adj_contrib, (size_t)std::max<int64_t>(d.nnz_e, 1) * 10);
     if (!rc && d.adj_bin[kAdjBins - 1].count > 0) {
         d.adj_scratch_slots = std::min<int32_t>(d.adj_bin[kAdjBins - 1].count, 256);
         d.adj_scratch_stride = mx[kAdjBins - 1] / 8;
@@ -213,6 +213,11 @@ static int ensure_adjoint_state(DeviceGrid &d, hipStream_t stream) {
     return NIN_OK;
 }
 
+// The contribution buffer, 80 bytes per entry of esup: the backward call's alone -- the tangent writes straight into CSR position
+static int ensure_adjoint_contrib(DeviceGrid &d) {
+    return d.adj_contrib ? NIN_OK : dev_alloc(d, &d.adj_contrib, (size_t)std::max<int64_t>(d.nnz_e, 1) * 10);
+}
+
 int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
                                     double *dev_grad_perm, double *dev_grad_diff_mag, void *stream_) {
     if (!g || !dev_grad_csr || !dev_grad_perm) return fail(NIN_EINVAL, "NULL argument");
@@ -221,7 +226,8 @@ int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *
     if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
     HIP_TRY(hipSetDevice(d.device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = ensure_adjoint_state(d, stream);
+    int rc = ensure_adjoint_bins(d, stream);
+    if (!rc) rc = ensure_adjoint_contrib(d);
     if (!rc) rc = ensure_transpose_index(d, stream);
     if (rc) return rc;
     const char *only_env = getenv("NIN_GLS_ADJ_ONLY");   // per-bin timing (tools/time_adjoint.py): launch only that bin; read at every call
@@ -273,12 +279,65 @@ int nin_gls_permeability_gradient_host(nin_grid *g, const double *node_values, c
     return NIN_OK;
 }
 
+// ---- the GLS tangent: d(stored weights) along a direction dK (kernels_gls_adjoint.hip's tangent mode) -------------------
+int nin_gls_weights_tangent_device(nin_grid *g, int add_neumann, int32_t n_tangents, const double *dev_tangent_perm,
+                                   const double *dev_tangent_diff_mag, double *dev_tangent_csr, double *dev_tangent_neumann_ws,
+                                   void *stream_) {
+    if (!g || !dev_tangent_perm || !dev_tangent_csr) return fail(NIN_EINVAL, "NULL argument");
+    if (n_tangents < 1) return fail(NIN_EINVAL, "n_tangents must be >= 1");
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the kernel has a bin for systems of any size)
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = ensure_adjoint_bins(d, stream);
+    if (rc) return rc;
+    const char *only_env = getenv("NIN_GLS_ADJ_ONLY");   // per-bin timing, as in the backward call: the other bins' rows are not written
+    const int only = only_env ? atoi(only_env) : -1;
+    for (int b = 0; b < kAdjBins && !rc; ++b) {
+        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
+        if (only >= 0 && b != only) continue;
+        rc = launch_gls_tangent(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, n_tangents, dev_tangent_perm, dev_tangent_diff_mag,
+                                dev_tangent_csr, dev_tangent_neumann_ws, d.nnz_e, d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots,
+                                stream);
+    }
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_gls_permeability_tangent_host(nin_grid *g, const double *tangent_permeability, const double *cell_values, int32_t n_fields,
+                                      double *node_values, double *neumann_ws) {
+    if (!g || !tangent_permeability || !cell_values || !node_values || !neumann_ws) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;
+    HIP_TRY(hipSetDevice(d.device));
+    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8, wb = (size_t)std::max<int64_t>(d.nnz_e, 1) * 8;
+    DevTmp<double> dk, du, dw, dv, dn;
+    HIP_TRY(hipMalloc((void **)&dk, std::max<size_t>(eb, 8) * 9 * n_fields));
+    HIP_TRY(hipMalloc((void **)&du, std::max<size_t>(eb, 8) * n_fields));
+    HIP_TRY(hipMalloc((void **)&dw, wb * n_fields));
+    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(pb, 8) * n_fields));
+    HIP_TRY(hipMalloc((void **)&dn, std::max<size_t>(pb, 8) * n_fields));
+    HIP_TRY(hipMemcpy(dk, tangent_permeability, eb * 9 * n_fields, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(du, cell_values, eb * n_fields, hipMemcpyHostToDevice));
+    // dW as apply() uses W (`+ neumann_ws[row]` included): add_neumann = 1, the diff_mag chain folded; direction f meets field f
+    int rc = nin_gls_weights_tangent_device(g, 1, n_fields, dk, nullptr, dw, dn, nullptr);
+    for (int32_t f = 0; f < n_fields && !rc; ++f)
+        rc = nin_spmv_device(g, dw.p + (size_t)f * (size_t)d.nnz_e, du.p + (size_t)f * g->h.n_elems, 1, dv.p + (size_t)f * g->h.n_points, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(node_values, dv, pb * n_fields, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(neumann_ws, dn, pb * n_fields, hipMemcpyDeviceToHost));
+    return NIN_OK;
+}
+
 int nin_gls_adjoint_plan(nin_grid *g, int64_t counts[4]) {
     if (!g || !counts) return fail(NIN_EINVAL, "NULL argument");
     DeviceGrid &d = g->d;
     if (int rc = on_device(g, kHintToDevice)) return rc;
     HIP_TRY(hipSetDevice(d.device));
-    const int rc = ensure_adjoint_state(d, nullptr);
+    const int rc = ensure_adjoint_bins(d, nullptr);
     if (rc) return rc;
     for (int b = 0; b < kAdjBins; ++b) counts[b] = d.adj_bin[b].count;
     return NIN_OK;

@@ -223,6 +223,7 @@ int64_t nin_grid_scalar(const nin_grid *g, const char *name) {
     if (n == "coords_dim") return g->coords_dim;
     if (n == "nnz_esup") return h.nnz_esup;
     if (n == "nnz_fsup") return h.nnz_fsup;
+    if (n == "gls_adjoint_contrib_bytes") return g->d.adj_contrib ? std::max<int64_t>(g->d.nnz_e, 1) * 80 : 0;
     return -1;
 }
 

@@ -163,7 +163,7 @@ int launch_lists(DeviceGrid &d, int method, const int32_t *lists, const int32_t 
                  int add_neumann, double *out, double *nws, hipStream_t stream, DirtyLaps *laps);
 // abi_update.hip: the host's copy of the resident flag bytes (flag_staging), brought up to date
 int fetch_flag_bytes(nin_grid *g);
-// abi_apply.hip: the adjoint's bins, contribution buffer and scratch slots given back
+// abi_apply.hip: the adjoint's and the tangent's bins and scratch slots, and the adjoint's contribution buffer, given back
 void release_adjoint_state(DeviceGrid &d);
 
 }  // namespace nin

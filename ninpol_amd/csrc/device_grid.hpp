@@ -103,7 +103,8 @@ struct DeviceGrid {
     // the GLS adjoint (nin_gls_weights_backward_device, kernels_gls_adjoint.hip): the node list of every bin (gls_adjoint.hpp) with the
     // largest slot among its nodes, the contribution buffer [nnz_e][10] (80 bytes per entry of esup: 6.4 GB at 216^3 hexahedra) and the
     // global-scratch bin's slots; built by the first call, kept until nin_grid_release_scratch.  The bins depend on the connectivity
-    // alone.  The kernels take their nodes by a static stride: no work counter, and no line of gls_queue
+    // alone.  The tangent (nin_gls_weights_tangent_device) shares the bins and the slots; the contribution buffer is the backward call's
+    // alone and is made by the first of those.  The kernels take their nodes by a static stride: no work counter, and no line of gls_queue
     struct AdjBin {
         int32_t count = 0;
         int32_t *nodes = nullptr;

@@ -22,6 +22,15 @@
 // (node, cell) -- Kbar[9] and etabar -- are summed in that fixed order and written to contrib[esup position][10].  nin_adjoint_gather_kernel
 // then sums, for every cell, the slots of its nodes in ascending node id through the cell-major index of the transpose (DeviceGrid::tr_*).
 // No atomics anywhere: two calls agree bit for bit.
+//
+// The tangent (TAN = true): the same kernel up to y, r, rho and the verdict, then for every direction dK (9 per cell; d
+// diff_mag per cell given, or folded from the resident perm) the directional derivative of the stored entries.  dA is non-zero where K
+// enters: -(dK_a N) / +(dK_b N) on the K.N row, -/+ dtau U on the tau.T2 row with dtau = -ln|T2| tau ddm_pick (pick: the cell the
+// forward's max() takes eta from), -(dK_a N) on a Neumann boundary row.  r = P_perp c, so with A = Q R
+//   dr = -P_perp (dA y) - (A^+)^T (dA^T r) = -Q [ R^-T (dA^T r) ; (Q^T (dA y))(n-1:m) ]
+//   drho = 2 r.dr,  dw_i = dr_i / rho - r_i drho / rho^2,  dnws = dw_{ne-1} on a Neumann node,  dd_i = dw_i + (add_neumann ? dnws : 0)
+// written straight to tangent_csr[t][esup position] (and tangent_nws[t][p]): no contribution buffer, no gather.  Every row of every
+// listed node is written, zeros where the forward has its zero row.
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
@@ -72,6 +81,43 @@ __device__ __forceinline__ void wave_sync() {
 
 __device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// What one launch reads and writes beside the grid: the adjoint's three pointers, or the tangent's
+struct AdjointIo {
+    const double *grad_csr, *grad_nws;   // adjoint: dL/d stored weights [nnz_esup], dL/d neumann_ws [P] or null
+    double *contrib;                     //          [nnz_esup][10]
+    int32_t n_tan;                       // tangent: directions
+    const double *tan_perm, *tan_dm;     //          dK [n_tan][E][9]; d diff_mag [n_tan][E] or null (folded from g.perm)
+    double *tan_csr, *tan_nws;           //          d stored weights [n_tan][nnz]; d neumann_ws [n_tan][P] or null
+    long long nnz;
+};
+
+// d diff_mag of cell e along the direction: given, or (1 - 3 / tr K)^2 differentiated (nin_adjoint_gather_kernel's factor)
+__device__ __forceinline__ double tangent_dm(const GridView &g, const double *dK, const double *dm, size_t e) {
+    if (dm) return dm[e];
+    const double *K = g.perm + 9 * e, *d = dK + 9 * e;
+    const double tr = (K[0] + K[4]) + K[8];
+    return (2.0 * (1.0 - 3.0 / tr) * 3.0 / (tr * tr)) * ((d[0] + d[4]) + d[8]);
+}
+
+// internal face f between cells ca and cb: U = N x T (T from the face centre to the node) and dtau = -ln|U| tau ddm_pick along the
+// direction, 0 when the forward's max() takes eta from nobody
+__device__ __forceinline__ double tangent_dtau(const GridView &g, size_t f, double xv0, double xv1, double xv2, double N0, double N1, double N2,
+                                               size_t ca, size_t cb, const double *dK, const double *dm, double U[3]) {
+    const double T0 = xv0 - g.face_center[3 * f + 0], T1 = xv1 - g.face_center[3 * f + 1], T2 = xv2 - g.face_center[3 * f + 2];
+    U[0] = N1 * T2 - N2 * T1; U[1] = N2 * T0 - N0 * T2; U[2] = N0 * T1 - N1 * T0;
+    const double da = g.diff_mag[ca], db = g.diff_mag[cb];
+    if (!(db > da) && !(da > 0.0)) return 0.0;
+    const double un = sqrt(U[0] * U[0] + U[1] * U[1] + U[2] * U[2]);
+    const double tj = glsmath::face_tau(un, db > da ? db : da);
+    return -log(un) * tj * tangent_dm(g, dK, dm, db > da ? cb : ca);
+}
+
+// row c of dK_e . N
+__device__ __forceinline__ double tangent_kn(const double *dK, size_t e, int c, double N0, double N1, double N2) {
+    const double *d = dK + 9 * e + 3 * c;
+    return d[0] * N0 + d[1] * N1 + d[2] * N2;
+}
+
 constexpr int JB = 4;  // columns updated together (independent reductions in flight)
 
 // z <- H_k z for the reflector in column k (v_k = 1, v_i = A[i, k] below it; tk = 0: the identity).  A lane touches only its own rows
@@ -97,11 +143,12 @@ __device__ __forceinline__ void back_substitute(const double *A, int ld, int nc,
     }
 }
 
-template <int TW, bool LDS>
+template <int TW, bool LDS, bool TAN>
 __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, const int32_t *__restrict__ nodes, int32_t count, int add_neumann,
-                                                                 const double *__restrict__ grad_csr, const double *__restrict__ grad_nws,
-                                                                 double *__restrict__ contrib, double *scratch, long long scratch_stride) {
+                                                                 AdjointIo io, double *scratch, long long scratch_stride) {
     extern __shared__ double smem[];
+    const double *__restrict__ const grad_csr = io.grad_csr, *__restrict__ const grad_nws = io.grad_nws;
+    double *__restrict__ const contrib = io.contrib;
     const int tid = threadIdx.x, nthr = 64 * TW;
     const int lane = tid & 63;
     const int wave = ufirst(tid >> 6);
@@ -125,7 +172,14 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
         const int m = ne + 3 * n_if + (is_neu ? n_bf : 0);     // rows actually populated
         // the forward's zero rows (kernels_gls.hip): nothing depends on K there
         if (((fl & 1) && !is_neu) || n_if == 0 || m < n - 1) {
-            for (int i = tid; i < 10 * ne; i += nthr) contrib[10 * (size_t)eb + i] = 0.0;
+            if constexpr (TAN) {
+                for (int t = 0; t < io.n_tan; ++t) {
+                    for (int i = tid; i < ne; i += nthr) io.tan_csr[(size_t)t * io.nnz + eb + i] = 0.0;
+                    if (io.tan_nws && tid == 0) io.tan_nws[(size_t)t * g.n_points + p] = 0.0;
+                }
+            } else {
+                for (int i = tid; i < 10 * ne; i += nthr) contrib[10 * (size_t)eb + i] = 0.0;
+            }
             continue;
         }
         const int ld = m;
@@ -278,28 +332,120 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
                 for (int i = lane; i < ne; i += 64) fin = fin && isfinite(rv[i] / rho);
                 ok = ok && __ballot(!fin) == 0ull;
             }
-            // g and rbar (into q)
-            double gsum = 0.0;
-            for (int i = lane; i < ne; i += 64) gsum += grad_csr[eb + i];
-            gsum = wave_sum(gsum);
-            const double extra = is_neu ? (add_neumann ? gsum : 0.0) + (grad_nws ? grad_nws[p] : 0.0) : 0.0;
-            double gr = 0.0;
-            for (int i = lane; i < ne; i += 64) gr += (grad_csr[eb + i] + (i == ne - 1 ? extra : 0.0)) * rv[i];
-            gr = wave_sum(gr);
-            const double irho = 1.0 / rho, c2 = 2.0 * gr * irho * irho;
-            for (int i = lane; i < m; i += 64) {
-                const double gi = i < ne ? grad_csr[eb + i] + (i == ne - 1 ? extra : 0.0) : 0.0;
-                qv[i] = gi * irho - c2 * rv[i];
+            if constexpr (TAN) {   // (tau and y hold n words, the reflectors and y n - 1: the last words carry the verdict and rho)
+                if (lane == 0) { tau[n - 1] = ok ? 1.0 : 0.0; y[n - 1] = rho; }
+            } else {
+                // g and rbar (into q)
+                double gsum = 0.0;
+                for (int i = lane; i < ne; i += 64) gsum += grad_csr[eb + i];
+                gsum = wave_sum(gsum);
+                const double extra = is_neu ? (add_neumann ? gsum : 0.0) + (grad_nws ? grad_nws[p] : 0.0) : 0.0;
+                double gr = 0.0;
+                for (int i = lane; i < ne; i += 64) gr += (grad_csr[eb + i] + (i == ne - 1 ? extra : 0.0)) * rv[i];
+                gr = wave_sum(gr);
+                const double irho = 1.0 / rho, c2 = 2.0 * gr * irho * irho;
+                for (int i = lane; i < m; i += 64) {
+                    const double gi = i < ne ? grad_csr[eb + i] + (i == ne - 1 ? extra : 0.0) : 0.0;
+                    qv[i] = gi * irho - c2 * rv[i];
+                }
+                // s = R^-1 (Q^T rbar)(0:n-1);  q = Q [0; (Q^T rbar)(n-1:m)]
+                for (int k = 0; k < n - 1; ++k) reflect(A, ld, m, k, tau[k], qv, lane);
+                for (int i = lane; i < n - 1; i += 64) { sv[i] = qv[i]; qv[i] = 0.0; }
+                for (int k = n - 2; k >= 0; --k) reflect(A, ld, m, k, tau[k], qv, lane);
+                wave_sync<LDS>();
+                back_substitute<LDS>(A, ld, n - 1, sv, lane);
+                if (lane == 0) tau[0] = ok ? 1.0 : 0.0;   // (tau is done with: its first word carries the verdict to the other waves)
             }
-            // s = R^-1 (Q^T rbar)(0:n-1);  q = Q [0; (Q^T rbar)(n-1:m)]
-            for (int k = 0; k < n - 1; ++k) reflect(A, ld, m, k, tau[k], qv, lane);
-            for (int i = lane; i < n - 1; i += 64) { sv[i] = qv[i]; qv[i] = 0.0; }
-            for (int k = n - 2; k >= 0; --k) reflect(A, ld, m, k, tau[k], qv, lane);
-            wave_sync<LDS>();
-            back_substitute<LDS>(A, ld, n - 1, sv, lane);
-            if (lane == 0) tau[0] = ok ? 1.0 : 0.0;   // (tau is done with: its first word carries the verdict to the other waves)
         }
         __syncthreads();
+
+        if constexpr (TAN) {
+            // ---- the tangent tail: per direction z1 = dA y (into q), z2 = dA^T r (into s), then wavefront 0 -----------------------
+            const bool ok = tau[n - 1] != 0.0;   // uniform: every thread reads the same word
+            const double rho = y[n - 1];
+            for (int t = 0; t < io.n_tan; ++t) {   // (n_tan is a kernel argument: the barriers below are reached by every wave)
+                const double *dK = io.tan_perm + (size_t)t * 9 * (size_t)g.n_elems;
+                const double *dm = io.tan_dm ? io.tan_dm + (size_t)t * (size_t)g.n_elems : nullptr;
+                // z1: the cell rows hold no K; a thread per face fills the face's rows
+                for (int i = tid; i < ne; i += nthr) qv[i] = 0.0;
+                for (int fi = tid; ok && fi < nf; fi += nthr) {
+                    const int row = frow[fi], Ia = fia[fi], Ib = fib[fi];
+                    if (row < 0) continue;
+                    const size_t f = (size_t)g.fsup[fb + fi];
+                    const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
+                    const size_t ca = (size_t)cells[Ia];
+                    double z = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) z -= tangent_kn(dK, ca, c, N0, N1, N2) * y[3 * Ia + c];
+                    if (Ib < 0) { qv[row] = z; continue; }   // a Neumann boundary face: one row
+                    const size_t cb = (size_t)cells[Ib];
+                    double U[3];
+                    const double dtau = tangent_dtau(g, f, xv0, xv1, xv2, N0, N1, N2, ca, cb, dK, dm, U);
+                    double zu = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        z += tangent_kn(dK, cb, c, N0, N1, N2) * y[3 * Ib + c];
+                        zu += U[c] * (y[3 * Ib + c] - y[3 * Ia + c]);
+                    }
+                    qv[row] = z; qv[row + 1] = 0.0; qv[row + 2] = dtau * zu;
+                }
+                // z2: thread i = cell i of the node, the node's faces in fsup order (the contributions loop read the other way)
+                for (int i = tid; ok && i < ne; i += nthr) {
+                    double z[3] = {0.0, 0.0, 0.0};
+                    for (int fi = 0; fi < nf; ++fi) {
+                        const int row = frow[fi], Ia = fia[fi], Ib = fib[fi];
+                        if (row < 0 || (Ia != i && Ib != i)) continue;
+                        const size_t f = (size_t)g.fsup[fb + fi];
+                        const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
+                        const double sign = Ia == i ? -1.0 : 1.0;
+                        const double rt = rv[row];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) z[c] += sign * tangent_kn(dK, (size_t)cells[i], c, N0, N1, N2) * rt;
+                        if (Ib < 0) continue;
+                        double U[3];
+                        const double dtau = tangent_dtau(g, f, xv0, xv1, xv2, N0, N1, N2, (size_t)cells[Ia], (size_t)cells[Ib], dK, dm, U);
+                        const double r2 = sign * dtau * rv[row + 2];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) z[c] += r2 * U[c];
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sv[3 * i + c] = z[c];
+                }
+                __syncthreads();
+                if (wave == 0) {
+                    double *oc = io.tan_csr + (size_t)t * (size_t)io.nnz + eb;
+                    double dnws = 0.0;
+                    if (ok) {
+                        for (int k = 0; k < n - 1; ++k) reflect(A, ld, m, k, tau[k], qv, lane);   // Q^T z1
+                        // x = R^-T z2 by columns of R: x_k = (z2_k - R(0:k, k) . x(0:k)) / R(k, k)
+                        for (int k = 0; k < n - 1; ++k) {
+                            const double *col = A + (size_t)k * ld;
+                            double s = 0.0;
+                            for (int i = lane; i < k; i += 64) s += col[i] * sv[i];
+                            s = wave_sum(s);
+                            if (lane == (k & 63)) sv[k] = (sv[k] - s) / col[k];
+                            wave_sync<LDS>();
+                        }
+                        for (int i = lane; i < n - 1; i += 64) qv[i] = sv[i];
+                        wave_sync<LDS>();
+                        for (int k = n - 2; k >= 0; --k) reflect(A, ld, m, k, tau[k], qv, lane);   // q = Q [x; (Q^T z1)(n-1:m)] = -dr
+                        wave_sync<LDS>();
+                        double rq = 0.0;
+                        for (int i = lane; i < m; i += 64) rq += rv[i] * qv[i];
+                        rq = wave_sum(rq);
+                        const double irho = 1.0 / rho, c2 = -2.0 * rq * irho * irho;   // drho / rho^2
+                        if (is_neu) dnws = -(qv[ne - 1] * irho) - c2 * rv[ne - 1];
+                        const double add = add_neumann ? dnws : 0.0;
+                        for (int i = lane; i < ne; i += 64) oc[i] = (-(qv[i] * irho) - c2 * rv[i]) + add;
+                    } else {
+                        for (int i = lane; i < ne; i += 64) oc[i] = 0.0;
+                    }
+                    if (io.tan_nws && lane == 0) io.tan_nws[(size_t)t * g.n_points + p] = dnws;
+                }
+                __syncthreads();   // (q and s are the next direction's, the slot the next node's)
+            }
+            continue;
+        }
 
         // ---- contributions: thread i = cell i of the node, the node's faces in fsup order ------------------------------------
         const bool ok = tau[0] != 0.0;
@@ -382,15 +528,15 @@ __global__ __launch_bounds__(256) void nin_adjoint_gather_kernel(int32_t n_elems
     for (int k = 0; k < 9; ++k) grad_perm[9 * (size_t)e + k] = acc[k];
 }
 
-template <int TW, bool LDS>
-int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const double *grad_csr,
-               const double *grad_nws, double *contrib, double *scratch, int64_t stride, int32_t slots, hipStream_t stream) {
-    auto kern = nin_gls_adjoint_kernel<TW, LDS>;
+template <int TW, bool LDS, bool TAN>
+int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io, double *scratch,
+               int64_t stride, int32_t slots, hipStream_t stream) {
+    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN>;
     int64_t blocks;
     size_t lds = 0;
     if (LDS) {
         lds = (size_t)bytes;
-        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS>>(lds)) return -3;
+        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN>>(lds)) return -3;
         int64_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : (int64_t)lds);
         if (per_cu > 32 / TW) per_cu = 32 / TW;
         if (per_cu < 1) per_cu = 1;
@@ -399,9 +545,24 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
         blocks = slots;   // one scratch slot per workgroup
     }
     if (blocks > count) blocks = count;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * TW), lds, stream, g, nodes, count, add_neumann, grad_csr, grad_nws, contrib,
-                       scratch, (long long)stride);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * TW), lds, stream, g, nodes, count, add_neumann, io, scratch, (long long)stride);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// one bin's nodes through the class of that bin: 1, 2, 4 wavefronts in LDS, 8 over a global-memory slot
+template <bool TAN>
+int launch_bin_of(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io,
+                  double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
+    if (count <= 0) return 0;
+    switch (bin) {
+        case 0: return launch_bin<1, true, TAN>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 1: return launch_bin<2, true, TAN>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 2: return launch_bin<4, true, TAN>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 3:
+            if (!scratch || scratch_slots < 1 || scratch_stride * 8 < bytes) return -1;
+            return launch_bin<8, false, TAN>(g, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+    }
+    return -1;
 }
 
 }  // namespace
@@ -415,16 +576,18 @@ int launch_adjoint_bytes(const GridView &g, int64_t *bytes, hipStream_t stream) 
 int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const double *grad_csr,
                        const double *grad_nws, double *contrib, double *scratch, int64_t scratch_stride, int32_t scratch_slots,
                        hipStream_t stream) {
-    if (count <= 0) return 0;
-    switch (bin) {
-        case 0: return launch_bin<1, true>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, nullptr, 0, 0, stream);
-        case 1: return launch_bin<2, true>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, nullptr, 0, 0, stream);
-        case 2: return launch_bin<4, true>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, nullptr, 0, 0, stream);
-        case 3:
-            if (!scratch || scratch_slots < 1 || scratch_stride * 8 < bytes) return -1;
-            return launch_bin<8, false>(g, nodes, count, bytes, add_neumann, grad_csr, grad_nws, contrib, scratch, scratch_stride, scratch_slots, stream);
-    }
-    return -1;
+    AdjointIo io{};
+    io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = contrib;
+    return launch_bin_of<false>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+}
+
+int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, int32_t n_tangents,
+                       const double *tangent_perm, const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz,
+                       double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
+    AdjointIo io{};
+    io.n_tan = n_tangents; io.tan_perm = tangent_perm; io.tan_dm = tangent_diff_mag; io.tan_csr = tangent_csr; io.tan_nws = tangent_nws;
+    io.nnz = (long long)nnz;
+    return launch_bin_of<true>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
 }
 
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,

@@ -128,6 +128,13 @@ int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t
                        hipStream_t stream);
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,
                           double *grad_diff_mag, hipStream_t stream);
+// launch_gls_tangent: the same kernel's tangent mode on the nodes of one bin -- n_tangents directions tangent_perm [n_tangents][E][9]
+//   (tangent_diff_mag [n_tangents][E], or null: folded from the resident g.perm) -> the directional derivative of the stored weights,
+//   tangent_csr [n_tangents][nnz] in esup position, and of neumann_ws, tangent_nws [n_tangents][P] or null; every row of every listed
+//   node is written
+int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, int32_t n_tangents,
+                       const double *tangent_perm, const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz,
+                       double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
 
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream);

@@ -881,6 +881,38 @@ class Interpolator:
         _lib.check(_lib.load().nin_gls_permeability_gradient_host(g._h, _ptr(v), _ptr(u), k, _ptr(out)))
         return out
 
+    def permeability_tangent(self, variable, dK, cell_values=None):
+        """The directional derivative of what `apply(variable, "gls")` returns, along a change `dK` of the permeability: `dK` one
+        direction (n_elems, 3, 3) or k of them as (k, n_elems, 3, 3); `cell_values` = u, (n_elems,) or (k, n_elems) alike (default: the
+        cell variable `variable` itself, for every direction).  Returns `(d_node_values, d_neumann_ws)`, each (n_points,) or
+        (k, n_points): `dW_f . u_f` for the GLS matrix W that apply() uses (the `+ neumann_ws[row]` included) and the derivative of its
+        neumann_ws, at the resident permeability table, the chain through diff_mag = (1 - 3 / tr K)^2 folded in.  On the device, the
+        sibling of permeability_gradient(): host-synchronous, numpy in and out; deterministic.  It is what a Newton-Krylov solver with
+        K(u) needs, `J . v` without differencing two weight launches.  Rows that are zero (Dirichlet nodes) have a zero derivative; the
+        Neumann values and the coordinates are not differentiated."""
+        self._check_call(variable=variable)
+        self._perm_rows()   # (ValueError without a permeability)
+        g = self.grid
+        d = np.ascontiguousarray(dK, dtype=DTYPE_F)
+        if d.shape != (g.n_elems, 3, 3) and not (d.ndim == 4 and d.shape[0] >= 1 and d.shape[1:] == (g.n_elems, 3, 3)):
+            raise ValueError(f"dK must have shape ({g.n_elems}, 3, 3) or (k, {g.n_elems}, 3, 3), not {d.shape}.")
+        lead = d.shape[:-3]
+        k = 1 if d.ndim == 3 else d.shape[0]
+        if cell_values is None:
+            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
+            u = np.ascontiguousarray(np.broadcast_to(u, (k, g.n_elems)), dtype=DTYPE_F)
+        else:
+            u = np.ascontiguousarray(cell_values, dtype=DTYPE_F)
+            if u.shape != lead + (g.n_elems,):
+                raise ValueError(f"cell_values must have shape {lead + (g.n_elems,)} beside dK of shape {d.shape}, not {u.shape}.")
+        if g.device < 0:
+            g.to_device(self.device)
+        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        out = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
+        nws = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_permeability_tangent_host(g._h, _ptr(d), _ptr(u), k, _ptr(out), _ptr(nws)))
+        return out, nws
+
     def release_scratch(self, pinned=True):
         """Give back what the object keeps between calls for speed: the grid's device scratch (weights, compacted
         triplets: ~2.3 GB of HBM at 10 M cells; the transpose index of apply_transpose(): 0.69 GB more) and, with pinned=True, the idle page-locked result buffers of the
@@ -1031,6 +1063,23 @@ class DevicePlan:
         vp = lambda a: ctypes.c_void_p(a) if a else None
         _lib.check(_lib.load().nin_gls_weights_backward_device(self.grid._h, int(bool(add_neumann)), vp(grad_csr_ptr), vp(grad_neumann_ws_ptr),
                                                                vp(grad_perm_ptr), vp(grad_diff_mag_ptr), ctypes.c_void_p(stream)))
+
+    def launch_weights_tangent(self, tangent_perm_ptr, tangent_csr_ptr, n_tangents=1, tangent_diff_mag_ptr=0, tangent_neumann_ws_ptr=0, stream=0,
+                               add_neumann=True):
+        """The directional derivative of the GLS weights in the permeability (nin_gls_weights_tangent_device): tangent_perm
+        [n_tangents][n_elems][9] = the directions dK -> tangent_csr [n_tangents][nnz_esup] = (d csr_data / dK) . dK for the csr_data of a
+        `launch(..., add_neumann)` at what is resident now, and tangent_neumann_ws [n_tangents][n_points] (0: not wanted) the same for
+        neumann_ws.  With tangent_diff_mag [n_tangents][n_elems] the table's diff_mag counts as an independent input with its own
+        direction; with 0 its chain is folded from the resident K.  All directions share one factorisation per node.  Every entry of
+        the outputs is written.  Asynchronous on `stream` after the first call on a grid (which makes the bins and synchronises); no
+        contribution buffer is allocated.  Only GLS depends on K."""
+        if self.method != "gls":
+            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: launch_weights_tangent is GLS only")
+        self.ensure_current()
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_weights_tangent_device(self.grid._h, int(bool(add_neumann)), int(n_tangents), vp(tangent_perm_ptr),
+                                                              vp(tangent_diff_mag_ptr), vp(tangent_csr_ptr), vp(tangent_neumann_ws_ptr),
+                                                              ctypes.c_void_p(stream)))
 
 
 class HostMatrix:

@@ -1,7 +1,9 @@
 """torch autograd for the interpolation operator: `CellToNode(interp, variable, method)(u)` is `W . u` on the device, and its
 backward pass is `W^T . grad` (nin_spmv_device / nin_spmv_transpose_device), both on torch's current stream.  `CellToNode(...)(u, K)`
 also makes the GLS weights a function of the permeability tensor K: its backward pass returns dL/dK through the sampled product
-(nin_sddmm_device) and the adjoint of the weight kernels (nin_gls_weights_backward_device).
+(nin_sddmm_device) and the adjoint of the weight kernels (nin_gls_weights_backward_device).  Under torch.autograd.forward_ad (dual
+tensors) the same call gives the forward derivative, W du + dW u, with dW from the tangent of the weight kernels
+(nin_gls_weights_tangent_device); torch.func.jvp, which needs setup_context-style Functions, is not supported.
 
 Not imported by `ninpol_amd/__init__.py`: importing the package loads nothing native and does not import torch.  This module
 imports torch, and opens its device, before the native library loads ("A process that also uses a PyTorch-ROCm
@@ -23,7 +25,21 @@ class _CellToNodeFn(torch.autograd.Function):
     def forward(ctx, u, op, weights):
         ctx.op, ctx.weights = op, weights
         ctx.u = u if ctx.needs_input_grad[2] else None
+        ctx.save_for_forward(u, weights)
         return op._spmv(weights, u)
+
+    @staticmethod
+    def jvp(ctx, du, _, dweights):
+        """forward mode: d(W u) = W du + dW u, the second term when the weights carry a tangent (they are _GlsWeightsFn's output)"""
+        u, weights = ctx.saved_tensors
+        op = ctx.op
+        out = None
+        if du is not None:
+            out = op._spmv(weights, du.contiguous())
+        if dweights is not None:
+            t = op._spmv(dweights.contiguous(), u)
+            out = t if out is None else out + t
+        return out
 
     @staticmethod
     def backward(ctx, grad):
@@ -47,8 +63,42 @@ class _GlsWeightsFn(torch.autograd.Function):
         w, nws = op._launch_weights()
         ctx.op, ctx.stamp = op, op._stamp()
         ctx.save_for_backward(K, scale)
+        ctx.save_for_forward(K, scale)
         ctx.set_materialize_grads(False)
         return w, nws
+
+    @staticmethod
+    def _check_stamp(ctx, what, call):
+        now = ctx.op._stamp()
+        if now != ctx.stamp:
+            names = ("field_updates", "geometry_updates", "flag_updates")
+            moved = ", ".join(f"{n} {a} -> {b}" for n, a, b in zip(names, ctx.stamp, now) if a != b)
+            raise RuntimeError("the grid's resident permeability, geometry or Neumann flags were updated after the forward pass "
+                               f"({moved}): the {what} with respect to K would be taken at another point.  Run {call} before "
+                               "the next update, or the forward pass again.")
+
+    @staticmethod
+    def jvp(ctx, dK, dscale, _):
+        """forward mode (torch.autograd.forward_ad): the tangent of perm = scale * K is scale * dK + dscale * K, a missing tangent
+        counts as zero; one DevicePlan.launch_weights_tangent call gives (dW, dneumann_ws).  Autograd calls this right behind
+        forward(); like backward() it reads what is resident and refuses once that was updated."""
+        K, scale = ctx.saved_tensors
+        op = ctx.op
+        _GlsWeightsFn._check_stamp(ctx, "tangent", "jvp()")
+        E = op.n_elems
+        tperm = None
+        if dK is not None:
+            tperm = dK.reshape(E, 9) if scale is None else dK.reshape(E, 9) * scale[:, None]
+        if dscale is not None and scale is not None:
+            t = K.reshape(E, 9) * dscale[:, None]
+            tperm = t if tperm is None else tperm + t
+        dw = torch.empty(op.plan.nnz, dtype=torch.float64, device=op.device)
+        dnws = torch.empty(op.n_points, dtype=torch.float64, device=op.device)
+        if tperm is None:
+            return dw.zero_(), dnws.zero_()
+        tperm = tperm.contiguous()
+        op.plan.launch_weights_tangent(tperm.data_ptr(), dw.data_ptr(), 1, 0, dnws.data_ptr(), op._stream(), add_neumann=True)
+        return dw, dnws
 
     @staticmethod
     def backward(ctx, gw, gnws):
@@ -56,13 +106,7 @@ class _GlsWeightsFn(torch.autograd.Function):
         op = ctx.op
         if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return None, None, None
-        now = op._stamp()
-        if now != ctx.stamp:
-            names = ("field_updates", "geometry_updates", "flag_updates")
-            moved = ", ".join(f"{n} {a} -> {b}" for n, a, b in zip(names, ctx.stamp, now) if a != b)
-            raise RuntimeError("the grid's resident permeability, geometry or Neumann flags were updated after the forward pass "
-                               f"({moved}): the gradient with respect to K would be taken at another point.  Run backward() before "
-                               "the next update, or the forward pass again.")
+        _GlsWeightsFn._check_stamp(ctx, "gradient", "backward()")
         E = op.n_elems
         gperm = torch.empty((E, 9), dtype=torch.float64, device=op.device)
         if gw is None:
@@ -86,7 +130,12 @@ class _ConstantWeightsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, scale, weights):
         ctx.save_for_backward(K, scale)
+        ctx.save_for_forward(weights)
         return weights.detach().clone()
+
+    @staticmethod
+    def jvp(ctx, dK, dscale, _):
+        return torch.zeros_like(ctx.saved_tensors[0])
 
     @staticmethod
     def backward(ctx, gw):
@@ -107,8 +156,10 @@ class CellToNode(torch.nn.Module):
     `interp.update_permeability(K_dev)` followed by `recompute_weights()`: the weight kernels run again on torch's current stream
     from whatever is resident -- geometry and permeability -- with no table re-read, no hash and no synchronisation.
 
-    The derivative with respect to the permeability comes through `forward(u, K, scale)` (GLS; see there) or `weights_of(K, scale)`.
-    Derivatives with respect to the Neumann values or the node coordinates are not provided."""
+    The derivative with respect to the permeability comes through `forward(u, K, scale)` (GLS; see there) or `weights_of(K, scale)`,
+    backwards (backward()) and forwards (torch.autograd.forward_ad: dual u, K, scale in any combination).
+    Derivatives with respect to the Neumann values or the node coordinates are not provided, nor are those of the sharded
+    (multi-GPU) path; the tangent is that of a full launch (recompute_weights(dirty_only=True) carries none)."""
 
     def __init__(self, interp, variable, method):
         super().__init__()
@@ -186,7 +237,9 @@ class CellToNode(torch.nn.Module):
         tensors on torch's current stream.  GLS: backward gives dL/dK = scale * dL/dperm and dL/dscale = sum(K * dL/dperm) through
         DevicePlan.launch_weights_backward, which reads the resident geometry, flags and permeability -- so backward raises
         RuntimeError if Grid.field_updates, geometry_updates or flag_updates moved after this call (another weights_of /
-        forward(u, K) included): run each backward before the next update.  IDW / LS: the module's weights, and zeros for K."""
+        forward(u, K) included): run each backward before the next update.  Under forward_ad.dual_level() dual K / scale give the
+        weights' tangent along scale * dK + dscale * K through DevicePlan.launch_weights_tangent.  IDW / LS: the module's weights, and
+        zeros for K."""
         if not isinstance(K, torch.Tensor):
             raise TypeError(f"K must be a torch.Tensor on {self.device}, not {type(K).__name__}")
         if K.device != self.device:

@@ -5,7 +5,10 @@ Per mesh: the bins of the adjoint kernel (Grid.gls_adjoint_plan), then HIP event
   the whole backward (DevicePlan.launch_weights_backward: the four bins' kernels + the gather),
   the gather alone and every bin alone (NIN_GLS_ADJ_ONLY, which the library reads at every call; the gather runs behind each and is
   subtracted),
-WARMUP calls first, median of REPS each; ms and ns per node of the bin."""
+WARMUP calls first, median of REPS each; ms and ns per node of the bin.
+
+--tangent: instead of the per-bin part, the tangent (DevicePlan.launch_weights_tangent) with n_tangents = 1 and 4 beside
+the forward launch and the backward of the same session: ms, ns per node, the ratio to the backward, each direction beyond the first."""
 import os
 import sys
 
@@ -67,6 +70,24 @@ def main():
         t_bwd = median_ms(backward, st)
         print(f"{name}: forward launch {t_fwd:.3f} ms = {t_fwd * 1e6 / P:.1f} ns/node; backward {t_bwd:.3f} ms = {t_bwd * 1e6 / P:.1f} ns/node; "
               f"backward / forward = {t_bwd / t_fwd:.1f}", flush=True)
+        if "--tangent" in sys.argv:
+            del gperm, ghat
+            I.release_scratch()                            # the backward's contribution buffer goes: the tangent needs none
+            t_tan = {}
+            for k in (1, 4):
+                dK = torch.rand((k, E, 9), dtype=torch.float64, device="cuda") - 0.5
+                dw = torch.empty((k, plan.nnz), dtype=torch.float64, device="cuda")
+                dn = torch.empty((k, P), dtype=torch.float64, device="cuda")
+                tangent = lambda: plan.launch_weights_tangent(dK.data_ptr(), dw.data_ptr(), k, 0, dn.data_ptr(), st.cuda_stream)
+                t_tan[k] = median_ms(tangent, st)
+                assert torch.isfinite(dw).all() and torch.isfinite(dn).all()
+                print(f"{name}: tangent, n_tangents = {k}: {t_tan[k]:.3f} ms = {t_tan[k] * 1e6 / P:.1f} ns/node; / backward = "
+                      f"{t_tan[k] / t_bwd:.2f}; / forward = {t_tan[k] / t_fwd:.1f}", flush=True)
+                del dK, dw, dn
+            print(f"{name}: each direction beyond the first {(t_tan[4] - t_tan[1]) / 3:.3f} ms = {(t_tan[4] - t_tan[1]) / 3 * 1e6 / P:.1f} ns/node; "
+                  f"contribution buffer allocated: {g._scalar('gls_adjoint_contrib_bytes')} bytes", flush=True)
+            del plan, I
+            continue
         try:
             os.environ["NIN_GLS_ADJ_ONLY"] = "9"          # no bin: the gather alone
             t_gather = median_ms(backward, st)
