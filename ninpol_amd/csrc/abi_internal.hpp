@@ -161,6 +161,8 @@ int gls_side_begin(DeviceGrid &d, int piece, int add_neumann, double *out, doubl
 int gls_main(DeviceGrid &d, int piece, bool cube, int only, int add_neumann, double *out, double *nws, hipStream_t stream);
 int launch_lists(DeviceGrid &d, int method, const int32_t *lists, const int32_t *off, uint32_t *desc, const size_t *desc_first,
                  int add_neumann, double *out, double *nws, hipStream_t stream, DirtyLaps *laps);
+// a count of descriptor words rounded up to a 16-byte boundary: where launch_lists' callers let a kernel's descriptors begin
+inline size_t desc_align(size_t words) { return (words + 3) & ~(size_t)3; }
 // abi_update.hip: the host's copy of the resident flag bytes (flag_staging), brought up to date
 int fetch_flag_bytes(nin_grid *g);
 // abi_apply.hip: the adjoint's and the tangent's bins and scratch slots, and the adjoint's contribution buffer, given back

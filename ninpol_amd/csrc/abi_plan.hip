@@ -323,7 +323,8 @@ int nin::gls_main(DeviceGrid &d, int piece, bool cube, int only, int add_neumann
 }
 
 // The plan's kernels on lists of their own nodes, not the plan's: kernel k takes lists[off[k] .. off[k + 1]) and writes its
-// descriptors to desc + desc_first[k] first (one descriptor launch per non-empty list, not per family: a few tiny launches more);
+// descriptors to desc + desc_first[k] first (one descriptor launch per non-empty list, not per family: a few tiny launches more;
+// desc and every desc_first[k] on a 16-byte boundary, desc_align(): the cube-node kernel fetches its records 16 bytes at a time);
 // IDW / LS take all off[kGlsPlanKernels] entries as one list.  No side stream: every listed row is written by exactly one kernel,
 // in any order.  laps: the dirty launch's marks (null: none).
 int nin::launch_lists(DeviceGrid &d, int method, const int32_t *lists, const int32_t *off, uint32_t *desc, const size_t *desc_first,
@@ -391,16 +392,17 @@ int nin_weights_device(nin_grid *g, int method, const int64_t *targets, int64_t 
     size_t desc_first[kGlsPlanKernels], words = 0;         // where its descriptors begin, behind the lists
     for (int k = 0; k < kGlsPlanKernels; ++k) {
         off[k] = (int32_t)flat.size();
-        desc_first[k] = words;
+        desc_first[k] = words = desc_align(words);
         flat.insert(flat.end(), lists[k].begin(), lists[k].end());
         if (gls) words += lists[k].size() * (size_t)gls_plan_row(k).desc_words;
     }
     off[kGlsPlanKernels] = (int32_t)flat.size();
+    const size_t list_words = desc_align(flat.size());     // (the descriptors begin on a 16-byte boundary)
     DevTmp<int32_t> dl0;
-    HIP_TRY(hipMalloc((void **)&dl0, (flat.size() + words) * 4));
+    HIP_TRY(hipMalloc((void **)&dl0, (list_words + words) * 4));
     const hipError_t e = hipMemcpy(dl0, flat.data(), flat.size() * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(NIN_EHIP, "hipMemcpy: %s", hipGetErrorString(e));
-    rc = launch_lists(d, method, dl0, off, reinterpret_cast<uint32_t *>(dl0 + flat.size()), desc_first, add_neumann, dev_csr_data,
+    rc = launch_lists(d, method, dl0, off, reinterpret_cast<uint32_t *>(dl0 + list_words), desc_first, add_neumann, dev_csr_data,
                       dev_neumann_ws, stream, nullptr);
     const hipError_t sy = hipStreamSynchronize(stream);   // the lists must outlive the kernels: dl0 goes after this
     if (sy != hipSuccess) return fail(NIN_EHIP, "target kernels: %s", hipGetErrorString(sy));

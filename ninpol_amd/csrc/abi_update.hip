@@ -417,7 +417,7 @@ int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *d
     size_t desc_first[kGlsPlanKernels], words = 0;
     for (int k = 0; gls && k < kGlsPlanKernels; ++k) {   // (IDW / LS: one list, no descriptors)
         if (off[k + 1] < off[k]) return fail(NIN_EHIP, "the dirty set's lists are out of order");
-        desc_first[k] = words;
+        desc_first[k] = words = desc_align(words);
         words += (size_t)(off[k + 1] - off[k]) * (size_t)gls_plan_row(k).desc_words;
     }
     if (words > d.dirty_desc_words && (rc = grow(d, &d.dirty_desc, &d.dirty_desc_words, words + words / 2))) return rc;

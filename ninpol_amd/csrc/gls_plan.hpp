@@ -79,7 +79,7 @@ struct GlsPlanRow {
     int16_t counter;      // the kernel's work counter: an offset into gls_queue; -1: the kernel takes none
 };
 // (the descriptor sizes are mfw_desc / mfx_desc / mfg_desc.hpp's kM*DescWords: those headers include this one, abi_plan.hip asserts the match)
-constexpr int kGlsDescHex8 = 4, kGlsDescQuad4 = 2, kGlsDescMfw = 40, kGlsDescMfx = 56, kGlsDescMfg = 124;
+constexpr int kGlsDescHex8 = 32, kGlsDescQuad4 = 2, kGlsDescMfw = 40, kGlsDescMfx = 56, kGlsDescMfg = 124;
 
 NIN_HD constexpr GlsPlanRow gls_plan_row(int k) {
     using F = GlsFamily;

@@ -579,7 +579,7 @@ __global__ void k_classify(GridView g, int use_group, int force_global, uint8_t 
     for (int32_t q = g.fsup_ptr[p]; q < g.fsup_ptr[p + 1]; ++q) nbf += g.face_cells[2 * (int64_t)g.fsup[q] + 1] == -1;
     if ((use_group & kRouteHex8) && ne == 8 && nf == 12 && nbf == 0 && g.dim == 3) {
         int32_t d[4];   // the hex8 kernel needs the cells to form the cube graph (hex8_desc.hpp)
-        if (hex8_descriptor(g, (int32_t)p, d)) { node_class[p] = gls_class_byte(gk::hex8); return; }
+        if (hex8_descriptor<false>(g, (int32_t)p, d)) { node_class[p] = gls_class_byte(gk::hex8); return; }
     }
     // (general-kind nodes that fit the small-node kernel -- pyramid apexes: 7 cells, 43 rows -- are cheaper there: 26.64 -> 26.54 ms
     //  on BASELINE config [3])

@@ -11,10 +11,18 @@
 //   O_(3-l) = the odd cell NOT adjacent to E_l,
 //   lane l of the node's quad works on E_l, owns the cell row of O_l, and holds the 3 faces of E_l ordered by the
 //   odd slot of the cell on their other side (ascending: the slots {0,1,2,3} \ {3 - l}).
-// One 32-bit word per lane:
+// One 32-bit descriptor word per lane:
 //   bits 0-2   position of E_l in the node's esup row        bits 3-5   position of O_l
 //   bits 6+8i .. 13+8i (i = 0,1,2), face i of E_l:  4 bits position in the fsup row, 3 bits position of the
 //   neighbour cell in the esup row, 1 bit "E_l is the first cell (side a) of the face" (row = [-B_a | +B_b]).
+//
+// The launch plan keeps one GATHER RECORD per lane, eight whole int32s (32 bytes):
+//   { p, eb, ce, co, f0, f1, f2, dsc }
+//   p = the node, eb = esup_ptr[p], ce / co = the cells E_l / O_l, f0 .. f2 = the lane's three faces in the order above,
+//   dsc = the descriptor word.  Entry i of a list, lane l: words 8 (4 i + l) .. + 7 -- the 16 nodes of a wavefront's pass are
+//   one contiguous 2 KiB block, which the kernel fetches with two 16-byte LDS-DMAs per lane instead of walking
+//   list -> esup_ptr / fsup_ptr -> esup / fsup on every pass of every launch.  The record holds connectivity only: no
+//   geometry, no permeability, no flags, so it stands for as long as the mesh topology does.
 #pragma once
 #include <cstdint>
 
@@ -22,10 +30,14 @@
 
 namespace nin {
 
-constexpr int kHex8DescWords = 4;   // descriptor words per list entry (gls_plan.hpp holds the same figure; abi_plan.hip asserts the match)
+constexpr int kHex8LaneWords = 8;                    // words of a lane's gather record
+constexpr int kHex8DescWords = 4 * kHex8LaneWords;   // words per list entry (gls_plan.hpp holds the same figure; abi_plan.hip asserts the match)
 
 #ifdef __HIPCC__
-__device__ inline bool hex8_descriptor(const GridView &g, int32_t p, int32_t d[kHex8DescWords]) {
+// RECORD = false: d[4], the four descriptor words (k_classify: the verdict is all it wants, it pays for no ids);
+// RECORD = true: d[kHex8DescWords], the four gather records
+template <bool RECORD>
+__device__ inline bool hex8_descriptor(const GridView &g, int32_t p, int32_t *d) {
     const int32_t eb = g.esup_ptr[p], fb = g.fsup_ptr[p];
     if (g.esup_ptr[p + 1] - eb != 8 || g.fsup_ptr[p + 1] - fb != 12 || g.dim != 3) return false;
     int32_t cells[8];
@@ -92,7 +104,17 @@ __device__ inline bool hex8_descriptor(const GridView &g, int32_t p, int32_t d[k
                 if (sa > sb) { const int t = ord[y]; ord[y] = ord[y + 1]; ord[y + 1] = t; }
             }
         for (int i = 0; i < 3; ++i) w |= ((adj[e] >> (8 * ord[i])) & 0xFFu) << (6 + 8 * i);
-        d[l] = (int32_t)w;
+        if (RECORD) {
+            int32_t *r = d + kHex8LaneWords * l;
+            r[0] = p;
+            r[1] = eb;
+            r[2] = g.esup[eb + e];
+            r[3] = g.esup[eb + odd[l]];
+            for (int i = 0; i < 3; ++i) r[4 + i] = g.fsup[fb + ((w >> (6 + 8 * i)) & 15)];
+            r[7] = (int32_t)w;
+        } else {
+            d[l] = (int32_t)w;
+        }
     }
     return true;
 }

@@ -90,12 +90,16 @@ struct BackLoop<-1> {
 //     [slot][lane], no conflicts, no synchronisation -- until the panel and the face records are gone;
 //   * phase 2 forms each column's dot where it is used (the other wave fills the scalar chain's latency), with u and s in the
 //     LDS slots the fill entries have left;
-//   * the index levels of the next pass (list entry -> CSR row starts -> coordinates, cell / face ids) come in by LDS-DMA
-//     during this one (nothing in flight that the compiler could move or spill), one level at the top of the pass, after the
-//     face rows and at tile completion; its geometry and permeability by plain loads into registers ahead of phase-2 step 6,
-//     in flight until the top of the next pass (round 5: at the top of the pass itself, the wave waited ~3.3 k of its 23 - 24 k
-//     cycles for them).  A lane loads its own two cells only: the cell across face i is O_s of lane s of the quad, its K by
-//     DPP.  A per-XCD work queue (the SIMD issues its older wave first: equal shares finish 4.0 / 5.85 ms apart).
+//   * the ids of the next pass are ONE level: the launch plan's gather record of the lane (hex8_desc.hpp: node, esup row start,
+//     its two cells, its three faces, the descriptor word -- 32 bytes, the 16 nodes of a pass one contiguous 2 KiB block) comes in
+//     by two 16-byte LDS-DMAs per lane at tile completion, into the parking slots the tile has just left (nothing in flight that
+//     the compiler could move or spill); ahead of phase-2 step 6 the one wait for it, then the node's coordinates, the geometry
+//     and the permeability by plain loads into registers, in flight until the top of the next pass (round 5: at the top of the
+//     pass itself, the wave waited ~3.3 k of its 23 - 24 k cycles for them).  Until round 15 the wave
+//     walked list entry -> esup_ptr / fsup_ptr -> esup / fsup itself, three dependent levels of 30 dword DMAs and three full drains
+//     a pass, for ids that depend on the connectivity alone.  A lane loads its own two cells only: the cell across face i is O_s
+//     of lane s of the quad, its K by DPP.  A per-XCD work queue (the SIMD issues its older wave first: equal shares finish
+//     4.0 / 5.85 ms apart).
 // With two waves the SIMD is bound by instruction issue (FP64 at ~2.6 ns an instruction, everything else at ~1): every change
 // since the first version that fitted was a cut in instructions -- 4 159 -> 4 096 a pass, of them FP64 2 926 -> 2 426; executed
 // flops per node 20.5 k (kernel above) -> 16.7 k against 15.9 k algorithmic.  5.95 -> 4.8 .. 5.0 ms per launch at 216^3.
@@ -108,7 +112,7 @@ struct BackLoop<-1> {
 #define NIN_W2_COLUMN_FENCE() do { } while (0)
 #endif
 constexpr int W2_SLOTS = 35;                                  // 64-lane slots of 8 B per wave
-constexpr int W2_WAVE_DOUBLES = W2_SLOTS * 64 + NPW * 8 + 64;  // + the weights' staging + two dword rows (19 456 B per wave: two workgroups per CU)
+constexpr int W2_WAVE_DOUBLES = W2_SLOTS * 64 + NPW * 8;       // + the weights' staging (18 944 B per wave: two workgroups per CU)
 
 template <int K>
 __device__ __forceinline__ void p2_step_lean(double (&C)[NR][NC], double (&rinvq)[3], int l) {
@@ -186,10 +190,10 @@ __device__ __forceinline__ void w2_column(const double (&P)[10][3], const double
     }
 }
 
-// LDS-DMA of one dword per lane (lane i's word lands at row[i]); the compiler does not order LDS reads behind it: every
+// LDS-DMA of four dwords per lane (lane i's 16 bytes land at row + 4 i); the compiler does not order LDS reads behind it: every
 // consumer goes through w2_dma_wait()
-__device__ __forceinline__ void w2_dma(const void *gptr, uint32_t *row) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gptr, (__attribute__((address_space(3))) void *)row, 4, 0, 0);
+__device__ __forceinline__ void w2_dma16(const void *gptr, uint32_t *row) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gptr, (__attribute__((address_space(3))) void *)row, 16, 0, 0);
 }
 // (a scheduling fence on both sides: the scheduler would otherwise move the arithmetic that is to cover the DMA behind the wait)
 __device__ __forceinline__ void w2_dma_wait() {
@@ -197,42 +201,34 @@ __device__ __forceinline__ void w2_dma_wait() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
-// level 0 of group `wg`: list entry and descriptor word (past the end: a clamped, valid entry -- never stored)
-__device__ __forceinline__ void w2_stage_a(const int32_t *nodes, const int32_t *desc, int32_t wg, int32_t count, int nd, int l,
-                                           uint32_t *row_p, uint32_t *row_dsc) {
+// the gather records of group `wg` (hex8_desc.hpp), one per lane: words 0 .. 3 (p, eb, ce, co) to the first 1 KiB row, words 4 .. 7
+// (f0, f1, f2, dsc) to the second (past the end of the list: a clamped, valid entry -- never stored)
+constexpr int W2_REC_ROW = 256;   // dwords of a row of 64 x 16 bytes
+__device__ __forceinline__ void w2_stage_rec(const int32_t *rec, int32_t wg, int32_t count, int nd, int l, uint32_t *rows_r) {
     const int32_t idx = wg * NPW + nd;
     const uint32_t sel = (uint32_t)((idx >= 0 && idx < count) ? idx : count - 1);
-    w2_dma(nodes + sel, row_p);
-    w2_dma(desc + 4 * (size_t)sel + l, row_dsc);
+    const int32_t *r = rec + kHex8LaneWords * (4 * (size_t)sel + l);
+    w2_dma16(r, rows_r);
+    w2_dma16(r + 4, rows_r + W2_REC_ROW);
 }
-// level 1: CSR row starts
-__device__ __forceinline__ void w2_stage_b(const GridView &g, uint32_t p, uint32_t *rows_b) {
-    w2_dma(g.esup_ptr + p, rows_b);
-    w2_dma(g.fsup_ptr + p, rows_b + 64);
-}
-// level 2: the node's coordinates (as six dwords, rows 2 .. 7), the lane's two cells (8, 9) and its three faces (10 .. 12)
-__device__ __forceinline__ void w2_stage_c(const GridView &g, uint32_t p, uint32_t eb, uint32_t fb, uint32_t dsc, uint32_t *rows_n) {
-    const uint32_t *xw = reinterpret_cast<const uint32_t *>(g.coords) + 6 * (size_t)p;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) w2_dma(xw + k, rows_n + 64 * (2 + k));
-    w2_dma(g.esup + eb + (dsc & 7), rows_n + 64 * 8);
-    w2_dma(g.esup + eb + ((dsc >> 3) & 7), rows_n + 64 * 9);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) w2_dma(g.fsup + fb + ((dsc >> (6 + 8 * i)) & 15), rows_n + 64 * (10 + i));
-}
-// level 3, in registers: geometry and permeability of the lane's own two cells and its three faces.  The cell across face i
-// of lane l is O_s, s = i (i < 3 - l) or i + 1 (hex8_desc.hpp) -- the cell lane s owns -- so its K and diff_mag come from lane
-// s by a quad permutation where they are used (w2_across), not from memory.
+// What the record names, in registers: the node's coordinates and flags, geometry and permeability of the lane's own two cells and
+// its three faces.  The cell across face i of lane l is O_s, s = i (i < 3 - l) or i + 1 (hex8_desc.hpp) -- the cell lane s owns --
+// so its K and diff_mag come from lane s by a quad permutation where they are used (w2_across), not from memory.
 struct W2Geo {
     double Ke[9], dme, ce[3];      // E_l
     double Ko[9], dmo, co[3];      // O_l
     double fc[3][3];               // face centres
     float fn[3][3];                // face normals
+    double xv[3];                  // the node
     uint32_t flags;                // the node's
 };
-__device__ __forceinline__ void w2_stage_d(const GridView &g, const uint32_t *row_p, const uint32_t *rows_n, int lane, W2Geo &q) {
-    q.flags = g.flags[row_p[lane]];
-    const uint32_t ce = rows_n[64 * 8 + lane], co = rows_n[64 * 9 + lane];
+__device__ __forceinline__ void w2_stage_d(const GridView &g, const uint32_t *rows_r, int lane, W2Geo &q) {
+    const uint4 ra = *reinterpret_cast<const uint4 *>(rows_r + 4 * lane);                 // p, eb, ce, co
+    const uint4 rb = *reinterpret_cast<const uint4 *>(rows_r + W2_REC_ROW + 4 * lane);    // f0, f1, f2, dsc
+#pragma unroll
+    for (int t = 0; t < 3; ++t) q.xv[t] = g.coords[3 * (size_t)ra.x + t];
+    q.flags = g.flags[ra.x];
+    const uint32_t ce = ra.z, co = ra.w;
 #pragma unroll
     for (int k = 0; k < 9; ++k) { q.Ke[k] = g.perm[9 * (size_t)ce + k]; q.Ko[k] = g.perm[9 * (size_t)co + k]; }
     q.dme = g.diff_mag[ce];
@@ -241,7 +237,7 @@ __device__ __forceinline__ void w2_stage_d(const GridView &g, const uint32_t *ro
     for (int t = 0; t < 3; ++t) { q.ce[t] = g.centroids[3 * (size_t)ce + t]; q.co[t] = g.centroids[3 * (size_t)co + t]; }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const uint32_t f = rows_n[64 * (10 + i) + lane];
+        const uint32_t f = i == 0 ? rb.x : i == 1 ? rb.y : rb.z;
 #pragma unroll
         for (int t = 0; t < 3; ++t) { q.fn[i][t] = g.face_normal[3 * (size_t)f + t]; q.fc[i][t] = g.face_center[3 * (size_t)f + t]; }
     }
@@ -250,16 +246,12 @@ __device__ __forceinline__ void w2_stage_d(const GridView &g, const uint32_t *ro
 template <int I>
 __device__ __forceinline__ double w2_across(double v) { return dpp_mov<I == 0 ? 0x40 : I == 1 ? 0xA5 : 0xFE>(v); }
 
-// Where the levels of the NEXT pass are requested (each waits for the one before with w2_dma_wait()): level 0 at the top of
-// the pass, 1 after the face rows (W2_B_LATE: after phase 1), 2 ahead of phase-2 step W2_C_STEP (0: at tile completion),
-// 3 ahead of step W2_D_STEP; level 3 is in flight from there to the top of the next pass.
-#ifndef W2_C_STEP
-#define W2_C_STEP 0
-#endif
+// Where the NEXT pass is requested: its records at tile completion, what they name -- coordinates, geometry, permeability --
+// ahead of phase-2 step W2_D_STEP, behind the pass's one wait for the records; in flight from there to the top of the next pass.
 #ifndef W2_D_STEP
 #define W2_D_STEP 6
 #endif
-static_assert(W2_C_STEP >= 0 && W2_C_STEP < W2_D_STEP && W2_D_STEP <= 12, "level 2 before level 3, both in phase 2");
+static_assert(W2_D_STEP >= 0 && W2_D_STEP <= 12, "the geometry is requested in phase 2");
 
 #ifdef NIN_W2_TRACE
 __device__ unsigned long long nin_w2_trace[4096 * 4];   // per wave: start, end (s_memrealtime, 100 MHz), HW_ID, passes
@@ -273,9 +265,10 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
                                                                 double *__restrict__ nws, int32_t *__restrict__ queue,
                                                                 const double *__restrict__ u_cells, int32_t n_fields,
                                                                 double *__restrict__ values) {
-    __shared__ double lds_all[4][W2_WAVE_DOUBLES];
-    // the tables of face_tau_tab_t, once per workgroup: 3 328 B beside the four waves' 77 824 -- 81 152 B a workgroup, 162 304 of
-    // the CU's 163 840 for the two that are resident (W2_WAVE_DOUBLES stays as it is; 1 536 B are left)
+    __shared__ __attribute__((aligned(16))) double lds_all[4][W2_WAVE_DOUBLES];
+    static_assert(W2_WAVE_DOUBLES % 2 == 0, "a wave's slots begin on a 16-byte boundary (the records' rows)");
+    // the tables of face_tau_tab_t, once per workgroup: 3 328 B beside the four waves' 75 776 -- 79 104 B a workgroup, 158 208 of
+    // the CU's 163 840 for the two that are resident (5 632 B are left)
     __shared__ double tau_tab[TAU_TAB_DOUBLES];
     static_assert(2 * (sizeof(double) * (4 * W2_WAVE_DOUBLES + TAU_TAB_DOUBLES)) <= 160 * 1024, "two workgroups per CU");
     tau_table_to_lds(tau_tab);
@@ -285,15 +278,11 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
     const int l = lane & 3, nd = lane >> 2;
     double *const L = lds_all[wave] + lane;                   // slot k of this lane: L[64 k]
     double *const wbuf = lds_all[wave] + W2_SLOTS * 64;
-    // The index levels of the NEXT pass (list entry -> CSR row starts -> coordinates, cell / face ids) come in by LDS-DMA
-    // (global_load_lds_dword: lane i's word lands at row[i]; no register is in flight, nothing the compiler could move or
-    // spill): rows of 64 dwords.  (p, dsc) have rows of their own; the CSR row starts land in the weights' staging, which is
-    // free until the weights; coordinates and ids in parking slots 13 .. 19, which are free from the moment the tile is
-    // complete until the next pass parks again -- after it has read them.
-    uint32_t *const row_p = reinterpret_cast<uint32_t *>(lds_all[wave] + W2_SLOTS * 64 + NPW * 8);
-    uint32_t *const row_dsc = row_p + 64;
-    uint32_t *const rows_b = reinterpret_cast<uint32_t *>(wbuf);                         // 0: eb, 1: fb
-    uint32_t *const rows_n = reinterpret_cast<uint32_t *>(lds_all[wave] + 13 * 64);   // 0: eb (copied), 2 .. 7: x_v, 8 .. 12: ids
+    // The records of the NEXT pass come in by LDS-DMA (global_load_lds_dwordx4: lane i's 16 bytes land at row + 16 i; no register is
+    // in flight, nothing the compiler could move or spill) into parking slots 13 .. 16, two rows of 1 KiB: slots that are free from
+    // the moment the tile is complete until the next pass parks again -- after it has read them.  (`nodes` is not read: the record
+    // holds the node.)
+    uint32_t *const rows_r = reinterpret_cast<uint32_t *>(lds_all[wave] + 13 * 64);
 
     const int32_t n_groups = (count + NPW - 1) / NPW;
     // XCD x walks the x-th contiguous eighth of the node list; its waves pull consecutive 16-node groups off a per-XCD counter.
@@ -316,19 +305,11 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
     int32_t wg = wg_lo + __builtin_amdgcn_readfirstlane(ticket);
     if (lane == 0) ticket = atomicAdd(q, 1);
     int32_t wg_next = wg_lo + __builtin_amdgcn_readfirstlane(ticket);
-    // the first group's index levels and geometry, one after the other
+    // the first group's records, then what they name
     W2Geo geo;
-    w2_stage_a(nodes, desc, wg, count, nd, l, row_p, row_dsc);
+    w2_stage_rec(desc, wg, count, nd, l, rows_r);
     w2_dma_wait();
-    w2_stage_b(g, row_p[lane], rows_b);
-    w2_dma_wait();
-    {
-        const uint32_t eb0 = rows_b[lane];
-        rows_n[lane] = eb0;
-        w2_stage_c(g, row_p[lane], eb0, rows_b[64 + lane], row_dsc[lane], rows_n);
-    }
-    w2_dma_wait();
-    w2_stage_d(g, row_p, rows_n, lane, geo);
+    w2_stage_d(g, rows_r, lane, geo);
 #ifdef NIN_MF_STAMPS     // diagnostic build (tools/stamps_hex8mf.py): s_memtime at the phase boundaries of one pass
 #ifndef NIN_MF_STAMP_PASS
 #define NIN_MF_STAMP_PASS 8
@@ -362,14 +343,12 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
 #else
 #define NIN_MF_STAMP_BACK() NIN_MF_STAMP()
 #endif
-        // (all of it landed during the last pass: p, dsc at its level-1 wait, x_v at its level-3 wait; eb was copied there)
-        const uint32_t p = row_p[lane], dsc = row_dsc[lane], eb = rows_n[lane];
-        double xv[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xv[k] = __hiloint2double((int)rows_n[64 * (3 + 2 * k) + lane], (int)rows_n[64 * (2 + 2 * k) + lane]);
+        // (the record landed at the last pass's wait, x_v with the geometry just now; p, eb, dsc are for the stores at the end of this pass and are
+        //  read here, before phase 1 parks over the rows -- pinned, so that they are in registers from here on)
+        uint32_t p = rows_r[4 * lane], eb = rows_r[4 * lane + 1], dsc = rows_r[W2_REC_ROW + 4 * lane + 3];
+        asm volatile("" : "+v"(p), "+v"(eb), "+v"(dsc));
+        const double xv[3] = {geo.xv[0], geo.xv[1], geo.xv[2]};
         const bool is_neu = (geo.flags & 2) != 0;
-        __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0): read before level 0 of the next pass overwrites them
-        w2_stage_a(nodes, desc, wg_next, count, nd, l, row_p, row_dsc);   // next pass: list entry and descriptor
         __builtin_amdgcn_sched_barrier(0);
 
         // ---- the front of E_l: rows 0 = cell row, 1 + 3 i + r = row r of face i; own columns in P ------------
@@ -412,18 +391,9 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
                 for (int t = 0; t < 3; ++t) { P[2 + 3 * i][t] = sav[i][0][t]; P[3 + 3 * i][t] = sav[i][1][t]; }
             }
         }
-        // (pinned: the face rows are what covers level 0; left alone the compiler sinks them behind the wait below)
-#pragma unroll
-        for (int r = 0; r < 10; ++r) { pin(P[r][0]); pin(P[r][1]); pin(P[r][2]); }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { pin(nb0[i][0]); pin(nb0[i][1]); pin(nb0[i][2]); }
         NIN_MF_STAMP();                                   // 1: face rows done
-#ifndef W2_B_LATE
-        w2_dma_wait();
-        w2_stage_b(g, row_p[lane], rows_b);               // next pass: CSR row starts
-#endif
-        // the ticket that names the group of the pass after the next (read at the end of the pass); drawn here, behind a wait,
-        // so that no wait of the first part of the pass covers its round trip
+        // the ticket that names the group of the pass after the next; drawn here, where no wait before the records' covers its
+        // round trip
         if (lane == 0) ticket = atomicAdd(q, 1);
         __builtin_amdgcn_sched_barrier(0);
         double C[NR][NC];
@@ -498,10 +468,6 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
             __builtin_amdgcn_sched_barrier(0);
         }
         NIN_MF_STAMP();                                   // 2: phase 1 done
-#ifdef W2_B_LATE
-        w2_dma_wait();
-        w2_stage_b(g, row_p[lane], rows_b);               // next pass: CSR row starts
-#endif
         // ---- the tile: odd slot 0 = F0 (lanes 0 .. 2); slot 1 = F1 (lanes 0, 1) or F0 (lane 3); slot 2 = F2 (lane 0) or F1
         //      (lanes 2, 3); slot 3 = F2 (lanes 1 .. 3); the slot a lane has no face on is zero.  The entries that waited in LDS
         //      come back; u and s take their place ------------------------------------------------------------------------------
@@ -539,16 +505,12 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
         double rinvq[3] = {0.0, 0.0, 0.0};
         NIN_MF_STAMP();                                   // 3: tile complete
         __builtin_amdgcn_sched_barrier(0);
-        P2LeanLoop<0, W2_C_STEP>::run(C, rinvq, l);
+        // next pass: its records, into the parking slots the tile has left (every read of them has returned: the DMA must not
+        // land under one)
+        __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0)
+        w2_stage_rec(desc, wg_next, count, nd, l, rows_r);
         __builtin_amdgcn_sched_barrier(0);
-        w2_dma_wait();
-        {   // next pass: coordinates, cell and face ids (the tile has left parking slots 13 .. 19); eb is kept for it in row 0
-            const uint32_t ebn = rows_b[lane];
-            rows_n[lane] = ebn;
-            w2_stage_c(g, row_p[lane], ebn, rows_b[64 + lane], row_dsc[lane], rows_n);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        P2LeanLoop<W2_C_STEP, W2_D_STEP>::run(C, rinvq, l);
+        P2LeanLoop<0, W2_D_STEP>::run(C, rinvq, l);
         NIN_MF_STAMP();                                   // 4: phase 2, steps 0 .. W2_D_STEP - 1
         __builtin_amdgcn_sched_barrier(0);
         w2_dma_wait();
@@ -557,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
         int32_t wg_after = wg_lo + __builtin_amdgcn_readfirstlane(ticket);
         asm volatile("" : "+s"(wg_after));
         __builtin_amdgcn_sched_barrier(0);
-        w2_stage_d(g, row_p, rows_n, lane, geo);          // next pass: geometry, in flight until its top
+        w2_stage_d(g, rows_r, lane, geo);         // next pass: coordinates and geometry, in flight until its top
         __builtin_amdgcn_sched_barrier(0);
         P2LeanLoop<W2_D_STEP, 12>::run(C, rinvq, l);
         NIN_MF_STAMP();                                   // 5: phase 2 done
@@ -632,10 +594,11 @@ __global__ __launch_bounds__(256, 2) void nin_gls_hex8w2_kernel(GridView g, cons
 __global__ void k_hex8_desc(GridView g, const int32_t *__restrict__ nodes, int32_t count, int32_t *__restrict__ desc) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    int32_t d[4] = {0, 0, 0, 0};
-    (void)hex8_descriptor(g, nodes ? nodes[i] : (int32_t)i, d);   // the list holds classified cube nodes only
+    int32_t d[kHex8DescWords] = {};
+    (void)hex8_descriptor<true>(g, nodes ? nodes[i] : (int32_t)i, d);   // the list holds classified cube nodes only
+    int4 *rec = reinterpret_cast<int4 *>(desc) + (kHex8DescWords / 4) * i;
 #pragma unroll
-    for (int l = 0; l < 4; ++l) desc[4 * i + l] = d[l];
+    for (int w = 0; w < kHex8DescWords / 4; ++w) rec[w] = make_int4(d[4 * w], d[4 * w + 1], d[4 * w + 2], d[4 * w + 3]);
 }
 
 }  // namespace

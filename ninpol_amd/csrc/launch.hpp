@@ -41,8 +41,8 @@ int launch_gls_class(const GridView &g, const int32_t *nodes, int32_t count, int
 int launch_gls_block(const GridView &g, const int32_t *nodes, int32_t count, int32_t waves, int32_t col_slots,
                      int32_t lds_bytes, int add_neumann, double *out, double *nws, int32_t *queue, hipStream_t stream);
 const char *kernel_name_gls_block();
-// the multifrontal kernel for cube nodes (kernels_gls_hex8mf.hip): 4 lanes per node; `desc` = 4 descriptor words per
-// list entry (hex8_desc.hpp, filled by launch_hex8_desc);
+// the multifrontal kernel for cube nodes (kernels_gls_hex8mf.hip): 4 lanes per node; `desc` = kHex8DescWords (32) words per list
+// entry, one 32-byte gather record per lane (hex8_desc.hpp, filled by launch_hex8_desc), 16-byte aligned;
 // `queue`: the grid's zeroed counter block + kGlsQueueHex8 (one work counter per XCD at queue + 16 * xcd, each on its own cache line:
 // ints kGlsQueueHex8 .. + 112 are the kernel's, gls_plan.hpp)
 int launch_hex8_desc(const GridView &g, const int32_t *nodes, int32_t count, int32_t *desc, hipStream_t stream);
