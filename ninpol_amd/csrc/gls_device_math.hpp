@@ -3,17 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include "gls_tau_table.hpp"
+#include "wave_ops.hpp"
 
 namespace nin {
 namespace glsmath {
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
+using waveops::dpp_mov;
+using waveops::wave_lds_sync;
 
 // 1/d and 1/sqrt(s) from the hardware seeds (v_rcp_f64 / v_rsq_f64: 2^-24.4, measured -- tools/micro_seed.hip) plus ONE cubic
 // correction step each: r (1 + e + e^2), e = 1 - d r, and y (1 + e/2 + 3 e^2/8), e = 1 - s y^2 -- the error cubes, 1e-22
@@ -35,6 +31,15 @@ __device__ __forceinline__ double rcp_newton(double d, int steps) {
     double r = __builtin_amdgcn_rcp(d);
     for (int i = 0; i < steps; ++i) r = fma(fma(-d, r, 1.0), r, r);
     return r;
+}
+// kernels_gls_block.hip's forms, older than the cubic steps: two Newton steps on the reciprocal, and the cubic step on the rsqrt
+// followed by one Newton step.  That kernel keeps them because its result bits are pinned (tools/parent_identity.py); nobody else
+// should call them.
+__device__ __forceinline__ double rcp_newton2(double d) { return rcp_newton(d, 2); }
+__device__ __forceinline__ double rsqrt_cubic_newton(double s) {
+    const double y = fast_rsqrt(s);
+    const double e = fma(-s * y, y, 1.0);
+    return fma(y * e, 0.5, y);
 }
 
 // Householder scalars for the column (alpha, x), ss = |x|^2:  beta = -sign(alpha) |(alpha, x)| (dlarfg);
@@ -254,12 +259,6 @@ __device__ __forceinline__ void apply_panel(const double (&P)[10][3], const doub
             for (int c = 0; c < W; ++c) B[r][c] = fma(w[c], P[r][k], B[r][c]);
         }
     }
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 }  // namespace glsmath

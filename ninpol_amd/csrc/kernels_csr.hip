@@ -10,6 +10,7 @@
 
 #include "device_grid.hpp"
 #include "launch.hpp"
+#include "wave_ops.hpp"
 
 namespace nin {
 
@@ -98,9 +99,7 @@ __global__ __launch_bounds__(256) void nin_apply_kernel(GridView g, const double
         if (staged) {
             for (int32_t i = lane; i < len; i += 64) { wl[i] = data[run_b + i]; cl[i] = g.esup[run_b + i]; }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        waveops::wave_lds_sync();
         if (live) {
             const int32_t b = g.esup_ptr[p], e = g.esup_ptr[p + 1];
             double acc[NF];
@@ -162,9 +161,7 @@ __global__ __launch_bounds__(256) void nin_apply_transpose_kernel(int32_t n_elem
         if (staged) {
             for (int32_t i = lane; i < len; i += 64) { pl[i] = cell_pos[run_b + i]; nl[i] = cell_node[run_b + i]; }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        waveops::wave_lds_sync();
         if (live) {
             const int32_t b = cell_ptr[e], end = cell_ptr[e + 1];
             double acc[NF];

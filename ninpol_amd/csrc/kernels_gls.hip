@@ -7,7 +7,8 @@
 //       [ -B_f,a  ... +B_f,b | 0 ]      3 rows per internal face: K N, T1, tau T2 (gls.pyx:293-356)
 //       [ -K N on the owner  | 0 ]      1 row per boundary face of a Neumann node (gls.pyx:394-416)
 // with n = 3 n_elem + 1 unknowns (a gradient per cell + the node value), solve it for n_elem (+1)
-// right-hand sides with LAPACK dgels and keep ONLY row n-1 of the solution (gls.pyx:466-472).
+// right-hand sides with LAPACK dgels and keep ONLY row n-1 of the solution (gls.pyx:466-472).  The node's header, the zero-row
+// verdict and these rows are written once, in gls_dense.hpp, for this kernel and kernels_gls_block.hip.
 //
 // What this kernel does: the same Householder QR of the same matrix (so the same conditioning and
 // the same kappa*eps-level agreement with dgels -- never normal equations), but it exploits that
@@ -25,50 +26,16 @@
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
+#include "gls_dense.hpp"
 #include "launch.hpp"
+#include "wave_ops.hpp"
 
 namespace nin {
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-// Sum over the 64 lanes, result in every lane.  All 64 lanes must be active.
-__device__ __forceinline__ double wave_sum(double v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror  -> every lane holds its 16-lane row sum
-    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-
-// Orders this wave's LDS / scratch traffic: a lane may read what another lane of the wave wrote.
-template <bool LDS>
-__device__ __forceinline__ void wave_sync() {
-    if (LDS) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-}
-
-__device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
+using namespace waveops;
+using namespace glsdense;
 
 constexpr int JB = 4;  // columns updated together (independent reductions in flight)
 
@@ -83,26 +50,11 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_team_kernel(GridView g, const
     double *base = scratch + (size_t)blockIdx.x * scratch_stride;
 
     for (int32_t idx = blockIdx.x; idx < count; idx += gridDim.x) {
-        const int32_t p = ufirst(nodes ? nodes[idx] : idx);
-        const int32_t eb = ufirst(g.esup_ptr[p]), ne = ufirst(g.esup_ptr[p + 1]) - eb;
-        const int32_t fb = ufirst(g.fsup_ptr[p]), nf = ufirst(g.fsup_ptr[p + 1]) - fb;
-        const int fl = ufirst((int)g.flags[p]);
-        const bool is_neu = (fl & 2) != 0;
-
-        // internal faces of the node (n_esuf == 2, gls.pyx:293-296)
-        int n_if = 0;
-        for (int f0 = 0; f0 < nf; f0 += 64) {
-            const int fi = f0 + lane;
-            const bool internal = fi < nf && g.face_cells[2 * (size_t)g.fsup[fb + fi] + 1] >= 0;
-            n_if += __popcll(__ballot(internal));
-        }
-        const int n_bf = nf - n_if;
-        const int n = 3 * ne + 1;                              // columns, the last one is c
-        const int m = ne + 3 * n_if + (is_neu ? n_bf : 0);     // rows actually populated
-        // Dirichlet boundary node (gls.pyx:165-166), n_bface >= n_face (gls.pyx:266-267: the system stays empty and
-        // dgels returns an all-zero row n-1), or fewer rows than unknowns next to the node value: zero row -- the
-        // same rule as kernels_gls_block.hip, so a node gets the same answer whichever kernel its size class runs on.
-        if (((fl & 1) && !is_neu) || n_if == 0 || m < n - 1) {
+        const DenseNode nd = read_node(g, nodes ? nodes[idx] : idx, lane);
+        const int32_t p = nd.p, eb = nd.eb, ne = nd.ne, fb = nd.fb, nf = nd.nf;
+        const int n_if = nd.n_if, n = nd.n, m = nd.m;
+        const bool is_neu = nd.is_neu;
+        if (nd.zero_row()) {
             for (int i = tid; i < ne; i += nthr) out[eb + i] = 0.0;
             if (tid == 0) nws[p] = 0.0;
             continue;
@@ -119,15 +71,10 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_team_kernel(GridView g, const
 
         const double xv0 = g.coords[3 * (size_t)p + 0], xv1 = g.coords[3 * (size_t)p + 1],
                      xv2 = g.coords[3 * (size_t)p + 2];
-        // cell rows: [x_K - x_v] on the cell's own block, 1 in the last column
-        for (int i = lane; i < ne; i += 64) {
-            const size_t c = (size_t)cells[i];
-            A[i + (3 * i + 0) * ld] = g.centroids[3 * c + 0] - xv0;
-            A[i + (3 * i + 1) * ld] = g.centroids[3 * c + 1] - xv1;
-            A[i + (3 * i + 2) * ld] = g.centroids[3 * c + 2] - xv2;
-            A[i + (n - 1) * ld] = 1.0;
-        }
-        // face rows
+        cell_rows(g, cells, ne, xv0, xv1, xv2, A, n, ld, lane);
+        // face rows: the internal faces' triples in fsup order behind the cell rows, then the Neumann rows
+        // (tau by the library pow here, not glsmath::face_tau: this kernel's bits)
+        const auto tau_pow = [](double un, double eta) { return pow(un, -eta); };
         int if_base = 0, bf_base = 0;
         for (int f0 = 0; f0 < nf; f0 += 64) {
             const int fi = f0 + lane;
@@ -138,46 +85,16 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_team_kernel(GridView g, const
             const bool bface = valid && cb < 0;
             const unsigned long long mi = __ballot(internal), mb = __ballot(bface);
             const unsigned long long below = (1ull << lane) - 1ull;
+            int Ia = 0, Ib = 0;
+            if (valid) local_index(cells, ne, ca, cb, Ia, Ib);
             if (internal) {
                 const int row = ne + 3 * (if_base + __popcll(mi & below));
-                const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
-                const double T0 = xv0 - g.face_center[3 * f + 0], T1 = xv1 - g.face_center[3 * f + 1],
-                             T2 = xv2 - g.face_center[3 * f + 2];
-                // T_sj2 = N x T_sj1, tau = |T_sj2|^(-eta), eta = max diff_mag of the two cells (gls.pyx:304-318)
-                const double U0 = N1 * T2 - N2 * T1, U1 = N2 * T0 - N0 * T2, U2 = N0 * T1 - N1 * T0;
-                const double da = g.diff_mag[ca], db = g.diff_mag[cb];
-                double eta = 0.0;
-                eta = da > eta ? da : eta;
-                eta = db > eta ? db : eta;
-                const double tj = pow(sqrt(U0 * U0 + U1 * U1 + U2 * U2), -eta);
-                const double *Ka = g.perm + 9 * (size_t)ca, *Kb = g.perm + 9 * (size_t)cb;
-                int Ia = 0, Ib = 0;
-                for (int q = 0; q < ne; ++q) {
-                    const int cq = cells[q];
-                    Ia = cq == ca ? q : Ia;
-                    Ib = cq == cb ? q : Ib;
-                }
-                double *ra = A + row + (size_t)(3 * Ia) * ld, *rb = A + row + (size_t)(3 * Ib) * ld;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double nLa = Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2;  // row c of K . N
-                    const double nLb = Kb[c * 3 + 0] * N0 + Kb[c * 3 + 1] * N1 + Kb[c * 3 + 2] * N2;
-                    const double t1 = c == 0 ? T0 : (c == 1 ? T1 : T2);
-                    const double u = tj * (c == 0 ? U0 : (c == 1 ? U1 : U2));
-                    ra[c * ld + 0] = -nLa; rb[c * ld + 0] = nLb;
-                    ra[c * ld + 1] = -t1;  rb[c * ld + 1] = t1;
-                    ra[c * ld + 2] = -u;   rb[c * ld + 2] = u;
-                }
+                internal_face_rows(g, f, ca, cb, xv0, xv1, xv2, A + row + (size_t)(3 * Ia) * ld, A + row + (size_t)(3 * Ib) * ld, ld, 0, 1, 2,
+                                   tau_pow);
             }
-            if (bface && is_neu) {  // set_neumann_rows, gls.pyx:394-416 (its RHS column is never read back)
+            if (bface && is_neu) {
                 const int row = ne + 3 * n_if + bf_base + __popcll(mb & below);
-                const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
-                const double *Ka = g.perm + 9 * (size_t)ca;
-                int Ia = 0;
-                for (int q = 0; q < ne; ++q) Ia = cells[q] == ca ? q : Ia;
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    A[row + (size_t)(3 * Ia + c) * ld] = -(Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2);
+                neumann_face_row(g, f, ca, A + row + (size_t)(3 * Ia) * ld, ld);
             }
             if_base += __popcll(mi);
             bf_base += __popcll(mb);

@@ -15,8 +15,11 @@
 // triangular solves need R, which the forward kernel never reads again).  Every wavefront forms reflector k from the pivot column,
 // wavefront w applies it to every TW-th group of four trailing columns, one barrier per reflector; the tail (two back substitutions,
 // three applications of Q) is wavefront 0's.  The system lives in LDS (LDS = true: the classes of 1, 2 and 4 wavefronts) or in a
-// global-memory scratch slot per workgroup (the systems that do not fit one CU's LDS), as nin_gls_team_kernel keeps it.  The assembly
-// is the forward's, expression for expression (gls_device_math.hpp's face_tau; K . N row by row).
+// global-memory scratch slot per workgroup (the systems that do not fit one CU's LDS), as nin_gls_team_kernel keeps it.
+// The node header, the zero-row rule and the assembly below are this unit's OWN TEXT of what gls_dense.hpp holds for the forward kernels
+// (read_node, DenseNode::zero_row, cell_rows, internal_face_rows with glsmath::face_tau, neumann_face_row): a change there is made here
+// too.  Calling the helpers gives the same bits (profiles/r16), but every form tried reallocated this kernel's registers and moved one
+// of the del20 timings by ~0.5 %, more than the parent's spread -- the row loops are the same instructions either way.
 //
 // Contributions: lane i of the workgroup owns cell i of the node and walks the node's faces in fsup order; the ten values of the pair
 // (node, cell) -- Kbar[9] and etabar -- are summed in that fixed order and written to contrib[esup position][10].  nin_adjoint_gather_kernel
@@ -37,49 +40,13 @@
 #include "gls_adjoint.hpp"
 #include "gls_device_math.hpp"
 #include "launch.hpp"
+#include "wave_ops.hpp"
 
 namespace nin {
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-// Sum over the 64 lanes, result in every lane.  All 64 lanes must be active.
-__device__ __forceinline__ double wave_sum(double v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror  -> every lane holds its 16-lane row sum
-    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-
-// Orders this wave's LDS / scratch traffic: a lane may read what another lane of the wave wrote.
-template <bool LDS>
-__device__ __forceinline__ void wave_sync() {
-    if (LDS) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-}
-
-__device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
+using namespace waveops;
 
 // What one launch reads and writes beside the grid: the adjoint's three pointers, or the tangent's
 struct AdjointIo {
@@ -170,7 +137,7 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
         const int n_bf = nf - n_if;
         const int n = 3 * ne + 1;                              // columns, the last one is c
         const int m = ne + 3 * n_if + (is_neu ? n_bf : 0);     // rows actually populated
-        // the forward's zero rows (kernels_gls.hip): nothing depends on K there
+        // the forward's zero rows (DenseNode::zero_row, gls_dense.hpp): nothing depends on K there
         if (((fl & 1) && !is_neu) || n_if == 0 || m < n - 1) {
             if constexpr (TAN) {
                 for (int t = 0; t < io.n_tan; ++t) {
@@ -194,7 +161,7 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
         for (int i = tid; i < ld * n; i += nthr) A[i] = 0.0;
         __syncthreads();
         const double xv0 = g.coords[3 * (size_t)p + 0], xv1 = g.coords[3 * (size_t)p + 1], xv2 = g.coords[3 * (size_t)p + 2];
-        if (wave == 0) {   // assembly, as kernels_gls.hip: a lane per cell / face
+        if (wave == 0) {   // assembly, the text of gls_dense.hpp's helpers: a lane per cell / face
             for (int i = lane; i < ne; i += 64) {
                 const size_t c = (size_t)cells[i];
                 A[i + (size_t)(3 * i + 0) * ld] = g.centroids[3 * c + 0] - xv0;

@@ -1,7 +1,7 @@
 // kernels_gls_block.hip -- GLS weights for nodes of any shape, gfx950: one node per workgroup of NW wavefronts.
 //
-// Same mathematics as kernels_gls.hip (the reference's dense m x n system of gls.pyx:252-416, Householder QR as in
-// dgels, only row n-1 of the solution kept, gls.pyx:466-472), laid out so that no dot product ever crosses lanes:
+// The reference's dense m x n system of gls.pyx:252-416 (assembled by gls_dense.hpp, as in kernels_gls.hip), Householder QR as
+// in dgels, only row n-1 of the solution kept (gls.pyx:466-472), laid out so that no dot product ever crosses lanes:
 //
 //   * a lane owns COLUMNS (column j sits in lane (n-1-j) % 64, slot (n-1-j) / 64, so the columns still alive at
 //     step k always fill the low lanes) and wave w owns the ROWS i = w (mod NW).  The system lives in LDS
@@ -25,59 +25,25 @@
 #include <cstdlib>
 
 #include "device_grid.hpp"
+#include "gls_dense.hpp"
 #include "gls_device_math.hpp"
 #include "launch.hpp"
+#include "wave_ops.hpp"
 
 namespace nin {
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror
-    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-
-__device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ double fast_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return r;
-}
-__device__ __forceinline__ double fast_rsqrt(double s) {
-    double y = __builtin_amdgcn_rsq(s);
-    double e = fma(-s * y, y, 1.0);
-    y = fma(y * e, fma(e, 0.375, 0.5), y);
-    e = fma(-s * y, y, 1.0);
-    y = fma(y * e, 0.5, y);
-    return y;
-}
+using namespace waveops;
+using namespace glsdense;
+using glsmath::rcp_newton2;          // this kernel's reciprocal and rsqrt are not glsmath::fast_rcp / fast_rsqrt:
+using glsmath::rsqrt_cubic_newton;   // see gls_device_math.hpp
 
 // Orders LDS traffic between the waves of the workgroup (or inside the single wave when NW == 1).
 template <int NW>
 __device__ __forceinline__ void group_sync() {
     if (NW == 1) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     } else {
         __syncthreads();
     }
@@ -129,7 +95,7 @@ __device__ __forceinline__ void first_dots(const Sys &s, int k0, double (&dn)[CS
             for (int q = 0; q <= TOP; ++q) own[u][q] = col[q][i + u * NW];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const double x = readlane_f64(own[u][TOP], l0);
+            const double x = rl64(own[u][TOP], l0);
 #pragma unroll
             for (int q = 0; q <= TOP; ++q) dn[q] = fma(x, own[u][q], dn[q]);
         }
@@ -138,7 +104,7 @@ __device__ __forceinline__ void first_dots(const Sys &s, int k0, double (&dn)[CS
         double own[TOP + 1];
 #pragma unroll
         for (int q = 0; q <= TOP; ++q) own[q] = col[q][i];
-        const double x = readlane_f64(own[TOP], l0);
+        const double x = rl64(own[TOP], l0);
 #pragma unroll
         for (int q = 0; q <= TOP; ++q) dn[q] = fma(x, own[q], dn[q]);
     }
@@ -179,11 +145,11 @@ __device__ __forceinline__ void qr_step(const Sys &s, int k, int buf, double (&d
     }
     if (NW > 1 && !s.db) group_sync<NW>();   // one partial buffer: nobody may publish before everybody has read
     NIN_STAMP(s, k, 0);
-    const double dk = readlane_f64(d[TOP], lk), alpha = readlane_f64(rowk[TOP], lk);
+    const double dk = rl64(d[TOP], lk), alpha = rl64(rowk[TOP], lk);
     if (!(dk != 0.0)) singular = true;                  // an all-zero pivot column (or NaN): no solution row
-    const double sq = dk * fast_rsqrt(dk);              // sqrt(d_k) = |(alpha, x)|
+    const double sq = dk * rsqrt_cubic_newton(dk);      // sqrt(d_k) = |(alpha, x)|
     const double beta = -copysign(sq, alpha);
-    const double inv = fast_rcp(fma(fabs(alpha), sq, dk));   // 1 / (beta (beta - alpha))
+    const double inv = rcp_newton2(fma(fabs(alpha), sq, dk));   // 1 / (beta (beta - alpha))
     const double vk = alpha - beta;
 #pragma unroll
     for (int q = 0; q <= TOP; ++q) {
@@ -211,14 +177,14 @@ __device__ __forceinline__ void qr_step(const Sys &s, int k, int buf, double (&d
             p[q] = col[q] + i0;
         }
         auto row = [&](int u, double (&cur)[G][TOP + 1]) {
-            const double x = readlane_f64(cur[u][TOP], lk);
+            const double x = rl64(cur[u][TOP], lk);
             double nv[TOP + 1];
 #pragma unroll
             for (int q = 0; q <= TOP; ++q) {
                 nv[q] = fma(-x, w[q], cur[u][q]);
                 p[q][u * NW] = nv[q];
             }
-            const double xn = readlane_f64(next_in_top ? nv[TOP] : nv[TOP > 0 ? TOP - 1 : 0], ln);
+            const double xn = rl64(next_in_top ? nv[TOP] : nv[TOP > 0 ? TOP - 1 : 0], ln);
 #pragma unroll
             for (int q = 0; q <= TOP; ++q) acc[u & 1][q] = fma(xn, nv[q], acc[u & 1][q]);
         };
@@ -228,7 +194,7 @@ __device__ __forceinline__ void qr_step(const Sys &s, int k, int buf, double (&d
         auto rows = [&](double (&cur)[G][TOP + 1]) {
             double x[G], xn[G], nv[G][TOP + 1];
 #pragma unroll
-            for (int u = 0; u < G; ++u) x[u] = readlane_f64(cur[u][TOP], lk);
+            for (int u = 0; u < G; ++u) x[u] = rl64(cur[u][TOP], lk);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < G; ++u) {
@@ -240,7 +206,7 @@ __device__ __forceinline__ void qr_step(const Sys &s, int k, int buf, double (&d
             for (int u = 0; u < G; ++u) {
 #pragma unroll
                 for (int q = 0; q <= TOP; ++q) p[q][u * NW] = nv[u][q];
-                xn[u] = readlane_f64(next_in_top ? nv[u][TOP] : nv[u][TOP > 0 ? TOP - 1 : 0], ln);
+                xn[u] = rl64(next_in_top ? nv[u][TOP] : nv[u][TOP > 0 ? TOP - 1 : 0], ln);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -365,16 +331,16 @@ __device__ __forceinline__ bool front_qr(const Sys &s, int rk, int L0, int nL) {
             double v = a[r][0];
 #pragma unroll
             for (int q = 1; q < CS; ++q) v = qk == q ? a[r][q] : v;
-            x[r] = readlane_f64(v, lk);
+            x[r] = rl64(v, lk);
             dk = fma(x[r], x[r], dk);
 #pragma unroll
             for (int q = 0; q < CS; ++q) d[q] = fma(x[r], a[r][q], d[q]);
         }
         const double alpha = x[t];
         bad = bad || !(dk != 0.0);                          // an all-zero pivot column (or NaN): no solution row
-        const double sq = dk * fast_rsqrt(dk);
+        const double sq = dk * rsqrt_cubic_newton(dk);
         const double beta = -copysign(sq, alpha);
-        const double inv = fast_rcp(fma(fabs(alpha), sq, dk));
+        const double inv = rcp_newton2(fma(fabs(alpha), sq, dk));
         const double vk = alpha - beta;
 #pragma unroll
         for (int q = 0; q < CS; ++q) w[q] = cidx[q] > k ? (d[q] - beta * a[t][q]) * inv : 0.0;
@@ -466,24 +432,11 @@ __global__ __launch_bounds__(64 * NW) void nin_gls_block_kernel(GridView g, cons
             group_sync<NW>();      // every wave holds idx: the slot may be rewritten
             if (tid == 0) *slot = atomicAdd(queue, 1);
         }
-        const int32_t p = ufirst(nodes ? nodes[idx] : idx);
-        const int32_t eb = ufirst(g.esup_ptr[p]), ne = ufirst(g.esup_ptr[p + 1]) - eb;
-        const int32_t fb = ufirst(g.fsup_ptr[p]), nf = ufirst(g.fsup_ptr[p + 1]) - fb;
-        const int fl = ufirst((int)g.flags[p]);
-        const bool is_neu = (fl & 2) != 0;
-
-        int n_if = 0;   // internal faces of the node (n_esuf == 2, gls.pyx:293-296); every wave counts them itself
-        for (int f0 = 0; f0 < nf; f0 += 64) {
-            const int fi = f0 + lane;
-            const bool internal = fi < nf && g.face_cells[2 * (size_t)g.fsup[fb + fi] + 1] >= 0;
-            n_if += __popcll(__ballot(internal));
-        }
-        const int n_bf = nf - n_if;
-        const int n = 3 * ne + 1;
-        const int m = ne + 3 * n_if + (is_neu ? n_bf : 0);
-        // Dirichlet boundary node (gls.pyx:165-166), n_bface >= n_face (gls.pyx:266-267), or fewer rows than
-        // unknowns next to the node value: zero row.
-        if (((fl & 1) && !is_neu) || n_if == 0 || m < n - 1) {
+        const DenseNode nd = read_node(g, nodes ? nodes[idx] : idx, lane);
+        const int32_t p = nd.p, eb = nd.eb, ne = nd.ne, fb = nd.fb, nf = nd.nf;
+        const int n_if = nd.n_if, n = nd.n, m = nd.m;
+        const bool is_neu = nd.is_neu;
+        if (nd.zero_row()) {
             for (int i = tid; i < ne; i += nthr) out[eb + i] = 0.0;
 #ifdef NIN_BLOCK_STAMPS
             if (tid == 0 && (dbg >> 8) == 0) nws[p] = 0.0;
@@ -546,12 +499,8 @@ __global__ __launch_bounds__(64 * NW) void nin_gls_block_kernel(GridView g, cons
                 if (face_lane) {
                     const size_t f = (size_t)g.fsup[fb + lane];
                     const int ca = g.face_cells[2 * f], cb = g.face_cells[2 * f + 1];
-                    int ib = 0;
-                    for (int q = 0; q < ne; ++q) {
-                        const int cq = cells[q];
-                        Ia = cq == ca ? q : Ia;
-                        ib = cq == cb ? q : ib;
-                    }
+                    int ib;
+                    local_index(cells, ne, ca, cb, Ia, ib);
                     Ib = cb >= 0 ? ib : 0xFF;
                     pl.fi[2 * lane] = (uint8_t)Ia;
                     pl.fi[2 * lane + 1] = (uint8_t)Ib;
@@ -629,16 +578,7 @@ __global__ __launch_bounds__(64 * NW) void nin_gls_block_kernel(GridView g, cons
             group_sync<NW>();
             // ---- assembly through the plan's row / column maps ----------------------------------------------------------
             if (wave == 1) {
-                // cell rows: [x_K - x_v] on the cell's own block, 1 in the last column (gls.pyx:269-281)
-                for (int i = lane; i < ne; i += 64) {
-                    const size_t c = (size_t)cells[i];
-                    double *row = s.A + pl.crow[i];
-                    const int cb3 = 3 * cpos[i];
-                    row[(cb3 + 0) * ld] = g.centroids[3 * c + 0] - xv0;
-                    row[(cb3 + 1) * ld] = g.centroids[3 * c + 1] - xv1;
-                    row[(cb3 + 2) * ld] = g.centroids[3 * c + 2] - xv2;
-                    row[(n - 1) * ld] = 1.0;
-                }
+                for (int i = lane; i < ne; i += 64) cell_row(g, (size_t)cells[i], xv0, xv1, xv2, s.A + pl.crow[i], 3 * cpos[i], n, ld);
             }
             if (wave == 0) {
                 for (int f0 = 0; f0 < nf; f0 += 64) {
@@ -647,53 +587,19 @@ __global__ __launch_bounds__(64 * NW) void nin_gls_block_kernel(GridView g, cons
                     const size_t f = (size_t)g.fsup[fb + fi];
                     const int Ia = pl.fi[2 * fi], Ib = pl.fi[2 * fi + 1];
                     const int16_t *fr = pl.frow + 3 * fi;
-                    const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
+                    double *ra = s.A + (size_t)(3 * cpos[Ia]) * ld;
                     if (Ib != 0xFF) {
-                        const int ca = cells[Ia], cb = cells[Ib];
-                        const double T0 = xv0 - g.face_center[3 * f + 0], T1 = xv1 - g.face_center[3 * f + 1],
-                                     T2 = xv2 - g.face_center[3 * f + 2];
-                        // T_sj2 = N x T_sj1, tau = |T_sj2|^(-eta), eta = max diff_mag of the two cells (gls.pyx:304-318)
-                        const double U0 = N1 * T2 - N2 * T1, U1 = N2 * T0 - N0 * T2, U2 = N0 * T1 - N1 * T0;
-                        const double da = g.diff_mag[ca], db = g.diff_mag[cb];
-                        double eta = 0.0;
-                        eta = da > eta ? da : eta;
-                        eta = db > eta ? db : eta;
-                        const double tj = glsmath::face_tau(sqrt(U0 * U0 + U1 * U1 + U2 * U2), eta);
-                        const double *Ka = g.perm + 9 * (size_t)ca, *Kb = g.perm + 9 * (size_t)cb;
-                        double *ra = s.A + (size_t)(3 * cpos[Ia]) * ld, *rb = s.A + (size_t)(3 * cpos[Ib]) * ld;
-                        const int r0 = fr[0], r1 = fr[1], r2 = fr[2];   // rows: K N, T1, tau T2
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const double nLa = Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2;  // row c of K . N
-                            const double nLb = Kb[c * 3 + 0] * N0 + Kb[c * 3 + 1] * N1 + Kb[c * 3 + 2] * N2;
-                            const double t1 = c == 0 ? T0 : (c == 1 ? T1 : T2);
-                            const double u = tj * (c == 0 ? U0 : (c == 1 ? U1 : U2));
-                            ra[c * ld + r0] = -nLa; rb[c * ld + r0] = nLb;
-                            ra[c * ld + r1] = -t1;  rb[c * ld + r1] = t1;
-                            ra[c * ld + r2] = -u;   rb[c * ld + r2] = u;
-                        }
-                    } else if (is_neu) {  // set_neumann_rows, gls.pyx:394-416 (its RHS column is never read back)
-                        const double *Ka = g.perm + 9 * (size_t)cells[Ia];
-#pragma unroll
-                        for (int c = 0; c < 3; ++c)
-                            s.A[(size_t)(3 * cpos[Ia] + c) * ld + fr[0]] = -(Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2);
+                        internal_face_rows(g, f, cells[Ia], cells[Ib], xv0, xv1, xv2, ra, s.A + (size_t)(3 * cpos[Ib]) * ld, ld, fr[0], fr[1],
+                                           fr[2], glsmath::face_tau);
+                    } else if (is_neu) {
+                        neumann_face_row(g, f, cells[Ia], ra + fr[0], ld);
                     }
                 }
             }
         } else {
         if (SPARSE)
             for (int i = tid; i < ne; i += nthr) cpos[i] = (uint8_t)i;
-        if (wave == (NW > 1 ? 1 : 0)) {
-            // cell rows: [x_K - x_v] on the cell's own block, 1 in the last column (gls.pyx:269-281)
-            for (int i = lane; i < ne; i += 64) {
-                const size_t c = (size_t)cells[i];
-                double *row = s.A + i;
-                row[(3 * i + 0) * ld] = g.centroids[3 * c + 0] - xv0;
-                row[(3 * i + 1) * ld] = g.centroids[3 * c + 1] - xv1;
-                row[(3 * i + 2) * ld] = g.centroids[3 * c + 2] - xv2;
-                row[(n - 1) * ld] = 1.0;
-            }
-        }
+        if (wave == (NW > 1 ? 1 : 0)) cell_rows(g, cells, ne, xv0, xv1, xv2, s.A, n, ld, lane);
         if (wave == 0) {
             int if_base = 0, bf_base = 0;
             for (int f0 = 0; f0 < nf; f0 += 64) {
@@ -705,46 +611,16 @@ __global__ __launch_bounds__(64 * NW) void nin_gls_block_kernel(GridView g, cons
                 const bool bface = valid && cb < 0;
                 const unsigned long long mi = __ballot(internal), mb = __ballot(bface);
                 const unsigned long long below = (1ull << lane) - 1ull;
+                int Ia = 0, Ib = 0;
+                if (valid) local_index(cells, ne, ca, cb, Ia, Ib);
                 if (internal) {
                     const int row = ne + 3 * (if_base + __popcll(mi & below));
-                    const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
-                    const double T0 = xv0 - g.face_center[3 * f + 0], T1 = xv1 - g.face_center[3 * f + 1],
-                                 T2 = xv2 - g.face_center[3 * f + 2];
-                    // T_sj2 = N x T_sj1, tau = |T_sj2|^(-eta), eta = max diff_mag of the two cells (gls.pyx:304-318)
-                    const double U0 = N1 * T2 - N2 * T1, U1 = N2 * T0 - N0 * T2, U2 = N0 * T1 - N1 * T0;
-                    const double da = g.diff_mag[ca], db = g.diff_mag[cb];
-                    double eta = 0.0;
-                    eta = da > eta ? da : eta;
-                    eta = db > eta ? db : eta;
-                    const double tj = glsmath::face_tau(sqrt(U0 * U0 + U1 * U1 + U2 * U2), eta);
-                    const double *Ka = g.perm + 9 * (size_t)ca, *Kb = g.perm + 9 * (size_t)cb;
-                    int Ia = 0, Ib = 0;
-                    for (int q = 0; q < ne; ++q) {
-                        const int cq = cells[q];
-                        Ia = cq == ca ? q : Ia;
-                        Ib = cq == cb ? q : Ib;
-                    }
-                    double *ra = s.A + (3 * Ia) * ld + row, *rb = s.A + (3 * Ib) * ld + row;   // rows row.. row+2 = K N, T1, tau T2
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const double nLa = Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2;  // row c of K . N
-                        const double nLb = Kb[c * 3 + 0] * N0 + Kb[c * 3 + 1] * N1 + Kb[c * 3 + 2] * N2;
-                        const double t1 = c == 0 ? T0 : (c == 1 ? T1 : T2);
-                        const double u = tj * (c == 0 ? U0 : (c == 1 ? U1 : U2));
-                        ra[c * ld + 0] = -nLa; rb[c * ld + 0] = nLb;
-                        ra[c * ld + 1] = -t1;  rb[c * ld + 1] = t1;
-                        ra[c * ld + 2] = -u;   rb[c * ld + 2] = u;
-                    }
+                    internal_face_rows(g, f, ca, cb, xv0, xv1, xv2, s.A + (3 * Ia) * ld + row, s.A + (3 * Ib) * ld + row, ld, 0, 1, 2,
+                                       glsmath::face_tau);
                 }
-                if (bface && is_neu) {  // set_neumann_rows, gls.pyx:394-416 (its RHS column is never read back)
+                if (bface && is_neu) {
                     const int row = ne + 3 * n_if + bf_base + __popcll(mb & below);
-                    const double N0 = g.face_normal[3 * f + 0], N1 = g.face_normal[3 * f + 1], N2 = g.face_normal[3 * f + 2];
-                    const double *Ka = g.perm + 9 * (size_t)ca;
-                    int Ia = 0;
-                    for (int q = 0; q < ne; ++q) Ia = cells[q] == ca ? q : Ia;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        s.A[(3 * Ia + c) * ld + row] = -(Ka[c * 3 + 0] * N0 + Ka[c * 3 + 1] * N1 + Ka[c * 3 + 2] * N2);
+                    neumann_face_row(g, f, ca, s.A + (3 * Ia) * ld + row, ld);
                 }
                 if_base += __popcll(mi);
                 bf_base += __popcll(mb);
@@ -843,11 +719,11 @@ __global__ __launch_bounds__(64 * NW) void nin_gls_block_kernel(GridView g, cons
 #pragma unroll
                 for (int q = 0; q < CS; ++q) {
                     if (q == ks) {
-                        rkk = readlane_f64(col[q], kl);
-                        ck = readlane_f64(ct[q], kl);
+                        rkk = rl64(col[q], kl);
+                        ck = rl64(ct[q], kl);
                     }
                 }
-                const double yk = ck * fast_rcp(rkk);
+                const double yk = ck * rcp_newton2(rkk);
 #pragma unroll
                 for (int q = 0; q < CS; ++q) ct[q] = fma(-yk, col[q], ct[q]);
                 if (lane == 0) y[k] = yk;
@@ -865,9 +741,9 @@ __global__ __launch_bounds__(64 * NW) void nin_gls_block_kernel(GridView g, cons
                 if (3 * lane < R0) {
                     const int r0 = 3 * lane;
                     const double *A0 = s.A + (size_t)r0 * ld, *A1 = A0 + ld, *A2 = A1 + ld;   // columns r0, r0 + 1, r0 + 2
-                    const double y2 = ctl[r0 + 2] * fast_rcp(A2[r0 + 2]);
-                    const double y1 = fma(-A2[r0 + 1], y2, ctl[r0 + 1]) * fast_rcp(A1[r0 + 1]);
-                    const double y0 = fma(-A2[r0], y2, fma(-A1[r0], y1, ctl[r0])) * fast_rcp(A0[r0]);
+                    const double y2 = ctl[r0 + 2] * rcp_newton2(A2[r0 + 2]);
+                    const double y1 = fma(-A2[r0 + 1], y2, ctl[r0 + 1]) * rcp_newton2(A1[r0 + 1]);
+                    const double y0 = fma(-A2[r0], y2, fma(-A1[r0], y1, ctl[r0])) * rcp_newton2(A0[r0]);
                     y[r0] = y0; y[r0 + 1] = y1; y[r0 + 2] = y2;
                 }
             }

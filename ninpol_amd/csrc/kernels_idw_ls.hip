@@ -22,6 +22,7 @@
 
 #include "device_grid.hpp"
 #include "launch.hpp"
+#include "wave_ops.hpp"
 
 namespace nin {
 
@@ -29,11 +30,7 @@ namespace {
 
 constexpr int kWavesPerBlock = 4;
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using waveops::wave_lds_sync;
 
 // a cell's centroid: from the padded [E][4] copy when the grid carries one (two 16-byte loads, one 64-byte line), else
 // from the packed [E][3] array (three 8-byte loads, 37 % of the records straddle two lines)

@@ -11,12 +11,8 @@ namespace mfwstrips {
 
 using namespace glsmath;
 
-__device__ __forceinline__ double rl64(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ uint32_t rl32(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
+using waveops::rl32;
+using waveops::rl64;
 
 // ---- the dense problem with lane = ROW (large instantiation) -------------------------------------------------------------
 // Cross-lane pieces.  v_permlane32_swap / v_permlane16_swap (gfx950) exchange halves / odd-even 16-lane rows between

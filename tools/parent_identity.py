@@ -11,12 +11,16 @@ Meshes (small: a few seconds each): jittered hexahedra, a mixed mesh, wedges and
 parts of tests/test_gpu_composite.py (between them all 22 plan kernels have nodes); and a random-cloud Delaunay mesh WITH a Neumann plane,
 for which mfx_boundary must have nodes and neumann_ws non-zero entries -- otherwise the boundary-face rows are never computed.
 Routes per mesh: nin_weights_host over all nodes and over a shuffled subset (GLS, IDW and LS), interpolate() pipelined
-(NIN_E2E_MIN_NODES=512), apply() fused and unfused, apply_transpose() with 3 fields, permeability_gradient().  On the meshes of LOCAL a
+(NIN_E2E_MIN_NODES=512), apply() fused and unfused, apply_transpose() with 3 fields, permeability_gradient() and
+permeability_tangent() along two directions.  On the meshes of LOCAL a
 scatter of permeability, of points and of Neumann flags (device tensors), each followed by the dirty launch -- weights and neumann_ws
 after each -- and by HostMatrix.update(), whose matrix must in the end be a fresh interpolate()'s in the same child.  On the composite
-mesh the all-nodes route runs again under each switch of SWITCHES (NIN_GLS_NO_SMALL is among them because only without the small-node
-kernels does the one-wavefront block kernel, block1, get nodes on these meshes).
-Exit status 1 if an array or a plan differs, or if one of the plan kernels has no nodes on any mesh.  Needs a GPU; reads nothing
+mesh the all-nodes route runs again under each switch set of SWITCHES (NIN_GLS_NO_SMALL is among them because only without the small-node
+kernels does the one-wavefront block kernel, block1, get nodes on these meshes; block_only and global_scratch send EVERY node through
+kernels_gls_block.hip and kernels_gls.hip), and on the mixed mesh the gradient and the tangent run again under ADJ_SWITCHES (every
+system of kernels_gls_adjoint.hip in global-memory scratch).
+Exit status 1 if an array or a plan differs, if one of the plan kernels has no nodes on any mesh, or if under ADJ_SWITCHES a node of
+the adjoint is left outside the global-scratch bin (Grid.gls_adjoint_plan(): looked at, not compared).  Needs a GPU; reads nothing
 outside the repository."""
 import json
 import os
@@ -26,7 +30,13 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_SECONDS = 240
-SWITCHES = ("NIN_MFW_LANE_COLUMNS", "NIN_MFW_NO_STRIPS", "NIN_MFW_SMALL_STRIPS", "NIN_GLS_MFW_GENERAL", "NIN_GLS_NO_MFX", "NIN_GLS_NO_SMALL")
+# a switch set's name -> the variables it sets to 1
+SWITCHES = {s: (s,) for s in ("NIN_MFW_LANE_COLUMNS", "NIN_MFW_NO_STRIPS", "NIN_MFW_SMALL_STRIPS", "NIN_GLS_MFW_GENERAL", "NIN_GLS_NO_MFX",
+                              "NIN_GLS_NO_SMALL")}
+SWITCHES.update(   # (as tests/util.py GLS_ROUTES spells them)
+    block_only=("NIN_GLS_NO_GROUP", "NIN_GLS_NO_MFW", "NIN_GLS_NO_MFX", "NIN_GLS_NO_SMALL", "NIN_GLS_NO_QUAD4"),
+    global_scratch=("NIN_GLS_NO_GROUP", "NIN_GLS_NO_MFW", "NIN_GLS_FORCE_GLOBAL"))
+ADJ_SWITCHES = {"adjoint_global_scratch": ("NIN_GLS_ADJ_FORCE_GLOBAL",)}
 PLANE = (2, 0.0)
 LOCAL = ("mixed", "delaunay_neumann")
 
@@ -95,13 +105,22 @@ def local_routes(I, A):
     A["local.interp.data"], A["local.interp.nws"] = W.data, n
 
 
+def adjoint_routes(I, A):
+    """permeability_gradient() for 3 node fields, permeability_tangent() along 2 directions (fixed seeds)"""
+    import numpy as np
+    P, E = int(I.grid.n_points), int(I.grid.n_elems)
+    A["perm_gradient.g"] = I.permeability_gradient("u", np.random.default_rng(8).random((3, P)))
+    A["perm_tangent.v"], A["perm_tangent.nws"] = I.permeability_tangent("u", np.random.default_rng(9).standard_normal((2, E, 3, 3)))
+
+
 def child(mesh_name, route_set, out):
-    """route_set: 'routes' (all of them) or the name of a switch (the all-nodes route under it)"""
+    """route_set: 'routes' (all of them), a name of SWITCHES (the all-nodes route under it) or of ADJ_SWITCHES (... and adjoint_routes)"""
     import numpy as np
     if route_set == "routes":
         os.environ["NIN_E2E_MIN_NODES"] = "512"
     else:
-        os.environ[route_set] = "1"
+        for var in {**SWITCHES, **ADJ_SWITCHES}[route_set]:
+            os.environ[var] = "1"
     sys.path.insert(0, ROOT)
     if mesh_name in LOCAL and route_set == "routes":
         import torch                                           # (torch's own HIP runtime has to open the device before the library's does)
@@ -129,11 +148,13 @@ def child(mesh_name, route_set, out):
         A["apply_fused.v"], A["apply_fused.nws"] = I.apply("u", "gls", values=np.random.default_rng(6).random((3, int(I.grid.n_elems))))
         os.environ["NIN_APPLY_NO_FUSION"] = "1"                # (the library reads this switch at every apply call)
         A["apply_unfused.v"], A["apply_unfused.nws"] = I.apply("u", "gls", values=np.random.default_rng(6).random((3, int(I.grid.n_elems))))
-        v3 = np.random.default_rng(8).random((3, P))
-        A["apply_transpose.x"] = I.apply_transpose("u", "gls", v3)
-        A["perm_gradient.g"] = I.permeability_gradient("u", v3)
+        A["apply_transpose.x"] = I.apply_transpose("u", "gls", np.random.default_rng(8).random((3, P)))
+        adjoint_routes(I, A)
         if mesh_name in LOCAL:
             local_routes(I, A)
+    elif route_set in ADJ_SWITCHES:
+        adjoint_routes(I, A)
+        A["__adjoint_bins__"] = np.array(list(I.grid.gls_adjoint_plan().values()))   # (not compared: main() wants every node in the last bin)
     plan = {k: int(v) for k, v in I.grid.gls_plan().items()}
     np.savez(out, __plan__=np.array(json.dumps(plan)), __kernels__=np.array(json.dumps(list(I.grid.PLAN_KERNELS))),
              **{k: np.asarray(v) for k, v in A.items()})
@@ -141,7 +162,7 @@ def child(mesh_name, route_set, out):
 
 def run_child(lib, mesh_name, route_set, out):
     env = dict(os.environ, NINPOL_AMD_LIB=os.path.abspath(lib))
-    for s in SWITCHES + ("NIN_E2E_MIN_NODES", "NIN_APPLY_NO_FUSION"):
+    for s in sum({**SWITCHES, **ADJ_SWITCHES}.values(), ("NIN_E2E_MIN_NODES", "NIN_APPLY_NO_FUSION")):
         env.pop(s, None)
     rc = subprocess.call(["timeout", "-k", "10", str(CHILD_SECONDS), sys.executable, os.path.abspath(__file__), "--child", mesh_name,
                           route_set, out], env=env)
@@ -155,7 +176,7 @@ def main():
     import numpy as np
     lib_a = sys.argv[1]
     lib_b = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "ninpol_amd", "libninpol_amd.so")
-    jobs = [(m, "routes") for m in MESHES] + [("composite", s) for s in SWITCHES]
+    jobs = [(m, "routes") for m in MESHES] + [("composite", s) for s in SWITCHES] + [("mixed", s) for s in ADJ_SWITCHES]
     lines, plans, bad, kernels, unmet = [], {}, 0, [], []
     with tempfile.TemporaryDirectory() as tmp:
         for mesh_name, route_set in jobs:
@@ -167,7 +188,7 @@ def main():
             a, b = z
             pa, pb = json.loads(str(a["__plan__"])), json.loads(str(b["__plan__"]))
             kernels = json.loads(str(b["__kernels__"]))
-            label = mesh_name if route_set == "routes" else f"{mesh_name}[{route_set}=1]"
+            label = mesh_name if route_set == "routes" else f"{mesh_name}[{route_set}{'=1' if SWITCHES.get(route_set) == (route_set,) else ''}]"
             plans[label] = (pa, pb)
             bad += pa != pb
             for k in sorted(set(a.files) | set(b.files)):
@@ -178,6 +199,8 @@ def main():
                 bad += not same
                 lines.append((f"{label}.{k}", str(b[k].shape) if k in b.files else "missing", "equal" if same else "DIFFERENT",
                               int(np.count_nonzero(b[k])) if k in b.files else 0))
+            if route_set in ADJ_SWITCHES and (np.count_nonzero(b["__adjoint_bins__"][:-1]) or not b["__adjoint_bins__"][-1]):
+                unmet.append(f"{label}: the adjoint's nodes are not all in the global-scratch bin")
             if mesh_name == "delaunay_neumann":
                 if not pb.get("mfx_boundary", 0) > 0:
                     unmet.append("the Neumann Delaunay mesh has no mfx_boundary nodes")
@@ -194,7 +217,8 @@ def main():
     missing = [k for k in kernels if k not in covered]
     print(f"plan kernels with nodes on at least one mesh ({len(covered)} of {len(kernels)}): " + ", ".join(covered))
     print("plan kernels NOT covered by these meshes: " + (", ".join(missing) or "none"))
-    print("Neumann Delaunay mesh: " + ("; ".join(unmet) if unmet else "mfx_boundary has nodes, neumann_ws has non-zero entries"))
+    print("coverage conditions: " + ("; ".join(unmet) if unmet else
+                                     "the Neumann Delaunay mesh has mfx_boundary nodes and non-zero neumann_ws, the forced adjoint runs in global scratch"))
     ok = not bad and not missing and not unmet
     print("RESULT: " + ("all equal, every plan kernel covered" if ok else "DIFFERENT" if bad else "all equal, but a coverage condition above is NOT met"))
     return 0 if ok else 1
