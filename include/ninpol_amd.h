@@ -461,6 +461,56 @@ int nin_gls_weights_tangent_device(nin_grid *g, int add_neumann, int32_t n_tange
 int nin_gls_permeability_tangent_host(nin_grid *g, const double *tangent_permeability, const double *cell_values, int32_t n_fields,
                                       double *node_values, double *neumann_ws);
 
+/* ---- the GLS Jacobian in the permeability, kept on the device: linearise once, apply J and J^T many times ----------------------
+ * The two calls above repeat the dense QR of every node at every call.  A Krylov solver applies J . dK or J^T . v once per iteration
+ * at ONE linearisation point; for it, a nin_gls_jacobian keeps the derivative itself.  For a fixed cell field u (and optional node
+ * values b) the node values  F_p(K) = sum_i d_i(K) u[c_i] + neumann_ws_p(K) b_p  (d: the stored weights with add_neumann = 1, the W of
+ * nin_apply_*) have the sparse Jacobian
+ *   C[pos][k] = dF_p / d perm_e[k], k < 9 (diff_mag held fixed),   C[pos][9] = dF_p / d diff_mag_e
+ * with pos the esup position of the pair (p, e) -- exactly what one launch of the adjoint kernel with dev_grad_csr[pos] = u[esup[pos]]
+ * and dev_grad_neumann_ws = b leaves in its contribution buffer.  The object owns such a buffer (80 bytes per entry of esup: 6.4 GB at
+ * 216^3 hexahedra; NOT the grid's, which the next backward call overwrites) and `fold` [n_elems] = 2 (1 - 3 / tr K_e) 3 / tr K_e^2, the
+ * derivative of the table's diff_mag at the linearisation point.  Lifetime as nin_hostmatrix: the object refers to its grid in every
+ * call but nin_gls_jacobian_destroy, which may come after nin_grid_destroy.  All dev_* pointers are DEVICE pointers, `stream` a
+ * hipStream_t (NULL = default).
+ *
+ * nin_gls_jacobian_create: the two buffers.  NIN_ENOMEM (nothing is left behind), NIN_ENODEVICE for a grid that is not on a device.
+ * nin_gls_jacobian_linearize: dev_u_cells [n_elems], dev_neumann_values [n_points] or NULL (b = 0).  One launch of the adjoint kernel
+ *   on every bin (NIN_GLS_ADJ_ONLY is not read: a linearisation is always complete) at what is resident NOW -- geometry, flags, K --
+ *   into the object's buffer, and `fold` from the resident K; the cost of one backward call.  Makes the grid's bins if they are not
+ *   there, never the grid's own contribution buffer; needs a temporary of 8 bytes per entry of esup and waits for the device when it
+ *   frees it.  May be called again on the same object.  Errors as nin_gls_weights_backward_device.
+ * nin_gls_jacobian_apply: dev_dnode[t][p] = sum over the row of p of ( sum_k C[pos][k] dev_dperm[t][e][k] + C[pos][9] ddm[t][e] ) for n
+ *   directions dev_dperm [n][n_elems][9]; ddm = dev_ddiff_mag [n][n_elems], or with NULL folded: ddm[t][e] = fold[e] tr dperm[t][e].
+ *   Every entry of dev_dnode [n][n_points] is written, exact zeros for the nodes the forward gives the zero row.
+ * nin_gls_jacobian_apply_transpose: dev_grad_perm[t][e][k] = sum over the nodes p of cell e, ascending node id, of dev_v[t][p]
+ *   C[pos][k] for dev_v [n][n_points], and dev_grad_diff_mag [n][n_elems] the same for k = 9; with NULL that sum times fold[e] is
+ *   added to the three diagonal entries.  dev_v = 1 gives, bit for bit, what nin_gls_weights_backward_device(g, 1, u[esup], b, ...)
+ *   returned at the linearisation point.  Uses the transpose index of nin_spmv_transpose_device (built, with a wait for `stream`,
+ *   when it is not there).
+ *   Both are single passes over the buffer, read once per four directions; asynchronous on `stream`, deterministic, no atomics: two
+ *   calls agree bit for bit, a batch equals its members one by one.  Both read only the object's buffers and the connectivity: a
+ *   later update of the permeability, the points or the flags does not change their answers -- the object IS the Jacobian at its
+ *   linearisation point.  NIN_ESTATE before the first nin_gls_jacobian_linearize, NIN_EINVAL for n < 1 or a NULL argument.
+ * nin_gls_jacobian_contrib: the two device buffers, read-only.  nin_gls_jacobian_stamp: the grid's (nin_grid_field_updates,
+ *   nin_grid_geometry_updates, nin_grid_flag_updates) as the last linearisation found them, -1 before it.
+ * nin_gls_jacobian_*_host: the same with HOST pointers, synchronous (temporaries on the device per call);
+ *   nin_gls_jacobian_fetch_host copies contrib [nnz_esup][10] and fold [n_elems] to the host. */
+typedef struct nin_gls_jacobian nin_gls_jacobian;
+int nin_gls_jacobian_create(nin_grid *g, nin_gls_jacobian **out);
+int nin_gls_jacobian_linearize(nin_gls_jacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream);
+int nin_gls_jacobian_apply(nin_gls_jacobian *J, int32_t n, const double *dev_dperm, const double *dev_ddiff_mag, double *dev_dnode,
+                           void *stream);
+int nin_gls_jacobian_apply_transpose(nin_gls_jacobian *J, int32_t n, const double *dev_v, double *dev_grad_perm,
+                                     double *dev_grad_diff_mag, void *stream);
+int nin_gls_jacobian_contrib(nin_gls_jacobian *J, const double **dev_contrib, const double **dev_fold);
+int nin_gls_jacobian_stamp(const nin_gls_jacobian *J, int64_t stamp[3]);
+void nin_gls_jacobian_destroy(nin_gls_jacobian *J);
+int nin_gls_jacobian_linearize_host(nin_gls_jacobian *J, const double *u_cells, const double *neumann_values);
+int nin_gls_jacobian_apply_host(nin_gls_jacobian *J, int32_t n, const double *dperm, const double *ddiff_mag, double *dnode);
+int nin_gls_jacobian_apply_transpose_host(nin_gls_jacobian *J, int32_t n, const double *v, double *grad_perm, double *grad_diff_mag);
+int nin_gls_jacobian_fetch_host(nin_gls_jacobian *J, double *contrib, double *fold);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].

@@ -31,6 +31,9 @@ EXPORTS = (
     "nin_csr_patch_rows",
     "nin_gls_weights_backward_device", "nin_sddmm_device", "nin_gls_adjoint_plan", "nin_gls_permeability_gradient_host",
     "nin_gls_weights_tangent_device", "nin_gls_permeability_tangent_host",
+    "nin_gls_jacobian_create", "nin_gls_jacobian_linearize", "nin_gls_jacobian_apply", "nin_gls_jacobian_apply_transpose",
+    "nin_gls_jacobian_contrib", "nin_gls_jacobian_stamp", "nin_gls_jacobian_destroy", "nin_gls_jacobian_linearize_host",
+    "nin_gls_jacobian_apply_host", "nin_gls_jacobian_apply_transpose_host", "nin_gls_jacobian_fetch_host",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -84,6 +87,18 @@ def load():
     L.nin_gls_permeability_gradient_host.argtypes = [vp, vp, vp, i32, vp]
     L.nin_gls_weights_tangent_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.nin_gls_permeability_tangent_host.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.nin_gls_jacobian_create.argtypes = [vp, ctypes.POINTER(vp)]
+    L.nin_gls_jacobian_linearize.argtypes = [vp, vp, vp, vp]
+    L.nin_gls_jacobian_apply.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.nin_gls_jacobian_apply_transpose.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.nin_gls_jacobian_contrib.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.nin_gls_jacobian_stamp.argtypes = [vp, vp]
+    L.nin_gls_jacobian_destroy.argtypes = [vp]
+    L.nin_gls_jacobian_destroy.restype = None
+    L.nin_gls_jacobian_linearize_host.argtypes = [vp, vp, vp]
+    L.nin_gls_jacobian_apply_host.argtypes = [vp, i32, vp, vp, vp]
+    L.nin_gls_jacobian_apply_transpose_host.argtypes = [vp, i32, vp, vp, vp]
+    L.nin_gls_jacobian_fetch_host.argtypes = [vp, vp, vp]
     L.nin_pack_connectivity.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     L.nin_pack_table_row.argtypes = [vp, i64, i64, i64, vp]
     L.nin_diff_mag.argtypes = [vp, i64, vp]

@@ -35,6 +35,8 @@ UNITS = [
     ("kernels_gls_quad4.hip", "hipcc", []),
     # the GLS weights differentiated with respect to the permeability: a dense QR per node kept for two solves, and the gather
     ("kernels_gls_adjoint.hip", "hipcc", []),
+    # the Jacobian that one adjoint launch leaves in a contribution buffer, applied: J . dK node-major, J^T . v cell-major
+    ("kernels_gls_jacobian.hip", "hipcc", []),
     ("kernels_csr.hip", "hipcc", []),
     # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
     ("csr_dirty.hip", "hipcc", []),
@@ -51,12 +53,13 @@ UNITS = [
     ("fields_scatter.hip", "hipcc", ["-ffp-contract=off"]),
     # Neumann flags from device memory: integer work on bytes, one float64 -> integer cast; nothing to contract
     ("flags_update.hip", "hipcc", []),
-    # the C ABI's host code by area (abi_internal.hpp is what the five share); only abi_plan.hip has a kernel, the locality keys
+    # the C ABI's host code by area (abi_internal.hpp is what the six share); only abi_plan.hip has a kernel, the locality keys
     ("abi_grid.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_plan.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_update.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_csr.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_apply.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_jacobian.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),
 ]

@@ -6,12 +6,10 @@
 
 using namespace nin;
 
-namespace {
-
 // The cell-major index of the esup pattern (DeviceGrid::tr_*), built once per grid by the first transpose call: a stable radix sort
 // of the pairs (esup[j], j) by cell keeps ascending j -- hence ascending node id -- within each cell; cell_ptr and the node of each
 // position follow by binary search.  Synchronises `stream` (the sort's temporaries are freed before the call returns).
-int ensure_transpose_index(DeviceGrid &d, hipStream_t stream) {
+int nin::ensure_transpose_index(DeviceGrid &d, hipStream_t stream) {
     if (d.tr_cell_ptr) return NIN_OK;
     const int32_t E = d.v.n_elems, nnz = (int32_t)d.nnz_e;
     int32_t *&ptr = d.tr_cell_ptr, *&pos = d.tr_cell_pos, *&node = d.tr_cell_node;   // (cleared again if the build fails)
@@ -39,8 +37,6 @@ int ensure_transpose_index(DeviceGrid &d, hipStream_t stream) {
     if (rc) { dev_release(d, ptr); dev_release(d, pos); dev_release(d, node); }
     return rc;
 }
-
-}  // namespace
 
 // the weights of the last apply: one buffer per grid, allocated on first use
 static int ensure_apply_weights(DeviceGrid &d) {
@@ -173,7 +169,7 @@ void nin::release_adjoint_state(DeviceGrid &d) {
 
 // The bins and the scratch slots, made by whichever of the backward, tangent and plan calls comes first.  Synchronises `stream` (one
 // device-to-host copy of 8 bytes a node).
-static int ensure_adjoint_bins(DeviceGrid &d, hipStream_t stream) {
+int nin::ensure_adjoint_bins(DeviceGrid &d, hipStream_t stream) {
     if (d.adj_ready) return NIN_OK;
     const int32_t P = d.v.n_points;
     const bool force_global = getenv("NIN_GLS_ADJ_FORCE_GLOBAL") != nullptr;   // testing switch: every system in global scratch
@@ -218,6 +214,20 @@ static int ensure_adjoint_contrib(DeviceGrid &d) {
     return d.adj_contrib ? NIN_OK : dev_alloc(d, &d.adj_contrib, (size_t)std::max<int64_t>(d.nnz_e, 1) * 10);
 }
 
+// The adjoint kernel on the nodes of every bin (only >= 0: of that bin alone), the ten values of every (node, cell) pair into `contrib`:
+// the grid's buffer for the backward call, a nin_gls_jacobian's own for a linearisation
+int nin::launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
+                             hipStream_t stream) {
+    int rc = NIN_OK;
+    for (int b = 0; b < kAdjBins && !rc; ++b) {
+        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
+        if (only >= 0 && b != only) continue;
+        rc = launch_gls_adjoint(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, grad_csr, grad_nws, contrib, d.adj_scratch,
+                                d.adj_scratch_stride, d.adj_scratch_slots, stream);
+    }
+    return rc;
+}
+
 int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
                                     double *dev_grad_perm, double *dev_grad_diff_mag, void *stream_) {
     if (!g || !dev_grad_csr || !dev_grad_perm) return fail(NIN_EINVAL, "NULL argument");
@@ -232,12 +242,7 @@ int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *
     if (rc) return rc;
     const char *only_env = getenv("NIN_GLS_ADJ_ONLY");   // per-bin timing (tools/time_adjoint.py): launch only that bin; read at every call
     const int only = only_env ? atoi(only_env) : -1;
-    for (int b = 0; b < kAdjBins && !rc; ++b) {
-        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
-        if (only >= 0 && b != only) continue;
-        rc = launch_gls_adjoint(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, dev_grad_csr, dev_grad_neumann_ws, d.adj_contrib,
-                                d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots, stream);
-    }
+    rc = launch_adjoint_bins(d, add_neumann, only, dev_grad_csr, dev_grad_neumann_ws, d.adj_contrib, stream);
     if (!rc) rc = launch_adjoint_gather(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.adj_contrib, dev_grad_perm, dev_grad_diff_mag, stream);
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     return NIN_OK;

@@ -1,4 +1,4 @@
-// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply.hip;
+// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian.hip;
 // exchange.hip takes the error setter): the grid behind the handle, the text of nin_last_error(), the preconditions of the entry
 // points, device memory owned by the grid or by one call, and the functions of one unit that another calls.
 #pragma once
@@ -167,6 +167,12 @@ inline size_t desc_align(size_t words) { return (words + 3) & ~(size_t)3; }
 int fetch_flag_bytes(nin_grid *g);
 // abi_apply.hip: the adjoint's and the tangent's bins and scratch slots, and the adjoint's contribution buffer, given back
 void release_adjoint_state(DeviceGrid &d);
+// abi_apply.hip, for abi_jacobian.hip: the cell-major index of the esup pattern and the adjoint's bins, made if they are not there
+// (both synchronise `stream` when they build); the adjoint kernel on every bin (only >= 0: that bin alone) into `contrib`
+int ensure_transpose_index(DeviceGrid &d, hipStream_t stream);
+int ensure_adjoint_bins(DeviceGrid &d, hipStream_t stream);
+int launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
+                        hipStream_t stream);
 
 }  // namespace nin
 #pragma GCC visibility pop

@@ -1,0 +1,183 @@
+// abi_jacobian.hip -- the C ABI, part 6: the GLS Jacobian in the permeability as an object the caller keeps: one adjoint
+// launch linearises, two streaming kernels apply J and J^T from the object's own buffers (kernels_gls_jacobian.hip).
+#include "abi_internal.hpp"
+#include "gls_adjoint.hpp"
+
+using namespace nin;
+
+struct nin_gls_jacobian {
+    nin_grid *g = nullptr;
+    int device = -1;                 // the grid's, as it was at creation: nin_gls_jacobian_destroy does not look at the grid, which may be gone
+    double *contrib = nullptr;       // [nnz_esup][10]: the adjoint's contribution buffer, this object's own -- the Jacobian
+    double *fold = nullptr;          // [E]: d diff_mag / d K_dd of the permeability that was resident at the linearisation
+    bool linearized = false;
+    int64_t stamp[3] = {-1, -1, -1};   // the grid's (field_updates, geometry_updates, flag_updates) at the linearisation
+};
+
+namespace {
+
+// what the two apply calls share: the arguments, the grid on its device, a linearisation to apply
+int apply_ready(const nin_gls_jacobian *J, int32_t n, const void *in, const void *out) {
+    if (n < 1) return fail(NIN_EINVAL, "n must be >= 1");
+    if (!J || !in || !out) return fail(NIN_EINVAL, "NULL argument");
+    if (int rc = on_device(J->g, kHintKernels)) return rc;
+    if (!J->linearized) return fail(NIN_ESTATE, "the Jacobian has not been linearised (call nin_gls_jacobian_linearize first)");
+    return NIN_OK;
+}
+
+}  // namespace
+
+int nin_gls_jacobian_create(nin_grid *g, nin_gls_jacobian **out) {
+    if (!g || !out) return fail(NIN_EINVAL, "NULL argument");
+    *out = nullptr;
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintToDevice)) return rc;
+    HIP_TRY(hipSetDevice(d.device));
+    nin_gls_jacobian *J = new (std::nothrow) nin_gls_jacobian();
+    if (!J) return fail(NIN_ENOMEM, "out of host memory");
+    J->g = g;
+    J->device = d.device;
+    const size_t cb = (size_t)std::max<int64_t>(d.nnz_e, 1) * 10 * sizeof(double), fb = (size_t)std::max<int64_t>(g->h.n_elems, 1) * sizeof(double);
+    hipError_t e = hipMalloc((void **)&J->contrib, cb);
+    if (e == hipSuccess) e = hipMalloc((void **)&J->fold, fb);
+    if (e != hipSuccess) {
+        nin_gls_jacobian_destroy(J);
+        return fail(NIN_ENOMEM, "hipMalloc(%zu + %zu bytes): %s", cb, fb, hipGetErrorString(e));
+    }
+    *out = J;
+    return NIN_OK;
+}
+
+void nin_gls_jacobian_destroy(nin_gls_jacobian *J) {
+    if (!J) return;
+    if (J->device >= 0) (void)hipSetDevice(J->device);
+    if (J->contrib) (void)hipFree(J->contrib);   // (waits for the device)
+    if (J->fold) (void)hipFree(J->fold);
+    delete J;
+}
+
+int nin_gls_jacobian_linearize(nin_gls_jacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream_) {
+    if (!J || !dev_u_cells) return fail(NIN_EINVAL, "NULL argument");
+    nin_grid *g = J->g;
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = ensure_adjoint_bins(d, stream);
+    if (rc) return rc;
+    J->linearized = false;
+    // the cotangent of F = W u + neumann_ws b: grad_csr[pos] = u[esup[pos]], grad_neumann_ws = b
+    DevTmp<double> seed;
+    HIP_TRY(hipMalloc((void **)&seed, (size_t)std::max<int64_t>(d.nnz_e, 1) * sizeof(double)));
+    rc = launch_jac_seed(d.v, d.nnz_e, dev_u_cells, seed, stream);
+    if (!rc) rc = launch_adjoint_bins(d, 1, -1, seed, dev_neumann_values, J->contrib, stream);   // always every bin
+    if (!rc) rc = launch_jac_fold(d.v, J->fold, stream);
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    J->stamp[0] = d.field_updates;
+    J->stamp[1] = d.geom_updates;
+    J->stamp[2] = d.flag_updates;
+    J->linearized = true;
+    return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
+}
+
+int nin_gls_jacobian_apply(nin_gls_jacobian *J, int32_t n, const double *dev_dperm, const double *dev_ddiff_mag, double *dev_dnode,
+                           void *stream_) {
+    if (int rc = apply_ready(J, n, dev_dperm, dev_dnode)) return rc;
+    DeviceGrid &d = J->g->d;
+    HIP_TRY(hipSetDevice(d.device));
+    const int rc = launch_jac_apply(d.v, J->contrib, J->fold, n, dev_dperm, dev_ddiff_mag, dev_dnode, static_cast<hipStream_t>(stream_));
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_gls_jacobian_apply_transpose(nin_gls_jacobian *J, int32_t n, const double *dev_v, double *dev_grad_perm, double *dev_grad_diff_mag,
+                                     void *stream_) {
+    if (int rc = apply_ready(J, n, dev_v, dev_grad_perm)) return rc;
+    DeviceGrid &d = J->g->d;
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = ensure_transpose_index(d, stream);   // (every time: nin_grid_release_scratch may have dropped it)
+    if (rc) return rc;
+    rc = launch_jac_apply_transpose(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.tr_cell_node, J->contrib, J->fold, n, dev_v, dev_grad_perm,
+                                    dev_grad_diff_mag, stream);
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_gls_jacobian_contrib(nin_gls_jacobian *J, const double **dev_contrib, const double **dev_fold) {
+    if (!J || !dev_contrib || !dev_fold) return fail(NIN_EINVAL, "NULL argument");
+    *dev_contrib = J->contrib;
+    *dev_fold = J->fold;
+    return NIN_OK;
+}
+
+int nin_gls_jacobian_stamp(const nin_gls_jacobian *J, int64_t stamp[3]) {
+    if (!J || !stamp) return fail(NIN_EINVAL, "NULL argument");
+    for (int i = 0; i < 3; ++i) stamp[i] = J->stamp[i];
+    return NIN_OK;
+}
+
+// ---- host pointers: what Interpolator.permeability_jacobian calls (synchronous) ------------------------------------------------------
+int nin_gls_jacobian_linearize_host(nin_gls_jacobian *J, const double *u_cells, const double *neumann_values) {
+    if (!J || !u_cells) return fail(NIN_EINVAL, "NULL argument");
+    nin_grid *g = J->g;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    HIP_TRY(hipSetDevice(g->d.device));
+    const size_t pb = std::max<size_t>((size_t)g->h.n_points, 1) * 8, eb = std::max<size_t>((size_t)g->h.n_elems, 1) * 8;
+    DevTmp<double> du, db;
+    HIP_TRY(hipMalloc((void **)&du, eb));
+    HIP_TRY(hipMemcpy(du, u_cells, (size_t)g->h.n_elems * 8, hipMemcpyHostToDevice));
+    if (neumann_values) {
+        HIP_TRY(hipMalloc((void **)&db, pb));
+        HIP_TRY(hipMemcpy(db, neumann_values, (size_t)g->h.n_points * 8, hipMemcpyHostToDevice));
+    }
+    if (int rc = nin_gls_jacobian_linearize(J, du, neumann_values ? db.p : nullptr, nullptr)) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return NIN_OK;
+}
+
+int nin_gls_jacobian_apply_host(nin_gls_jacobian *J, int32_t n, const double *dperm, const double *ddiff_mag, double *dnode) {
+    if (int rc = apply_ready(J, n, dperm, dnode)) return rc;
+    nin_grid *g = J->g;
+    HIP_TRY(hipSetDevice(g->d.device));
+    const size_t P = (size_t)g->h.n_points, E = (size_t)g->h.n_elems, k = (size_t)n;
+    DevTmp<double> dk, dm, dv;
+    HIP_TRY(hipMalloc((void **)&dk, std::max<size_t>(E, 1) * 72 * k));
+    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(P, 1) * 8 * k));
+    HIP_TRY(hipMemcpy(dk, dperm, E * 72 * k, hipMemcpyHostToDevice));
+    if (ddiff_mag) {
+        HIP_TRY(hipMalloc((void **)&dm, std::max<size_t>(E, 1) * 8 * k));
+        HIP_TRY(hipMemcpy(dm, ddiff_mag, E * 8 * k, hipMemcpyHostToDevice));
+    }
+    if (int rc = nin_gls_jacobian_apply(J, n, dk, ddiff_mag ? dm.p : nullptr, dv, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(dnode, dv, P * 8 * k, hipMemcpyDeviceToHost));
+    return NIN_OK;
+}
+
+int nin_gls_jacobian_apply_transpose_host(nin_gls_jacobian *J, int32_t n, const double *v, double *grad_perm, double *grad_diff_mag) {
+    if (int rc = apply_ready(J, n, v, grad_perm)) return rc;
+    nin_grid *g = J->g;
+    HIP_TRY(hipSetDevice(g->d.device));
+    const size_t P = (size_t)g->h.n_points, E = (size_t)g->h.n_elems, k = (size_t)n;
+    DevTmp<double> dk, dm, dv;
+    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(P, 1) * 8 * k));
+    HIP_TRY(hipMalloc((void **)&dk, std::max<size_t>(E, 1) * 72 * k));
+    if (grad_diff_mag) HIP_TRY(hipMalloc((void **)&dm, std::max<size_t>(E, 1) * 8 * k));
+    HIP_TRY(hipMemcpy(dv, v, P * 8 * k, hipMemcpyHostToDevice));
+    if (int rc = nin_gls_jacobian_apply_transpose(J, n, dv, dk, grad_diff_mag ? dm.p : nullptr, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(grad_perm, dk, E * 72 * k, hipMemcpyDeviceToHost));
+    if (grad_diff_mag) HIP_TRY(hipMemcpy(grad_diff_mag, dm, E * 8 * k, hipMemcpyDeviceToHost));
+    return NIN_OK;
+}
+
+int nin_gls_jacobian_fetch_host(nin_gls_jacobian *J, double *contrib, double *fold) {
+    if (!J || !contrib || !fold) return fail(NIN_EINVAL, "NULL argument");
+    if (!J->linearized) return fail(NIN_ESTATE, "the Jacobian has not been linearised (call nin_gls_jacobian_linearize first)");
+    nin_grid *g = J->g;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    HIP_TRY(hipSetDevice(g->d.device));
+    HIP_TRY(hipMemcpy(contrib, J->contrib, (size_t)g->d.nnz_e * 80, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fold, J->fold, (size_t)g->h.n_elems * 8, hipMemcpyDeviceToHost));
+    return NIN_OK;
+}

@@ -136,6 +136,20 @@ int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t
                        const double *tangent_perm, const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz,
                        double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
 
+// the GLS Jacobian kept and applied (kernels_gls_jacobian.hip), all DEVICE pointers; contrib [nnz_esup][10] as an adjoint
+// launch with grad_csr = u[esup] left it, fold [E] = d diff_mag / d K_dd at the linearisation point.
+// launch_jac_seed: grad_csr[pos] = u[esup[pos]].  launch_jac_fold: fold from the resident g.perm.
+// launch_jac_apply: out [n][P] = J . (dperm [n][E][9], ddm [n][E] or null: folded); every entry written.
+// launch_jac_apply_transpose: grad_perm [n][E][9] (grad_dm [n][E], or null: folded into the diagonal) = J^T . v [n][P], per cell in
+//   ascending node id through the transpose index, the order of launch_adjoint_gather
+int launch_jac_seed(const GridView &g, int64_t nnz, const double *u, double *grad_csr, hipStream_t stream);
+int launch_jac_fold(const GridView &g, double *fold, hipStream_t stream);
+int launch_jac_apply(const GridView &g, const double *contrib, const double *fold, int32_t n, const double *dperm, const double *ddm,
+                     double *out, hipStream_t stream);
+int launch_jac_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
+                               const double *contrib, const double *fold, int32_t n, const double *v, double *grad_perm, double *grad_dm,
+                               hipStream_t stream);
+
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream);
 // GLS launch plan (grid_device.hip): the class byte of every node (gls_plan.hpp: gls_class_byte of the kernel that takes it; use_group =

@@ -13,6 +13,7 @@ import time
 
 import numpy as np
 import scipy.sparse as sp
+import scipy.sparse.linalg as spla
 
 from . import _args as A
 from . import _lib
@@ -913,6 +914,38 @@ class Interpolator:
         _lib.check(_lib.load().nin_gls_permeability_tangent_host(g._h, _ptr(d), _ptr(u), k, _ptr(out), _ptr(nws)))
         return out, nws
 
+    def permeability_jacobian(self, variable, cell_values=None, neumann_values=None):
+        """The Jacobian of what `apply(variable, "gls")` returns, `W u` (+ `neumann_ws * neumann_values` when those are given), with
+        respect to the permeability table, linearised ONCE at the resident table and kept on the device: a scipy LinearOperator of
+        shape (n_points, 9 n_elems), float64 (PermeabilityJacobian: `matvec` = J . dK for a flattened (n_elems, 3, 3) direction,
+        `rmatvec` = J^T . v, `matmat` / `rmatmat` batched in one launch each, `to_scipy()` the explicit csr_matrix, `release()`).
+        `cell_values` = u (n_elems,), default the cell variable `variable` itself; `neumann_values` = b (n_points,) or None.  The chain
+        through diff_mag = (1 - 3 / tr K)^2 is folded in.  The sibling of permeability_gradient() / permeability_tangent() for a Krylov
+        solver: those factorise every node at every call, this does so once (the cost of one permeability_gradient) and every product
+        afterwards streams the kept buffer (80 bytes per entry of esup, on the device).  Later update_*() calls do not change the
+        operator; build a new one at the new point.  Host-synchronous, numpy in and out."""
+        self._check_call(variable=variable)
+        self._perm_rows()   # (ValueError without a permeability)
+        g = self.grid
+        if cell_values is None:
+            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
+        else:
+            u = cell_values
+        u = np.ascontiguousarray(u, dtype=DTYPE_F)
+        if u.shape != (g.n_elems,):
+            raise ValueError(f"cell_values must have shape ({g.n_elems},), not {u.shape}.")
+        b = None
+        if neumann_values is not None:
+            b = np.ascontiguousarray(neumann_values, dtype=DTYPE_F)
+            if b.shape != (g.n_points,):
+                raise ValueError(f"neumann_values must have shape ({g.n_points},), not {b.shape}.")
+        if g.device < 0:
+            g.to_device(self.device)
+        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        jac = GlsJacobian(g)
+        _lib.check(_lib.load().nin_gls_jacobian_linearize_host(jac._handle(), _ptr(u), _ptr(b)))
+        return PermeabilityJacobian(jac)
+
     def release_scratch(self, pinned=True):
         """Give back what the object keeps between calls for speed: the grid's device scratch (weights, compacted
         triplets: ~2.3 GB of HBM at 10 M cells; the transpose index of apply_transpose(): 0.69 GB more) and, with pinned=True, the idle page-locked result buffers of the
@@ -1080,6 +1113,163 @@ class DevicePlan:
         _lib.check(_lib.load().nin_gls_weights_tangent_device(self.grid._h, int(bool(add_neumann)), int(n_tangents), vp(tangent_perm_ptr),
                                                               vp(tangent_diff_mag_ptr), vp(tangent_csr_ptr), vp(tangent_neumann_ws_ptr),
                                                               ctypes.c_void_p(stream)))
+
+    def linearize(self, u_ptr, neumann_values_ptr=0, stream=0):
+        """The Jacobian of the node values `W u + neumann_ws * b` in the permeability, kept on the device: a GlsJacobian linearised at
+        what is resident now, for the cell field u [n_elems] (and node values b [n_points], 0: none), both device pointers.  One launch
+        of the adjoint kernel (the cost of one launch_weights_backward); its launch_jvp / launch_vjp then stream 80 bytes per entry of
+        esup instead of factorising every node again.  The object owns its buffers (80 bytes per entry of esup).  Only GLS depends on K."""
+        if self.method != "gls":
+            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: linearize is GLS only")
+        if not u_ptr:
+            raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
+        J = GlsJacobian(self.grid, plan=self)
+        J.relinearize(u_ptr, neumann_values_ptr, stream)
+        return J
+
+
+class GlsJacobian:
+    """The sparse Jacobian of `F(K) = W(K) u + neumann_ws(K) * b` with respect to the permeability at ONE linearisation point, resident
+    on the device (nin_gls_jacobian): `contrib_ptr` [nnz_esup][10] holds, per (node, cell) pair in esup position, dF_p / d
+    perm_e[0..9) and dF_p / d diff_mag_e; `fold_ptr` [n_elems] the derivative of the table's diff_mag = (1 - 3 / tr K)^2 there.
+    `launch_jvp` is J . dK, `launch_vjp` is J^T . v, each one streaming pass over the buffer per four directions, asynchronous on the
+    caller's stream, bitwise reproducible.  Later updates of the permeability, the points or the flags do not change the answers: the
+    object is the Jacobian where it was linearised (`stamp`; `is_current()` says whether the grid is still there).  `relinearize`
+    moves it.  Made by DevicePlan.linearize(); its device buffers (`nbytes`) are its own: a launch_weights_backward in between does not
+    disturb it."""
+
+    def __init__(self, grid, plan=None):
+        self.grid, self.plan = grid, plan
+        self._h = None
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().nin_gls_jacobian_create(grid._h, ctypes.byref(h)))
+        self._h = h
+        self.nbytes = 80 * int(grid.nnz_esup) + 8 * int(grid.n_elems)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("this GlsJacobian was released")
+        return self._h
+
+    def relinearize(self, u_ptr, neumann_values_ptr=0, stream=0):
+        """Linearise again, at what is resident now, for u [n_elems] (and b [n_points], 0: none), device pointers: what a fresh
+        DevicePlan.linearize would hold, bit for bit, in the buffers this object already owns."""
+        if self.plan is not None:
+            self.plan.ensure_current()
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_jacobian_linearize(self._handle(), vp(u_ptr), vp(neumann_values_ptr), ctypes.c_void_p(stream)))
+
+    def launch_jvp(self, dperm_ptr, out_ptr, n=1, ddm_ptr=0, stream=0):
+        """J . dK for n directions (nin_gls_jacobian_apply): dperm [n][n_elems][9] -> out [n][n_points], every entry written.  ddm
+        [n][n_elems]: the table's diff_mag as an independent input with its own direction; 0: its chain folded, at the permeability of
+        the linearisation.  Asynchronous on `stream`."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_jacobian_apply(self._handle(), int(n), vp(dperm_ptr), vp(ddm_ptr), vp(out_ptr), ctypes.c_void_p(stream)))
+
+    def launch_vjp(self, v_ptr, grad_perm_ptr, n=1, grad_dm_ptr=0, stream=0):
+        """J^T . v for n node fields (nin_gls_jacobian_apply_transpose): v [n][n_points] -> grad_perm [n][n_elems][9] (and grad_dm
+        [n][n_elems]; 0: folded into the diagonal of grad_perm).  v = 1 is launch_weights_backward(grad_csr = u[esup], grad_neumann_ws =
+        b) at the linearisation point, bit for bit.  Asynchronous on `stream` (the first call on a grid without the transpose index
+        builds it and synchronises)."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_jacobian_apply_transpose(self._handle(), int(n), vp(v_ptr), vp(grad_perm_ptr), vp(grad_dm_ptr),
+                                                                ctypes.c_void_p(stream)))
+
+    def _buffers(self):
+        c, f = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(_lib.load().nin_gls_jacobian_contrib(self._handle(), ctypes.byref(c), ctypes.byref(f)))
+        return int(c.value or 0), int(f.value or 0)
+
+    @property
+    def contrib_ptr(self):
+        return self._buffers()[0]
+
+    @property
+    def fold_ptr(self):
+        return self._buffers()[1]
+
+    @property
+    def stamp(self):
+        """the grid's (field_updates, geometry_updates, flag_updates) at the last linearisation"""
+        s = np.zeros(3, dtype=np.int64)
+        _lib.check(_lib.load().nin_gls_jacobian_stamp(self._handle(), _ptr(s)))
+        return tuple(int(x) for x in s)
+
+    def is_current(self):
+        """Is the grid's resident permeability, geometry and flag set still the one this object was linearised at?  (Device-side updates
+        count; launch_jvp / launch_vjp answer for the linearisation point either way.)"""
+        g = self.grid
+        return self.stamp == (g.field_updates, g.geometry_updates, g.flag_updates)
+
+    def fetch(self):
+        """(contrib (nnz_esup, 10), fold (n_elems,)) on the host (waits for the device)"""
+        g = self.grid
+        contrib, fold = np.empty((int(g.nnz_esup), 10), dtype=DTYPE_F), np.empty(int(g.n_elems), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_jacobian_fetch_host(self._handle(), _ptr(contrib), _ptr(fold)))
+        return contrib, fold
+
+    def release(self):
+        """Give the device buffers back (waits for the device); the object is unusable afterwards."""
+        if self._h is not None:
+            _lib.load().nin_gls_jacobian_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+class PermeabilityJacobian(spla.LinearOperator):
+    """Interpolator.permeability_jacobian's result: the (n_points, 9 n_elems) Jacobian of `apply(variable, "gls")`'s node values in
+    the permeability table (column 9 e + k is entry k of cell e's row-major 3 x 3 tensor; the diff_mag chain folded), as a
+    scipy LinearOperator over a GlsJacobian: numpy in and out, host-synchronous, one launch per matvec / rmatvec and one per batched
+    matmat / rmatmat."""
+
+    def __init__(self, jac):
+        g = jac.grid
+        self.jacobian = jac
+        self._P, self._E = int(g.n_points), int(g.n_elems)
+        super().__init__(dtype=np.dtype(DTYPE_F), shape=(self._P, 9 * self._E))
+
+    def _jvp(self, d):        # d (k, 9 E) -> (k, P)
+        d = np.ascontiguousarray(d, dtype=DTYPE_F)
+        out = np.empty((len(d), self._P), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_jacobian_apply_host(self.jacobian._handle(), len(d), _ptr(d), None, _ptr(out)))
+        return out
+
+    def _vjp(self, v):        # v (k, P) -> (k, 9 E)
+        v = np.ascontiguousarray(v, dtype=DTYPE_F)
+        out = np.empty((len(v), 9 * self._E), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_jacobian_apply_transpose_host(self.jacobian._handle(), len(v), _ptr(v), _ptr(out), None))
+        return out
+
+    def _matvec(self, x):
+        return self._jvp(np.asarray(x).reshape(1, -1))[0]
+
+    def _rmatvec(self, x):
+        return self._vjp(np.asarray(x).reshape(1, -1))[0]
+
+    def _matmat(self, X):
+        return self._jvp(np.asarray(X).T).T
+
+    def _rmatmat(self, X):
+        return self._vjp(np.asarray(X).T).T
+
+    def to_scipy(self):
+        """The explicit csr_matrix (n_points, 9 n_elems) from the fetched buffer: row p, column 9 e + k, the fold applied."""
+        g = self.jacobian.grid
+        contrib, fold = self.jacobian.fetch()
+        esup = np.asarray(g.esup).astype(np.int64)
+        data = contrib[:, :9].copy()
+        data[:, (0, 4, 8)] += (contrib[:, 9] * fold[esup])[:, None]
+        cols = 9 * esup[:, None] + np.arange(9)
+        indptr = 9 * np.asarray(g.esup_ptr).astype(np.int64)
+        return sp.csr_matrix((data.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)
+
+    def release(self):
+        self.jacobian.release()
 
 
 class HostMatrix:

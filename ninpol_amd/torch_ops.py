@@ -4,6 +4,9 @@ also makes the GLS weights a function of the permeability tensor K: its backward
 (nin_sddmm_device) and the adjoint of the weight kernels (nin_gls_weights_backward_device).  Under torch.autograd.forward_ad (dual
 tensors) the same call gives the forward derivative, W du + dW u, with dW from the tangent of the weight kernels
 (nin_gls_weights_tangent_device); torch.func.jvp, which needs setup_context-style Functions, is not supported.
+`CellToNode.linearize(u, K, scale)` is for a caller that needs many such products at one point (a Krylov solver): it keeps the
+Jacobian of W u in the permeability on the device (nin_gls_jacobian) and returns a Linearization whose jvp / vjp are plain tensor
+methods, one streaming pass each instead of a factorisation of every node.
 
 Not imported by `ninpol_amd/__init__.py`: importing the package loads nothing native and does not import torch.  This module
 imports torch, and opens its device, before the native library loads ("A process that also uses a PyTorch-ROCm
@@ -144,6 +147,91 @@ class _ConstantWeightsFn(torch.autograd.Function):
                 torch.zeros_like(scale) if scale is not None and ctx.needs_input_grad[1] else None, None)
 
 
+class Linearization:
+    """CellToNode.linearize's result: `value` = W u at one permeability, with the weights (`weights`, `neumann_ws`), the resident
+    Jacobian of W u (+ neumann_ws * neumann_values) in the permeability (`jacobian`: a GlsJacobian; None for IDW / LS, whose J is 0)
+    and the K / scale it was taken at.  jvp() and vjp() are plain tensor methods on torch's current stream -- no autograd graph -- and
+    cost one streaming pass each instead of a factorisation of every node: what a Krylov solver calls once per iteration."""
+
+    def __init__(self, op, u, weights, neumann_ws, jacobian, K, scale):
+        self.op, self.u, self.weights, self.neumann_ws, self.jacobian, self.K, self.scale = op, u, weights, neumann_ws, jacobian, K, scale
+        self.value = op._spmv(weights, u)
+
+    def _batch(self, t, name, shapes):
+        """t as (k, ...) with its batch flag: one of `shapes` as it is, or with one leading batch dimension"""
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.op.device:
+            raise TypeError(f"{name} must be a float64 torch.Tensor on {self.op.device}")
+        if tuple(t.shape) in shapes:
+            return t.unsqueeze(0), False
+        if t.dim() >= 2 and t.shape[0] >= 1 and tuple(t.shape[1:]) in shapes:
+            return t, True
+        raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, optionally with a leading batch dimension, "
+                         f"not {tuple(t.shape)}")
+
+    def jvp(self, du=None, dK=None, dscale=None):
+        """W du + J (scale * dK + dscale * K): the change of `value` along du (n_elems,), dK shaped like K and dscale (n_elems,), each
+        optional, all with the same optional leading batch dimension.  Returns (n_points,) or (k, n_points)."""
+        op = self.op
+        E, P = op.n_elems, op.n_points
+        if dscale is not None and (self.scale is None or self.K is None):
+            raise ValueError("dscale needs a linearisation taken with K and scale")
+        given = [(t, name, shapes) for t, name, shapes in ((du, "du", ((E,),)), (dK, "dK", ((E, 3, 3), (E, 9))), (dscale, "dscale", ((E,),)))
+                 if t is not None]
+        parts = {name: self._batch(t, name, shapes) for t, name, shapes in given}
+        flags = {b for _, b in parts.values()}
+        ks = {int(t.shape[0]) for t, _ in parts.values()}
+        if len(flags) > 1 or len(ks) > 1:
+            raise ValueError("du, dK and dscale must share their leading batch dimension")
+        batched, k = (flags.pop(), ks.pop()) if parts else (False, 1)
+        out = None
+        if du is not None:
+            out = op._spmv(self.weights, parts["du"][0].contiguous())
+        tperm = None
+        if dK is not None:
+            tperm = parts["dK"][0].reshape(k, E, 9)
+            if self.scale is not None:
+                tperm = tperm * self.scale[None, :, None]
+        if dscale is not None:
+            t = self.K.reshape(1, E, 9) * parts["dscale"][0][:, :, None]
+            tperm = t if tperm is None else tperm + t
+        if tperm is not None and self.jacobian is not None:
+            tperm = tperm.contiguous()
+            jv = torch.empty((k, P), dtype=torch.float64, device=op.device)
+            self.jacobian.launch_jvp(tperm.data_ptr(), jv.data_ptr(), k, 0, op._stream())
+            out = jv if out is None else out + jv
+        if out is None:
+            out = torch.zeros((k, P), dtype=torch.float64, device=op.device)
+        return out if batched else out[0]
+
+    def vjp(self, g):
+        """g (n_points,) or (k, n_points) -> (W^T g, scale * J^T g shaped like K, sum_k K * J^T g or None without a scale): the
+        gradients of <g, value> in u, K and scale, what backward() of CellToNode(u, K, scale) returns."""
+        op = self.op
+        E = op.n_elems
+        g, batched = self._batch(g, "g", ((op.n_points,),))
+        g = g.contiguous()
+        k = int(g.shape[0])
+        gu = op._spmv_transpose(self.weights, g)
+        if self.jacobian is not None:
+            gperm = torch.empty((k, E, 9), dtype=torch.float64, device=op.device)
+            self.jacobian.launch_vjp(g.data_ptr(), gperm.data_ptr(), k, 0, op._stream())
+        else:
+            gperm = torch.zeros((k, E, 9), dtype=torch.float64, device=op.device)
+        kshape = (E, 3, 3) if self.K is None else tuple(self.K.shape)
+        gK = (gperm if self.scale is None else gperm * self.scale[None, :, None]).reshape((k,) + kshape)
+        gscale = None
+        if self.scale is not None and self.K is not None:
+            gscale = (self.K.reshape(1, E, 9) * gperm).sum(dim=2)
+        if batched:
+            return gu, gK, gscale
+        return gu[0], gK[0], None if gscale is None else gscale[0]
+
+    def release(self):
+        """give the Jacobian's device buffers back: jvp() / vjp() with a permeability direction raise afterwards"""
+        if self.jacobian is not None:
+            self.jacobian.release()
+
+
 class CellToNode(torch.nn.Module):
     """Cell fields -> node values through the nodal interpolation matrix W of `interp.interpolate(variable, method)` (with the
     `+ neumann_ws[row]` of the Neumann rows), differentiable in the cell values.
@@ -254,6 +342,44 @@ class CellToNode(torch.nn.Module):
                     raise ValueError(f"{name} must be on {self.device} with shape {' or '.join(map(str, shapes))}")
             return _ConstantWeightsFn.apply(K, scale, self.weights), self.neumann_ws
         return _GlsWeightsFn.apply(K, scale, self)
+
+    def linearize(self, u, K=None, scale=None, neumann_values=None):
+        """Linearise `forward(u, K, scale)` once, for many jvp / vjp products at that point: u float64 (n_elems,) on the plan's device
+        (one field).  With K (and scale) it first does what weights_of does -- scale * K becomes the grid's resident permeability --
+        and computes fresh weights; without, the weights of what is resident now.  Returns a Linearization: `value` = W u, `jvp(du, dK,
+        dscale)`, `vjp(g)`, the weights and -- GLS -- the GlsJacobian of W u + neumann_ws * neumann_values ((n_points,) or None) in the
+        permeability, resident on the device (80 bytes per entry of esup; the cost of one backward pass, once).  IDW / LS do not
+        depend on K: no buffer is allocated and J counts as 0.  No autograd Function is involved: the methods are plain tensor calls
+        on torch's current stream."""
+        if not isinstance(u, torch.Tensor):
+            raise TypeError(f"u must be a torch.Tensor, not {type(u).__name__}")
+        if u.dtype != torch.float64:
+            raise TypeError(f"u must be float64, not {u.dtype} (no silent cast)")
+        if tuple(u.shape) != (self.n_elems,):
+            raise ValueError(f"u must have shape ({self.n_elems},): one field per linearisation, not {tuple(u.shape)}")
+        if u.device != self.device:
+            raise ValueError(f"u must be on {self.device}, not {u.device}")
+        if neumann_values is not None:
+            if not isinstance(neumann_values, torch.Tensor) or neumann_values.dtype != torch.float64:
+                raise TypeError("neumann_values must be a float64 torch.Tensor (no silent cast)")
+            if tuple(neumann_values.shape) != (self.n_points,) or neumann_values.device != self.device:
+                raise ValueError(f"neumann_values must have shape ({self.n_points},) on {self.device}")
+        if K is None and scale is not None:
+            raise ValueError("scale needs K")
+        u = u.detach().contiguous()
+        if K is not None:
+            with torch.no_grad():
+                weights, neumann_ws = self.weights_of(K.detach(), None if scale is None else scale.detach())
+            K, scale = K.detach(), None if scale is None else scale.detach()
+        elif self.plan.method == "gls":
+            weights, neumann_ws = self._launch_weights()
+        else:
+            weights, neumann_ws = self.weights, self.neumann_ws
+        jac = None
+        if self.plan.method == "gls":
+            b = None if neumann_values is None else neumann_values.detach().contiguous()
+            jac = self.plan.linearize(u.data_ptr(), 0 if b is None else b.data_ptr(), self._stream())
+        return Linearization(self, u, weights, neumann_ws, jac, K, scale)
 
     def forward(self, u, K=None, scale=None):
         """u: float64 (n_elems,) or (k, n_elems) on the plan's device -> node values (n_points,) or (k, n_points).
