@@ -511,6 +511,42 @@ int nin_gls_jacobian_apply_host(nin_gls_jacobian *J, int32_t n, const double *dp
 int nin_gls_jacobian_apply_transpose_host(nin_gls_jacobian *J, int32_t n, const double *v, double *grad_perm, double *grad_diff_mag);
 int nin_gls_jacobian_fetch_host(nin_gls_jacobian *J, double *contrib, double *fold);
 
+/* ---- the same Jacobian in a reduced parametrisation of K: 8 M bytes per entry of esup instead of 80 -----------------------------
+ * A permeability that moves along M parameters per cell,  perm_e = sum_{m < M} theta_(e,m) B_(e,m)  with B_(e,m) a 3 x 3 tensor of 9
+ * doubles, row-major like perm: M = 1 (k_r(S(u)) K_abs, a log-multiplier), 3 (principal values in a fixed frame) or 6 (a symmetric
+ * tensor).  With C and fold as above the reduced Jacobian is
+ *   R[pos][m] = sum_{k < 9} C[pos][k] B_(e,m)[k] + C[pos][9] fold[e] (B_(e,m)[0] + B_(e,m)[4] + B_(e,m)[8]),   e = esup[pos]
+ * [nnz_esup][M] doubles, row-major in esup position; the diff_mag chain is always folded (an explicit d diff_mag has no meaning in
+ * theta).  The adjoint kernel contracts the ten values of a pair with the cell's basis where it has them: C is never stored and
+ * nothing of 80 bytes per entry is allocated.  Lifetime and ownership as nin_gls_jacobian.
+ *
+ * nin_gls_rjacobian_create: the buffer, 8 n_params bytes per entry of esup.  NIN_EINVAL unless n_params is 1, 3 or 6; NIN_ENOMEM,
+ *   NIN_ENODEVICE as nin_gls_jacobian_create.
+ * nin_gls_rjacobian_linearize: as nin_gls_jacobian_linearize, with the basis: dev_basis [n_elems][n_params][9] (basis_per_cell != 0),
+ *   [n_params][9] shared by every cell (basis_per_cell = 0), or NULL with n_params = 1 (else NIN_EINVAL): the resident perm itself, so
+ *   theta is a log-multiplier and dperm = perm dtheta.  The basis is read by this call only.  Every entry of R is written.  May be
+ *   called again, with another basis too.
+ * nin_gls_rjacobian_apply: dev_dnode[t][p] = sum over the row of p, sum_m R[pos][m] dev_dtheta[t][esup[pos]][m] for n directions
+ *   dev_dtheta [n][n_elems][n_params]; every entry of dev_dnode [n][n_points] is written.
+ * nin_gls_rjacobian_apply_transpose: dev_grad_theta[t][e][m] = sum over the nodes p of cell e, ascending node id, of dev_v[t][p]
+ *   R[pos][m].  Determinism, state, errors and the independence of later updates as for nin_gls_jacobian_apply / _apply_transpose.
+ * nin_gls_rjacobian_buffer: the device buffer, read-only, and n_params.  nin_gls_rjacobian_stamp as nin_gls_jacobian_stamp.
+ * nin_gls_rjacobian_*_host: the same with HOST pointers, synchronous; nin_gls_rjacobian_fetch_host copies R to the host. */
+typedef struct nin_gls_rjacobian nin_gls_rjacobian;
+int nin_gls_rjacobian_create(nin_grid *g, int32_t n_params, nin_gls_rjacobian **out);
+int nin_gls_rjacobian_linearize(nin_gls_rjacobian *J, const double *dev_u_cells, const double *dev_neumann_values, const double *dev_basis,
+                                int32_t basis_per_cell, void *stream);
+int nin_gls_rjacobian_apply(nin_gls_rjacobian *J, int32_t n, const double *dev_dtheta, double *dev_dnode, void *stream);
+int nin_gls_rjacobian_apply_transpose(nin_gls_rjacobian *J, int32_t n, const double *dev_v, double *dev_grad_theta, void *stream);
+int nin_gls_rjacobian_buffer(nin_gls_rjacobian *J, const double **dev_R, int32_t *n_params);
+int nin_gls_rjacobian_stamp(const nin_gls_rjacobian *J, int64_t stamp[3]);
+void nin_gls_rjacobian_destroy(nin_gls_rjacobian *J);
+int nin_gls_rjacobian_linearize_host(nin_gls_rjacobian *J, const double *u_cells, const double *neumann_values, const double *basis,
+                                     int32_t basis_per_cell);
+int nin_gls_rjacobian_apply_host(nin_gls_rjacobian *J, int32_t n, const double *dtheta, double *dnode);
+int nin_gls_rjacobian_apply_transpose_host(nin_gls_rjacobian *J, int32_t n, const double *v, double *grad_theta);
+int nin_gls_rjacobian_fetch_host(nin_gls_rjacobian *J, double *R);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].

@@ -37,6 +37,8 @@ UNITS = [
     ("kernels_gls_adjoint.hip", "hipcc", []),
     # the Jacobian that one adjoint launch leaves in a contribution buffer, applied: J . dK node-major, J^T . v cell-major
     ("kernels_gls_jacobian.hip", "hipcc", []),
+    # the same Jacobian in M = 1, 3 or 6 parameters per cell: R [nnz_esup][M] streamed, 8 M bytes per entry instead of 80
+    ("kernels_gls_jacobian_reduced.hip", "hipcc", []),
     ("kernels_csr.hip", "hipcc", []),
     # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
     ("csr_dirty.hip", "hipcc", []),
@@ -53,13 +55,14 @@ UNITS = [
     ("fields_scatter.hip", "hipcc", ["-ffp-contract=off"]),
     # Neumann flags from device memory: integer work on bytes, one float64 -> integer cast; nothing to contract
     ("flags_update.hip", "hipcc", []),
-    # the C ABI's host code by area (abi_internal.hpp is what the six share); only abi_plan.hip has a kernel, the locality keys
+    # the C ABI's host code by area (abi_internal.hpp is what they share); only abi_plan.hip has a kernel, the locality keys
     ("abi_grid.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_plan.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_update.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_csr.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_apply.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_jacobian_reduced.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),
 ]

@@ -217,13 +217,17 @@ static int ensure_adjoint_contrib(DeviceGrid &d) {
 // The adjoint kernel on the nodes of every bin (only >= 0: of that bin alone), the ten values of every (node, cell) pair into `contrib`:
 // the grid's buffer for the backward call, a nin_gls_jacobian's own for a linearisation
 int nin::launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
-                             hipStream_t stream) {
+                             hipStream_t stream, const AdjointReduce *reduce) {
     int rc = NIN_OK;
     for (int b = 0; b < kAdjBins && !rc; ++b) {
         const DeviceGrid::AdjBin &bin = d.adj_bin[b];
         if (only >= 0 && b != only) continue;
-        rc = launch_gls_adjoint(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, grad_csr, grad_nws, contrib, d.adj_scratch,
-                                d.adj_scratch_stride, d.adj_scratch_slots, stream);
+        if (reduce)   // a nin_gls_rjacobian's linearisation: `contrib` is its [nnz_esup][n_params] buffer
+            rc = launch_gls_adjoint_reduced(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, grad_csr, grad_nws, *reduce, contrib,
+                                            d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots, stream);
+        else
+            rc = launch_gls_adjoint(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, grad_csr, grad_nws, contrib, d.adj_scratch,
+                                    d.adj_scratch_stride, d.adj_scratch_slots, stream);
     }
     return rc;
 }

@@ -1,4 +1,4 @@
-// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian.hip;
+// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian / abi_jacobian_reduced.hip;
 // exchange.hip takes the error setter): the grid behind the handle, the text of nin_last_error(), the preconditions of the entry
 // points, device memory owned by the grid or by one call, and the functions of one unit that another calls.
 #pragma once
@@ -171,8 +171,23 @@ void release_adjoint_state(DeviceGrid &d);
 // (both synchronise `stream` when they build); the adjoint kernel on every bin (only >= 0: that bin alone) into `contrib`
 int ensure_transpose_index(DeviceGrid &d, hipStream_t stream);
 int ensure_adjoint_bins(DeviceGrid &d, hipStream_t stream);
+// (reduce: into a [nnz_esup][n_params] buffer through launch_gls_adjoint_reduced instead, for abi_jacobian_reduced.hip)
 int launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
-                        hipStream_t stream);
+                        hipStream_t stream, const AdjointReduce *reduce = nullptr);
+// abi_jacobian.hip, for abi_jacobian_reduced.hip too -- what the two kept Jacobians share.
+// jacobian_seed: a linearisation can go on g (on its device, GLS ready, the adjoint's bins made) and `seed` [nnz_esup] holds its
+// cotangent u[esup[pos]].  jacobian_host_fields: u [n_elems] and b [n_points] (or NULL) on the device for a *_linearize_host.
+// jacobian_apply_ready: the arguments of an apply call, the grid on its device, a linearisation to apply.
+int jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed);
+int jacobian_host_fields(nin_grid *g, const double *u_cells, const double *neumann_values, DevTmp<double> &du, DevTmp<double> &db);
+template <class Jac>
+int jacobian_apply_ready(const Jac *J, int32_t n, const void *in, const void *out, const char *linearize_name) {
+    if (n < 1) return fail(NIN_EINVAL, "n must be >= 1");
+    if (!J || !in || !out) return fail(NIN_EINVAL, "NULL argument");
+    if (int rc = on_device(J->g, kHintKernels)) return rc;
+    if (!J->linearized) return fail(NIN_ESTATE, "the Jacobian has not been linearised (call %s first)", linearize_name);
+    return NIN_OK;
+}
 
 }  // namespace nin
 #pragma GCC visibility pop

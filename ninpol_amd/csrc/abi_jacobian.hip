@@ -16,16 +16,37 @@ struct nin_gls_jacobian {
 
 namespace {
 
-// what the two apply calls share: the arguments, the grid on its device, a linearisation to apply
 int apply_ready(const nin_gls_jacobian *J, int32_t n, const void *in, const void *out) {
-    if (n < 1) return fail(NIN_EINVAL, "n must be >= 1");
-    if (!J || !in || !out) return fail(NIN_EINVAL, "NULL argument");
-    if (int rc = on_device(J->g, kHintKernels)) return rc;
-    if (!J->linearized) return fail(NIN_ESTATE, "the Jacobian has not been linearised (call nin_gls_jacobian_linearize first)");
-    return NIN_OK;
+    return jacobian_apply_ready(J, n, in, out, "nin_gls_jacobian_linearize");
 }
 
 }  // namespace
+
+// ---- what a linearisation of either kept Jacobian begins with (abi_jacobian_reduced.hip calls these too) -----------------------------
+int nin::jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed) {
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
+    HIP_TRY(hipSetDevice(d.device));
+    if (int rc = ensure_adjoint_bins(d, stream)) return rc;
+    // the cotangent of F = W u + neumann_ws b: grad_csr[pos] = u[esup[pos]], grad_neumann_ws = b
+    HIP_TRY(hipMalloc((void **)&seed, (size_t)std::max<int64_t>(d.nnz_e, 1) * sizeof(double)));
+    if (int rc = launch_jac_seed(d.v, d.nnz_e, dev_u_cells, seed, stream)) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin::jacobian_host_fields(nin_grid *g, const double *u_cells, const double *neumann_values, DevTmp<double> &du, DevTmp<double> &db) {
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    HIP_TRY(hipSetDevice(g->d.device));
+    const size_t pb = std::max<size_t>((size_t)g->h.n_points, 1) * 8, eb = std::max<size_t>((size_t)g->h.n_elems, 1) * 8;
+    HIP_TRY(hipMalloc((void **)&du, eb));
+    HIP_TRY(hipMemcpy(du, u_cells, (size_t)g->h.n_elems * 8, hipMemcpyHostToDevice));
+    if (neumann_values) {
+        HIP_TRY(hipMalloc((void **)&db, pb));
+        HIP_TRY(hipMemcpy(db, neumann_values, (size_t)g->h.n_points * 8, hipMemcpyHostToDevice));
+    }
+    return NIN_OK;
+}
 
 int nin_gls_jacobian_create(nin_grid *g, nin_gls_jacobian **out) {
     if (!g || !out) return fail(NIN_EINVAL, "NULL argument");
@@ -58,20 +79,13 @@ void nin_gls_jacobian_destroy(nin_gls_jacobian *J) {
 
 int nin_gls_jacobian_linearize(nin_gls_jacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream_) {
     if (!J || !dev_u_cells) return fail(NIN_EINVAL, "NULL argument");
-    nin_grid *g = J->g;
-    DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
-    HIP_TRY(hipSetDevice(d.device));
+    DeviceGrid &d = J->g->d;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = ensure_adjoint_bins(d, stream);
+    DevTmp<double> seed;
+    int rc = jacobian_seed(J->g, dev_u_cells, stream, seed);
     if (rc) return rc;
     J->linearized = false;
-    // the cotangent of F = W u + neumann_ws b: grad_csr[pos] = u[esup[pos]], grad_neumann_ws = b
-    DevTmp<double> seed;
-    HIP_TRY(hipMalloc((void **)&seed, (size_t)std::max<int64_t>(d.nnz_e, 1) * sizeof(double)));
-    rc = launch_jac_seed(d.v, d.nnz_e, dev_u_cells, seed, stream);
-    if (!rc) rc = launch_adjoint_bins(d, 1, -1, seed, dev_neumann_values, J->contrib, stream);   // always every bin
+    rc = launch_adjoint_bins(d, 1, -1, seed, dev_neumann_values, J->contrib, stream);   // always every bin
     if (!rc) rc = launch_jac_fold(d.v, J->fold, stream);
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     J->stamp[0] = d.field_updates;
@@ -121,17 +135,8 @@ int nin_gls_jacobian_stamp(const nin_gls_jacobian *J, int64_t stamp[3]) {
 // ---- host pointers: what Interpolator.permeability_jacobian calls (synchronous) ------------------------------------------------------
 int nin_gls_jacobian_linearize_host(nin_gls_jacobian *J, const double *u_cells, const double *neumann_values) {
     if (!J || !u_cells) return fail(NIN_EINVAL, "NULL argument");
-    nin_grid *g = J->g;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    HIP_TRY(hipSetDevice(g->d.device));
-    const size_t pb = std::max<size_t>((size_t)g->h.n_points, 1) * 8, eb = std::max<size_t>((size_t)g->h.n_elems, 1) * 8;
     DevTmp<double> du, db;
-    HIP_TRY(hipMalloc((void **)&du, eb));
-    HIP_TRY(hipMemcpy(du, u_cells, (size_t)g->h.n_elems * 8, hipMemcpyHostToDevice));
-    if (neumann_values) {
-        HIP_TRY(hipMalloc((void **)&db, pb));
-        HIP_TRY(hipMemcpy(db, neumann_values, (size_t)g->h.n_points * 8, hipMemcpyHostToDevice));
-    }
+    if (int rc = jacobian_host_fields(J->g, u_cells, neumann_values, du, db)) return rc;
     if (int rc = nin_gls_jacobian_linearize(J, du, neumann_values ? db.p : nullptr, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NIN_OK;

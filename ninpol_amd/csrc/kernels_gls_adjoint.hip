@@ -25,6 +25,8 @@
 // (node, cell) -- Kbar[9] and etabar -- are summed in that fixed order and written to contrib[esup position][10].  nin_adjoint_gather_kernel
 // then sums, for every cell, the slots of its nodes in ascending node id through the cell-major index of the transpose (DeviceGrid::tr_*).
 // No atomics anywhere: two calls agree bit for bit.
+// RED = true (with TAN = false only): the lane contracts its ten values with the cell's basis B [red_m][9] and writes the
+// red_m values of the reduced Jacobian instead, contrib [esup position][red_m] -- the 80-byte record is never stored.
 //
 // The tangent (TAN = true): the same kernel up to y, r, rho and the verdict, then for every direction dK (9 per cell; d
 // diff_mag per cell given, or folded from the resident perm) the directional derivative of the stored entries.  dA is non-zero where K
@@ -48,14 +50,26 @@ namespace {
 
 using namespace waveops;
 
-// What one launch reads and writes beside the grid: the adjoint's three pointers, or the tangent's
+// What one launch reads and writes beside the grid: the adjoint's three pointers, or the tangent's.  The reduced adjoint (RED, never
+// with TAN) keeps its three words in the tangent's slots, so that the struct -- and with it the kernel arguments of the adjoint and
+// tangent instantiations, and their code -- is what it was before RED existed
 struct AdjointIo {
     const double *grad_csr, *grad_nws;   // adjoint: dL/d stored weights [nnz_esup], dL/d neumann_ws [P] or null
-    double *contrib;                     //          [nnz_esup][10]
-    int32_t n_tan;                       // tangent: directions
-    const double *tan_perm, *tan_dm;     //          dK [n_tan][E][9]; d diff_mag [n_tan][E] or null (folded from g.perm)
+    double *contrib;                     //          [nnz_esup][10]; RED: the reduced Jacobian R [nnz_esup][red_m]
+    union {
+        int32_t n_tan;                   // tangent: directions
+        int32_t red_m;                   // RED: parameters per cell
+    };
+    union {
+        const double *tan_perm;          // tangent: dK [n_tan][E][9]
+        const double *red_basis;         // RED: B [E][red_m][9] (red_stride = 9 red_m), [red_m][9] (red_stride = 0: shared) or null: g.perm
+    };
+    const double *tan_dm;                // tangent: d diff_mag [n_tan][E] or null (folded from g.perm)
     double *tan_csr, *tan_nws;           //          d stored weights [n_tan][nnz]; d neumann_ws [n_tan][P] or null
-    long long nnz;
+    union {
+        long long nnz;
+        long long red_stride;            // RED: doubles from one cell's basis to the next
+    };
 };
 
 // d diff_mag of cell e along the direction: given, or (1 - 3 / tr K)^2 differentiated (nin_adjoint_gather_kernel's factor)
@@ -110,7 +124,7 @@ __device__ __forceinline__ void back_substitute(const double *A, int ld, int nc,
     }
 }
 
-template <int TW, bool LDS, bool TAN>
+template <int TW, bool LDS, bool TAN, bool RED>
 __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, const int32_t *__restrict__ nodes, int32_t count, int add_neumann,
                                                                  AdjointIo io, double *scratch, long long scratch_stride) {
     extern __shared__ double smem[];
@@ -144,6 +158,8 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
                     for (int i = tid; i < ne; i += nthr) io.tan_csr[(size_t)t * io.nnz + eb + i] = 0.0;
                     if (io.tan_nws && tid == 0) io.tan_nws[(size_t)t * g.n_points + p] = 0.0;
                 }
+            } else if constexpr (RED) {
+                for (int i = tid; i < io.red_m * ne; i += nthr) contrib[(size_t)io.red_m * (size_t)eb + i] = 0.0;
             } else {
                 for (int i = tid; i < 10 * ne; i += nthr) contrib[10 * (size_t)eb + i] = 0.0;
             }
@@ -451,10 +467,27 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
                 }
                 etab += dot * (-log(un) * tj);   // d tau / d eta = -ln|T2| tau
             }
-            double *o = contrib + 10 * (size_t)(eb + i);
+            if constexpr (RED) {
+                // the chain rule folded in where the ten values are: R[pos][m] = sum_k kb[k] B_m[k] + etab fold tr B_m,
+                // one chain of fmas from 0.0, k ascending, the fold term last; fold is nin_jac_fold_kernel's expression of g.perm
+                const double *K = g.perm + 9 * (size_t)cells[i];
+                const double tr = (K[0] + K[4]) + K[8];
+                const double fold = (2.0 * (1.0 - 3.0 / tr) * 3.0 / (tr * tr));
+                const double *B = io.red_basis ? io.red_basis + (size_t)io.red_stride * (size_t)cells[i] : K;
+                double *o = contrib + (size_t)io.red_m * (size_t)(eb + i);
+                for (int m = 0; m < io.red_m; ++m) {
+                    const double *bm = B + 9 * m;
+                    double r = 0.0;
 #pragma unroll
-            for (int c = 0; c < 9; ++c) o[c] = kb[c];
-            o[9] = etab;
+                    for (int c = 0; c < 9; ++c) r = fma(kb[c], bm[c], r);
+                    o[m] = fma(etab, fold * ((bm[0] + bm[4]) + bm[8]), r);
+                }
+            } else {
+                double *o = contrib + 10 * (size_t)(eb + i);
+#pragma unroll
+                for (int c = 0; c < 9; ++c) o[c] = kb[c];
+                o[9] = etab;
+            }
         }
         __syncthreads();   // (the slot is the next node's)
     }
@@ -495,15 +528,15 @@ __global__ __launch_bounds__(256) void nin_adjoint_gather_kernel(int32_t n_elems
     for (int k = 0; k < 9; ++k) grad_perm[9 * (size_t)e + k] = acc[k];
 }
 
-template <int TW, bool LDS, bool TAN>
+template <int TW, bool LDS, bool TAN, bool RED>
 int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io, double *scratch,
                int64_t stride, int32_t slots, hipStream_t stream) {
-    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN>;
+    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN, RED>;
     int64_t blocks;
     size_t lds = 0;
     if (LDS) {
         lds = (size_t)bytes;
-        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN>>(lds)) return -3;
+        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED>>(lds)) return -3;
         int64_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : (int64_t)lds);
         if (per_cu > 32 / TW) per_cu = 32 / TW;
         if (per_cu < 1) per_cu = 1;
@@ -517,17 +550,17 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
 }
 
 // one bin's nodes through the class of that bin: 1, 2, 4 wavefronts in LDS, 8 over a global-memory slot
-template <bool TAN>
+template <bool TAN, bool RED>
 int launch_bin_of(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io,
                   double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
     if (count <= 0) return 0;
     switch (bin) {
-        case 0: return launch_bin<1, true, TAN>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 1: return launch_bin<2, true, TAN>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 2: return launch_bin<4, true, TAN>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 0: return launch_bin<1, true, TAN, RED>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 1: return launch_bin<2, true, TAN, RED>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 2: return launch_bin<4, true, TAN, RED>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
         case 3:
             if (!scratch || scratch_slots < 1 || scratch_stride * 8 < bytes) return -1;
-            return launch_bin<8, false, TAN>(g, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+            return launch_bin<8, false, TAN, RED>(g, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
     }
     return -1;
 }
@@ -545,7 +578,16 @@ int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t
                        hipStream_t stream) {
     AdjointIo io{};
     io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = contrib;
-    return launch_bin_of<false>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+    return launch_bin_of<false, false>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+}
+
+int launch_gls_adjoint_reduced(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
+                               const double *grad_csr, const double *grad_nws, const AdjointReduce &red, double *reduced, double *scratch,
+                               int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
+    AdjointIo io{};
+    io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = reduced;
+    io.red_basis = red.basis; io.red_stride = (long long)red.stride; io.red_m = red.n_params;
+    return launch_bin_of<false, true>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
 }
 
 int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, int32_t n_tangents,
@@ -554,7 +596,7 @@ int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t
     AdjointIo io{};
     io.n_tan = n_tangents; io.tan_perm = tangent_perm; io.tan_dm = tangent_diff_mag; io.tan_csr = tangent_csr; io.tan_nws = tangent_nws;
     io.nnz = (long long)nnz;
-    return launch_bin_of<true>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+    return launch_bin_of<true, false>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
 }
 
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,

@@ -128,6 +128,18 @@ int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t
                        hipStream_t stream);
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,
                           double *grad_diff_mag, hipStream_t stream);
+// launch_gls_adjoint_reduced: the same launch with the chain rule of perm_e = sum_m theta_(e,m) B_(e,m) folded in where the
+//   ten values are: every (node, cell) pair writes its n_params values to reduced [nnz_esup][n_params], the diff_mag chain folded from
+//   the resident g.perm; the 80-byte record is not stored.  basis: [E][n_params][9] with stride = 9 n_params, [n_params][9] with
+//   stride = 0 (one set for every cell), or null (n_params = 1): the resident g.perm itself
+struct AdjointReduce {
+    int32_t n_params;
+    const double *basis;
+    int64_t stride;
+};
+int launch_gls_adjoint_reduced(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
+                               const double *grad_csr, const double *grad_nws, const AdjointReduce &red, double *reduced, double *scratch,
+                               int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
 // launch_gls_tangent: the same kernel's tangent mode on the nodes of one bin -- n_tangents directions tangent_perm [n_tangents][E][9]
 //   (tangent_diff_mag [n_tangents][E], or null: folded from the resident g.perm) -> the directional derivative of the stored weights,
 //   tangent_csr [n_tangents][nnz] in esup position, and of neumann_ws, tangent_nws [n_tangents][P] or null; every row of every listed
@@ -149,6 +161,14 @@ int launch_jac_apply(const GridView &g, const double *contrib, const double *fol
 int launch_jac_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
                                const double *contrib, const double *fold, int32_t n, const double *v, double *grad_perm, double *grad_dm,
                                hipStream_t stream);
+
+// the reduced GLS Jacobian applied (kernels_gls_jacobian_reduced.hip), all DEVICE pointers; R [nnz_esup][M] as
+// launch_gls_adjoint_reduced left it, M in {1, 3, 6} (anything else: -1).
+// launch_jacr_apply: out [n][P] = J_theta . dtheta [n][E][M]; every entry written.
+// launch_jacr_apply_transpose: grad_theta [n][E][M] = J_theta^T . v [n][P], per cell in ascending node id through the transpose index
+int launch_jacr_apply(const GridView &g, int32_t M, const double *R, int32_t n, const double *dtheta, double *out, hipStream_t stream);
+int launch_jacr_apply_transpose(const GridView &g, int32_t M, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
+                                const double *R, int32_t n, const double *v, double *grad_theta, hipStream_t stream);
 
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream);

@@ -914,7 +914,7 @@ class Interpolator:
         _lib.check(_lib.load().nin_gls_permeability_tangent_host(g._h, _ptr(d), _ptr(u), k, _ptr(out), _ptr(nws)))
         return out, nws
 
-    def permeability_jacobian(self, variable, cell_values=None, neumann_values=None):
+    def permeability_jacobian(self, variable, cell_values=None, neumann_values=None, basis=None):
         """The Jacobian of what `apply(variable, "gls")` returns, `W u` (+ `neumann_ws * neumann_values` when those are given), with
         respect to the permeability table, linearised ONCE at the resident table and kept on the device: a scipy LinearOperator of
         shape (n_points, 9 n_elems), float64 (PermeabilityJacobian: `matvec` = J . dK for a flattened (n_elems, 3, 3) direction,
@@ -923,10 +923,18 @@ class Interpolator:
         through diff_mag = (1 - 3 / tr K)^2 is folded in.  The sibling of permeability_gradient() / permeability_tangent() for a Krylov
         solver: those factorise every node at every call, this does so once (the cost of one permeability_gradient) and every product
         afterwards streams the kept buffer (80 bytes per entry of esup, on the device).  Later update_*() calls do not change the
-        operator; build a new one at the new point.  Host-synchronous, numpy in and out."""
+        operator; build a new one at the new point.  Host-synchronous, numpy in and out.
+
+        `basis`: the permeability moves along M = 1, 3 or 6 parameters per cell, perm_e = sum_m theta_(e,m) B_(e,m), and
+        the result is the Jacobian in theta instead: a ReducedPermeabilityJacobian of shape (n_points, M n_elems), column M e + m,
+        kept in 8 M bytes per entry of esup (the 80-byte buffer is never made).  "scale": B = the resident permeability itself (M = 1,
+        theta a log-multiplier); "diagonal": e_d e_d^T (M = 3); "symmetric": xx, yy, zz, xy, xz, yz with the off-diagonals e_i e_j^T +
+        e_j e_i^T (M = 6); or a float64 ndarray (n_elems, M, 9), (n_elems, M, 3, 3) per cell, (M, 9) or (M, 3, 3) shared."""
         self._check_call(variable=variable)
         self._perm_rows()   # (ValueError without a permeability)
         g = self.grid
+        if basis is not None:
+            M, B, per_cell = reduced_basis(basis, g.n_elems)
         if cell_values is None:
             u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
         else:
@@ -942,6 +950,10 @@ class Interpolator:
         if g.device < 0:
             g.to_device(self.device)
         _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        if basis is not None:
+            rjac = GlsReducedJacobian(g, M)
+            _lib.check(_lib.load().nin_gls_rjacobian_linearize_host(rjac._handle(), _ptr(u), _ptr(b), _ptr(B), int(per_cell)))
+            return ReducedPermeabilityJacobian(rjac)
         jac = GlsJacobian(g)
         _lib.check(_lib.load().nin_gls_jacobian_linearize_host(jac._handle(), _ptr(u), _ptr(b)))
         return PermeabilityJacobian(jac)
@@ -1127,6 +1139,21 @@ class DevicePlan:
         J.relinearize(u_ptr, neumann_values_ptr, stream)
         return J
 
+    def linearize_reduced(self, u_ptr, n_params=1, basis_ptr=0, basis_per_cell=True, neumann_values_ptr=0, stream=0):
+        """linearize() for a permeability that moves along n_params = 1, 3 or 6 parameters per cell, perm_e = sum_m theta_(e,m)
+        B_(e,m): a GlsReducedJacobian, 8 n_params bytes per entry of esup, linearised at what is resident now.
+        basis_ptr: device pointer to B [n_elems][n_params][9] (basis_per_cell) or [n_params][9] shared by every cell, read by this call
+        only; 0 with n_params = 1: the resident permeability itself (theta a log-multiplier).  The adjoint kernel contracts with the
+        basis where it has the ten values of a (node, cell) pair: the 80-byte buffer of linearize() is never written or allocated."""
+        if self.method != "gls":
+            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: linearize_reduced is GLS only")
+        if not u_ptr:
+            raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
+        _check_n_params(n_params, basis_ptr)
+        J = GlsReducedJacobian(self.grid, n_params, plan=self)
+        J.relinearize(u_ptr, basis_ptr, basis_per_cell, neumann_values_ptr, stream)
+        return J
+
 
 class GlsJacobian:
     """The sparse Jacobian of `F(K) = W(K) u + neumann_ws(K) * b` with respect to the permeability at ONE linearisation point, resident
@@ -1219,6 +1246,177 @@ class GlsJacobian:
             self.release()
         except Exception:       # interpreter shutdown
             pass
+
+
+REDUCED_N_PARAMS = (1, 3, 6)
+
+
+def _check_n_params(n_params, basis_ptr=1):
+    if isinstance(n_params, bool) or not isinstance(n_params, (int, np.integer)) or int(n_params) not in REDUCED_N_PARAMS:
+        raise ValueError(f"n_params must be one of {REDUCED_N_PARAMS}, not {n_params!r}")
+    if not basis_ptr and int(n_params) != 1:
+        raise ValueError(f"basis_ptr = 0 (the resident permeability as the basis) needs n_params = 1, not {n_params}")
+
+
+def reduced_basis(basis, n_elems):
+    """Interpolator.permeability_jacobian's `basis` as (M, B, per_cell): B a C-contiguous float64 array (n_elems, M, 9) (per_cell) or
+    (M, 9) (shared by every cell), or None for "scale" (M = 1: the resident permeability itself)."""
+    if isinstance(basis, str):
+        if basis == "scale":
+            return 1, None, False
+        if basis == "diagonal":
+            B = np.zeros((3, 3, 3), dtype=DTYPE_F)
+            for d in range(3):
+                B[d, d, d] = 1.0
+            return 3, B.reshape(3, 9), False
+        if basis == "symmetric":
+            B = np.zeros((6, 3, 3), dtype=DTYPE_F)
+            for m, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+                B[m, i, j] = B[m, j, i] = 1.0
+            return 6, B.reshape(6, 9), False
+        raise ValueError(f"basis must be 'scale', 'diagonal', 'symmetric' or an ndarray, not '{basis}'")
+    if not isinstance(basis, np.ndarray):
+        raise ValueError(f"basis must be 'scale', 'diagonal', 'symmetric' or a float64 ndarray, not {type(basis).__name__}")
+    if basis.dtype != DTYPE_F:
+        raise ValueError(f"basis must be float64, not {basis.dtype} (no silent cast)")
+    E = int(n_elems)
+    shape = tuple(basis.shape)
+    per_cell = len(shape) >= 3 and shape[0] == E and shape[2:] in ((9,), (3, 3))     # (the last axis tells (E, M, 9) from (M, 3, 3))
+    shared = len(shape) >= 2 and shape[1:] in ((9,), (3, 3))
+    M = shape[1] if per_cell else shape[0] if shared else None
+    if M not in REDUCED_N_PARAMS:
+        raise ValueError(f"basis must have shape ({E}, M, 9), ({E}, M, 3, 3), (M, 9) or (M, 3, 3) with M in {REDUCED_N_PARAMS}, not {shape}")
+    return M, np.ascontiguousarray(basis).reshape((E, M, 9) if per_cell else (M, 9)), per_cell
+
+
+class GlsReducedJacobian:
+    """The Jacobian of `F = W(K) u + neumann_ws(K) * b` in a reduced parametrisation of the permeability, perm_e = sum_m theta_(e,m)
+    B_(e,m) with `n_params` = M = 1, 3 or 6 per cell, at ONE linearisation point, resident on the device (nin_gls_rjacobian, DESIGN.md
+    4.14): `buffer_ptr` [nnz_esup][M] holds dF_p / d theta_(e,m) per (node, cell) pair in esup position, the diff_mag chain folded --
+    `nbytes` = 8 M nnz_esup, where a GlsJacobian keeps 80 nnz_esup.  `launch_jvp` is J_theta . dtheta, `launch_vjp` J_theta^T . v, one
+    streaming pass per four directions each, asynchronous, bitwise reproducible.  Later updates of the permeability, the points or the
+    flags do not change the answers (`stamp`, `is_current()`); `relinearize` moves it, to another basis too.  Made by
+    DevicePlan.linearize_reduced(); its device buffer is its own."""
+
+    def __init__(self, grid, n_params=1, plan=None):
+        _check_n_params(n_params)
+        self.grid, self.plan, self.n_params = grid, plan, int(n_params)
+        self._h = None
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().nin_gls_rjacobian_create(grid._h, self.n_params, ctypes.byref(h)))
+        self._h = h
+        self.nbytes = 8 * self.n_params * int(grid.nnz_esup)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("this GlsReducedJacobian was released")
+        return self._h
+
+    def relinearize(self, u_ptr, basis_ptr=0, basis_per_cell=True, neumann_values_ptr=0, stream=0):
+        """Linearise again, at what is resident now, for u [n_elems], the basis (see DevicePlan.linearize_reduced) and b [n_points]
+        (0: none), device pointers: what a fresh linearize_reduced would hold, bit for bit, in the buffer this object already owns."""
+        _check_n_params(self.n_params, basis_ptr)
+        if self.plan is not None:
+            self.plan.ensure_current()
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_rjacobian_linearize(self._handle(), vp(u_ptr), vp(neumann_values_ptr), vp(basis_ptr),
+                                                           int(bool(basis_per_cell)), ctypes.c_void_p(stream)))
+
+    def launch_jvp(self, dtheta_ptr, out_ptr, n=1, stream=0):
+        """J_theta . dtheta for n directions (nin_gls_rjacobian_apply): dtheta [n][n_elems][M] -> out [n][n_points], every entry
+        written.  Asynchronous on `stream`."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_rjacobian_apply(self._handle(), int(n), vp(dtheta_ptr), vp(out_ptr), ctypes.c_void_p(stream)))
+
+    def launch_vjp(self, v_ptr, grad_theta_ptr, n=1, stream=0):
+        """J_theta^T . v for n node fields (nin_gls_rjacobian_apply_transpose): v [n][n_points] -> grad_theta [n][n_elems][M].
+        Asynchronous on `stream` (the first call on a grid without the transpose index builds it and synchronises)."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_rjacobian_apply_transpose(self._handle(), int(n), vp(v_ptr), vp(grad_theta_ptr), ctypes.c_void_p(stream)))
+
+    @property
+    def buffer_ptr(self):
+        r, m = ctypes.c_void_p(), ctypes.c_int(0)
+        _lib.check(_lib.load().nin_gls_rjacobian_buffer(self._handle(), ctypes.byref(r), ctypes.byref(m)))
+        return int(r.value or 0)
+
+    @property
+    def stamp(self):
+        """the grid's (field_updates, geometry_updates, flag_updates) at the last linearisation"""
+        s = np.zeros(3, dtype=np.int64)
+        _lib.check(_lib.load().nin_gls_rjacobian_stamp(self._handle(), _ptr(s)))
+        return tuple(int(x) for x in s)
+
+    def is_current(self):
+        """Is the grid's resident permeability, geometry and flag set still the one this object was linearised at?"""
+        g = self.grid
+        return self.stamp == (g.field_updates, g.geometry_updates, g.flag_updates)
+
+    def fetch(self):
+        """R (nnz_esup, M) on the host (waits for the device)"""
+        R = np.empty((int(self.grid.nnz_esup), self.n_params), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_rjacobian_fetch_host(self._handle(), _ptr(R)))
+        return R
+
+    def release(self):
+        """Give the device buffer back (waits for the device); the object is unusable afterwards."""
+        if self._h is not None:
+            _lib.load().nin_gls_rjacobian_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+class ReducedPermeabilityJacobian(spla.LinearOperator):
+    """Interpolator.permeability_jacobian(basis=...)'s result: the (n_points, M n_elems) Jacobian of `apply(variable, "gls")`'s node
+    values in the parameters theta of perm_e = sum_m theta_(e,m) B_(e,m) (column M e + m), as a scipy LinearOperator over a
+    GlsReducedJacobian: numpy in and out, host-synchronous, one launch per matvec / rmatvec and one per batched matmat / rmatmat."""
+
+    def __init__(self, jac):
+        g = jac.grid
+        self.jacobian = jac
+        self._P, self._E, self._M = int(g.n_points), int(g.n_elems), int(jac.n_params)
+        super().__init__(dtype=np.dtype(DTYPE_F), shape=(self._P, self._M * self._E))
+
+    def _jvp(self, d):        # d (k, M E) -> (k, P)
+        d = np.ascontiguousarray(d, dtype=DTYPE_F)
+        out = np.empty((len(d), self._P), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_rjacobian_apply_host(self.jacobian._handle(), len(d), _ptr(d), _ptr(out)))
+        return out
+
+    def _vjp(self, v):        # v (k, P) -> (k, M E)
+        v = np.ascontiguousarray(v, dtype=DTYPE_F)
+        out = np.empty((len(v), self._M * self._E), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_rjacobian_apply_transpose_host(self.jacobian._handle(), len(v), _ptr(v), _ptr(out)))
+        return out
+
+    def _matvec(self, x):
+        return self._jvp(np.asarray(x).reshape(1, -1))[0]
+
+    def _rmatvec(self, x):
+        return self._vjp(np.asarray(x).reshape(1, -1))[0]
+
+    def _matmat(self, X):
+        return self._jvp(np.asarray(X).T).T
+
+    def _rmatmat(self, X):
+        return self._vjp(np.asarray(X).T).T
+
+    def to_scipy(self):
+        """The explicit csr_matrix (n_points, M n_elems) from the fetched buffer: row p, column M e + m."""
+        g = self.jacobian.grid
+        R = self.jacobian.fetch()
+        esup = np.asarray(g.esup).astype(np.int64)
+        cols = self._M * esup[:, None] + np.arange(self._M)
+        indptr = self._M * np.asarray(g.esup_ptr).astype(np.int64)
+        return sp.csr_matrix((R.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)
+
+    def release(self):
+        self.jacobian.release()
 
 
 class PermeabilityJacobian(spla.LinearOperator):

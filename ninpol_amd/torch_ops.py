@@ -153,8 +153,9 @@ class Linearization:
     and the K / scale it was taken at.  jvp() and vjp() are plain tensor methods on torch's current stream -- no autograd graph -- and
     cost one streaming pass each instead of a factorisation of every node: what a Krylov solver calls once per iteration."""
 
-    def __init__(self, op, u, weights, neumann_ws, jacobian, K, scale):
+    def __init__(self, op, u, weights, neumann_ws, jacobian, K, scale, wrt="K"):
         self.op, self.u, self.weights, self.neumann_ws, self.jacobian, self.K, self.scale = op, u, weights, neumann_ws, jacobian, K, scale
+        self.wrt = wrt       # "scale": `jacobian` is a GlsReducedJacobian in the one parameter per cell, basis K (DESIGN.md 4.14)
         self.value = op._spmv(weights, u)
 
     def _batch(self, t, name, shapes):
@@ -170,9 +171,12 @@ class Linearization:
 
     def jvp(self, du=None, dK=None, dscale=None):
         """W du + J (scale * dK + dscale * K): the change of `value` along du (n_elems,), dK shaped like K and dscale (n_elems,), each
-        optional, all with the same optional leading batch dimension.  Returns (n_points,) or (k, n_points)."""
+        optional, all with the same optional leading batch dimension.  Returns (n_points,) or (k, n_points).  A linearisation taken
+        with wrt="scale" gives W du + R dscale from its (nnz_esup,) Jacobian, with no (n_elems, 9) temporary, and takes no dK."""
         op = self.op
         E, P = op.n_elems, op.n_points
+        if self.wrt == "scale" and dK is not None:
+            raise ValueError('a linearisation taken with wrt="scale" holds no derivative in K: dK must be None (take one with wrt="K")')
         if dscale is not None and (self.scale is None or self.K is None):
             raise ValueError("dscale needs a linearisation taken with K and scale")
         given = [(t, name, shapes) for t, name, shapes in ((du, "du", ((E,),)), (dK, "dK", ((E, 3, 3), (E, 9))), (dscale, "dscale", ((E,),)))
@@ -186,6 +190,15 @@ class Linearization:
         out = None
         if du is not None:
             out = op._spmv(self.weights, parts["du"][0].contiguous())
+        if self.wrt == "scale":
+            if dscale is not None and self.jacobian is not None:
+                ds = parts["dscale"][0].contiguous()
+                jv = torch.empty((k, P), dtype=torch.float64, device=op.device)
+                self.jacobian.launch_jvp(ds.data_ptr(), jv.data_ptr(), k, op._stream())
+                out = jv if out is None else out + jv
+            if out is None:
+                out = torch.zeros((k, P), dtype=torch.float64, device=op.device)
+            return out if batched else out[0]
         tperm = None
         if dK is not None:
             tperm = parts["dK"][0].reshape(k, E, 9)
@@ -212,6 +225,13 @@ class Linearization:
         g = g.contiguous()
         k = int(g.shape[0])
         gu = op._spmv_transpose(self.weights, g)
+        if self.wrt == "scale":      # (W^T g, None, R^T g): the gradient in scale straight from the reduced Jacobian
+            if self.jacobian is not None:
+                gscale = torch.empty((k, E), dtype=torch.float64, device=op.device)
+                self.jacobian.launch_vjp(g.data_ptr(), gscale.data_ptr(), k, op._stream())
+            else:
+                gscale = torch.zeros((k, E), dtype=torch.float64, device=op.device)
+            return (gu, None, gscale) if batched else (gu[0], None, gscale[0])
         if self.jacobian is not None:
             gperm = torch.empty((k, E, 9), dtype=torch.float64, device=op.device)
             self.jacobian.launch_vjp(g.data_ptr(), gperm.data_ptr(), k, 0, op._stream())
@@ -343,14 +363,23 @@ class CellToNode(torch.nn.Module):
             return _ConstantWeightsFn.apply(K, scale, self.weights), self.neumann_ws
         return _GlsWeightsFn.apply(K, scale, self)
 
-    def linearize(self, u, K=None, scale=None, neumann_values=None):
+    def linearize(self, u, K=None, scale=None, neumann_values=None, wrt="K"):
         """Linearise `forward(u, K, scale)` once, for many jvp / vjp products at that point: u float64 (n_elems,) on the plan's device
         (one field).  With K (and scale) it first does what weights_of does -- scale * K becomes the grid's resident permeability --
         and computes fresh weights; without, the weights of what is resident now.  Returns a Linearization: `value` = W u, `jvp(du, dK,
         dscale)`, `vjp(g)`, the weights and -- GLS -- the GlsJacobian of W u + neumann_ws * neumann_values ((n_points,) or None) in the
         permeability, resident on the device (80 bytes per entry of esup; the cost of one backward pass, once).  IDW / LS do not
         depend on K: no buffer is allocated and J counts as 0.  No autograd Function is involved: the methods are plain tensor calls
-        on torch's current stream."""
+        on torch's current stream.
+
+        wrt="scale" (needs K and scale): the permeability scale * K moves along the one parameter per cell only, d perm / d scale = K,
+        and the Jacobian kept is the reduced one with the per-cell basis K (a GlsReducedJacobian, 8 bytes per entry of esup instead of
+        80).  `jvp(du, dscale=...)` is then W du + R dscale with no (n_elems, 9) temporary and takes no dK; `vjp(g)` returns (W^T g,
+        None, R^T g)."""
+        if wrt not in ("K", "scale"):
+            raise ValueError(f'wrt must be "K" or "scale", not {wrt!r}')
+        if wrt == "scale" and (K is None or scale is None):
+            raise ValueError('wrt="scale" needs K and scale: the derivative is taken along scale at the permeability scale * K')
         if not isinstance(u, torch.Tensor):
             raise TypeError(f"u must be a torch.Tensor, not {type(u).__name__}")
         if u.dtype != torch.float64:
@@ -378,8 +407,12 @@ class CellToNode(torch.nn.Module):
         jac = None
         if self.plan.method == "gls":
             b = None if neumann_values is None else neumann_values.detach().contiguous()
-            jac = self.plan.linearize(u.data_ptr(), 0 if b is None else b.data_ptr(), self._stream())
-        return Linearization(self, u, weights, neumann_ws, jac, K, scale)
+            if wrt == "scale":
+                basis = K.reshape(self.n_elems, 9).contiguous()       # read by the launch below only (stream-ordered)
+                jac = self.plan.linearize_reduced(u.data_ptr(), 1, basis.data_ptr(), True, 0 if b is None else b.data_ptr(), self._stream())
+            else:
+                jac = self.plan.linearize(u.data_ptr(), 0 if b is None else b.data_ptr(), self._stream())
+        return Linearization(self, u, weights, neumann_ws, jac, K, scale, wrt)
 
     def forward(self, u, K=None, scale=None):
         """u: float64 (n_elems,) or (k, n_elems) on the plan's device -> node values (n_points,) or (k, n_points).

@@ -1,5 +1,5 @@
 """The resident GLS Jacobian against the per-call tangent and backward, same mesh, same session.
-python tools/time_jacobian.py [hex216 del54 ...]
+python tools/time_jacobian.py [--reduced] [hex216 del54 ...]
 
 Per mesh, HIP events, WARMUP calls first, median of REPS each:
   linearize (DevicePlan.linearize's relinearize: one adjoint launch into the object's buffer),
@@ -7,7 +7,13 @@ Per mesh, HIP events, WARMUP calls first, median of REPS each:
   the tangent launch with 1 direction and the backward call (what a Krylov iteration costs without the object),
   the gather alone (NIN_GLS_ADJ_ONLY=9: nin_adjoint_gather_kernel reads the same buffer in the same order as launch_vjp).
 For the two new kernels the algorithmic bytes, computed here from the shapes -- the buffer and the index once per chunk of four
-directions, the directions and the results once each -- and the share of the 6.3 TB/s HBM rate those bytes reach."""
+directions, the directions and the results once each -- and the share of the 6.3 TB/s HBM rate those bytes reach.
+
+--reduced: beside the above, in the same session, the reduced Jacobian for M = 1, 3 and 6 parameters per cell --
+linearize_reduced's relinearize, launch_jvp and launch_vjp with 1 and 4 directions, their algorithmic bytes ((8 M + 4) nnz for the
+apply, (8 M + 8) nnz + 4 E for the transpose, 8 M E + 8 P more per direction) and ratios to the full products -- and for M = 1 the two
+yardsticks: the route CellToNode takes for dscale without it (the torch product dscale * K, then the full launch_jvp) and
+nin_spmv_device on the same pattern, which moves the same bytes."""
 import os
 import sys
 
@@ -49,8 +55,69 @@ def vjp_bytes(nnz, E, P, n):
     return -(-n // 4) * (80 * nnz + 8 * nnz + 4 * E) + n * (8 * P + 80 * E)
 
 
+def rjvp_bytes(nnz, E, P, n, M):
+    """R and esup once per chunk of four directions; per direction dtheta read (8 M E) and the node values written (8 P)"""
+    return -(-n // 4) * (8 * M + 4) * nnz + n * (8 * M * E + 8 * P)
+
+
+def rvjp_bytes(nnz, E, P, n, M):
+    """R and the index (cell_pos, cell_node: 8 nnz; cell_ptr: 4 E) once per chunk; per direction v read (8 P), grad_theta written (8 M E)"""
+    return -(-n // 4) * ((8 * M + 8) * nnz + 4 * E) + n * (8 * P + 8 * M * E)
+
+
+def time_reduced(name, I, plan, J, t, u, b, st):
+    """the reduced Jacobian beside the full one `J` whose times are in `t` (same session)"""
+    g = I.grid
+    P, E, nnz, s = int(g.n_points), int(g.n_elems), plan.nnz, st.cuda_stream
+    f64 = dict(dtype=torch.float64, device="cuda")
+    for M in (1, 3, 6):
+        B = None if M == 1 else torch.rand((M, 9), **f64) - 0.5          # M = 1: the resident permeability; else one shared set
+        bp = 0 if B is None else B.data_ptr()
+        R = plan.linearize_reduced(u.data_ptr(), M, bp, False, b.data_ptr(), s)
+        r = {"linearize": median_ms(lambda: R.relinearize(u.data_ptr(), bp, False, b.data_ptr(), s), st)}
+        print(f"{name}: M = {M}: buffer {R.nbytes / 1e9:.3f} GB; linearize {r['linearize']:.3f} ms = {r['linearize'] / t['linearize']:.3f} x "
+              f"the full linearize", flush=True)
+        for k in (1, 4):
+            dth, out = torch.rand((k, E, M), **f64) - 0.5, torch.empty((k, P), **f64)
+            r[f"jvp{k}"] = median_ms(lambda: R.launch_jvp(dth.data_ptr(), out.data_ptr(), k, s), st)
+            v, gt = torch.rand((k, P), **f64) - 0.5, torch.empty((k, E, M), **f64)
+            r[f"vjp{k}"] = median_ms(lambda: R.launch_vjp(v.data_ptr(), gt.data_ptr(), k, s), st)
+            assert torch.isfinite(out).all() and torch.isfinite(gt).all()
+            for what, nbytes in ((f"jvp{k}", rjvp_bytes(nnz, E, P, k, M)), (f"vjp{k}", rvjp_bytes(nnz, E, P, k, M))):
+                rate = nbytes / (r[what] * 1e-3) / 1e12
+                print(f"{name}: M = {M}: launch_{what[:3]}, n = {k}: {r[what]:.3f} ms = {r[what] / t[what]:.3f} x the full product; "
+                      f"{nbytes / 1e9:.3f} GB algorithmic = {rate:.2f} TB/s = {100 * rate / HBM_TBS:.0f} % of {HBM_TBS} TB/s", flush=True)
+            del dth, out, v, gt
+        if M == 1:
+            # today's route for dscale: the (E, 9) direction dscale * K by torch, then the full product
+            K = torch.rand((E, 9), **f64) + 0.5
+            for k in (1, 4):
+                ds, out = torch.rand((k, E), **f64) - 0.5, torch.empty((k, P), **f64)
+
+                def today():
+                    tperm = (K.reshape(1, E, 9) * ds[:, :, None]).contiguous()
+                    J.launch_jvp(tperm.data_ptr(), out.data_ptr(), k, 0, s)
+                ms = median_ms(today, st)
+                print(f"{name}: dscale today (torch dscale * K, full launch_jvp), n = {k}: {ms:.3f} ms = {ms / r[f'jvp{k}']:.2f} x the "
+                      f"reduced launch_jvp", flush=True)
+                # the same bytes through the CSR kernel: R as a value array on esup's pattern
+                w, x = torch.rand(nnz, **f64) - 0.5, torch.rand((k, E), **f64) - 0.5
+                ms = median_ms(lambda: plan.launch_spmv(w.data_ptr(), x.data_ptr(), k, out.data_ptr(), s), st)
+                print(f"{name}: nin_spmv_device on the same pattern, n = {k}: {ms:.3f} ms; reduced launch_jvp / spmv = {r[f'jvp{k}'] / ms:.2f}",
+                      flush=True)
+                gx = torch.empty((k, E), **f64)
+                vv = torch.rand((k, P), **f64) - 0.5
+                ms = median_ms(lambda: plan.launch_spmv_transpose(w.data_ptr(), vv.data_ptr(), k, gx.data_ptr(), s), st)
+                print(f"{name}: nin_spmv_transpose_device, n = {k}: {ms:.3f} ms; reduced launch_vjp / spmv_transpose = {r[f'vjp{k}'] / ms:.2f}",
+                      flush=True)
+                del ds, out, w, x, gx, vv
+            del K
+        R.release()
+
+
 def main():
     names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["hex216", "del54"]
+    reduced = "--reduced" in sys.argv[1:]
     if not torch.cuda.is_available():
         raise SystemExit("time_jacobian.py needs a GPU")
     torch.cuda.init()
@@ -97,8 +164,11 @@ def main():
         print(f"{name}: tangent / jvp = {t['tangent1'] / t['jvp1']:.0f}; backward / vjp = {t['backward'] / t['vjp1']:.0f}; "
               f"vjp / gather = {t['vjp1'] / t['gather']:.2f}; each direction beyond the first: jvp {(t['jvp4'] - t['jvp1']) / 3:.3f} ms, "
               f"vjp {(t['vjp4'] - t['vjp1']) / 3:.3f} ms", flush=True)
+        del ghat, gperm
+        if reduced:
+            time_reduced(name, I, plan, J, t, u, b, st)
         J.release()
-        del ghat, gperm, plan, J
+        del plan, J
         I.release_scratch()
         del I
 
