@@ -207,11 +207,13 @@ TRANSFORMS = {
 TRANSFORM_MESHES = ("hex8", "tet5", "mixed844")
 
 
-def transformed_mesh(name, transform):
+def transformed_mesh(name, transform, factory=None, seed=7):
+    """unit_cases()[name] under TRANSFORMS[transform]; factory: a (mesh factory, Neumann plane) pair of the caller's own instead of
+    the unit case's (tests/gls_derivative_exact.py: the meshes of the derivative tests), seed: attach_fields' """
     from ninpol_amd import mesh as M
     t = TRANSFORMS[transform]
-    make, plane = unit_cases()[name]
-    m = M.attach_fields(make(), "u", perm="LIN" if "lin" in t else "ALH", neumann_plane=plane, seed=7)
+    make, plane = unit_cases()[name] if factory is None else factory
+    m = M.attach_fields(make(), "u", perm="LIN" if "lin" in t else "ALH", neumann_plane=plane, seed=seed)
     if "lin" in t:
         m.cell_data["permeability"] = [np.ascontiguousarray(k * t["lin"]) for k in m.cell_data["permeability"]]
     m.points = np.ascontiguousarray(m.points * np.asarray(t.get("A", (1.0, 1.0, 1.0))) + np.asarray(t.get("b", (0.0, 0.0, 0.0))))

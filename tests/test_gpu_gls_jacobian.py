@@ -12,7 +12,12 @@ and n = 5), against the model:
   J . dK    per row, of the model's row scale:                        4.45e-13 (Delaunay; 9.0e-14 hex, 1.5e-13 mixed, 2.5e-14 tet)
   J^T . v   per cell, of scale_perm / scale_diff_mag (+ their fold):  8.64e-12 (Delaunay; 5.2e-13 hex, 3.2e-13 mixed, 3.6e-13 tet)
 The bars are 10 x those, never looser than the 1e-8 at which the model itself is pinned.  The device duality gap measured 0 to 3.3e-16
-absolute against derived bars of 4.9e-12 and more."""
+absolute against derived bars of 4.9e-12 and more.
+The Delaunay figures contain the lstsq MODEL's own distance from the exact derivative: against the 80-bit model of
+tests/gls_derivative_exact.py (this file's u and b, one direction and one cotangent of its own) the lstsq model is 6.1e-13 (J . dK) and
+1.02e-11 (J^T . v, grad_perm; 3.9e-12 grad_diff_mag) away on that mesh, the device 4.4e-15 to 9.0e-15 (J . dK) and 7.5e-14 / 4.3e-12
+(J^T . v, grad_perm / grad_diff_mag) -- tests/test_gpu_gls_derivative_exact.py, profiles/r17.  The bars stay: they bound the distance
+between the device and this model."""
 import math
 
 import numpy as np
