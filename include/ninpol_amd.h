@@ -79,7 +79,8 @@ int nin_grid_create_on_device(int64_t dim, int64_t n_elems, int64_t n_points,
 
 /* Readonly attributes of Grid (grid.pxd:128-187).  Scalars: dim n_elems n_points n_faces n_edges
  * MX_ELEMENTS_PER_POINT MX_POINTS_PER_POINT MX_ELEMENTS_PER_FACE MX_FACES_PER_POINT; of the library's own: coords_dim nnz_esup
- * nnz_fsup gls_adjoint_contrib_bytes (the GLS adjoint's contribution buffer as allocated now, 0: not there).  Unknown -> -1. */
+ * nnz_fsup gls_adjoint_contrib_bytes (the GLS adjoint's contribution buffer as allocated now, 0: not there) gls_shape_contrib_bytes
+ * (the same for the three buffers of the adjoint in the node coordinates).  Unknown -> -1. */
 int64_t nin_grid_scalar(const nin_grid *g, const char *name);
 
 /* Number of elements of array `name` and its dtype code; arrays: esup esup_ptr psup psup_ptr fsup
@@ -461,6 +462,38 @@ int nin_gls_weights_tangent_device(nin_grid *g, int add_neumann, int32_t n_tange
 int nin_gls_permeability_tangent_host(nin_grid *g, const double *tangent_permeability, const double *cell_values, int32_t n_fields,
                                       double *node_values, double *neumann_ws);
 
+/* ---- the GLS weights differentiated with respect to the node coordinates: a shape adjoint ---------------------------------------
+ * The GLS weights are a function of the resident geometry too: the centroids of a node's cells, the centres and unit normals of its
+ * faces and the node's own position fill its system, and all of them follow the node coordinates (nin_grid_update_points*).  Given
+ * the gradient of a scalar L with respect to the STORED weights these calls return dL/d point_coords, for shape fitting, shape
+ * optimisation and error-driven mesh motion -- one backward pass instead of two launches per coordinate.  3-D grids, GLS only: IDW
+ * and LS depend on the coordinates as well but are not differentiated.  Not provided: a tangent (forward mode) or a kept Jacobian in
+ * the coordinates, dirty-row / local-motion variants, 2-D meshes, the sharded path, the Neumann values.
+ *
+ * nin_gls_weights_backward_points_device: dev_grad_csr, dev_grad_neumann_ws and add_neumann as in nin_gls_weights_backward_device;
+ *   writes dev_grad_points [n_points][3] = dL/d point_coords at what is resident NOW (geometry, flags, K).  The derivative is that
+ *   of the real-valued model: the float32 casts of the stored normals count as the identity.  Nodes the forward gives the zero row
+ *   contribute nothing, but every node -- Dirichlet nodes too -- receives gradient as a vertex of its cells and faces.  The adjoint
+ *   kernel in its coordinate mode (the same bins, factorisation and slots) writes per node three records in a fixed order --
+ *   xbar_own, cbar per entry of esup, (fcbar, Nbar) per entry of fsup -- and three gather kernels take them through the geometry
+ *   (centroid, face centre, normal of the first three points of a face) to the vertices: per face in inpofa order, per cell in
+ *   ascending node id, per node in row order.  No atomics: two calls agree bit for bit.
+ *   The first call allocates 24 bytes per entry of esup, 48 per entry of fsup and 96 per face (1.9 + 5.8 + 2.9 GB at 216^3
+ *   hexahedra; nin_grid_scalar "gls_shape_contrib_bytes": what is allocated now), makes the adjoint's bins, the transpose index and
+ *   the connectivity copies of nin_grid_update_points* if they are not there, and synchronises `stream`; later calls are
+ *   asynchronous on it.  Kept until nin_grid_release_scratch.  Errors as nin_gls_weights_backward_device (NULL: grid, dev_grad_csr,
+ *   dev_grad_points), and NIN_EINVAL for a grid that is not 3-D.  NIN_GLS_ADJ_FORCE_GLOBAL as there.  NIN_GLS_ADJ_ONLY=<bin> is a
+ *   TIMING switch only: the other bins' kernels are skipped, so their nodes' records keep what an earlier call left, xbar_own of
+ *   those nodes is not written (the gathers add onto whatever dev_grad_points held) and the call still returns NIN_OK -- with a
+ *   value that is no bin (tools/time_shape_adjoint.py: the three gathers alone) nothing of the result means anything.
+ * nin_gls_points_gradient_host: the host-pointer counterpart, the sibling of nin_gls_permeability_gradient_host -- grad_points
+ *   [n_points][3] = d <node_values, W cell_values> / d point_coords for the W of nin_apply_* (add_neumann = 1); node_values
+ *   [n_fields][n_points], cell_values [n_fields][n_elems]; synchronous.  Errors as the two calls it makes. */
+int nin_gls_weights_backward_points_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
+                                           double *dev_grad_points, void *stream);
+int nin_gls_points_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields,
+                                 double *grad_points);
+
 /* ---- the GLS Jacobian in the permeability, kept on the device: linearise once, apply J and J^T many times ----------------------
  * The two calls above repeat the dense QR of every node at every call.  A Krylov solver applies J . dK or J^T . v once per iteration
  * at ONE linearisation point; for it, a nin_gls_jacobian keeps the derivative itself.  For a fixed cell field u (and optional node
@@ -569,7 +602,7 @@ int nin_host_free(void *ptr);
 
 /* Give back the scratch a grid keeps between calls: the device buffers nin_interpolate_csr_host / nin_csr_compact_host /
  * nin_apply_* allocate on first use (weights, compacted triplets, counters: ~2.3 GB of HBM at 10 M cells, 8 x that at
- * 80 M), the transpose index of nin_spmv_transpose_device (~0.69 GB at 10 M hexahedra), the bins, contribution buffer and scratch slots of nin_gls_weights_backward_device (6.4 GB at 10 M hexahedra), the connectivity copies of nin_grid_update_points* (~1.05 GB at 10 M hexahedra; kept while a grid built on the device still mirrors from them) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
+ * 80 M), the transpose index of nin_spmv_transpose_device (~0.69 GB at 10 M hexahedra), the bins, contribution buffer and scratch slots of nin_gls_weights_backward_device (6.4 GB at 10 M hexahedra), the three buffers of nin_gls_weights_backward_points_device (10.7 GB at 10 M hexahedra), the connectivity copies of nin_grid_update_points* (~1.05 GB at 10 M hexahedra; kept while a grid built on the device still mirrors from them) and the page-locked flag staging buffer.  The next call allocates them again.  (The reference frees its dense
  * weight table when interpolate() returns, interpolator.pyx:650-651.) */
 int nin_grid_release_scratch(nin_grid *g);
 

@@ -161,6 +161,9 @@ int nin_apply_transpose_fields_host(nin_grid *g, int method, const double *node_
 void nin::release_adjoint_state(DeviceGrid &d) {
     for (auto &b : d.adj_bin) { dev_release(d, b.nodes); b = DeviceGrid::AdjBin{}; }
     dev_release(d, d.adj_contrib);
+    dev_release(d, d.shape_cell);
+    dev_release(d, d.shape_face);
+    dev_release(d, d.shape_slot);
     dev_release(d, d.adj_scratch);
     d.adj_scratch_stride = 0;
     d.adj_scratch_slots = 0;
@@ -285,6 +288,74 @@ int nin_gls_permeability_gradient_host(nin_grid *g, const double *node_values, c
     if (!rc) rc = nin_gls_weights_backward_device(g, 1, dg, nullptr, dk, nullptr, nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(grad_permeability, dk, eb * 9, hipMemcpyDeviceToHost));
+    return NIN_OK;
+}
+
+// ---- the GLS adjoint in the node coordinates: dL/d point_coords from dL/d(stored weights) -----------------------------
+// cbar, (fcbar, Nbar) and the faces' point slots: 24 bytes per entry of esup, 48 per entry of fsup, 96 per face; the first call's
+static int ensure_shape_buffers(DeviceGrid &d) {
+    int rc = d.shape_cell ? NIN_OK : dev_alloc(d, &d.shape_cell, (size_t)std::max<int64_t>(d.nnz_e, 1) * 3);
+    if (!rc && !d.shape_face) rc = dev_alloc(d, &d.shape_face, (size_t)std::max<int64_t>(d.nnz_f, 1) * 6);
+    if (!rc && !d.shape_slot) rc = dev_alloc(d, &d.shape_slot, (size_t)std::max<int32_t>(d.v.n_faces, 1) * 12);
+    if (rc) { dev_release(d, d.shape_cell); dev_release(d, d.shape_face); dev_release(d, d.shape_slot); }
+    return rc;
+}
+
+static int points_3d(const nin_grid *g) {
+    return g->d.v.dim == 3 ? NIN_OK
+                           : fail(NIN_EINVAL, "the derivative with respect to the node coordinates is for 3-D grids only (this grid is %d-D)", (int)g->d.v.dim);
+}
+
+int nin_gls_weights_backward_points_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
+                                           double *dev_grad_points, void *stream_) {
+    if (!g || !dev_grad_csr || !dev_grad_points) return fail(NIN_EINVAL, "NULL argument");
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (int rc = points_3d(g)) return rc;
+    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
+    HIP_TRY(hipSetDevice(d.device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = ensure_adjoint_bins(d, stream);
+    if (!rc) rc = ensure_shape_buffers(d);
+    if (!rc) rc = ensure_transpose_index(d, stream);
+    if (!rc) rc = ensure_update_inputs(g);   // inpofa, as the update path brings it
+    if (rc) return rc;
+    // per-bin timing (tools/time_shape_adjoint.py), as in the backward call.  Timing only: a skipped bin's nodes keep stale records and
+    // write no xbar_own, so the gathers add onto what dev_grad_points held -- NIN_OK, but the result means nothing (ninpol_amd.h)
+    const char *only_env = getenv("NIN_GLS_ADJ_ONLY");
+    const int only = only_env ? atoi(only_env) : -1;
+    for (int b = 0; b < kAdjBins && !rc; ++b) {
+        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
+        if (only >= 0 && b != only) continue;
+        rc = launch_gls_adjoint_points(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, dev_grad_csr, dev_grad_neumann_ws, d.shape_cell,
+                                       d.shape_face, dev_grad_points, d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots, stream);
+    }
+    if (!rc) rc = launch_shape_gather(d.v, d.up_inpofa, d.tr_cell_ptr, d.tr_cell_pos, d.shape_cell, d.shape_face, d.shape_slot, dev_grad_points, stream);
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_gls_points_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields, double *grad_points) {
+    if (!g || !node_values || !cell_values || !grad_points) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (int rc = points_3d(g)) return rc;
+    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;
+    HIP_TRY(hipSetDevice(d.device));
+    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8;
+    DevTmp<double> dv, du, dg, dx;
+    HIP_TRY(hipMalloc((void **)&dv, pb * n_fields));
+    HIP_TRY(hipMalloc((void **)&du, eb * n_fields));
+    HIP_TRY(hipMalloc((void **)&dg, (size_t)std::max<int64_t>(d.nnz_e, 1) * 8));
+    HIP_TRY(hipMalloc((void **)&dx, std::max<size_t>(pb, 8) * 3));
+    HIP_TRY(hipMemcpy(dv, node_values, pb * n_fields, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(du, cell_values, eb * n_fields, hipMemcpyHostToDevice));
+    // W as apply() uses it (`+ neumann_ws[row]` included): add_neumann = 1, nothing flows through neumann_ws itself
+    int rc = nin_sddmm_device(g, du, dv, n_fields, dg, nullptr);
+    if (!rc) rc = nin_gls_weights_backward_points_device(g, 1, dg, nullptr, dx, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(grad_points, dx, pb * 3, hipMemcpyDeviceToHost));
     return NIN_OK;
 }
 

@@ -224,6 +224,8 @@ int64_t nin_grid_scalar(const nin_grid *g, const char *name) {
     if (n == "nnz_esup") return h.nnz_esup;
     if (n == "nnz_fsup") return h.nnz_fsup;
     if (n == "gls_adjoint_contrib_bytes") return g->d.adj_contrib ? std::max<int64_t>(g->d.nnz_e, 1) * 80 : 0;
+    if (n == "gls_shape_contrib_bytes")
+        return g->d.shape_cell ? std::max<int64_t>(g->d.nnz_e, 1) * 24 + std::max<int64_t>(g->d.nnz_f, 1) * 48 + std::max<int64_t>(g->d.v.n_faces, 1) * 96 : 0;
     return -1;
 }
 

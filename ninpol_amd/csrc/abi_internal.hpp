@@ -165,6 +165,9 @@ int launch_lists(DeviceGrid &d, int method, const int32_t *lists, const int32_t 
 inline size_t desc_align(size_t words) { return (words + 3) & ~(size_t)3; }
 // abi_update.hip: the host's copy of the resident flag bytes (flag_staging), brought up to date
 int fetch_flag_bytes(nin_grid *g);
+// abi_update.hip, for abi_apply.hip's coordinate adjoint too: inpoel / etype / inpofa on the device (DeviceGrid::up_*), brought by the
+// first caller (synchronous)
+int ensure_update_inputs(nin_grid *g);
 // abi_apply.hip: the adjoint's and the tangent's bins and scratch slots, and the adjoint's contribution buffer, given back
 void release_adjoint_state(DeviceGrid &d);
 // abi_apply.hip, for abi_jacobian.hip: the cell-major index of the esup pattern and the adjoint's bins, made if they are not there

@@ -35,9 +35,11 @@ struct GeometryMirror : LazyArrays {
     }
 };
 
+}  // namespace
+
 // inpoel / etype / inpofa and the face-area array on the device (DeviceGrid::up_*): from the device builder's mirror if it still
-// holds them, else uploaded from the host arrays.  Synchronous.
-int ensure_update_inputs(nin_grid *g) {
+// holds them, else uploaded from the host arrays.  Synchronous.  (The coordinate adjoint of abi_apply.hip reads inpofa through it too.)
+int nin::ensure_update_inputs(nin_grid *g) {
     DeviceGrid &d = g->d;
     HostGrid &h = g->h;
     if (d.up_inpoel) return NIN_OK;
@@ -64,6 +66,8 @@ int ensure_update_inputs(nin_grid *g) {
     d.up_areas_valid = false;   // room only: a whole-mesh update writes every area, a local one uploads the host's first
     return NIN_OK;
 }
+
+namespace {
 
 // the points per cell of the element types, one byte each (grid_update.hip, fields_scatter.hip)
 uint64_t pack_npoel8(const HostGrid &h) {

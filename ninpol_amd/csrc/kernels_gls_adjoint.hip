@@ -28,6 +28,12 @@
 // RED = true (with TAN = false only): the lane contracts its ten values with the cell's basis B [red_m][9] and writes the
 // red_m values of the reduced Jacobian instead, contrib [esup position][red_m] -- the 80-byte record is never stored.
 //
+// PTS = true (with TAN = RED = false only): the weights differentiated with respect to the node coordinates.  The same
+// kernel up to y, r, s, q; then Abar meets the four geometric inputs of the node's system instead of K -- the centroids of its cells
+// (cbar, contrib [esup position][3]), the centre and the normal of its faces ((fcbar, Nbar), pts_face [fsup position][6]) and the
+// node itself (xbar_own, pts_own [P][3], summed by wavefront 0 in a fixed order) -- and kernels_gls_shape.hip takes those through
+// the geometry of geom_math.hpp to the vertices.  No slot memory beyond the adjoint's, no atomics.
+//
 // The tangent (TAN = true): the same kernel up to y, r, rho and the verdict, then for every direction dK (9 per cell; d
 // diff_mag per cell given, or folded from the resident perm) the directional derivative of the stored entries.  dA is non-zero where K
 // enters: -(dK_a N) / +(dK_b N) on the K.N row, -/+ dtau U on the tau.T2 row with dtau = -ln|T2| tau ddm_pick (pick: the cell the
@@ -65,7 +71,14 @@ struct AdjointIo {
         const double *red_basis;         // RED: B [E][red_m][9] (red_stride = 9 red_m), [red_m][9] (red_stride = 0: shared) or null: g.perm
     };
     const double *tan_dm;                // tangent: d diff_mag [n_tan][E] or null (folded from g.perm)
-    double *tan_csr, *tan_nws;           //          d stored weights [n_tan][nnz]; d neumann_ws [n_tan][P] or null
+    union {
+        double *tan_csr;                 // tangent: d stored weights [n_tan][nnz]
+        double *pts_face;                // PTS: (fcbar, Nbar) of every (node, face) pair [nnz_fsup][6]
+    };
+    union {
+        double *tan_nws;                 // tangent: d neumann_ws [n_tan][P] or null
+        double *pts_own;                 // PTS: xbar_own [P][3]
+    };
     union {
         long long nnz;
         long long red_stride;            // RED: doubles from one cell's basis to the next
@@ -124,7 +137,7 @@ __device__ __forceinline__ void back_substitute(const double *A, int ld, int nc,
     }
 }
 
-template <int TW, bool LDS, bool TAN, bool RED>
+template <int TW, bool LDS, bool TAN, bool RED, bool PTS>
 __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, const int32_t *__restrict__ nodes, int32_t count, int add_neumann,
                                                                  AdjointIo io, double *scratch, long long scratch_stride) {
     extern __shared__ double smem[];
@@ -158,6 +171,10 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
                     for (int i = tid; i < ne; i += nthr) io.tan_csr[(size_t)t * io.nnz + eb + i] = 0.0;
                     if (io.tan_nws && tid == 0) io.tan_nws[(size_t)t * g.n_points + p] = 0.0;
                 }
+            } else if constexpr (PTS) {
+                for (int i = tid; i < 3 * ne; i += nthr) contrib[3 * (size_t)eb + i] = 0.0;
+                for (int i = tid; i < 6 * nf; i += nthr) io.pts_face[6 * (size_t)fb + i] = 0.0;
+                if (tid < 3) io.pts_own[3 * (size_t)p + tid] = 0.0;
             } else if constexpr (RED) {
                 for (int i = tid; i < io.red_m * ne; i += nthr) contrib[(size_t)io.red_m * (size_t)eb + i] = 0.0;
             } else {
@@ -432,6 +449,85 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
 
         // ---- contributions: thread i = cell i of the node, the node's faces in fsup order ------------------------------------
         const bool ok = tau[0] != 0.0;
+        if constexpr (PTS) {
+            // ---- the coordinate mode: Abar meets the geometry instead of K.  Thread i = cell i: cbar = Abar(i, 3i:3i+3);
+            //      thread fi = face fi of the node: (fcbar, Nbar); then wavefront 0 sums xbar_own = -sum cbar - sum fcbar in a fixed order
+            for (int i = tid; i < ne; i += nthr) {
+                double *o = contrib + 3 * (size_t)(eb + i);
+                const double qi = qv[i], ri = rv[i];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[c] = ok ? -(qi * y[3 * i + c]) - ri * sv[3 * i + c] : 0.0;
+            }
+            for (int fi = tid; fi < nf; fi += nthr) {
+                double o[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                const int t = frow[fi], Ia = fia[fi], Ib = fib[fi];
+                if (ok && t >= 0) {
+                    const size_t f = (size_t)g.fsup[fb + fi];
+                    const double N[3] = {(double)g.face_normal[3 * f + 0], (double)g.face_normal[3 * f + 1], (double)g.face_normal[3 * f + 2]};
+                    const double *Ka = g.perm + 9 * (size_t)cells[Ia];
+                    const double qt = qv[t], rt = rv[t];
+                    double aA[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) aA[c] = -(qt * y[3 * Ia + c]) - rt * sv[3 * Ia + c];
+                    if (Ib < 0) {   // a Neumann boundary face: the row holds -(K_a N)
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) o[3 + j] = -((Ka[j] * aA[0] + Ka[3 + j] * aA[1]) + Ka[6 + j] * aA[2]);
+                    } else {
+                        const double *Kb = g.perm + 9 * (size_t)cells[Ib];
+                        const double q1 = qv[t + 1], r1 = rv[t + 1], q2 = qv[t + 2], r2 = rv[t + 2];
+                        double nb[3], D1[3], D2[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const double ya = y[3 * Ia + c], yb = y[3 * Ib + c], sa = sv[3 * Ia + c], sb = sv[3 * Ib + c];
+                            D1[c] = (-(q1 * yb) - r1 * sb) - (-(q1 * ya) - r1 * sa);
+                            D2[c] = (-(q2 * yb) - r2 * sb) - (-(q2 * ya) - r2 * sa);
+                        }
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) {   // K_b^T Abar(t, 3Ib:) - K_a^T Abar(t, 3Ia:)
+                            const double aB0 = -(qt * y[3 * Ib + 0]) - rt * sv[3 * Ib + 0], aB1 = -(qt * y[3 * Ib + 1]) - rt * sv[3 * Ib + 1],
+                                         aB2 = -(qt * y[3 * Ib + 2]) - rt * sv[3 * Ib + 2];
+                            nb[j] = ((Kb[j] * aB0 + Kb[3 + j] * aB1) + Kb[6 + j] * aB2) - ((Ka[j] * aA[0] + Ka[3 + j] * aA[1]) + Ka[6 + j] * aA[2]);
+                        }
+                        const double T[3] = {xv0 - g.face_center[3 * f + 0], xv1 - g.face_center[3 * f + 1], xv2 - g.face_center[3 * f + 2]};
+                        const double U[3] = {N[1] * T[2] - N[2] * T[1], N[2] * T[0] - N[0] * T[2], N[0] * T[1] - N[1] * T[0]};
+                        const double un2 = U[0] * U[0] + U[1] * U[1] + U[2] * U[2];
+                        const double da = g.diff_mag[cells[Ia]], db = g.diff_mag[cells[Ib]];
+                        double eta = 0.0;
+                        eta = da > eta ? da : eta;
+                        eta = db > eta ? db : eta;
+                        const double tj = glsmath::face_tau(sqrt(un2), eta);
+                        // Ubar = tau D_2 - eta tau (D_2.U) / |U|^2 U:  d(tau U) = tau dU + U dtau,  dtau = -eta tau (U.dU) / |U|^2
+                        const double k = eta != 0.0 ? eta * tj * ((D2[0] * U[0] + D2[1] * U[1]) + D2[2] * U[2]) / un2 : 0.0;
+                        const double ub[3] = {tj * D2[0] - k * U[0], tj * D2[1] - k * U[1], tj * D2[2] - k * U[2]};
+                        // Tbar = D_1 + Ubar x N (fcbar = -Tbar);  Nbar += T x Ubar
+                        o[0] = -(D1[0] + (ub[1] * N[2] - ub[2] * N[1]));
+                        o[1] = -(D1[1] + (ub[2] * N[0] - ub[0] * N[2]));
+                        o[2] = -(D1[2] + (ub[0] * N[1] - ub[1] * N[0]));
+                        o[3] = nb[0] + (T[1] * ub[2] - T[2] * ub[1]);
+                        o[4] = nb[1] + (T[2] * ub[0] - T[0] * ub[2]);
+                        o[5] = nb[2] + (T[0] * ub[1] - T[1] * ub[0]);
+                    }
+                }
+                double *of = io.pts_face + 6 * (size_t)(fb + fi);
+#pragma unroll
+                for (int c = 0; c < 6; ++c) of[c] = o[c];
+            }
+            __syncthreads();   // the node's records are written: wavefront 0 reads them back
+            if (wave == 0) {
+                double a[3] = {0.0, 0.0, 0.0};
+                for (int i = lane; i < ne; i += 64)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) a[c] -= contrib[3 * (size_t)(eb + i) + c];
+                for (int fi = lane; fi < nf; fi += 64)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) a[c] -= io.pts_face[6 * (size_t)(fb + fi) + c];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) a[c] = wave_sum(a[c]);
+                if (lane < 3) io.pts_own[3 * (size_t)p + lane] = lane == 0 ? a[0] : (lane == 1 ? a[1] : a[2]);
+            }
+            __syncthreads();   // (the slot is the next node's)
+            continue;
+        }
         for (int i = tid; i < ne; i += nthr) {
             double kb[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, etab = 0.0;
             for (int fi = 0; ok && fi < nf; ++fi) {
@@ -528,15 +624,15 @@ __global__ __launch_bounds__(256) void nin_adjoint_gather_kernel(int32_t n_elems
     for (int k = 0; k < 9; ++k) grad_perm[9 * (size_t)e + k] = acc[k];
 }
 
-template <int TW, bool LDS, bool TAN, bool RED>
+template <int TW, bool LDS, bool TAN, bool RED, bool PTS>
 int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io, double *scratch,
                int64_t stride, int32_t slots, hipStream_t stream) {
-    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN, RED>;
+    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS>;
     int64_t blocks;
     size_t lds = 0;
     if (LDS) {
         lds = (size_t)bytes;
-        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED>>(lds)) return -3;
+        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS>>(lds)) return -3;
         int64_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : (int64_t)lds);
         if (per_cu > 32 / TW) per_cu = 32 / TW;
         if (per_cu < 1) per_cu = 1;
@@ -550,17 +646,17 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
 }
 
 // one bin's nodes through the class of that bin: 1, 2, 4 wavefronts in LDS, 8 over a global-memory slot
-template <bool TAN, bool RED>
+template <bool TAN, bool RED, bool PTS = false>
 int launch_bin_of(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io,
                   double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
     if (count <= 0) return 0;
     switch (bin) {
-        case 0: return launch_bin<1, true, TAN, RED>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 1: return launch_bin<2, true, TAN, RED>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 2: return launch_bin<4, true, TAN, RED>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 0: return launch_bin<1, true, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 1: return launch_bin<2, true, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 2: return launch_bin<4, true, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
         case 3:
             if (!scratch || scratch_slots < 1 || scratch_stride * 8 < bytes) return -1;
-            return launch_bin<8, false, TAN, RED>(g, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+            return launch_bin<8, false, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
     }
     return -1;
 }
@@ -588,6 +684,14 @@ int launch_gls_adjoint_reduced(const GridView &g, int bin, const int32_t *nodes,
     io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = reduced;
     io.red_basis = red.basis; io.red_stride = (long long)red.stride; io.red_m = red.n_params;
     return launch_bin_of<false, true>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+}
+
+int launch_gls_adjoint_points(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
+                              const double *grad_csr, const double *grad_nws, double *cell_bar, double *face_bar, double *own_bar,
+                              double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
+    AdjointIo io{};
+    io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = cell_bar; io.pts_face = face_bar; io.pts_own = own_bar;
+    return launch_bin_of<false, false, true>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
 }
 
 int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, int32_t n_tangents,

@@ -1,0 +1,137 @@
+// kernels_gls_shape.hip -- the GLS weights differentiated with respect to the node coordinates, part 2: from the geometric inputs of
+// the nodes' systems to the vertices, gfx950.
+//
+// The adjoint kernel in its coordinate mode (kernels_gls_adjoint.hip, PTS) leaves, per computed node p,
+//   xbar_own [p][3]               what the node's own position gets through the rows of its system (in grad_points itself),
+//   cbar [esup position][3]       dL/d centroid_e through node p's system,
+//   (fcbar, Nbar) [fsup position][6]   dL/d face centre and dL/d unit normal of face f through node p's system.
+// The geometry of geom_math.hpp (3-D) is differentiated here, in three kernels that follow each other on one stream:
+//   nin_shape_face_kernel, thread f: Fcbar_f and Nbar_f summed over the face's points in inpofa order (the position of f in a point's
+//     fsup row by binary search: the rows are ascending).  fc_f = sum x_v / npofa gives every point Fcbar_f / npofa, the fourth point
+//     of a quadrilateral too; n = v1 x v2 with v1 = x_0 - x_1, v2 = x_2 - x_1, N = n / |n| gives
+//       nbar = (Nbar_f - (Nbar_f . N) N) / |n|,  v1bar = v2 x nbar,  v2bar = nbar x v1,  x_0 += v1bar, x_2 += v2bar, x_1 -= v1bar + v2bar
+//     (v1, v2 and |n| in float64 from the resident coordinates, N the resident float32 normal: the derivative is that of the real-valued
+//     model, the float32 casts of face_geometry_of count as the identity).  One 3-vector per point slot of the face, face_slot [F][4][3].
+//   nin_shape_cell_kernel, thread e: Cbar_e over the cell's nodes in ascending node id through the transpose index; centroid_e =
+//     sum x_v / n_e, so Cbar_e / n_e replaces the records of the cell in cbar, in place (they are the cell's alone).
+//   nin_shape_node_kernel, thread p: grad_points[p] = xbar_own[p] + sum over esup[p] of cbar + sum over fsup[p] of the slot of p in f,
+//     each sum in row order.
+// No atomics: two calls agree bit for bit.
+#include <hip/hip_runtime.h>
+
+#include "device_grid.hpp"
+#include "launch.hpp"
+
+namespace nin {
+
+namespace {
+
+__global__ __launch_bounds__(256) void nin_shape_face_kernel(GridView g, const int4 *__restrict__ inpofa, const double *__restrict__ face_bar,
+                                                             double *__restrict__ face_slot) {
+    const int32_t f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= g.n_faces) return;
+    const int4 r = inpofa[f];
+    const int32_t q[4] = {r.x, r.y, r.z, r.w};
+    int npofa = 0;
+    while (npofa < 4 && q[npofa] >= 0 && q[npofa] < g.n_points) ++npofa;   // (a row ends at the first -1; the builders checked every index)
+    double *slot = face_slot + 12 * (size_t)f;
+    if (npofa < 3) {   // (no face of a 3-D mesh)
+        for (int i = 0; i < 12; ++i) slot[i] = 0.0;
+        return;
+    }
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < npofa; ++k) {
+        int32_t lo = g.fsup_ptr[q[k]], hi = g.fsup_ptr[q[k] + 1];
+        while (lo < hi) {   // the first position with fsup >= f
+            const int32_t mid = lo + ((hi - lo) >> 1);
+            if (g.fsup[mid] < f) lo = mid + 1; else hi = mid;
+        }
+        if (lo >= g.fsup_ptr[q[k] + 1] || g.fsup[lo] != f) continue;
+        const double *rec = face_bar + 6 * (size_t)lo;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) acc[c] += rec[c];
+    }
+    double x[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[j][c] = g.coords[3 * (size_t)q[j] + c];
+    const double v1[3] = {x[0][0] - x[1][0], x[0][1] - x[1][1], x[0][2] - x[1][2]};
+    const double v2[3] = {x[2][0] - x[1][0], x[2][1] - x[1][1], x[2][2] - x[1][2]};
+    const double n[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+    // (no guard on |n| = 0: a face whose first three points are collinear has no normal, the forward's rows of it are NaN already, and
+    // so is the gradient of its three points -- also where Nbar_f itself is zero)
+    const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double N[3] = {(double)g.face_normal[3 * (size_t)f + 0], (double)g.face_normal[3 * (size_t)f + 1], (double)g.face_normal[3 * (size_t)f + 2]};
+    const double dot = (acc[3] * N[0] + acc[4] * N[1]) + acc[5] * N[2];
+    const double nb[3] = {(acc[3] - dot * N[0]) / nn, (acc[4] - dot * N[1]) / nn, (acc[5] - dot * N[2]) / nn};
+    const double v1b[3] = {v2[1] * nb[2] - v2[2] * nb[1], v2[2] * nb[0] - v2[0] * nb[2], v2[0] * nb[1] - v2[1] * nb[0]};
+    const double v2b[3] = {nb[1] * v1[2] - nb[2] * v1[1], nb[2] * v1[0] - nb[0] * v1[2], nb[0] * v1[1] - nb[1] * v1[0]};
+    const double dn = (double)npofa;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double share = acc[c] / dn;
+        slot[0 + c] = share + v1b[c];
+        slot[3 + c] = share - (v1b[c] + v2b[c]);
+        slot[6 + c] = share + v2b[c];
+        slot[9 + c] = npofa == 4 ? share : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void nin_shape_cell_kernel(int32_t n_elems, const int32_t *__restrict__ cell_ptr, const int32_t *__restrict__ cell_pos,
+                                                             double *__restrict__ cell_bar) {
+    const int32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_elems) return;
+    const int32_t jb = cell_ptr[e], je = cell_ptr[e + 1];
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int32_t j = jb; j < je; ++j) {
+        const double *c = cell_bar + 3 * (size_t)cell_pos[j];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc[k] += c[k];
+    }
+    const double dn = (double)(je - jb);   // the points of the cell
+    for (int32_t j = jb; j < je; ++j) {
+        double *c = cell_bar + 3 * (size_t)cell_pos[j];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = acc[k] / dn;
+    }
+}
+
+__global__ __launch_bounds__(256) void nin_shape_node_kernel(GridView g, const int4 *__restrict__ inpofa, const double *__restrict__ cell_bar,
+                                                             const double *__restrict__ face_slot, double *__restrict__ grad_points) {
+    const int32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= g.n_points) return;
+    double acc[3] = {grad_points[3 * (size_t)p + 0], grad_points[3 * (size_t)p + 1], grad_points[3 * (size_t)p + 2]};   // xbar_own
+    for (int32_t j = g.esup_ptr[p]; j < g.esup_ptr[p + 1]; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += cell_bar[3 * (size_t)j + c];
+    for (int32_t j = g.fsup_ptr[p]; j < g.fsup_ptr[p + 1]; ++j) {
+        const int32_t f = g.fsup[j];
+        const int4 r = inpofa[f];
+        const int k = r.x == p ? 0 : (r.y == p ? 1 : (r.z == p ? 2 : (r.w == p ? 3 : -1)));
+        if (k < 0) continue;
+        const double *s = face_slot + 12 * (size_t)f + 3 * k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += s[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) grad_points[3 * (size_t)p + c] = acc[c];
+}
+
+}  // namespace
+
+int launch_shape_gather(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos, double *cell_bar,
+                        const double *face_bar, double *face_slot, double *grad_points, hipStream_t stream) {
+    const int4 *rows = reinterpret_cast<const int4 *>(inpofa);
+    if (g.n_faces > 0)
+        hipLaunchKernelGGL(nin_shape_face_kernel, dim3((unsigned)((g.n_faces + 255) / 256)), dim3(256), 0, stream, g, rows, face_bar, face_slot);
+    if (g.n_elems > 0)
+        hipLaunchKernelGGL(nin_shape_cell_kernel, dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems, cell_ptr, cell_pos,
+                           cell_bar);
+    if (g.n_points > 0)
+        hipLaunchKernelGGL(nin_shape_node_kernel, dim3((unsigned)((g.n_points + 255) / 256)), dim3(256), 0, stream, g, rows, cell_bar, face_slot,
+                           grad_points);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace nin

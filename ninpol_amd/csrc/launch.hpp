@@ -140,6 +140,16 @@ struct AdjointReduce {
 int launch_gls_adjoint_reduced(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
                                const double *grad_csr, const double *grad_nws, const AdjointReduce &red, double *reduced, double *scratch,
                                int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
+// launch_gls_adjoint_points: the same launch in the kernel's coordinate mode -- every listed node writes cbar of its cells to
+//   cell_bar [nnz_esup][3], (fcbar, Nbar) of its faces to face_bar [nnz_fsup][6] and xbar_own to own_bar [P][3], zeros where the forward
+//   has its zero row.  launch_shape_gather (kernels_gls_shape.hip) then takes them through the geometry to the vertices: inpofa [F][4] as
+//   launch_update_geometry reads it, the transpose index (cell_ptr, cell_pos), face_slot [F][4][3] its own scratch; cell_bar is
+//   overwritten; grad_points [P][3] holds xbar_own on entry and dL/d coords on return (3-D grids only)
+int launch_gls_adjoint_points(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
+                              const double *grad_csr, const double *grad_nws, double *cell_bar, double *face_bar, double *own_bar,
+                              double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
+int launch_shape_gather(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos, double *cell_bar,
+                        const double *face_bar, double *face_slot, double *grad_points, hipStream_t stream);
 // launch_gls_tangent: the same kernel's tangent mode on the nodes of one bin -- n_tangents directions tangent_perm [n_tangents][E][9]
 //   (tangent_diff_mag [n_tangents][E], or null: folded from the resident g.perm) -> the directional derivative of the stored weights,
 //   tangent_csr [n_tangents][nnz] in esup position, and of neumann_ws, tangent_nws [n_tangents][P] or null; every row of every listed

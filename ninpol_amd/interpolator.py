@@ -859,7 +859,7 @@ class Interpolator:
         shaped alike with n_elems (default: the cell variable `variable` itself, for every v).  Returns (n_elems, 3, 3): the gradient
         with respect to the resident permeability table, the chain through diff_mag = (1 - 3 / tr K)^2 folded in.  On the device, the
         sibling of apply_transpose(): host-synchronous, numpy in and out; deterministic.  Nodes whose row is zero (Dirichlet nodes)
-        contribute nothing; the Neumann values and the coordinates are not differentiated."""
+        contribute nothing; the Neumann values are not differentiated (the node coordinates: points_gradient())."""
         self._check_call(variable=variable)
         self._perm_rows()   # (ValueError without a permeability)
         g = self.grid
@@ -882,6 +882,37 @@ class Interpolator:
         _lib.check(_lib.load().nin_gls_permeability_gradient_host(g._h, _ptr(v), _ptr(u), k, _ptr(out)))
         return out
 
+    def points_gradient(self, variable, node_values, cell_values=None):
+        """The derivative of `<v, W u>` with respect to the node coordinates, for the GLS matrix W that `apply(variable, "gls")` uses
+        (the `+ neumann_ws[row]` included): `node_values` = v, one node array (n_points,) or k of them as (k, n_points);
+        `cell_values` = u, shaped alike with n_elems (default: the cell variable `variable` itself, for every v).  Returns
+        (n_points, 3): the gradient with respect to the grid's resident coordinates -- what update_points() rewrites -- at the
+        resident permeability and flags; the float32 casts of the stored normals count as the identity.  On the device, the sibling
+        of permeability_gradient(): host-synchronous, numpy in and out; deterministic.  Nodes whose row is zero (Dirichlet nodes)
+        contribute nothing but receive gradient as vertices of their cells and faces.  3-D meshes, GLS only; the Neumann values are
+        not differentiated."""
+        self._check_call(variable=variable)
+        self._perm_rows()   # (ValueError without a permeability)
+        g = self.grid
+        v = np.ascontiguousarray(node_values, dtype=DTYPE_F)
+        if v.shape != (g.n_points,) and not (v.ndim == 2 and v.shape[0] >= 1 and v.shape[1] == g.n_points):
+            raise ValueError(f"node_values must have shape ({g.n_points},) or (k, {g.n_points}), not {v.shape}.")
+        k = 1 if v.ndim == 1 else v.shape[0]
+        if cell_values is None:
+            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
+            u = np.ascontiguousarray(np.broadcast_to(u, (k, g.n_elems)), dtype=DTYPE_F)
+        else:
+            u = np.ascontiguousarray(cell_values, dtype=DTYPE_F)
+            if u.shape != v.shape[:-1] + (g.n_elems,):
+                raise ValueError(f"cell_values must have shape {v.shape[:-1] + (g.n_elems,)} beside node_values of shape {v.shape}, "
+                                 f"not {u.shape}.")
+        if g.device < 0:
+            g.to_device(self.device)
+        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        out = np.empty((g.n_points, 3), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_points_gradient_host(g._h, _ptr(v), _ptr(u), k, _ptr(out)))
+        return out
+
     def permeability_tangent(self, variable, dK, cell_values=None):
         """The directional derivative of what `apply(variable, "gls")` returns, along a change `dK` of the permeability: `dK` one
         direction (n_elems, 3, 3) or k of them as (k, n_elems, 3, 3); `cell_values` = u, (n_elems,) or (k, n_elems) alike (default: the
@@ -890,7 +921,7 @@ class Interpolator:
         neumann_ws, at the resident permeability table, the chain through diff_mag = (1 - 3 / tr K)^2 folded in.  On the device, the
         sibling of permeability_gradient(): host-synchronous, numpy in and out; deterministic.  It is what a Newton-Krylov solver with
         K(u) needs, `J . v` without differencing two weight launches.  Rows that are zero (Dirichlet nodes) have a zero derivative; the
-        Neumann values and the coordinates are not differentiated."""
+        Neumann values are not differentiated, and the node coordinates have no tangent (their adjoint: points_gradient())."""
         self._check_call(variable=variable)
         self._perm_rows()   # (ValueError without a permeability)
         g = self.grid
@@ -1108,6 +1139,22 @@ class DevicePlan:
         vp = lambda a: ctypes.c_void_p(a) if a else None
         _lib.check(_lib.load().nin_gls_weights_backward_device(self.grid._h, int(bool(add_neumann)), vp(grad_csr_ptr), vp(grad_neumann_ws_ptr),
                                                                vp(grad_perm_ptr), vp(grad_diff_mag_ptr), ctypes.c_void_p(stream)))
+
+    def launch_weights_backward_points(self, grad_csr_ptr, grad_points_ptr, grad_neumann_ws_ptr=0, stream=0, add_neumann=True):
+        """The GLS weights differentiated with respect to the node coordinates (nin_gls_weights_backward_points_device): grad_csr
+        [nnz_esup] = dL/d csr_data of a `launch(..., add_neumann)` (grad_neumann_ws [n_points] = dL/d neumann_ws, 0: none) ->
+        grad_points [n_points][3] = dL/d point_coords at what is resident now (geometry, flags, K): a shape adjoint, the sibling of
+        launch_weights_backward.  Every node gets its gradient, Dirichlet nodes too (as vertices of their cells and faces).
+        Asynchronous on `stream` after the first call on a grid (which makes the bins and buffers -- 24 bytes per entry of esup, 48 per
+        entry of fsup, 96 per face -- and synchronises); deterministic.  3-D grids.  GLS only: the IDW and LS weights depend on the
+        coordinates too, but their derivative is not provided -- a plan of those methods raises instead of returning zeros."""
+        if self.method != "gls":
+            raise ValueError(f"the weights of '{self.method}' do depend on the node coordinates, but they are not differentiated here: "
+                             "launch_weights_backward_points is GLS only")
+        self.ensure_current()
+        vp = lambda a: ctypes.c_void_p(a) if a else None
+        _lib.check(_lib.load().nin_gls_weights_backward_points_device(self.grid._h, int(bool(add_neumann)), vp(grad_csr_ptr),
+                                                                      vp(grad_neumann_ws_ptr), vp(grad_points_ptr), ctypes.c_void_p(stream)))
 
     def launch_weights_tangent(self, tangent_perm_ptr, tangent_csr_ptr, n_tangents=1, tangent_diff_mag_ptr=0, tangent_neumann_ws_ptr=0, stream=0,
                                add_neumann=True):

@@ -4,6 +4,8 @@ also makes the GLS weights a function of the permeability tensor K: its backward
 (nin_sddmm_device) and the adjoint of the weight kernels (nin_gls_weights_backward_device).  Under torch.autograd.forward_ad (dual
 tensors) the same call gives the forward derivative, W du + dW u, with dW from the tangent of the weight kernels
 (nin_gls_weights_tangent_device); torch.func.jvp, which needs setup_context-style Functions, is not supported.
+`CellToNode(...)(u, points=X)` makes the GLS weights a function of the node coordinates as well: the mesh moves to X
+(Interpolator.update_points) and the backward pass returns dL/dX (nin_gls_weights_backward_points_device), backwards only.
 `CellToNode.linearize(u, K, scale)` is for a caller that needs many such products at one point (a Krylov solver): it keeps the
 Jacobian of W u in the permeability on the device (nin_gls_jacobian) and returns a Linearization whose jvp / vjp are plain tensor
 methods, one streaming pass each instead of a factorisation of every node.
@@ -55,14 +57,18 @@ class _CellToNodeFn(torch.autograd.Function):
 
 
 class _GlsWeightsFn(torch.autograd.Function):
-    """K [n_elems][3][3] (or [n_elems][9]), scale [n_elems] or None -> the stored GLS weights [nnz_esup] and neumann_ws [n_points] of the
-    permeability scale * K, which becomes the grid's resident table (Interpolator.update_permeability).  Backward reads what is
-    resident -- geometry, flags, permeability -- so it refuses to run once any of them was updated after the forward pass: it would
-    differentiate at another point."""
+    """K [n_elems][3][3] (or [n_elems][9]) or None, scale [n_elems] or None, points [n_points][3] or None -> the stored GLS weights
+    [nnz_esup] and neumann_ws [n_points] of the permeability scale * K on the mesh moved to `points`: the points become the grid's
+    resident coordinates (Interpolator.update_points), scale * K its resident table (Interpolator.update_permeability); None leaves
+    what is resident.  Backward reads what is resident -- geometry, flags, permeability -- so it refuses to run once any of them was
+    updated after the forward pass: it would differentiate at another point."""
 
     @staticmethod
-    def forward(ctx, K, scale, op):
-        op.plan.interp.update_permeability(K.detach(), None if scale is None else scale.detach())
+    def forward(ctx, K, scale, op, points=None):
+        if points is not None:
+            op.plan.interp.update_points(points.detach())
+        if K is not None:
+            op.plan.interp.update_permeability(K.detach(), None if scale is None else scale.detach())
         w, nws = op._launch_weights()
         ctx.op, ctx.stamp = op, op._stamp()
         ctx.save_for_backward(K, scale)
@@ -81,10 +87,13 @@ class _GlsWeightsFn(torch.autograd.Function):
                                "the next update, or the forward pass again.")
 
     @staticmethod
-    def jvp(ctx, dK, dscale, _):
+    def jvp(ctx, dK, dscale, _=None, dpoints=None):
         """forward mode (torch.autograd.forward_ad): the tangent of perm = scale * K is scale * dK + dscale * K, a missing tangent
         counts as zero; one DevicePlan.launch_weights_tangent call gives (dW, dneumann_ws).  Autograd calls this right behind
-        forward(); like backward() it reads what is resident and refuses once that was updated."""
+        forward(); like backward() it reads what is resident and refuses once that was updated.  The node coordinates have no
+        forward mode."""
+        if dpoints is not None:
+            raise NotImplementedError("the GLS weights have no forward-mode derivative in the node coordinates (backward() has one)")
         K, scale = ctx.saved_tensors
         op = ctx.op
         _GlsWeightsFn._check_stamp(ctx, "tangent", "jvp()")
@@ -107,24 +116,30 @@ class _GlsWeightsFn(torch.autograd.Function):
     def backward(ctx, gw, gnws):
         K, scale = ctx.saved_tensors
         op = ctx.op
-        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-            return None, None, None
+        want_perm, want_points = ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if not (want_perm or want_points):
+            return None, None, None, None
         _GlsWeightsFn._check_stamp(ctx, "gradient", "backward()")
         E = op.n_elems
-        gperm = torch.empty((E, 9), dtype=torch.float64, device=op.device)
         if gw is None:
             gw = torch.zeros(op.plan.nnz, dtype=torch.float64, device=op.device)
         gw = gw.contiguous()
         gnws = None if gnws is None else gnws.contiguous()
-        op.plan.launch_weights_backward(gw.data_ptr(), gperm.data_ptr(), 0, 0 if gnws is None else gnws.data_ptr(), op._stream(),
-                                        add_neumann=True)
-        # perm = scale * K, entry by entry
-        gK = gscale = None
-        if ctx.needs_input_grad[0]:
-            gK = (gperm if scale is None else gperm * scale[:, None]).reshape(K.shape)
-        if scale is not None and ctx.needs_input_grad[1]:
-            gscale = (K.reshape(E, 9) * gperm).sum(dim=1)
-        return gK, gscale, None
+        gK = gscale = gpoints = None
+        if want_perm:
+            gperm = torch.empty((E, 9), dtype=torch.float64, device=op.device)
+            op.plan.launch_weights_backward(gw.data_ptr(), gperm.data_ptr(), 0, 0 if gnws is None else gnws.data_ptr(), op._stream(),
+                                            add_neumann=True)
+            # perm = scale * K, entry by entry
+            if ctx.needs_input_grad[0]:
+                gK = (gperm if scale is None else gperm * scale[:, None]).reshape(K.shape)
+            if scale is not None and ctx.needs_input_grad[1]:
+                gscale = (K.reshape(E, 9) * gperm).sum(dim=1)
+        if want_points:
+            gpoints = torch.empty((op.n_points, 3), dtype=torch.float64, device=op.device)
+            op.plan.launch_weights_backward_points(gw.data_ptr(), gpoints.data_ptr(), 0 if gnws is None else gnws.data_ptr(), op._stream(),
+                                                   add_neumann=True)
+        return gK, gscale, None, gpoints
 
 
 class _ConstantWeightsFn(torch.autograd.Function):
@@ -265,9 +280,10 @@ class CellToNode(torch.nn.Module):
     from whatever is resident -- geometry and permeability -- with no table re-read, no hash and no synchronisation.
 
     The derivative with respect to the permeability comes through `forward(u, K, scale)` (GLS; see there) or `weights_of(K, scale)`,
-    backwards (backward()) and forwards (torch.autograd.forward_ad: dual u, K, scale in any combination).
-    Derivatives with respect to the Neumann values or the node coordinates are not provided, nor are those of the sharded
-    (multi-GPU) path; the tangent is that of a full launch (recompute_weights(dirty_only=True) carries none)."""
+    backwards (backward()) and forwards (torch.autograd.forward_ad: dual u, K, scale in any combination).  The derivative with
+    respect to the node coordinates comes through `forward(u, points=...)` / `weights_of(points=...)`, backwards only (GLS, 3-D).
+    Derivatives with respect to the Neumann values are not provided, nor are those of the sharded (multi-GPU) path; the tangent is
+    that of a full launch (recompute_weights(dirty_only=True) carries none)."""
 
     def __init__(self, interp, variable, method):
         super().__init__()
@@ -337,7 +353,7 @@ class CellToNode(torch.nn.Module):
         self.plan.launch_sddmm(u.data_ptr(), v.data_ptr(), k, out.data_ptr(), self._stream())
         return out
 
-    def weights_of(self, K, scale=None):
+    def weights_of(self, K=None, scale=None, points=None):
         """The stored weights [nnz_esup] (esup / CSR position, `+ neumann_ws[row]` included) and neumann_ws [n_points] as differentiable
         functions of the permeability: K float64 (n_elems, 3, 3) or (n_elems, 9) on the plan's device, optionally times the per-cell
         factor `scale` (n_elems,) -- the arguments, and the checks, of Interpolator.update_permeability with device tensors, which is
@@ -347,7 +363,27 @@ class CellToNode(torch.nn.Module):
         RuntimeError if Grid.field_updates, geometry_updates or flag_updates moved after this call (another weights_of /
         forward(u, K) included): run each backward before the next update.  Under forward_ad.dual_level() dual K / scale give the
         weights' tangent along scale * dK + dscale * K through DevicePlan.launch_weights_tangent.  IDW / LS: the module's weights, and
-        zeros for K."""
+        zeros for K.
+
+        points: float64 (n_points, 3) on the plan's device, alone or beside K (3-D meshes, GLS) -- the weights as a differentiable
+        function of the node coordinates.  It is given to Interpolator.update_points() first, as K is to update_permeability(): the
+        mesh moves there.  Backward gives dL/dpoints through DevicePlan.launch_weights_backward_points, under the same rule about
+        later updates; there is no forward mode in the coordinates.  IDW / LS depend on the coordinates too, but that derivative is
+        not provided: ValueError, never zeros."""
+        if points is not None:
+            if self.plan.method != "gls":
+                raise ValueError(f"the weights of '{self.plan.method}' do depend on the node coordinates, but they are not differentiated "
+                                 "here: points= is GLS only")
+            if not isinstance(points, torch.Tensor) or points.dtype != torch.float64:
+                raise TypeError(f"points must be a float64 torch.Tensor on {self.device} (no silent cast)")
+            if points.device != self.device or tuple(points.shape) != (self.n_points, 3):
+                raise ValueError(f"points must be on {self.device} with shape ({self.n_points}, 3), not {tuple(points.shape)} on {points.device}")
+        if K is None:
+            if scale is not None:
+                raise ValueError("scale needs K")
+            if points is None:
+                raise ValueError("weights_of needs K or points")
+            return _GlsWeightsFn.apply(None, None, self, points)
         if not isinstance(K, torch.Tensor):
             raise TypeError(f"K must be a torch.Tensor on {self.device}, not {type(K).__name__}")
         if K.device != self.device:
@@ -361,7 +397,7 @@ class CellToNode(torch.nn.Module):
                 if t.device != self.device or tuple(t.shape) not in shapes:
                     raise ValueError(f"{name} must be on {self.device} with shape {' or '.join(map(str, shapes))}")
             return _ConstantWeightsFn.apply(K, scale, self.weights), self.neumann_ws
-        return _GlsWeightsFn.apply(K, scale, self)
+        return _GlsWeightsFn.apply(K, scale, self, points)
 
     def linearize(self, u, K=None, scale=None, neumann_values=None, wrt="K"):
         """Linearise `forward(u, K, scale)` once, for many jvp / vjp products at that point: u float64 (n_elems,) on the plan's device
@@ -414,11 +450,12 @@ class CellToNode(torch.nn.Module):
                 jac = self.plan.linearize(u.data_ptr(), 0 if b is None else b.data_ptr(), self._stream())
         return Linearization(self, u, weights, neumann_ws, jac, K, scale, wrt)
 
-    def forward(self, u, K=None, scale=None):
+    def forward(self, u, K=None, scale=None, points=None):
         """u: float64 (n_elems,) or (k, n_elems) on the plan's device -> node values (n_points,) or (k, n_points).
 
         With K (and optionally scale; see weights_of): the weights are first computed from the permeability scale * K, and the
-        result is differentiable in u, K and scale.  Without K nothing changes: the module's weights are applied."""
+        result is differentiable in u, K and scale.  With points (see weights_of): the mesh is first moved there, and the result is
+        differentiable in the node coordinates too.  Without either nothing changes: the module's weights are applied."""
         if not isinstance(u, torch.Tensor):
             raise TypeError(f"u must be a torch.Tensor, not {type(u).__name__}")
         if u.dtype != torch.float64:
@@ -427,9 +464,9 @@ class CellToNode(torch.nn.Module):
             raise ValueError(f"u must be on {self.device}, not {u.device}")
         if tuple(u.shape) != (self.n_elems,) and not (u.dim() == 2 and u.shape[0] >= 1 and u.shape[1] == self.n_elems):
             raise ValueError(f"u must have shape ({self.n_elems},) or (k, {self.n_elems}), not {tuple(u.shape)}")
-        if K is None:
+        if K is None and points is None:
             if scale is not None:
                 raise ValueError("scale needs K")
             return _CellToNodeFn.apply(u.contiguous(), self, self.weights)
-        weights, _ = self.weights_of(K, scale)
+        weights, _ = self.weights_of(K, scale, points)
         return _CellToNodeFn.apply(u.contiguous(), self, weights)
