@@ -178,6 +178,16 @@ def check(rc):
         raise NinpolError(rc, load().nin_last_error().decode())
 
 
+def _ptr(a):
+    """a numpy array as a pointer argument (None stays None: an optional argument of the C entry point)"""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _vp(address):
+    """a device address held as an int as a pointer argument (0 becomes NULL: an optional argument of the C entry point)"""
+    return ctypes.c_void_p(address) if address else None
+
+
 def device_count():
     n = ctypes.c_int(0)
     rc = load().nin_device_count(ctypes.byref(n))

@@ -143,18 +143,15 @@ int nin_apply_transpose_fields_host(nin_grid *g, int method, const double *node_
     if (int rc = weights_ready(d, method, false)) return rc;   // (the weight launch below adds the size check)
     HIP_TRY(hipSetDevice(d.device));
     if (int rc = ensure_apply_weights(d)) return rc;
-    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8;
+    const size_t P = (size_t)g->h.n_points, E = (size_t)g->h.n_elems, k = (size_t)n_fields;
     DevTmp<double> dn, dv, dx;
-    HIP_TRY(hipMalloc((void **)&dn, pb));
-    HIP_TRY(hipMalloc((void **)&dv, pb * n_fields));
-    HIP_TRY(hipMalloc((void **)&dx, eb * n_fields));
-    HIP_TRY(hipMemcpy(dv, node_values, pb * n_fields, hipMemcpyHostToDevice));
+    int rc = dev_stage(dn, nullptr, P);
+    if (!rc) rc = dev_stage(dv, node_values, P * k);
+    if (!rc) rc = dev_stage(dx, nullptr, E * k);
     // the unfused weights (the fused cube-node apply writes no rows for cube nodes), with `+ neumann_ws[row]` as apply() uses them
-    int rc = nin_weights_device(g, method, nullptr, 0, 1, d.apply_weights, dn, nullptr);
+    if (!rc) rc = nin_weights_device(g, method, nullptr, 0, 1, d.apply_weights, dn, nullptr);
     if (!rc) rc = nin_spmv_transpose_device(g, d.apply_weights, dv, n_fields, dx, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(cell_values, dx, eb * n_fields, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    return rc ? rc : dev_fetch(cell_values, dx, E * k);
 }
 
 // ---- the GLS adjoint: dL/dK from dL/d(stored weights) (kernels_gls_adjoint.hip) ---------------------------------------
@@ -217,39 +214,47 @@ static int ensure_adjoint_contrib(DeviceGrid &d) {
     return d.adj_contrib ? NIN_OK : dev_alloc(d, &d.adj_contrib, (size_t)std::max<int64_t>(d.nnz_e, 1) * 10);
 }
 
+AdjBinRun nin::adjoint_bin_run(const DeviceGrid &d, int b) {
+    const DeviceGrid::AdjBin &bin = d.adj_bin[b];
+    return {bin.nodes, bin.count, bin.bytes, d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots};
+}
+
+int nin::adjoint_only_from_env() {
+    const char *only = getenv("NIN_GLS_ADJ_ONLY");
+    return only ? atoi(only) : -1;
+}
+
+int nin::derivative_ready(nin_grid *g, hipStream_t stream, bool coordinates) {
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (coordinates && d.v.dim != 3)
+        return fail(NIN_EINVAL, "the derivative with respect to the node coordinates is for 3-D grids only (this grid is %d-D)", (int)d.v.dim);
+    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;
+    HIP_TRY(hipSetDevice(d.device));
+    return ensure_adjoint_bins(d, stream);
+}
+
 // The adjoint kernel on the nodes of every bin (only >= 0: of that bin alone), the ten values of every (node, cell) pair into `contrib`:
-// the grid's buffer for the backward call, a nin_gls_jacobian's own for a linearisation
+// the grid's buffer for the backward call, a nin_gls_jacobian's own for a linearisation, a nin_gls_rjacobian's [nnz_esup][n_params]
+// with `reduce`
 int nin::launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
                              hipStream_t stream, const AdjointReduce *reduce) {
-    int rc = NIN_OK;
-    for (int b = 0; b < kAdjBins && !rc; ++b) {
-        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
-        if (only >= 0 && b != only) continue;
-        if (reduce)   // a nin_gls_rjacobian's linearisation: `contrib` is its [nnz_esup][n_params] buffer
-            rc = launch_gls_adjoint_reduced(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, grad_csr, grad_nws, *reduce, contrib,
-                                            d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots, stream);
-        else
-            rc = launch_gls_adjoint(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, grad_csr, grad_nws, contrib, d.adj_scratch,
-                                    d.adj_scratch_stride, d.adj_scratch_slots, stream);
-    }
-    return rc;
+    return for_each_adjoint_bin(d, only, [&](int b, const AdjBinRun &run) {
+        return reduce ? launch_gls_adjoint_reduced(d.v, b, run, add_neumann ? 1 : 0, grad_csr, grad_nws, *reduce, contrib, stream)
+                      : launch_gls_adjoint(d.v, b, run, add_neumann ? 1 : 0, grad_csr, grad_nws, contrib, stream);
+    });
 }
 
 int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
                                     double *dev_grad_perm, double *dev_grad_diff_mag, void *stream_) {
     if (!g || !dev_grad_csr || !dev_grad_perm) return fail(NIN_EINVAL, "NULL argument");
     DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
-    HIP_TRY(hipSetDevice(d.device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = ensure_adjoint_bins(d, stream);
+    int rc = derivative_ready(g, stream);
     if (!rc) rc = ensure_adjoint_contrib(d);
     if (!rc) rc = ensure_transpose_index(d, stream);
     if (rc) return rc;
-    const char *only_env = getenv("NIN_GLS_ADJ_ONLY");   // per-bin timing (tools/time_adjoint.py): launch only that bin; read at every call
-    const int only = only_env ? atoi(only_env) : -1;
-    rc = launch_adjoint_bins(d, add_neumann, only, dev_grad_csr, dev_grad_neumann_ws, d.adj_contrib, stream);
+    rc = launch_adjoint_bins(d, add_neumann, adjoint_only_from_env(), dev_grad_csr, dev_grad_neumann_ws, d.adj_contrib, stream);
     if (!rc) rc = launch_adjoint_gather(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.adj_contrib, dev_grad_perm, dev_grad_diff_mag, stream);
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     return NIN_OK;
@@ -267,28 +272,30 @@ int nin_sddmm_device(nin_grid *g, const double *dev_u_cells, const double *dev_n
     return NIN_OK;
 }
 
+// The two gradients of <v, W u> from host arrays: v [n_fields][P] and u [n_fields][E] up, grad_csr = the sampled product, `backward`
+// (dev_grad_csr, dev_out) the device sibling, `out` [out_count] down.  W as apply() uses it (`+ neumann_ws[row]` included): the siblings
+// run with add_neumann = 1, and nothing flows through neumann_ws itself
+template <class Backward>
+static int gradient_host(nin_grid *g, bool coordinates, const double *node_values, const double *cell_values, int32_t n_fields, double *out,
+                         size_t out_count, Backward backward) {
+    if (!g || !node_values || !cell_values || !out) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    if (int rc = derivative_ready(g, nullptr, coordinates)) return rc;
+    const size_t k = (size_t)n_fields;
+    DevTmp<double> dv, du, dg, dout;
+    int rc = dev_stage(dv, node_values, (size_t)g->h.n_points * k);
+    if (!rc) rc = dev_stage(du, cell_values, (size_t)g->h.n_elems * k);
+    if (!rc) rc = dev_stage(dg, nullptr, (size_t)g->d.nnz_e);
+    if (!rc) rc = dev_stage(dout, nullptr, out_count);
+    if (!rc) rc = nin_sddmm_device(g, du, dv, n_fields, dg, nullptr);
+    if (!rc) rc = backward(dg.p, dout.p);
+    return rc ? rc : dev_fetch(out, dout, out_count);
+}
+
 int nin_gls_permeability_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields,
                                        double *grad_permeability) {
-    if (!g || !node_values || !cell_values || !grad_permeability) return fail(NIN_EINVAL, "NULL argument");
-    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
-    DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
-    HIP_TRY(hipSetDevice(d.device));
-    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8;
-    DevTmp<double> dv, du, dg, dk;
-    HIP_TRY(hipMalloc((void **)&dv, pb * n_fields));
-    HIP_TRY(hipMalloc((void **)&du, eb * n_fields));
-    HIP_TRY(hipMalloc((void **)&dg, (size_t)std::max<int64_t>(d.nnz_e, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&dk, std::max<size_t>(eb, 8) * 9));
-    HIP_TRY(hipMemcpy(dv, node_values, pb * n_fields, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du, cell_values, eb * n_fields, hipMemcpyHostToDevice));
-    // W as apply() uses it (`+ neumann_ws[row]` included): add_neumann = 1, nothing flows through neumann_ws itself
-    int rc = nin_sddmm_device(g, du, dv, n_fields, dg, nullptr);
-    if (!rc) rc = nin_gls_weights_backward_device(g, 1, dg, nullptr, dk, nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(grad_permeability, dk, eb * 9, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    return gradient_host(g, false, node_values, cell_values, n_fields, grad_permeability, g ? (size_t)g->h.n_elems * 9 : 0,
+                         [&](const double *dg, double *dk) { return nin_gls_weights_backward_device(g, 1, dg, nullptr, dk, nullptr, nullptr); });
 }
 
 // ---- the GLS adjoint in the node coordinates: dL/d point_coords from dL/d(stored weights) -----------------------------
@@ -301,62 +308,30 @@ static int ensure_shape_buffers(DeviceGrid &d) {
     return rc;
 }
 
-static int points_3d(const nin_grid *g) {
-    return g->d.v.dim == 3 ? NIN_OK
-                           : fail(NIN_EINVAL, "the derivative with respect to the node coordinates is for 3-D grids only (this grid is %d-D)", (int)g->d.v.dim);
-}
-
 int nin_gls_weights_backward_points_device(nin_grid *g, int add_neumann, const double *dev_grad_csr, const double *dev_grad_neumann_ws,
                                            double *dev_grad_points, void *stream_) {
     if (!g || !dev_grad_csr || !dev_grad_points) return fail(NIN_EINVAL, "NULL argument");
     DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = points_3d(g)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
-    HIP_TRY(hipSetDevice(d.device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = ensure_adjoint_bins(d, stream);
+    int rc = derivative_ready(g, stream, true);
     if (!rc) rc = ensure_shape_buffers(d);
     if (!rc) rc = ensure_transpose_index(d, stream);
     if (!rc) rc = ensure_update_inputs(g);   // inpofa, as the update path brings it
     if (rc) return rc;
     // per-bin timing (tools/time_shape_adjoint.py), as in the backward call.  Timing only: a skipped bin's nodes keep stale records and
     // write no xbar_own, so the gathers add onto what dev_grad_points held -- NIN_OK, but the result means nothing (ninpol_amd.h)
-    const char *only_env = getenv("NIN_GLS_ADJ_ONLY");
-    const int only = only_env ? atoi(only_env) : -1;
-    for (int b = 0; b < kAdjBins && !rc; ++b) {
-        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
-        if (only >= 0 && b != only) continue;
-        rc = launch_gls_adjoint_points(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, dev_grad_csr, dev_grad_neumann_ws, d.shape_cell,
-                                       d.shape_face, dev_grad_points, d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots, stream);
-    }
+    rc = for_each_adjoint_bin(d, adjoint_only_from_env(), [&](int b, const AdjBinRun &run) {
+        return launch_gls_adjoint_points(d.v, b, run, add_neumann ? 1 : 0, dev_grad_csr, dev_grad_neumann_ws, d.shape_cell, d.shape_face,
+                                         dev_grad_points, stream);
+    });
     if (!rc) rc = launch_shape_gather(d.v, d.up_inpofa, d.tr_cell_ptr, d.tr_cell_pos, d.shape_cell, d.shape_face, d.shape_slot, dev_grad_points, stream);
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     return NIN_OK;
 }
 
 int nin_gls_points_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields, double *grad_points) {
-    if (!g || !node_values || !cell_values || !grad_points) return fail(NIN_EINVAL, "NULL argument");
-    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
-    DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = points_3d(g)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;
-    HIP_TRY(hipSetDevice(d.device));
-    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8;
-    DevTmp<double> dv, du, dg, dx;
-    HIP_TRY(hipMalloc((void **)&dv, pb * n_fields));
-    HIP_TRY(hipMalloc((void **)&du, eb * n_fields));
-    HIP_TRY(hipMalloc((void **)&dg, (size_t)std::max<int64_t>(d.nnz_e, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&dx, std::max<size_t>(pb, 8) * 3));
-    HIP_TRY(hipMemcpy(dv, node_values, pb * n_fields, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du, cell_values, eb * n_fields, hipMemcpyHostToDevice));
-    // W as apply() uses it (`+ neumann_ws[row]` included): add_neumann = 1, nothing flows through neumann_ws itself
-    int rc = nin_sddmm_device(g, du, dv, n_fields, dg, nullptr);
-    if (!rc) rc = nin_gls_weights_backward_points_device(g, 1, dg, nullptr, dx, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(grad_points, dx, pb * 3, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    return gradient_host(g, true, node_values, cell_values, n_fields, grad_points, g ? (size_t)g->h.n_points * 3 : 0,
+                         [&](const double *dg, double *dx) { return nin_gls_weights_backward_points_device(g, 1, dg, nullptr, dx, nullptr); });
 }
 
 // ---- the GLS tangent: d(stored weights) along a direction dK (kernels_gls_adjoint.hip's tangent mode) -------------------
@@ -366,21 +341,13 @@ int nin_gls_weights_tangent_device(nin_grid *g, int add_neumann, int32_t n_tange
     if (!g || !dev_tangent_perm || !dev_tangent_csr) return fail(NIN_EINVAL, "NULL argument");
     if (n_tangents < 1) return fail(NIN_EINVAL, "n_tangents must be >= 1");
     DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the kernel has a bin for systems of any size)
-    HIP_TRY(hipSetDevice(d.device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    int rc = ensure_adjoint_bins(d, stream);
-    if (rc) return rc;
-    const char *only_env = getenv("NIN_GLS_ADJ_ONLY");   // per-bin timing, as in the backward call: the other bins' rows are not written
-    const int only = only_env ? atoi(only_env) : -1;
-    for (int b = 0; b < kAdjBins && !rc; ++b) {
-        const DeviceGrid::AdjBin &bin = d.adj_bin[b];
-        if (only >= 0 && b != only) continue;
-        rc = launch_gls_tangent(d.v, b, bin.nodes, bin.count, bin.bytes, add_neumann ? 1 : 0, n_tangents, dev_tangent_perm, dev_tangent_diff_mag,
-                                dev_tangent_csr, dev_tangent_neumann_ws, d.nnz_e, d.adj_scratch, d.adj_scratch_stride, d.adj_scratch_slots,
-                                stream);
-    }
+    if (int rc = derivative_ready(g, stream)) return rc;
+    // (per-bin timing, as in the backward call: the other bins' rows are not written)
+    const int rc = for_each_adjoint_bin(d, adjoint_only_from_env(), [&](int b, const AdjBinRun &run) {
+        return launch_gls_tangent(d.v, b, run, add_neumann ? 1 : 0, n_tangents, dev_tangent_perm, dev_tangent_diff_mag, dev_tangent_csr,
+                                  dev_tangent_neumann_ws, d.nnz_e, stream);
+    });
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     return NIN_OK;
 }
@@ -390,26 +357,19 @@ int nin_gls_permeability_tangent_host(nin_grid *g, const double *tangent_permeab
     if (!g || !tangent_permeability || !cell_values || !node_values || !neumann_ws) return fail(NIN_EINVAL, "NULL argument");
     if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
     DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;
-    HIP_TRY(hipSetDevice(d.device));
-    const size_t pb = (size_t)g->h.n_points * 8, eb = (size_t)g->h.n_elems * 8, wb = (size_t)std::max<int64_t>(d.nnz_e, 1) * 8;
+    if (int rc = derivative_ready(g, nullptr)) return rc;
+    const size_t P = (size_t)g->h.n_points, E = (size_t)g->h.n_elems, k = (size_t)n_fields;
     DevTmp<double> dk, du, dw, dv, dn;
-    HIP_TRY(hipMalloc((void **)&dk, std::max<size_t>(eb, 8) * 9 * n_fields));
-    HIP_TRY(hipMalloc((void **)&du, std::max<size_t>(eb, 8) * n_fields));
-    HIP_TRY(hipMalloc((void **)&dw, wb * n_fields));
-    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(pb, 8) * n_fields));
-    HIP_TRY(hipMalloc((void **)&dn, std::max<size_t>(pb, 8) * n_fields));
-    HIP_TRY(hipMemcpy(dk, tangent_permeability, eb * 9 * n_fields, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(du, cell_values, eb * n_fields, hipMemcpyHostToDevice));
+    int rc = dev_stage(dk, tangent_permeability, E * 9 * k);
+    if (!rc) rc = dev_stage(du, cell_values, E * k);
+    if (!rc) rc = dev_stage(dw, nullptr, (size_t)d.nnz_e * k);
+    if (!rc) rc = dev_stage(dv, nullptr, P * k);
+    if (!rc) rc = dev_stage(dn, nullptr, P * k);
     // dW as apply() uses W (`+ neumann_ws[row]` included): add_neumann = 1, the diff_mag chain folded; direction f meets field f
-    int rc = nin_gls_weights_tangent_device(g, 1, n_fields, dk, nullptr, dw, dn, nullptr);
-    for (int32_t f = 0; f < n_fields && !rc; ++f)
-        rc = nin_spmv_device(g, dw.p + (size_t)f * (size_t)d.nnz_e, du.p + (size_t)f * g->h.n_elems, 1, dv.p + (size_t)f * g->h.n_points, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(node_values, dv, pb * n_fields, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(neumann_ws, dn, pb * n_fields, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    if (!rc) rc = nin_gls_weights_tangent_device(g, 1, n_fields, dk, nullptr, dw, dn, nullptr);
+    for (size_t f = 0; f < k && !rc; ++f) rc = nin_spmv_device(g, dw.p + f * (size_t)d.nnz_e, du.p + f * E, 1, dv.p + f * P, nullptr);
+    if (!rc) rc = dev_fetch(node_values, dv, P * k);
+    return rc ? rc : dev_fetch(neumann_ws, dn, P * k);
 }
 
 int nin_gls_adjoint_plan(nin_grid *g, int64_t counts[4]) {

@@ -14,6 +14,7 @@
 
 #include "../../include/ninpol_amd.h"
 #include "device_grid.hpp"
+#include "gls_adjoint.hpp"
 #include "grid_host.hpp"
 #include "launch.hpp"
 
@@ -102,6 +103,18 @@ struct DevTmp {
     T **operator&() { return &p; }
 };
 
+// What a host-pointer entry point stages around its device sibling: dev_stage gives `buf` room for `count` doubles (at least one)
+// and, with a host array, copies its `count` values up; dev_fetch copies `count` values back down (synchronous, as hipMemcpy is)
+inline int dev_stage(DevTmp<double> &buf, const double *host_or_null, size_t count) {
+    HIP_TRY(hipMalloc((void **)&buf, std::max<size_t>(count, 1) * sizeof(double)));
+    if (host_or_null) HIP_TRY(hipMemcpy(buf, host_or_null, count * sizeof(double), hipMemcpyHostToDevice));
+    return NIN_OK;
+}
+inline int dev_fetch(double *host, const double *dev, size_t count) {
+    HIP_TRY(hipMemcpy(host, dev, count * sizeof(double), hipMemcpyDeviceToHost));
+    return NIN_OK;
+}
+
 // A stream (non-blocking) or an event (no timing) of the grid, made by the first call that needs it and never earlier: the streams a
 // process has open share its hardware queues
 inline int lazy_stream(void *&slot) {
@@ -171,25 +184,78 @@ int ensure_update_inputs(nin_grid *g);
 // abi_apply.hip: the adjoint's and the tangent's bins and scratch slots, and the adjoint's contribution buffer, given back
 void release_adjoint_state(DeviceGrid &d);
 // abi_apply.hip, for abi_jacobian.hip: the cell-major index of the esup pattern and the adjoint's bins, made if they are not there
-// (both synchronise `stream` when they build); the adjoint kernel on every bin (only >= 0: that bin alone) into `contrib`
+// (both synchronise `stream` when they build)
 int ensure_transpose_index(DeviceGrid &d, hipStream_t stream);
 int ensure_adjoint_bins(DeviceGrid &d, hipStream_t stream);
-// (reduce: into a [nnz_esup][n_params] buffer through launch_gls_adjoint_reduced instead, for abi_jacobian_reduced.hip)
+// abi_apply.hip: what every derivative entry point begins with, in this order -- the grid on its device (kHintKernels), for the
+// coordinates a 3-D grid, the GLS weights ready (of any size: the adjoint kernel has a bin for every system), the device set, the
+// adjoint's bins made
+int derivative_ready(nin_grid *g, hipStream_t stream, bool coordinates = false);
+// abi_apply.hip: fn(b, run) for every bin of the adjoint kernel (only >= 0: for that bin alone) until one returns non-zero, which is
+// handed back; an empty bin is the launcher's to skip.  adjoint_only_from_env: NIN_GLS_ADJ_ONLY, read at every call of the backward, the
+// coordinate and the tangent entry points (per-bin timing: tools/time_adjoint.py), or -1; a linearisation passes -1 and does not read it
+AdjBinRun adjoint_bin_run(const DeviceGrid &d, int b);
+int adjoint_only_from_env();
+template <class Fn>
+int for_each_adjoint_bin(const DeviceGrid &d, int only, Fn fn) {
+    for (int b = 0; b < kAdjBins; ++b)
+        if (only < 0 || b == only)
+            if (int rc = fn(b, adjoint_bin_run(d, b))) return rc;
+    return 0;
+}
+// the adjoint kernel on every bin (only >= 0: that bin alone), the ten values of every (node, cell) pair into `contrib`; reduce: into a
+// [nnz_esup][n_params] buffer through launch_gls_adjoint_reduced instead, for abi_jacobian_reduced.hip
 int launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
                         hipStream_t stream, const AdjointReduce *reduce = nullptr);
-// abi_jacobian.hip, for abi_jacobian_reduced.hip too -- what the two kept Jacobians share.
-// jacobian_seed: a linearisation can go on g (on its device, GLS ready, the adjoint's bins made) and `seed` [nnz_esup] holds its
-// cotangent u[esup[pos]].  jacobian_host_fields: u [n_elems] and b [n_points] (or NULL) on the device for a *_linearize_host.
-// jacobian_apply_ready: the arguments of an apply call, the grid on its device, a linearisation to apply.
+
+// ---- what the two kept Jacobians share (abi_jacobian.hip, abi_jacobian_reduced.hip) --------------------------------------------------
+// nin_gls_jacobian and nin_gls_rjacobian begin with this; each adds the buffers it owns
+struct KeptJacobian {
+    nin_grid *g = nullptr;
+    int device = -1;                   // the grid's, as it was at creation: a destroy does not look at the grid, which may be gone
+    bool linearized = false;
+    int64_t stamp[3] = {-1, -1, -1};   // the grid's (field_updates, geometry_updates, flag_updates) at the linearisation
+    void record_stamp(const DeviceGrid &d) {
+        stamp[0] = d.field_updates;
+        stamp[1] = d.geom_updates;
+        stamp[2] = d.flag_updates;
+        linearized = true;
+    }
+};
+// the body of a *_stamp call
+inline int copy_stamp(const KeptJacobian *J, int64_t stamp[3]) {
+    if (!J || !stamp) return fail(NIN_EINVAL, "NULL argument");
+    std::copy(J->stamp, J->stamp + 3, stamp);
+    return NIN_OK;
+}
+// jacobian_seed (abi_jacobian.hip): a linearisation can go on g (derivative_ready) and `seed` [nnz_esup] holds its cotangent
+// u[esup[pos]].  jacobian_apply_ready: the arguments of an apply call, the grid on its device, a linearisation to apply.
 int jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed);
-int jacobian_host_fields(nin_grid *g, const double *u_cells, const double *neumann_values, DevTmp<double> &du, DevTmp<double> &db);
-template <class Jac>
-int jacobian_apply_ready(const Jac *J, int32_t n, const void *in, const void *out, const char *linearize_name) {
+inline int jacobian_apply_ready(const KeptJacobian *J, int32_t n, const void *in, const void *out, const char *linearize_name) {
     if (n < 1) return fail(NIN_EINVAL, "n must be >= 1");
     if (!J || !in || !out) return fail(NIN_EINVAL, "NULL argument");
     if (int rc = on_device(J->g, kHintKernels)) return rc;
     if (!J->linearized) return fail(NIN_ESTATE, "the Jacobian has not been linearised (call %s first)", linearize_name);
     return NIN_OK;
+}
+// One *_apply_host or *_apply_transpose_host: `in` [n][in_per] goes up, launch(dev_in, dev_out, dev_extra) is the device sibling, `out`
+// [n][out_per] comes down.  The full Jacobian's optional diff_mag is the extra pair [n][extra_per]: an input with extra_in, an output
+// with extra_out; with neither the launch gets a null dev_extra
+template <class Launch>
+int jacobian_apply_host(const KeptJacobian *J, int32_t n, const char *linearize_name, const double *in, size_t in_per, double *out,
+                        size_t out_per, const double *extra_in, double *extra_out, size_t extra_per, Launch launch) {
+    if (int rc = jacobian_apply_ready(J, n, in, out, linearize_name)) return rc;
+    HIP_TRY(hipSetDevice(J->g->d.device));
+    const size_t k = (size_t)n;
+    const bool extra = extra_in || extra_out;
+    DevTmp<double> din, dout, dextra;
+    if (int rc = dev_stage(din, in, in_per * k)) return rc;
+    if (int rc = dev_stage(dout, nullptr, out_per * k)) return rc;
+    if (extra)
+        if (int rc = dev_stage(dextra, extra_in, extra_per * k)) return rc;
+    if (int rc = launch(din.p, dout.p, extra ? dextra.p : nullptr)) return rc;
+    if (int rc = dev_fetch(out, dout, out_per * k)) return rc;
+    return extra_out ? dev_fetch(extra_out, dextra, extra_per * k) : NIN_OK;
 }
 
 }  // namespace nin

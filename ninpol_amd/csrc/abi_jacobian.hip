@@ -1,50 +1,23 @@
 // abi_jacobian.hip -- the C ABI, part 6: the GLS Jacobian in the permeability as an object the caller keeps: one adjoint
 // launch linearises, two streaming kernels apply J and J^T from the object's own buffers (kernels_gls_jacobian.hip).
 #include "abi_internal.hpp"
-#include "gls_adjoint.hpp"
 
 using namespace nin;
 
-struct nin_gls_jacobian {
-    nin_grid *g = nullptr;
-    int device = -1;                 // the grid's, as it was at creation: nin_gls_jacobian_destroy does not look at the grid, which may be gone
+struct nin_gls_jacobian : KeptJacobian {
     double *contrib = nullptr;       // [nnz_esup][10]: the adjoint's contribution buffer, this object's own -- the Jacobian
     double *fold = nullptr;          // [E]: d diff_mag / d K_dd of the permeability that was resident at the linearisation
-    bool linearized = false;
-    int64_t stamp[3] = {-1, -1, -1};   // the grid's (field_updates, geometry_updates, flag_updates) at the linearisation
 };
 
-namespace {
+static const char *const kLinearize = "nin_gls_jacobian_linearize";
 
-int apply_ready(const nin_gls_jacobian *J, int32_t n, const void *in, const void *out) {
-    return jacobian_apply_ready(J, n, in, out, "nin_gls_jacobian_linearize");
-}
-
-}  // namespace
-
-// ---- what a linearisation of either kept Jacobian begins with (abi_jacobian_reduced.hip calls these too) -----------------------------
+// ---- what a linearisation of either kept Jacobian begins with (abi_jacobian_reduced.hip calls it too) -------------------------------
 int nin::jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed) {
     DeviceGrid &d = g->d;
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    if (int rc = weights_ready(d, NIN_METHOD_GLS, false)) return rc;   // (the adjoint has a bin for systems of any size)
-    HIP_TRY(hipSetDevice(d.device));
-    if (int rc = ensure_adjoint_bins(d, stream)) return rc;
+    if (int rc = derivative_ready(g, stream)) return rc;
     // the cotangent of F = W u + neumann_ws b: grad_csr[pos] = u[esup[pos]], grad_neumann_ws = b
-    HIP_TRY(hipMalloc((void **)&seed, (size_t)std::max<int64_t>(d.nnz_e, 1) * sizeof(double)));
+    if (int rc = dev_stage(seed, nullptr, (size_t)d.nnz_e)) return rc;
     if (int rc = launch_jac_seed(d.v, d.nnz_e, dev_u_cells, seed, stream)) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return NIN_OK;
-}
-
-int nin::jacobian_host_fields(nin_grid *g, const double *u_cells, const double *neumann_values, DevTmp<double> &du, DevTmp<double> &db) {
-    if (int rc = on_device(g, kHintKernels)) return rc;
-    HIP_TRY(hipSetDevice(g->d.device));
-    const size_t pb = std::max<size_t>((size_t)g->h.n_points, 1) * 8, eb = std::max<size_t>((size_t)g->h.n_elems, 1) * 8;
-    HIP_TRY(hipMalloc((void **)&du, eb));
-    HIP_TRY(hipMemcpy(du, u_cells, (size_t)g->h.n_elems * 8, hipMemcpyHostToDevice));
-    if (neumann_values) {
-        HIP_TRY(hipMalloc((void **)&db, pb));
-        HIP_TRY(hipMemcpy(db, neumann_values, (size_t)g->h.n_points * 8, hipMemcpyHostToDevice));
-    }
     return NIN_OK;
 }
 
@@ -88,16 +61,13 @@ int nin_gls_jacobian_linearize(nin_gls_jacobian *J, const double *dev_u_cells, c
     rc = launch_adjoint_bins(d, 1, -1, seed, dev_neumann_values, J->contrib, stream);   // always every bin
     if (!rc) rc = launch_jac_fold(d.v, J->fold, stream);
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
-    J->stamp[0] = d.field_updates;
-    J->stamp[1] = d.geom_updates;
-    J->stamp[2] = d.flag_updates;
-    J->linearized = true;
+    J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
 }
 
 int nin_gls_jacobian_apply(nin_gls_jacobian *J, int32_t n, const double *dev_dperm, const double *dev_ddiff_mag, double *dev_dnode,
                            void *stream_) {
-    if (int rc = apply_ready(J, n, dev_dperm, dev_dnode)) return rc;
+    if (int rc = jacobian_apply_ready(J, n, dev_dperm, dev_dnode, kLinearize)) return rc;
     DeviceGrid &d = J->g->d;
     HIP_TRY(hipSetDevice(d.device));
     const int rc = launch_jac_apply(d.v, J->contrib, J->fold, n, dev_dperm, dev_ddiff_mag, dev_dnode, static_cast<hipStream_t>(stream_));
@@ -107,7 +77,7 @@ int nin_gls_jacobian_apply(nin_gls_jacobian *J, int32_t n, const double *dev_dpe
 
 int nin_gls_jacobian_apply_transpose(nin_gls_jacobian *J, int32_t n, const double *dev_v, double *dev_grad_perm, double *dev_grad_diff_mag,
                                      void *stream_) {
-    if (int rc = apply_ready(J, n, dev_v, dev_grad_perm)) return rc;
+    if (int rc = jacobian_apply_ready(J, n, dev_v, dev_grad_perm, kLinearize)) return rc;
     DeviceGrid &d = J->g->d;
     HIP_TRY(hipSetDevice(d.device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -126,54 +96,35 @@ int nin_gls_jacobian_contrib(nin_gls_jacobian *J, const double **dev_contrib, co
     return NIN_OK;
 }
 
-int nin_gls_jacobian_stamp(const nin_gls_jacobian *J, int64_t stamp[3]) {
-    if (!J || !stamp) return fail(NIN_EINVAL, "NULL argument");
-    for (int i = 0; i < 3; ++i) stamp[i] = J->stamp[i];
-    return NIN_OK;
-}
+int nin_gls_jacobian_stamp(const nin_gls_jacobian *J, int64_t stamp[3]) { return copy_stamp(J, stamp); }
 
 // ---- host pointers: what Interpolator.permeability_jacobian calls (synchronous) ------------------------------------------------------
 int nin_gls_jacobian_linearize_host(nin_gls_jacobian *J, const double *u_cells, const double *neumann_values) {
     if (!J || !u_cells) return fail(NIN_EINVAL, "NULL argument");
+    nin_grid *g = J->g;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    HIP_TRY(hipSetDevice(g->d.device));
     DevTmp<double> du, db;
-    if (int rc = jacobian_host_fields(J->g, u_cells, neumann_values, du, db)) return rc;
-    if (int rc = nin_gls_jacobian_linearize(J, du, neumann_values ? db.p : nullptr, nullptr)) return rc;
+    if (int rc = dev_stage(du, u_cells, (size_t)g->h.n_elems)) return rc;
+    if (neumann_values)
+        if (int rc = dev_stage(db, neumann_values, (size_t)g->h.n_points)) return rc;
+    if (int rc = nin_gls_jacobian_linearize(J, du, db, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NIN_OK;
 }
 
 int nin_gls_jacobian_apply_host(nin_gls_jacobian *J, int32_t n, const double *dperm, const double *ddiff_mag, double *dnode) {
-    if (int rc = apply_ready(J, n, dperm, dnode)) return rc;
-    nin_grid *g = J->g;
-    HIP_TRY(hipSetDevice(g->d.device));
-    const size_t P = (size_t)g->h.n_points, E = (size_t)g->h.n_elems, k = (size_t)n;
-    DevTmp<double> dk, dm, dv;
-    HIP_TRY(hipMalloc((void **)&dk, std::max<size_t>(E, 1) * 72 * k));
-    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(P, 1) * 8 * k));
-    HIP_TRY(hipMemcpy(dk, dperm, E * 72 * k, hipMemcpyHostToDevice));
-    if (ddiff_mag) {
-        HIP_TRY(hipMalloc((void **)&dm, std::max<size_t>(E, 1) * 8 * k));
-        HIP_TRY(hipMemcpy(dm, ddiff_mag, E * 8 * k, hipMemcpyHostToDevice));
-    }
-    if (int rc = nin_gls_jacobian_apply(J, n, dk, ddiff_mag ? dm.p : nullptr, dv, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(dnode, dv, P * 8 * k, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    const size_t P = J ? (size_t)J->g->h.n_points : 0, E = J ? (size_t)J->g->h.n_elems : 0;
+    return jacobian_apply_host(J, n, kLinearize, dperm, 9 * E, dnode, P, ddiff_mag, nullptr, E, [&](const double *dk, double *dv, double *dm) {
+        return nin_gls_jacobian_apply(J, n, dk, dm, dv, nullptr);
+    });
 }
 
 int nin_gls_jacobian_apply_transpose_host(nin_gls_jacobian *J, int32_t n, const double *v, double *grad_perm, double *grad_diff_mag) {
-    if (int rc = apply_ready(J, n, v, grad_perm)) return rc;
-    nin_grid *g = J->g;
-    HIP_TRY(hipSetDevice(g->d.device));
-    const size_t P = (size_t)g->h.n_points, E = (size_t)g->h.n_elems, k = (size_t)n;
-    DevTmp<double> dk, dm, dv;
-    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(P, 1) * 8 * k));
-    HIP_TRY(hipMalloc((void **)&dk, std::max<size_t>(E, 1) * 72 * k));
-    if (grad_diff_mag) HIP_TRY(hipMalloc((void **)&dm, std::max<size_t>(E, 1) * 8 * k));
-    HIP_TRY(hipMemcpy(dv, v, P * 8 * k, hipMemcpyHostToDevice));
-    if (int rc = nin_gls_jacobian_apply_transpose(J, n, dv, dk, grad_diff_mag ? dm.p : nullptr, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(grad_perm, dk, E * 72 * k, hipMemcpyDeviceToHost));
-    if (grad_diff_mag) HIP_TRY(hipMemcpy(grad_diff_mag, dm, E * 8 * k, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    const size_t P = J ? (size_t)J->g->h.n_points : 0, E = J ? (size_t)J->g->h.n_elems : 0;
+    return jacobian_apply_host(J, n, kLinearize, v, P, grad_perm, 9 * E, nullptr, grad_diff_mag, E, [&](const double *dv, double *dk, double *dm) {
+        return nin_gls_jacobian_apply_transpose(J, n, dv, dk, dm, nullptr);
+    });
 }
 
 int nin_gls_jacobian_fetch_host(nin_gls_jacobian *J, double *contrib, double *fold) {
@@ -182,7 +133,6 @@ int nin_gls_jacobian_fetch_host(nin_gls_jacobian *J, double *contrib, double *fo
     nin_grid *g = J->g;
     if (int rc = on_device(g, kHintKernels)) return rc;
     HIP_TRY(hipSetDevice(g->d.device));
-    HIP_TRY(hipMemcpy(contrib, J->contrib, (size_t)g->d.nnz_e * 80, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(fold, J->fold, (size_t)g->h.n_elems * 8, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    if (int rc = dev_fetch(contrib, J->contrib, (size_t)g->d.nnz_e * 10)) return rc;
+    return dev_fetch(fold, J->fold, (size_t)g->h.n_elems);
 }

@@ -2,25 +2,19 @@
 // theta_(e,m) B_(e,m) with M = 1, 3 or 6 parameters per cell, as an object the caller keeps.  One adjoint launch in its
 // RED mode linearises straight into R [nnz_esup][M] -- the 80-byte record of abi_jacobian.hip is never stored -- and two streaming
 // kernels apply J_theta and its transpose (kernels_gls_jacobian_reduced.hip).  The preconditions are abi_jacobian.hip's
-// (abi_internal.hpp: jacobian_seed, jacobian_host_fields, jacobian_apply_ready).
+// (abi_internal.hpp: KeptJacobian, jacobian_seed, jacobian_apply_ready, jacobian_apply_host).
 #include "abi_internal.hpp"
 
 using namespace nin;
 
-struct nin_gls_rjacobian {
-    nin_grid *g = nullptr;
-    int device = -1;                 // the grid's, as it was at creation: nin_gls_rjacobian_destroy does not look at the grid, which may be gone
+struct nin_gls_rjacobian : KeptJacobian {
     int32_t n_params = 0;            // M
     double *R = nullptr;             // [nnz_esup][M]: this object's own -- the Jacobian
-    bool linearized = false;
-    int64_t stamp[3] = {-1, -1, -1};   // the grid's (field_updates, geometry_updates, flag_updates) at the linearisation
 };
 
 namespace {
 
-int apply_ready(const nin_gls_rjacobian *J, int32_t n, const void *in, const void *out) {
-    return jacobian_apply_ready(J, n, in, out, "nin_gls_rjacobian_linearize");
-}
+const char *const kLinearize = "nin_gls_rjacobian_linearize";
 
 // how many cells' worth of basis the caller passes: NULL is the resident perm and goes with one parameter only
 int basis_ready(const nin_gls_rjacobian *J, const void *basis) {
@@ -72,15 +66,12 @@ int nin_gls_rjacobian_linearize(nin_gls_rjacobian *J, const double *dev_u_cells,
     const AdjointReduce red{J->n_params, dev_basis, dev_basis && basis_per_cell ? (int64_t)9 * J->n_params : 0};
     rc = launch_adjoint_bins(d, 1, -1, seed, dev_neumann_values, J->R, stream, &red);   // always every bin: every entry of R is written
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
-    J->stamp[0] = d.field_updates;
-    J->stamp[1] = d.geom_updates;
-    J->stamp[2] = d.flag_updates;
-    J->linearized = true;
+    J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
 }
 
 int nin_gls_rjacobian_apply(nin_gls_rjacobian *J, int32_t n, const double *dev_dtheta, double *dev_dnode, void *stream_) {
-    if (int rc = apply_ready(J, n, dev_dtheta, dev_dnode)) return rc;
+    if (int rc = jacobian_apply_ready(J, n, dev_dtheta, dev_dnode, kLinearize)) return rc;
     DeviceGrid &d = J->g->d;
     HIP_TRY(hipSetDevice(d.device));
     const int rc = launch_jacr_apply(d.v, J->n_params, J->R, n, dev_dtheta, dev_dnode, static_cast<hipStream_t>(stream_));
@@ -89,7 +80,7 @@ int nin_gls_rjacobian_apply(nin_gls_rjacobian *J, int32_t n, const double *dev_d
 }
 
 int nin_gls_rjacobian_apply_transpose(nin_gls_rjacobian *J, int32_t n, const double *dev_v, double *dev_grad_theta, void *stream_) {
-    if (int rc = apply_ready(J, n, dev_v, dev_grad_theta)) return rc;
+    if (int rc = jacobian_apply_ready(J, n, dev_v, dev_grad_theta, kLinearize)) return rc;
     DeviceGrid &d = J->g->d;
     HIP_TRY(hipSetDevice(d.device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -107,55 +98,39 @@ int nin_gls_rjacobian_buffer(nin_gls_rjacobian *J, const double **dev_R, int32_t
     return NIN_OK;
 }
 
-int nin_gls_rjacobian_stamp(const nin_gls_rjacobian *J, int64_t stamp[3]) {
-    if (!J || !stamp) return fail(NIN_EINVAL, "NULL argument");
-    for (int i = 0; i < 3; ++i) stamp[i] = J->stamp[i];
-    return NIN_OK;
-}
+int nin_gls_rjacobian_stamp(const nin_gls_rjacobian *J, int64_t stamp[3]) { return copy_stamp(J, stamp); }
 
 // ---- host pointers: what Interpolator.permeability_jacobian(basis=...) calls (synchronous) ---------------------------------------------
 int nin_gls_rjacobian_linearize_host(nin_gls_rjacobian *J, const double *u_cells, const double *neumann_values, const double *basis,
                                      int32_t basis_per_cell) {
     if (!J || !u_cells) return fail(NIN_EINVAL, "NULL argument");
     if (int rc = basis_ready(J, basis)) return rc;
+    nin_grid *g = J->g;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    HIP_TRY(hipSetDevice(g->d.device));
     DevTmp<double> du, db, dB;
-    if (int rc = jacobian_host_fields(J->g, u_cells, neumann_values, du, db)) return rc;
-    if (basis) {
-        const size_t count = (basis_per_cell ? (size_t)J->g->h.n_elems : 1) * 9 * (size_t)J->n_params;
-        HIP_TRY(hipMalloc((void **)&dB, std::max<size_t>(count, 1) * 8));
-        HIP_TRY(hipMemcpy(dB, basis, count * 8, hipMemcpyHostToDevice));
-    }
-    if (int rc = nin_gls_rjacobian_linearize(J, du, neumann_values ? db.p : nullptr, basis ? dB.p : nullptr, basis_per_cell, nullptr)) return rc;
+    if (int rc = dev_stage(du, u_cells, (size_t)g->h.n_elems)) return rc;
+    if (neumann_values)
+        if (int rc = dev_stage(db, neumann_values, (size_t)g->h.n_points)) return rc;
+    if (basis)
+        if (int rc = dev_stage(dB, basis, (basis_per_cell ? (size_t)g->h.n_elems : 1) * 9 * (size_t)J->n_params)) return rc;
+    if (int rc = nin_gls_rjacobian_linearize(J, du, db, dB, basis_per_cell, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NIN_OK;
 }
 
 int nin_gls_rjacobian_apply_host(nin_gls_rjacobian *J, int32_t n, const double *dtheta, double *dnode) {
-    if (int rc = apply_ready(J, n, dtheta, dnode)) return rc;
-    nin_grid *g = J->g;
-    HIP_TRY(hipSetDevice(g->d.device));
-    const size_t P = (size_t)g->h.n_points, EM = (size_t)g->h.n_elems * (size_t)J->n_params, k = (size_t)n;
-    DevTmp<double> dt, dv;
-    HIP_TRY(hipMalloc((void **)&dt, std::max<size_t>(EM, 1) * 8 * k));
-    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(P, 1) * 8 * k));
-    HIP_TRY(hipMemcpy(dt, dtheta, EM * 8 * k, hipMemcpyHostToDevice));
-    if (int rc = nin_gls_rjacobian_apply(J, n, dt, dv, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(dnode, dv, P * 8 * k, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    const size_t P = J ? (size_t)J->g->h.n_points : 0, EM = J ? (size_t)J->g->h.n_elems * (size_t)J->n_params : 0;
+    return jacobian_apply_host(J, n, kLinearize, dtheta, EM, dnode, P, nullptr, nullptr, 0, [&](const double *dt, double *dv, double *) {
+        return nin_gls_rjacobian_apply(J, n, dt, dv, nullptr);
+    });
 }
 
 int nin_gls_rjacobian_apply_transpose_host(nin_gls_rjacobian *J, int32_t n, const double *v, double *grad_theta) {
-    if (int rc = apply_ready(J, n, v, grad_theta)) return rc;
-    nin_grid *g = J->g;
-    HIP_TRY(hipSetDevice(g->d.device));
-    const size_t P = (size_t)g->h.n_points, EM = (size_t)g->h.n_elems * (size_t)J->n_params, k = (size_t)n;
-    DevTmp<double> dt, dv;
-    HIP_TRY(hipMalloc((void **)&dv, std::max<size_t>(P, 1) * 8 * k));
-    HIP_TRY(hipMalloc((void **)&dt, std::max<size_t>(EM, 1) * 8 * k));
-    HIP_TRY(hipMemcpy(dv, v, P * 8 * k, hipMemcpyHostToDevice));
-    if (int rc = nin_gls_rjacobian_apply_transpose(J, n, dv, dt, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(grad_theta, dt, EM * 8 * k, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    const size_t P = J ? (size_t)J->g->h.n_points : 0, EM = J ? (size_t)J->g->h.n_elems * (size_t)J->n_params : 0;
+    return jacobian_apply_host(J, n, kLinearize, v, P, grad_theta, EM, nullptr, nullptr, 0, [&](const double *dv, double *dt, double *) {
+        return nin_gls_rjacobian_apply_transpose(J, n, dv, dt, nullptr);
+    });
 }
 
 int nin_gls_rjacobian_fetch_host(nin_gls_rjacobian *J, double *R) {
@@ -164,6 +139,5 @@ int nin_gls_rjacobian_fetch_host(nin_gls_rjacobian *J, double *R) {
     nin_grid *g = J->g;
     if (int rc = on_device(g, kHintKernels)) return rc;
     HIP_TRY(hipSetDevice(g->d.device));
-    HIP_TRY(hipMemcpy(R, J->R, (size_t)g->d.nnz_e * (size_t)J->n_params * 8, hipMemcpyDeviceToHost));
-    return NIN_OK;
+    return dev_fetch(R, J->R, (size_t)g->d.nnz_e * (size_t)J->n_params);
 }

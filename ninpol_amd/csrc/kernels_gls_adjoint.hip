@@ -45,6 +45,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
+#include "diff_mag.hpp"
 #include "gls_adjoint.hpp"
 #include "gls_device_math.hpp"
 #include "launch.hpp"
@@ -89,8 +90,7 @@ struct AdjointIo {
 __device__ __forceinline__ double tangent_dm(const GridView &g, const double *dK, const double *dm, size_t e) {
     if (dm) return dm[e];
     const double *K = g.perm + 9 * e, *d = dK + 9 * e;
-    const double tr = (K[0] + K[4]) + K[8];
-    return (2.0 * (1.0 - 3.0 / tr) * 3.0 / (tr * tr)) * ((d[0] + d[4]) + d[8]);
+    return diff_mag_fold(K) * ((d[0] + d[4]) + d[8]);
 }
 
 // internal face f between cells ca and cb: U = N x T (T from the face centre to the node) and dtau = -ln|U| tau ddm_pick along the
@@ -567,8 +567,7 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
                 // the chain rule folded in where the ten values are: R[pos][m] = sum_k kb[k] B_m[k] + etab fold tr B_m,
                 // one chain of fmas from 0.0, k ascending, the fold term last; fold is nin_jac_fold_kernel's expression of g.perm
                 const double *K = g.perm + 9 * (size_t)cells[i];
-                const double tr = (K[0] + K[4]) + K[8];
-                const double fold = (2.0 * (1.0 - 3.0 / tr) * 3.0 / (tr * tr));
+                const double fold = diff_mag_fold(K);
                 const double *B = io.red_basis ? io.red_basis + (size_t)io.red_stride * (size_t)cells[i] : K;
                 double *o = contrib + (size_t)io.red_m * (size_t)(eb + i);
                 for (int m = 0; m < io.red_m; ++m) {
@@ -615,9 +614,7 @@ __global__ __launch_bounds__(256) void nin_adjoint_gather_kernel(int32_t n_elems
     if (grad_dm) {
         grad_dm[e] = acc[9];
     } else {   // diff_mag = (1 - 3 / tr K)^2 (diff_mag.hpp): d diff_mag / d K_dd = 2 (1 - 3 / tr) 3 / tr^2 on the three diagonal entries
-        const double *K = perm + 9 * (size_t)e;
-        const double tr = (K[0] + K[4]) + K[8];
-        const double t = acc[9] * (2.0 * (1.0 - 3.0 / tr) * 3.0 / (tr * tr));
+        const double t = acc[9] * diff_mag_fold(perm + 9 * (size_t)e);
         acc[0] += t; acc[4] += t; acc[8] += t;
     }
 #pragma unroll
@@ -647,16 +644,16 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
 
 // one bin's nodes through the class of that bin: 1, 2, 4 wavefronts in LDS, 8 over a global-memory slot
 template <bool TAN, bool RED, bool PTS = false>
-int launch_bin_of(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io,
-                  double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
-    if (count <= 0) return 0;
+int launch_bin_of(const GridView &g, int bin, const AdjBinRun &r, int add_neumann, const AdjointIo &io, hipStream_t stream) {
+    if (r.count <= 0) return 0;
     switch (bin) {
-        case 0: return launch_bin<1, true, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 1: return launch_bin<2, true, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 2: return launch_bin<4, true, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 0: return launch_bin<1, true, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 1: return launch_bin<2, true, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 2: return launch_bin<4, true, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
         case 3:
-            if (!scratch || scratch_slots < 1 || scratch_stride * 8 < bytes) return -1;
-            return launch_bin<8, false, TAN, RED, PTS>(g, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+            if (!r.scratch || r.scratch_slots < 1 || r.scratch_stride * 8 < r.bytes) return -1;
+            return launch_bin<8, false, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, r.scratch, r.scratch_stride, r.scratch_slots,
+                                                       stream);
     }
     return -1;
 }
@@ -669,38 +666,34 @@ int launch_adjoint_bytes(const GridView &g, int64_t *bytes, hipStream_t stream) 
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const double *grad_csr,
-                       const double *grad_nws, double *contrib, double *scratch, int64_t scratch_stride, int32_t scratch_slots,
-                       hipStream_t stream) {
+int launch_gls_adjoint(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, const double *grad_csr, const double *grad_nws,
+                       double *contrib, hipStream_t stream) {
     AdjointIo io{};
     io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = contrib;
-    return launch_bin_of<false, false>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+    return launch_bin_of<false, false>(g, bin, run, add_neumann, io, stream);
 }
 
-int launch_gls_adjoint_reduced(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
-                               const double *grad_csr, const double *grad_nws, const AdjointReduce &red, double *reduced, double *scratch,
-                               int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
+int launch_gls_adjoint_reduced(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, const double *grad_csr,
+                               const double *grad_nws, const AdjointReduce &red, double *reduced, hipStream_t stream) {
     AdjointIo io{};
     io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = reduced;
     io.red_basis = red.basis; io.red_stride = (long long)red.stride; io.red_m = red.n_params;
-    return launch_bin_of<false, true>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+    return launch_bin_of<false, true>(g, bin, run, add_neumann, io, stream);
 }
 
-int launch_gls_adjoint_points(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
-                              const double *grad_csr, const double *grad_nws, double *cell_bar, double *face_bar, double *own_bar,
-                              double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
+int launch_gls_adjoint_points(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, const double *grad_csr,
+                              const double *grad_nws, double *cell_bar, double *face_bar, double *own_bar, hipStream_t stream) {
     AdjointIo io{};
     io.grad_csr = grad_csr; io.grad_nws = grad_nws; io.contrib = cell_bar; io.pts_face = face_bar; io.pts_own = own_bar;
-    return launch_bin_of<false, false, true>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+    return launch_bin_of<false, false, true>(g, bin, run, add_neumann, io, stream);
 }
 
-int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, int32_t n_tangents,
-                       const double *tangent_perm, const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz,
-                       double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream) {
+int launch_gls_tangent(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, int32_t n_tangents, const double *tangent_perm,
+                       const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz, hipStream_t stream) {
     AdjointIo io{};
     io.n_tan = n_tangents; io.tan_perm = tangent_perm; io.tan_dm = tangent_diff_mag; io.tan_csr = tangent_csr; io.tan_nws = tangent_nws;
     io.nnz = (long long)nnz;
-    return launch_bin_of<true, false>(g, bin, nodes, count, bytes, add_neumann, io, scratch, scratch_stride, scratch_slots, stream);
+    return launch_bin_of<true, false>(g, bin, run, add_neumann, io, stream);
 }
 
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,

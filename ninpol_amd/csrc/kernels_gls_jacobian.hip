@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
+#include "diff_mag.hpp"
 #include "launch.hpp"
 #include "wave_ops.hpp"
 
@@ -58,9 +59,7 @@ __global__ __launch_bounds__(256) void nin_jac_seed_kernel(const int32_t *__rest
 __global__ __launch_bounds__(256) void nin_jac_fold_kernel(int32_t n_elems, const double *__restrict__ perm, double *__restrict__ fold) {
     const int32_t e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n_elems) return;
-    const double *K = perm + 9 * (size_t)e;
-    const double tr = (K[0] + K[4]) + K[8];
-    fold[e] = (2.0 * (1.0 - 3.0 / tr) * 3.0 / (tr * tr));
+    fold[e] = diff_mag_fold(perm + 9 * (size_t)e);
 }
 
 template <int NT>

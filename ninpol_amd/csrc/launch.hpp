@@ -117,15 +117,24 @@ int launch_sddmm(const GridView &g, const double *u, const double *v, int32_t k,
 
 // the GLS adjoint (kernels_gls_adjoint.hip, gls_adjoint.hpp), all DEVICE pointers.
 // launch_adjoint_bytes: bytes[p] = adj_node_bytes of node p.
-// launch_gls_adjoint: the nodes of one bin (`bytes`: the largest slot among them; bin 3: `scratch` holds scratch_slots slots of
+// launch_gls_adjoint: the nodes of one bin (run.bytes: the largest slot among them; bin 3: run.scratch holds scratch_slots slots of
 //   scratch_stride doubles); grad_csr [nnz_esup] = dL/d stored weights, grad_nws [n_points] = dL/d neumann_ws or null; writes the ten
 //   values (Kbar[9], etabar) of every (node, cell) pair of the listed nodes to contrib [nnz_esup][10].
 // launch_adjoint_gather: grad_perm [E][9] (and grad_diff_mag [E]; null: its term folded into the diagonal of grad_perm through the
 //   resident g.perm) = per cell the sum of its nodes' slots, ascending node id, through the transpose index (cell_ptr, cell_pos)
+// AdjBinRun: what every launch of the adjoint kernel on one bin takes from the grid -- the bin's nodes, the largest slot among them, the
+//   scratch slots of bin 3 (abi_apply.hip makes one from DeviceGrid::adj_bin[b] and adj_scratch*)
+struct AdjBinRun {
+    const int32_t *nodes;
+    int32_t count;
+    int64_t bytes;
+    double *scratch;
+    int64_t scratch_stride;
+    int32_t scratch_slots;
+};
 int launch_adjoint_bytes(const GridView &g, int64_t *bytes, hipStream_t stream);
-int launch_gls_adjoint(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const double *grad_csr,
-                       const double *grad_nws, double *contrib, double *scratch, int64_t scratch_stride, int32_t scratch_slots,
-                       hipStream_t stream);
+int launch_gls_adjoint(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, const double *grad_csr, const double *grad_nws,
+                       double *contrib, hipStream_t stream);
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,
                           double *grad_diff_mag, hipStream_t stream);
 // launch_gls_adjoint_reduced: the same launch with the chain rule of perm_e = sum_m theta_(e,m) B_(e,m) folded in where the
@@ -137,26 +146,23 @@ struct AdjointReduce {
     const double *basis;
     int64_t stride;
 };
-int launch_gls_adjoint_reduced(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
-                               const double *grad_csr, const double *grad_nws, const AdjointReduce &red, double *reduced, double *scratch,
-                               int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
+int launch_gls_adjoint_reduced(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, const double *grad_csr,
+                               const double *grad_nws, const AdjointReduce &red, double *reduced, hipStream_t stream);
 // launch_gls_adjoint_points: the same launch in the kernel's coordinate mode -- every listed node writes cbar of its cells to
 //   cell_bar [nnz_esup][3], (fcbar, Nbar) of its faces to face_bar [nnz_fsup][6] and xbar_own to own_bar [P][3], zeros where the forward
 //   has its zero row.  launch_shape_gather (kernels_gls_shape.hip) then takes them through the geometry to the vertices: inpofa [F][4] as
 //   launch_update_geometry reads it, the transpose index (cell_ptr, cell_pos), face_slot [F][4][3] its own scratch; cell_bar is
 //   overwritten; grad_points [P][3] holds xbar_own on entry and dL/d coords on return (3-D grids only)
-int launch_gls_adjoint_points(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann,
-                              const double *grad_csr, const double *grad_nws, double *cell_bar, double *face_bar, double *own_bar,
-                              double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
+int launch_gls_adjoint_points(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, const double *grad_csr,
+                              const double *grad_nws, double *cell_bar, double *face_bar, double *own_bar, hipStream_t stream);
 int launch_shape_gather(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos, double *cell_bar,
                         const double *face_bar, double *face_slot, double *grad_points, hipStream_t stream);
 // launch_gls_tangent: the same kernel's tangent mode on the nodes of one bin -- n_tangents directions tangent_perm [n_tangents][E][9]
 //   (tangent_diff_mag [n_tangents][E], or null: folded from the resident g.perm) -> the directional derivative of the stored weights,
 //   tangent_csr [n_tangents][nnz] in esup position, and of neumann_ws, tangent_nws [n_tangents][P] or null; every row of every listed
 //   node is written
-int launch_gls_tangent(const GridView &g, int bin, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, int32_t n_tangents,
-                       const double *tangent_perm, const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz,
-                       double *scratch, int64_t scratch_stride, int32_t scratch_slots, hipStream_t stream);
+int launch_gls_tangent(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, int32_t n_tangents, const double *tangent_perm,
+                       const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz, hipStream_t stream);
 
 // the GLS Jacobian kept and applied (kernels_gls_jacobian.hip), all DEVICE pointers; contrib [nnz_esup][10] as an adjoint
 // launch with grad_csr = u[esup] left it, fold [E] = d diff_mag / d K_dd at the linearisation point.

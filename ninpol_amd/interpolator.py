@@ -13,12 +13,14 @@ import time
 
 import numpy as np
 import scipy.sparse as sp
-import scipy.sparse.linalg as spla
 
 from . import _args as A
 from . import _lib
 from . import topology as T
+from ._lib import _ptr, _vp
 from .grid import Grid
+from .jacobian import (GlsJacobian, GlsReducedJacobian, PermeabilityJacobian, REDUCED_N_PARAMS,  # noqa: F401  (their import path of old)
+                       ReducedPermeabilityJacobian, _check_n_params, reduced_basis)
 
 _pinned = _lib.PinnedPool()
 
@@ -29,10 +31,6 @@ def pinned_pool():
 
 DTYPE_I = np.int64
 DTYPE_F = np.float64
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 class _MethodPlugin:
@@ -853,6 +851,27 @@ class Interpolator:
         _lib.check(_lib.load().nin_apply_transpose_fields_host(g._h, _lib.METHOD_ID[method], _ptr(v), k, _ptr(out)))
         return out
 
+    def _derivative_inputs(self, variable, lead_shape, cell_values, beside):
+        """(u, k) of a derivative call: `cell_values` as a contiguous float64 array of shape lead_shape + (n_elems,) -- default: the cell
+        variable `variable` itself, for each of the k = 1 or lead_shape[0] leading entries -- where lead_shape () or (k,) is that of the
+        caller's own array, which `beside` names in the ValueError (None: there is none, and one field only)."""
+        E = self.grid.n_elems
+        k = lead_shape[0] if lead_shape else 1
+        if cell_values is None:
+            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:E]
+            return np.ascontiguousarray(np.broadcast_to(u, (k, E)) if beside else u, dtype=DTYPE_F), k
+        u = np.ascontiguousarray(cell_values, dtype=DTYPE_F)
+        if u.shape != tuple(lead_shape) + (E,):
+            raise ValueError(f"cell_values must have shape {tuple(lead_shape) + (E,)} beside {beside}, not {u.shape}." if beside else
+                             f"cell_values must have shape ({E},), not {u.shape}.")
+        return u, k
+
+    def _gls_tables_to_device(self, variable):
+        """the grid on the device with the GLS tables of `variable`: the last step before a derivative's native call"""
+        if self.grid.device < 0:
+            self.grid.to_device(self.device)
+        _upload_fields(self.grid, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+
     def permeability_gradient(self, variable, node_values, cell_values=None):
         """The derivative of `<v, W u>` with respect to the permeability, for the GLS matrix W that `apply(variable, "gls")` uses (the
         `+ neumann_ws[row]` included): `node_values` = v, one node array (n_points,) or k of them as (k, n_points); `cell_values` = u,
@@ -866,18 +885,8 @@ class Interpolator:
         v = np.ascontiguousarray(node_values, dtype=DTYPE_F)
         if v.shape != (g.n_points,) and not (v.ndim == 2 and v.shape[0] >= 1 and v.shape[1] == g.n_points):
             raise ValueError(f"node_values must have shape ({g.n_points},) or (k, {g.n_points}), not {v.shape}.")
-        k = 1 if v.ndim == 1 else v.shape[0]
-        if cell_values is None:
-            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
-            u = np.ascontiguousarray(np.broadcast_to(u, (k, g.n_elems)), dtype=DTYPE_F)
-        else:
-            u = np.ascontiguousarray(cell_values, dtype=DTYPE_F)
-            if u.shape != v.shape[:-1] + (g.n_elems,):
-                raise ValueError(f"cell_values must have shape {v.shape[:-1] + (g.n_elems,)} beside node_values of shape {v.shape}, "
-                                 f"not {u.shape}.")
-        if g.device < 0:
-            g.to_device(self.device)
-        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        u, k = self._derivative_inputs(variable, v.shape[:-1], cell_values, f"node_values of shape {v.shape}")
+        self._gls_tables_to_device(variable)
         out = np.empty((g.n_elems, 3, 3), dtype=DTYPE_F)
         _lib.check(_lib.load().nin_gls_permeability_gradient_host(g._h, _ptr(v), _ptr(u), k, _ptr(out)))
         return out
@@ -897,18 +906,8 @@ class Interpolator:
         v = np.ascontiguousarray(node_values, dtype=DTYPE_F)
         if v.shape != (g.n_points,) and not (v.ndim == 2 and v.shape[0] >= 1 and v.shape[1] == g.n_points):
             raise ValueError(f"node_values must have shape ({g.n_points},) or (k, {g.n_points}), not {v.shape}.")
-        k = 1 if v.ndim == 1 else v.shape[0]
-        if cell_values is None:
-            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
-            u = np.ascontiguousarray(np.broadcast_to(u, (k, g.n_elems)), dtype=DTYPE_F)
-        else:
-            u = np.ascontiguousarray(cell_values, dtype=DTYPE_F)
-            if u.shape != v.shape[:-1] + (g.n_elems,):
-                raise ValueError(f"cell_values must have shape {v.shape[:-1] + (g.n_elems,)} beside node_values of shape {v.shape}, "
-                                 f"not {u.shape}.")
-        if g.device < 0:
-            g.to_device(self.device)
-        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        u, k = self._derivative_inputs(variable, v.shape[:-1], cell_values, f"node_values of shape {v.shape}")
+        self._gls_tables_to_device(variable)
         out = np.empty((g.n_points, 3), dtype=DTYPE_F)
         _lib.check(_lib.load().nin_gls_points_gradient_host(g._h, _ptr(v), _ptr(u), k, _ptr(out)))
         return out
@@ -929,17 +928,8 @@ class Interpolator:
         if d.shape != (g.n_elems, 3, 3) and not (d.ndim == 4 and d.shape[0] >= 1 and d.shape[1:] == (g.n_elems, 3, 3)):
             raise ValueError(f"dK must have shape ({g.n_elems}, 3, 3) or (k, {g.n_elems}, 3, 3), not {d.shape}.")
         lead = d.shape[:-3]
-        k = 1 if d.ndim == 3 else d.shape[0]
-        if cell_values is None:
-            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
-            u = np.ascontiguousarray(np.broadcast_to(u, (k, g.n_elems)), dtype=DTYPE_F)
-        else:
-            u = np.ascontiguousarray(cell_values, dtype=DTYPE_F)
-            if u.shape != lead + (g.n_elems,):
-                raise ValueError(f"cell_values must have shape {lead + (g.n_elems,)} beside dK of shape {d.shape}, not {u.shape}.")
-        if g.device < 0:
-            g.to_device(self.device)
-        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        u, k = self._derivative_inputs(variable, lead, cell_values, f"dK of shape {d.shape}")
+        self._gls_tables_to_device(variable)
         out = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
         nws = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
         _lib.check(_lib.load().nin_gls_permeability_tangent_host(g._h, _ptr(d), _ptr(u), k, _ptr(out), _ptr(nws)))
@@ -966,21 +956,13 @@ class Interpolator:
         g = self.grid
         if basis is not None:
             M, B, per_cell = reduced_basis(basis, g.n_elems)
-        if cell_values is None:
-            u = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
-        else:
-            u = cell_values
-        u = np.ascontiguousarray(u, dtype=DTYPE_F)
-        if u.shape != (g.n_elems,):
-            raise ValueError(f"cell_values must have shape ({g.n_elems},), not {u.shape}.")
+        u, _ = self._derivative_inputs(variable, (), cell_values, None)
         b = None
         if neumann_values is not None:
             b = np.ascontiguousarray(neumann_values, dtype=DTYPE_F)
             if b.shape != (g.n_points,):
                 raise ValueError(f"neumann_values must have shape ({g.n_points},), not {b.shape}.")
-        if g.device < 0:
-            g.to_device(self.device)
-        _upload_fields(g, "gls", self.cells_data, self.points_data, self.variable_to_index, variable)
+        self._gls_tables_to_device(variable)
         if basis is not None:
             rjac = GlsReducedJacobian(g, M)
             _lib.check(_lib.load().nin_gls_rjacobian_linearize_host(rjac._handle(), _ptr(u), _ptr(b), _ptr(B), int(per_cell)))
@@ -1127,18 +1109,23 @@ class DevicePlan:
         _lib.check(_lib.load().nin_sddmm_device(self.grid._h, ctypes.c_void_p(u_ptr), ctypes.c_void_p(values_ptr), int(n_fields),
                                                 ctypes.c_void_p(grad_csr_ptr), ctypes.c_void_p(stream)))
 
+    def _gls_derivative(self, name, why="do not depend on the permeability", current=True):
+        """what the derivative launches begin with: GLS only -- a plan of another method raises, it does not return zeros -- and the
+        tables current (a linearisation leaves that to the object's relinearize, after its own argument checks)"""
+        if self.method != "gls":
+            raise ValueError(f"the weights of '{self.method}' {why}: {name} is GLS only")
+        if current:
+            self.ensure_current()
+
     def launch_weights_backward(self, grad_csr_ptr, grad_perm_ptr, grad_diff_mag_ptr=0, grad_neumann_ws_ptr=0, stream=0, add_neumann=True):
         """The GLS weights differentiated with respect to the permeability (nin_gls_weights_backward_device): grad_csr [nnz_esup] =
         dL/d csr_data of a `launch(..., add_neumann)` (grad_neumann_ws [n_points] = dL/d neumann_ws, 0: none) -> grad_perm
         [n_elems][9] = dL/dK at what is resident now.  With grad_diff_mag [n_elems] the table's diff_mag counts as an independent
         input and gets its own gradient; with 0 its chain is folded into grad_perm.  Asynchronous on `stream` after the first call on
         a grid (which makes the bins and buffers -- 80 bytes per entry of esup -- and synchronises).  Only GLS depends on K."""
-        if self.method != "gls":
-            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: launch_weights_backward is GLS only")
-        self.ensure_current()
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_weights_backward_device(self.grid._h, int(bool(add_neumann)), vp(grad_csr_ptr), vp(grad_neumann_ws_ptr),
-                                                               vp(grad_perm_ptr), vp(grad_diff_mag_ptr), ctypes.c_void_p(stream)))
+        self._gls_derivative("launch_weights_backward")
+        _lib.check(_lib.load().nin_gls_weights_backward_device(self.grid._h, int(bool(add_neumann)), _vp(grad_csr_ptr), _vp(grad_neumann_ws_ptr),
+                                                               _vp(grad_perm_ptr), _vp(grad_diff_mag_ptr), ctypes.c_void_p(stream)))
 
     def launch_weights_backward_points(self, grad_csr_ptr, grad_points_ptr, grad_neumann_ws_ptr=0, stream=0, add_neumann=True):
         """The GLS weights differentiated with respect to the node coordinates (nin_gls_weights_backward_points_device): grad_csr
@@ -1148,13 +1135,9 @@ class DevicePlan:
         Asynchronous on `stream` after the first call on a grid (which makes the bins and buffers -- 24 bytes per entry of esup, 48 per
         entry of fsup, 96 per face -- and synchronises); deterministic.  3-D grids.  GLS only: the IDW and LS weights depend on the
         coordinates too, but their derivative is not provided -- a plan of those methods raises instead of returning zeros."""
-        if self.method != "gls":
-            raise ValueError(f"the weights of '{self.method}' do depend on the node coordinates, but they are not differentiated here: "
-                             "launch_weights_backward_points is GLS only")
-        self.ensure_current()
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_weights_backward_points_device(self.grid._h, int(bool(add_neumann)), vp(grad_csr_ptr),
-                                                                      vp(grad_neumann_ws_ptr), vp(grad_points_ptr), ctypes.c_void_p(stream)))
+        self._gls_derivative("launch_weights_backward_points", "do depend on the node coordinates, but they are not differentiated here")
+        _lib.check(_lib.load().nin_gls_weights_backward_points_device(self.grid._h, int(bool(add_neumann)), _vp(grad_csr_ptr),
+                                                                      _vp(grad_neumann_ws_ptr), _vp(grad_points_ptr), ctypes.c_void_p(stream)))
 
     def launch_weights_tangent(self, tangent_perm_ptr, tangent_csr_ptr, n_tangents=1, tangent_diff_mag_ptr=0, tangent_neumann_ws_ptr=0, stream=0,
                                add_neumann=True):
@@ -1165,12 +1148,9 @@ class DevicePlan:
         direction; with 0 its chain is folded from the resident K.  All directions share one factorisation per node.  Every entry of
         the outputs is written.  Asynchronous on `stream` after the first call on a grid (which makes the bins and synchronises); no
         contribution buffer is allocated.  Only GLS depends on K."""
-        if self.method != "gls":
-            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: launch_weights_tangent is GLS only")
-        self.ensure_current()
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_weights_tangent_device(self.grid._h, int(bool(add_neumann)), int(n_tangents), vp(tangent_perm_ptr),
-                                                              vp(tangent_diff_mag_ptr), vp(tangent_csr_ptr), vp(tangent_neumann_ws_ptr),
+        self._gls_derivative("launch_weights_tangent")
+        _lib.check(_lib.load().nin_gls_weights_tangent_device(self.grid._h, int(bool(add_neumann)), int(n_tangents), _vp(tangent_perm_ptr),
+                                                              _vp(tangent_diff_mag_ptr), _vp(tangent_csr_ptr), _vp(tangent_neumann_ws_ptr),
                                                               ctypes.c_void_p(stream)))
 
     def linearize(self, u_ptr, neumann_values_ptr=0, stream=0):
@@ -1178,8 +1158,7 @@ class DevicePlan:
         what is resident now, for the cell field u [n_elems] (and node values b [n_points], 0: none), both device pointers.  One launch
         of the adjoint kernel (the cost of one launch_weights_backward); its launch_jvp / launch_vjp then stream 80 bytes per entry of
         esup instead of factorising every node again.  The object owns its buffers (80 bytes per entry of esup).  Only GLS depends on K."""
-        if self.method != "gls":
-            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: linearize is GLS only")
+        self._gls_derivative("linearize", current=False)
         if not u_ptr:
             raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
         J = GlsJacobian(self.grid, plan=self)
@@ -1192,329 +1171,13 @@ class DevicePlan:
         basis_ptr: device pointer to B [n_elems][n_params][9] (basis_per_cell) or [n_params][9] shared by every cell, read by this call
         only; 0 with n_params = 1: the resident permeability itself (theta a log-multiplier).  The adjoint kernel contracts with the
         basis where it has the ten values of a (node, cell) pair: the 80-byte buffer of linearize() is never written or allocated."""
-        if self.method != "gls":
-            raise ValueError(f"the weights of '{self.method}' do not depend on the permeability: linearize_reduced is GLS only")
+        self._gls_derivative("linearize_reduced", current=False)
         if not u_ptr:
             raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
         _check_n_params(n_params, basis_ptr)
         J = GlsReducedJacobian(self.grid, n_params, plan=self)
         J.relinearize(u_ptr, basis_ptr, basis_per_cell, neumann_values_ptr, stream)
         return J
-
-
-class GlsJacobian:
-    """The sparse Jacobian of `F(K) = W(K) u + neumann_ws(K) * b` with respect to the permeability at ONE linearisation point, resident
-    on the device (nin_gls_jacobian): `contrib_ptr` [nnz_esup][10] holds, per (node, cell) pair in esup position, dF_p / d
-    perm_e[0..9) and dF_p / d diff_mag_e; `fold_ptr` [n_elems] the derivative of the table's diff_mag = (1 - 3 / tr K)^2 there.
-    `launch_jvp` is J . dK, `launch_vjp` is J^T . v, each one streaming pass over the buffer per four directions, asynchronous on the
-    caller's stream, bitwise reproducible.  Later updates of the permeability, the points or the flags do not change the answers: the
-    object is the Jacobian where it was linearised (`stamp`; `is_current()` says whether the grid is still there).  `relinearize`
-    moves it.  Made by DevicePlan.linearize(); its device buffers (`nbytes`) are its own: a launch_weights_backward in between does not
-    disturb it."""
-
-    def __init__(self, grid, plan=None):
-        self.grid, self.plan = grid, plan
-        self._h = None
-        h = ctypes.c_void_p()
-        _lib.check(_lib.load().nin_gls_jacobian_create(grid._h, ctypes.byref(h)))
-        self._h = h
-        self.nbytes = 80 * int(grid.nnz_esup) + 8 * int(grid.n_elems)
-
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("this GlsJacobian was released")
-        return self._h
-
-    def relinearize(self, u_ptr, neumann_values_ptr=0, stream=0):
-        """Linearise again, at what is resident now, for u [n_elems] (and b [n_points], 0: none), device pointers: what a fresh
-        DevicePlan.linearize would hold, bit for bit, in the buffers this object already owns."""
-        if self.plan is not None:
-            self.plan.ensure_current()
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_jacobian_linearize(self._handle(), vp(u_ptr), vp(neumann_values_ptr), ctypes.c_void_p(stream)))
-
-    def launch_jvp(self, dperm_ptr, out_ptr, n=1, ddm_ptr=0, stream=0):
-        """J . dK for n directions (nin_gls_jacobian_apply): dperm [n][n_elems][9] -> out [n][n_points], every entry written.  ddm
-        [n][n_elems]: the table's diff_mag as an independent input with its own direction; 0: its chain folded, at the permeability of
-        the linearisation.  Asynchronous on `stream`."""
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_jacobian_apply(self._handle(), int(n), vp(dperm_ptr), vp(ddm_ptr), vp(out_ptr), ctypes.c_void_p(stream)))
-
-    def launch_vjp(self, v_ptr, grad_perm_ptr, n=1, grad_dm_ptr=0, stream=0):
-        """J^T . v for n node fields (nin_gls_jacobian_apply_transpose): v [n][n_points] -> grad_perm [n][n_elems][9] (and grad_dm
-        [n][n_elems]; 0: folded into the diagonal of grad_perm).  v = 1 is launch_weights_backward(grad_csr = u[esup], grad_neumann_ws =
-        b) at the linearisation point, bit for bit.  Asynchronous on `stream` (the first call on a grid without the transpose index
-        builds it and synchronises)."""
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_jacobian_apply_transpose(self._handle(), int(n), vp(v_ptr), vp(grad_perm_ptr), vp(grad_dm_ptr),
-                                                                ctypes.c_void_p(stream)))
-
-    def _buffers(self):
-        c, f = ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.check(_lib.load().nin_gls_jacobian_contrib(self._handle(), ctypes.byref(c), ctypes.byref(f)))
-        return int(c.value or 0), int(f.value or 0)
-
-    @property
-    def contrib_ptr(self):
-        return self._buffers()[0]
-
-    @property
-    def fold_ptr(self):
-        return self._buffers()[1]
-
-    @property
-    def stamp(self):
-        """the grid's (field_updates, geometry_updates, flag_updates) at the last linearisation"""
-        s = np.zeros(3, dtype=np.int64)
-        _lib.check(_lib.load().nin_gls_jacobian_stamp(self._handle(), _ptr(s)))
-        return tuple(int(x) for x in s)
-
-    def is_current(self):
-        """Is the grid's resident permeability, geometry and flag set still the one this object was linearised at?  (Device-side updates
-        count; launch_jvp / launch_vjp answer for the linearisation point either way.)"""
-        g = self.grid
-        return self.stamp == (g.field_updates, g.geometry_updates, g.flag_updates)
-
-    def fetch(self):
-        """(contrib (nnz_esup, 10), fold (n_elems,)) on the host (waits for the device)"""
-        g = self.grid
-        contrib, fold = np.empty((int(g.nnz_esup), 10), dtype=DTYPE_F), np.empty(int(g.n_elems), dtype=DTYPE_F)
-        _lib.check(_lib.load().nin_gls_jacobian_fetch_host(self._handle(), _ptr(contrib), _ptr(fold)))
-        return contrib, fold
-
-    def release(self):
-        """Give the device buffers back (waits for the device); the object is unusable afterwards."""
-        if self._h is not None:
-            _lib.load().nin_gls_jacobian_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:       # interpreter shutdown
-            pass
-
-
-REDUCED_N_PARAMS = (1, 3, 6)
-
-
-def _check_n_params(n_params, basis_ptr=1):
-    if isinstance(n_params, bool) or not isinstance(n_params, (int, np.integer)) or int(n_params) not in REDUCED_N_PARAMS:
-        raise ValueError(f"n_params must be one of {REDUCED_N_PARAMS}, not {n_params!r}")
-    if not basis_ptr and int(n_params) != 1:
-        raise ValueError(f"basis_ptr = 0 (the resident permeability as the basis) needs n_params = 1, not {n_params}")
-
-
-def reduced_basis(basis, n_elems):
-    """Interpolator.permeability_jacobian's `basis` as (M, B, per_cell): B a C-contiguous float64 array (n_elems, M, 9) (per_cell) or
-    (M, 9) (shared by every cell), or None for "scale" (M = 1: the resident permeability itself)."""
-    if isinstance(basis, str):
-        if basis == "scale":
-            return 1, None, False
-        if basis == "diagonal":
-            B = np.zeros((3, 3, 3), dtype=DTYPE_F)
-            for d in range(3):
-                B[d, d, d] = 1.0
-            return 3, B.reshape(3, 9), False
-        if basis == "symmetric":
-            B = np.zeros((6, 3, 3), dtype=DTYPE_F)
-            for m, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
-                B[m, i, j] = B[m, j, i] = 1.0
-            return 6, B.reshape(6, 9), False
-        raise ValueError(f"basis must be 'scale', 'diagonal', 'symmetric' or an ndarray, not '{basis}'")
-    if not isinstance(basis, np.ndarray):
-        raise ValueError(f"basis must be 'scale', 'diagonal', 'symmetric' or a float64 ndarray, not {type(basis).__name__}")
-    if basis.dtype != DTYPE_F:
-        raise ValueError(f"basis must be float64, not {basis.dtype} (no silent cast)")
-    E = int(n_elems)
-    shape = tuple(basis.shape)
-    per_cell = len(shape) >= 3 and shape[0] == E and shape[2:] in ((9,), (3, 3))     # (the last axis tells (E, M, 9) from (M, 3, 3))
-    shared = len(shape) >= 2 and shape[1:] in ((9,), (3, 3))
-    M = shape[1] if per_cell else shape[0] if shared else None
-    if M not in REDUCED_N_PARAMS:
-        raise ValueError(f"basis must have shape ({E}, M, 9), ({E}, M, 3, 3), (M, 9) or (M, 3, 3) with M in {REDUCED_N_PARAMS}, not {shape}")
-    return M, np.ascontiguousarray(basis).reshape((E, M, 9) if per_cell else (M, 9)), per_cell
-
-
-class GlsReducedJacobian:
-    """The Jacobian of `F = W(K) u + neumann_ws(K) * b` in a reduced parametrisation of the permeability, perm_e = sum_m theta_(e,m)
-    B_(e,m) with `n_params` = M = 1, 3 or 6 per cell, at ONE linearisation point, resident on the device (nin_gls_rjacobian, DESIGN.md
-    4.14): `buffer_ptr` [nnz_esup][M] holds dF_p / d theta_(e,m) per (node, cell) pair in esup position, the diff_mag chain folded --
-    `nbytes` = 8 M nnz_esup, where a GlsJacobian keeps 80 nnz_esup.  `launch_jvp` is J_theta . dtheta, `launch_vjp` J_theta^T . v, one
-    streaming pass per four directions each, asynchronous, bitwise reproducible.  Later updates of the permeability, the points or the
-    flags do not change the answers (`stamp`, `is_current()`); `relinearize` moves it, to another basis too.  Made by
-    DevicePlan.linearize_reduced(); its device buffer is its own."""
-
-    def __init__(self, grid, n_params=1, plan=None):
-        _check_n_params(n_params)
-        self.grid, self.plan, self.n_params = grid, plan, int(n_params)
-        self._h = None
-        h = ctypes.c_void_p()
-        _lib.check(_lib.load().nin_gls_rjacobian_create(grid._h, self.n_params, ctypes.byref(h)))
-        self._h = h
-        self.nbytes = 8 * self.n_params * int(grid.nnz_esup)
-
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("this GlsReducedJacobian was released")
-        return self._h
-
-    def relinearize(self, u_ptr, basis_ptr=0, basis_per_cell=True, neumann_values_ptr=0, stream=0):
-        """Linearise again, at what is resident now, for u [n_elems], the basis (see DevicePlan.linearize_reduced) and b [n_points]
-        (0: none), device pointers: what a fresh linearize_reduced would hold, bit for bit, in the buffer this object already owns."""
-        _check_n_params(self.n_params, basis_ptr)
-        if self.plan is not None:
-            self.plan.ensure_current()
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_rjacobian_linearize(self._handle(), vp(u_ptr), vp(neumann_values_ptr), vp(basis_ptr),
-                                                           int(bool(basis_per_cell)), ctypes.c_void_p(stream)))
-
-    def launch_jvp(self, dtheta_ptr, out_ptr, n=1, stream=0):
-        """J_theta . dtheta for n directions (nin_gls_rjacobian_apply): dtheta [n][n_elems][M] -> out [n][n_points], every entry
-        written.  Asynchronous on `stream`."""
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_rjacobian_apply(self._handle(), int(n), vp(dtheta_ptr), vp(out_ptr), ctypes.c_void_p(stream)))
-
-    def launch_vjp(self, v_ptr, grad_theta_ptr, n=1, stream=0):
-        """J_theta^T . v for n node fields (nin_gls_rjacobian_apply_transpose): v [n][n_points] -> grad_theta [n][n_elems][M].
-        Asynchronous on `stream` (the first call on a grid without the transpose index builds it and synchronises)."""
-        vp = lambda a: ctypes.c_void_p(a) if a else None
-        _lib.check(_lib.load().nin_gls_rjacobian_apply_transpose(self._handle(), int(n), vp(v_ptr), vp(grad_theta_ptr), ctypes.c_void_p(stream)))
-
-    @property
-    def buffer_ptr(self):
-        r, m = ctypes.c_void_p(), ctypes.c_int(0)
-        _lib.check(_lib.load().nin_gls_rjacobian_buffer(self._handle(), ctypes.byref(r), ctypes.byref(m)))
-        return int(r.value or 0)
-
-    @property
-    def stamp(self):
-        """the grid's (field_updates, geometry_updates, flag_updates) at the last linearisation"""
-        s = np.zeros(3, dtype=np.int64)
-        _lib.check(_lib.load().nin_gls_rjacobian_stamp(self._handle(), _ptr(s)))
-        return tuple(int(x) for x in s)
-
-    def is_current(self):
-        """Is the grid's resident permeability, geometry and flag set still the one this object was linearised at?"""
-        g = self.grid
-        return self.stamp == (g.field_updates, g.geometry_updates, g.flag_updates)
-
-    def fetch(self):
-        """R (nnz_esup, M) on the host (waits for the device)"""
-        R = np.empty((int(self.grid.nnz_esup), self.n_params), dtype=DTYPE_F)
-        _lib.check(_lib.load().nin_gls_rjacobian_fetch_host(self._handle(), _ptr(R)))
-        return R
-
-    def release(self):
-        """Give the device buffer back (waits for the device); the object is unusable afterwards."""
-        if self._h is not None:
-            _lib.load().nin_gls_rjacobian_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:       # interpreter shutdown
-            pass
-
-
-class ReducedPermeabilityJacobian(spla.LinearOperator):
-    """Interpolator.permeability_jacobian(basis=...)'s result: the (n_points, M n_elems) Jacobian of `apply(variable, "gls")`'s node
-    values in the parameters theta of perm_e = sum_m theta_(e,m) B_(e,m) (column M e + m), as a scipy LinearOperator over a
-    GlsReducedJacobian: numpy in and out, host-synchronous, one launch per matvec / rmatvec and one per batched matmat / rmatmat."""
-
-    def __init__(self, jac):
-        g = jac.grid
-        self.jacobian = jac
-        self._P, self._E, self._M = int(g.n_points), int(g.n_elems), int(jac.n_params)
-        super().__init__(dtype=np.dtype(DTYPE_F), shape=(self._P, self._M * self._E))
-
-    def _jvp(self, d):        # d (k, M E) -> (k, P)
-        d = np.ascontiguousarray(d, dtype=DTYPE_F)
-        out = np.empty((len(d), self._P), dtype=DTYPE_F)
-        _lib.check(_lib.load().nin_gls_rjacobian_apply_host(self.jacobian._handle(), len(d), _ptr(d), _ptr(out)))
-        return out
-
-    def _vjp(self, v):        # v (k, P) -> (k, M E)
-        v = np.ascontiguousarray(v, dtype=DTYPE_F)
-        out = np.empty((len(v), self._M * self._E), dtype=DTYPE_F)
-        _lib.check(_lib.load().nin_gls_rjacobian_apply_transpose_host(self.jacobian._handle(), len(v), _ptr(v), _ptr(out)))
-        return out
-
-    def _matvec(self, x):
-        return self._jvp(np.asarray(x).reshape(1, -1))[0]
-
-    def _rmatvec(self, x):
-        return self._vjp(np.asarray(x).reshape(1, -1))[0]
-
-    def _matmat(self, X):
-        return self._jvp(np.asarray(X).T).T
-
-    def _rmatmat(self, X):
-        return self._vjp(np.asarray(X).T).T
-
-    def to_scipy(self):
-        """The explicit csr_matrix (n_points, M n_elems) from the fetched buffer: row p, column M e + m."""
-        g = self.jacobian.grid
-        R = self.jacobian.fetch()
-        esup = np.asarray(g.esup).astype(np.int64)
-        cols = self._M * esup[:, None] + np.arange(self._M)
-        indptr = self._M * np.asarray(g.esup_ptr).astype(np.int64)
-        return sp.csr_matrix((R.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)
-
-    def release(self):
-        self.jacobian.release()
-
-
-class PermeabilityJacobian(spla.LinearOperator):
-    """Interpolator.permeability_jacobian's result: the (n_points, 9 n_elems) Jacobian of `apply(variable, "gls")`'s node values in
-    the permeability table (column 9 e + k is entry k of cell e's row-major 3 x 3 tensor; the diff_mag chain folded), as a
-    scipy LinearOperator over a GlsJacobian: numpy in and out, host-synchronous, one launch per matvec / rmatvec and one per batched
-    matmat / rmatmat."""
-
-    def __init__(self, jac):
-        g = jac.grid
-        self.jacobian = jac
-        self._P, self._E = int(g.n_points), int(g.n_elems)
-        super().__init__(dtype=np.dtype(DTYPE_F), shape=(self._P, 9 * self._E))
-
-    def _jvp(self, d):        # d (k, 9 E) -> (k, P)
-        d = np.ascontiguousarray(d, dtype=DTYPE_F)
-        out = np.empty((len(d), self._P), dtype=DTYPE_F)
-        _lib.check(_lib.load().nin_gls_jacobian_apply_host(self.jacobian._handle(), len(d), _ptr(d), None, _ptr(out)))
-        return out
-
-    def _vjp(self, v):        # v (k, P) -> (k, 9 E)
-        v = np.ascontiguousarray(v, dtype=DTYPE_F)
-        out = np.empty((len(v), 9 * self._E), dtype=DTYPE_F)
-        _lib.check(_lib.load().nin_gls_jacobian_apply_transpose_host(self.jacobian._handle(), len(v), _ptr(v), _ptr(out), None))
-        return out
-
-    def _matvec(self, x):
-        return self._jvp(np.asarray(x).reshape(1, -1))[0]
-
-    def _rmatvec(self, x):
-        return self._vjp(np.asarray(x).reshape(1, -1))[0]
-
-    def _matmat(self, X):
-        return self._jvp(np.asarray(X).T).T
-
-    def _rmatmat(self, X):
-        return self._vjp(np.asarray(X).T).T
-
-    def to_scipy(self):
-        """The explicit csr_matrix (n_points, 9 n_elems) from the fetched buffer: row p, column 9 e + k, the fold applied."""
-        g = self.jacobian.grid
-        contrib, fold = self.jacobian.fetch()
-        esup = np.asarray(g.esup).astype(np.int64)
-        data = contrib[:, :9].copy()
-        data[:, (0, 4, 8)] += (contrib[:, 9] * fold[esup])[:, None]
-        cols = 9 * esup[:, None] + np.arange(9)
-        indptr = 9 * np.asarray(g.esup_ptr).astype(np.int64)
-        return sp.csr_matrix((data.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)
-
-    def release(self):
-        self.jacobian.release()
 
 
 class HostMatrix:

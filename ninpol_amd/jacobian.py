@@ -1,0 +1,301 @@
+"""The GLS Jacobian in the permeability as objects the caller keeps: GlsJacobian and GlsReducedJacobian over the
+C objects nin_gls_jacobian / nin_gls_rjacobian (device pointers, asynchronous), and the scipy LinearOperators
+Interpolator.permeability_jacobian returns over them (numpy, host-synchronous).  What the two of each pair share is written once:
+_KeptJacobian -- the handle, the stamp, the lifetime -- and _JacobianOperator -- the two host products.  ninpol_amd.interpolator
+re-exports every public name."""
+import ctypes
+
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+from . import _lib
+from ._lib import _ptr, _vp
+
+DTYPE_F = np.float64
+
+
+class _KeptJacobian:
+    """What GlsJacobian and GlsReducedJacobian share: the C object `_C`_create made, its stamp, and giving it back."""
+
+    _C = None       # the prefix of the C entry points: "nin_gls_jacobian" or "nin_gls_rjacobian"
+
+    def _create(self, grid, plan, *args):
+        self.grid, self.plan = grid, plan
+        self._h = None
+        h = ctypes.c_void_p()
+        _lib.check(self._c("create")(grid._h, *args, ctypes.byref(h)))
+        self._h = h
+
+    def _c(self, name):
+        return getattr(_lib.load(), f"{self._C}_{name}")
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError(f"this {type(self).__name__} was released")
+        return self._h
+
+    def _linearize(self, *args):
+        if self.plan is not None:
+            self.plan.ensure_current()
+        _lib.check(self._c("linearize")(self._handle(), *args))
+
+    @property
+    def stamp(self):
+        """the grid's (field_updates, geometry_updates, flag_updates) at the last linearisation"""
+        s = np.zeros(3, dtype=np.int64)
+        _lib.check(self._c("stamp")(self._handle(), _ptr(s)))
+        return tuple(int(x) for x in s)
+
+    def is_current(self):
+        """Is the grid's resident permeability, geometry and flag set still the one this object was linearised at?  (Device-side updates
+        count; launch_jvp / launch_vjp answer for the linearisation point either way.)"""
+        g = self.grid
+        return self.stamp == (g.field_updates, g.geometry_updates, g.flag_updates)
+
+    def release(self):
+        """Give the device buffers back (waits for the device); the object is unusable afterwards."""
+        if self._h is not None:
+            self._c("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:       # interpreter shutdown
+            pass
+
+
+class GlsJacobian(_KeptJacobian):
+    """The sparse Jacobian of `F(K) = W(K) u + neumann_ws(K) * b` with respect to the permeability at ONE linearisation point, resident
+    on the device (nin_gls_jacobian): `contrib_ptr` [nnz_esup][10] holds, per (node, cell) pair in esup position, dF_p / d
+    perm_e[0..9) and dF_p / d diff_mag_e; `fold_ptr` [n_elems] the derivative of the table's diff_mag = (1 - 3 / tr K)^2 there.
+    `launch_jvp` is J . dK, `launch_vjp` is J^T . v, each one streaming pass over the buffer per four directions, asynchronous on the
+    caller's stream, bitwise reproducible.  Later updates of the permeability, the points or the flags do not change the answers: the
+    object is the Jacobian where it was linearised (`stamp`; `is_current()` says whether the grid is still there).  `relinearize`
+    moves it.  Made by DevicePlan.linearize(); its device buffers (`nbytes`) are its own: a launch_weights_backward in between does not
+    disturb it."""
+
+    _C = "nin_gls_jacobian"
+
+    def __init__(self, grid, plan=None):
+        self._create(grid, plan)
+        self.nbytes = 80 * int(grid.nnz_esup) + 8 * int(grid.n_elems)
+
+    def relinearize(self, u_ptr, neumann_values_ptr=0, stream=0):
+        """Linearise again, at what is resident now, for u [n_elems] (and b [n_points], 0: none), device pointers: what a fresh
+        DevicePlan.linearize would hold, bit for bit, in the buffers this object already owns."""
+        self._linearize(_vp(u_ptr), _vp(neumann_values_ptr), ctypes.c_void_p(stream))
+
+    def launch_jvp(self, dperm_ptr, out_ptr, n=1, ddm_ptr=0, stream=0):
+        """J . dK for n directions (nin_gls_jacobian_apply): dperm [n][n_elems][9] -> out [n][n_points], every entry written.  ddm
+        [n][n_elems]: the table's diff_mag as an independent input with its own direction; 0: its chain folded, at the permeability of
+        the linearisation.  Asynchronous on `stream`."""
+        _lib.check(_lib.load().nin_gls_jacobian_apply(self._handle(), int(n), _vp(dperm_ptr), _vp(ddm_ptr), _vp(out_ptr), ctypes.c_void_p(stream)))
+
+    def launch_vjp(self, v_ptr, grad_perm_ptr, n=1, grad_dm_ptr=0, stream=0):
+        """J^T . v for n node fields (nin_gls_jacobian_apply_transpose): v [n][n_points] -> grad_perm [n][n_elems][9] (and grad_dm
+        [n][n_elems]; 0: folded into the diagonal of grad_perm).  v = 1 is launch_weights_backward(grad_csr = u[esup], grad_neumann_ws =
+        b) at the linearisation point, bit for bit.  Asynchronous on `stream` (the first call on a grid without the transpose index
+        builds it and synchronises)."""
+        _lib.check(_lib.load().nin_gls_jacobian_apply_transpose(self._handle(), int(n), _vp(v_ptr), _vp(grad_perm_ptr), _vp(grad_dm_ptr),
+                                                                ctypes.c_void_p(stream)))
+
+    def _buffers(self):
+        c, f = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(_lib.load().nin_gls_jacobian_contrib(self._handle(), ctypes.byref(c), ctypes.byref(f)))
+        return int(c.value or 0), int(f.value or 0)
+
+    @property
+    def contrib_ptr(self):
+        return self._buffers()[0]
+
+    @property
+    def fold_ptr(self):
+        return self._buffers()[1]
+
+    def fetch(self):
+        """(contrib (nnz_esup, 10), fold (n_elems,)) on the host (waits for the device)"""
+        g = self.grid
+        contrib, fold = np.empty((int(g.nnz_esup), 10), dtype=DTYPE_F), np.empty(int(g.n_elems), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_jacobian_fetch_host(self._handle(), _ptr(contrib), _ptr(fold)))
+        return contrib, fold
+
+
+REDUCED_N_PARAMS = (1, 3, 6)
+
+
+def _check_n_params(n_params, basis_ptr=1):
+    if isinstance(n_params, bool) or not isinstance(n_params, (int, np.integer)) or int(n_params) not in REDUCED_N_PARAMS:
+        raise ValueError(f"n_params must be one of {REDUCED_N_PARAMS}, not {n_params!r}")
+    if not basis_ptr and int(n_params) != 1:
+        raise ValueError(f"basis_ptr = 0 (the resident permeability as the basis) needs n_params = 1, not {n_params}")
+
+
+def reduced_basis(basis, n_elems):
+    """Interpolator.permeability_jacobian's `basis` as (M, B, per_cell): B a C-contiguous float64 array (n_elems, M, 9) (per_cell) or
+    (M, 9) (shared by every cell), or None for "scale" (M = 1: the resident permeability itself)."""
+    if isinstance(basis, str):
+        if basis == "scale":
+            return 1, None, False
+        if basis == "diagonal":
+            B = np.zeros((3, 3, 3), dtype=DTYPE_F)
+            for d in range(3):
+                B[d, d, d] = 1.0
+            return 3, B.reshape(3, 9), False
+        if basis == "symmetric":
+            B = np.zeros((6, 3, 3), dtype=DTYPE_F)
+            for m, (i, j) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+                B[m, i, j] = B[m, j, i] = 1.0
+            return 6, B.reshape(6, 9), False
+        raise ValueError(f"basis must be 'scale', 'diagonal', 'symmetric' or an ndarray, not '{basis}'")
+    if not isinstance(basis, np.ndarray):
+        raise ValueError(f"basis must be 'scale', 'diagonal', 'symmetric' or a float64 ndarray, not {type(basis).__name__}")
+    if basis.dtype != DTYPE_F:
+        raise ValueError(f"basis must be float64, not {basis.dtype} (no silent cast)")
+    E = int(n_elems)
+    shape = tuple(basis.shape)
+    per_cell = len(shape) >= 3 and shape[0] == E and shape[2:] in ((9,), (3, 3))     # (the last axis tells (E, M, 9) from (M, 3, 3))
+    shared = len(shape) >= 2 and shape[1:] in ((9,), (3, 3))
+    M = shape[1] if per_cell else shape[0] if shared else None
+    if M not in REDUCED_N_PARAMS:
+        raise ValueError(f"basis must have shape ({E}, M, 9), ({E}, M, 3, 3), (M, 9) or (M, 3, 3) with M in {REDUCED_N_PARAMS}, not {shape}")
+    return M, np.ascontiguousarray(basis).reshape((E, M, 9) if per_cell else (M, 9)), per_cell
+
+
+class GlsReducedJacobian(_KeptJacobian):
+    """The Jacobian of `F = W(K) u + neumann_ws(K) * b` in a reduced parametrisation of the permeability, perm_e = sum_m theta_(e,m)
+    B_(e,m) with `n_params` = M = 1, 3 or 6 per cell, at ONE linearisation point, resident on the device (nin_gls_rjacobian, DESIGN.md
+    4.14): `buffer_ptr` [nnz_esup][M] holds dF_p / d theta_(e,m) per (node, cell) pair in esup position, the diff_mag chain folded --
+    `nbytes` = 8 M nnz_esup, where a GlsJacobian keeps 80 nnz_esup.  `launch_jvp` is J_theta . dtheta, `launch_vjp` J_theta^T . v, one
+    streaming pass per four directions each, asynchronous, bitwise reproducible.  Later updates of the permeability, the points or the
+    flags do not change the answers (`stamp`, `is_current()`); `relinearize` moves it, to another basis too.  Made by
+    DevicePlan.linearize_reduced(); its device buffer is its own."""
+
+    _C = "nin_gls_rjacobian"
+
+    def __init__(self, grid, n_params=1, plan=None):
+        _check_n_params(n_params)
+        self.n_params = int(n_params)
+        self._create(grid, plan, self.n_params)
+        self.nbytes = 8 * self.n_params * int(grid.nnz_esup)
+
+    def relinearize(self, u_ptr, basis_ptr=0, basis_per_cell=True, neumann_values_ptr=0, stream=0):
+        """Linearise again, at what is resident now, for u [n_elems], the basis (see DevicePlan.linearize_reduced) and b [n_points]
+        (0: none), device pointers: what a fresh linearize_reduced would hold, bit for bit, in the buffer this object already owns."""
+        _check_n_params(self.n_params, basis_ptr)
+        self._linearize(_vp(u_ptr), _vp(neumann_values_ptr), _vp(basis_ptr), int(bool(basis_per_cell)), ctypes.c_void_p(stream))
+
+    def launch_jvp(self, dtheta_ptr, out_ptr, n=1, stream=0):
+        """J_theta . dtheta for n directions (nin_gls_rjacobian_apply): dtheta [n][n_elems][M] -> out [n][n_points], every entry
+        written.  Asynchronous on `stream`."""
+        _lib.check(_lib.load().nin_gls_rjacobian_apply(self._handle(), int(n), _vp(dtheta_ptr), _vp(out_ptr), ctypes.c_void_p(stream)))
+
+    def launch_vjp(self, v_ptr, grad_theta_ptr, n=1, stream=0):
+        """J_theta^T . v for n node fields (nin_gls_rjacobian_apply_transpose): v [n][n_points] -> grad_theta [n][n_elems][M].
+        Asynchronous on `stream` (the first call on a grid without the transpose index builds it and synchronises)."""
+        _lib.check(_lib.load().nin_gls_rjacobian_apply_transpose(self._handle(), int(n), _vp(v_ptr), _vp(grad_theta_ptr), ctypes.c_void_p(stream)))
+
+    @property
+    def buffer_ptr(self):
+        r, m = ctypes.c_void_p(), ctypes.c_int(0)
+        _lib.check(_lib.load().nin_gls_rjacobian_buffer(self._handle(), ctypes.byref(r), ctypes.byref(m)))
+        return int(r.value or 0)
+
+    def fetch(self):
+        """R (nnz_esup, M) on the host (waits for the device)"""
+        R = np.empty((int(self.grid.nnz_esup), self.n_params), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_rjacobian_fetch_host(self._handle(), _ptr(R)))
+        return R
+
+
+class _JacobianOperator(spla.LinearOperator):
+    """What PermeabilityJacobian and ReducedPermeabilityJacobian share: a (n_points, cols n_elems) operator over a kept Jacobian whose two
+    products are the *_apply_host and *_apply_transpose_host entry points of that object, one launch for k directions each."""
+
+    _diff_mag = ()      # the optional diff_mag argument of the full Jacobian's two entry points: (None,) there, its chain folded
+
+    def __init__(self, jac, cols):
+        g = jac.grid
+        self.jacobian = jac
+        self._P, self._E, self._cols = int(g.n_points), int(g.n_elems), int(cols)
+        super().__init__(dtype=np.dtype(DTYPE_F), shape=(self._P, self._cols * self._E))
+
+    def _jvp(self, d):        # d (k, cols E) -> (k, P)
+        d = np.ascontiguousarray(d, dtype=DTYPE_F)
+        out = np.empty((len(d), self._P), dtype=DTYPE_F)
+        _lib.check(self.jacobian._c("apply_host")(self.jacobian._handle(), len(d), _ptr(d), *self._diff_mag, _ptr(out)))
+        return out
+
+    def _vjp(self, v):        # v (k, P) -> (k, cols E)
+        v = np.ascontiguousarray(v, dtype=DTYPE_F)
+        out = np.empty((len(v), self._cols * self._E), dtype=DTYPE_F)
+        _lib.check(self.jacobian._c("apply_transpose_host")(self.jacobian._handle(), len(v), _ptr(v), _ptr(out), *self._diff_mag))
+        return out
+
+    def _matvec(self, x):
+        return self._jvp(np.asarray(x).reshape(1, -1))[0]
+
+    def _rmatvec(self, x):
+        return self._vjp(np.asarray(x).reshape(1, -1))[0]
+
+    def _matmat(self, X):
+        return self._jvp(np.asarray(X).T).T
+
+    def _rmatmat(self, X):
+        return self._vjp(np.asarray(X).T).T
+
+    def release(self):
+        self.jacobian.release()
+
+
+class ReducedPermeabilityJacobian(_JacobianOperator):
+    """Interpolator.permeability_jacobian(basis=...)'s result: the (n_points, M n_elems) Jacobian of `apply(variable, "gls")`'s node
+    values in the parameters theta of perm_e = sum_m theta_(e,m) B_(e,m) (column M e + m), as a scipy LinearOperator over a
+    GlsReducedJacobian: numpy in and out, host-synchronous, one launch per matvec / rmatvec and one per batched matmat / rmatmat."""
+
+    def __init__(self, jac):
+        super().__init__(jac, jac.n_params)
+        self._M = self._cols
+
+    # (scipy's hooks and release named on the class itself, as tests/test_gls_reduced_jacobian_host.py looks for them)
+    _matvec, _rmatvec, _matmat, _rmatmat = (_JacobianOperator._matvec, _JacobianOperator._rmatvec, _JacobianOperator._matmat,
+                                            _JacobianOperator._rmatmat)
+    release = _JacobianOperator.release
+
+    def to_scipy(self):
+        """The explicit csr_matrix (n_points, M n_elems) from the fetched buffer: row p, column M e + m."""
+        g = self.jacobian.grid
+        R = self.jacobian.fetch()
+        esup = np.asarray(g.esup).astype(np.int64)
+        cols = self._M * esup[:, None] + np.arange(self._M)
+        indptr = self._M * np.asarray(g.esup_ptr).astype(np.int64)
+        return sp.csr_matrix((R.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)
+
+
+class PermeabilityJacobian(_JacobianOperator):
+    """Interpolator.permeability_jacobian's result: the (n_points, 9 n_elems) Jacobian of `apply(variable, "gls")`'s node values in
+    the permeability table (column 9 e + k is entry k of cell e's row-major 3 x 3 tensor; the diff_mag chain folded), as a
+    scipy LinearOperator over a GlsJacobian: numpy in and out, host-synchronous, one launch per matvec / rmatvec and one per batched
+    matmat / rmatmat."""
+
+    _diff_mag = (None,)
+
+    def __init__(self, jac):
+        super().__init__(jac, 9)
+
+    # (scipy's hooks and release named on the class itself, as tests/test_gls_jacobian_host.py looks for them)
+    _matvec, _rmatvec, _matmat, _rmatmat = (_JacobianOperator._matvec, _JacobianOperator._rmatvec, _JacobianOperator._matmat,
+                                            _JacobianOperator._rmatmat)
+    release = _JacobianOperator.release
+
+    def to_scipy(self):
+        """The explicit csr_matrix (n_points, 9 n_elems) from the fetched buffer: row p, column 9 e + k, the fold applied."""
+        g = self.jacobian.grid
+        contrib, fold = self.jacobian.fetch()
+        esup = np.asarray(g.esup).astype(np.int64)
+        data = contrib[:, :9].copy()
+        data[:, (0, 4, 8)] += (contrib[:, 9] * fold[esup])[:, None]
+        cols = 9 * esup[:, None] + np.arange(9)
+        indptr = 9 * np.asarray(g.esup_ptr).astype(np.int64)
+        return sp.csr_matrix((data.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)

@@ -12,15 +12,18 @@ parts of tests/test_gpu_composite.py (between them all 22 plan kernels have node
 for which mfx_boundary must have nodes and neumann_ws non-zero entries -- otherwise the boundary-face rows are never computed.
 Routes per mesh: nin_weights_host over all nodes and over a shuffled subset (GLS, IDW and LS), interpolate() pipelined
 (NIN_E2E_MIN_NODES=512), apply() fused and unfused, apply_transpose() with 3 fields, permeability_gradient() and
-permeability_tangent() along two directions.  On the meshes of LOCAL a
+permeability_tangent() along two directions.  On the meshes of LOCAL also points_gradient() and permeability_jacobian() -- in the
+permeability and in the bases "scale", "diagonal", "symmetric" and one per-cell (n_elems, 3, 9) array, each with neumann_values:
+matmat / rmatmat over 5 columns, matvec, rmatvec and to_scipy().data -- and a
 scatter of permeability, of points and of Neumann flags (device tensors), each followed by the dirty launch -- weights and neumann_ws
 after each -- and by HostMatrix.update(), whose matrix must in the end be a fresh interpolate()'s in the same child.  On the composite
 mesh the all-nodes route runs again under each switch set of SWITCHES (NIN_GLS_NO_SMALL is among them because only without the small-node
 kernels does the one-wavefront block kernel, block1, get nodes on these meshes; block_only and global_scratch send EVERY node through
-kernels_gls_block.hip and kernels_gls.hip), and on the mixed mesh the gradient and the tangent run again under ADJ_SWITCHES (every
+kernels_gls_block.hip and kernels_gls.hip), and on the mixed mesh the derivative routes run again under ADJ_SWITCHES (every
 system of kernels_gls_adjoint.hip in global-memory scratch).
-Exit status 1 if an array or a plan differs, if one of the plan kernels has no nodes on any mesh, or if under ADJ_SWITCHES a node of
-the adjoint is left outside the global-scratch bin (Grid.gls_adjoint_plan(): looked at, not compared).  Needs a GPU; reads nothing
+Exit status 1 if an array or a plan differs, if one of the plan kernels has no nodes on any mesh, if the Neumann Delaunay mesh leaves
+one of the adjoint's three LDS bins without nodes, or if under ADJ_SWITCHES a node of the adjoint is left outside the global-scratch
+bin (Grid.gls_adjoint_plan(): looked at, not compared).  Needs a GPU; reads nothing
 outside the repository."""
 import json
 import os
@@ -105,12 +108,27 @@ def local_routes(I, A):
     A["local.interp.data"], A["local.interp.nws"] = W.data, n
 
 
-def adjoint_routes(I, A):
-    """permeability_gradient() for 3 node fields, permeability_tangent() along 2 directions (fixed seeds)"""
+def adjoint_routes(I, A, kept=False):
+    """permeability_gradient() for 3 node fields, permeability_tangent() along 2 directions (fixed seeds); kept: points_gradient() for 3
+    node fields too, and permeability_jacobian() with neumann_values in the permeability and in every kind of basis -- matmat over 5
+    directions and rmatmat over 5 node fields (5 crosses the chunk of 4 and leaves a chunk of 1), matvec, rmatvec, to_scipy().data"""
     import numpy as np
     P, E = int(I.grid.n_points), int(I.grid.n_elems)
     A["perm_gradient.g"] = I.permeability_gradient("u", np.random.default_rng(8).random((3, P)))
     A["perm_tangent.v"], A["perm_tangent.nws"] = I.permeability_tangent("u", np.random.default_rng(9).standard_normal((2, E, 3, 3)))
+    if not kept:
+        return
+    A["points_gradient.g"] = I.points_gradient("u", np.random.default_rng(10).random((3, P)))
+    b = np.random.default_rng(12).standard_normal(P)
+    bases = {"perm": None, "scale": "scale", "diagonal": "diagonal", "symmetric": "symmetric",
+             "per_cell": np.random.default_rng(13).uniform(-1.0, 1.0, (E, 3, 9))}
+    for name, basis in bases.items():
+        J = I.permeability_jacobian("u", neumann_values=b, basis=basis)
+        D, V = np.random.default_rng(14).standard_normal((J.shape[1], 5)), np.random.default_rng(15).standard_normal((P, 5))
+        A[f"jacobian.{name}.matmat"], A[f"jacobian.{name}.rmatmat"] = J.matmat(D), J.rmatmat(V)
+        A[f"jacobian.{name}.matvec"], A[f"jacobian.{name}.rmatvec"] = J.matvec(D[:, 0]), J.rmatvec(V[:, 0])
+        A[f"jacobian.{name}.scipy"] = J.to_scipy().data
+        J.release()
 
 
 def child(mesh_name, route_set, out):
@@ -149,11 +167,12 @@ def child(mesh_name, route_set, out):
         os.environ["NIN_APPLY_NO_FUSION"] = "1"                # (the library reads this switch at every apply call)
         A["apply_unfused.v"], A["apply_unfused.nws"] = I.apply("u", "gls", values=np.random.default_rng(6).random((3, int(I.grid.n_elems))))
         A["apply_transpose.x"] = I.apply_transpose("u", "gls", np.random.default_rng(8).random((3, P)))
-        adjoint_routes(I, A)
+        adjoint_routes(I, A, kept=mesh_name in LOCAL)
+        A["__adjoint_bins__"] = np.array(list(I.grid.gls_adjoint_plan().values()))   # (not compared: see main())
         if mesh_name in LOCAL:
             local_routes(I, A)
     elif route_set in ADJ_SWITCHES:
-        adjoint_routes(I, A)
+        adjoint_routes(I, A, kept=True)
         A["__adjoint_bins__"] = np.array(list(I.grid.gls_adjoint_plan().values()))   # (not compared: main() wants every node in the last bin)
     plan = {k: int(v) for k, v in I.grid.gls_plan().items()}
     np.savez(out, __plan__=np.array(json.dumps(plan)), __kernels__=np.array(json.dumps(list(I.grid.PLAN_KERNELS))),
@@ -202,6 +221,8 @@ def main():
             if route_set in ADJ_SWITCHES and (np.count_nonzero(b["__adjoint_bins__"][:-1]) or not b["__adjoint_bins__"][-1]):
                 unmet.append(f"{label}: the adjoint's nodes are not all in the global-scratch bin")
             if mesh_name == "delaunay_neumann":
+                if not all(b["__adjoint_bins__"][:3]):
+                    unmet.append(f"the Neumann Delaunay mesh leaves an LDS bin of the adjoint empty: {b['__adjoint_bins__'].tolist()}")
                 if not pb.get("mfx_boundary", 0) > 0:
                     unmet.append("the Neumann Delaunay mesh has no mfx_boundary nodes")
                 if not np.count_nonzero(b["all.nws"]) > 0:
@@ -218,7 +239,8 @@ def main():
     print(f"plan kernels with nodes on at least one mesh ({len(covered)} of {len(kernels)}): " + ", ".join(covered))
     print("plan kernels NOT covered by these meshes: " + (", ".join(missing) or "none"))
     print("coverage conditions: " + ("; ".join(unmet) if unmet else
-                                     "the Neumann Delaunay mesh has mfx_boundary nodes and non-zero neumann_ws, the forced adjoint runs in global scratch"))
+                                     "the Neumann Delaunay mesh has mfx_boundary nodes, non-zero neumann_ws and nodes in each LDS bin of the adjoint, "
+                                     "the forced adjoint runs in global scratch"))
     ok = not bad and not missing and not unmet
     print("RESULT: " + ("all equal, every plan kernel covered" if ok else "DIFFERENT" if bad else "all equal, but a coverage condition above is NOT met"))
     return 0 if ok else 1
