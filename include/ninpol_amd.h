@@ -467,8 +467,8 @@ int nin_gls_permeability_tangent_host(nin_grid *g, const double *tangent_permeab
  * faces and the node's own position fill its system, and all of them follow the node coordinates (nin_grid_update_points*).  Given
  * the gradient of a scalar L with respect to the STORED weights these calls return dL/d point_coords, for shape fitting, shape
  * optimisation and error-driven mesh motion -- one backward pass instead of two launches per coordinate.  3-D grids, GLS only: IDW
- * and LS depend on the coordinates as well but are not differentiated.  Not provided: a tangent (forward mode) or a kept Jacobian in
- * the coordinates, dirty-row / local-motion variants, 2-D meshes, the sharded path, the Neumann values.
+ * and LS depend on the coordinates as well but are not differentiated.  Not provided: a kept Jacobian in the coordinates, dirty-row /
+ * local-motion variants, 2-D meshes, the sharded path, the Neumann values.  The tangent (forward mode) follows below.
  *
  * nin_gls_weights_backward_points_device: dev_grad_csr, dev_grad_neumann_ws and add_neumann as in nin_gls_weights_backward_device;
  *   writes dev_grad_points [n_points][3] = dL/d point_coords at what is resident NOW (geometry, flags, K).  The derivative is that
@@ -493,6 +493,34 @@ int nin_gls_weights_backward_points_device(nin_grid *g, int add_neumann, const d
                                            double *dev_grad_points, void *stream);
 int nin_gls_points_gradient_host(nin_grid *g, const double *node_values, const double *cell_values, int32_t n_fields,
                                  double *grad_points);
+
+/* ---- the GLS weights along a direction of the node coordinates: a shape tangent ---------------------------------------------------
+ * The forward derivative in the coordinates, for a solver that moves the mesh (ALE, r-adaptivity, Newton-Krylov on a mesh-motion
+ * residual, a Gauss-Newton shape fit) and for sensitivities along a few design directions: dW = (dW/dX) . dX without differencing
+ * two nin_grid_update_points* + weight launches.  3-D grids, GLS only, as the shape adjoint above.
+ *
+ * nin_gls_weights_tangent_points_device: dev_tangent_points [n_tangents][n_points][3] = the directions dX.  Writes dev_tangent_csr
+ *   [n_tangents][nnz_esup] and dev_tangent_neumann_ws [n_tangents][n_points] (NULL: not wanted) as nin_gls_weights_tangent_device
+ *   does, at what is resident NOW (geometry, flags, K): every entry is written, zeros for the nodes the forward gives the zero row
+ *   and for neumann_ws of the nodes that are not Neumann nodes.  The derivative is that of the real-valued model: the float32 casts
+ *   of the stored normals count as the identity.  Two small kernels take dX through the geometry (d centroid per cell, d face
+ *   centre and d unit normal per face: 24 bytes per cell and 48 per face, per direction; nin_grid_scalar
+ *   "gls_shape_tangent_bytes": what is allocated now, grown to the largest n_tangents seen, kept until nin_grid_release_scratch),
+ *   then the adjoint's kernel in its tangent mode factors every node once for all directions.  No contribution buffer, no
+ *   transpose index, no atomics: two calls agree bit for bit and a batch equals its directions one by one.  With the shape
+ *   adjoint's dL/dX = Xbar:  <grad_csr, tangent_csr> + <grad_neumann_ws, tangent_neumann_ws> = <Xbar, dX>.
+ *   The first call makes the adjoint's bins and the connectivity copies of nin_grid_update_points* if they are not there (and
+ *   synchronises `stream`); a call with more directions than any before reallocates the two buffers (hipFree waits for the
+ *   device).  Errors as nin_gls_weights_tangent_device (NULL: grid, dev_tangent_points, dev_tangent_csr; n_tangents < 1), and
+ *   NIN_EINVAL for a grid that is not 3-D; a refused call writes nothing.  NIN_GLS_ADJ_FORCE_GLOBAL and NIN_GLS_ADJ_ONLY as there.
+ * nin_gls_points_tangent_host: the host-pointer counterpart, the sibling of nin_gls_permeability_tangent_host -- direction f meets
+ *   field f: node_values[f] = dW_f . cell_values[f] along tangent_points[f] (add_neumann = 1), neumann_ws[f] the tangent of
+ *   neumann_ws; tangent_points [n_fields][n_points][3], cell_values [n_fields][n_elems], node_values and neumann_ws
+ *   [n_fields][n_points]; synchronous.  Errors as the calls it makes (the tangent, then nin_spmv_device). */
+int nin_gls_weights_tangent_points_device(nin_grid *g, int add_neumann, int32_t n_tangents, const double *dev_tangent_points,
+                                          double *dev_tangent_csr, double *dev_tangent_neumann_ws, void *stream);
+int nin_gls_points_tangent_host(nin_grid *g, const double *tangent_points, const double *cell_values, int32_t n_fields,
+                                double *node_values, double *neumann_ws);
 
 /* ---- the GLS Jacobian in the permeability, kept on the device: linearise once, apply J and J^T many times ----------------------
  * The two calls above repeat the dense QR of every node at every call.  A Krylov solver applies J . dK or J^T . v once per iteration

@@ -35,7 +35,8 @@ UNITS = [
     ("kernels_gls_quad4.hip", "hipcc", []),
     # the GLS weights differentiated with respect to the permeability: a dense QR per node kept for two solves, and the gather
     ("kernels_gls_adjoint.hip", "hipcc", []),
-    # the adjoint in the node coordinates, from the records of the adjoint kernel's coordinate mode to the vertices: three gathers
+    # the adjoint in the node coordinates, from the records of the adjoint kernel's coordinate mode to the vertices: three gathers;
+    # and the same geometry read forwards for the tangent in the coordinates: a direction of the nodes to cells and faces
     ("kernels_gls_shape.hip", "hipcc", []),
     # the Jacobian that one adjoint launch leaves in a contribution buffer, applied: J . dK node-major, J^T . v cell-major
     ("kernels_gls_jacobian.hip", "hipcc", []),

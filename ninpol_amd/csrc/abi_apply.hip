@@ -161,6 +161,9 @@ void nin::release_adjoint_state(DeviceGrid &d) {
     dev_release(d, d.shape_cell);
     dev_release(d, d.shape_face);
     dev_release(d, d.shape_slot);
+    dev_release(d, d.shape_tan_cell);
+    dev_release(d, d.shape_tan_face);
+    d.shape_tan_n = 0;
     dev_release(d, d.adj_scratch);
     d.adj_scratch_stride = 0;
     d.adj_scratch_slots = 0;
@@ -367,6 +370,60 @@ int nin_gls_permeability_tangent_host(nin_grid *g, const double *tangent_permeab
     if (!rc) rc = dev_stage(dn, nullptr, P * k);
     // dW as apply() uses W (`+ neumann_ws[row]` included): add_neumann = 1, the diff_mag chain folded; direction f meets field f
     if (!rc) rc = nin_gls_weights_tangent_device(g, 1, n_fields, dk, nullptr, dw, dn, nullptr);
+    for (size_t f = 0; f < k && !rc; ++f) rc = nin_spmv_device(g, dw.p + f * (size_t)d.nnz_e, du.p + f * E, 1, dv.p + f * P, nullptr);
+    if (!rc) rc = dev_fetch(node_values, dv, P * k);
+    return rc ? rc : dev_fetch(neumann_ws, dn, P * k);
+}
+
+// ---- the GLS tangent in the node coordinates: d(stored weights) along a direction dX ---------------------------------
+// dC and (dFc, dN) of n_tangents directions: 24 bytes per cell and 48 per face, per direction; grown to the largest batch seen
+static int ensure_shape_tangent_buffers(DeviceGrid &d, int32_t n_tangents) {
+    if (d.shape_tan_cell && d.shape_tan_face && n_tangents <= d.shape_tan_n) return NIN_OK;
+    dev_release(d, d.shape_tan_cell);
+    dev_release(d, d.shape_tan_face);
+    d.shape_tan_n = 0;
+    int rc = dev_alloc(d, &d.shape_tan_cell, (size_t)n_tangents * (size_t)std::max<int32_t>(d.v.n_elems, 1) * 3);
+    if (!rc) rc = dev_alloc(d, &d.shape_tan_face, (size_t)n_tangents * (size_t)std::max<int32_t>(d.v.n_faces, 1) * 6);
+    if (rc) { dev_release(d, d.shape_tan_cell); dev_release(d, d.shape_tan_face); return rc; }
+    d.shape_tan_n = n_tangents;
+    return NIN_OK;
+}
+
+int nin_gls_weights_tangent_points_device(nin_grid *g, int add_neumann, int32_t n_tangents, const double *dev_tangent_points,
+                                          double *dev_tangent_csr, double *dev_tangent_neumann_ws, void *stream_) {
+    if (!g || !dev_tangent_points || !dev_tangent_csr) return fail(NIN_EINVAL, "NULL argument");
+    if (n_tangents < 1) return fail(NIN_EINVAL, "n_tangents must be >= 1");
+    DeviceGrid &d = g->d;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    int rc = derivative_ready(g, stream, true);
+    if (!rc) rc = ensure_update_inputs(g);   // inpoel and inpofa, as the update path brings them
+    if (!rc) rc = ensure_shape_tangent_buffers(d, n_tangents);
+    if (rc) return rc;
+    rc = launch_shape_tangent_geometry(d.v, d.up_inpoel, d.up_inpofa, n_tangents, dev_tangent_points, d.shape_tan_cell, d.shape_tan_face, stream);
+    // (per-bin timing, as in the K tangent: the other bins' rows are not written)
+    if (!rc) rc = for_each_adjoint_bin(d, adjoint_only_from_env(), [&](int b, const AdjBinRun &run) {
+        return launch_gls_tangent_points(d.v, b, run, add_neumann ? 1 : 0, n_tangents, dev_tangent_points, d.shape_tan_cell, d.shape_tan_face,
+                                         dev_tangent_csr, dev_tangent_neumann_ws, d.nnz_e, stream);
+    });
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
+int nin_gls_points_tangent_host(nin_grid *g, const double *tangent_points, const double *cell_values, int32_t n_fields, double *node_values,
+                                double *neumann_ws) {
+    if (!g || !tangent_points || !cell_values || !node_values || !neumann_ws) return fail(NIN_EINVAL, "NULL argument");
+    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
+    DeviceGrid &d = g->d;
+    if (int rc = derivative_ready(g, nullptr, true)) return rc;
+    const size_t P = (size_t)g->h.n_points, E = (size_t)g->h.n_elems, k = (size_t)n_fields;
+    DevTmp<double> dx, du, dw, dv, dn;
+    int rc = dev_stage(dx, tangent_points, P * 3 * k);
+    if (!rc) rc = dev_stage(du, cell_values, E * k);
+    if (!rc) rc = dev_stage(dw, nullptr, (size_t)d.nnz_e * k);
+    if (!rc) rc = dev_stage(dv, nullptr, P * k);
+    if (!rc) rc = dev_stage(dn, nullptr, P * k);
+    // dW as apply() uses W (`+ neumann_ws[row]` included): add_neumann = 1; direction f meets field f
+    if (!rc) rc = nin_gls_weights_tangent_points_device(g, 1, n_fields, dx, dw, dn, nullptr);
     for (size_t f = 0; f < k && !rc; ++f) rc = nin_spmv_device(g, dw.p + f * (size_t)d.nnz_e, du.p + f * E, 1, dv.p + f * P, nullptr);
     if (!rc) rc = dev_fetch(node_values, dv, P * k);
     return rc ? rc : dev_fetch(neumann_ws, dn, P * k);

@@ -226,6 +226,8 @@ int64_t nin_grid_scalar(const nin_grid *g, const char *name) {
     if (n == "gls_adjoint_contrib_bytes") return g->d.adj_contrib ? std::max<int64_t>(g->d.nnz_e, 1) * 80 : 0;
     if (n == "gls_shape_contrib_bytes")
         return g->d.shape_cell ? std::max<int64_t>(g->d.nnz_e, 1) * 24 + std::max<int64_t>(g->d.nnz_f, 1) * 48 + std::max<int64_t>(g->d.v.n_faces, 1) * 96 : 0;
+    if (n == "gls_shape_tangent_bytes")
+        return g->d.shape_tan_cell ? (int64_t)g->d.shape_tan_n * (std::max<int64_t>(h.n_elems, 1) * 24 + std::max<int64_t>(g->d.v.n_faces, 1) * 48) : 0;
     return -1;
 }
 

@@ -118,6 +118,11 @@ struct DeviceGrid {
     // [nnz_f][6] and the faces' point slots [F][4][3] -- 24 bytes per entry of esup, 48 per entry of fsup, 96 per face (1.9 + 5.8 + 2.9 GB at 216^3
     // hexahedra); made by the first call, given back with the adjoint's state.  It shares the bins and the scratch slots above
     double *shape_cell = nullptr, *shape_face = nullptr, *shape_slot = nullptr;
+    // the tangent in the node coordinates (nin_gls_weights_tangent_points_device): dC [shape_tan_n][E][3] and (dFc, dN)
+    // [shape_tan_n][F][6] -- 24 bytes per cell and 48 per face, per direction; grown to the largest n_tangents seen, given back with the
+    // adjoint's state.  None of the three buffers above is made by that path
+    double *shape_tan_cell = nullptr, *shape_tan_face = nullptr;
+    int32_t shape_tan_n = 0;
     // what a geometry refresh (nin_grid_update_points*, grid_update.hip) reads next to the coordinates and the one array it writes that
     // no weight kernel reads: inpoel [E][8], etype [E], inpofa [F][4], face areas [F].  Put here by the first update -- handed over by the
     // device builder's mirror, or uploaded from the host arrays -- and given back with the scratch (0.32 + 0.01 + 0.48 + 0.24 GB at 10 M

@@ -42,6 +42,11 @@
 //   drho = 2 r.dr,  dw_i = dr_i / rho - r_i drho / rho^2,  dnws = dw_{ne-1} on a Neumann node,  dd_i = dw_i + (add_neumann ? dnws : 0)
 // written straight to tangent_csr[t][esup position] (and tangent_nws[t][p]): no contribution buffer, no gather.  Every row of every
 // listed node is written, zeros where the forward has its zero row.
+//
+// TAN = PTS = true: the tangent along a direction dX of the node coordinates.  The same tangent text; only z1 = dA y
+// and z2 = dA^T r differ: dA holds dC_e - dx_p on the cell rows, -/+ (K dN) on the K.N row, -/+ dT on the T row (dT = dx_p - dFc_f) and
+// -/+ d(tau U) on the tau.T2 row, from the geometry tangents dC [n_tan][E][3] and (dFc, dN) [n_tan][F][6] that kernels_gls_shape.hip
+// makes of dX.  No logarithm: eta depends on K alone.
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
@@ -61,7 +66,11 @@ using namespace waveops;
 // with TAN) keeps its three words in the tangent's slots, so that the struct -- and with it the kernel arguments of the adjoint and
 // tangent instantiations, and their code -- is what it was before RED existed
 struct AdjointIo {
-    const double *grad_csr, *grad_nws;   // adjoint: dL/d stored weights [nnz_esup], dL/d neumann_ws [P] or null
+    union {
+        const double *grad_csr;          // adjoint: dL/d stored weights [nnz_esup]
+        const double *tpt_face;          // tangent with PTS: (dFc, dN) of every face [n_tan][F][6]
+    };
+    const double *grad_nws;              // adjoint: dL/d neumann_ws [P] or null
     double *contrib;                     //          [nnz_esup][10]; RED: the reduced Jacobian R [nnz_esup][red_m]
     union {
         int32_t n_tan;                   // tangent: directions
@@ -70,8 +79,12 @@ struct AdjointIo {
     union {
         const double *tan_perm;          // tangent: dK [n_tan][E][9]
         const double *red_basis;         // RED: B [E][red_m][9] (red_stride = 9 red_m), [red_m][9] (red_stride = 0: shared) or null: g.perm
+        const double *tpt_dx;            // tangent with PTS: dX [n_tan][P][3]
     };
-    const double *tan_dm;                // tangent: d diff_mag [n_tan][E] or null (folded from g.perm)
+    union {
+        const double *tan_dm;            // tangent: d diff_mag [n_tan][E] or null (folded from g.perm)
+        const double *tpt_cell;          // tangent with PTS: dC of every cell [n_tan][E][3]
+    };
     union {
         double *tan_csr;                 // tangent: d stored weights [n_tan][nnz]
         double *pts_face;                // PTS: (fcbar, Nbar) of every (node, face) pair [nnz_fsup][6]
@@ -110,6 +123,33 @@ __device__ __forceinline__ double tangent_dtau(const GridView &g, size_t f, doub
 __device__ __forceinline__ double tangent_kn(const double *dK, size_t e, int c, double N0, double N1, double N2) {
     const double *d = dK + 9 * e + 3 * c;
     return d[0] * N0 + d[1] * N1 + d[2] * N2;
+}
+
+// row c of K . v
+__device__ __forceinline__ double shape_kn(const double *K, int c, const double v[3]) {
+    return K[3 * c + 0] * v[0] + K[3 * c + 1] * v[1] + K[3 * c + 2] * v[2];
+}
+
+// internal face f between cells ca and cb along a direction of the coordinates: dT = dx_p - dFc_f and d(tau U) =
+// tau dU - eta tau (U.dU) / |U|^2 U with U = N x T, dU = dN x T + N x dT -- the PTS adjoint's Ubar read the other way.  dfn: (dFc, dN)
+// of the face, dp: dx_p
+__device__ __forceinline__ void shape_face_tangent(const GridView &g, size_t f, double xv0, double xv1, double xv2, const double dp[3],
+                                                   const double *dfn, size_t ca, size_t cb, double dT[3], double dtU[3]) {
+    const double N[3] = {(double)g.face_normal[3 * f + 0], (double)g.face_normal[3 * f + 1], (double)g.face_normal[3 * f + 2]};
+    const double T[3] = {xv0 - g.face_center[3 * f + 0], xv1 - g.face_center[3 * f + 1], xv2 - g.face_center[3 * f + 2]};
+    const double U[3] = {N[1] * T[2] - N[2] * T[1], N[2] * T[0] - N[0] * T[2], N[0] * T[1] - N[1] * T[0]};
+    const double dN[3] = {dfn[3], dfn[4], dfn[5]};
+    dT[0] = dp[0] - dfn[0]; dT[1] = dp[1] - dfn[1]; dT[2] = dp[2] - dfn[2];
+    const double dU[3] = {(dN[1] * T[2] - dN[2] * T[1]) + (N[1] * dT[2] - N[2] * dT[1]), (dN[2] * T[0] - dN[0] * T[2]) + (N[2] * dT[0] - N[0] * dT[2]),
+                          (dN[0] * T[1] - dN[1] * T[0]) + (N[0] * dT[1] - N[1] * dT[0])};
+    const double un2 = U[0] * U[0] + U[1] * U[1] + U[2] * U[2];
+    const double da = g.diff_mag[ca], db = g.diff_mag[cb];
+    double eta = 0.0;
+    eta = da > eta ? da : eta;
+    eta = db > eta ? db : eta;
+    const double tj = glsmath::face_tau(sqrt(un2), eta);
+    const double k = eta != 0.0 ? eta * tj * ((U[0] * dU[0] + U[1] * dU[1]) + U[2] * dU[2]) / un2 : 0.0;
+    dtU[0] = tj * dU[0] - k * U[0]; dtU[1] = tj * dU[1] - k * U[1]; dtU[2] = tj * dU[2] - k * U[2];
 }
 
 constexpr int JB = 4;  // columns updated together (independent reductions in flight)
@@ -364,6 +404,74 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
             const bool ok = tau[n - 1] != 0.0;   // uniform: every thread reads the same word
             const double rho = y[n - 1];
             for (int t = 0; t < io.n_tan; ++t) {   // (n_tan is a kernel argument: the barriers below are reached by every wave)
+              if constexpr (PTS) {
+                // ---- a direction dX of the coordinates: dA from dC of the node's cells, (dFc, dN) of its faces and dx_p
+                const double *dC = io.tpt_cell + (size_t)t * 3 * (size_t)g.n_elems;
+                const double *dFN = io.tpt_face + (size_t)t * 6 * (size_t)g.n_faces;
+                const double *dxp = io.tpt_dx + ((size_t)t * (size_t)g.n_points + (size_t)p) * 3;
+                const double dp[3] = {dxp[0], dxp[1], dxp[2]};
+                // z1: the cell rows hold dC_e - dx_p; a thread per face fills the face's rows
+                for (int i = tid; i < ne; i += nthr) {
+                    double z = 0.0;
+                    if (ok) {
+                        const double *dc = dC + 3 * (size_t)cells[i];
+                        z = ((dc[0] - dp[0]) * y[3 * i + 0] + (dc[1] - dp[1]) * y[3 * i + 1]) + (dc[2] - dp[2]) * y[3 * i + 2];
+                    }
+                    qv[i] = z;
+                }
+                for (int fi = tid; ok && fi < nf; fi += nthr) {
+                    const int row = frow[fi], Ia = fia[fi], Ib = fib[fi];
+                    if (row < 0) continue;
+                    const size_t f = (size_t)g.fsup[fb + fi];
+                    const double *dfn = dFN + 6 * f;
+                    const double dN[3] = {dfn[3], dfn[4], dfn[5]};
+                    const size_t ca = (size_t)cells[Ia];
+                    const double *Ka = g.perm + 9 * ca;
+                    double z = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) z -= shape_kn(Ka, c, dN) * y[3 * Ia + c];
+                    if (Ib < 0) { qv[row] = z; continue; }   // a Neumann boundary face: one row
+                    const size_t cb = (size_t)cells[Ib];
+                    const double *Kb = g.perm + 9 * cb;
+                    double dT[3], dtU[3];
+                    shape_face_tangent(g, f, xv0, xv1, xv2, dp, dfn, ca, cb, dT, dtU);
+                    double zt = 0.0, zu = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const double dy = y[3 * Ib + c] - y[3 * Ia + c];
+                        z += shape_kn(Kb, c, dN) * y[3 * Ib + c];
+                        zt += dT[c] * dy;
+                        zu += dtU[c] * dy;
+                    }
+                    qv[row] = z; qv[row + 1] = zt; qv[row + 2] = zu;
+                }
+                // z2: thread i = cell i of the node, the node's faces in fsup order
+                for (int i = tid; ok && i < ne; i += nthr) {
+                    const size_t e = (size_t)cells[i];
+                    const double *dc = dC + 3 * e, *Ke = g.perm + 9 * e;
+                    const double ri = rv[i];
+                    double z[3] = {(dc[0] - dp[0]) * ri, (dc[1] - dp[1]) * ri, (dc[2] - dp[2]) * ri};
+                    for (int fi = 0; fi < nf; ++fi) {
+                        const int row = frow[fi], Ia = fia[fi], Ib = fib[fi];
+                        if (row < 0 || (Ia != i && Ib != i)) continue;
+                        const size_t f = (size_t)g.fsup[fb + fi];
+                        const double *dfn = dFN + 6 * f;
+                        const double dN[3] = {dfn[3], dfn[4], dfn[5]};
+                        const double sign = Ia == i ? -1.0 : 1.0;
+                        const double rt = sign * rv[row];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) z[c] += shape_kn(Ke, c, dN) * rt;
+                        if (Ib < 0) continue;
+                        double dT[3], dtU[3];
+                        shape_face_tangent(g, f, xv0, xv1, xv2, dp, dfn, (size_t)cells[Ia], (size_t)cells[Ib], dT, dtU);
+                        const double r1 = sign * rv[row + 1], r2 = sign * rv[row + 2];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) z[c] += r1 * dT[c] + r2 * dtU[c];
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sv[3 * i + c] = z[c];
+                }
+              } else {
                 const double *dK = io.tan_perm + (size_t)t * 9 * (size_t)g.n_elems;
                 const double *dm = io.tan_dm ? io.tan_dm + (size_t)t * (size_t)g.n_elems : nullptr;
                 // z1: the cell rows hold no K; a thread per face fills the face's rows
@@ -411,6 +519,7 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
 #pragma unroll
                     for (int c = 0; c < 3; ++c) sv[3 * i + c] = z[c];
                 }
+              }
                 __syncthreads();
                 if (wave == 0) {
                     double *oc = io.tan_csr + (size_t)t * (size_t)io.nnz + eb;
@@ -694,6 +803,15 @@ int launch_gls_tangent(const GridView &g, int bin, const AdjBinRun &run, int add
     io.n_tan = n_tangents; io.tan_perm = tangent_perm; io.tan_dm = tangent_diff_mag; io.tan_csr = tangent_csr; io.tan_nws = tangent_nws;
     io.nnz = (long long)nnz;
     return launch_bin_of<true, false>(g, bin, run, add_neumann, io, stream);
+}
+
+int launch_gls_tangent_points(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, int32_t n_tangents, const double *tangent_points,
+                              const double *tangent_cell, const double *tangent_face, double *tangent_csr, double *tangent_nws, int64_t nnz,
+                              hipStream_t stream) {
+    AdjointIo io{};
+    io.n_tan = n_tangents; io.tpt_dx = tangent_points; io.tpt_cell = tangent_cell; io.tpt_face = tangent_face; io.tan_csr = tangent_csr;
+    io.tan_nws = tangent_nws; io.nnz = (long long)nnz;
+    return launch_bin_of<true, false, true>(g, bin, run, add_neumann, io, stream);
 }
 
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,

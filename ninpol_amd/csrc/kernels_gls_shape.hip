@@ -17,6 +17,11 @@
 //   nin_shape_node_kernel, thread p: grad_points[p] = xbar_own[p] + sum over esup[p] of cbar + sum over fsup[p] of the slot of p in f,
 //     each sum in row order.
 // No atomics: two calls agree bit for bit.
+//
+// The tangent reads the same geometry forwards, before the adjoint kernel's tangent mode runs: a direction dX [P][3] to
+//   nin_shape_tangent_cell_kernel, thread (direction, e): dC_e = sum dx_v / n_e over the cell's inpoel row,
+//   nin_shape_tangent_face_kernel, thread (direction, f): dFc_f = sum dx_v / npofa (the fourth point of a quadrilateral too) and
+//     dN_f = (dn - (dn.N) N) / |n| with dn = dv1 x v2 + v1 x dv2, dv1 = dx_0 - dx_1, dv2 = dx_2 - dx_1 -- v1, v2, |n| and N as above.
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
@@ -118,7 +123,91 @@ __global__ __launch_bounds__(256) void nin_shape_node_kernel(GridView g, const i
     for (int c = 0; c < 3; ++c) grad_points[3 * (size_t)p + c] = acc[c];
 }
 
+// ---- the same geometry read forwards: a direction dX [P][3] of the coordinates to dC, dFc and dN.  One thread per
+//      (direction, cell) or (direction, face), the direction in blockIdx.y; every entry is written, sums in row order, no atomics ----
+__global__ __launch_bounds__(256) void nin_shape_tangent_cell_kernel(int32_t n_elems, int32_t n_points, int32_t n_tan, const int4 *__restrict__ inpoel,
+                                                                     const double *__restrict__ dX, double *__restrict__ dC) {
+    const int32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_elems) return;
+    const int4 a = inpoel[2 * (size_t)e], b = inpoel[2 * (size_t)e + 1];
+    const int32_t q[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    int n = 0;
+    while (n < 8 && q[n] >= 0 && q[n] < n_points) ++n;   // (a row ends at the first -1; the builders checked every index)
+    const double dn = (double)n;
+    for (int32_t t = blockIdx.y; t < n_tan; t += gridDim.y) {
+        const double *dx = dX + (size_t)t * 3 * (size_t)n_points;
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int j = 0; j < n; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += dx[3 * (size_t)q[j] + c];
+        double *o = dC + ((size_t)t * (size_t)n_elems + (size_t)e) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = n > 0 ? acc[c] / dn : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void nin_shape_tangent_face_kernel(GridView g, int32_t n_tan, const int4 *__restrict__ inpofa,
+                                                                     const double *__restrict__ dX, double *__restrict__ dFN) {
+    const int32_t f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= g.n_faces) return;
+    const int4 r = inpofa[f];
+    const int32_t q[4] = {r.x, r.y, r.z, r.w};
+    int npofa = 0;
+    while (npofa < 4 && q[npofa] >= 0 && q[npofa] < g.n_points) ++npofa;
+    if (npofa < 3) {   // (no face of a 3-D mesh)
+        for (int32_t t = blockIdx.y; t < n_tan; t += gridDim.y) {
+            double *o = dFN + ((size_t)t * (size_t)g.n_faces + (size_t)f) * 6;
+            for (int i = 0; i < 6; ++i) o[i] = 0.0;
+        }
+        return;
+    }
+    double x[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[j][c] = g.coords[3 * (size_t)q[j] + c];
+    const double v1[3] = {x[0][0] - x[1][0], x[0][1] - x[1][1], x[0][2] - x[1][2]};
+    const double v2[3] = {x[2][0] - x[1][0], x[2][1] - x[1][1], x[2][2] - x[1][2]};
+    const double n[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+    // (no guard on |n| = 0, as in nin_shape_face_kernel: such a face has no normal and the forward's rows of it are NaN already)
+    const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double N[3] = {(double)g.face_normal[3 * (size_t)f + 0], (double)g.face_normal[3 * (size_t)f + 1], (double)g.face_normal[3 * (size_t)f + 2]};
+    const double dnp = (double)npofa;
+    for (int32_t t = blockIdx.y; t < n_tan; t += gridDim.y) {
+        const double *dx = dX + (size_t)t * 3 * (size_t)g.n_points;
+        double d[4][3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[j][c] = j < npofa ? dx[3 * (size_t)q[j] + c] : 0.0;
+        const double dv1[3] = {d[0][0] - d[1][0], d[0][1] - d[1][1], d[0][2] - d[1][2]};
+        const double dv2[3] = {d[2][0] - d[1][0], d[2][1] - d[1][1], d[2][2] - d[1][2]};
+        const double dn[3] = {(dv1[1] * v2[2] - dv1[2] * v2[1]) + (v1[1] * dv2[2] - v1[2] * dv2[1]),
+                              (dv1[2] * v2[0] - dv1[0] * v2[2]) + (v1[2] * dv2[0] - v1[0] * dv2[2]),
+                              (dv1[0] * v2[1] - dv1[1] * v2[0]) + (v1[0] * dv2[1] - v1[1] * dv2[0])};
+        const double dot = (dn[0] * N[0] + dn[1] * N[1]) + dn[2] * N[2];
+        double *o = dFN + ((size_t)t * (size_t)g.n_faces + (size_t)f) * 6;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            o[c] = (((d[0][c] + d[1][c]) + d[2][c]) + d[3][c]) / dnp;   // the fourth point of a quadrilateral too (a triangle: + 0.0)
+            o[3 + c] = (dn[c] - dot * N[c]) / nn;
+        }
+    }
+}
+
 }  // namespace
+
+int launch_shape_tangent_geometry(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, int32_t n_tangents, const double *tangent_points,
+                                  double *tangent_cell, double *tangent_face, hipStream_t stream) {
+    const unsigned ny = (unsigned)(n_tangents < 65535 ? n_tangents : 65535);
+    if (g.n_elems > 0)
+        hipLaunchKernelGGL(nin_shape_tangent_cell_kernel, dim3((unsigned)((g.n_elems + 255) / 256), ny), dim3(256), 0, stream, g.n_elems, g.n_points,
+                           n_tangents, reinterpret_cast<const int4 *>(inpoel), tangent_points, tangent_cell);
+    if (g.n_faces > 0)
+        hipLaunchKernelGGL(nin_shape_tangent_face_kernel, dim3((unsigned)((g.n_faces + 255) / 256), ny), dim3(256), 0, stream, g, n_tangents,
+                           reinterpret_cast<const int4 *>(inpofa), tangent_points, tangent_face);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int launch_shape_gather(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos, double *cell_bar,
                         const double *face_bar, double *face_slot, double *grad_points, hipStream_t stream) {

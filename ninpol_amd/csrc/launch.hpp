@@ -163,6 +163,16 @@ int launch_shape_gather(const GridView &g, const int32_t *inpofa, const int32_t 
 //   node is written
 int launch_gls_tangent(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, int32_t n_tangents, const double *tangent_perm,
                        const double *tangent_diff_mag, double *tangent_csr, double *tangent_nws, int64_t nnz, hipStream_t stream);
+// launch_shape_tangent_geometry (kernels_gls_shape.hip): n_tangents directions tangent_points [n_tangents][P][3] of the
+//   node coordinates through the geometry -- tangent_cell [n_tangents][E][3] = d centroid, tangent_face [n_tangents][F][6] = (d face
+//   centre, d unit normal); inpoel [E][8] and inpofa [F][4] as launch_update_geometry reads them; every entry written (3-D grids only).
+// launch_gls_tangent_points: the tangent mode of the adjoint kernel along those directions on the nodes of one bin, the outputs of
+//   launch_gls_tangent
+int launch_shape_tangent_geometry(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, int32_t n_tangents, const double *tangent_points,
+                                  double *tangent_cell, double *tangent_face, hipStream_t stream);
+int launch_gls_tangent_points(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, int32_t n_tangents, const double *tangent_points,
+                              const double *tangent_cell, const double *tangent_face, double *tangent_csr, double *tangent_nws, int64_t nnz,
+                              hipStream_t stream);
 
 // the GLS Jacobian kept and applied (kernels_gls_jacobian.hip), all DEVICE pointers; contrib [nnz_esup][10] as an adjoint
 // launch with grad_csr = u[esup] left it, fold [E] = d diff_mag / d K_dd at the linearisation point.

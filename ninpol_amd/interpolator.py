@@ -920,7 +920,7 @@ class Interpolator:
         neumann_ws, at the resident permeability table, the chain through diff_mag = (1 - 3 / tr K)^2 folded in.  On the device, the
         sibling of permeability_gradient(): host-synchronous, numpy in and out; deterministic.  It is what a Newton-Krylov solver with
         K(u) needs, `J . v` without differencing two weight launches.  Rows that are zero (Dirichlet nodes) have a zero derivative; the
-        Neumann values are not differentiated, and the node coordinates have no tangent (their adjoint: points_gradient())."""
+        Neumann values are not differentiated (the node coordinates: points_tangent())."""
         self._check_call(variable=variable)
         self._perm_rows()   # (ValueError without a permeability)
         g = self.grid
@@ -933,6 +933,30 @@ class Interpolator:
         out = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
         nws = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
         _lib.check(_lib.load().nin_gls_permeability_tangent_host(g._h, _ptr(d), _ptr(u), k, _ptr(out), _ptr(nws)))
+        return out, nws
+
+    def points_tangent(self, variable, dX, cell_values=None):
+        """The directional derivative of what `apply(variable, "gls")` returns, along a change `dX` of the node coordinates: `dX` one
+        direction (n_points, 3) or k of them as (k, n_points, 3); `cell_values` = u, (n_elems,) or (k, n_elems) alike (default: the
+        cell variable `variable` itself, for every direction).  Returns `(d_node_values, d_neumann_ws)`, each (n_points,) or
+        (k, n_points): `dW_f . u_f` for the GLS matrix W that apply() uses (the `+ neumann_ws[row]` included) and the derivative of its
+        neumann_ws, at the grid's resident coordinates -- what update_points() rewrites -- permeability and flags; the float32 casts of
+        the stored normals count as the identity.  On the device, the sibling of permeability_tangent() and the forward mode of
+        points_gradient(): host-synchronous, numpy in and out; deterministic.  It is what a solver that moves the mesh needs, `J . dX`
+        without differencing two update_points() + apply() pairs.  Rows that are zero (Dirichlet nodes) have a zero derivative, but
+        moving a Dirichlet node moves the rows of its neighbours.  3-D meshes, GLS only; the Neumann values are not differentiated."""
+        self._check_call(variable=variable)
+        self._perm_rows()   # (ValueError without a permeability)
+        g = self.grid
+        d = np.ascontiguousarray(dX, dtype=DTYPE_F)
+        if d.shape != (g.n_points, 3) and not (d.ndim == 3 and d.shape[0] >= 1 and d.shape[1:] == (g.n_points, 3)):
+            raise ValueError(f"dX must have shape ({g.n_points}, 3) or (k, {g.n_points}, 3), not {d.shape}.")
+        lead = d.shape[:-2]
+        u, k = self._derivative_inputs(variable, lead, cell_values, f"dX of shape {d.shape}")
+        self._gls_tables_to_device(variable)
+        out = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
+        nws = np.empty(lead + (g.n_points,), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_points_tangent_host(g._h, _ptr(d), _ptr(u), k, _ptr(out), _ptr(nws)))
         return out, nws
 
     def permeability_jacobian(self, variable, cell_values=None, neumann_values=None, basis=None):
@@ -1152,6 +1176,19 @@ class DevicePlan:
         _lib.check(_lib.load().nin_gls_weights_tangent_device(self.grid._h, int(bool(add_neumann)), int(n_tangents), _vp(tangent_perm_ptr),
                                                               _vp(tangent_diff_mag_ptr), _vp(tangent_csr_ptr), _vp(tangent_neumann_ws_ptr),
                                                               ctypes.c_void_p(stream)))
+
+    def launch_weights_tangent_points(self, tangent_points_ptr, tangent_csr_ptr, n_tangents=1, tangent_neumann_ws_ptr=0, stream=0, add_neumann=True):
+        """The directional derivative of the GLS weights in the node coordinates (nin_gls_weights_tangent_points_device):
+        tangent_points [n_tangents][n_points][3] = the directions dX -> tangent_csr [n_tangents][nnz_esup] = (d csr_data / dX) . dX for the
+        csr_data of a `launch(..., add_neumann)` at what is resident now (geometry, flags, K), and tangent_neumann_ws
+        [n_tangents][n_points] (0: not wanted) the same for neumann_ws: a shape tangent, the sibling of launch_weights_tangent and the
+        forward mode of launch_weights_backward_points.  All directions share one factorisation per node.  Every entry of the outputs
+        is written.  Asynchronous on `stream` after the first call on a grid (which makes the bins and synchronises); the grid keeps
+        24 bytes per cell and 48 per face, per direction, grown to the largest n_tangents seen -- none of the adjoints' buffers.  3-D
+        grids.  GLS only: a plan of IDW or LS raises instead of returning zeros."""
+        self._gls_derivative("launch_weights_tangent_points", "do depend on the node coordinates, but they are not differentiated here")
+        _lib.check(_lib.load().nin_gls_weights_tangent_points_device(self.grid._h, int(bool(add_neumann)), int(n_tangents), _vp(tangent_points_ptr),
+                                                                     _vp(tangent_csr_ptr), _vp(tangent_neumann_ws_ptr), ctypes.c_void_p(stream)))
 
     def linearize(self, u_ptr, neumann_values_ptr=0, stream=0):
         """The Jacobian of the node values `W u + neumann_ws * b` in the permeability, kept on the device: a GlsJacobian linearised at

@@ -5,7 +5,8 @@ also makes the GLS weights a function of the permeability tensor K: its backward
 tensors) the same call gives the forward derivative, W du + dW u, with dW from the tangent of the weight kernels
 (nin_gls_weights_tangent_device); torch.func.jvp, which needs setup_context-style Functions, is not supported.
 `CellToNode(...)(u, points=X)` makes the GLS weights a function of the node coordinates as well: the mesh moves to X
-(Interpolator.update_points) and the backward pass returns dL/dX (nin_gls_weights_backward_points_device), backwards only.
+(Interpolator.update_points) and the backward pass returns dL/dX (nin_gls_weights_backward_points_device); under forward_ad a dual X
+gives dW u along dX (nin_gls_weights_tangent_points_device).
 `CellToNode.linearize(u, K, scale)` is for a caller that needs many such products at one point (a Krylov solver): it keeps the
 Jacobian of W u in the permeability on the device (nin_gls_jacobian) and returns a Linearization whose jvp / vjp are plain tensor
 methods, one streaming pass each instead of a factorisation of every node.
@@ -89,11 +90,9 @@ class _GlsWeightsFn(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, dK, dscale, _=None, dpoints=None):
         """forward mode (torch.autograd.forward_ad): the tangent of perm = scale * K is scale * dK + dscale * K, a missing tangent
-        counts as zero; one DevicePlan.launch_weights_tangent call gives (dW, dneumann_ws).  Autograd calls this right behind
-        forward(); like backward() it reads what is resident and refuses once that was updated.  The node coordinates have no
-        forward mode."""
-        if dpoints is not None:
-            raise NotImplementedError("the GLS weights have no forward-mode derivative in the node coordinates (backward() has one)")
+        counts as zero; one DevicePlan.launch_weights_tangent call gives (dW, dneumann_ws).  A tangent of the node coordinates adds
+        one DevicePlan.launch_weights_tangent_points call; the two results are summed.  Autograd calls this right behind forward();
+        like backward() it reads what is resident and refuses once that was updated."""
         K, scale = ctx.saved_tensors
         op = ctx.op
         _GlsWeightsFn._check_stamp(ctx, "tangent", "jvp()")
@@ -106,11 +105,20 @@ class _GlsWeightsFn(torch.autograd.Function):
             tperm = t if tperm is None else tperm + t
         dw = torch.empty(op.plan.nnz, dtype=torch.float64, device=op.device)
         dnws = torch.empty(op.n_points, dtype=torch.float64, device=op.device)
-        if tperm is None:
+        if tperm is None and dpoints is None:
             return dw.zero_(), dnws.zero_()
-        tperm = tperm.contiguous()
-        op.plan.launch_weights_tangent(tperm.data_ptr(), dw.data_ptr(), 1, 0, dnws.data_ptr(), op._stream(), add_neumann=True)
-        return dw, dnws
+        if tperm is not None:
+            tperm = tperm.contiguous()
+            op.plan.launch_weights_tangent(tperm.data_ptr(), dw.data_ptr(), 1, 0, dnws.data_ptr(), op._stream(), add_neumann=True)
+            if dpoints is None:
+                return dw, dnws
+        if tperm is None:
+            dwx, dnx = dw, dnws
+        else:
+            dwx, dnx = torch.empty_like(dw), torch.empty_like(dnws)
+        dx = dpoints.contiguous()
+        op.plan.launch_weights_tangent_points(dx.data_ptr(), dwx.data_ptr(), 1, dnx.data_ptr(), op._stream(), add_neumann=True)
+        return (dw, dnws) if tperm is None else (dw + dwx, dnws + dnx)
 
     @staticmethod
     def backward(ctx, gw, gnws):
@@ -281,7 +289,8 @@ class CellToNode(torch.nn.Module):
 
     The derivative with respect to the permeability comes through `forward(u, K, scale)` (GLS; see there) or `weights_of(K, scale)`,
     backwards (backward()) and forwards (torch.autograd.forward_ad: dual u, K, scale in any combination).  The derivative with
-    respect to the node coordinates comes through `forward(u, points=...)` / `weights_of(points=...)`, backwards only (GLS, 3-D).
+    respect to the node coordinates comes through `forward(u, points=...)` / `weights_of(points=...)`, backwards and forwards alike
+    (GLS, 3-D; dual points beside dual u, K, scale in any combination).
     Derivatives with respect to the Neumann values are not provided, nor are those of the sharded (multi-GPU) path; the tangent is
     that of a full launch (recompute_weights(dirty_only=True) carries none)."""
 
@@ -368,7 +377,8 @@ class CellToNode(torch.nn.Module):
         points: float64 (n_points, 3) on the plan's device, alone or beside K (3-D meshes, GLS) -- the weights as a differentiable
         function of the node coordinates.  It is given to Interpolator.update_points() first, as K is to update_permeability(): the
         mesh moves there.  Backward gives dL/dpoints through DevicePlan.launch_weights_backward_points, under the same rule about
-        later updates; there is no forward mode in the coordinates.  IDW / LS depend on the coordinates too, but that derivative is
+        later updates; under forward_ad.dual_level() dual points give the weights' tangent along dX through
+        DevicePlan.launch_weights_tangent_points, added to that of dual K / scale.  IDW / LS depend on the coordinates too, but that derivative is
         not provided: ValueError, never zeros."""
         if points is not None:
             if self.plan.method != "gls":
