@@ -1,52 +1,19 @@
-// kernels_gls_adjoint.hip -- the GLS weights differentiated with respect to the permeability, gfx950.
+// kernels_gls_adjoint.hip -- the GLS weights differentiated with respect to the permeability and to the node coordinates, gfx950.
+// DESIGN.md 4.11 has the mathematics, the bins and the layout of this unit; 4.12, 4.14, 4.15 and 4.17 the other four modes.
 //
-// Notation of kernels_gls.hip's header: M is the node's m x n system, n = 3 n_e + 1, A its first n - 1 columns, c its last (1 on the
-// n_e cell rows).  Forward:  y = argmin |c - A y|,  r = c - A y,  rho = r.r,  w_i = r_i / rho on the cell rows; the stored entry is
-// d_i = w_i + nws, nws = w_{ne-1} on a Neumann node (when add_neumann), else 0.  Backward, given ghat_i = dL/dd_i:
-//   g     = ghat on the cell rows, 0 elsewhere; on a Neumann node g_{ne-1} += sum_j ghat_j (add_neumann) + dL/dneumann_ws[p] (if given)
-//   rbar  = g / rho - 2 (g.r) r / rho^2
-//   s     = argmin |rbar - A s|,  q = rbar - A s          (a second least-squares solve with the SAME factorisation)
-//   Abar  = -q y^T - r s^T                                 (only the entries of the K.N and tau.T2 rows are ever formed)
-// K enters A through the K.N row of an internal face (-(K_a N) on cell a's columns, +(K_b N) on cell b's), through the -(K_0 N) row of
-// a Neumann boundary face, and through eta = max(0, diff_mag_a, diff_mag_b) in tau = |T2|^(-eta) of the tau.T2 row.
-//
-// nin_gls_adjoint_kernel: one node per WORKGROUP of TW wavefronts, the dense formulation of kernels_gls.hip -- rows across the lanes
-// (row r in lane r % 64), column-major, Householder reflectors kept in place (v_k below the diagonal, R on and above it: the two
-// triangular solves need R, which the forward kernel never reads again).  Every wavefront forms reflector k from the pivot column,
-// wavefront w applies it to every TW-th group of four trailing columns, one barrier per reflector; the tail (two back substitutions,
-// three applications of Q) is wavefront 0's.  The system lives in LDS (LDS = true: the classes of 1, 2 and 4 wavefronts) or in a
-// global-memory scratch slot per workgroup (the systems that do not fit one CU's LDS), as nin_gls_team_kernel keeps it.
-// The node header, the zero-row rule and the assembly below are this unit's OWN TEXT of what gls_dense.hpp holds for the forward kernels
-// (read_node, DenseNode::zero_row, cell_rows, internal_face_rows with glsmath::face_tau, neumann_face_row): a change there is made here
-// too.  Calling the helpers gives the same bits (profiles/r16), but every form tried reallocated this kernel's registers and moved one
-// of the del20 timings by ~0.5 %, more than the parent's spread -- the row loops are the same instructions either way.
-//
-// Contributions: lane i of the workgroup owns cell i of the node and walks the node's faces in fsup order; the ten values of the pair
-// (node, cell) -- Kbar[9] and etabar -- are summed in that fixed order and written to contrib[esup position][10].  nin_adjoint_gather_kernel
-// then sums, for every cell, the slots of its nodes in ascending node id through the cell-major index of the transpose (DeviceGrid::tr_*).
-// No atomics anywhere: two calls agree bit for bit.
-// RED = true (with TAN = false only): the lane contracts its ten values with the cell's basis B [red_m][9] and writes the
-// red_m values of the reduced Jacobian instead, contrib [esup position][red_m] -- the 80-byte record is never stored.
-//
-// PTS = true (with TAN = RED = false only): the weights differentiated with respect to the node coordinates.  The same
-// kernel up to y, r, s, q; then Abar meets the four geometric inputs of the node's system instead of K -- the centroids of its cells
-// (cbar, contrib [esup position][3]), the centre and the normal of its faces ((fcbar, Nbar), pts_face [fsup position][6]) and the
-// node itself (xbar_own, pts_own [P][3], summed by wavefront 0 in a fixed order) -- and kernels_gls_shape.hip takes those through
-// the geometry of geom_math.hpp to the vertices.  No slot memory beyond the adjoint's, no atomics.
-//
-// The tangent (TAN = true): the same kernel up to y, r, rho and the verdict, then for every direction dK (9 per cell; d
-// diff_mag per cell given, or folded from the resident perm) the directional derivative of the stored entries.  dA is non-zero where K
-// enters: -(dK_a N) / +(dK_b N) on the K.N row, -/+ dtau U on the tau.T2 row with dtau = -ln|T2| tau ddm_pick (pick: the cell the
-// forward's max() takes eta from), -(dK_a N) on a Neumann boundary row.  r = P_perp c, so with A = Q R
-//   dr = -P_perp (dA y) - (A^+)^T (dA^T r) = -Q [ R^-T (dA^T r) ; (Q^T (dA y))(n-1:m) ]
-//   drho = 2 r.dr,  dw_i = dr_i / rho - r_i drho / rho^2,  dnws = dw_{ne-1} on a Neumann node,  dd_i = dw_i + (add_neumann ? dnws : 0)
-// written straight to tangent_csr[t][esup position] (and tangent_nws[t][p]): no contribution buffer, no gather.  Every row of every
-// listed node is written, zeros where the forward has its zero row.
-//
-// TAN = PTS = true: the tangent along a direction dX of the node coordinates.  The same tangent text; only z1 = dA y
-// and z2 = dA^T r differ: dA holds dC_e - dx_p on the cell rows, -/+ (K dN) on the K.N row, -/+ dT on the T row (dT = dx_p - dFc_f) and
-// -/+ d(tau U) on the tau.T2 row, from the geometry tangents dC [n_tan][E][3] and (dFc, dN) [n_tan][F][6] that kernels_gls_shape.hip
-// makes of dX.  No logarithm: eta depends on K alone.
+// nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS> serves five modes (listed at its static_assert).  They share the head: node header,
+// assembly, Householder QR with R kept, y, r, rho and the verdict.  The header, the zero-row rule and the assembly are this unit's OWN
+// TEXT of what gls_dense.hpp holds for the forward kernels (read_node, DenseNode::zero_row, cell_rows, internal_face_rows with
+// glsmath::face_tau, neumann_face_row): a change there is made here too.  Calling the helpers gives the same bits, but every form tried
+// reallocated this kernel's registers and moved one of the del20 timings by ~0.5 %, more than the parent's spread (profiles/r16).
+// The steps after the head are inline for the same reason: each was hoisted alone into a function, and one face frame tried at each of
+// its two function sites, and every one changes the device code of the instantiations that run it (profiles/r20).
+// Determinism: no atomics anywhere.  A thread owns a cell or a face of the node and sums over the node's faces in fsup order, wavefront
+// 0 sums in lane order, nin_adjoint_gather_kernel sums a cell's nodes in ascending node id: two calls agree bit for bit.
+// Storage: every row of every listed node is written, zeros where the forward has its zero row.  RED: the lane contracts its ten values
+// with the cell's basis B [red_m][9] and the 80-byte record is never stored.  PTS: the records of the cells' centroids (contrib [esup
+// position][3]), of the faces' centres and normals (pts_face [fsup position][6]) and of the node (pts_own [P][3]) are
+// kernels_gls_shape.hip's to take to the vertices; the PTS tangent reads dC [n_tan][E][3] and (dFc, dN) [n_tan][F][6] made there of dX.
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
@@ -180,6 +147,9 @@ __device__ __forceinline__ void back_substitute(const double *A, int ld, int nc,
 template <int TW, bool LDS, bool TAN, bool RED, bool PTS>
 __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, const int32_t *__restrict__ nodes, int32_t count, int add_neumann,
                                                                  AdjointIo io, double *scratch, long long scratch_stride) {
+    // (TAN, RED, PTS): (0, 0, 0) K adjoint, (0, 1, 0) reduced K adjoint, (0, 0, 1) coordinate adjoint, (1, 0, 0) K tangent,
+    // (1, 0, 1) coordinate tangent; the other three combinations mean nothing
+    static_assert(!RED || (!TAN && !PTS), "(TAN, RED, PTS) is not one of the five modes: RED goes with neither TAN nor PTS");
     extern __shared__ double smem[];
     const double *__restrict__ const grad_csr = io.grad_csr, *__restrict__ const grad_nws = io.grad_nws;
     double *__restrict__ const contrib = io.contrib;

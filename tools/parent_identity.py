@@ -12,8 +12,9 @@ parts of tests/test_gpu_composite.py (between them all 22 plan kernels have node
 for which mfx_boundary must have nodes and neumann_ws non-zero entries -- otherwise the boundary-face rows are never computed.
 Routes per mesh: nin_weights_host over all nodes and over a shuffled subset (GLS, IDW and LS), interpolate() pipelined
 (NIN_E2E_MIN_NODES=512), apply() fused and unfused, apply_transpose() with 3 fields, permeability_gradient() and
-permeability_tangent() along two directions.  On the meshes of LOCAL also points_gradient() and permeability_jacobian() -- in the
-permeability and in the bases "scale", "diagonal", "symmetric" and one per-cell (n_elems, 3, 9) array, each with neumann_values:
+permeability_tangent() along two directions.  On the meshes of LOCAL also points_gradient(), points_tangent() along two directions
+and permeability_jacobian() -- in the permeability and in the bases "scale", "diagonal", "symmetric" and one per-cell
+(n_elems, 3, 9) array, each with neumann_values:
 matmat / rmatmat over 5 columns, matvec, rmatvec and to_scipy().data -- and a
 scatter of permeability, of points and of Neumann flags (device tensors), each followed by the dirty launch -- weights and neumann_ws
 after each -- and by HostMatrix.update(), whose matrix must in the end be a fresh interpolate()'s in the same child.  On the composite
@@ -110,8 +111,9 @@ def local_routes(I, A):
 
 def adjoint_routes(I, A, kept=False):
     """permeability_gradient() for 3 node fields, permeability_tangent() along 2 directions (fixed seeds); kept: points_gradient() for 3
-    node fields too, and permeability_jacobian() with neumann_values in the permeability and in every kind of basis -- matmat over 5
-    directions and rmatmat over 5 node fields (5 crosses the chunk of 4 and leaves a chunk of 1), matvec, rmatvec, to_scipy().data"""
+    node fields too, points_tangent() along 2 directions, and permeability_jacobian() with neumann_values in the permeability and in
+    every kind of basis -- matmat over 5 directions and rmatmat over 5 node fields (5 crosses the chunk of 4 and leaves a chunk of 1),
+    matvec, rmatvec, to_scipy().data"""
     import numpy as np
     P, E = int(I.grid.n_points), int(I.grid.n_elems)
     A["perm_gradient.g"] = I.permeability_gradient("u", np.random.default_rng(8).random((3, P)))
@@ -119,6 +121,7 @@ def adjoint_routes(I, A, kept=False):
     if not kept:
         return
     A["points_gradient.g"] = I.points_gradient("u", np.random.default_rng(10).random((3, P)))
+    A["points_tangent.v"], A["points_tangent.nws"] = I.points_tangent("u", np.random.default_rng(16).standard_normal((2, P, 3)))
     b = np.random.default_rng(12).standard_normal(P)
     bases = {"perm": None, "scale": "scale", "diagonal": "diagonal", "symmetric": "symmetric",
              "per_cell": np.random.default_rng(13).uniform(-1.0, 1.0, (E, 3, 9))}
