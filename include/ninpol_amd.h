@@ -608,6 +608,54 @@ int nin_gls_rjacobian_apply_host(nin_gls_rjacobian *J, int32_t n, const double *
 int nin_gls_rjacobian_apply_transpose_host(nin_gls_rjacobian *J, int32_t n, const double *v, double *grad_theta);
 int nin_gls_rjacobian_fetch_host(nin_gls_rjacobian *J, double *R);
 
+/* ---- the GLS Jacobian in the node coordinates, kept on the device: linearise once, apply J . dX and J^T . v many times ------------
+ * nin_gls_weights_backward_points_device and nin_gls_weights_tangent_points_device repeat the dense QR of every node at every call.
+ * A solver that moves the mesh (ALE, r-adaptivity, Newton-Krylov on a mesh-motion residual, a Gauss-Newton shape fit) applies J . dX
+ * or J^T . v once per iteration at ONE linearisation point; for it, a nin_gls_xjacobian keeps the derivative.  For a fixed cell field
+ * u (and optional node values b) the node values  F_p(X) = sum_i d_i(X) u[c_i] + neumann_ws_p(X) b_p  (d: the stored weights with
+ * add_neumann = 1, the W of nin_apply_*) depend on the coordinates through the centroids of p's cells, the centres and unit normals
+ * of its faces and its own position.  One launch of the adjoint kernel's coordinate mode with dev_grad_csr[pos] = u[esup[pos]] and
+ * dev_grad_neumann_ws = b leaves the derivative in exactly those inputs, and the object owns them:
+ *   cell [nnz_esup][3] = dF_p / d centroid_e,   face [nnz_fsup][6] = (dF_p / d face centre_f, dF_p / d unit normal_f),
+ *   own [n_points][3] = dF_p / d x_p through the rows of p's own system
+ * (24 nnz_esup + 48 nnz_fsup + 24 n_points bytes: 8.0 GB at 216^3 hexahedra).  The Jacobian is kept FACTORED through the mesh
+ * geometry: an apply call takes its direction, or its result, through the chain centroid / face centre / normal <-> vertices with
+ * the grid's RESIDENT coordinates and normals.  Hence the one difference from nin_gls_jacobian: an apply call after the coordinates
+ * moved (nin_grid_geometry_updates differs from the stamp) is refused with NIN_ESTATE and writes nothing -- linearise again; a snapshot
+ * of the geometry would cost about 80 bytes per face, and the solvers above apply at the linearisation point.  Later updates of
+ * the permeability or the flags do not change the answers and are not refused.  Lifetime and ownership as nin_gls_jacobian.  Scratch of
+ * the applies is the object's too, made by the first call that needs it and kept: 24 bytes per cell and 48 per face per direction of a
+ * chunk of nin_gls_xjacobian_apply (up to 4), 24 per cell and 96 per face per field of a chunk of _apply_transpose (up to 2: the
+ * faces' point slots are 2.9 GB per field at 216^3).  One apply call at a time per object: the calls share that scratch.  None of
+ * the grid's buffers of the two calls above is used or made.  3-D grids.
+ *
+ * nin_gls_xjacobian_create: the three record buffers.  Errors as nin_gls_jacobian_create.
+ * nin_gls_xjacobian_linearize: dev_u_cells [n_elems], dev_neumann_values [n_points] or NULL (b = 0).  One launch of the adjoint kernel's
+ *   coordinate mode on every bin (NIN_GLS_ADJ_ONLY is not read) at what is resident NOW; every record is written, zeros for the nodes
+ *   the forward gives the zero row.  NIN_EINVAL for a grid that is not 3-D; otherwise as nin_gls_jacobian_linearize.
+ * nin_gls_xjacobian_apply: dev_dnode [n][n_points] = J . dev_dpoints [n][n_points][3]; every entry written, exact zeros for zero rows.
+ * nin_gls_xjacobian_apply_transpose: dev_grad_points [n][n_points][3] = J^T . dev_v [n][n_points]; dev_v = 1 gives, bit for bit, what
+ *   nin_gls_weights_backward_points_device(g, 1, u[esup], b, ...) returned at the linearisation point.  A Dirichlet node receives
+ *   gradient as a vertex of its cells and faces.  Uses the transpose index (built, with a wait for `stream`, when it is not there).
+ *   Both asynchronous on `stream`, deterministic, no atomics: two calls agree bit for bit, a batch equals its members one by one.
+ *   NIN_ESTATE before the first linearisation and after an update of the points, NIN_EINVAL for n < 1 or a NULL argument.
+ * nin_gls_xjacobian_records: the three device buffers, read-only, and (scratch_bytes not NULL) the bytes of scratch the object holds.
+ * nin_gls_xjacobian_stamp as nin_gls_jacobian_stamp.  nin_gls_xjacobian_*_host: the same with HOST pointers, synchronous;
+ *   nin_gls_xjacobian_fetch_host copies the three record buffers to the host. */
+typedef struct nin_gls_xjacobian nin_gls_xjacobian;
+int nin_gls_xjacobian_create(nin_grid *g, nin_gls_xjacobian **out);
+int nin_gls_xjacobian_linearize(nin_gls_xjacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream);
+int nin_gls_xjacobian_apply(nin_gls_xjacobian *J, int32_t n, const double *dev_dpoints, double *dev_dnode, void *stream);
+int nin_gls_xjacobian_apply_transpose(nin_gls_xjacobian *J, int32_t n, const double *dev_v, double *dev_grad_points, void *stream);
+int nin_gls_xjacobian_records(nin_gls_xjacobian *J, const double **dev_cell, const double **dev_face, const double **dev_own,
+                              int64_t *scratch_bytes);
+int nin_gls_xjacobian_stamp(const nin_gls_xjacobian *J, int64_t stamp[3]);
+void nin_gls_xjacobian_destroy(nin_gls_xjacobian *J);
+int nin_gls_xjacobian_linearize_host(nin_gls_xjacobian *J, const double *u_cells, const double *neumann_values);
+int nin_gls_xjacobian_apply_host(nin_gls_xjacobian *J, int32_t n, const double *dpoints, double *dnode);
+int nin_gls_xjacobian_apply_transpose_host(nin_gls_xjacobian *J, int32_t n, const double *v, double *grad_points);
+int nin_gls_xjacobian_fetch_host(nin_gls_xjacobian *J, double *cell, double *face, double *own);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].

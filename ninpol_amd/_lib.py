@@ -39,6 +39,9 @@ EXPORTS = (
     "nin_gls_rjacobian_create", "nin_gls_rjacobian_linearize", "nin_gls_rjacobian_apply", "nin_gls_rjacobian_apply_transpose",
     "nin_gls_rjacobian_buffer", "nin_gls_rjacobian_stamp", "nin_gls_rjacobian_destroy", "nin_gls_rjacobian_linearize_host",
     "nin_gls_rjacobian_apply_host", "nin_gls_rjacobian_apply_transpose_host", "nin_gls_rjacobian_fetch_host",
+    "nin_gls_xjacobian_create", "nin_gls_xjacobian_linearize", "nin_gls_xjacobian_apply", "nin_gls_xjacobian_apply_transpose",
+    "nin_gls_xjacobian_records", "nin_gls_xjacobian_stamp", "nin_gls_xjacobian_destroy", "nin_gls_xjacobian_linearize_host",
+    "nin_gls_xjacobian_apply_host", "nin_gls_xjacobian_apply_transpose_host", "nin_gls_xjacobian_fetch_host",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -120,6 +123,18 @@ def load():
     L.nin_gls_rjacobian_apply_host.argtypes = [vp, i32, vp, vp]
     L.nin_gls_rjacobian_apply_transpose_host.argtypes = [vp, i32, vp, vp]
     L.nin_gls_rjacobian_fetch_host.argtypes = [vp, vp]
+    L.nin_gls_xjacobian_create.argtypes = [vp, ctypes.POINTER(vp)]
+    L.nin_gls_xjacobian_linearize.argtypes = [vp, vp, vp, vp]
+    L.nin_gls_xjacobian_apply.argtypes = [vp, i32, vp, vp, vp]
+    L.nin_gls_xjacobian_apply_transpose.argtypes = [vp, i32, vp, vp, vp]
+    L.nin_gls_xjacobian_records.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)]
+    L.nin_gls_xjacobian_stamp.argtypes = [vp, vp]
+    L.nin_gls_xjacobian_destroy.argtypes = [vp]
+    L.nin_gls_xjacobian_destroy.restype = None
+    L.nin_gls_xjacobian_linearize_host.argtypes = [vp, vp, vp]
+    L.nin_gls_xjacobian_apply_host.argtypes = [vp, i32, vp, vp]
+    L.nin_gls_xjacobian_apply_transpose_host.argtypes = [vp, i32, vp, vp]
+    L.nin_gls_xjacobian_fetch_host.argtypes = [vp, vp, vp, vp]
     L.nin_pack_connectivity.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     L.nin_pack_table_row.argtypes = [vp, i64, i64, i64, vp]
     L.nin_diff_mag.argtypes = [vp, i64, vp]

@@ -42,6 +42,9 @@ UNITS = [
     ("kernels_gls_jacobian.hip", "hipcc", []),
     # the same Jacobian in M = 1, 3 or 6 parameters per cell: R [nnz_esup][M] streamed, 8 M bytes per entry instead of 80
     ("kernels_gls_jacobian_reduced.hip", "hipcc", []),
+    # the Jacobian in the node coordinates that one launch of the adjoint kernel's coordinate mode leaves in three record buffers,
+    # applied through the mesh geometry: J . dX node-major, J^T . v as the shape adjoint's three gathers with a factor
+    ("kernels_gls_shape_jacobian.hip", "hipcc", []),
     ("kernels_csr.hip", "hipcc", []),
     # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
     ("csr_dirty.hip", "hipcc", []),
@@ -66,6 +69,7 @@ UNITS = [
     ("abi_apply.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian_reduced.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_jacobian_points.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),
 ]

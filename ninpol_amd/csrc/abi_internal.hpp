@@ -1,4 +1,4 @@
-// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian / abi_jacobian_reduced.hip;
+// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian / abi_jacobian_reduced / abi_jacobian_points.hip;
 // exchange.hip takes the error setter): the grid behind the handle, the text of nin_last_error(), the preconditions of the entry
 // points, device memory owned by the grid or by one call, and the functions of one unit that another calls.
 #pragma once
@@ -208,8 +208,8 @@ int for_each_adjoint_bin(const DeviceGrid &d, int only, Fn fn) {
 int launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
                         hipStream_t stream, const AdjointReduce *reduce = nullptr);
 
-// ---- what the two kept Jacobians share (abi_jacobian.hip, abi_jacobian_reduced.hip) --------------------------------------------------
-// nin_gls_jacobian and nin_gls_rjacobian begin with this; each adds the buffers it owns
+// ---- what the kept Jacobians share (abi_jacobian.hip, abi_jacobian_reduced.hip, abi_jacobian_points.hip) --------------------------------------------------
+// nin_gls_jacobian, nin_gls_rjacobian and nin_gls_xjacobian begin with this; each adds the buffers it owns
 struct KeptJacobian {
     nin_grid *g = nullptr;
     int device = -1;                   // the grid's, as it was at creation: a destroy does not look at the grid, which may be gone
@@ -228,9 +228,9 @@ inline int copy_stamp(const KeptJacobian *J, int64_t stamp[3]) {
     std::copy(J->stamp, J->stamp + 3, stamp);
     return NIN_OK;
 }
-// jacobian_seed (abi_jacobian.hip): a linearisation can go on g (derivative_ready) and `seed` [nnz_esup] holds its cotangent
-// u[esup[pos]].  jacobian_apply_ready: the arguments of an apply call, the grid on its device, a linearisation to apply.
-int jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed);
+// jacobian_seed (abi_jacobian.hip): a linearisation can go on g (derivative_ready; coordinates: of the Jacobian in the node coordinates)
+// and `seed` [nnz_esup] holds its cotangent u[esup[pos]].  jacobian_apply_ready: the arguments of an apply call, the grid on its device, a linearisation to apply.
+int jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed, bool coordinates = false);
 inline int jacobian_apply_ready(const KeptJacobian *J, int32_t n, const void *in, const void *out, const char *linearize_name) {
     if (n < 1) return fail(NIN_EINVAL, "n must be >= 1");
     if (!J || !in || !out) return fail(NIN_EINVAL, "NULL argument");

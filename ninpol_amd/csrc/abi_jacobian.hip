@@ -11,10 +11,10 @@ struct nin_gls_jacobian : KeptJacobian {
 
 static const char *const kLinearize = "nin_gls_jacobian_linearize";
 
-// ---- what a linearisation of either kept Jacobian begins with (abi_jacobian_reduced.hip calls it too) -------------------------------
-int nin::jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed) {
+// ---- what a linearisation of a kept Jacobian begins with (abi_jacobian_reduced.hip and abi_jacobian_points.hip call it too) -------------------------------
+int nin::jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t stream, DevTmp<double> &seed, bool coordinates) {
     DeviceGrid &d = g->d;
-    if (int rc = derivative_ready(g, stream)) return rc;
+    if (int rc = derivative_ready(g, stream, coordinates)) return rc;
     // the cotangent of F = W u + neumann_ws b: grad_csr[pos] = u[esup[pos]], grad_neumann_ws = b
     if (int rc = dev_stage(seed, nullptr, (size_t)d.nnz_e)) return rc;
     if (int rc = launch_jac_seed(d.v, d.nnz_e, dev_u_cells, seed, stream)) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_grid.hpp"
+#include "gls_shape_chain.hpp"
 #include "launch.hpp"
 
 namespace nin {
@@ -68,19 +69,7 @@ __global__ __launch_bounds__(256) void nin_shape_face_kernel(GridView g, const i
     // so is the gradient of its three points -- also where Nbar_f itself is zero)
     const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
     const double N[3] = {(double)g.face_normal[3 * (size_t)f + 0], (double)g.face_normal[3 * (size_t)f + 1], (double)g.face_normal[3 * (size_t)f + 2]};
-    const double dot = (acc[3] * N[0] + acc[4] * N[1]) + acc[5] * N[2];
-    const double nb[3] = {(acc[3] - dot * N[0]) / nn, (acc[4] - dot * N[1]) / nn, (acc[5] - dot * N[2]) / nn};
-    const double v1b[3] = {v2[1] * nb[2] - v2[2] * nb[1], v2[2] * nb[0] - v2[0] * nb[2], v2[0] * nb[1] - v2[1] * nb[0]};
-    const double v2b[3] = {nb[1] * v1[2] - nb[2] * v1[1], nb[2] * v1[0] - nb[0] * v1[2], nb[0] * v1[1] - nb[1] * v1[0]};
-    const double dn = (double)npofa;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double share = acc[c] / dn;
-        slot[0 + c] = share + v1b[c];
-        slot[3 + c] = share - (v1b[c] + v2b[c]);
-        slot[6 + c] = share + v2b[c];
-        slot[9 + c] = npofa == 4 ? share : 0.0;
-    }
+    shape_face_chain(acc, v1, v2, nn, N, npofa, slot);
 }
 
 __global__ __launch_bounds__(256) void nin_shape_cell_kernel(int32_t n_elems, const int32_t *__restrict__ cell_ptr, const int32_t *__restrict__ cell_pos,

@@ -196,6 +196,21 @@ int launch_jacr_apply(const GridView &g, int32_t M, const double *R, int32_t n, 
 int launch_jacr_apply_transpose(const GridView &g, int32_t M, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
                                 const double *R, int32_t n, const double *v, double *grad_theta, hipStream_t stream);
 
+// the GLS Jacobian in the node coordinates applied (kernels_gls_shape_jacobian.hip), all DEVICE pointers; cell_bar
+// [nnz_esup][3], face_bar [nnz_fsup][6] and own_bar [P][3] as launch_gls_adjoint_points with grad_csr = u[esup] left them, kept (read
+// only here); inpoel / inpofa as launch_update_geometry reads them; the resident coordinates and normals are those of the linearisation.
+// launch_xjac_apply: out [n][P] = J . dX [n][P][3], kXjacApplyChunk directions per pass over the records; tangent_cell / tangent_face: scratch
+//   for launch_shape_tangent_geometry of one chunk ([min(n, chunk)][E][3] and [..][F][6]); every entry of out written.
+// launch_xjac_apply_transpose: grad_points [n][P][3] = J^T . v [n][P], kXjacTransposeChunk fields per pass; cell_share [min(n, chunk)][E][3]
+//   and face_slot [..][F][4][3] scratch; the transpose index as launch_shape_gather; with v = 1 what launch_shape_gather gives, bit for bit
+constexpr int kXjacApplyChunk = 4, kXjacTransposeChunk = 2;
+int launch_xjac_apply(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, const double *cell_bar, const double *face_bar,
+                      const double *own_bar, int32_t n, const double *dX, double *tangent_cell, double *tangent_face, double *out,
+                      hipStream_t stream);
+int launch_xjac_apply_transpose(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos,
+                                const int32_t *cell_node, const double *cell_bar, const double *face_bar, const double *own_bar, int32_t n,
+                                const double *v, double *cell_share, double *face_slot, double *grad_points, hipStream_t stream);
+
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream);
 // GLS launch plan (grid_device.hip): the class byte of every node (gls_plan.hpp: gls_class_byte of the kernel that takes it; use_group =

@@ -19,8 +19,8 @@ from . import _lib
 from . import topology as T
 from ._lib import _ptr, _vp
 from .grid import Grid
-from .jacobian import (GlsJacobian, GlsReducedJacobian, PermeabilityJacobian, REDUCED_N_PARAMS,  # noqa: F401  (their import path of old)
-                       ReducedPermeabilityJacobian, _check_n_params, reduced_basis)
+from .jacobian import (GlsJacobian, GlsReducedJacobian, GlsShapeJacobian, PermeabilityJacobian, PointsJacobian,  # noqa: F401  (their import path of old)
+                       REDUCED_N_PARAMS, ReducedPermeabilityJacobian, _check_n_params, reduced_basis)
 
 _pinned = _lib.PinnedPool()
 
@@ -995,6 +995,33 @@ class Interpolator:
         _lib.check(_lib.load().nin_gls_jacobian_linearize_host(jac._handle(), _ptr(u), _ptr(b)))
         return PermeabilityJacobian(jac)
 
+    def points_jacobian(self, variable, cell_values=None, neumann_values=None):
+        """The Jacobian of what `apply(variable, "gls")` returns, `W u` (+ `neumann_ws * neumann_values` when those are given), with
+        respect to the node coordinates, linearised ONCE at the grid's resident coordinates -- what update_points() rewrites --
+        permeability and flags, and kept on the device: a scipy LinearOperator of shape (n_points, 3 n_points), float64
+        (PointsJacobian: `matvec` = J . dX for a flattened (n_points, 3) direction, `rmatvec` = J^T . v, `matmat` / `rmatmat` batched in
+        one launch each, `release()`).  `cell_values` = u (n_elems,), default the cell variable `variable` itself; `neumann_values` = b
+        (n_points,) or None.  The sibling of points_gradient() / points_tangent() for a Krylov solver on a moving mesh: those factorise
+        every node at every call, this does so once (the cost of one points_gradient) and every product afterwards streams the kept
+        records (24 bytes per entry of esup, 48 per entry of fsup, 24 per node, on the device).  The Jacobian is kept factored through
+        the mesh geometry and is never assembled: there is no `to_scipy()`.  The products read the resident coordinates, so after a
+        later update_points() they raise (NinpolError, a RuntimeError): build a new operator at the new point; updates of the
+        permeability or the flags do not change the operator.  3-D meshes, GLS only; the Neumann values are not differentiated.
+        Host-synchronous, numpy in and out."""
+        self._check_call(variable=variable)
+        self._perm_rows()   # (ValueError without a permeability)
+        g = self.grid
+        u, _ = self._derivative_inputs(variable, (), cell_values, None)
+        b = None
+        if neumann_values is not None:
+            b = np.ascontiguousarray(neumann_values, dtype=DTYPE_F)
+            if b.shape != (g.n_points,):
+                raise ValueError(f"neumann_values must have shape ({g.n_points},), not {b.shape}.")
+        self._gls_tables_to_device(variable)
+        jac = GlsShapeJacobian(g)
+        _lib.check(_lib.load().nin_gls_xjacobian_linearize_host(jac._handle(), _ptr(u), _ptr(b)))
+        return PointsJacobian(jac)
+
     def release_scratch(self, pinned=True):
         """Give back what the object keeps between calls for speed: the grid's device scratch (weights, compacted
         triplets: ~2.3 GB of HBM at 10 M cells; the transpose index of apply_transpose(): 0.69 GB more) and, with pinned=True, the idle page-locked result buffers of the
@@ -1199,6 +1226,22 @@ class DevicePlan:
         if not u_ptr:
             raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
         J = GlsJacobian(self.grid, plan=self)
+        J.relinearize(u_ptr, neumann_values_ptr, stream)
+        return J
+
+    def linearize_points(self, u_ptr, neumann_values_ptr=0, stream=0):
+        """The Jacobian of the node values `W u + neumann_ws * b` in the node coordinates, kept on the device: a GlsShapeJacobian
+        linearised at what is resident now (geometry, flags, K), for the cell field u [n_elems] (and node values b [n_points], 0:
+        none), both device pointers.  One launch of the adjoint kernel's coordinate mode (the factorisations of one
+        launch_weights_backward_points); its launch_jvp / launch_vjp then stream the kept records through the mesh geometry instead of
+        factorising every node again.  The object owns its buffers (24 bytes per entry of esup, 48 per entry of fsup, 24 per node,
+        plus the scratch of its launches); none of the grid's buffers of launch_weights_backward_points / launch_weights_tangent_points
+        is made.  Its launches answer until the next update of the points.  3-D grids.  GLS only: a plan of IDW or LS raises instead
+        of returning zeros."""
+        self._gls_derivative("linearize_points", "do depend on the node coordinates, but they are not differentiated here", current=False)
+        if not u_ptr:
+            raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
+        J = GlsShapeJacobian(self.grid, plan=self)
         J.relinearize(u_ptr, neumann_values_ptr, stream)
         return J
 

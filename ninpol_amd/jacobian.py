@@ -1,8 +1,8 @@
-"""The GLS Jacobian in the permeability as objects the caller keeps: GlsJacobian and GlsReducedJacobian over the
-C objects nin_gls_jacobian / nin_gls_rjacobian (device pointers, asynchronous), and the scipy LinearOperators
-Interpolator.permeability_jacobian returns over them (numpy, host-synchronous).  What the two of each pair share is written once:
-_KeptJacobian -- the handle, the stamp, the lifetime -- and _JacobianOperator -- the two host products.  ninpol_amd.interpolator
-re-exports every public name."""
+"""The GLS Jacobians as objects the caller keeps: in the permeability GlsJacobian and GlsReducedJacobian over
+the C objects nin_gls_jacobian / nin_gls_rjacobian, in the node coordinates GlsShapeJacobian over nin_gls_xjacobian
+(device pointers, asynchronous), and the scipy LinearOperators Interpolator.permeability_jacobian and Interpolator.points_jacobian
+return over them (numpy, host-synchronous).  What they share is written once: _KeptJacobian -- the handle, the stamp, the lifetime
+-- and _JacobianOperator -- the two host products.  ninpol_amd.interpolator re-exports every public name."""
 import ctypes
 
 import numpy as np
@@ -16,9 +16,9 @@ DTYPE_F = np.float64
 
 
 class _KeptJacobian:
-    """What GlsJacobian and GlsReducedJacobian share: the C object `_C`_create made, its stamp, and giving it back."""
+    """What GlsJacobian, GlsReducedJacobian and GlsShapeJacobian share: the C object `_C`_create made, its stamp, and giving it back."""
 
-    _C = None       # the prefix of the C entry points: "nin_gls_jacobian" or "nin_gls_rjacobian"
+    _C = None       # the prefix of the C entry points: "nin_gls_jacobian", "nin_gls_rjacobian" or "nin_gls_xjacobian"
 
     def _create(self, grid, plan, *args):
         self.grid, self.plan = grid, plan
@@ -209,16 +209,86 @@ class GlsReducedJacobian(_KeptJacobian):
         return R
 
 
+XJAC_APPLY_CHUNK, XJAC_TRANSPOSE_CHUNK = 4, 2      # directions per pass over the records (csrc/launch.hpp: kXjacApplyChunk, kXjacTransposeChunk)
+
+
+class GlsShapeJacobian(_KeptJacobian):
+    """The Jacobian of `F(X) = W(X) u + neumann_ws(X) * b` with respect to the node coordinates at ONE linearisation point, resident on
+    the device (nin_gls_xjacobian) and kept factored through the mesh geometry: per computed node the derivative of F_p
+    in the centroids of its cells ([nnz_esup][3]), the centres and unit normals of its faces ([nnz_fsup][6]) and its own position
+    ([n_points][3]) -- what one launch of the adjoint kernel's coordinate mode leaves for the cotangent u[esup], b.  `launch_jvp` is
+    J . dX, `launch_vjp` is J^T . v, streaming passes over those records instead of a factorisation of every node, asynchronous on the
+    caller's stream, bitwise reproducible.  The geometry chain between the records and the vertices reads the grid's RESIDENT
+    coordinates and normals, so -- unlike a GlsJacobian -- the object answers only while they are those of the linearisation: after
+    Interpolator.update_points() both launches raise (NinpolError, a RuntimeError, NIN_ESTATE) and write nothing until `relinearize`.
+    Updates of the permeability or the flags do not change the answers and are not refused (`stamp`, `is_current()`).  Made by
+    DevicePlan.linearize_points(); records and scratch (`nbytes`) are its own: a launch_weights_backward_points in between does not
+    disturb it, and none of the grid's buffers of that call or of launch_weights_tangent_points is made.  One launch at a time per
+    object (the launches share its scratch)."""
+
+    _C = "nin_gls_xjacobian"
+
+    def __init__(self, grid, plan=None):
+        self._create(grid, plan)
+
+    @property
+    def record_bytes(self):
+        g = self.grid
+        return 24 * int(g.nnz_esup) + 48 * int(g._scalar("nnz_fsup")) + 24 * int(g.n_points)
+
+    @property
+    def nbytes(self):
+        """records plus the scratch the launches have made so far: 24 bytes per cell and 48 per face for each of the up to four
+        directions of a launch_jvp chunk, 24 per cell and 96 per face for each of the up to two fields of a launch_vjp chunk"""
+        return self.record_bytes + self._buffers()[3]
+
+    def relinearize(self, u_ptr, neumann_values_ptr=0, stream=0):
+        """Linearise again, at what is resident now, for u [n_elems] (and b [n_points], 0: none), device pointers: what a fresh
+        DevicePlan.linearize_points would hold, bit for bit, in the buffers this object already owns."""
+        self._linearize(_vp(u_ptr), _vp(neumann_values_ptr), ctypes.c_void_p(stream))
+
+    def launch_jvp(self, dX_ptr, out_ptr, n=1, stream=0):
+        """J . dX for n directions (nin_gls_xjacobian_apply): dX [n][n_points][3] -> out [n][n_points], every entry written (exact
+        zeros for the rows the forward gives as zero).  Asynchronous on `stream`."""
+        _lib.check(_lib.load().nin_gls_xjacobian_apply(self._handle(), int(n), _vp(dX_ptr), _vp(out_ptr), ctypes.c_void_p(stream)))
+
+    def launch_vjp(self, v_ptr, grad_points_ptr, n=1, stream=0):
+        """J^T . v for n node fields (nin_gls_xjacobian_apply_transpose): v [n][n_points] -> grad_points [n][n_points][3].  v = 1 is
+        launch_weights_backward_points(grad_csr = u[esup], grad_neumann_ws = b) at the linearisation point, bit for bit.  Asynchronous
+        on `stream` (the first call on a grid without the transpose index builds it and synchronises)."""
+        _lib.check(_lib.load().nin_gls_xjacobian_apply_transpose(self._handle(), int(n), _vp(v_ptr), _vp(grad_points_ptr), ctypes.c_void_p(stream)))
+
+    def _buffers(self):
+        c, f, o, b = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(0)
+        _lib.check(_lib.load().nin_gls_xjacobian_records(self._handle(), ctypes.byref(c), ctypes.byref(f), ctypes.byref(o), ctypes.byref(b)))
+        return int(c.value or 0), int(f.value or 0), int(o.value or 0), int(b.value)
+
+    @property
+    def record_ptrs(self):
+        """the device addresses of (cell records, face records, own records), read-only"""
+        return self._buffers()[:3]
+
+    def fetch(self):
+        """(cell (nnz_esup, 3), face (nnz_fsup, 6), own (n_points, 3)) on the host (waits for the device)"""
+        g = self.grid
+        cell, face = np.empty((int(g.nnz_esup), 3), dtype=DTYPE_F), np.empty((int(g._scalar("nnz_fsup")), 6), dtype=DTYPE_F)
+        own = np.empty((int(g.n_points), 3), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_xjacobian_fetch_host(self._handle(), _ptr(cell), _ptr(face), _ptr(own)))
+        return cell, face, own
+
+
 class _JacobianOperator(spla.LinearOperator):
-    """What PermeabilityJacobian and ReducedPermeabilityJacobian share: a (n_points, cols n_elems) operator over a kept Jacobian whose two
-    products are the *_apply_host and *_apply_transpose_host entry points of that object, one launch for k directions each."""
+    """What PermeabilityJacobian, ReducedPermeabilityJacobian and PointsJacobian share: a (n_points, cols n_elems) -- or, with per =
+    n_points, (n_points, cols n_points) -- operator over a kept Jacobian whose two products are the *_apply_host and
+    *_apply_transpose_host entry points of that object, one launch for k directions each."""
 
     _diff_mag = ()      # the optional diff_mag argument of the full Jacobian's two entry points: (None,) there, its chain folded
 
-    def __init__(self, jac, cols):
+    def __init__(self, jac, cols, per=None):
         g = jac.grid
         self.jacobian = jac
-        self._P, self._E, self._cols = int(g.n_points), int(g.n_elems), int(cols)
+        self._P, self._cols = int(g.n_points), int(cols)
+        self._E = int(g.n_elems) if per is None else int(per)       # what a column block belongs to: a cell, or (PointsJacobian) a node
         super().__init__(dtype=np.dtype(DTYPE_F), shape=(self._P, self._cols * self._E))
 
     def _jvp(self, d):        # d (k, cols E) -> (k, P)
@@ -299,3 +369,18 @@ class PermeabilityJacobian(_JacobianOperator):
         cols = 9 * esup[:, None] + np.arange(9)
         indptr = 9 * np.asarray(g.esup_ptr).astype(np.int64)
         return sp.csr_matrix((data.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)
+
+
+class PointsJacobian(_JacobianOperator):
+    """Interpolator.points_jacobian's result: the (n_points, 3 n_points) Jacobian of `apply(variable, "gls")`'s node values in the node
+    coordinates (column 3 q + c is coordinate c of node q), as a scipy LinearOperator over a GlsShapeJacobian: numpy in and out,
+    host-synchronous, one launch per matvec / rmatvec and one per batched matmat / rmatmat.  There is no to_scipy(): the Jacobian is
+    kept factored through the mesh geometry and is never assembled.  After Interpolator.update_points() the
+    products raise (NinpolError, a RuntimeError): build a new operator at the new point."""
+
+    def __init__(self, jac):
+        super().__init__(jac, 3, per=jac.grid.n_points)
+
+    _matvec, _rmatvec, _matmat, _rmatmat = (_JacobianOperator._matvec, _JacobianOperator._rmatvec, _JacobianOperator._matmat,
+                                            _JacobianOperator._rmatmat)
+    release = _JacobianOperator.release

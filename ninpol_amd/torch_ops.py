@@ -9,7 +9,8 @@ tensors) the same call gives the forward derivative, W du + dW u, with dW from t
 gives dW u along dX (nin_gls_weights_tangent_points_device).
 `CellToNode.linearize(u, K, scale)` is for a caller that needs many such products at one point (a Krylov solver): it keeps the
 Jacobian of W u in the permeability on the device (nin_gls_jacobian) and returns a Linearization whose jvp / vjp are plain tensor
-methods, one streaming pass each instead of a factorisation of every node.
+methods, one streaming pass each instead of a factorisation of every node; with wrt="points" it keeps the Jacobian in the node
+coordinates instead (nin_gls_xjacobian).
 
 Not imported by `ninpol_amd/__init__.py`: importing the package loads nothing native and does not import torch.  This module
 imports torch, and opens its device, before the native library loads ("A process that also uses a PyTorch-ROCm
@@ -174,11 +175,15 @@ class Linearization:
     """CellToNode.linearize's result: `value` = W u at one permeability, with the weights (`weights`, `neumann_ws`), the resident
     Jacobian of W u (+ neumann_ws * neumann_values) in the permeability (`jacobian`: a GlsJacobian; None for IDW / LS, whose J is 0)
     and the K / scale it was taken at.  jvp() and vjp() are plain tensor methods on torch's current stream -- no autograd graph -- and
-    cost one streaming pass each instead of a factorisation of every node: what a Krylov solver calls once per iteration."""
+    cost one streaming pass each instead of a factorisation of every node: what a Krylov solver calls once per iteration.
+    wrt="points": `jacobian` is a GlsShapeJacobian, the derivative in the node coordinates; jvp(du, dpoints=...) is
+    W du + J dX and vjp(g) is (W^T g, J^T g).  Its products read the resident coordinates and raise (RuntimeError) once
+    Interpolator.update_points() ran after the linearisation."""
 
     def __init__(self, op, u, weights, neumann_ws, jacobian, K, scale, wrt="K"):
         self.op, self.u, self.weights, self.neumann_ws, self.jacobian, self.K, self.scale = op, u, weights, neumann_ws, jacobian, K, scale
-        self.wrt = wrt       # "scale": `jacobian` is a GlsReducedJacobian in the one parameter per cell, basis K (DESIGN.md 4.14)
+        # "scale": `jacobian` is a GlsReducedJacobian in the one parameter per cell, basis K (DESIGN.md 4.14); "points": a GlsShapeJacobian
+        self.wrt = wrt
         self.value = op._spmv(weights, u)
 
     def _batch(self, t, name, shapes):
@@ -192,27 +197,47 @@ class Linearization:
         raise ValueError(f"{name} must have shape {' or '.join(map(str, shapes))}, optionally with a leading batch dimension, "
                          f"not {tuple(t.shape)}")
 
-    def jvp(self, du=None, dK=None, dscale=None):
+    def jvp(self, du=None, dK=None, dscale=None, dpoints=None):
         """W du + J (scale * dK + dscale * K): the change of `value` along du (n_elems,), dK shaped like K and dscale (n_elems,), each
         optional, all with the same optional leading batch dimension.  Returns (n_points,) or (k, n_points).  A linearisation taken
-        with wrt="scale" gives W du + R dscale from its (nnz_esup,) Jacobian, with no (n_elems, 9) temporary, and takes no dK."""
+        with wrt="scale" gives W du + R dscale from its (nnz_esup,) Jacobian, with no (n_elems, 9) temporary, and takes no dK.  One
+        taken with wrt="points" gives W du + J dX for dpoints (n_points, 3) and takes neither dK nor dscale; the others take no
+        dpoints."""
         op = self.op
         E, P = op.n_elems, op.n_points
         if self.wrt == "scale" and dK is not None:
             raise ValueError('a linearisation taken with wrt="scale" holds no derivative in K: dK must be None (take one with wrt="K")')
+        if self.wrt == "points":
+            for t, name in ((dK, "dK"), (dscale, "dscale")):
+                if t is not None:
+                    raise ValueError(f'a linearisation taken with wrt="points" holds no derivative in K: {name} must be None (take one with '
+                                     'wrt="K")')
+        elif dpoints is not None:
+            raise ValueError(f'a linearisation taken with wrt="{self.wrt}" holds no derivative in the node coordinates: dpoints must be None '
+                             '(take one with wrt="points")')
         if dscale is not None and (self.scale is None or self.K is None):
             raise ValueError("dscale needs a linearisation taken with K and scale")
-        given = [(t, name, shapes) for t, name, shapes in ((du, "du", ((E,),)), (dK, "dK", ((E, 3, 3), (E, 9))), (dscale, "dscale", ((E,),)))
+        given = [(t, name, shapes) for t, name, shapes in ((du, "du", ((E,),)), (dK, "dK", ((E, 3, 3), (E, 9))), (dscale, "dscale", ((E,),)),
+                                                           (dpoints, "dpoints", ((P, 3),)))
                  if t is not None]
         parts = {name: self._batch(t, name, shapes) for t, name, shapes in given}
         flags = {b for _, b in parts.values()}
         ks = {int(t.shape[0]) for t, _ in parts.values()}
         if len(flags) > 1 or len(ks) > 1:
-            raise ValueError("du, dK and dscale must share their leading batch dimension")
+            raise ValueError("du, dK, dscale and dpoints must share their leading batch dimension")
         batched, k = (flags.pop(), ks.pop()) if parts else (False, 1)
         out = None
         if du is not None:
             out = op._spmv(self.weights, parts["du"][0].contiguous())
+        if self.wrt == "points":
+            if dpoints is not None:
+                dx = parts["dpoints"][0].contiguous()
+                jv = torch.empty((k, P), dtype=torch.float64, device=op.device)
+                self.jacobian.launch_jvp(dx.data_ptr(), jv.data_ptr(), k, op._stream())
+                out = jv if out is None else out + jv
+            if out is None:
+                out = torch.zeros((k, P), dtype=torch.float64, device=op.device)
+            return out if batched else out[0]
         if self.wrt == "scale":
             if dscale is not None and self.jacobian is not None:
                 ds = parts["dscale"][0].contiguous()
@@ -241,13 +266,19 @@ class Linearization:
 
     def vjp(self, g):
         """g (n_points,) or (k, n_points) -> (W^T g, scale * J^T g shaped like K, sum_k K * J^T g or None without a scale): the
-        gradients of <g, value> in u, K and scale, what backward() of CellToNode(u, K, scale) returns."""
+        gradients of <g, value> in u, K and scale, what backward() of CellToNode(u, K, scale) returns.  A linearisation taken with
+        wrt="points" returns (W^T g, J^T g shaped (n_points, 3)): the gradients in u and in the node coordinates, what backward() of
+        CellToNode(u, points=X) returns."""
         op = self.op
         E = op.n_elems
         g, batched = self._batch(g, "g", ((op.n_points,),))
         g = g.contiguous()
         k = int(g.shape[0])
         gu = op._spmv_transpose(self.weights, g)
+        if self.wrt == "points":
+            gx = torch.empty((k, op.n_points, 3), dtype=torch.float64, device=op.device)
+            self.jacobian.launch_vjp(g.data_ptr(), gx.data_ptr(), k, op._stream())
+            return (gu, gx) if batched else (gu[0], gx[0])
         if self.wrt == "scale":      # (W^T g, None, R^T g): the gradient in scale straight from the reduced Jacobian
             if self.jacobian is not None:
                 gscale = torch.empty((k, E), dtype=torch.float64, device=op.device)
@@ -409,7 +440,7 @@ class CellToNode(torch.nn.Module):
             return _ConstantWeightsFn.apply(K, scale, self.weights), self.neumann_ws
         return _GlsWeightsFn.apply(K, scale, self, points)
 
-    def linearize(self, u, K=None, scale=None, neumann_values=None, wrt="K"):
+    def linearize(self, u, K=None, scale=None, points=None, neumann_values=None, wrt="K"):
         """Linearise `forward(u, K, scale)` once, for many jvp / vjp products at that point: u float64 (n_elems,) on the plan's device
         (one field).  With K (and scale) it first does what weights_of does -- scale * K becomes the grid's resident permeability --
         and computes fresh weights; without, the weights of what is resident now.  Returns a Linearization: `value` = W u, `jvp(du, dK,
@@ -421,11 +452,21 @@ class CellToNode(torch.nn.Module):
         wrt="scale" (needs K and scale): the permeability scale * K moves along the one parameter per cell only, d perm / d scale = K,
         and the Jacobian kept is the reduced one with the per-cell basis K (a GlsReducedJacobian, 8 bytes per entry of esup instead of
         80).  `jvp(du, dscale=...)` is then W du + R dscale with no (n_elems, 9) temporary and takes no dK; `vjp(g)` returns (W^T g,
-        None, R^T g)."""
-        if wrt not in ("K", "scale"):
-            raise ValueError(f'wrt must be "K" or "scale", not {wrt!r}')
+        None, R^T g).
+
+        points: float64 (n_points, 3) on the plan's device (3-D meshes, GLS) -- given to Interpolator.update_points() first, as in
+        forward(): the mesh moves there and `value` is bit for bit what forward(u, K, scale, points) returns.  wrt="points": the
+        Jacobian kept is the one in the node coordinates (a GlsShapeJacobian, DESIGN.md 4.18: 24 bytes per entry of esup, 48 per entry
+        of fsup, 24 per node), `jvp(du, dpoints=...)` is W du + J dX and takes neither dK nor dscale, `vjp(g)` returns (W^T g, J^T g).
+        Its products read the resident coordinates: after a later update_points() they raise RuntimeError -- linearise again.  IDW /
+        LS depend on the coordinates too, but that derivative is not provided: ValueError, never zeros."""
+        if wrt not in ("K", "scale", "points"):
+            raise ValueError(f'wrt must be "K", "scale" or "points", not {wrt!r}')
         if wrt == "scale" and (K is None or scale is None):
             raise ValueError('wrt="scale" needs K and scale: the derivative is taken along scale at the permeability scale * K')
+        if wrt == "points" and self.plan.method != "gls":
+            raise ValueError(f"the weights of '{self.plan.method}' do depend on the node coordinates, but they are not differentiated "
+                             'here: wrt="points" is GLS only')
         if not isinstance(u, torch.Tensor):
             raise TypeError(f"u must be a torch.Tensor, not {type(u).__name__}")
         if u.dtype != torch.float64:
@@ -442,10 +483,11 @@ class CellToNode(torch.nn.Module):
         if K is None and scale is not None:
             raise ValueError("scale needs K")
         u = u.detach().contiguous()
-        if K is not None:
-            with torch.no_grad():
-                weights, neumann_ws = self.weights_of(K.detach(), None if scale is None else scale.detach())
-            K, scale = K.detach(), None if scale is None else scale.detach()
+        if K is not None or points is not None:
+            with torch.no_grad():      # (weights_of checks points, moves the mesh there and makes scale * K resident)
+                weights, neumann_ws = self.weights_of(None if K is None else K.detach(), None if scale is None else scale.detach(),
+                                                      None if points is None else points.detach())
+            K, scale = None if K is None else K.detach(), None if scale is None else scale.detach()
         elif self.plan.method == "gls":
             weights, neumann_ws = self._launch_weights()
         else:
@@ -456,6 +498,8 @@ class CellToNode(torch.nn.Module):
             if wrt == "scale":
                 basis = K.reshape(self.n_elems, 9).contiguous()       # read by the launch below only (stream-ordered)
                 jac = self.plan.linearize_reduced(u.data_ptr(), 1, basis.data_ptr(), True, 0 if b is None else b.data_ptr(), self._stream())
+            elif wrt == "points":
+                jac = self.plan.linearize_points(u.data_ptr(), 0 if b is None else b.data_ptr(), self._stream())
             else:
                 jac = self.plan.linearize(u.data_ptr(), 0 if b is None else b.data_ptr(), self._stream())
         return Linearization(self, u, weights, neumann_ws, jac, K, scale, wrt)

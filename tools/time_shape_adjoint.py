@@ -11,7 +11,13 @@ WARMUP calls first, median of REPS each; ms and ns per node.  The K adjoint's bu
 makes its own (at 216^3 hexahedra: 6.4 GB and 10.7 GB).
 
 --tangent: instead, the tangent in the node coordinates (DevicePlan.launch_weights_tangent_points) with n_tangents = 1
-and 4 beside the forward launch, the coordinate backward and the K tangent (n_tangents = 1 and 4) of the same session."""
+and 4 beside the forward launch, the coordinate backward and the K tangent (n_tangents = 1 and 4) of the same session.
+
+--jacobian: instead, the kept Jacobian in the node coordinates (DevicePlan.linearize_points; default meshes hex64 and
+del20, hex216 where the memory allows): the linearisation, GlsShapeJacobian.launch_jvp and launch_vjp with 1 and 4 directions, beside
+the one-shot coordinate tangent and coordinate backward, the three gathers alone and the forward launch of the same session.  Next to
+the times: the algorithmic bytes of each product -- records and indices counted once per chunk of directions, the gathered geometry
+tangents / shares / slots and the in- and outputs once per direction -- and the rate they give."""
 import os
 import sys
 
@@ -25,8 +31,76 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from time_adjoint import CASES, median_ms  # noqa: E402
 
 
+APPLY_CHUNK, TRANSPOSE_CHUNK = 4, 2     # directions per pass over the records (csrc/launch.hpp)
+
+
+def jacobian_bytes(g, nnz_e, n):
+    """(J . dX, J^T . v): the bytes the algorithm needs for n directions"""
+    P, E, F, nnz_f = int(g.n_points), int(g.n_elems), int(g.n_faces), int(g._scalar("nnz_fsup"))
+    chunks = lambda c: -(-n // c)                                        # noqa: E731
+    records = 24 * nnz_e + 48 * nnz_f + 24 * P
+    # J . dX: per chunk the records, esup / fsup and their row pointers; per direction dX read by the geometry kernels (through inpoel,
+    # inpofa) and by the node kernel, dC / dFN written once and gathered per entry, the output
+    jvp = chunks(APPLY_CHUNK) * (records + 4 * (nnz_e + nnz_f) + 16 * P + 32 * E + 16 * F) + \
+        n * (24 * P + 24 * E + 48 * F + 24 * nnz_e + 48 * nnz_f + 24 * P + 8 * P)
+    # J^T . v: per chunk the records, the transpose index (ptr, pos, node), esup / fsup / inpofa; per field v, the slots and shares
+    # written once and gathered per entry, the output
+    vjp = chunks(TRANSPOSE_CHUNK) * (records + 8 * nnz_e + 4 * E + 4 * (nnz_e + nnz_f) + 16 * P + 16 * F + 16 * nnz_f) + \
+        n * (8 * P + 96 * F + 24 * E + 24 * nnz_e + 24 * nnz_f + 24 * P)
+    return jvp, vjp
+
+
+def time_jacobian(name, I, plan, st, t_fwd):
+    g = I.grid
+    P, E = int(g.n_points), int(g.n_elems)
+    ghat = torch.rand(plan.nnz, dtype=torch.float64, device="cuda") - 0.5
+    u = torch.rand(E, dtype=torch.float64, device="cuda") - 0.5
+    b = torch.rand(P, dtype=torch.float64, device="cuda") - 0.5
+    gpts = torch.empty((P, 3), dtype=torch.float64, device="cuda")
+    shape = lambda: plan.launch_weights_backward_points(ghat.data_ptr(), gpts.data_ptr(), stream=st.cuda_stream)   # noqa: E731
+    t_back = median_ms(shape, st)
+    try:
+        os.environ["NIN_GLS_ADJ_ONLY"] = "9"              # no bin: the three gathers alone
+        t_gather = median_ms(shape, st)
+    finally:
+        del os.environ["NIN_GLS_ADJ_ONLY"]
+    del gpts
+    I.release_scratch()                                    # the one-shot adjoint's buffers go before the object's come
+    t = {}
+    for n in (1, 4):
+        dX = torch.rand((n, P, 3), dtype=torch.float64, device="cuda") - 0.5
+        dw = torch.empty((n, plan.nnz), dtype=torch.float64, device="cuda")
+        t["tangent", n] = median_ms(lambda: plan.launch_weights_tangent_points(dX.data_ptr(), dw.data_ptr(), n, stream=st.cuda_stream), st)
+        del dX, dw
+    I.release_scratch()
+    J = plan.linearize_points(u.data_ptr(), b.data_ptr(), st.cuda_stream)
+    t_lin = median_ms(lambda: J.relinearize(u.data_ptr(), b.data_ptr(), st.cuda_stream), st)
+    for n in (1, 4):
+        dX = torch.rand((n, P, 3), dtype=torch.float64, device="cuda") - 0.5
+        v = torch.rand((n, P), dtype=torch.float64, device="cuda") - 0.5
+        out = torch.full((n, P), float("nan"), dtype=torch.float64, device="cuda")
+        grad = torch.full((n, P, 3), float("nan"), dtype=torch.float64, device="cuda")
+        t["jvp", n] = median_ms(lambda: J.launch_jvp(dX.data_ptr(), out.data_ptr(), n, st.cuda_stream), st)
+        t["vjp", n] = median_ms(lambda: J.launch_vjp(v.data_ptr(), grad.data_ptr(), n, st.cuda_stream), st)
+        assert torch.isfinite(out).all() and torch.isfinite(grad).all()
+        del dX, v, out, grad
+    assert g._scalar("gls_shape_contrib_bytes") == 0 and g._scalar("gls_shape_tangent_bytes") == 0
+    print(f"{name}: kept records {J.record_bytes / 1e9:.3f} GB, with the scratch of 4 directions {J.nbytes / 1e9:.3f} GB", flush=True)
+    print(f"{name}: forward launch {t_fwd:.3f} ms; one-shot coordinate backward {t_back:.3f} ms (its gathers {t_gather:.3f} ms); one-shot "
+          f"coordinate tangent {t['tangent', 1]:.3f} ms (1 direction), {t['tangent', 4]:.3f} ms (4); linearize {t_lin:.3f} ms", flush=True)
+    for key, one_shot, i in (("jvp", t["tangent", 1], 0), ("vjp", t_back, 1)):
+        for n in (1, 4):
+            by = jacobian_bytes(g, plan.nnz, n)[i]
+            print(f"{name}: launch_{key} n={n}: {t[key, n]:.4f} ms, {by / 1e9:.4f} GB algorithmic = {by / t[key, n] / 1e9:.3f} TB/s "
+                  f"({by / t[key, n] / 1e9 / 6.3 * 100:.0f} % of 6.3 TB/s)" + (f"; one-shot / kept = {one_shot / t[key, 1]:.1f}" if n == 1 else
+                  f"; a further direction {(t[key, 4] - t[key, 1]) / 3:.4f} ms = {(t[key, 4] - t[key, 1]) / 3 / t[key, 1] * 100:.0f} % of the first"),
+                  flush=True)
+    J.release()
+
+
 def main():
-    names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["hex216", "del54"]
+    jacobian = "--jacobian" in sys.argv
+    names = [a for a in sys.argv[1:] if not a.startswith("--")] or (["hex64", "del20"] if jacobian else ["hex216", "del54"])
     if not torch.cuda.is_available():
         raise SystemExit("time_shape_adjoint.py needs a GPU")
     torch.cuda.init()
@@ -46,6 +120,11 @@ def main():
         print(f"{name}: P={P} E={E} F={int(g.n_faces)} nnz_esup={plan.nnz} nnz_fsup={g._scalar('nnz_fsup')}; adjoint bins {g.gls_adjoint_plan()}",
               flush=True)
         t_fwd = median_ms(forward, st)
+        if jacobian:
+            time_jacobian(name, I, plan, st, t_fwd)
+            I.release_scratch()
+            del plan, I, ghat, w, nws
+            continue
         if "--tangent" in sys.argv:
             gpts = torch.empty((P, 3), dtype=torch.float64, device="cuda")
             t_x = median_ms(lambda: plan.launch_weights_backward_points(ghat.data_ptr(), gpts.data_ptr(), stream=st.cuda_stream), st)
