@@ -656,6 +656,36 @@ int nin_gls_xjacobian_apply_host(nin_gls_xjacobian *J, int32_t n, const double *
 int nin_gls_xjacobian_apply_transpose_host(nin_gls_xjacobian *J, int32_t n, const double *v, double *grad_points);
 int nin_gls_xjacobian_fetch_host(nin_gls_xjacobian *J, double *cell, double *face, double *own);
 
+/* ---- the same Jacobian assembled: a block-CSR matrix on the device ----------------------------------------------------------------
+ * A simulator that assembles a global sparse Jacobian, builds an ILU or AMG preconditioner or calls a direct solver needs the block
+ * d(W u + neumann_ws b) / dX as a matrix.  J is [n_points][3 n_points]: row p, column 3 q + c; block (p, q) = dF_p / d x_q, three
+ * doubles.  The columns of row p come from the connectivity alone,
+ *   C(p) = {p} + the vertices of the cells in esup[p] + the points of the faces in fsup[p],   ascending in q, each once,
+ * so the pattern -- block_ptr [n_points + 1] (int64: a large mesh has more than 2^31 blocks), block_col [n_blocks] (int32) -- is made
+ * once per object, by the first call below that needs it (one wait for the stream, for the count), and survives linearisations and
+ * every update of the grid: a caller can keep a symbolic factorisation.  It counts in nin_gls_xjacobian_records' scratch_bytes
+ * (8 (n_points + 1) + 4 n_blocks) from then on.  Rows the forward gives as zero keep their blocks, as exact zeros.
+ * The values [n_blocks][3] are assembled per linearisation from the object's records through the RESIDENT coordinates and normals:
+ * block (p, q) = own[p] if q == p, + cell[pos(p, e)] / n_e for the cells e of esup[p] that contain q in row order, + for the faces f of
+ * fsup[p] with q their point k in row order the slot values 3 k .. 3 k + 2 of the face chain applied to the one record face[pos(p, f)].
+ * That order is fixed and depends on the row alone: no atomics, two calls agree bit for bit, every entry is written (no memset).
+ *
+ * nin_gls_xjacobian_pattern: the object's own device arrays, valid until nin_gls_xjacobian_destroy; needs no linearisation.
+ * nin_gls_xjacobian_pattern_copy: the same arrays copied device-to-device into the caller's buffers ([n_points + 1] and [n_blocks]),
+ *   asynchronous on `stream` once the pattern exists.
+ * nin_gls_xjacobian_assemble: dev_values [n_blocks][3]; asynchronous on `stream` once the pattern exists.  It reads the resident
+ *   geometry, so as the apply calls: NIN_ESTATE before the first linearisation and after an update of the points, nothing written;
+ *   updates of the permeability or the flags are not refused.
+ * nin_gls_xjacobian_pattern_host / _assemble_host: the same with HOST pointers, synchronous; block_col may be NULL to ask for
+ *   *n_blocks alone.
+ * All refuse a NULL object or a NULL required pointer with NIN_EINVAL; NIN_EINVAL for a grid that is not 3-D. */
+int nin_gls_xjacobian_pattern(nin_gls_xjacobian *J, int64_t *n_blocks, const int64_t **dev_block_ptr, const int32_t **dev_block_col,
+                              void *stream);
+int nin_gls_xjacobian_pattern_copy(nin_gls_xjacobian *J, int64_t *dev_block_ptr_out, int32_t *dev_block_col_out, void *stream);
+int nin_gls_xjacobian_assemble(nin_gls_xjacobian *J, double *dev_values, void *stream);
+int nin_gls_xjacobian_pattern_host(nin_gls_xjacobian *J, int64_t *block_ptr, int32_t *block_col, int64_t *n_blocks);
+int nin_gls_xjacobian_assemble_host(nin_gls_xjacobian *J, double *values);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].

@@ -42,6 +42,8 @@ EXPORTS = (
     "nin_gls_xjacobian_create", "nin_gls_xjacobian_linearize", "nin_gls_xjacobian_apply", "nin_gls_xjacobian_apply_transpose",
     "nin_gls_xjacobian_records", "nin_gls_xjacobian_stamp", "nin_gls_xjacobian_destroy", "nin_gls_xjacobian_linearize_host",
     "nin_gls_xjacobian_apply_host", "nin_gls_xjacobian_apply_transpose_host", "nin_gls_xjacobian_fetch_host",
+    "nin_gls_xjacobian_pattern", "nin_gls_xjacobian_pattern_copy", "nin_gls_xjacobian_assemble", "nin_gls_xjacobian_pattern_host",
+    "nin_gls_xjacobian_assemble_host",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -135,6 +137,11 @@ def load():
     L.nin_gls_xjacobian_apply_host.argtypes = [vp, i32, vp, vp]
     L.nin_gls_xjacobian_apply_transpose_host.argtypes = [vp, i32, vp, vp]
     L.nin_gls_xjacobian_fetch_host.argtypes = [vp, vp, vp, vp]
+    L.nin_gls_xjacobian_pattern.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
+    L.nin_gls_xjacobian_pattern_copy.argtypes = [vp, vp, vp, vp]
+    L.nin_gls_xjacobian_assemble.argtypes = [vp, vp, vp]
+    L.nin_gls_xjacobian_pattern_host.argtypes = [vp, vp, vp, ctypes.POINTER(i64)]
+    L.nin_gls_xjacobian_assemble_host.argtypes = [vp, vp]
     L.nin_pack_connectivity.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     L.nin_pack_table_row.argtypes = [vp, i64, i64, i64, vp]
     L.nin_diff_mag.argtypes = [vp, i64, vp]

@@ -45,6 +45,9 @@ UNITS = [
     # the Jacobian in the node coordinates that one launch of the adjoint kernel's coordinate mode leaves in three record buffers,
     # applied through the mesh geometry: J . dX node-major, J^T . v as the shape adjoint's three gathers with a factor
     ("kernels_gls_shape_jacobian.hip", "hipcc", []),
+    # the same records assembled into a block-CSR matrix: a symbolic pass per object (the column set of every row), a numeric pass per
+    # linearisation
+    ("kernels_gls_shape_assemble.hip", "hipcc", []),
     ("kernels_csr.hip", "hipcc", []),
     # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
     ("csr_dirty.hip", "hipcc", []),

@@ -1,6 +1,7 @@
 // abi_jacobian_points.hip -- the C ABI, part 8: the GLS Jacobian in the node coordinates as an object the caller keeps: one
 // launch of the adjoint kernel's coordinate mode linearises, and the kernels of kernels_gls_shape_jacobian.hip apply J and J^T from the
-// object's own records through the grid's resident geometry.
+// object's own records through the grid's resident geometry.  The kernels of kernels_gls_shape_assemble.hip assemble the same records
+// into a block-CSR matrix whose pattern the object makes once and keeps.
 #include "abi_internal.hpp"
 
 using namespace nin;
@@ -13,7 +14,15 @@ struct nin_gls_xjacobian : KeptJacobian {
     // and [tr_n][F][4][3], tr_n <= kXjacTransposeChunk)
     double *tan_cell = nullptr, *tan_face = nullptr, *tr_share = nullptr, *tr_slot = nullptr;
     int32_t tan_n = 0, tr_n = 0;
-    int64_t scratch_bytes() const { return (int64_t)tan_n * (24 * cells + 48 * faces) + (int64_t)tr_n * (24 * cells + 96 * faces); }
+    // the pattern of the assembled matrix, made by the first call that needs it and kept until the object goes: block_ptr [P + 1],
+    // block_col [n_blocks] ascending within a row; from the connectivity alone, so no update of the grid touches it
+    int64_t *block_ptr = nullptr;
+    int32_t *block_col = nullptr;
+    int64_t n_blocks = 0, points = 0;   // (points: P of the grid at creation)
+    int64_t scratch_bytes() const {
+        return (int64_t)tan_n * (24 * cells + 48 * faces) + (int64_t)tr_n * (24 * cells + 96 * faces) +
+               (block_col ? 8 * (points + 1) + 4 * n_blocks : 0);
+    }
     int64_t cells = 1, faces = 1;   // max(E, 1) and max(F, 1) of the grid at creation
 };
 
@@ -52,6 +61,7 @@ int nin_gls_xjacobian_create(nin_grid *g, nin_gls_xjacobian **out) {
     J->device = d.device;
     J->cells = (int64_t)at_least_one(d.v.n_elems);
     J->faces = (int64_t)at_least_one(d.v.n_faces);
+    J->points = (int64_t)g->h.n_points;
     const size_t cb = at_least_one(d.nnz_e) * 3 * sizeof(double), fb = at_least_one(d.nnz_f) * 6 * sizeof(double),
                  ob = at_least_one(g->h.n_points) * 3 * sizeof(double);
     hipError_t e = hipMalloc((void **)&J->cell, cb);
@@ -68,7 +78,8 @@ int nin_gls_xjacobian_create(nin_grid *g, nin_gls_xjacobian **out) {
 void nin_gls_xjacobian_destroy(nin_gls_xjacobian *J) {
     if (!J) return;
     if (J->device >= 0) (void)hipSetDevice(J->device);
-    for (double *p : {J->cell, J->face, J->own, J->tan_cell, J->tan_face, J->tr_share, J->tr_slot})
+    for (void *p : {(void *)J->cell, (void *)J->face, (void *)J->own, (void *)J->tan_cell, (void *)J->tan_face, (void *)J->tr_share,
+                    (void *)J->tr_slot, (void *)J->block_ptr, (void *)J->block_col})
         if (p) (void)hipFree(p);   // (waits for the device)
     delete J;
 }
@@ -147,6 +158,81 @@ int nin_gls_xjacobian_records(nin_gls_xjacobian *J, const double **dev_cell, con
 
 int nin_gls_xjacobian_stamp(const nin_gls_xjacobian *J, int64_t stamp[3]) { return copy_stamp(J, stamp); }
 
+// ---- the assembled matrix -------------------------------------------------------------------------------------------------
+// The pattern of the object, made if it is not there: count, scan, one synchronisation of `stream` for the number of blocks, fill.
+// NIN_GLS_XJAC_PATTERN_FORCE_SLOW (testing switch, read when the pattern is made): every row through the symbolic pass's slow path.
+static int ensure_pattern(nin_gls_xjacobian *J, hipStream_t stream) {
+    if (J->block_col) return NIN_OK;
+    nin_grid *g = J->g;
+    DeviceGrid &d = g->d;
+    if (int rc = on_device(g, kHintKernels)) return rc;
+    if (d.v.dim != 3)
+        return fail(NIN_EINVAL, "the derivative with respect to the node coordinates is for 3-D grids only (this grid is %d-D)", (int)d.v.dim);
+    HIP_TRY(hipSetDevice(d.device));
+    if (int rc = ensure_update_inputs(g)) return rc;
+    const int force_slow = getenv("NIN_GLS_XJAC_PATTERN_FORCE_SLOW") != nullptr;
+    const int32_t P = d.v.n_points;
+    DevTmp<int64_t> count, ptr;
+    DevTmp<char> tmp;
+    DevTmp<int32_t> col;
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipMalloc((void **)&count, ((size_t)P + 1) * sizeof(int64_t)));
+    HIP_TRY(hipMalloc((void **)&ptr, ((size_t)P + 1) * sizeof(int64_t)));
+    if (P == 0) HIP_TRY(hipMemsetAsync(count, 0, sizeof(int64_t), stream));
+    int rc = launch_xjac_pattern_count(d.v, d.up_inpoel, d.up_inpofa, force_slow, count, stream);
+    if (!rc) rc = xjac_pattern_scan(nullptr, &tmp_bytes, count, ptr, P, stream);
+    if (rc) return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipMalloc((void **)&tmp, std::max<size_t>(tmp_bytes, 1)));
+    if (xjac_pattern_scan(tmp, &tmp_bytes, count, ptr, P, stream)) return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    int64_t n_blocks = 0;
+    HIP_TRY(hipMemcpyAsync(&n_blocks, ptr.p + P, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    hipError_t e = hipMalloc((void **)&col, at_least_one(n_blocks) * sizeof(int32_t));
+    if (e != hipSuccess) return fail(NIN_ENOMEM, "hipMalloc(%zu bytes): %s", at_least_one(n_blocks) * sizeof(int32_t), hipGetErrorString(e));
+    if (launch_xjac_pattern_fill(d.v, d.up_inpoel, d.up_inpofa, force_slow, ptr, col, stream))
+        return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    J->block_ptr = ptr.p;
+    J->block_col = col.p;
+    ptr.p = nullptr;   // (the object's now)
+    col.p = nullptr;
+    J->n_blocks = n_blocks;
+    return NIN_OK;   // (count and tmp are freed on the way out: hipFree waits for the kernels that read them)
+}
+
+int nin_gls_xjacobian_pattern(nin_gls_xjacobian *J, int64_t *n_blocks, const int64_t **dev_block_ptr, const int32_t **dev_block_col, void *stream) {
+    if (!J || !n_blocks || !dev_block_ptr || !dev_block_col) return fail(NIN_EINVAL, "NULL argument");
+    if (int rc = ensure_pattern(J, static_cast<hipStream_t>(stream))) return rc;
+    *n_blocks = J->n_blocks;
+    *dev_block_ptr = J->block_ptr;
+    *dev_block_col = J->block_col;
+    return NIN_OK;
+}
+
+int nin_gls_xjacobian_pattern_copy(nin_gls_xjacobian *J, int64_t *dev_block_ptr_out, int32_t *dev_block_col_out, void *stream_) {
+    if (!J || !dev_block_ptr_out || !dev_block_col_out) return fail(NIN_EINVAL, "NULL argument");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (int rc = ensure_pattern(J, stream)) return rc;
+    HIP_TRY(hipSetDevice(J->g->d.device));
+    HIP_TRY(hipMemcpyAsync(dev_block_ptr_out, J->block_ptr, ((size_t)J->points + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+    if (J->n_blocks > 0)
+        HIP_TRY(hipMemcpyAsync(dev_block_col_out, J->block_col, (size_t)J->n_blocks * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    return NIN_OK;
+}
+
+int nin_gls_xjacobian_assemble(nin_gls_xjacobian *J, double *dev_values, void *stream_) {
+    if (int rc = xjacobian_apply_ready(J, 1, dev_values, dev_values)) return rc;
+    nin_grid *g = J->g;
+    DeviceGrid &d = g->d;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(d.device));
+    int rc = ensure_update_inputs(g);   // (every time: nin_grid_release_scratch may have dropped them)
+    if (!rc) rc = ensure_pattern(J, stream);
+    if (rc) return rc;
+    rc = launch_xjac_assemble(d.v, d.up_inpoel, d.up_inpofa, J->cell, J->face, J->own, J->block_ptr, J->block_col, dev_values, stream);
+    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return NIN_OK;
+}
+
 // ---- host pointers: what Interpolator.points_jacobian calls (synchronous) -------------------------------------------------------------
 int nin_gls_xjacobian_linearize_host(nin_gls_xjacobian *J, const double *u_cells, const double *neumann_values) {
     if (!J || !u_cells) return fail(NIN_EINVAL, "NULL argument");
@@ -185,4 +271,25 @@ int nin_gls_xjacobian_fetch_host(nin_gls_xjacobian *J, double *cell, double *fac
     if (int rc = dev_fetch(cell, J->cell, (size_t)g->d.nnz_e * 3)) return rc;
     if (int rc = dev_fetch(face, J->face, (size_t)g->d.nnz_f * 6)) return rc;
     return dev_fetch(own, J->own, (size_t)g->h.n_points * 3);
+}
+
+int nin_gls_xjacobian_pattern_host(nin_gls_xjacobian *J, int64_t *block_ptr, int32_t *block_col, int64_t *n_blocks) {
+    if (!J || !block_ptr || !n_blocks) return fail(NIN_EINVAL, "NULL argument");
+    if (int rc = ensure_pattern(J, nullptr)) return rc;
+    HIP_TRY(hipSetDevice(J->g->d.device));
+    HIP_TRY(hipMemcpy(block_ptr, J->block_ptr, ((size_t)J->points + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (block_col && J->n_blocks > 0)   // (NULL: the caller asks for the size)
+        HIP_TRY(hipMemcpy(block_col, J->block_col, (size_t)J->n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *n_blocks = J->n_blocks;
+    return NIN_OK;
+}
+
+int nin_gls_xjacobian_assemble_host(nin_gls_xjacobian *J, double *values) {
+    if (int rc = xjacobian_apply_ready(J, 1, values, values)) return rc;
+    HIP_TRY(hipSetDevice(J->g->d.device));
+    if (int rc = ensure_pattern(J, nullptr)) return rc;
+    DevTmp<double> dv;
+    if (int rc = dev_stage(dv, nullptr, 3 * (size_t)J->n_blocks)) return rc;
+    if (int rc = nin_gls_xjacobian_assemble(J, dv, nullptr)) return rc;
+    return dev_fetch(values, dv, 3 * (size_t)J->n_blocks);
 }

@@ -211,6 +211,20 @@ int launch_xjac_apply_transpose(const GridView &g, const int32_t *inpofa, const 
                                 const int32_t *cell_node, const double *cell_bar, const double *face_bar, const double *own_bar, int32_t n,
                                 const double *v, double *cell_share, double *face_slot, double *grad_points, hipStream_t stream);
 
+// the same Jacobian assembled as a block-CSR matrix (kernels_gls_shape_assemble.hip), all DEVICE pointers: block (p, q) =
+// dF_p / d x_q [3] for q in C(p) = {p} + the vertices of the cells of esup[p] + the points of the faces of fsup[p], ascending.
+// The pattern, from the connectivity alone: launch_xjac_pattern_count writes |C(p)| to count [P + 1] (count[P] = 0), xjac_pattern_scan
+//   is the exclusive sum of those P + 1 values into block_ptr (tmp = null: *tmp_bytes is set to what it needs), launch_xjac_pattern_fill
+//   writes the columns at block_ptr[p] into block_col [block_ptr[P]].  force_slow != 0: every row through the path that stages nothing
+//   (the same bytes).
+// launch_xjac_assemble: values [block_ptr[P]][3] from the kept records through the resident coordinates and normals; every entry written.
+int launch_xjac_pattern_count(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, int force_slow, int64_t *count, hipStream_t stream);
+int xjac_pattern_scan(void *tmp, size_t *tmp_bytes, const int64_t *count, int64_t *block_ptr, int32_t n_points, hipStream_t stream);
+int launch_xjac_pattern_fill(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, int force_slow, const int64_t *block_ptr,
+                             int32_t *block_col, hipStream_t stream);
+int launch_xjac_assemble(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, const double *cell_bar, const double *face_bar,
+                         const double *own_bar, const int64_t *block_ptr, const int32_t *block_col, double *values, hipStream_t stream);
+
 // kernels_csr.hip: dst[e] = (src[3 e], src[3 e + 1], src[3 e + 2], 0)
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream);
 // GLS launch plan (grid_device.hip): the class byte of every node (gls_plan.hpp: gls_class_byte of the kernel that takes it; use_group =

@@ -1004,8 +1004,9 @@ class Interpolator:
         (n_points,) or None.  The sibling of points_gradient() / points_tangent() for a Krylov solver on a moving mesh: those factorise
         every node at every call, this does so once (the cost of one points_gradient) and every product afterwards streams the kept
         records (24 bytes per entry of esup, 48 per entry of fsup, 24 per node, on the device).  The Jacobian is kept factored through
-        the mesh geometry and is never assembled: there is no `to_scipy()`.  The products read the resident coordinates, so after a
-        later update_points() they raise (NinpolError, a RuntimeError): build a new operator at the new point; updates of the
+        the mesh geometry; `assemble()` builds the explicit csr_matrix from it with kernels on the device -- not a
+        `to_scipy()`, which elsewhere is a host-side reshape that cannot fail.  The products and `assemble()` read the resident
+        coordinates, so after a later update_points() they raise (NinpolError, a RuntimeError): build a new operator at the new point; updates of the
         permeability or the flags do not change the operator.  3-D meshes, GLS only; the Neumann values are not differentiated.
         Host-synchronous, numpy in and out."""
         self._check_call(variable=variable)

@@ -239,7 +239,8 @@ class GlsShapeJacobian(_KeptJacobian):
     @property
     def nbytes(self):
         """records plus the scratch the launches have made so far: 24 bytes per cell and 48 per face for each of the up to four
-        directions of a launch_jvp chunk, 24 per cell and 96 per face for each of the up to two fields of a launch_vjp chunk"""
+        directions of a launch_jvp chunk, 24 per cell and 96 per face for each of the up to two fields of a launch_vjp chunk, and
+        8 (n_points + 1) + 4 n_blocks for the pattern of the assembled matrix once pattern() or launch_assemble made it"""
         return self.record_bytes + self._buffers()[3]
 
     def relinearize(self, u_ptr, neumann_values_ptr=0, stream=0):
@@ -275,6 +276,44 @@ class GlsShapeJacobian(_KeptJacobian):
         own = np.empty((int(g.n_points), 3), dtype=DTYPE_F)
         _lib.check(_lib.load().nin_gls_xjacobian_fetch_host(self._handle(), _ptr(cell), _ptr(face), _ptr(own)))
         return cell, face, own
+
+    # ---- the assembled matrix: block (p, q) = dF_p / d x_q [3] for q in C(p) = {p} + the vertices of the cells of
+    #      esup[p] + the points of the faces of fsup[p], ascending ----
+    def pattern(self, stream=0):
+        """(n_blocks, block_ptr_ptr, block_col_ptr): the block-CSR pattern of the assembled Jacobian as the object's own device arrays
+        (nin_gls_xjacobian_pattern) -- block_ptr [n_points + 1] int64, block_col [n_blocks] int32, ascending within a row -- valid
+        until release().  Made by the first call (one wait for `stream`), from the connectivity alone: it needs no linearisation and
+        survives relinearize and every update of the grid, the same addresses and the same bytes.  `nbytes` counts it from then on."""
+        n, bp, bc = ctypes.c_int64(0), ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(_lib.load().nin_gls_xjacobian_pattern(self._handle(), ctypes.byref(n), ctypes.byref(bp), ctypes.byref(bc), ctypes.c_void_p(stream)))
+        return int(n.value), int(bp.value or 0), int(bc.value or 0)
+
+    def launch_pattern_copy(self, block_ptr_ptr, block_col_ptr, stream=0):
+        """the pattern copied device-to-device into the caller's buffers (nin_gls_xjacobian_pattern_copy): int64 [n_points + 1] and
+        int32 [n_blocks].  Asynchronous on `stream` once the pattern exists."""
+        _lib.check(_lib.load().nin_gls_xjacobian_pattern_copy(self._handle(), _vp(block_ptr_ptr), _vp(block_col_ptr), ctypes.c_void_p(stream)))
+
+    def fetch_pattern(self):
+        """(block_ptr (n_points + 1,) int64, block_col (n_blocks,) int32) on the host (waits for the device)"""
+        L, n = _lib.load(), ctypes.c_int64(0)
+        block_ptr = np.empty(int(self.grid.n_points) + 1, dtype=np.int64)
+        _lib.check(L.nin_gls_xjacobian_pattern_host(self._handle(), _ptr(block_ptr), None, ctypes.byref(n)))
+        block_col = np.empty(int(n.value), dtype=np.int32)
+        _lib.check(L.nin_gls_xjacobian_pattern_host(self._handle(), _ptr(block_ptr), _ptr(block_col), ctypes.byref(n)))
+        return block_ptr, block_col
+
+    def launch_assemble(self, values_ptr, stream=0):
+        """values [n_blocks][3] = the blocks of the Jacobian at the linearisation point (nin_gls_xjacobian_assemble), every entry
+        written, exact zeros for the rows the forward gives as zero, two calls bit for bit the same.  Asynchronous on `stream` once
+        the pattern exists.  Like launch_jvp it reads the resident coordinates: NinpolError (NIN_ESTATE) before the first
+        linearisation and after Interpolator.update_points(), nothing written."""
+        _lib.check(_lib.load().nin_gls_xjacobian_assemble(self._handle(), _vp(values_ptr), ctypes.c_void_p(stream)))
+
+    def fetch_assembled(self):
+        """values (n_blocks, 3) float64 on the host: one launch_assemble and the copy down (waits for the device)"""
+        values = np.empty((self.pattern()[0], 3), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_xjacobian_assemble_host(self._handle(), _ptr(values)))
+        return values
 
 
 class _JacobianOperator(spla.LinearOperator):
@@ -374,12 +413,28 @@ class PermeabilityJacobian(_JacobianOperator):
 class PointsJacobian(_JacobianOperator):
     """Interpolator.points_jacobian's result: the (n_points, 3 n_points) Jacobian of `apply(variable, "gls")`'s node values in the node
     coordinates (column 3 q + c is coordinate c of node q), as a scipy LinearOperator over a GlsShapeJacobian: numpy in and out,
-    host-synchronous, one launch per matvec / rmatvec and one per batched matmat / rmatmat.  There is no to_scipy(): the Jacobian is
-    kept factored through the mesh geometry and is never assembled.  After Interpolator.update_points() the
-    products raise (NinpolError, a RuntimeError): build a new operator at the new point."""
+    host-synchronous, one launch per matvec / rmatvec and one per batched matmat / rmatmat.  The Jacobian is kept factored through
+    the mesh geometry; assemble() builds the explicit matrix from it on the device.  There is no
+    to_scipy(): where the other two operators reshape a fetched buffer on the host, assemble() launches kernels and reads the resident
+    geometry, so it can raise.  After Interpolator.update_points() the products and assemble() raise (NinpolError, a RuntimeError):
+    build a new operator at the new point."""
 
     def __init__(self, jac):
         super().__init__(jac, 3, per=jac.grid.n_points)
+
+    def assemble(self):
+        """The explicit scipy.sparse.csr_matrix (n_points, 3 n_points): row p, column 3 q + c for every q of
+        C(p) = {p} + the vertices of the cells around p + the points of the faces around p, sorted, int64 indices, explicit zeros kept
+        (the rows the forward gives as zero keep their pattern).  The pattern depends on the connectivity alone and is made once per
+        operator; the values are assembled on the device from the kept records and copied down."""
+        jac = self.jacobian
+        block_ptr, block_col = jac.fetch_pattern()
+        values = jac.fetch_assembled()
+        indices = (3 * block_col.astype(np.int64)[:, None] + np.arange(3, dtype=np.int64)).reshape(-1)
+        A = sp.csr_matrix((values.reshape(-1), indices, 3 * block_ptr), shape=self.shape)
+        A.indices, A.indptr = indices, 3 * block_ptr       # (the constructor narrows index arrays that fit int32)
+        A.has_sorted_indices = True
+        return A
 
     _matvec, _rmatvec, _matmat, _rmatmat = (_JacobianOperator._matvec, _JacobianOperator._rmatvec, _JacobianOperator._matmat,
                                             _JacobianOperator._rmatmat)

@@ -300,6 +300,26 @@ class Linearization:
             return gu, gK, gscale
         return gu[0], gK[0], None if gscale is None else gscale[0]
 
+    def assemble(self):
+        """The Jacobian of a linearisation taken with wrt="points" as an explicit matrix: a torch.sparse_csr_tensor (n_points, 3
+        n_points) on the plan's device, column 3 q + c = coordinate c of node q, sorted columns, explicit zeros kept.
+        The pattern and the values go straight into tensors torch allocates, on torch's current stream; the pattern is made once per
+        linearisation object and does not depend on the point.  Like jvp() it reads the resident coordinates and raises
+        (RuntimeError) once Interpolator.update_points() ran after the linearisation.  Any other wrt: ValueError (K has to_scipy() on
+        Interpolator.permeability_jacobian)."""
+        if self.wrt != "points":
+            raise ValueError(f'assemble() is for a linearisation taken with wrt="points", not wrt="{self.wrt}"')
+        op = self.op
+        P = op.n_points
+        n_blocks = self.jacobian.pattern(op._stream())[0]
+        block_ptr = torch.empty(P + 1, dtype=torch.int64, device=op.device)
+        block_col = torch.empty(n_blocks, dtype=torch.int32, device=op.device)
+        values = torch.empty((n_blocks, 3), dtype=torch.float64, device=op.device)
+        self.jacobian.launch_pattern_copy(block_ptr.data_ptr(), block_col.data_ptr(), op._stream())
+        self.jacobian.launch_assemble(values.data_ptr(), op._stream())
+        col = (3 * block_col.to(torch.int64)[:, None] + torch.arange(3, dtype=torch.int64, device=op.device)).reshape(-1)
+        return torch.sparse_csr_tensor(3 * block_ptr, col, values.reshape(-1), size=(P, 3 * P))
+
     def release(self):
         """give the Jacobian's device buffers back: jvp() / vjp() with a permeability direction raise afterwards"""
         if self.jacobian is not None:

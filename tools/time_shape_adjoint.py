@@ -17,9 +17,16 @@ and 4 beside the forward launch, the coordinate backward and the K tangent (n_ta
 del20, hex216 where the memory allows): the linearisation, GlsShapeJacobian.launch_jvp and launch_vjp with 1 and 4 directions, beside
 the one-shot coordinate tangent and coordinate backward, the three gathers alone and the forward launch of the same session.  Next to
 the times: the algorithmic bytes of each product -- records and indices counted once per chunk of directions, the gathered geometry
-tangents / shares / slots and the in- and outputs once per direction -- and the rate they give."""
+tangents / shares / slots and the in- and outputs once per direction -- and the rate they give.
+
+--assemble: instead, the same Jacobian assembled as a block-CSR matrix (default meshes hex216 and del54, the 2 M-cell
+Delaunay mesh): the first GlsShapeJacobian.pattern() of an object (host clock: allocations, count, scan, one synchronisation, fill) and of
+two further objects, launch_assemble (HIP events, median), and PointsJacobian.assemble() on the host, device-to-host copies and the
+scipy constructor included (--no-host: left out) -- each beside its algorithmic bytes (records read, geometry and connectivity read
+once, 24 bytes per block written) and beside the linearisation of the same run."""
 import os
 import sys
+import time
 
 sys.path.insert(0, os.getcwd())
 import torch
@@ -48,6 +55,57 @@ def jacobian_bytes(g, nnz_e, n):
     vjp = chunks(TRANSPOSE_CHUNK) * (records + 8 * nnz_e + 4 * E + 4 * (nnz_e + nnz_f) + 16 * P + 16 * F + 16 * nnz_f) + \
         n * (8 * P + 96 * F + 24 * E + 24 * nnz_e + 24 * nnz_f + 24 * P)
     return jvp, vjp
+
+
+def assembly_bytes(g, nnz_e, n_blocks):
+    """(pattern, assemble): the bytes the algorithm needs, every array counted once"""
+    P, E, F, nnz_f = int(g.n_points), int(g.n_elems), int(g.n_faces), int(g._scalar("nnz_fsup"))
+    connectivity = 4 * (nnz_e + nnz_f) + 8 * (P + 1) + 32 * E + 16 * F            # esup, fsup, their row pointers, inpoel, inpofa
+    # the symbolic pass reads the connectivity twice (count, fill), writes the counts, scans them and writes the columns
+    pattern = 2 * connectivity + 3 * 8 * (P + 1) + 4 * n_blocks
+    # the numeric pass: the records, the connectivity, the pattern, the coordinates and the float32 normals; 24 bytes per block written
+    records = 24 * nnz_e + 48 * nnz_f + 24 * P
+    assemble = records + connectivity + 8 * (P + 1) + 4 * n_blocks + 24 * P + 12 * F + 24 * n_blocks
+    return pattern, assemble
+
+
+def time_assemble(name, I, plan, st):
+    from ninpol_amd.interpolator import GlsShapeJacobian, PointsJacobian
+    g = I.grid
+    P, E = int(g.n_points), int(g.n_elems)
+    u = torch.rand(E, dtype=torch.float64, device="cuda") - 0.5
+    b = torch.rand(P, dtype=torch.float64, device="cuda") - 0.5
+    J = plan.linearize_points(u.data_ptr(), b.data_ptr(), st.cuda_stream)
+    t_lin = median_ms(lambda: J.relinearize(u.data_ptr(), b.data_ptr(), st.cuda_stream), st)
+    t_pat = []
+    for obj in (J, GlsShapeJacobian(g), GlsShapeJacobian(g)):                   # the pattern needs no linearisation
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_blocks = obj.pattern(st.cuda_stream)[0]
+        torch.cuda.synchronize()
+        t_pat.append((time.perf_counter() - t0) * 1e3)
+        if obj is not J:
+            obj.release()
+    values = torch.full((n_blocks, 3), float("nan"), dtype=torch.float64, device="cuda")
+    t_asm = median_ms(lambda: J.launch_assemble(values.data_ptr(), st.cuda_stream), st)
+    assert torch.isfinite(values).all()
+    del values
+    by_pat, by_asm = assembly_bytes(g, plan.nnz, n_blocks)
+    print(f"{name}: n_blocks {n_blocks} = {n_blocks / P:.1f} per node; records {J.record_bytes / 1e9:.3f} GB, pattern "
+          f"{(8 * (P + 1) + 4 * n_blocks) / 1e9:.3f} GB, values {24 * n_blocks / 1e9:.3f} GB; linearize {t_lin:.3f} ms", flush=True)
+    print(f"{name}: first pattern() {t_pat[0]:.3f} ms (further objects {t_pat[1]:.3f}, {t_pat[2]:.3f} ms), {by_pat / 1e9:.4f} GB algorithmic = "
+          f"{by_pat / t_pat[0] / 1e9:.3f} TB/s ({by_pat / t_pat[0] / 1e9 / 6.3 * 100:.1f} % of 6.3 TB/s); {t_pat[0] / t_lin * 100:.1f} % of linearize",
+          flush=True)
+    print(f"{name}: launch_assemble {t_asm:.4f} ms, {by_asm / 1e9:.4f} GB algorithmic = {by_asm / t_asm / 1e9:.3f} TB/s "
+          f"({by_asm / t_asm / 1e9 / 6.3 * 100:.0f} % of 6.3 TB/s); {t_asm / t_lin * 100:.2f} % of linearize", flush=True)
+    if "--no-host" not in sys.argv:
+        t0 = time.perf_counter()
+        A = PointsJacobian(J).assemble()
+        t_host = (time.perf_counter() - t0) * 1e3
+        print(f"{name}: PointsJacobian.assemble() on the host {t_host:.1f} ms (nnz {A.nnz}, device-to-host copies and the scipy constructor "
+              f"included); {t_host / t_lin * 100:.0f} % of linearize", flush=True)
+        del A
+    J.release()
 
 
 def time_jacobian(name, I, plan, st, t_fwd):
@@ -99,7 +157,7 @@ def time_jacobian(name, I, plan, st, t_fwd):
 
 
 def main():
-    jacobian = "--jacobian" in sys.argv
+    jacobian, assemble = "--jacobian" in sys.argv, "--assemble" in sys.argv
     names = [a for a in sys.argv[1:] if not a.startswith("--")] or (["hex64", "del20"] if jacobian else ["hex216", "del54"])
     if not torch.cuda.is_available():
         raise SystemExit("time_shape_adjoint.py needs a GPU")
@@ -119,6 +177,11 @@ def main():
         forward = lambda: plan.launch(w.data_ptr(), nws.data_ptr(), st.cuda_stream)
         print(f"{name}: P={P} E={E} F={int(g.n_faces)} nnz_esup={plan.nnz} nnz_fsup={g._scalar('nnz_fsup')}; adjoint bins {g.gls_adjoint_plan()}",
               flush=True)
+        if assemble:
+            time_assemble(name, I, plan, st)
+            I.release_scratch()
+            del plan, I, ghat, w, nws
+            continue
         t_fwd = median_ms(forward, st)
         if jacobian:
             time_jacobian(name, I, plan, st, t_fwd)
