@@ -686,6 +686,47 @@ int nin_gls_xjacobian_assemble(nin_gls_xjacobian *J, double *dev_values, void *s
 int nin_gls_xjacobian_pattern_host(nin_gls_xjacobian *J, int64_t *block_ptr, int32_t *block_col, int64_t *n_blocks);
 int nin_gls_xjacobian_assemble_host(nin_gls_xjacobian *J, double *values);
 
+/* ---- kept Jacobians follow local updates: relinearise only the dirty rows --------------------------------------
+ * nin_weights_dirty_device's contract restated for the three kept Jacobians.  PRECONDITION: the object held the Jacobian of
+ * W u_old + neumann_ws b_old at the grid's state as of the last clear of the dirty set; u may differ from u_old only in cells all of whose
+ * vertices are marked, b from b_old only at marked nodes.  RESULT: the object's buffers equal, byte for byte, what its *_linearize
+ * writes now for (u, b).  Rows of nodes outside the set are not touched, whatever u holds there; a row in the set is written whether it
+ * is computed or the zero row of a Dirichlet node.  *n_rows (may be NULL): the number of rows recomputed.
+ *
+ * nin_gls_jacobian_linearize_dirty / nin_gls_rjacobian_linearize_dirty / nin_gls_xjacobian_linearize_dirty: the arguments of the
+ *   object's *_linearize (DEVICE pointers; the reduced one reads its basis again, for the listed rows only), then clear and n_rows.  The
+ *   marked nodes are binned by the adjoint kernel's bins on the device (ascending node id per bin); the per-bin counts and the
+ *   refused-id counter come back in one 32-byte copy -- the ONLY synchronisation of the call (of `stream`); the cotangent
+ *   grad_csr[pos] = u[esup[pos]] is written for the listed rows into a buffer the object keeps from its first such call on
+ *   (8 bytes per entry of esup); the adjoint kernel runs on the lists, a bin without marked nodes is skipped; nin_gls_jacobian's fold
+ *   [n_elems] is recomputed whole.  Beyond the listed rows the work is proportional to n_points and n_elems, never to nnz_esup.
+ *   clear != 0: the set is empty afterwards; clear = 0 keeps it: several consumers -- a weights buffer, a nin_hostmatrix, Jacobians --
+ *   are served from one grid on one stream, all but the last with clear = 0.  While everything is dirty (nin_grid_dirty_nodes == -1) the
+ *   call is the object's full *_linearize (and, with clear, ends that state), *n_rows = n_points.  With an empty set no adjoint kernel
+ *   is launched and *n_rows = 0.  In every case the object's stamp becomes the grid's current one: for nin_gls_xjacobian the applies and
+ *   nin_gls_xjacobian_assemble answer again after a local move of the points.  If ids were refused since the last dirty launch:
+ *   NIN_EINVAL with the count in nin_last_error() (the text of nin_weights_dirty_device), nothing is launched, the set and the object
+ *   are kept and the counter starts again from zero.  NIN_ESTATE before the object's first full linearisation.  A NULL object or a NULL
+ *   dev_u_cells is NIN_EINVAL.
+ * nin_gls_*jacobian_linearize_dirty_host: the same with HOST pointers, on the null stream, synchronous.
+ * nin_grid_mark_dirty_device: marks without an update, for a u or b that changed where K, the points and the flags did not.  dev_ids [n]
+ *   node ids (int32, or int64 when ids_are_int64 != 0) join the dirty set, or, ids_are_cells != 0, the vertices of those cells.  Every id
+ *   is checked on the device before any access: one outside [0, n_points) (resp. [0, n_elems)) marks nothing and is counted in the
+ *   counter of the scatters; the next dirty launch reports the count.  Asynchronous on `stream`, no host copy (with cells the first
+ *   call on a grid brings the cell -> vertex table to the device and synchronises).  It counts in none of the update counters.  n == 0
+ *   is a no-op. */
+int nin_gls_jacobian_linearize_dirty(nin_gls_jacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream, int clear,
+                                     int64_t *n_rows);
+int nin_gls_rjacobian_linearize_dirty(nin_gls_rjacobian *J, const double *dev_u_cells, const double *dev_neumann_values, const double *dev_basis,
+                                      int32_t basis_per_cell, void *stream, int clear, int64_t *n_rows);
+int nin_gls_xjacobian_linearize_dirty(nin_gls_xjacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream, int clear,
+                                      int64_t *n_rows);
+int nin_gls_jacobian_linearize_dirty_host(nin_gls_jacobian *J, const double *u_cells, const double *neumann_values, int clear, int64_t *n_rows);
+int nin_gls_rjacobian_linearize_dirty_host(nin_gls_rjacobian *J, const double *u_cells, const double *neumann_values, const double *basis,
+                                           int32_t basis_per_cell, int clear, int64_t *n_rows);
+int nin_gls_xjacobian_linearize_dirty_host(nin_gls_xjacobian *J, const double *u_cells, const double *neumann_values, int clear, int64_t *n_rows);
+int nin_grid_mark_dirty_device(nin_grid *g, const void *dev_ids, int ids_are_int64, int64_t n, int ids_are_cells, void *stream);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].

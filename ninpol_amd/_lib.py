@@ -44,6 +44,9 @@ EXPORTS = (
     "nin_gls_xjacobian_apply_host", "nin_gls_xjacobian_apply_transpose_host", "nin_gls_xjacobian_fetch_host",
     "nin_gls_xjacobian_pattern", "nin_gls_xjacobian_pattern_copy", "nin_gls_xjacobian_assemble", "nin_gls_xjacobian_pattern_host",
     "nin_gls_xjacobian_assemble_host",
+    "nin_gls_jacobian_linearize_dirty", "nin_gls_rjacobian_linearize_dirty", "nin_gls_xjacobian_linearize_dirty",
+    "nin_gls_jacobian_linearize_dirty_host", "nin_gls_rjacobian_linearize_dirty_host", "nin_gls_xjacobian_linearize_dirty_host",
+    "nin_grid_mark_dirty_device",
     "nin_exchange_create", "nin_exchange_destroy", "nin_exchange_handle", "nin_exchange_connect", "nin_exchange_push",
     "nin_exchange_wait_sent", "nin_exchange_buffer", "nin_exchange_slot_bytes",
 )
@@ -142,6 +145,13 @@ def load():
     L.nin_gls_xjacobian_assemble.argtypes = [vp, vp, vp]
     L.nin_gls_xjacobian_pattern_host.argtypes = [vp, vp, vp, ctypes.POINTER(i64)]
     L.nin_gls_xjacobian_assemble_host.argtypes = [vp, vp]
+    L.nin_gls_jacobian_linearize_dirty.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(i64)]
+    L.nin_gls_rjacobian_linearize_dirty.argtypes = [vp, vp, vp, vp, i32, vp, i32, ctypes.POINTER(i64)]
+    L.nin_gls_xjacobian_linearize_dirty.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(i64)]
+    L.nin_gls_jacobian_linearize_dirty_host.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i64)]
+    L.nin_gls_rjacobian_linearize_dirty_host.argtypes = [vp, vp, vp, vp, i32, i32, ctypes.POINTER(i64)]
+    L.nin_gls_xjacobian_linearize_dirty_host.argtypes = [vp, vp, vp, i32, ctypes.POINTER(i64)]
+    L.nin_grid_mark_dirty_device.argtypes = [vp, vp, i32, i64, i32, vp]
     L.nin_pack_connectivity.argtypes = [i32, vp, vp, vp, vp, vp, vp]
     L.nin_pack_table_row.argtypes = [vp, i64, i64, i64, vp]
     L.nin_diff_mag.argtypes = [vp, i64, vp]

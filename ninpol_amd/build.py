@@ -64,6 +64,9 @@ UNITS = [
     ("fields_scatter.hip", "hipcc", ["-ffp-contract=off"]),
     # Neumann flags from device memory: integer work on bytes, one float64 -> integer cast; nothing to contract
     ("flags_update.hip", "hipcc", []),
+    # a kept Jacobian follows local updates: the dirty set binned by adjoint bin, the cotangent for the listed rows, marks without an
+    # update; integer work and copies, nothing to contract (the adjoint kernel itself stays in its own unit, launched on these lists)
+    ("jacobian_dirty.hip", "hipcc", []),
     # the C ABI's host code by area (abi_internal.hpp is what they share); only abi_plan.hip has a kernel, the locality keys
     ("abi_grid.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_plan.hip", "hipcc", ["-Wno-unknown-pragmas"]),
@@ -73,6 +76,7 @@ UNITS = [
     ("abi_jacobian.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian_reduced.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian_points.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_jacobian_dirty.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     # the peer-to-peer exchange of the multi-GPU path (nin_exchange_*): HIP runtime calls only, no kernel
     ("exchange.hip", "hipcc", []),
 ]

@@ -164,6 +164,12 @@ void nin::release_adjoint_state(DeviceGrid &d) {
     dev_release(d, d.shape_tan_cell);
     dev_release(d, d.shape_tan_face);
     d.shape_tan_n = 0;
+    dev_release(d, d.adj_node_bin);
+    dev_release(d, d.adj_dirty_lists);
+    dev_release(d, d.adj_dirty_hist);
+    dev_release(d, d.adj_dirty_hdr);
+    dev_release(d, d.adj_dirty_tmp);
+    d.adj_dirty_tmp_bytes = 0;
     dev_release(d, d.adj_scratch);
     d.adj_scratch_stride = 0;
     d.adj_scratch_slots = 0;

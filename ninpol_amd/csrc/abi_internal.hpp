@@ -1,4 +1,4 @@
-// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian / abi_jacobian_reduced / abi_jacobian_points.hip;
+// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian / abi_jacobian_reduced / abi_jacobian_points / abi_jacobian_dirty.hip;
 // exchange.hip takes the error setter): the grid behind the handle, the text of nin_last_error(), the preconditions of the entry
 // points, device memory owned by the grid or by one call, and the functions of one unit that another calls.
 #pragma once
@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -181,6 +182,10 @@ int fetch_flag_bytes(nin_grid *g);
 // abi_update.hip, for abi_apply.hip's coordinate adjoint too: inpoel / etype / inpofa on the device (DeviceGrid::up_*), brought by the
 // first caller (synchronous)
 int ensure_update_inputs(nin_grid *g);
+// abi_update.hip: the marks of the dirty set and their header block, made if they are not there; and what a dirty launch answers when
+// ids were refused since the last one -- NIN_EINVAL with the count and whose ids they can have been, the counter zeroed behind `stream`
+int ensure_dirty_state(DeviceGrid &d, int64_t P);
+int dirty_ids_refused(nin_grid *g, int32_t count, hipStream_t stream);
 // abi_apply.hip: the adjoint's and the tangent's bins and scratch slots, and the adjoint's contribution buffer, given back
 void release_adjoint_state(DeviceGrid &d);
 // abi_apply.hip, for abi_jacobian.hip: the cell-major index of the esup pattern and the adjoint's bins, made if they are not there
@@ -215,6 +220,9 @@ struct KeptJacobian {
     int device = -1;                   // the grid's, as it was at creation: a destroy does not look at the grid, which may be gone
     bool linearized = false;
     int64_t stamp[3] = {-1, -1, -1};   // the grid's (field_updates, geometry_updates, flag_updates) at the linearisation
+    // the cotangent of a dirty relinearisation [nnz_esup], written for the listed rows only: made by the first one that finds no refused
+    // ids and kept (a buffer per call would be freed per call, and hipFree waits for the device); every *_destroy frees it
+    double *seed = nullptr;
     void record_stamp(const DeviceGrid &d) {
         stamp[0] = d.field_updates;
         stamp[1] = d.geom_updates;
@@ -238,6 +246,23 @@ inline int jacobian_apply_ready(const KeptJacobian *J, int32_t n, const void *in
     if (!J->linearized) return fail(NIN_ESTATE, "the Jacobian has not been linearised (call %s first)", linearize_name);
     return NIN_OK;
 }
+// abi_jacobian_dirty.hip: the body of the three *_linearize_dirty calls, nin_weights_dirty_device's contract restated for
+// a kept Jacobian.  The grid's marked nodes are binned by adjoint bin on the device, the counts and the refused-id counter come back in
+// one copy of kAdjDirtyHdrInts ints -- the only synchronisation, of `stream` -- the cotangent is seeded for the listed rows in J->seed and
+// bin(b, run, seed) runs the object's mode of the adjoint kernel on every bin that has marked nodes: `run` is the bin's own (bytes,
+// scratch) with the compacted list as its nodes.  finish (may be empty) follows the bins.  While everything is dirty full() -- the object's
+// own *_linearize -- runs instead.  NIN_ESTATE before the first linearisation (the text names `linearize_name`).
+struct DirtyLinearize {
+    const char *linearize_name;
+    bool coordinates;
+    std::function<int()> full;
+    std::function<int(int, const AdjBinRun &, const double *)> bin;
+    std::function<int()> finish;
+};
+int jacobian_linearize_dirty(KeptJacobian *J, const double *dev_u_cells, hipStream_t stream, int clear, int64_t *n_rows, const DirtyLinearize &how);
+// One *_linearize_dirty_host: u [E] and b [P] (may be NULL) go up, launch(dev_u, dev_b) is the device sibling on the null stream, and the call waits
+int jacobian_linearize_dirty_host(KeptJacobian *J, const double *u_cells, const double *neumann_values,
+                                  const std::function<int(const double *, const double *)> &launch);
 // One *_apply_host or *_apply_transpose_host: `in` [n][in_per] goes up, launch(dev_in, dev_out, dev_extra) is the device sibling, `out`
 // [n][out_per] comes down.  The full Jacobian's optional diff_mag is the extra pair [n][extra_per]: an input with extra_in, an output
 // with extra_out; with neither the launch gets a null dev_extra

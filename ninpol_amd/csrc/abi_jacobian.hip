@@ -47,6 +47,7 @@ void nin_gls_jacobian_destroy(nin_gls_jacobian *J) {
     if (J->device >= 0) (void)hipSetDevice(J->device);
     if (J->contrib) (void)hipFree(J->contrib);   // (waits for the device)
     if (J->fold) (void)hipFree(J->fold);
+    if (J->seed) (void)hipFree(J->seed);
     delete J;
 }
 
@@ -63,6 +64,19 @@ int nin_gls_jacobian_linearize(nin_gls_jacobian *J, const double *dev_u_cells, c
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
+}
+
+// the records of the grid's dirty nodes alone, and the fold whole (8 E bytes: it reads the resident perm, which a scatter rewrote)
+int nin_gls_jacobian_linearize_dirty(nin_gls_jacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream_, int clear,
+                                     int64_t *n_rows) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DirtyLinearize how{kLinearize, false, nullptr, nullptr, nullptr};
+    how.full = [&] { return nin_gls_jacobian_linearize(J, dev_u_cells, dev_neumann_values, stream_); };
+    how.bin = [&](int b, const AdjBinRun &run, const double *seed) {
+        return launch_gls_adjoint(J->g->d.v, b, run, 1, seed, dev_neumann_values, J->contrib, stream);
+    };
+    how.finish = [&] { return launch_jac_fold(J->g->d.v, J->fold, stream); };
+    return jacobian_linearize_dirty(J, dev_u_cells, stream, clear, n_rows, how);
 }
 
 int nin_gls_jacobian_apply(nin_gls_jacobian *J, int32_t n, const double *dev_dperm, const double *dev_ddiff_mag, double *dev_dnode,
@@ -111,6 +125,13 @@ int nin_gls_jacobian_linearize_host(nin_gls_jacobian *J, const double *u_cells, 
     if (int rc = nin_gls_jacobian_linearize(J, du, db, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NIN_OK;
+}
+
+int nin_gls_jacobian_linearize_dirty_host(nin_gls_jacobian *J, const double *u_cells, const double *neumann_values, int clear, int64_t *n_rows) {
+    if (n_rows) *n_rows = 0;
+    return jacobian_linearize_dirty_host(J, u_cells, neumann_values, [&](const double *du, const double *db) {
+        return nin_gls_jacobian_linearize_dirty(J, du, db, nullptr, clear, n_rows);
+    });
 }
 
 int nin_gls_jacobian_apply_host(nin_gls_jacobian *J, int32_t n, const double *dperm, const double *ddiff_mag, double *dnode) {

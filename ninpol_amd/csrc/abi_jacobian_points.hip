@@ -79,7 +79,7 @@ void nin_gls_xjacobian_destroy(nin_gls_xjacobian *J) {
     if (!J) return;
     if (J->device >= 0) (void)hipSetDevice(J->device);
     for (void *p : {(void *)J->cell, (void *)J->face, (void *)J->own, (void *)J->tan_cell, (void *)J->tan_face, (void *)J->tr_share,
-                    (void *)J->tr_slot, (void *)J->block_ptr, (void *)J->block_col})
+                    (void *)J->tr_slot, (void *)J->block_ptr, (void *)J->block_col, (void *)J->seed})
         if (p) (void)hipFree(p);   // (waits for the device)
     delete J;
 }
@@ -101,6 +101,19 @@ int nin_gls_xjacobian_linearize(nin_gls_xjacobian *J, const double *dev_u_cells,
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
+}
+
+// the records of the grid's dirty nodes alone: after a local move of the points those are the nodes whose cells or faces moved, so the
+// other nodes' records are still those of the resident geometry and the applies answer again
+int nin_gls_xjacobian_linearize_dirty(nin_gls_xjacobian *J, const double *dev_u_cells, const double *dev_neumann_values, void *stream_, int clear,
+                                      int64_t *n_rows) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DirtyLinearize how{kLinearize, true, nullptr, nullptr, nullptr};
+    how.full = [&] { return nin_gls_xjacobian_linearize(J, dev_u_cells, dev_neumann_values, stream_); };
+    how.bin = [&](int b, const AdjBinRun &run, const double *seed) {
+        return launch_gls_adjoint_points(J->g->d.v, b, run, 1, seed, dev_neumann_values, J->cell, J->face, J->own, stream);
+    };
+    return jacobian_linearize_dirty(J, dev_u_cells, stream, clear, n_rows, how);
 }
 
 // jacobian_apply_ready, and the geometry the records are applied through still that of the linearisation
@@ -152,7 +165,8 @@ int nin_gls_xjacobian_records(nin_gls_xjacobian *J, const double **dev_cell, con
     *dev_cell = J->cell;
     *dev_face = J->face;
     *dev_own = J->own;
-    if (scratch_bytes) *scratch_bytes = J->scratch_bytes();
+    if (scratch_bytes)   // (and the cotangent a dirty relinearisation keeps, 8 bytes per entry of esup)
+        *scratch_bytes = J->scratch_bytes() + (J->seed ? 8 * std::max<int64_t>(J->g->d.nnz_e, 1) : 0);
     return NIN_OK;
 }
 
@@ -246,6 +260,13 @@ int nin_gls_xjacobian_linearize_host(nin_gls_xjacobian *J, const double *u_cells
     if (int rc = nin_gls_xjacobian_linearize(J, du, db, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NIN_OK;
+}
+
+int nin_gls_xjacobian_linearize_dirty_host(nin_gls_xjacobian *J, const double *u_cells, const double *neumann_values, int clear, int64_t *n_rows) {
+    if (n_rows) *n_rows = 0;
+    return jacobian_linearize_dirty_host(J, u_cells, neumann_values, [&](const double *du, const double *db) {
+        return nin_gls_xjacobian_linearize_dirty(J, du, db, nullptr, clear, n_rows);
+    });
 }
 
 int nin_gls_xjacobian_apply_host(nin_gls_xjacobian *J, int32_t n, const double *dpoints, double *dnode) {

@@ -50,6 +50,7 @@ void nin_gls_rjacobian_destroy(nin_gls_rjacobian *J) {
     if (!J) return;
     if (J->device >= 0) (void)hipSetDevice(J->device);
     if (J->R) (void)hipFree(J->R);   // (waits for the device)
+    if (J->seed) (void)hipFree(J->seed);
     delete J;
 }
 
@@ -68,6 +69,22 @@ int nin_gls_rjacobian_linearize(nin_gls_rjacobian *J, const double *dev_u_cells,
     if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
     J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
+}
+
+// the rows of R of the grid's dirty nodes alone; the basis is read again, for those rows only
+int nin_gls_rjacobian_linearize_dirty(nin_gls_rjacobian *J, const double *dev_u_cells, const double *dev_neumann_values, const double *dev_basis,
+                                      int32_t basis_per_cell, void *stream_, int clear, int64_t *n_rows) {
+    if (n_rows) *n_rows = 0;
+    if (!J || !dev_u_cells) return fail(NIN_EINVAL, "NULL argument");
+    if (int rc = basis_ready(J, dev_basis)) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const AdjointReduce red{J->n_params, dev_basis, dev_basis && basis_per_cell ? (int64_t)9 * J->n_params : 0};
+    DirtyLinearize how{kLinearize, false, nullptr, nullptr, nullptr};
+    how.full = [&] { return nin_gls_rjacobian_linearize(J, dev_u_cells, dev_neumann_values, dev_basis, basis_per_cell, stream_); };
+    how.bin = [&](int b, const AdjBinRun &run, const double *seed) {
+        return launch_gls_adjoint_reduced(J->g->d.v, b, run, 1, seed, dev_neumann_values, red, J->R, stream);
+    };
+    return jacobian_linearize_dirty(J, dev_u_cells, stream, clear, n_rows, how);
 }
 
 int nin_gls_rjacobian_apply(nin_gls_rjacobian *J, int32_t n, const double *dev_dtheta, double *dev_dnode, void *stream_) {
@@ -117,6 +134,21 @@ int nin_gls_rjacobian_linearize_host(nin_gls_rjacobian *J, const double *u_cells
     if (int rc = nin_gls_rjacobian_linearize(J, du, db, dB, basis_per_cell, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NIN_OK;
+}
+
+int nin_gls_rjacobian_linearize_dirty_host(nin_gls_rjacobian *J, const double *u_cells, const double *neumann_values, const double *basis,
+                                           int32_t basis_per_cell, int clear, int64_t *n_rows) {
+    if (n_rows) *n_rows = 0;
+    if (!J || !u_cells) return fail(NIN_EINVAL, "NULL argument");
+    if (int rc = basis_ready(J, basis)) return rc;
+    if (int rc = on_device(J->g, kHintKernels)) return rc;
+    HIP_TRY(hipSetDevice(J->g->d.device));
+    DevTmp<double> dB;   // (outlives the wait at the end of the call below)
+    if (basis)
+        if (int rc = dev_stage(dB, basis, (basis_per_cell ? (size_t)J->g->h.n_elems : 1) * 9 * (size_t)J->n_params)) return rc;
+    return jacobian_linearize_dirty_host(J, u_cells, neumann_values, [&](const double *du, const double *db) {
+        return nin_gls_rjacobian_linearize_dirty(J, du, db, dB, basis_per_cell, nullptr, clear, n_rows);
+    });
 }
 
 int nin_gls_rjacobian_apply_host(nin_gls_rjacobian *J, int32_t n, const double *dtheta, double *dnode) {

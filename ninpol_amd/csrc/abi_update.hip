@@ -179,7 +179,7 @@ int64_t nin_grid_field_updates(const nin_grid *g) { return g ? g->d.field_update
 
 // ---- local permeability updates (fields_scatter.hip) ---------------------------------------------------------------
 // the marks and their header block: state of the grid from the first scatter on (P + 128 bytes)
-static int ensure_dirty_state(DeviceGrid &d, int64_t P) {
+int nin::ensure_dirty_state(DeviceGrid &d, int64_t P) {
     if (d.dirty) return NIN_OK;
     int rc = dev_alloc(d, &d.dirty, (size_t)P);
     if (!rc) rc = dev_alloc(d, &d.dirty_hdr, (size_t)kDirtyHdrInts);
@@ -351,6 +351,51 @@ int nin_grid_scatter_points(nin_grid *g, const int64_t *node_ids, int64_t n, con
     return NIN_OK;
 }
 
+// ---- marks without an update (jacobian_dirty.hip) -------------------------------------------------------------------
+int nin_grid_mark_dirty_device(nin_grid *g, const void *dev_ids, int ids_are_int64, int64_t n, int ids_are_cells, void *stream) {
+    if (!g) return fail(NIN_EINVAL, "NULL grid");
+    if (n < 0) return fail(NIN_EINVAL, "negative n");
+    if (int rc = on_device(g, kHintToDevice)) return rc;
+    if (n == 0) return NIN_OK;
+    if (!dev_ids) return fail(NIN_EINVAL, "NULL argument");
+    DeviceGrid &d = g->d;
+    HIP_TRY(hipSetDevice(d.device));
+    int rc = ids_are_cells ? ensure_update_inputs(g) : NIN_OK;   // inpoel / etype on the device: the first call brings them (synchronous)
+    if (!rc) rc = ensure_dirty_state(d, g->h.n_points);
+    if (rc) return rc;
+    rc = launch_mark_dirty(d.v, pack_npoel8(g->h), d.up_inpoel, d.up_etype, dev_ids, ids_are_int64, n, ids_are_cells, d.dirty,
+                           d.dirty_hdr + kDirtyHdrRejected, static_cast<hipStream_t>(stream));
+    if (rc) return fail(rc, "mark kernel: %s", hipGetErrorString(hipGetLastError()));
+    d.scattered_marks = true;
+    return NIN_OK;
+}
+
+// Ids were refused by a scatter since the last dirty launch: the counter starts again from zero, and the error says how many and whose
+// they can have been (nin_weights_dirty_device, and the dirty relinearisations of abi_jacobian_dirty.hip)
+int nin::dirty_ids_refused(nin_grid *g, int32_t count, hipStream_t stream) {
+    DeviceGrid &d = g->d;
+    HIP_TRY(hipMemsetAsync(d.dirty_hdr + kDirtyHdrRejected, 0, sizeof(int32_t), stream));
+    // one counter for the scatters: what was called since the last dirty launch says whose ids they can be (nin_grid_mark_dirty_device
+    // takes cells or nodes)
+    const bool nodes = d.scattered_nodes || d.scattered_marks, flags = d.scattered_flags,
+               cells = d.scattered_cells || d.scattered_marks || !(nodes || flags);
+    d.scattered_cells = d.scattered_nodes = d.scattered_flags = d.scattered_marks = false;
+    char who[240];
+    if (cells && (nodes || flags))
+        snprintf(who, sizeof who, "cell ids outside [0, %lld) or node ids outside [0, %lld) were given to the local updates%s",
+                 (long long)g->h.n_elems, (long long)g->h.n_points, flags ? " (nin_fields_scatter_flags_device among them)" : "");
+    else if (nodes && flags)
+        snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_grid_scatter_points_device or nin_fields_scatter_flags_device",
+                 (long long)g->h.n_points);
+    else if (flags)
+        snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_fields_scatter_flags_device", (long long)g->h.n_points);
+    else if (nodes)
+        snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_grid_scatter_points_device", (long long)g->h.n_points);
+    else
+        snprintf(who, sizeof who, "cell ids outside [0, %lld) were given to nin_fields_scatter_permeability_device", (long long)g->h.n_elems);
+    return fail(NIN_EINVAL, "%d %s and written nowhere; nothing was launched, the dirty set is kept", (int)count, who);
+}
+
 int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *dev_csr_data, double *dev_neumann_ws, void *stream_, int clear,
                              int64_t *n_recomputed) {
     if (n_recomputed) *n_recomputed = 0;
@@ -382,27 +427,8 @@ int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *d
         // the one synchronisation of the call: the lists' offsets and the refused-id counter, 128 bytes
         HIP_TRY(hipMemcpyAsync(hdr, d.dirty_hdr, sizeof hdr, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        if (hdr[kDirtyHdrRejected] != 0) {   // the marks are as they were (the fill pass clears nothing while the counter is set)
-            HIP_TRY(hipMemsetAsync(d.dirty_hdr + kDirtyHdrRejected, 0, sizeof(int32_t), stream));
-            // one counter for the three scatters: what was called since the last dirty launch says whose ids they can be
-            const bool nodes = d.scattered_nodes, flags = d.scattered_flags, cells = d.scattered_cells || !(nodes || flags);
-            d.scattered_cells = d.scattered_nodes = d.scattered_flags = false;
-            char who[240];
-            if (cells && (nodes || flags))
-                snprintf(who, sizeof who, "cell ids outside [0, %lld) or node ids outside [0, %lld) were given to the local updates%s",
-                         (long long)g->h.n_elems, (long long)g->h.n_points, flags ? " (nin_fields_scatter_flags_device among them)" : "");
-            else if (nodes && flags)
-                snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_grid_scatter_points_device or nin_fields_scatter_flags_device",
-                         (long long)g->h.n_points);
-            else if (flags)
-                snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_fields_scatter_flags_device", (long long)g->h.n_points);
-            else if (nodes)
-                snprintf(who, sizeof who, "node ids outside [0, %lld) were given to nin_grid_scatter_points_device", (long long)g->h.n_points);
-            else
-                snprintf(who, sizeof who, "cell ids outside [0, %lld) were given to nin_fields_scatter_permeability_device", (long long)g->h.n_elems);
-            return fail(NIN_EINVAL, "%d %s and written nowhere; nothing was launched, the dirty set is kept", (int)hdr[kDirtyHdrRejected], who);
-        }
-        d.scattered_cells = d.scattered_nodes = d.scattered_flags = false;
+        if (hdr[kDirtyHdrRejected] != 0) return dirty_ids_refused(g, hdr[kDirtyHdrRejected], stream);   // the marks are as they were (the fill pass clears nothing while the counter is set)
+        d.scattered_cells = d.scattered_nodes = d.scattered_flags = d.scattered_marks = false;
     }
     if (d.all_dirty) {   // the ordinary full launch
         if ((rc = nin_weights_device(g, method, nullptr, 0, add_neumann, dev_csr_data, dev_neumann_ws, stream_))) return rc;

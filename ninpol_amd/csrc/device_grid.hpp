@@ -123,6 +123,13 @@ struct DeviceGrid {
     // adjoint's state.  None of the three buffers above is made by that path
     double *shape_tan_cell = nullptr, *shape_tan_face = nullptr;
     int32_t shape_tan_n = 0;
+    // a dirty relinearisation of a kept Jacobian (jacobian_dirty.hip): the adjoint bin of every node as a byte [P], written
+    // from the bins' lists above, and what its compaction of the dirty set needs -- the flat list buffer [P], the block histogram and its
+    // scan, the scan's temporary, the header [kAdjDirtyHdrInts].  Made by the first such call, given back with the adjoint's state
+    uint8_t *adj_node_bin = nullptr;
+    int32_t *adj_dirty_lists = nullptr, *adj_dirty_hist = nullptr, *adj_dirty_hdr = nullptr;
+    void *adj_dirty_tmp = nullptr;
+    size_t adj_dirty_tmp_bytes = 0;
     // what a geometry refresh (nin_grid_update_points*, grid_update.hip) reads next to the coordinates and the one array it writes that
     // no weight kernel reads: inpoel [E][8], etype [E], inpofa [F][4], face areas [F].  Put here by the first update -- handed over by the
     // device builder's mirror, or uploaded from the host arrays -- and given back with the scratch (0.32 + 0.01 + 0.48 + 0.24 GB at 10 M
@@ -148,6 +155,7 @@ struct DeviceGrid {
     // which of the three scatters (fields_scatter.hip's cells, grid_scatter.hip's nodes, flags_update.hip's flags) ran since the last
     // dirty launch: they share the refused-id counter, and the error that reports it names the ids they can have been
     bool scattered_cells = false, scattered_nodes = false, scattered_flags = false;
+    bool scattered_marks = false;   // nin_grid_mark_dirty_device ran too: its ids are cells' or nodes', counted in the same counter
     // Neumann flags from device memory (flags_update.hip): flag_updates counts the updates; flags_host_stale: flag_staging,
     // the host's copy of the resident bytes, is older than the device's (fetched again by whoever reads it)
     int64_t flag_updates = 0;

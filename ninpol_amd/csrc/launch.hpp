@@ -293,6 +293,26 @@ int launch_dirty_row_nnz(const GridView &g, const double *data, const int32_t *l
 int launch_dirty_pack(const GridView &g, const double *data, const double *nws, const int32_t *list, int32_t total, const int32_t *pack_off,
                       int32_t *pack_node, double *pack_nws, int32_t *pack_indices, double *pack_data, hipStream_t stream);
 
+// jacobian_dirty.hip: what a dirty relinearisation of a kept Jacobian runs before the adjoint kernel, all DEVICE pointers.
+// The header of the adjoint's dirty lists: [b] where bin b's list begins in the flat list buffer ([kAdjBins]: the total) and
+// [kAdjBins + 1] the grid's refused-id counter as the fill pass read it
+constexpr int kAdjDirtyHdrInts = 8;
+// bin_of[nodes[i]] = bin for the count nodes of one adjoint bin (bin_of [n_points])
+int launch_adj_bin_byte(const int32_t *nodes, int32_t count, int32_t n_points, int bin, uint8_t *bin_of, hipStream_t stream);
+// the marked nodes binned by adjoint bin into `lists` [n_points], ascending node ids, bin b at hdr[b] .. hdr[b + 1]; hist / scanned:
+// adj_dirty_hist_ints() ints each, tmp: the scan's (adj_dirty_tmp_bytes).  clear != 0: the marks are cleared as they are read, unless
+// *rejected is non-zero
+size_t adj_dirty_hist_ints(int32_t n_points);
+int adj_dirty_tmp_bytes(int32_t n_points, size_t *bytes);
+int launch_adj_dirty_compact(int32_t n_points, int clear, uint8_t *dirty, const uint8_t *bin_of, const int32_t *rejected, int32_t *hist,
+                             int32_t *scanned, void *tmp, size_t tmp_bytes, int32_t *lists, int32_t *hdr, hipStream_t stream);
+// launch_jac_seed for the rows of list[0 .. total) alone: grad_csr[pos] = u[esup[pos]]
+int launch_jac_seed_rows(const GridView &g, const int32_t *list, int32_t total, const double *u, double *grad_csr, hipStream_t stream);
+// dirty[v] = 1 for the nodes dev_ids[0 .. n) (int32, or int64 when ids_are_int64) or, ids_are_cells != 0, for the vertices of those cells
+// (inpoel / etype / npoel8 as launch_scatter_permeability); an id outside its range marks nothing and adds one to *rejected
+int launch_mark_dirty(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const void *dev_ids, int ids_are_int64,
+                      int64_t n, int ids_are_cells, uint8_t *dirty, int32_t *rejected, hipStream_t stream);
+
 const char *kernel_name_idw();
 const char *kernel_name_ls();
 const char *kernel_name_gls();

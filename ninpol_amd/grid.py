@@ -396,6 +396,33 @@ class Grid:
         """Every node is dirty: the next DevicePlan.launch_dirty is a full launch."""
         _lib.check(_lib.load().nin_grid_dirty_reset(self._h, 1, ctypes.c_void_p(stream)))
 
+    def mark_dirty(self, cells=None, nodes=None, stream=0):
+        """Nodes join the dirty set without an update (nin_grid_mark_dirty_device): `nodes`, or the vertices of `cells` -- exactly one
+        of the two -- for a cell field u (resp. node values b) that changed there while K, the points and the flags did not, so that a
+        kept Jacobian's relinearize_dirty() recomputes those rows.  1-D integer ids.  A torch tensor (int32 / int64) on
+        the grid's device: asynchronous on `stream` (0: torch's current stream), no host copy; ids are checked on the device -- one
+        outside the mesh marks nothing, and the next dirty launch raises with the count.  A numpy array, a list or a CPU tensor: checked
+        here (ValueError for an id outside the mesh), copied up and marked before the call returns (needs torch).  Counts in none of
+        the update counters: `is_current()` of a kept Jacobian does not see it."""
+        from . import _args
+        if (cells is None) == (nodes is None):
+            raise ValueError("mark_dirty takes exactly one of cells= and nodes=")
+        ids, name, n = (cells, "cells", self.n_elems) if nodes is None else (nodes, "nodes", self.n_points)
+        L = _lib.load()
+        if self.device < 0:
+            _lib.check(L.nin_grid_mark_dirty_device(self._h, None, 0, 0, int(nodes is None), None))     # (NIN_ENODEVICE, in the library's words)
+        import torch
+        on_host = not on_gpu(ids)
+        if on_host:
+            ids = torch.from_numpy(_args.host_ids(_args.to_host(ids), name, int(n))).to(torch.device("cuda", self.device))
+        else:
+            _args.device_ids(ids, name, self.device)
+            ids = ids.detach().contiguous()
+        s = ctypes.c_void_p(stream) if stream and not on_host else _stream_of(ids)     # (host ids: behind their copy, on torch's stream)
+        _lib.check(L.nin_grid_mark_dirty_device(self._h, *_dev_ids(ids), int(nodes is None), s))
+        if on_host:
+            torch.cuda.current_stream(ids.device).synchronize()
+
     def fetch_permeability(self):
         """(permeability (n_elems, 9), diff_mag (n_elems,)) as resident on the device (nin_fields_get_permeability: waits for the
         device); None when the grid is on no device or holds no permeability there."""

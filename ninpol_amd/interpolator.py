@@ -21,6 +21,8 @@ from ._lib import _ptr, _vp
 from .grid import Grid
 from .jacobian import (GlsJacobian, GlsReducedJacobian, GlsShapeJacobian, PermeabilityJacobian, PointsJacobian,  # noqa: F401  (their import path of old)
                        REDUCED_N_PARAMS, ReducedPermeabilityJacobian, _check_n_params, reduced_basis)
+from .jacobian import (GlsDirtyJacobian, GlsDirtyReducedJacobian, UpdatablePermeabilityJacobian,  # noqa: F401
+                       UpdatableReducedPermeabilityJacobian)
 
 _pinned = _lib.PinnedPool()
 
@@ -968,7 +970,8 @@ class Interpolator:
         through diff_mag = (1 - 3 / tr K)^2 is folded in.  The sibling of permeability_gradient() / permeability_tangent() for a Krylov
         solver: those factorise every node at every call, this does so once (the cost of one permeability_gradient) and every product
         afterwards streams the kept buffer (80 bytes per entry of esup, on the device).  Later update_*() calls do not change the
-        operator; build a new one at the new point.  Host-synchronous, numpy in and out.
+        operator; build a new one at the new point, or -- after local updates (`cells=`, `nodes=`, Grid.mark_dirty) -- call its
+        `update()`, which recomputes only the rows of the grid's dirty nodes.  Host-synchronous, numpy in and out.
 
         `basis`: the permeability moves along M = 1, 3 or 6 parameters per cell, perm_e = sum_m theta_(e,m) B_(e,m), and
         the result is the Jacobian in theta instead: a ReducedPermeabilityJacobian of shape (n_points, M n_elems), column M e + m,
@@ -990,10 +993,10 @@ class Interpolator:
         if basis is not None:
             rjac = GlsReducedJacobian(g, M)
             _lib.check(_lib.load().nin_gls_rjacobian_linearize_host(rjac._handle(), _ptr(u), _ptr(b), _ptr(B), int(per_cell)))
-            return ReducedPermeabilityJacobian(rjac)
+            return UpdatableReducedPermeabilityJacobian(rjac)._bind(self, variable, (B, per_cell))
         jac = GlsJacobian(g)
         _lib.check(_lib.load().nin_gls_jacobian_linearize_host(jac._handle(), _ptr(u), _ptr(b)))
-        return PermeabilityJacobian(jac)
+        return UpdatablePermeabilityJacobian(jac)._bind(self, variable)
 
     def points_jacobian(self, variable, cell_values=None, neumann_values=None):
         """The Jacobian of what `apply(variable, "gls")` returns, `W u` (+ `neumann_ws * neumann_values` when those are given), with
@@ -1006,7 +1009,8 @@ class Interpolator:
         records (24 bytes per entry of esup, 48 per entry of fsup, 24 per node, on the device).  The Jacobian is kept factored through
         the mesh geometry; `assemble()` builds the explicit csr_matrix from it with kernels on the device -- not a
         `to_scipy()`, which elsewhere is a host-side reshape that cannot fail.  The products and `assemble()` read the resident
-        coordinates, so after a later update_points() they raise (NinpolError, a RuntimeError): build a new operator at the new point; updates of the
+        coordinates, so after a later update_points() they raise (NinpolError, a RuntimeError): build a new operator at the new point, or after
+        update_points(nodes=) call its `update()`, which recomputes only the moved neighbourhood; updates of the
         permeability or the flags do not change the operator.  3-D meshes, GLS only; the Neumann values are not differentiated.
         Host-synchronous, numpy in and out."""
         self._check_call(variable=variable)
@@ -1021,7 +1025,7 @@ class Interpolator:
         self._gls_tables_to_device(variable)
         jac = GlsShapeJacobian(g)
         _lib.check(_lib.load().nin_gls_xjacobian_linearize_host(jac._handle(), _ptr(u), _ptr(b)))
-        return PointsJacobian(jac)
+        return PointsJacobian(jac)._bind(self, variable)
 
     def release_scratch(self, pinned=True):
         """Give back what the object keeps between calls for speed: the grid's device scratch (weights, compacted
@@ -1226,7 +1230,7 @@ class DevicePlan:
         self._gls_derivative("linearize", current=False)
         if not u_ptr:
             raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
-        J = GlsJacobian(self.grid, plan=self)
+        J = GlsDirtyJacobian(self.grid, plan=self)
         J.relinearize(u_ptr, neumann_values_ptr, stream)
         return J
 
@@ -1256,7 +1260,7 @@ class DevicePlan:
         if not u_ptr:
             raise ValueError("u_ptr must be a device pointer to n_elems float64 values, not 0")
         _check_n_params(n_params, basis_ptr)
-        J = GlsReducedJacobian(self.grid, n_params, plan=self)
+        J = GlsDirtyReducedJacobian(self.grid, n_params, plan=self)
         J.relinearize(u_ptr, basis_ptr, basis_per_cell, neumann_values_ptr, stream)
         return J
 

@@ -40,6 +40,26 @@ class _KeptJacobian:
             self.plan.ensure_current()
         _lib.check(self._c("linearize")(self._handle(), *args))
 
+    _seeded = False     # the object keeps the cotangent buffer of its dirty relinearisations (8 bytes per entry of esup)
+
+    def _linearize_dirty(self, *args, clear=True):
+        """What the three relinearize_dirty share (nin_gls_*jacobian_linearize_dirty): the arguments of `_linearize`,
+        then clear; returns the number of rows recomputed."""
+        if self.plan is not None:
+            self.plan.ensure_current()
+        n = ctypes.c_int64(0)
+        _lib.check(self._c("linearize_dirty")(self._handle(), *args, int(bool(clear)), ctypes.byref(n)))
+        self._count_seed()
+        return int(n.value)
+
+    def _count_seed(self):
+        """the first dirty relinearisation that went through made the object's cotangent buffer: `nbytes` counts it from here on (the
+        shape Jacobian's nbytes asks the C object, which counts it itself)"""
+        if not self._seeded:
+            self._seeded = True
+            if "nbytes" in self.__dict__:
+                self.nbytes += 8 * int(self.grid.nnz_esup)
+
     @property
     def stamp(self):
         """the grid's (field_updates, geometry_updates, flag_updates) at the last linearisation"""
@@ -80,7 +100,7 @@ class GlsJacobian(_KeptJacobian):
 
     def __init__(self, grid, plan=None):
         self._create(grid, plan)
-        self.nbytes = 80 * int(grid.nnz_esup) + 8 * int(grid.n_elems)
+        self.nbytes = 80 * int(grid.nnz_esup) + 8 * int(grid.n_elems)       # (+ 8 nnz_esup from the first relinearize_dirty on: its cotangent)
 
     def relinearize(self, u_ptr, neumann_values_ptr=0, stream=0):
         """Linearise again, at what is resident now, for u [n_elems] (and b [n_points], 0: none), device pointers: what a fresh
@@ -120,6 +140,26 @@ class GlsJacobian(_KeptJacobian):
         contrib, fold = np.empty((int(g.nnz_esup), 10), dtype=DTYPE_F), np.empty(int(g.n_elems), dtype=DTYPE_F)
         _lib.check(_lib.load().nin_gls_jacobian_fetch_host(self._handle(), _ptr(contrib), _ptr(fold)))
         return contrib, fold
+
+
+class GlsDirtyJacobian(GlsJacobian):
+    """A GlsJacobian that follows local updates: what DevicePlan.linearize() returns.  Everything of GlsJacobian, and
+    `relinearize_dirty`, which recomputes only the rows of the grid's dirty nodes.  (A class of its own because the public names of
+    GlsJacobian are a pinned, closed set.)"""
+
+    def relinearize_dirty(self, u_ptr, neumann_values_ptr=0, stream=0, clear=True):
+        """relinearize for the rows of the grid's dirty nodes only (nin_gls_jacobian_linearize_dirty) -- after
+        Interpolator.update_permeability(cells=), update_points(nodes=), update_neumann_flags(nodes=) or Grid.mark_dirty() -- and return
+        how many rows that were.  If the object was the Jacobian at the grid's state as of the last clear, and u (b) differs from
+        the u (b) of that linearisation only in cells all of whose vertices are marked (only at marked nodes), the buffers hold
+        afterwards what relinearize(u, b) would write now, bit for bit, `fold` included; no other row is touched.  One 32-byte
+        read-back waits for `stream`; everything else is asynchronous on it.  clear=False keeps the set (another consumer follows:
+        DevicePlan.launch_dirty, a HostMatrix, a second Jacobian -- one grid, one stream, the last with clear=True).  While every node
+        is dirty (Grid.dirty_nodes == -1) this is relinearize() and returns n_points; with an empty set it launches no adjoint kernel
+        and returns 0.  Either way `is_current()` is true afterwards.  Raises what launch_dirty raises if ids outside the mesh were
+        scattered since the last dirty launch (nothing is launched, the set and the object are kept, the next call goes through), and
+        NinpolError (NIN_ESTATE) on an object that was never linearised."""
+        return self._linearize_dirty(_vp(u_ptr), _vp(neumann_values_ptr), ctypes.c_void_p(stream), clear=clear)
 
 
 REDUCED_N_PARAMS = (1, 3, 6)
@@ -178,7 +218,7 @@ class GlsReducedJacobian(_KeptJacobian):
         _check_n_params(n_params)
         self.n_params = int(n_params)
         self._create(grid, plan, self.n_params)
-        self.nbytes = 8 * self.n_params * int(grid.nnz_esup)
+        self.nbytes = 8 * self.n_params * int(grid.nnz_esup)                 # (+ 8 nnz_esup from the first relinearize_dirty on: its cotangent)
 
     def relinearize(self, u_ptr, basis_ptr=0, basis_per_cell=True, neumann_values_ptr=0, stream=0):
         """Linearise again, at what is resident now, for u [n_elems], the basis (see DevicePlan.linearize_reduced) and b [n_points]
@@ -207,6 +247,19 @@ class GlsReducedJacobian(_KeptJacobian):
         R = np.empty((int(self.grid.nnz_esup), self.n_params), dtype=DTYPE_F)
         _lib.check(_lib.load().nin_gls_rjacobian_fetch_host(self._handle(), _ptr(R)))
         return R
+
+
+class GlsDirtyReducedJacobian(GlsReducedJacobian):
+    """A GlsReducedJacobian that follows local updates: what DevicePlan.linearize_reduced() returns.  Everything of
+    GlsReducedJacobian, and `relinearize_dirty`."""
+
+    def relinearize_dirty(self, u_ptr, basis_ptr=0, basis_per_cell=True, neumann_values_ptr=0, stream=0, clear=True):
+        """relinearize for the rows of the grid's dirty nodes only (nin_gls_rjacobian_linearize_dirty): the contract
+        of GlsDirtyJacobian.relinearize_dirty, with the basis of this call -- the one the object was linearised with, if the other rows
+        are to stay its Jacobian -- read again for the listed rows only.  Returns how many rows were recomputed."""
+        _check_n_params(self.n_params, basis_ptr)
+        return self._linearize_dirty(_vp(u_ptr), _vp(neumann_values_ptr), _vp(basis_ptr), int(bool(basis_per_cell)), ctypes.c_void_p(stream),
+                                     clear=clear)
 
 
 XJAC_APPLY_CHUNK, XJAC_TRANSPOSE_CHUNK = 4, 2      # directions per pass over the records (csrc/launch.hpp: kXjacApplyChunk, kXjacTransposeChunk)
@@ -247,6 +300,15 @@ class GlsShapeJacobian(_KeptJacobian):
         """Linearise again, at what is resident now, for u [n_elems] (and b [n_points], 0: none), device pointers: what a fresh
         DevicePlan.linearize_points would hold, bit for bit, in the buffers this object already owns."""
         self._linearize(_vp(u_ptr), _vp(neumann_values_ptr), ctypes.c_void_p(stream))
+
+    def relinearize_dirty(self, u_ptr, neumann_values_ptr=0, stream=0, clear=True):
+        """relinearize for the records of the grid's dirty nodes only (nin_gls_xjacobian_linearize_dirty): the
+        contract of GlsDirtyJacobian.relinearize_dirty.  After Interpolator.update_points(nodes=) the dirty nodes are exactly those whose
+        cells or faces moved, so the records of every other node are still those of the resident geometry: launch_jvp, launch_vjp
+        and launch_assemble, which raise after the update, answer again after this call -- for the new point, bit for bit what a
+        fresh DevicePlan.linearize_points gives.  The pattern of the assembled matrix is kept.  Returns how many nodes were
+        recomputed; `nbytes` counts the cotangent this path keeps (8 bytes per entry of esup) from the first call on."""
+        return self._linearize_dirty(_vp(u_ptr), _vp(neumann_values_ptr), ctypes.c_void_p(stream), clear=clear)
 
     def launch_jvp(self, dX_ptr, out_ptr, n=1, stream=0):
         """J . dX for n directions (nin_gls_xjacobian_apply): dX [n][n_points][3] -> out [n][n_points], every entry written (exact
@@ -358,6 +420,46 @@ class _JacobianOperator(spla.LinearOperator):
         self.jacobian.release()
 
 
+class _FollowsUpdates:
+    """update() for an operator that Interpolator.permeability_jacobian or Interpolator.points_jacobian made: it knows the Interpolator,
+    the variable and the basis of that call.  Mixed into PointsJacobian and into the two classes those methods return for the permeability."""
+
+    _interp = _variable = None
+    _basis = ()         # the reduced operator's (B or None, per_cell): the basis arguments of its linearisation, kept for update()
+
+    def _bind(self, interp, variable, basis=()):
+        """what update() needs of the call that made the operator: the Interpolator, its variable, the basis"""
+        self._interp, self._variable, self._basis = interp, variable, tuple(basis)
+        return self
+
+    def update(self, cell_values=None, neumann_values=None, clear=True):
+        """Bring the operator to the grid's state as it is now by recomputing only the rows of the grid's dirty nodes
+        (nin_gls_*jacobian_linearize_dirty_host) -- after update_permeability(cells=), update_points(nodes=),
+        update_neumann_flags(nodes=) or Grid.mark_dirty() -- and return how many rows that were.  `cell_values` / `neumann_values` as
+        for the call that made the operator (default: the cell variable itself / None); they may differ from the earlier ones only
+        in cells all of whose vertices are dirty / at dirty nodes.  Afterwards the products, to_scipy() and assemble() are those of a
+        newly made operator, bit for bit.  clear=False keeps the dirty set for another consumer.  Host-synchronous."""
+        I = self._interp
+        if I is None:
+            raise ValueError("update() needs an operator made by Interpolator.permeability_jacobian or Interpolator.points_jacobian")
+        jac = self.jacobian
+        if I.grid is not jac.grid:
+            raise ValueError("the Interpolator has loaded another mesh since this operator was made")
+        I._check_call(variable=self._variable)
+        u, _ = I._derivative_inputs(self._variable, (), cell_values, None)
+        b = None
+        if neumann_values is not None:
+            b = np.ascontiguousarray(neumann_values, dtype=DTYPE_F)
+            if b.shape != (self._P,):
+                raise ValueError(f"neumann_values must have shape ({self._P},), not {b.shape}.")
+        I._gls_tables_to_device(self._variable)
+        basis = (_ptr(self._basis[0]), int(self._basis[1])) if self._basis else ()
+        n = ctypes.c_int64(0)
+        _lib.check(jac._c("linearize_dirty_host")(jac._handle(), _ptr(u), _ptr(b), *basis, int(bool(clear)), ctypes.byref(n)))
+        jac._count_seed()
+        return int(n.value)
+
+
 class ReducedPermeabilityJacobian(_JacobianOperator):
     """Interpolator.permeability_jacobian(basis=...)'s result: the (n_points, M n_elems) Jacobian of `apply(variable, "gls")`'s node
     values in the parameters theta of perm_e = sum_m theta_(e,m) B_(e,m) (column M e + m), as a scipy LinearOperator over a
@@ -410,14 +512,26 @@ class PermeabilityJacobian(_JacobianOperator):
         return sp.csr_matrix((data.reshape(-1), cols.reshape(-1), indptr), shape=self.shape)
 
 
-class PointsJacobian(_JacobianOperator):
+class UpdatablePermeabilityJacobian(_FollowsUpdates, PermeabilityJacobian):
+    """What Interpolator.permeability_jacobian() returns: a PermeabilityJacobian with `update()`, which follows local updates by
+    recomputing only the rows of the grid's dirty nodes.  (A class of its own because the public names of
+    PermeabilityJacobian are a pinned, closed set -- and an operator made from a bare GlsJacobian has no tables to update from.)"""
+
+
+class UpdatableReducedPermeabilityJacobian(_FollowsUpdates, ReducedPermeabilityJacobian):
+    """What Interpolator.permeability_jacobian(basis=...) returns: a ReducedPermeabilityJacobian with `update()`; the basis of the call
+    is kept and read again for the recomputed rows."""
+
+
+class PointsJacobian(_FollowsUpdates, _JacobianOperator):
     """Interpolator.points_jacobian's result: the (n_points, 3 n_points) Jacobian of `apply(variable, "gls")`'s node values in the node
     coordinates (column 3 q + c is coordinate c of node q), as a scipy LinearOperator over a GlsShapeJacobian: numpy in and out,
     host-synchronous, one launch per matvec / rmatvec and one per batched matmat / rmatmat.  The Jacobian is kept factored through
     the mesh geometry; assemble() builds the explicit matrix from it on the device.  There is no
     to_scipy(): where the other two operators reshape a fetched buffer on the host, assemble() launches kernels and reads the resident
     geometry, so it can raise.  After Interpolator.update_points() the products and assemble() raise (NinpolError, a RuntimeError):
-    build a new operator at the new point."""
+    build a new operator at the new point, or after update_points(nodes=) call update(): the numeric pass of assemble() is then run
+    whole again, the pattern is kept."""
 
     def __init__(self, jac):
         super().__init__(jac, 3, per=jac.grid.n_points)

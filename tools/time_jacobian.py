@@ -13,7 +13,12 @@ directions, the directions and the results once each -- and the share of the 6.3
 linearize_reduced's relinearize, launch_jvp and launch_vjp with 1 and 4 directions, their algorithmic bytes ((8 M + 4) nnz for the
 apply, (8 M + 8) nnz + 4 E for the transpose, 8 M E + 8 P more per direction) and ratios to the full products -- and for M = 1 the two
 yardsticks: the route CellToNode takes for dscale without it (the torch product dscale * K, then the full launch_jvp) and
-nin_spmv_device on the same pattern, which moves the same bytes."""
+nin_spmv_device on the same pattern, which moves the same bytes.
+
+--dirty: instead, the full relinearize and, in the same session, relinearize_dirty with 0.1 %, 1 % and 10 % of the cells
+rewritten as one compact block at the middle of the mesh (update_permeability's scatter before every call, outside the events; HIP events
+around the call, which waits for the stream once: they span that wait), and the library's own split of the call into compaction +
+read-back, seed and adjoint launches (NIN_TIMING=1 makes it print them on stderr): REPS more steps, median of each."""
 import os
 import sys
 
@@ -115,6 +120,74 @@ def time_reduced(name, I, plan, J, t, u, b, st):
         R.release()
 
 
+def dirty_split(run, n):
+    """medians of the three phases a dirty relinearisation reports under NIN_TIMING=1 (stderr is read back through a file)"""
+    import re
+    import tempfile
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile(mode="w+") as tmp:
+        os.dup2(tmp.fileno(), 2)
+        os.environ["NIN_TIMING"] = "1"
+        try:
+            for _ in range(n):
+                run()
+            torch.cuda.synchronize()
+        finally:
+            del os.environ["NIN_TIMING"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        rows = [tuple(map(float, m.groups())) for m in
+                re.finditer(r"\[nin_jac_dirty\] rows \d+ compact\+readback (\S+) seed (\S+) adjoint (\S+) ms", tmp.read())]
+    if len(rows) != n:   # (a call with an empty set, or one that found everything dirty, reports no phases)
+        return [float("nan")] * 3
+    return [float(np.median([r[k] for r in rows])) for k in range(3)]
+
+
+def time_dirty(name, I, redo, t_full, st, what="relinearize"):
+    """redo() = the object's relinearize_dirty on the stream of `st`, returning its row count; t_full = its full relinearize (ms, this
+    session).  Also tools/time_shape_adjoint.py --jacobian --dirty."""
+    g = I.grid
+    E, P = int(g.n_elems), int(g.n_points)
+    C = np.asarray(g.centroids, dtype=np.float64).reshape(E, 3)
+    far = np.abs(C - C.mean(axis=0)).max(axis=1)            # a cube around the middle of the mesh grows with this
+    order = np.argsort(far, kind="stable")
+    del C, far
+    g.clear_dirty(st.cuda_stream)                           # the object holds a full result as of now
+    for frac in (0.001, 0.01, 0.1):
+        m = max(1, int(round(frac * E)))
+        cells = torch.from_numpy(np.sort(order[:m])).to("cuda")
+        K = (torch.tensor([1.5, 0.1, 0.0, 0.1, 1.2, 0.05, 0.0, 0.05, 1.1], dtype=torch.float64, device="cuda").repeat(m, 1) *
+             (1.0 + torch.rand((m, 1), dtype=torch.float64, device="cuda"))).contiguous()
+        rows = []
+
+        def step():
+            g.scatter_permeability_device(cells, K)        # marks the vertices of the block (outside the events)
+            rows.append(redo())
+
+        for _ in range(WARMUP):
+            step()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(REPS):
+            g.scatter_permeability_device(cells, K)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(st)
+            rows.append(redo())
+            b.record(st)
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        t = float(np.median(ms))
+        assert len(set(rows)) == 1 and 0 < rows[0] < P, rows
+        split = dirty_split(step, REPS)
+        print(f"{name}: {what}_dirty, {100 * frac:g} % of the cells ({m}) as one block: {rows[0]} rows = {100 * rows[0] / P:.2f} % of the nodes; "
+              f"{t:.3f} ms = {t / t_full:.4f} x the full {what} ({t_full:.3f} ms); compaction + read-back {split[0]:.4f} ms, seed {split[1]:.4f} ms, "
+              f"adjoint launches {split[2]:.4f} ms; {1e6 * split[2] / rows[0]:.1f} ns per row in the adjoint, full pass {1e6 * t_full / P:.1f} ns per row",
+              flush=True)
+        del cells, K
+
+
 def main():
     names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["hex216", "del54"]
     reduced = "--reduced" in sys.argv[1:]
@@ -138,6 +211,13 @@ def main():
         J = plan.linearize(u.data_ptr(), b.data_ptr(), s)
         t = {"linearize": median_ms(lambda: J.relinearize(u.data_ptr(), b.data_ptr(), s), st)}
         print(f"{name}: linearize {t['linearize']:.3f} ms", flush=True)
+        if "--dirty" in sys.argv[1:]:
+            time_dirty(name, I, lambda: J.relinearize_dirty(u.data_ptr(), b.data_ptr(), s), t["linearize"], st)
+            J.release()
+            del plan, J
+            I.release_scratch()
+            del I
+            continue
         for k in (1, 4):
             dK, out = torch.rand((k, E, 9), **f64) - 0.5, torch.empty((k, P), **f64)
             t[f"jvp{k}"] = median_ms(lambda: J.launch_jvp(dK.data_ptr(), out.data_ptr(), k, 0, s), st)

@@ -133,6 +133,12 @@ def time_jacobian(name, I, plan, st, t_fwd):
     I.release_scratch()
     J = plan.linearize_points(u.data_ptr(), b.data_ptr(), st.cuda_stream)
     t_lin = median_ms(lambda: J.relinearize(u.data_ptr(), b.data_ptr(), st.cuda_stream), st)
+    if "--dirty" in sys.argv:                              # the same object follows a block of rewritten cells
+        from time_jacobian import time_dirty
+        print(f"{name}: linearize {t_lin:.3f} ms", flush=True)
+        time_dirty(name, I, lambda: J.relinearize_dirty(u.data_ptr(), b.data_ptr(), st.cuda_stream), t_lin, st)
+        J.release()
+        return
     for n in (1, 4):
         dX = torch.rand((n, P, 3), dtype=torch.float64, device="cuda") - 0.5
         v = torch.rand((n, P), dtype=torch.float64, device="cuda") - 0.5
