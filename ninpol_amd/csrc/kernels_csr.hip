@@ -315,6 +315,7 @@ int launch_apply_list(const GridView &g, const double *data, const double *u, in
 
 // LDS entries per wavefront and nodes per tile for rows of at most `mx_row` entries, `nnz` in all: 64 rows in steps of 64, at most
 // kApplyCap; past that kApplyCapLong and as many nodes a tile as fit it at 1.25 x the mean row length
+// (restated for the tests by rows_tiling() in tests/rows_paths.py)
 static int32_t apply_cap(int32_t mx_row, int64_t nnz, int32_t n_points, int32_t *tn) {
     int64_t c = 64 * (int64_t)(mx_row > 0 ? mx_row : 1);
     *tn = 64;

@@ -233,7 +233,7 @@ int launch_rows(const GridView &g, const int32_t *targets, int32_t n_targets, in
     }
     // LDS per wave: room for 64 rows of the longest length if that is at most 12 KiB of weights + ids (structured meshes); else 18 KiB
     // and as many nodes a tile -- 64, 32 or 16 -- as fit it at 1.25 x the mesh's mean row length (a tile that is longer still takes
-    // the lane-by-lane path)
+    // the lane-by-lane path)  (restated for the tests by rows_tiling() in tests/rows_paths.py)
     int64_t cap = (int64_t)64 * (mx_row > 0 ? mx_row : 8);
     int32_t tn = 64;
     if (cap > 1024) {
