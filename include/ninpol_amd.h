@@ -522,6 +522,38 @@ int nin_gls_weights_tangent_points_device(nin_grid *g, int add_neumann, int32_t 
 int nin_gls_points_tangent_host(nin_grid *g, const double *tangent_points, const double *cell_values, int32_t n_fields,
                                 double *node_values, double *neumann_ws);
 
+/* ---- the corner gradients of the GLS reconstruction: the gradient half of the per-node solve --------------------------------------
+ * A GLS node solves one least-squares system in 3 ne + 1 unknowns: a gradient for each of the ne cells around it, and the node
+ * value.  The weights keep the node value alone.  These calls return the other 3 ne unknowns -- the gradient of the piecewise-linear
+ * reconstruction in every cell around the node, continuous in flux and in the tangential derivative across the faces -- for MPFA-D
+ * and nonlinear finite-volume fluxes, for the Darcy velocity -K grad u at the nodes, for error indicators.  Per node, with A, c, r and
+ * rho of the weights (csrc/kernels_gls.hip) and a cell field u:  b = u on the cell rows and 0 on EVERY face row (the Neumann boundary
+ * rows too: the values are those of a homogeneous system, as the stored weights are),  u_p = (r.b) / rho,
+ * g = argmin |(b - c u_p) - A g|;  (g, u_p) is the full least-squares solution of [A | c] x = b.  3-D grids, GLS only.  Not provided:
+ * 2-D meshes, IDW / LS, nonzero Neumann data on the face rows, derivatives of the gradients, the sharded path, dirty-row launches.
+ *
+ * nin_gls_corner_gradients_device: dev_u_cells [n_fields][n_elems] -> dev_grad [n_fields][nnz_esup][3], the gradient in cell
+ *   esup[pos] as seen from the node whose row holds pos, at what is resident NOW (geometry, flags, K).  Optional (NULL: not wanted):
+ *   dev_node_values [n_fields][n_points] = u_p (sum_i w_i u_i with the weights of add_neumann = 0, without `+ neumann_ws`);
+ *   dev_flux [n_fields][nnz_esup][3] = -K_e g with the resident permeability of cell e = esup[pos], row c computed as
+ *   -((K[3c] g[0] + K[3c+1] g[1]) + K[3c+2] g[2]) without contraction; dev_node_gradient [n_fields][n_points][3] = the mean of a
+ *   node's corner gradients, summed from 0.0 in row order and divided by their number -- an average for visualisation, not a
+ *   projection.  Every entry of every output is written: zeros for the nodes the forward gives the zero row (Dirichlet nodes, no
+ *   internal face, too few rows, a singular or non-finite system), u_p included.  The adjoint's kernel in its gradient mode: the
+ *   same bins, assembly and Householder QR, factored once per node for all n_fields fields; per field one application of Q^T and
+ *   one triangular solve.  Two streaming kernels follow for the flux and the mean.  No atomics: two calls agree bit for bit and a
+ *   batch equals its fields one by one.  The first of the backward, tangent, gradient and plan calls on a grid bins the nodes and
+ *   allocates the scratch slots (and synchronises `stream`); later calls are asynchronous on `stream`.  NIN_EINVAL for a NULL grid,
+ *   dev_u_cells or dev_grad, for n_fields < 1 and for a grid that is not 3-D (answered in this order, before the grid's residency);
+ *   otherwise errors as nin_gls_weights_tangent_device (NIN_ENODEVICE; fields without a permeability are refused: only GLS has
+ *   such a system).  A refused call writes nothing.  NIN_GLS_ADJ_FORCE_GLOBAL and NIN_GLS_ADJ_ONLY as there.
+ * nin_gls_corner_gradients_host: the host-pointer counterpart -- cell_values [n_fields][n_elems] up, grad and the optional
+ *   node_values, flux and node_gradient (NULL: not wanted) down; synchronous.  Errors as the device call. */
+int nin_gls_corner_gradients_device(nin_grid *g, int32_t n_fields, const double *dev_u_cells, double *dev_grad, double *dev_node_values,
+                                    double *dev_flux, double *dev_node_gradient, void *stream);
+int nin_gls_corner_gradients_host(nin_grid *g, const double *cell_values, int32_t n_fields, double *grad, double *node_values, double *flux,
+                                  double *node_gradient);
+
 /* ---- the GLS Jacobian in the permeability, kept on the device: linearise once, apply J and J^T many times ----------------------
  * The two calls above repeat the dense QR of every node at every call.  A Krylov solver applies J . dK or J^T . v once per iteration
  * at ONE linearisation point; for it, a nin_gls_jacobian keeps the derivative itself.  For a fixed cell field u (and optional node

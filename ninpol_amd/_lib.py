@@ -33,6 +33,7 @@ EXPORTS = (
     "nin_gls_weights_tangent_device", "nin_gls_permeability_tangent_host",
     "nin_gls_weights_backward_points_device", "nin_gls_points_gradient_host",
     "nin_gls_weights_tangent_points_device", "nin_gls_points_tangent_host",
+    "nin_gls_corner_gradients_device", "nin_gls_corner_gradients_host",
     "nin_gls_jacobian_create", "nin_gls_jacobian_linearize", "nin_gls_jacobian_apply", "nin_gls_jacobian_apply_transpose",
     "nin_gls_jacobian_contrib", "nin_gls_jacobian_stamp", "nin_gls_jacobian_destroy", "nin_gls_jacobian_linearize_host",
     "nin_gls_jacobian_apply_host", "nin_gls_jacobian_apply_transpose_host", "nin_gls_jacobian_fetch_host",
@@ -104,6 +105,8 @@ def load():
     L.nin_gls_points_gradient_host.argtypes = [vp, vp, vp, i32, vp]
     L.nin_gls_weights_tangent_points_device.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     L.nin_gls_points_tangent_host.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.nin_gls_corner_gradients_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.nin_gls_corner_gradients_host.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.nin_gls_jacobian_create.argtypes = [vp, ctypes.POINTER(vp)]
     L.nin_gls_jacobian_linearize.argtypes = [vp, vp, vp, vp]
     L.nin_gls_jacobian_apply.argtypes = [vp, i32, vp, vp, vp, vp]

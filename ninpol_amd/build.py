@@ -48,6 +48,9 @@ UNITS = [
     # the same records assembled into a block-CSR matrix: a symbolic pass per object (the column set of every row), a numeric pass per
     # linearisation
     ("kernels_gls_shape_assemble.hip", "hipcc", []),
+    # what follows the corner gradients of the adjoint kernel's gradient mode: the fluxes -K g and the nodal mean, streamed; no contraction,
+    # so that the host gets the same bits from the stated expression
+    ("kernels_gls_gradient.hip", "hipcc", ["-ffp-contract=off"]),
     ("kernels_csr.hip", "hipcc", []),
     # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
     ("csr_dirty.hip", "hipcc", []),
@@ -73,6 +76,7 @@ UNITS = [
     ("abi_update.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_csr.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_apply.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_gradient.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian_reduced.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian_points.hip", "hipcc", ["-Wno-unknown-pragmas"]),

@@ -1,4 +1,4 @@
-// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_jacobian / abi_jacobian_reduced / abi_jacobian_points / abi_jacobian_dirty.hip;
+// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_gradient / abi_jacobian / abi_jacobian_reduced / abi_jacobian_points / abi_jacobian_dirty.hip;
 // exchange.hip takes the error setter): the grid behind the handle, the text of nin_last_error(), the preconditions of the entry
 // points, device memory owned by the grid or by one call, and the functions of one unit that another calls.
 #pragma once
@@ -212,6 +212,13 @@ int for_each_adjoint_bin(const DeviceGrid &d, int only, Fn fn) {
 // [nnz_esup][n_params] buffer through launch_gls_adjoint_reduced instead, for abi_jacobian_reduced.hip
 int launch_adjoint_bins(DeviceGrid &d, int add_neumann, int only, const double *grad_csr, const double *grad_nws, double *contrib,
                         hipStream_t stream, const AdjointReduce *reduce = nullptr);
+
+// abi_gradient.hip: the doubles behind the arguments of nin_gls_corner_gradients_* for n_fields fields -- u [n_fields][E], grad and flux
+// [n_fields][nnz_esup][3], node_values [n_fields][P], node_gradient [n_fields][P][3] -- as the host entry point stages them
+struct CornerGradientCounts {
+    size_t u, grad, node_values, node_gradient;
+};
+CornerGradientCounts corner_gradient_counts(int64_t n_elems, int64_t n_points, int64_t nnz_esup, int32_t n_fields);
 
 // ---- what the kept Jacobians share (abi_jacobian.hip, abi_jacobian_reduced.hip, abi_jacobian_points.hip) --------------------------------------------------
 // nin_gls_jacobian, nin_gls_rjacobian and nin_gls_xjacobian begin with this; each adds the buffers it owns

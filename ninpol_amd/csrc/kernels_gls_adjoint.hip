@@ -1,7 +1,8 @@
 // kernels_gls_adjoint.hip -- the GLS weights differentiated with respect to the permeability and to the node coordinates, gfx950.
-// DESIGN.md 4.11 has the mathematics, the bins and the layout of this unit; 4.12, 4.14, 4.15 and 4.17 the other four modes.
+// DESIGN.md 4.11 has the mathematics, the bins and the layout of this unit; 4.12, 4.14, 4.15, 4.17 and 4.21 the other five modes.
 //
-// nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS> serves five modes (listed at its static_assert).  They share the head: node header,
+// nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD> serves six modes (listed at its static_assert; GRD, the corner gradients of DESIGN.md
+// 4.21, differentiates nothing: it solves for the other 3 ne unknowns of the node's system).  They share the head: node header,
 // assembly, Householder QR with R kept, y, r, rho and the verdict.  The header, the zero-row rule and the assembly are this unit's OWN
 // TEXT of what gls_dense.hpp holds for the forward kernels (read_node, DenseNode::zero_row, cell_rows, internal_face_rows with
 // glsmath::face_tau, neumann_face_row): a change there is made here too.  Calling the helpers gives the same bits, but every form tried
@@ -41,12 +42,14 @@ struct AdjointIo {
     double *contrib;                     //          [nnz_esup][10]; RED: the reduced Jacobian R [nnz_esup][red_m]
     union {
         int32_t n_tan;                   // tangent: directions
+        int32_t grd_n;                   // GRD: cell fields
         int32_t red_m;                   // RED: parameters per cell
     };
     union {
         const double *tan_perm;          // tangent: dK [n_tan][E][9]
         const double *red_basis;         // RED: B [E][red_m][9] (red_stride = 9 red_m), [red_m][9] (red_stride = 0: shared) or null: g.perm
         const double *tpt_dx;            // tangent with PTS: dX [n_tan][P][3]
+        const double *grd_u;             // GRD: the cell fields u [grd_n][E]
     };
     union {
         const double *tan_dm;            // tangent: d diff_mag [n_tan][E] or null (folded from g.perm)
@@ -55,10 +58,12 @@ struct AdjointIo {
     union {
         double *tan_csr;                 // tangent: d stored weights [n_tan][nnz]
         double *pts_face;                // PTS: (fcbar, Nbar) of every (node, face) pair [nnz_fsup][6]
+        double *grd_out;                 // GRD: the corner gradients [grd_n][nnz][3]
     };
     union {
         double *tan_nws;                 // tangent: d neumann_ws [n_tan][P] or null
         double *pts_own;                 // PTS: xbar_own [P][3]
+        double *grd_up;                  // GRD: the node values u_p [grd_n][P] or null
     };
     union {
         long long nnz;
@@ -144,12 +149,14 @@ __device__ __forceinline__ void back_substitute(const double *A, int ld, int nc,
     }
 }
 
-template <int TW, bool LDS, bool TAN, bool RED, bool PTS>
+template <int TW, bool LDS, bool TAN, bool RED, bool PTS, bool GRD = false>
 __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, const int32_t *__restrict__ nodes, int32_t count, int add_neumann,
                                                                  AdjointIo io, double *scratch, long long scratch_stride) {
     // (TAN, RED, PTS): (0, 0, 0) K adjoint, (0, 1, 0) reduced K adjoint, (0, 0, 1) coordinate adjoint, (1, 0, 0) K tangent,
-    // (1, 0, 1) coordinate tangent; the other three combinations mean nothing
+    // (1, 0, 1) coordinate tangent; the other three combinations mean nothing.  GRD, with none
+    // of the three: the corner gradients of cell fields
     static_assert(!RED || (!TAN && !PTS), "(TAN, RED, PTS) is not one of the five modes: RED goes with neither TAN nor PTS");
+    static_assert(!GRD || (!TAN && !RED && !PTS), "GRD is a mode of its own: it goes with none of TAN, RED and PTS");
     extern __shared__ double smem[];
     const double *__restrict__ const grad_csr = io.grad_csr, *__restrict__ const grad_nws = io.grad_nws;
     double *__restrict__ const contrib = io.contrib;
@@ -176,7 +183,12 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
         const int m = ne + 3 * n_if + (is_neu ? n_bf : 0);     // rows actually populated
         // the forward's zero rows (DenseNode::zero_row, gls_dense.hpp): nothing depends on K there
         if (((fl & 1) && !is_neu) || n_if == 0 || m < n - 1) {
-            if constexpr (TAN) {
+            if constexpr (GRD) {
+                for (int t = 0; t < io.grd_n; ++t) {
+                    for (int i = tid; i < 3 * ne; i += nthr) io.grd_out[3 * ((size_t)t * (size_t)io.nnz + (size_t)eb) + i] = 0.0;
+                    if (io.grd_up && tid == 0) io.grd_up[(size_t)t * g.n_points + p] = 0.0;
+                }
+            } else if constexpr (TAN) {
                 for (int t = 0; t < io.n_tan; ++t) {
                     for (int i = tid; i < ne; i += nthr) io.tan_csr[(size_t)t * io.nnz + eb + i] = 0.0;
                     if (io.tan_nws && tid == 0) io.tan_nws[(size_t)t * g.n_points + p] = 0.0;
@@ -334,7 +346,7 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
             rho = wave_sum(rho);
             for (int k = n - 2; k >= 0; --k) reflect(A, ld, m, k, tau[k], rv, lane);
             wave_sync<LDS>();
-            back_substitute<LDS>(A, ld, n - 1, y, lane);
+            if constexpr (!GRD) back_substitute<LDS>(A, ld, n - 1, y, lane);   // (GRD solves for every unknown at once and has no use for y)
             // the forward's last zero-row rule: a singular system, or a result that is not finite
             bool ok = !singular && rho > 0.0;
             {
@@ -342,7 +354,7 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
                 for (int i = lane; i < ne; i += 64) fin = fin && isfinite(rv[i] / rho);
                 ok = ok && __ballot(!fin) == 0ull;
             }
-            if constexpr (TAN) {   // (tau and y hold n words, the reflectors and y n - 1: the last words carry the verdict and rho)
+            if constexpr (TAN || GRD) {   // (tau and y hold n words, the reflectors and y n - 1: the last words carry the verdict and rho)
                 if (lane == 0) { tau[n - 1] = ok ? 1.0 : 0.0; y[n - 1] = rho; }
             } else {
                 // g and rbar (into q)
@@ -368,6 +380,37 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
             }
         }
         __syncthreads();
+
+        if constexpr (GRD) {
+            // ---- the gradient tail: per field b = u on the cell rows and 0 on every face row, u_p = (r.b) / rho,
+            //      g = R^-1 (Q^T (b - c u_p))(0:n-1) -- with u_p the full least-squares solution of [A | c] x = b.  Wavefront 0 alone: one
+            //      Q^T and one triangular solve per field, in q.  Lane sums in lane order, wave_sum's fixed tree: two calls agree bit for bit
+            if (wave == 0) {
+                const bool ok = tau[n - 1] != 0.0;   // uniform
+                const double rho = y[n - 1];
+                for (int t = 0; t < io.grd_n; ++t) {
+                    const double *u = io.grd_u + (size_t)t * (size_t)g.n_elems;
+                    double *og = io.grd_out + 3 * ((size_t)t * (size_t)io.nnz + (size_t)eb);
+                    double up = 0.0;
+                    if (ok) {
+                        double s = 0.0;
+                        for (int i = lane; i < ne; i += 64) s += rv[i] * u[cells[i]];
+                        up = wave_sum(s) / rho;
+                        for (int i = lane; i < m; i += 64) qv[i] = i < ne ? u[cells[i]] - up : 0.0;   // (a lane's own rows, as reflect takes them)
+                        for (int k = 0; k < n - 1; ++k) reflect(A, ld, m, k, tau[k], qv, lane);
+                        wave_sync<LDS>();
+                        back_substitute<LDS>(A, ld, n - 1, qv, lane);
+                        for (int i = lane; i < 3 * ne; i += 64) og[i] = qv[i];
+                    } else {
+                        for (int i = lane; i < 3 * ne; i += 64) og[i] = 0.0;
+                    }
+                    if (io.grd_up && lane == 0) io.grd_up[(size_t)t * g.n_points + p] = up;
+                    wave_sync<LDS>();   // (q is the next field's)
+                }
+            }
+            __syncthreads();   // (the slot is the next node's)
+            continue;
+        }
 
         if constexpr (TAN) {
             // ---- the tangent tail: per direction z1 = dA y (into q), z2 = dA^T r (into s), then wavefront 0 -----------------------
@@ -700,15 +743,15 @@ __global__ __launch_bounds__(256) void nin_adjoint_gather_kernel(int32_t n_elems
     for (int k = 0; k < 9; ++k) grad_perm[9 * (size_t)e + k] = acc[k];
 }
 
-template <int TW, bool LDS, bool TAN, bool RED, bool PTS>
+template <int TW, bool LDS, bool TAN, bool RED, bool PTS, bool GRD>
 int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io, double *scratch,
                int64_t stride, int32_t slots, hipStream_t stream) {
-    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS>;
+    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD>;
     int64_t blocks;
     size_t lds = 0;
     if (LDS) {
         lds = (size_t)bytes;
-        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS>>(lds)) return -3;
+        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD>>(lds)) return -3;
         int64_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : (int64_t)lds);
         if (per_cu > 32 / TW) per_cu = 32 / TW;
         if (per_cu < 1) per_cu = 1;
@@ -722,16 +765,16 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
 }
 
 // one bin's nodes through the class of that bin: 1, 2, 4 wavefronts in LDS, 8 over a global-memory slot
-template <bool TAN, bool RED, bool PTS = false>
+template <bool TAN, bool RED, bool PTS = false, bool GRD = false>
 int launch_bin_of(const GridView &g, int bin, const AdjBinRun &r, int add_neumann, const AdjointIo &io, hipStream_t stream) {
     if (r.count <= 0) return 0;
     switch (bin) {
-        case 0: return launch_bin<1, true, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 1: return launch_bin<2, true, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 2: return launch_bin<4, true, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 0: return launch_bin<1, true, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 1: return launch_bin<2, true, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 2: return launch_bin<4, true, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
         case 3:
             if (!r.scratch || r.scratch_slots < 1 || r.scratch_stride * 8 < r.bytes) return -1;
-            return launch_bin<8, false, TAN, RED, PTS>(g, r.nodes, r.count, r.bytes, add_neumann, io, r.scratch, r.scratch_stride, r.scratch_slots,
+            return launch_bin<8, false, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, r.scratch, r.scratch_stride, r.scratch_slots,
                                                        stream);
     }
     return -1;
@@ -782,6 +825,13 @@ int launch_gls_tangent_points(const GridView &g, int bin, const AdjBinRun &run, 
     io.n_tan = n_tangents; io.tpt_dx = tangent_points; io.tpt_cell = tangent_cell; io.tpt_face = tangent_face; io.tan_csr = tangent_csr;
     io.tan_nws = tangent_nws; io.nnz = (long long)nnz;
     return launch_bin_of<true, false, true>(g, bin, run, add_neumann, io, stream);
+}
+
+int launch_gls_corner_gradients(const GridView &g, int bin, const AdjBinRun &run, int32_t n_fields, const double *u_cells, double *grad,
+                                double *node_values, int64_t nnz, hipStream_t stream) {
+    AdjointIo io{};
+    io.grd_n = n_fields; io.grd_u = u_cells; io.grd_out = grad; io.grd_up = node_values; io.nnz = (long long)nnz;
+    return launch_bin_of<false, false, false, true>(g, bin, run, 0, io, stream);
 }
 
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,

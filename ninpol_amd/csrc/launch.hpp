@@ -173,6 +173,15 @@ int launch_shape_tangent_geometry(const GridView &g, const int32_t *inpoel, cons
 int launch_gls_tangent_points(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, int32_t n_tangents, const double *tangent_points,
                               const double *tangent_cell, const double *tangent_face, double *tangent_csr, double *tangent_nws, int64_t nnz,
                               hipStream_t stream);
+// launch_gls_corner_gradients: the same kernel's gradient mode on the nodes of one bin -- n_fields cell fields u_cells
+//   [n_fields][E] -> the gradient of the node's least-squares reconstruction in each of its cells, grad [n_fields][nnz][3] in esup
+//   position, and the node value u_p = (r.b) / rho, node_values [n_fields][P] or null; every row of every listed node is written, zeros
+//   where the forward has its zero row.  launch_corner_flux / launch_node_gradient (kernels_gls_gradient.hip) stream that buffer:
+//   flux [n_fields][nnz][3] = -K_e g with the resident permeability, node_gradient [n_fields][P][3] = the mean of a row in row order
+int launch_gls_corner_gradients(const GridView &g, int bin, const AdjBinRun &run, int32_t n_fields, const double *u_cells, double *grad,
+                                double *node_values, int64_t nnz, hipStream_t stream);
+int launch_corner_flux(const GridView &g, int64_t nnz, int32_t n_fields, const double *grad, double *flux, hipStream_t stream);
+int launch_node_gradient(const GridView &g, int64_t nnz, int32_t n_fields, const double *grad, double *node_gradient, hipStream_t stream);
 
 // the GLS Jacobian kept and applied (kernels_gls_jacobian.hip), all DEVICE pointers; contrib [nnz_esup][10] as an adjoint
 // launch with grad_csr = u[esup] left it, fold [E] = d diff_mag / d K_dd at the linearisation point.

@@ -961,6 +961,46 @@ class Interpolator:
         _lib.check(_lib.load().nin_gls_points_tangent_host(g._h, _ptr(d), _ptr(u), k, _ptr(out), _ptr(nws)))
         return out, nws
 
+    def _corner_gradient_inputs(self, variable, values):
+        """(u, k, lead) of corner_gradients() / node_gradient(): `values` as apply() takes them, the GLS tables on the device"""
+        self._check_call(variable=variable)
+        self._perm_rows()   # (ValueError without a permeability)
+        g = self.grid
+        if values is None:
+            values = np.asarray(self.cells_data[self.variable_to_index["cells"][variable]])[:g.n_elems]
+        u = np.ascontiguousarray(values, dtype=DTYPE_F)
+        if u.shape != (g.n_elems,) and not (u.ndim == 2 and u.shape[0] >= 1 and u.shape[1] == g.n_elems):
+            raise ValueError(f"values must have shape ({g.n_elems},) or (k, {g.n_elems}), not {u.shape}.")
+        self._gls_tables_to_device(variable)
+        return u, (1 if u.ndim == 1 else u.shape[0]), u.shape[:-1]
+
+    def corner_gradients(self, variable, values=None, flux=False):
+        """The gradients of the GLS reconstruction in the cells around every node: per node the least-squares system whose last
+        unknown `apply(variable, "gls")` keeps as the node value has a gradient for each of the node's cells as its other unknowns,
+        continuous in flux and in the tangential derivative across the faces.  `values` as in apply(): one cell array (n_elems,) --
+        default: the cell variable `variable` itself -- or k of them as (k, n_elems).  Returns grad, (nnz_esup, 3) or (k, nnz_esup, 3) in
+        esup order; with flux=True (grad, flux), flux = -K_e grad with the resident permeability, shaped alike.
+        Indexing: grad[grid.esup_ptr[p]:grid.esup_ptr[p + 1]] are the gradients node p gives its cells grid.esup[that range].
+        The face rows of the right-hand side are zero (Neumann rows too); rows that are zero in W (Dirichlet nodes) are zeros here.
+        On the device, host-synchronous, numpy in and out; deterministic.  3-D meshes, GLS only."""
+        u, k, lead = self._corner_gradient_inputs(variable, values)
+        g = self.grid
+        nnz = int(g.nnz_esup)
+        grad = np.empty(lead + (nnz, 3), dtype=DTYPE_F)
+        fl = np.empty(lead + (nnz, 3), dtype=DTYPE_F) if flux else None
+        _lib.check(_lib.load().nin_gls_corner_gradients_host(g._h, _ptr(u), k, _ptr(grad), None, _ptr(fl), None))
+        return (grad, fl) if flux else grad
+
+    def node_gradient(self, variable, values=None):
+        """One gradient per node: the mean of the node's corner gradients (corner_gradients()) in row order, zeros on zero rows --
+        an average for visualisation, not a projection.  `values` as there; returns (n_points, 3) or (k, n_points, 3)."""
+        u, k, lead = self._corner_gradient_inputs(variable, values)
+        g = self.grid
+        grad = np.empty(lead + (int(g.nnz_esup), 3), dtype=DTYPE_F)
+        out = np.empty(lead + (g.n_points, 3), dtype=DTYPE_F)
+        _lib.check(_lib.load().nin_gls_corner_gradients_host(g._h, _ptr(u), k, _ptr(grad), None, None, _ptr(out)))
+        return out
+
     def permeability_jacobian(self, variable, cell_values=None, neumann_values=None, basis=None):
         """The Jacobian of what `apply(variable, "gls")` returns, `W u` (+ `neumann_ws * neumann_values` when those are given), with
         respect to the permeability table, linearised ONCE at the resident table and kept on the device: a scipy LinearOperator of
@@ -1221,6 +1261,20 @@ class DevicePlan:
         self._gls_derivative("launch_weights_tangent_points", "do depend on the node coordinates, but they are not differentiated here")
         _lib.check(_lib.load().nin_gls_weights_tangent_points_device(self.grid._h, int(bool(add_neumann)), int(n_tangents), _vp(tangent_points_ptr),
                                                                      _vp(tangent_csr_ptr), _vp(tangent_neumann_ws_ptr), ctypes.c_void_p(stream)))
+
+    def launch_corner_gradients(self, u_ptr, grad_ptr, n_fields=1, node_values_ptr=0, flux_ptr=0, node_gradient_ptr=0, stream=0):
+        """The corner gradients of the GLS reconstruction (nin_gls_corner_gradients_device): u [n_fields][n_elems] -> grad
+        [n_fields][nnz_esup][3], the gradient in cell esup[pos] as the node whose row holds pos reconstructs it -- the other 3 ne
+        unknowns of the least-squares system whose last unknown the weights keep -- at what is resident now (geometry, flags, K).
+        Optional (0: not wanted): node_values [n_fields][n_points] = sum_i w_i u_i with the weights of add_neumann=False; flux
+        [n_fields][nnz_esup][3] = -K_e grad; node_gradient [n_fields][n_points][3] = the mean of a node's corner gradients in row
+        order (an average for visualisation, not a projection).  The face rows of the right-hand side are zero, Neumann rows too.
+        All fields share one factorisation per node; every entry of every output is written, zeros where the row is zero.
+        Asynchronous on `stream` after the first call on a grid (which makes the adjoint's bins and synchronises); deterministic.
+        3-D grids.  GLS only: IDW and LS solve no such system -- a plan of those methods raises instead of returning zeros."""
+        self._gls_derivative("launch_corner_gradients", "are not the solution of a system that has cell gradients")
+        _lib.check(_lib.load().nin_gls_corner_gradients_device(self.grid._h, int(n_fields), _vp(u_ptr), _vp(grad_ptr), _vp(node_values_ptr),
+                                                               _vp(flux_ptr), _vp(node_gradient_ptr), ctypes.c_void_p(stream)))
 
     def linearize(self, u_ptr, neumann_values_ptr=0, stream=0):
         """The Jacobian of the node values `W u + neumann_ws * b` in the permeability, kept on the device: a GlsJacobian linearised at

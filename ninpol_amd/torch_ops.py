@@ -544,3 +544,22 @@ class CellToNode(torch.nn.Module):
             return _CellToNodeFn.apply(u.contiguous(), self, self.weights)
         weights, _ = self.weights_of(K, scale, points)
         return _CellToNodeFn.apply(u.contiguous(), self, weights)
+
+    def corner_gradients(self, u):
+        """u as in forward() -> the corner gradients of the GLS reconstruction (DevicePlan.launch_corner_gradients): float64
+        (nnz_esup, 3) or (k, nnz_esup, 3) in esup position, from what is resident on the device NOW.  A plain tensor call on torch's
+        current stream: NO autograd -- the result carries no graph even when u requires grad; differentiating through the gradients
+        is not provided.  GLS, 3-D."""
+        if not isinstance(u, torch.Tensor):
+            raise TypeError(f"u must be a torch.Tensor, not {type(u).__name__}")
+        if u.dtype != torch.float64:
+            raise TypeError(f"u must be float64, not {u.dtype} (no silent cast)")
+        if u.device != self.device:
+            raise ValueError(f"u must be on {self.device}, not {u.device}")
+        if tuple(u.shape) != (self.n_elems,) and not (u.dim() == 2 and u.shape[0] >= 1 and u.shape[1] == self.n_elems):
+            raise ValueError(f"u must have shape ({self.n_elems},) or (k, {self.n_elems}), not {tuple(u.shape)}")
+        u = u.detach().contiguous()
+        k = 1 if u.dim() == 1 else u.shape[0]
+        grad = torch.empty(tuple(u.shape[:-1]) + (self.plan.nnz, 3), dtype=torch.float64, device=self.device)
+        self.plan.launch_corner_gradients(u.data_ptr(), grad.data_ptr(), k, stream=self._stream())
+        return grad
