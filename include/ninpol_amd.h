@@ -759,6 +759,55 @@ int nin_gls_rjacobian_linearize_dirty_host(nin_gls_rjacobian *J, const double *u
 int nin_gls_xjacobian_linearize_dirty_host(nin_gls_xjacobian *J, const double *u_cells, const double *neumann_values, int clear, int64_t *n_rows);
 int nin_grid_mark_dirty_device(nin_grid *g, const void *dev_ids, int ids_are_int64, int64_t n, int ids_are_cells, void *stream);
 
+/* ---- the corner-gradient operator, kept on the device: factorise once, apply G . u and G^T . v many times ----------
+ * nin_gls_corner_gradients_device assembles and factorises every node at every call.  The map u -> g is linear and depends on the
+ * points, the permeability and the Neumann flags alone: in a time loop or a Krylov solve on a fixed mesh every call after the first
+ * repeats the same factorisation, and the call has no transpose.  A nin_gls_gradop keeps the map.  It is block diagonal over the nodes:
+ * node p with ne = esup_ptr[p + 1] - esup_ptr[p] cells cells[0 .. ne) owns G_p [3 ne x ne], stored by columns,
+ *   gop[gop_ptr[p] + j * 3 ne + i],   i = 3 * (cell slot) + component,
+ * column j = the 3 ne corner gradients of p for the cell field that is 1 on cells[j] and 0 elsewhere -- bit for bit what
+ * nin_gls_corner_gradients_device writes for such a field.  gop_ptr [n_points + 1] (int64) is the exclusive sum of 3 ne^2, made on the
+ * device at creation from the connectivity alone; no update invalidates it.  The buffer takes 24 sum_p ne_p^2 bytes (15.4 GB at 216^3
+ * hexahedra): ask nin_gls_gradop_bytes before creating one.  A node the forward gives the zero row has zeros in every entry of its
+ * block; every entry is written by a factorisation (no memset, no atomics).  The face rows of the right-hand side are zero, as there.
+ * The operator depends on all three inputs, so a product after ANY of nin_grid_field_updates, nin_grid_geometry_updates or
+ * nin_grid_flag_updates moved from the stamp is refused with NIN_ESTATE and writes nothing; nin_gls_gradop_factorize answers for the new
+ * state (whole: following the dirty set is not provided).  Lifetime and ownership as nin_gls_jacobian.  3-D grids, GLS.
+ *
+ * nin_gls_gradop_bytes: *bytes = the size of gop for this grid (one scan on the device and a wait for it).
+ * nin_gls_gradop_create: gop_ptr, the node of every esup position (4 bytes per entry) and gop.  NIN_EINVAL for a NULL argument or a
+ *   grid that is not 3-D (both before the residency is looked at), NIN_ENODEVICE for a grid that is not on a device, NIN_ENOMEM.
+ * nin_gls_gradop_factorize: one launch of the adjoint kernel's gradient mode on every bin (NIN_GLS_ADJ_ONLY is not read) with the unit
+ *   columns as its fields, at what is resident NOW; asynchronous on `stream` after the first derivative call on a grid (which makes the
+ *   bins and synchronises).  Errors as nin_gls_corner_gradients_device.
+ * nin_gls_gradop_apply: dev_grad [n][nnz_esup][3] = G . dev_u [n][n_elems]: per entry the sum over the node's cells j ascending, from
+ *   0.0, each product rounded and then added; up to four fields share a pass over gop.  dev_flux [n][nnz_esup][3] and
+ *   dev_node_gradient [n][n_points][3] (either may be NULL) as nin_gls_corner_gradients_device derives them from dev_grad.
+ * nin_gls_gradop_apply_transpose: dev_ubar [n][n_elems] = G^T . dev_gbar [n][nnz_esup][3]: per (node, cell) pair the product of its
+ *   column with the node's slice of gbar, i ascending from 0.0, then per cell the sum of its pairs in ascending node id (the
+ *   transpose index, built, with a wait for `stream`, when it is not there).  The per-pair products are the object's scratch.
+ *   Both asynchronous on `stream`, deterministic: two calls agree bit for bit, a batch equals its members one by one.  Refusals in this
+ *   order: NIN_EINVAL for a NULL argument, for n < 1, for a grid that is not 3-D; NIN_ENODEVICE; NIN_ESTATE before the first
+ *   factorisation and after an update of the permeability, the points or the flags.
+ * nin_gls_gradop_records: the object's device arrays, read-only, the number of doubles in gop and (scratch_bytes not NULL) the bytes the
+ *   object holds beside gop.  nin_gls_gradop_stamp as nin_gls_jacobian_stamp.
+ * nin_gls_gradop_*_host: the same with HOST pointers, on the null stream, synchronous; nin_gls_gradop_fetch_host copies gop_ptr
+ *   [n_points + 1] and gop [gop_ptr[n_points]] to the host (gop NULL: gop_ptr alone, which needs no factorisation). */
+typedef struct nin_gls_gradop nin_gls_gradop;
+int nin_gls_gradop_bytes(nin_grid *g, int64_t *bytes);
+int nin_gls_gradop_create(nin_grid *g, nin_gls_gradop **out);
+int nin_gls_gradop_factorize(nin_gls_gradop *op, void *stream);
+int nin_gls_gradop_apply(nin_gls_gradop *op, int32_t n, const double *dev_u, double *dev_grad, double *dev_flux, double *dev_node_gradient,
+                         void *stream);
+int nin_gls_gradop_apply_transpose(nin_gls_gradop *op, int32_t n, const double *dev_gbar, double *dev_ubar, void *stream);
+int nin_gls_gradop_records(nin_gls_gradop *op, const int64_t **dev_gop_ptr, const double **dev_gop, int64_t *n_values, int64_t *scratch_bytes);
+int nin_gls_gradop_stamp(const nin_gls_gradop *op, int64_t stamp[3]);
+void nin_gls_gradop_destroy(nin_gls_gradop *op);
+int nin_gls_gradop_factorize_host(nin_gls_gradop *op);
+int nin_gls_gradop_apply_host(nin_gls_gradop *op, int32_t n, const double *u, double *grad, double *flux, double *node_gradient);
+int nin_gls_gradop_apply_transpose_host(nin_gls_gradop *op, int32_t n, const double *gbar, double *ubar);
+int nin_gls_gradop_fetch_host(nin_gls_gradop *op, int64_t *gop_ptr, double *gop);
+
 /* ---- native table packing (replaces the Python loops of interpolator.pyx:255-451, 501-509) ---------------------
  * nin_pack_connectivity: interpolator.pyx:333-361 -- per-type cell blocks (block b: rows[b] x cols[b] int64 node ids,
  *   element type type_id[b]) -> fixed-width, -1 padded connectivity [n_elems][8] + element_types [n_elems].

@@ -34,6 +34,9 @@ EXPORTS = (
     "nin_gls_weights_backward_points_device", "nin_gls_points_gradient_host",
     "nin_gls_weights_tangent_points_device", "nin_gls_points_tangent_host",
     "nin_gls_corner_gradients_device", "nin_gls_corner_gradients_host",
+    "nin_gls_gradop_bytes", "nin_gls_gradop_create", "nin_gls_gradop_factorize", "nin_gls_gradop_apply", "nin_gls_gradop_apply_transpose",
+    "nin_gls_gradop_records", "nin_gls_gradop_stamp", "nin_gls_gradop_destroy", "nin_gls_gradop_factorize_host", "nin_gls_gradop_apply_host",
+    "nin_gls_gradop_apply_transpose_host", "nin_gls_gradop_fetch_host",
     "nin_gls_jacobian_create", "nin_gls_jacobian_linearize", "nin_gls_jacobian_apply", "nin_gls_jacobian_apply_transpose",
     "nin_gls_jacobian_contrib", "nin_gls_jacobian_stamp", "nin_gls_jacobian_destroy", "nin_gls_jacobian_linearize_host",
     "nin_gls_jacobian_apply_host", "nin_gls_jacobian_apply_transpose_host", "nin_gls_jacobian_fetch_host",
@@ -107,6 +110,19 @@ def load():
     L.nin_gls_points_tangent_host.argtypes = [vp, vp, vp, i32, vp, vp]
     L.nin_gls_corner_gradients_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.nin_gls_corner_gradients_host.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.nin_gls_gradop_bytes.argtypes = [vp, ctypes.POINTER(i64)]
+    L.nin_gls_gradop_create.argtypes = [vp, ctypes.POINTER(vp)]
+    L.nin_gls_gradop_factorize.argtypes = [vp, vp]
+    L.nin_gls_gradop_apply.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.nin_gls_gradop_apply_transpose.argtypes = [vp, i32, vp, vp, vp]
+    L.nin_gls_gradop_records.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.nin_gls_gradop_stamp.argtypes = [vp, vp]
+    L.nin_gls_gradop_destroy.argtypes = [vp]
+    L.nin_gls_gradop_destroy.restype = None
+    L.nin_gls_gradop_factorize_host.argtypes = [vp]
+    L.nin_gls_gradop_apply_host.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.nin_gls_gradop_apply_transpose_host.argtypes = [vp, i32, vp, vp]
+    L.nin_gls_gradop_fetch_host.argtypes = [vp, vp, vp]
     L.nin_gls_jacobian_create.argtypes = [vp, ctypes.POINTER(vp)]
     L.nin_gls_jacobian_linearize.argtypes = [vp, vp, vp, vp]
     L.nin_gls_jacobian_apply.argtypes = [vp, i32, vp, vp, vp, vp]

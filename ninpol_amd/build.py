@@ -51,6 +51,9 @@ UNITS = [
     # what follows the corner gradients of the adjoint kernel's gradient mode: the fluxes -K g and the nodal mean, streamed; no contraction,
     # so that the host gets the same bits from the stated expression
     ("kernels_gls_gradient.hip", "hipcc", ["-ffp-contract=off"]),
+    # the corner-gradient operator the adjoint kernel's gradient mode leaves, applied: G . u per entry of esup, G^T . v per column and then
+    # per cell; no contraction, so that the host gets the same bits from the stated sums
+    ("kernels_gls_gradop.hip", "hipcc", ["-ffp-contract=off"]),
     ("kernels_csr.hip", "hipcc", []),
     # an incremental interpolate(): the dirty rows counted and packed on the device, patched into the caller's matrix on the host
     ("csr_dirty.hip", "hipcc", []),
@@ -77,6 +80,7 @@ UNITS = [
     ("abi_csr.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_apply.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_gradient.hip", "hipcc", ["-Wno-unknown-pragmas"]),
+    ("abi_gradop.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian_reduced.hip", "hipcc", ["-Wno-unknown-pragmas"]),
     ("abi_jacobian_points.hip", "hipcc", ["-Wno-unknown-pragmas"]),

@@ -13,10 +13,7 @@ CornerGradientCounts nin::corner_gradient_counts(int64_t n_elems, int64_t n_poin
 
 // what both entry points answer before they look at a device: NULL arguments first, then the count, then the grid's dimension
 static int corner_gradient_args(const nin_grid *g, const void *u, const void *grad, int32_t n_fields) {
-    if (!g || !u || !grad) return fail(NIN_EINVAL, "NULL argument");
-    if (n_fields < 1) return fail(NIN_EINVAL, "n_fields must be >= 1");
-    if (g->h.dim != 3) return fail(NIN_EINVAL, "the corner gradients are for 3-D grids only (this grid is %d-D)", (int)g->h.dim);
-    return NIN_OK;
+    return gradient_args(g, u, grad, n_fields, "n_fields", "the corner gradients are");
 }
 
 int nin_gls_corner_gradients_device(nin_grid *g, int32_t n_fields, const double *dev_u_cells, double *dev_grad, double *dev_node_values,

@@ -1,4 +1,4 @@
-// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_gradient / abi_jacobian / abi_jacobian_reduced / abi_jacobian_points / abi_jacobian_dirty.hip;
+// abi_internal.hpp -- what the units behind include/ninpol_amd.h share (abi_grid / abi_plan / abi_update / abi_csr / abi_apply / abi_gradient / abi_gradop / abi_jacobian / abi_jacobian_reduced / abi_jacobian_points / abi_jacobian_dirty.hip;
 // exchange.hip takes the error setter): the grid behind the handle, the text of nin_last_error(), the preconditions of the entry
 // points, device memory owned by the grid or by one call, and the functions of one unit that another calls.
 #pragma once
@@ -219,6 +219,14 @@ struct CornerGradientCounts {
     size_t u, grad, node_values, node_gradient;
 };
 CornerGradientCounts corner_gradient_counts(int64_t n_elems, int64_t n_points, int64_t nnz_esup, int32_t n_fields);
+// what the entry points of abi_gradient.hip and abi_gradop.hip answer before they look at a device, in this order: a NULL argument, a
+// count below one (`count_name` in the text), a grid that is not 3-D (`what` in the text)
+inline int gradient_args(const nin_grid *g, const void *in, const void *out, int32_t n, const char *count_name, const char *what) {
+    if (!g || !in || !out) return fail(NIN_EINVAL, "NULL argument");
+    if (n < 1) return fail(NIN_EINVAL, "%s must be >= 1", count_name);
+    if (g->h.dim != 3) return fail(NIN_EINVAL, "%s for 3-D grids only (this grid is %d-D)", what, (int)g->h.dim);
+    return NIN_OK;
+}
 
 // ---- what the kept Jacobians share (abi_jacobian.hip, abi_jacobian_reduced.hip, abi_jacobian_points.hip) --------------------------------------------------
 // nin_gls_jacobian, nin_gls_rjacobian and nin_gls_xjacobian begin with this; each adds the buffers it owns
@@ -290,5 +298,28 @@ int jacobian_apply_host(const KeptJacobian *J, int32_t n, const char *linearize_
     return extra_out ? dev_fetch(extra_out, dextra, extra_per * k) : NIN_OK;
 }
 
+// abi_gradop.hip: the sizes behind a nin_gls_gradop, in 64-bit arithmetic.  A node with ne cells owns 3 ne^2 doubles of the
+// operator; n_values is their sum over the nodes (gop_ptr[P], scanned on the device).  The object holds gop [n_values], gop_ptr [P + 1]
+// (int64) and pos_node [nnz_esup] (int32); dots [min(n, kGradopChunk)][nnz_esup] is the transposed product's scratch
+inline int64_t gradop_block_values(int64_t ne) { return 3 * ne * ne; }
+struct GradopBytes {
+    int64_t gop, gop_ptr, pos_node;
+};
+inline GradopBytes gradop_bytes(int64_t n_values, int64_t n_points, int64_t nnz_esup) {
+    return {8 * n_values, 8 * (n_points + 1), 4 * nnz_esup};
+}
+inline size_t gradop_dots_count(int64_t nnz_esup, int32_t n) { return (size_t)std::min<int32_t>(n, kGradopChunk) * (size_t)nnz_esup; }
+
 }  // namespace nin
 #pragma GCC visibility pop
+
+// The corner-gradient operator a caller keeps (abi_gradop.hip; here so that tools/sanitize_gradop_driver.hip can stand one on a host-only
+// grid).  `linearized` and `stamp` of KeptJacobian are those of the last factorisation
+struct nin_gls_gradop : nin::KeptJacobian {
+    int64_t *gop_ptr = nullptr;    // [P + 1], made at creation from the connectivity alone
+    int32_t *pos_node = nullptr;   // [nnz_esup]
+    double *gop = nullptr;         // [n_values]
+    double *dots = nullptr;        // the transposed product's scratch, made by the first call and grown to the largest chunk seen
+    int32_t dots_n = 0;
+    int64_t n_values = 0, nnz = 0, points = 0, elems = 0;   // (of the grid at creation)
+};

@@ -1,7 +1,8 @@
 // kernels_gls_adjoint.hip -- the GLS weights differentiated with respect to the permeability and to the node coordinates, gfx950.
-// DESIGN.md 4.11 has the mathematics, the bins and the layout of this unit; 4.12, 4.14, 4.15, 4.17 and 4.21 the other five modes.
+// DESIGN.md 4.11 has the mathematics, the bins and the layout of this unit; 4.12, 4.14, 4.15, 4.17 and 4.21 the other five modes, 4.22
+// the unit-column variant of the last.
 //
-// nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD> serves six modes (listed at its static_assert; GRD, the corner gradients of DESIGN.md
+// nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD, GOP> serves six modes (listed at its static_assert; GRD, the corner gradients of DESIGN.md
 // 4.21, differentiates nothing: it solves for the other 3 ne unknowns of the node's system).  They share the head: node header,
 // assembly, Householder QR with R kept, y, r, rho and the verdict.  The header, the zero-row rule and the assembly are this unit's OWN
 // TEXT of what gls_dense.hpp holds for the forward kernels (read_node, DenseNode::zero_row, cell_rows, internal_face_rows with
@@ -54,11 +55,12 @@ struct AdjointIo {
     union {
         const double *tan_dm;            // tangent: d diff_mag [n_tan][E] or null (folded from g.perm)
         const double *tpt_cell;          // tangent with PTS: dC of every cell [n_tan][E][3]
+        const long long *gop_ptr;        // GOP: where node p's block begins in grd_out [P + 1]
     };
     union {
         double *tan_csr;                 // tangent: d stored weights [n_tan][nnz]
         double *pts_face;                // PTS: (fcbar, Nbar) of every (node, face) pair [nnz_fsup][6]
-        double *grd_out;                 // GRD: the corner gradients [grd_n][nnz][3]
+        double *grd_out;                 // GRD: the corner gradients [grd_n][nnz][3]; GOP: the kept operator [gop_ptr[P]]
     };
     union {
         double *tan_nws;                 // tangent: d neumann_ws [n_tan][P] or null
@@ -149,14 +151,16 @@ __device__ __forceinline__ void back_substitute(const double *A, int ld, int nc,
     }
 }
 
-template <int TW, bool LDS, bool TAN, bool RED, bool PTS, bool GRD = false>
+template <int TW, bool LDS, bool TAN, bool RED, bool PTS, bool GRD = false, bool GOP = false>
 __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, const int32_t *__restrict__ nodes, int32_t count, int add_neumann,
                                                                  AdjointIo io, double *scratch, long long scratch_stride) {
     // (TAN, RED, PTS): (0, 0, 0) K adjoint, (0, 1, 0) reduced K adjoint, (0, 0, 1) coordinate adjoint, (1, 0, 0) K tangent,
     // (1, 0, 1) coordinate tangent; the other three combinations mean nothing.  GRD, with none
-    // of the three: the corner gradients of cell fields
+    // of the three: the corner gradients of cell fields.  GOP, with GRD: the fields are the indicators of the node's own
+    // cells, one after the other, and column t of the node's block of the kept gradient operator takes the result
     static_assert(!RED || (!TAN && !PTS), "(TAN, RED, PTS) is not one of the five modes: RED goes with neither TAN nor PTS");
     static_assert(!GRD || (!TAN && !RED && !PTS), "GRD is a mode of its own: it goes with none of TAN, RED and PTS");
+    static_assert(!GOP || GRD, "GOP is a variant of GRD");
     extern __shared__ double smem[];
     const double *__restrict__ const grad_csr = io.grad_csr, *__restrict__ const grad_nws = io.grad_nws;
     double *__restrict__ const contrib = io.contrib;
@@ -183,7 +187,10 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
         const int m = ne + 3 * n_if + (is_neu ? n_bf : 0);     // rows actually populated
         // the forward's zero rows (DenseNode::zero_row, gls_dense.hpp): nothing depends on K there
         if (((fl & 1) && !is_neu) || n_if == 0 || m < n - 1) {
-            if constexpr (GRD) {
+            if constexpr (GOP) {
+                double *ob = io.grd_out + io.gop_ptr[p];
+                for (int i = tid; i < 3 * ne * ne; i += nthr) ob[i] = 0.0;
+            } else if constexpr (GRD) {
                 for (int t = 0; t < io.grd_n; ++t) {
                     for (int i = tid; i < 3 * ne; i += nthr) io.grd_out[3 * ((size_t)t * (size_t)io.nnz + (size_t)eb) + i] = 0.0;
                     if (io.grd_up && tid == 0) io.grd_up[(size_t)t * g.n_points + p] = 0.0;
@@ -384,19 +391,22 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
         if constexpr (GRD) {
             // ---- the gradient tail: per field b = u on the cell rows and 0 on every face row, u_p = (r.b) / rho,
             //      g = R^-1 (Q^T (b - c u_p))(0:n-1) -- with u_p the full least-squares solution of [A | c] x = b.  Wavefront 0 alone: one
-            //      Q^T and one triangular solve per field, in q.  Lane sums in lane order, wave_sum's fixed tree: two calls agree bit for bit
+            //      Q^T and one triangular solve per field, in q.  Lane sums in lane order, wave_sum's fixed tree: two calls agree bit for bit.
+            //      GOP: field t is the indicator of the node's cell t, the same expressions on 1.0 and 0.0, so column t of
+            //      the node's block holds, bit for bit, what the loop writes for a global field that is 1 on that cell alone among the node's
             if (wave == 0) {
                 const bool ok = tau[n - 1] != 0.0;   // uniform
                 const double rho = y[n - 1];
-                for (int t = 0; t < io.grd_n; ++t) {
-                    const double *u = io.grd_u + (size_t)t * (size_t)g.n_elems;
-                    double *og = io.grd_out + 3 * ((size_t)t * (size_t)io.nnz + (size_t)eb);
+                for (int t = 0; t < (GOP ? ne : io.grd_n); ++t) {
+                    const double *u = GOP ? nullptr : io.grd_u + (size_t)t * (size_t)g.n_elems;
+                    double *og = GOP ? io.grd_out + ((size_t)io.gop_ptr[p] + (size_t)t * (size_t)(3 * ne))
+                                     : io.grd_out + 3 * ((size_t)t * (size_t)io.nnz + (size_t)eb);
                     double up = 0.0;
                     if (ok) {
                         double s = 0.0;
-                        for (int i = lane; i < ne; i += 64) s += rv[i] * u[cells[i]];
+                        for (int i = lane; i < ne; i += 64) s += rv[i] * (GOP ? (i == t ? 1.0 : 0.0) : u[cells[i]]);
                         up = wave_sum(s) / rho;
-                        for (int i = lane; i < m; i += 64) qv[i] = i < ne ? u[cells[i]] - up : 0.0;   // (a lane's own rows, as reflect takes them)
+                        for (int i = lane; i < m; i += 64) qv[i] = i < ne ? (GOP ? (i == t ? 1.0 : 0.0) : u[cells[i]]) - up : 0.0;   // (a lane's own rows, as reflect takes them)
                         for (int k = 0; k < n - 1; ++k) reflect(A, ld, m, k, tau[k], qv, lane);
                         wave_sync<LDS>();
                         back_substitute<LDS>(A, ld, n - 1, qv, lane);
@@ -404,7 +414,8 @@ __global__ __launch_bounds__(64 * TW) void nin_gls_adjoint_kernel(GridView g, co
                     } else {
                         for (int i = lane; i < 3 * ne; i += 64) og[i] = 0.0;
                     }
-                    if (io.grd_up && lane == 0) io.grd_up[(size_t)t * g.n_points + p] = up;
+                    if constexpr (!GOP)
+                        if (io.grd_up && lane == 0) io.grd_up[(size_t)t * g.n_points + p] = up;
                     wave_sync<LDS>();   // (q is the next field's)
                 }
             }
@@ -743,15 +754,15 @@ __global__ __launch_bounds__(256) void nin_adjoint_gather_kernel(int32_t n_elems
     for (int k = 0; k < 9; ++k) grad_perm[9 * (size_t)e + k] = acc[k];
 }
 
-template <int TW, bool LDS, bool TAN, bool RED, bool PTS, bool GRD>
+template <int TW, bool LDS, bool TAN, bool RED, bool PTS, bool GRD, bool GOP>
 int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t bytes, int add_neumann, const AdjointIo &io, double *scratch,
                int64_t stride, int32_t slots, hipStream_t stream) {
-    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD>;
+    auto kern = nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD, GOP>;
     int64_t blocks;
     size_t lds = 0;
     if (LDS) {
         lds = (size_t)bytes;
-        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD>>(lds)) return -3;
+        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD, GOP>>(lds)) return -3;
         int64_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : (int64_t)lds);
         if (per_cu > 32 / TW) per_cu = 32 / TW;
         if (per_cu < 1) per_cu = 1;
@@ -765,16 +776,16 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
 }
 
 // one bin's nodes through the class of that bin: 1, 2, 4 wavefronts in LDS, 8 over a global-memory slot
-template <bool TAN, bool RED, bool PTS = false, bool GRD = false>
+template <bool TAN, bool RED, bool PTS = false, bool GRD = false, bool GOP = false>
 int launch_bin_of(const GridView &g, int bin, const AdjBinRun &r, int add_neumann, const AdjointIo &io, hipStream_t stream) {
     if (r.count <= 0) return 0;
     switch (bin) {
-        case 0: return launch_bin<1, true, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 1: return launch_bin<2, true, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
-        case 2: return launch_bin<4, true, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 0: return launch_bin<1, true, TAN, RED, PTS, GRD, GOP>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 1: return launch_bin<2, true, TAN, RED, PTS, GRD, GOP>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
+        case 2: return launch_bin<4, true, TAN, RED, PTS, GRD, GOP>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
         case 3:
             if (!r.scratch || r.scratch_slots < 1 || r.scratch_stride * 8 < r.bytes) return -1;
-            return launch_bin<8, false, TAN, RED, PTS, GRD>(g, r.nodes, r.count, r.bytes, add_neumann, io, r.scratch, r.scratch_stride, r.scratch_slots,
+            return launch_bin<8, false, TAN, RED, PTS, GRD, GOP>(g, r.nodes, r.count, r.bytes, add_neumann, io, r.scratch, r.scratch_stride, r.scratch_slots,
                                                        stream);
     }
     return -1;
@@ -832,6 +843,13 @@ int launch_gls_corner_gradients(const GridView &g, int bin, const AdjBinRun &run
     AdjointIo io{};
     io.grd_n = n_fields; io.grd_u = u_cells; io.grd_out = grad; io.grd_up = node_values; io.nnz = (long long)nnz;
     return launch_bin_of<false, false, false, true>(g, bin, run, 0, io, stream);
+}
+
+int launch_gls_gradop_factorize(const GridView &g, int bin, const AdjBinRun &run, const int64_t *gop_ptr, double *gop, hipStream_t stream) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "gop_ptr is read as long long");
+    AdjointIo io{};
+    io.gop_ptr = reinterpret_cast<const long long *>(gop_ptr); io.grd_out = gop;
+    return launch_bin_of<false, false, false, true, true>(g, bin, run, 0, io, stream);
 }
 
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,

@@ -183,6 +183,25 @@ int launch_gls_corner_gradients(const GridView &g, int bin, const AdjBinRun &run
 int launch_corner_flux(const GridView &g, int64_t nnz, int32_t n_fields, const double *grad, double *flux, hipStream_t stream);
 int launch_node_gradient(const GridView &g, int64_t nnz, int32_t n_fields, const double *grad, double *node_gradient, hipStream_t stream);
 
+// the corner-gradient operator kept and applied, all DEVICE pointers.  Node p with ne cells owns the block G_p [3 ne x ne] at
+// gop[gop_ptr[p] + j * 3 ne + i]: column j = the 3 ne corner gradients of p for the indicator of its cell j, i = 3 * (cell slot) + component.
+// launch_gradop_layout: gop_ptr [P + 1] = the exclusive sum of 3 ne^2 (count [P + 1] and tmp scratch; tmp = null: *tmp_bytes is set to what
+//   the scan needs and nothing is launched) and pos_node [nnz] = the node whose row holds the esup position.
+// launch_gls_gradop_factorize (kernels_gls_adjoint.hip): the gradient mode on the nodes of one bin with the unit columns as its fields;
+//   every entry of every listed node's block is written, zeros where the forward has its zero row.
+// launch_gradop_apply: grad [n][nnz][3] = G . u [n][E], per entry j ascending from 0.0, up to kGradopChunk fields per pass over gop.
+// launch_gradop_apply_transpose: ubar [n][E] = G^T . gbar [n][nnz][3]: dots [min(n, kGradopChunk)][nnz] takes the product of every column
+//   with its node's slice of gbar (i ascending from 0.0), then a cell sums its entries in the order of the transpose index
+constexpr int kGradopChunk = 4;
+int launch_gradop_layout(const GridView &g, int64_t nnz, int64_t *count, void *tmp, size_t *tmp_bytes, int64_t *gop_ptr, int32_t *pos_node,
+                         hipStream_t stream);
+int launch_gls_gradop_factorize(const GridView &g, int bin, const AdjBinRun &run, const int64_t *gop_ptr, double *gop, hipStream_t stream);
+int launch_gradop_apply(const GridView &g, int64_t nnz, const int64_t *gop_ptr, const int32_t *pos_node, const double *gop, int32_t n,
+                        const double *u, double *grad, hipStream_t stream);
+int launch_gradop_apply_transpose(const GridView &g, int64_t nnz, const int32_t *cell_ptr, const int32_t *cell_pos, const int64_t *gop_ptr,
+                                  const int32_t *pos_node, const double *gop, int32_t n, const double *gbar, double *dots, double *ubar,
+                                  hipStream_t stream);
+
 // the GLS Jacobian kept and applied (kernels_gls_jacobian.hip), all DEVICE pointers; contrib [nnz_esup][10] as an adjoint
 // launch with grad_csr = u[esup] left it, fold [E] = d diff_mag / d K_dd at the linearisation point.
 // launch_jac_seed: grad_csr[pos] = u[esup[pos]].  launch_jac_fold: fold from the resident g.perm.

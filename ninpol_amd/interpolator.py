@@ -23,6 +23,7 @@ from .jacobian import (GlsJacobian, GlsReducedJacobian, GlsShapeJacobian, Permea
                        REDUCED_N_PARAMS, ReducedPermeabilityJacobian, _check_n_params, reduced_basis)
 from .jacobian import (GlsDirtyJacobian, GlsDirtyReducedJacobian, UpdatablePermeabilityJacobian,  # noqa: F401
                        UpdatableReducedPermeabilityJacobian)
+from .gradop import GlsGradientOperator, GradientOperator  # noqa: F401
 
 _pinned = _lib.PinnedPool()
 
@@ -1001,6 +1002,24 @@ class Interpolator:
         _lib.check(_lib.load().nin_gls_corner_gradients_host(g._h, _ptr(u), k, _ptr(grad), None, None, _ptr(out)))
         return out
 
+    def gradient_operator(self, variable):
+        """The map from a cell field to what `corner_gradients(variable, field)` returns, factorised ONCE at the grid's resident
+        coordinates, permeability and flags and kept on the device: a scipy LinearOperator of shape (3 nnz_esup, n_elems), float64
+        (GradientOperator: `matvec` = the corner gradients of a cell field, flattened (nnz_esup, 3); `rmatvec` = the transpose, which
+        corner_gradients() does not have; `matmat` / `rmatmat` batched in one launch each; `to_scipy()` the explicit csr_matrix, the
+        gradient stencil dg/du of an implicit flux scheme; `update()`; `release()`).  corner_gradients() assembles and factorises every
+        node at every call; this does so once and every product afterwards streams the kept buffer (24 sum_p ne_p^2 bytes on the
+        device, 15.4 GB at 216^3 hexahedra).  The operator depends on all three inputs: after a later update_permeability(),
+        update_points() or update_neumann_flags() the products raise (NinpolError, a RuntimeError) until `update()` factorises again.
+        The face rows of the right-hand side are zero, as in corner_gradients().  3-D meshes, GLS only.  Host-synchronous, numpy in
+        and out."""
+        self._check_call(variable=variable)
+        self._perm_rows()   # (ValueError without a permeability)
+        self._gls_tables_to_device(variable)
+        op = GlsGradientOperator(self.grid)
+        _lib.check(_lib.load().nin_gls_gradop_factorize_host(op._handle()))
+        return GradientOperator(op, self, variable)
+
     def permeability_jacobian(self, variable, cell_values=None, neumann_values=None, basis=None):
         """The Jacobian of what `apply(variable, "gls")` returns, `W u` (+ `neumann_ws * neumann_values` when those are given), with
         respect to the permeability table, linearised ONCE at the resident table and kept on the device: a scipy LinearOperator of
@@ -1275,6 +1294,18 @@ class DevicePlan:
         self._gls_derivative("launch_corner_gradients", "are not the solution of a system that has cell gradients")
         _lib.check(_lib.load().nin_gls_corner_gradients_device(self.grid._h, int(n_fields), _vp(u_ptr), _vp(grad_ptr), _vp(node_values_ptr),
                                                                _vp(flux_ptr), _vp(node_gradient_ptr), ctypes.c_void_p(stream)))
+
+    def gradient_operator(self, stream=0):
+        """The map u -> launch_corner_gradients(u), kept on the device: a GlsGradientOperator factorised at what is resident now
+        (geometry, flags, K).  One launch of the adjoint kernel's gradient mode with the unit columns of every node as its fields;
+        its launch_apply / launch_apply_transpose then stream 24 sum_p ne_p^2 bytes instead of factorising every node again, and the
+        second is the transpose launch_corner_gradients does not have.  The object owns its buffers.  Its launches answer until the
+        next update of the permeability, the points or the flags (then: its factorize()).  3-D grids.  GLS only: a plan of IDW or LS
+        raises instead of returning zeros."""
+        self._gls_derivative("gradient_operator", "are not the solution of a system that has cell gradients")
+        op = GlsGradientOperator(self.grid, plan=self)
+        op.factorize(stream)
+        return op
 
     def linearize(self, u_ptr, neumann_values_ptr=0, stream=0):
         """The Jacobian of the node values `W u + neumann_ws * b` in the permeability, kept on the device: a GlsJacobian linearised at

@@ -15,6 +15,7 @@ coordinates instead (nin_gls_xjacobian).
 Not imported by `ninpol_amd/__init__.py`: importing the package loads nothing native and does not import torch.  This module
 imports torch, and opens its device, before the native library loads ("A process that also uses a PyTorch-ROCm
 wheel")."""
+import numpy as np
 import torch
 
 if torch.cuda.is_available():
@@ -169,6 +170,85 @@ class _ConstantWeightsFn(torch.autograd.Function):
         K, scale = ctx.saved_tensors
         return (torch.zeros_like(K) if ctx.needs_input_grad[0] else None,
                 torch.zeros_like(scale) if scale is not None and ctx.needs_input_grad[1] else None, None)
+
+
+class _GradientOperatorFn(torch.autograd.Function):
+    """u [k][n_elems] -> G u [k][nnz_esup][3] (and the flux -K G u beside it) through a kept gradient operator; backward G^T of the
+    cotangent, the flux's folded in first; linear in u, so the forward derivative is the function itself on du."""
+
+    @staticmethod
+    def forward(ctx, u, op, want_flux):
+        ctx.op, ctx.want_flux = op, want_flux
+        grad, flux = op._apply(u, want_flux)
+        return (grad, flux) if want_flux else grad
+
+    @staticmethod
+    def jvp(ctx, du, _, __):
+        grad, flux = ctx.op._apply(du.contiguous(), ctx.want_flux)
+        return (grad, flux) if ctx.want_flux else grad
+
+    @staticmethod
+    def backward(ctx, ggrad, gflux=None):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return ctx.op._apply_transpose(ctx.op.fold(ggrad, gflux)), None, None
+
+
+class KeptGradients:
+    """What CellToNode.gradient_operator() returns: `op(u, flux=False)` is the corner gradients of u -- float64 (nnz_esup, 3) or
+    (k, nnz_esup, 3) in esup position, what CellToNode.corner_gradients(u) returns up to the rounding of another summation order -- from
+    a GlsGradientOperator (`operator`) factorised once, and, unlike corner_gradients(), differentiable in u: backward() is the
+    transposed product, and under torch.autograd.forward_ad the call is linear.  With flux=True it returns (grad, flux), flux = -K_e grad
+    with the permeability resident at the factorisation; a cotangent fbar of the flux reaches u through
+    `gbar[..., d] += -((K[0][d] fbar[0] + K[1][d] fbar[1]) + K[2][d] fbar[2])` (torch arithmetic, one rounding per operation) before the
+    one transposed product.  Everything runs on torch's current stream.  After an update of the permeability, the points or the flags
+    the call raises (NinpolError) until `factorize()`."""
+
+    def __init__(self, module):
+        self.module = module
+        self.operator = module.plan.gradient_operator(module._stream())
+        self._read_permeability()
+
+    def _read_permeability(self):
+        m = self.module
+        g = m.plan.grid
+        got = g.fetch_permeability()                    # (waits for the device: the factorisation is behind it)
+        K = torch.from_numpy(got[0]).to(m.device)       # [E][9]
+        self.K = K[torch.from_numpy(np.asarray(g.esup).astype(np.int64)).to(m.device)].reshape(-1, 3, 3)      # [nnz][3][3], row-major K_e per entry
+
+    def factorize(self):
+        """Factorise again at what is resident now (GlsGradientOperator.factorize) and read the permeability of the flux fold again."""
+        self.operator.factorize(self.module._stream())
+        self._read_permeability()
+
+    def fold(self, ggrad, gflux):
+        """the cotangent of G u from those of (grad, flux): ggrad + (-K^T gflux) per entry of esup, either may be None"""
+        if gflux is None:
+            return ggrad.contiguous()
+        K, f = self.K, gflux
+        back = torch.stack([-((K[:, 0, d] * f[..., 0] + K[:, 1, d] * f[..., 1]) + K[:, 2, d] * f[..., 2]) for d in range(3)], dim=-1)
+        return (back if ggrad is None else ggrad + back).contiguous()
+
+    def _apply(self, u, want_flux):
+        m = self.module
+        k = 1 if u.dim() == 1 else u.shape[0]
+        shape = tuple(u.shape[:-1]) + (m.plan.nnz, 3)
+        grad = torch.empty(shape, dtype=torch.float64, device=m.device)
+        flux = torch.empty(shape, dtype=torch.float64, device=m.device) if want_flux else None
+        self.operator.launch_apply(u.data_ptr(), grad.data_ptr(), k, flux.data_ptr() if want_flux else 0, 0, m._stream())
+        return grad, flux
+
+    def _apply_transpose(self, gbar):
+        m = self.module
+        k = 1 if gbar.dim() == 2 else gbar.shape[0]
+        out = torch.empty(tuple(gbar.shape[:-2]) + (m.n_elems,), dtype=torch.float64, device=m.device)
+        self.operator.launch_apply_transpose(gbar.data_ptr(), out.data_ptr(), k, m._stream())
+        return out
+
+    def __call__(self, u, flux=False):
+        m = self.module
+        m._check_cell_field(u)
+        return _GradientOperatorFn.apply(u.contiguous(), self, bool(flux))
 
 
 class Linearization:
@@ -544,6 +624,23 @@ class CellToNode(torch.nn.Module):
             return _CellToNodeFn.apply(u.contiguous(), self, self.weights)
         weights, _ = self.weights_of(K, scale, points)
         return _CellToNodeFn.apply(u.contiguous(), self, weights)
+
+    def _check_cell_field(self, u):
+        if not isinstance(u, torch.Tensor):
+            raise TypeError(f"u must be a torch.Tensor, not {type(u).__name__}")
+        if u.dtype != torch.float64:
+            raise TypeError(f"u must be float64, not {u.dtype} (no silent cast)")
+        if u.device != self.device:
+            raise ValueError(f"u must be on {self.device}, not {u.device}")
+        if tuple(u.shape) != (self.n_elems,) and not (u.dim() == 2 and u.shape[0] >= 1 and u.shape[1] == self.n_elems):
+            raise ValueError(f"u must have shape ({self.n_elems},) or (k, {self.n_elems}), not {tuple(u.shape)}")
+
+    def gradient_operator(self):
+        """The corner gradients as a kept, differentiable operator: a KeptGradients `op`, `op(u, flux=False)`,
+        factorised once from what is resident on the device NOW.  Where corner_gradients(u) factorises every node at every call and
+        carries no graph, `op(u)` streams the kept operator, its backward pass is the transposed product (the flux's cotangent
+        folded in) and it works under torch.autograd.forward_ad.  GLS, 3-D; corner_gradients() itself is unchanged."""
+        return KeptGradients(self)
 
     def corner_gradients(self, u):
         """u as in forward() -> the corner gradients of the GLS reconstruction (DevicePlan.launch_corner_gradients): float64
