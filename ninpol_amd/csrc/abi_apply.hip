@@ -66,7 +66,7 @@ int nin_apply_device(nin_grid *g, int method, const double *dev_u_cells, int32_t
                                               dev_node_values, dev_neumann_ws, d.gls_queue + gls_plan_row(gk::hex8).counter, stream);
         if (!rc) rc = gls_main(d, -1, false, gls_only(), 1, d.apply_weights, dev_neumann_ws, stream);
         if (!rc) rc = launch_apply_list(d.v, d.apply_weights, dev_u_cells, n_fields, dev_node_values, d.noncube_nodes, d.noncube_count, stream);
-        if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (rc) return rc;
         return NIN_OK;
     }
     // the weights are computed ONCE, whatever the number of fields (they depend on the mesh, the permeability and the
@@ -115,7 +115,7 @@ int nin_spmv_device(nin_grid *g, const double *dev_csr_data, const double *dev_u
     const int rc = n_fields == 1 ? launch_apply(d.v, dev_csr_data, dev_u_cells, dev_node_values, (int32_t)g->h.mx_elems_per_point, d.nnz_e, stream)
                                  : launch_apply_fields(d.v, dev_csr_data, dev_u_cells, n_fields, dev_node_values, (int32_t)g->h.mx_elems_per_point,
                                                        d.nnz_e, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -131,7 +131,7 @@ int nin_spmv_transpose_device(nin_grid *g, const double *dev_csr_data, const dou
     if (rc) return rc;
     rc = launch_apply_transpose(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.tr_cell_node, d.v.dim == 2 ? 4 : 8, dev_csr_data, dev_node_values,
                                 n_fields, dev_cell_values, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -265,7 +265,7 @@ int nin_gls_weights_backward_device(nin_grid *g, int add_neumann, const double *
     if (rc) return rc;
     rc = launch_adjoint_bins(d, add_neumann, adjoint_only_from_env(), dev_grad_csr, dev_grad_neumann_ws, d.adj_contrib, stream);
     if (!rc) rc = launch_adjoint_gather(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.adj_contrib, dev_grad_perm, dev_grad_diff_mag, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -277,7 +277,7 @@ int nin_sddmm_device(nin_grid *g, const double *dev_u_cells, const double *dev_n
     if (int rc = on_device(g, kHintKernels)) return rc;
     HIP_TRY(hipSetDevice(d.device));
     const int rc = launch_sddmm(d.v, dev_u_cells, dev_node_values, n_fields, dev_grad_csr, static_cast<hipStream_t>(stream_));
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -334,7 +334,7 @@ int nin_gls_weights_backward_points_device(nin_grid *g, int add_neumann, const d
                                          dev_grad_points, stream);
     });
     if (!rc) rc = launch_shape_gather(d.v, d.up_inpofa, d.tr_cell_ptr, d.tr_cell_pos, d.shape_cell, d.shape_face, d.shape_slot, dev_grad_points, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -357,7 +357,7 @@ int nin_gls_weights_tangent_device(nin_grid *g, int add_neumann, int32_t n_tange
         return launch_gls_tangent(d.v, b, run, add_neumann ? 1 : 0, n_tangents, dev_tangent_perm, dev_tangent_diff_mag, dev_tangent_csr,
                                   dev_tangent_neumann_ws, d.nnz_e, stream);
     });
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -411,7 +411,7 @@ int nin_gls_weights_tangent_points_device(nin_grid *g, int add_neumann, int32_t 
         return launch_gls_tangent_points(d.v, b, run, add_neumann ? 1 : 0, n_tangents, dev_tangent_points, d.shape_tan_cell, d.shape_tan_face,
                                          dev_tangent_csr, dev_tangent_neumann_ws, d.nnz_e, stream);
     });
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 

@@ -94,7 +94,7 @@ int weights_chunk(nin_grid *g, int method, int k, double *out, double *nws, hipS
     HIP_TRY(hipMemsetAsync(d.gls_queue, 0, kGlsQueueInts * sizeof(int32_t), stream));   // the launches' work counters
     int rc = gls_side_begin(d, k, 1, out, nws, stream);
     if (!rc) rc = gls_main(d, k, true, -1, 1, out, nws, stream);
-    return rc ? fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError())) : NIN_OK;
+    return rc;
 }
 
 // interpolate() as a pipeline over kE2eChunks pieces of the node range: while piece k's surviving entries cross PCIe (the floor
@@ -353,16 +353,14 @@ int nin_hostmatrix_update(nin_hostmatrix *m, int clear, void *stream_, int64_t *
     if (!rc) {
         (void)(step(hipMemsetAsync(m->pack_cnt + total, 0, sizeof(int32_t), stream), "hipMemsetAsync") &&
                step(hipMemsetAsync(m->pack_off + total + 1, 0, sizeof(int32_t), stream), "hipMemsetAsync"));
-        if (!rc && launch_dirty_row_nnz(d.v, m->weights, d.dirty_lists, total, m->pack_cnt, m->cnt, m->pack_off + total + 1, stream))
-            rc = fail(NIN_EHIP, "row count kernel: %s", hipGetErrorString(hipGetLastError()));
+        if (!rc) rc = launch_dirty_row_nnz(d.v, m->weights, d.dirty_lists, total, m->pack_cnt, m->cnt, m->pack_off + total + 1, stream);
         size_t tb = m->scan_tmp_bytes;
         // the sizes leave on the copy stream as soon as the scan is done, under the pack kernel: the call's second and last wait
         (void)(step(hipcub::DeviceScan::ExclusiveSum(m->scan_tmp, tb, m->pack_cnt, m->pack_off, total + 1, stream), "scan of the row counts") &&
                step(hipEventRecord(ev_scan, stream), "hipEventRecord") && step(hipStreamWaitEvent(cs, ev_scan, 0), "hipStreamWaitEvent") &&
                step(hipMemcpyAsync(back, m->pack_off + total, sizeof back, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync"));
-        if (!rc && launch_dirty_pack(d.v, m->weights, m->nws, d.dirty_lists, total, m->pack_off, m->pack_node, m->pack_nws, m->pack_indices,
-                                     m->pack_data, stream))
-            rc = fail(NIN_EHIP, "pack kernel: %s", hipGetErrorString(hipGetLastError()));
+        if (!rc)
+            rc = launch_dirty_pack(d.v, m->weights, m->nws, d.dirty_lists, total, m->pack_off, m->pack_node, m->pack_nws, m->pack_indices, m->pack_data, stream);
         (void)(step(hipEventRecord(ev_pack, stream), "hipEventRecord") && step(hipStreamSynchronize(cs), "reading the pack's size back"));
     }
     if (!rc && (back[0] < 0 || (size_t)back[0] > bound || back[1] < 0 || back[1] > total))

@@ -28,7 +28,7 @@ int nin_gls_corner_gradients_device(nin_grid *g, int32_t n_fields, const double 
     });
     if (!rc && dev_flux) rc = launch_corner_flux(d.v, d.nnz_e, n_fields, dev_grad, dev_flux, stream);
     if (!rc && dev_node_gradient) rc = launch_node_gradient(d.v, d.nnz_e, n_fields, dev_grad, dev_node_gradient, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 

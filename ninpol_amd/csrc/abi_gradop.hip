@@ -19,11 +19,9 @@ static int gradop_layout(DeviceGrid &d, int64_t *gop_ptr, int32_t *pos_node, int
     DevTmp<char> tmp;
     size_t tmp_bytes = 0;
     HIP_TRY(hipMalloc((void **)&count, ((size_t)P + 1) * sizeof(int64_t)));
-    if (launch_gradop_layout(d.v, d.nnz_e, count, nullptr, &tmp_bytes, gop_ptr, pos_node, stream))
-        return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (int rc = launch_gradop_layout(d.v, d.nnz_e, count, nullptr, &tmp_bytes, gop_ptr, pos_node, stream)) return rc;
     HIP_TRY(hipMalloc((void **)&tmp, std::max<size_t>(tmp_bytes, 1)));
-    if (launch_gradop_layout(d.v, d.nnz_e, count, tmp, &tmp_bytes, gop_ptr, pos_node, stream))
-        return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (int rc = launch_gradop_layout(d.v, d.nnz_e, count, tmp, &tmp_bytes, gop_ptr, pos_node, stream)) return rc;
     HIP_TRY(hipMemcpyAsync(n_values, gop_ptr + P, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return NIN_OK;   // (count and tmp are freed on the way out)
@@ -98,7 +96,7 @@ int nin_gls_gradop_factorize(nin_gls_gradop *op, void *stream_) {
     const int rc = for_each_adjoint_bin(d, -1, [&](int b, const AdjBinRun &run) {
         return launch_gls_gradop_factorize(d.v, b, run, op->gop_ptr, op->gop, stream);
     });
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     op->record_stamp(d);
     return NIN_OK;
 }
@@ -127,7 +125,7 @@ int nin_gls_gradop_apply(nin_gls_gradop *op, int32_t n, const double *dev_u, dou
     int rc = launch_gradop_apply(d.v, op->nnz, op->gop_ptr, op->pos_node, op->gop, n, dev_u, dev_grad, stream);
     if (!rc && dev_flux) rc = launch_corner_flux(d.v, op->nnz, n, dev_grad, dev_flux, stream);
     if (!rc && dev_node_gradient) rc = launch_node_gradient(d.v, op->nnz, n, dev_grad, dev_node_gradient, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -147,9 +145,9 @@ int nin_gls_gradop_apply_transpose(nin_gls_gradop *op, int32_t n, const double *
         if (e != hipSuccess) return fail(NIN_ENOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
         op->dots_n = want;
     }
-    if (launch_gradop_apply_transpose(d.v, op->nnz, d.tr_cell_ptr, d.tr_cell_pos, op->gop_ptr, op->pos_node, op->gop, n, dev_gbar, op->dots,
-                                      dev_ubar, stream))
-        return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (int rc = launch_gradop_apply_transpose(d.v, op->nnz, d.tr_cell_ptr, d.tr_cell_pos, op->gop_ptr, op->pos_node, op->gop, n, dev_gbar, op->dots,
+                                               dev_ubar, stream))
+        return rc;
     return NIN_OK;
 }
 

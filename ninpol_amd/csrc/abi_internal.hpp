@@ -29,9 +29,7 @@ struct nin_grid {
 #pragma GCC visibility push(hidden)   // between the library's own units: none of this is a dynamic symbol
 namespace nin {
 
-// sets what nin_last_error() returns (per thread) and hands `code` back (abi_grid.hip)
-int fail(int code, const char *fmt, ...);
-
+// (fail(code, fmt, ...), the setter of nin_last_error()'s text, is declared in launch.hpp: the launchers word their own HIP errors)
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \

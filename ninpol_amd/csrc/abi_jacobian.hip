@@ -17,7 +17,7 @@ int nin::jacobian_seed(nin_grid *g, const double *dev_u_cells, hipStream_t strea
     if (int rc = derivative_ready(g, stream, coordinates)) return rc;
     // the cotangent of F = W u + neumann_ws b: grad_csr[pos] = u[esup[pos]], grad_neumann_ws = b
     if (int rc = dev_stage(seed, nullptr, (size_t)d.nnz_e)) return rc;
-    if (int rc = launch_jac_seed(d.v, d.nnz_e, dev_u_cells, seed, stream)) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (int rc = launch_jac_seed(d.v, d.nnz_e, dev_u_cells, seed, stream)) return rc;
     return NIN_OK;
 }
 
@@ -61,7 +61,7 @@ int nin_gls_jacobian_linearize(nin_gls_jacobian *J, const double *dev_u_cells, c
     J->linearized = false;
     rc = launch_adjoint_bins(d, 1, -1, seed, dev_neumann_values, J->contrib, stream);   // always every bin
     if (!rc) rc = launch_jac_fold(d.v, J->fold, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
 }
@@ -85,7 +85,7 @@ int nin_gls_jacobian_apply(nin_gls_jacobian *J, int32_t n, const double *dev_dpe
     DeviceGrid &d = J->g->d;
     HIP_TRY(hipSetDevice(d.device));
     const int rc = launch_jac_apply(d.v, J->contrib, J->fold, n, dev_dperm, dev_ddiff_mag, dev_dnode, static_cast<hipStream_t>(stream_));
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -99,7 +99,7 @@ int nin_gls_jacobian_apply_transpose(nin_gls_jacobian *J, int32_t n, const doubl
     if (rc) return rc;
     rc = launch_jac_apply_transpose(d.v, d.tr_cell_ptr, d.tr_cell_pos, d.tr_cell_node, J->contrib, J->fold, n, dev_v, dev_grad_perm,
                                     dev_grad_diff_mag, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 

@@ -67,9 +67,9 @@ int nin::jacobian_linearize_dirty(KeptJacobian *J, const double *dev_u_cells, hi
         if (!d.all_dirty) {
             if (int rc = ensure_adjoint_dirty_state(d, P, stream)) return rc;
             const size_t ints = adj_dirty_hist_ints(P);
-            if (launch_adj_dirty_compact(P, clear, d.dirty, d.adj_node_bin, d.dirty_hdr + kDirtyHdrRejected, d.adj_dirty_hist, d.adj_dirty_hist + ints,
-                                         d.adj_dirty_tmp, d.adj_dirty_tmp_bytes, d.adj_dirty_lists, d.adj_dirty_hdr, stream))
-                return fail(NIN_EHIP, "compacting the dirty set: %s", hipGetErrorString(hipGetLastError()));
+            if (int rc = launch_adj_dirty_compact(P, clear, d.dirty, d.adj_node_bin, d.dirty_hdr + kDirtyHdrRejected, d.adj_dirty_hist, d.adj_dirty_hist + ints,
+                                                  d.adj_dirty_tmp, d.adj_dirty_tmp_bytes, d.adj_dirty_lists, d.adj_dirty_hdr, stream))
+                return rc;
             // the one synchronisation of the call: where every bin's list begins and the refused-id counter, 32 bytes
             HIP_TRY(hipMemcpyAsync(hdr, d.adj_dirty_hdr, sizeof hdr, hipMemcpyDeviceToHost, stream));
         } else {
@@ -123,7 +123,7 @@ int nin::jacobian_linearize_dirty(KeptJacobian *J, const double *dev_u_cells, hi
         rc = how.bin(b, run, J->seed);
     }
     if (!rc && how.finish) rc = how.finish();
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     laps.mark(3);
     J->record_stamp(d);
     laps.report(total);

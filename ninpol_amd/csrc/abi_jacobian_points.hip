@@ -98,7 +98,7 @@ int nin_gls_xjacobian_linearize(nin_gls_xjacobian *J, const double *dev_u_cells,
     rc = for_each_adjoint_bin(d, -1, [&](int b, const AdjBinRun &run) {
         return launch_gls_adjoint_points(d.v, b, run, 1, seed, dev_neumann_values, J->cell, J->face, J->own, stream);
     });
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
 }
@@ -138,7 +138,7 @@ int nin_gls_xjacobian_apply(nin_gls_xjacobian *J, int32_t n, const double *dev_d
     if (rc) return rc;
     rc = launch_xjac_apply(d.v, d.up_inpoel, d.up_inpofa, J->cell, J->face, J->own, n, dev_dpoints, J->tan_cell, J->tan_face, dev_dnode,
                            static_cast<hipStream_t>(stream_));
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -155,7 +155,7 @@ int nin_gls_xjacobian_apply_transpose(nin_gls_xjacobian *J, int32_t n, const dou
     if (rc) return rc;
     rc = launch_xjac_apply_transpose(d.v, d.up_inpofa, d.tr_cell_ptr, d.tr_cell_pos, d.tr_cell_node, J->cell, J->face, J->own, n, dev_v,
                                      J->tr_share, J->tr_slot, dev_grad_points, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -195,16 +195,15 @@ static int ensure_pattern(nin_gls_xjacobian *J, hipStream_t stream) {
     if (P == 0) HIP_TRY(hipMemsetAsync(count, 0, sizeof(int64_t), stream));
     int rc = launch_xjac_pattern_count(d.v, d.up_inpoel, d.up_inpofa, force_slow, count, stream);
     if (!rc) rc = xjac_pattern_scan(nullptr, &tmp_bytes, count, ptr, P, stream);
-    if (rc) return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     HIP_TRY(hipMalloc((void **)&tmp, std::max<size_t>(tmp_bytes, 1)));
-    if (xjac_pattern_scan(tmp, &tmp_bytes, count, ptr, P, stream)) return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if ((rc = xjac_pattern_scan(tmp, &tmp_bytes, count, ptr, P, stream))) return rc;
     int64_t n_blocks = 0;
     HIP_TRY(hipMemcpyAsync(&n_blocks, ptr.p + P, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     hipError_t e = hipMalloc((void **)&col, at_least_one(n_blocks) * sizeof(int32_t));
     if (e != hipSuccess) return fail(NIN_ENOMEM, "hipMalloc(%zu bytes): %s", at_least_one(n_blocks) * sizeof(int32_t), hipGetErrorString(e));
-    if (launch_xjac_pattern_fill(d.v, d.up_inpoel, d.up_inpofa, force_slow, ptr, col, stream))
-        return fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if ((rc = launch_xjac_pattern_fill(d.v, d.up_inpoel, d.up_inpofa, force_slow, ptr, col, stream))) return rc;
     J->block_ptr = ptr.p;
     J->block_col = col.p;
     ptr.p = nullptr;   // (the object's now)
@@ -243,7 +242,7 @@ int nin_gls_xjacobian_assemble(nin_gls_xjacobian *J, double *dev_values, void *s
     if (!rc) rc = ensure_pattern(J, stream);
     if (rc) return rc;
     rc = launch_xjac_assemble(d.v, d.up_inpoel, d.up_inpofa, J->cell, J->face, J->own, J->block_ptr, J->block_col, dev_values, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 

@@ -66,7 +66,7 @@ int nin_gls_rjacobian_linearize(nin_gls_rjacobian *J, const double *dev_u_cells,
     J->linearized = false;
     const AdjointReduce red{J->n_params, dev_basis, dev_basis && basis_per_cell ? (int64_t)9 * J->n_params : 0};
     rc = launch_adjoint_bins(d, 1, -1, seed, dev_neumann_values, J->R, stream, &red);   // always every bin: every entry of R is written
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     J->record_stamp(d);
     return NIN_OK;   // (the seed is freed on the way out: hipFree waits for the kernels that read it)
 }
@@ -92,7 +92,7 @@ int nin_gls_rjacobian_apply(nin_gls_rjacobian *J, int32_t n, const double *dev_d
     DeviceGrid &d = J->g->d;
     HIP_TRY(hipSetDevice(d.device));
     const int rc = launch_jacr_apply(d.v, J->n_params, J->R, n, dev_dtheta, dev_dnode, static_cast<hipStream_t>(stream_));
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 
@@ -104,7 +104,7 @@ int nin_gls_rjacobian_apply_transpose(nin_gls_rjacobian *J, int32_t n, const dou
     int rc = ensure_transpose_index(d, stream);   // (every time: nin_grid_release_scratch may have dropped it)
     if (rc) return rc;
     rc = launch_jacr_apply_transpose(d.v, J->n_params, d.tr_cell_ptr, d.tr_cell_pos, d.tr_cell_node, J->R, n, dev_v, dev_grad_theta, stream);
-    if (rc) return fail(rc, "launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     return NIN_OK;
 }
 

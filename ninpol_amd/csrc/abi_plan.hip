@@ -100,7 +100,7 @@ int locality_order(const DeviceGrid &d, int32_t *list, int32_t count, const int3
         const char *mode = getenv("NIN_GLS_LOCALITY_ORDER");
         const int32_t strip = !mode ? 16 : mode[0] == 's' ? (mode[1] ? atoi(mode + 1) : 16) : 0;   // default: strips of 16 rows; "m": Morton
         const double levels = std::cbrt((double)d.v.n_points) - 1.0;                          // mesh intervals per axis of a cube of this many nodes
-        hipLaunchKernelGGL(k_locality_keys, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, d.v.coords, list, count, lo,
+        hipLaunchKernelGGL(k_locality_keys, blocks_for(count), dim3(256), 0, nullptr, d.v.coords, list, count, lo,
                            1024.0 / (hi - lo), chunk_node[1], chunk_node[2], chunk_node[3], strip, (levels > 1.0 ? levels : 1.0) / (hi - lo), keys.p);
         if (step(hipGetLastError()) && step(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys_out.p, list, list_out.p, count)) &&
             step(hipMalloc(&tmp, tmp_bytes)) &&
@@ -147,7 +147,7 @@ int launch_plan_kernel(const DeviceGrid &d, GlsKernel k, const int32_t *nodes, c
         case GlsFamily::mfx: return launch_gls_mfx(d.v, nodes, desc, count, r.sub, add_neumann, out, nws, queue, stream);
         case GlsFamily::mfg: return launch_gls_mfg(d.v, nodes, desc, count, add_neumann, out, nws, queue, d.mfg_tiles, d.mfg_slots, stream);
     }
-    return NIN_EINVAL;
+    return fail(NIN_EINVAL, "the GLS launch plan has no kernel family %d", (int)r.family);
 }
 
 }  // namespace
@@ -282,23 +282,26 @@ int nin::gls_side_begin(DeviceGrid &d, int piece, int add_neumann, double *out, 
     bool any = false;
     for (GlsKernel k : kSideOrder) any = any || plan_range(d, k, piece).count > 0;
     if (!any || getenv("NIN_GLS_NO_SIDE_STREAM") != nullptr) return 0;
-    if (lazy_stream(d.side_stream) || lazy_event(d.ev_fork) || lazy_event(d.ev_join)) return -3;
+    int rc = lazy_stream(d.side_stream);
+    if (!rc) rc = lazy_event(d.ev_fork);
+    if (!rc) rc = lazy_event(d.ev_join);
+    if (rc) return rc;
     hipStream_t side = static_cast<hipStream_t>(d.side_stream);
-    if (hipEventRecord(static_cast<hipEvent_t>(d.ev_fork), stream) != hipSuccess || hipStreamWaitEvent(side, static_cast<hipEvent_t>(d.ev_fork), 0) != hipSuccess)
-        return -3;
-    int rc = 0;
+    HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(d.ev_fork), stream));
+    HIP_TRY(hipStreamWaitEvent(side, static_cast<hipEvent_t>(d.ev_fork), 0));
     for (GlsKernel k : kSideOrder) {
         const PlanRange r = plan_range(d, k, piece);
         if (!rc && r.count > 0) rc = launch_plan_kernel(d, k, r.nodes, r.desc, r.count, add_neumann, out, nws, side);
     }
-    if (!rc && hipEventRecord(static_cast<hipEvent_t>(d.ev_join), side) != hipSuccess) rc = -3;
+    if (!rc) rc = launch_status(hipEventRecord(static_cast<hipEvent_t>(d.ev_join), side));
     d.side_pending = rc == 0;
     return rc;
 }
 static int gls_side_end(DeviceGrid &d, hipStream_t stream) {
     if (!d.side_pending) return 0;
     d.side_pending = false;
-    return hipStreamWaitEvent(stream, static_cast<hipEvent_t>(d.ev_join), 0) == hipSuccess ? 0 : -3;
+    HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(d.ev_join), 0));
+    return NIN_OK;
 }
 
 // NIN_GLS_ONLY=<k>: launch only kernel k of the plan (a GlsKernel: numbered as nin_gls_plan counts them; measurement: bench.py times
@@ -346,7 +349,7 @@ int nin::launch_lists(DeviceGrid &d, int method, const int32_t *lists, const int
         for (GlsKernel k : kMainOrder)
             if (!rc && off[k + 1] > off[k])
                 rc = launch_plan_kernel(d, k, lists + off[k], desc + desc_first[k], off[k + 1] - off[k], add_neumann, out, nws, stream);
-    if (rc) return fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     if (laps) laps->mark(3);
     return NIN_OK;
 }
@@ -372,7 +375,7 @@ int nin_weights_device(nin_grid *g, int method, const int64_t *targets, int64_t 
             if (only < 0) rc = gls_side_begin(d, -1, add_neumann, dev_csr_data, dev_neumann_ws, stream);
             if (!rc) rc = gls_main(d, -1, true, only, add_neumann, dev_csr_data, dev_neumann_ws, stream);
         }
-        if (rc) return fail(rc, "kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (rc) return rc;
         return NIN_OK;
     }
     // explicit target list: outputs of every other node are zero

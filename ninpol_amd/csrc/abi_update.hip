@@ -110,12 +110,12 @@ int update_points_on_device(nin_grid *g, const double *xyz, bool on_host, int cd
             HIP_TRY(hipMalloc((void **)&staged, P * cd * sizeof(double)));
             if (hipMemcpy(staged, xyz, P * cd * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail(NIN_EHIP, "uploading the coordinates failed");
         }
-        if (!rc && launch_update_coords(on_host ? staged.p : xyz, cd, (int64_t)P, coords, stream)) rc = fail(NIN_EHIP, "coordinate copy: %s", hipGetErrorString(hipGetLastError()));
+        if (!rc) rc = launch_update_coords(on_host ? staged.p : xyz, cd, (int64_t)P, coords, stream);
     }
     const uint64_t npoel8 = pack_npoel8(h);
-    if (!rc && launch_update_geometry(d.v, npoel8, d.up_inpoel, d.up_etype, d.up_inpofa, const_cast<double *>(d.v.centroids),
-                                      const_cast<double *>(d.v.face_center), const_cast<float *>(d.v.face_normal), d.up_areas, stream))
-        rc = fail(NIN_EHIP, "geometry kernels: %s", hipGetErrorString(hipGetLastError()));
+    if (!rc)
+        rc = launch_update_geometry(d.v, npoel8, d.up_inpoel, d.up_etype, d.up_inpofa, const_cast<double *>(d.v.centroids),
+                                    const_cast<double *>(d.v.face_center), const_cast<float *>(d.v.face_normal), d.up_areas, stream);
     if (!rc && d.v.centroids4 && launch_pad_centroids(d.v.centroids, h.n_elems, const_cast<double *>(d.v.centroids4), stream))
         rc = fail(NIN_EHIP, "centroid padding kernel");
     rc = finish_geometry_update(g, rc, on_host, stream, "geometry update");
@@ -204,7 +204,7 @@ int nin_fields_scatter_permeability_device(nin_grid *g, const void *dev_cell_ids
     if (rc) return rc;
     rc = launch_scatter_permeability(d.v, pack_npoel8(g->h), d.up_inpoel, d.up_etype, dev_cell_ids, ids_are_int64, n, dev_permeability, dev_scale,
                                      d.dirty, d.dirty_hdr + kDirtyHdrRejected, static_cast<hipStream_t>(stream));
-    if (rc) return fail(rc, "scatter kernel: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     d.scattered_cells = true;
     ++d.field_updates;
     return NIN_OK;
@@ -221,7 +221,7 @@ int nin_fields_set_flags_device(nin_grid *g, const void *dev_flags, int flags_ar
     // while everything is dirty no marks are needed; afterwards only the nodes whose byte changes are marked
     rc = launch_set_flags(d.v.n_points, dev_flags, flags_are_bytes, const_cast<uint8_t *>(d.v.flags), d.all_dirty ? nullptr : d.dirty,
                           static_cast<hipStream_t>(stream));
-    if (rc) return fail(rc, "flag kernel: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     d.fields_set = true;
     d.flags_host_stale = true;
     ++d.flag_updates;
@@ -242,7 +242,7 @@ int nin_fields_scatter_flags_device(nin_grid *g, const void *dev_node_ids, int i
     if (rc) return rc;
     rc = launch_scatter_flags(d.v.n_points, dev_node_ids, ids_are_int64, n, dev_flags, flags_are_bytes, const_cast<uint8_t *>(d.v.flags),
                               d.all_dirty ? nullptr : d.dirty, d.dirty_hdr + kDirtyHdrRejected, static_cast<hipStream_t>(stream));
-    if (rc) return fail(rc, "flag scatter kernel: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     d.scattered_flags = true;
     d.flags_host_stale = true;
     ++d.flag_updates;
@@ -308,9 +308,8 @@ static int scatter_points_on_device(nin_grid *g, const void *ids, int ids_are_in
         if (rc) return rc;   // nothing was launched: the geometry is as it was
         ids = staged_ids; xyz = staged_xyz;
     }
-    if (launch_scatter_points(d.v, pack_npoel8(h), d.up_inpoel, d.up_etype, d.up_inpofa, ids, ids_are_int64, n, xyz, cd, d.up_areas, d.dirty,
-                              d.dirty_hdr + kDirtyHdrRejected, stream))
-        rc = fail(NIN_EHIP, "local geometry kernels: %s", hipGetErrorString(hipGetLastError()));
+    rc = launch_scatter_points(d.v, pack_npoel8(h), d.up_inpoel, d.up_etype, d.up_inpofa, ids, ids_are_int64, n, xyz, cd, d.up_areas, d.dirty,
+                               d.dirty_hdr + kDirtyHdrRejected, stream);
     d.scattered_nodes = true;
     return finish_geometry_update(g, rc, on_host, stream, "local geometry update");   // all_dirty stays as it is: the kernels marked the rows that can move
 }
@@ -365,7 +364,7 @@ int nin_grid_mark_dirty_device(nin_grid *g, const void *dev_ids, int ids_are_int
     if (rc) return rc;
     rc = launch_mark_dirty(d.v, pack_npoel8(g->h), d.up_inpoel, d.up_etype, dev_ids, ids_are_int64, n, ids_are_cells, d.dirty,
                            d.dirty_hdr + kDirtyHdrRejected, static_cast<hipStream_t>(stream));
-    if (rc) return fail(rc, "mark kernel: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) return rc;
     d.scattered_marks = true;
     return NIN_OK;
 }
@@ -420,9 +419,9 @@ int nin_weights_dirty_device(nin_grid *g, int method, int add_neumann, double *d
             if (!d.dirty_hist && (rc = dev_alloc(d, &d.dirty_hist, ints))) return rc;
             if (!d.dirty_lists && (rc = dev_alloc(d, &d.dirty_lists, (size_t)P))) return rc;
             if ((rc = grow(d, reinterpret_cast<char **>(&d.dirty_tmp), &d.dirty_tmp_bytes, std::max<size_t>(tmp_bytes, 16)))) return rc;
-            if (launch_dirty_compact(P, gls ? 0 : 1, clear, d.dirty, d.node_class, d.dirty_hdr + kDirtyHdrRejected, d.dirty_hist,
-                                     d.dirty_hist + ints / 2, d.dirty_tmp, d.dirty_tmp_bytes, d.dirty_lists, d.dirty_hdr, stream))
-                return fail(NIN_EHIP, "compacting the dirty set: %s", hipGetErrorString(hipGetLastError()));
+            if ((rc = launch_dirty_compact(P, gls ? 0 : 1, clear, d.dirty, d.node_class, d.dirty_hdr + kDirtyHdrRejected, d.dirty_hist,
+                                           d.dirty_hist + ints / 2, d.dirty_tmp, d.dirty_tmp_bytes, d.dirty_lists, d.dirty_hdr, stream)))
+                return rc;
         }
         // the one synchronisation of the call: the lists' offsets and the refused-id counter, 128 bytes
         HIP_TRY(hipMemcpyAsync(hdr, d.dirty_hdr, sizeof hdr, hipMemcpyDeviceToHost, stream));
@@ -463,14 +462,15 @@ int64_t nin_grid_dirty_nodes(nin_grid *g) {
     if (d.all_dirty) return -1;
     if (!d.dirty) return 0;
     int32_t n = 0;
-    if (hipSetDevice(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||   // a scatter may be in flight on any stream
-        hipMemset(d.dirty_hdr + kDirtyHdrCount, 0, sizeof(int32_t)) != hipSuccess ||
-        launch_dirty_count((int32_t)g->h.n_points, d.dirty, d.dirty_hdr + kDirtyHdrCount, nullptr) ||
-        hipMemcpy(&n, d.dirty_hdr + kDirtyHdrCount, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) {
-        (void)fail(NIN_EHIP, "counting the dirty nodes: %s", hipGetErrorString(hipGetLastError()));
-        return -2;
-    }
-    return n;
+    const int rc = [&]() -> int {
+        HIP_TRY(hipSetDevice(d.device));
+        HIP_TRY(hipDeviceSynchronize());   // a scatter may be in flight on any stream
+        HIP_TRY(hipMemset(d.dirty_hdr + kDirtyHdrCount, 0, sizeof(int32_t)));
+        if (int rc = launch_dirty_count((int32_t)g->h.n_points, d.dirty, d.dirty_hdr + kDirtyHdrCount, nullptr)) return rc;
+        HIP_TRY(hipMemcpy(&n, d.dirty_hdr + kDirtyHdrCount, sizeof n, hipMemcpyDeviceToHost));
+        return NIN_OK;
+    }();
+    return rc ? -2 : n;
 }
 
 int nin_grid_dirty_reset(nin_grid *g, int all_dirty, void *stream) {

@@ -97,7 +97,7 @@ int launch_dirty_row_nnz(const GridView &g, const double *data, const int32_t *l
     if (total <= 0) return 0;
     hipLaunchKernelGGL(nin_dirty_row_nnz_kernel, dim3(grid_for_rows(total)), dim3(256), 0, stream, g.esup_ptr, data, list, total, pack_cnt, cnt,
                        changed);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_dirty_pack(const GridView &g, const double *data, const double *nws, const int32_t *list, int32_t total, const int32_t *pack_off,
@@ -105,7 +105,7 @@ int launch_dirty_pack(const GridView &g, const double *data, const double *nws, 
     if (total <= 0) return 0;
     hipLaunchKernelGGL(nin_dirty_pack_kernel, dim3(grid_for_rows(total)), dim3(256), 0, stream, g.esup_ptr, g.esup, data, nws, list, total,
                        pack_off, pack_node, pack_nws, pack_indices, pack_data);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

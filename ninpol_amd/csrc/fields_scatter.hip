@@ -39,7 +39,6 @@ constexpr int WAVES = TPB / 64;
 constexpr int NK = kGlsPlanKernels;
 static_assert(TPB == 256, "the compaction fills its class-byte table with one thread per byte value");
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 template <bool SCALED, class Id>
 __global__ __launch_bounds__(TPB) void nin_scatter_perm_kernel(int64_t m, const Id *__restrict__ ids, const double *__restrict__ K,
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(TPB) void nin_dirty_count_kernel(int32_t P, const u
 template <bool SCALED, class Id>
 void scatter_variant(int64_t n, const void *ids, const double *K, const double *scale, const GridView &g, uint64_t npoel8, const int32_t *inpoel,
                      const int8_t *etype, uint8_t *dirty, int32_t *rejected, hipStream_t stream) {
-    hipLaunchKernelGGL((nin_scatter_perm_kernel<SCALED, Id>), dim3(blocks_for(n)), dim3(TPB), 0, stream, n, static_cast<const Id *>(ids), K, scale,
+    hipLaunchKernelGGL((nin_scatter_perm_kernel<SCALED, Id>), blocks_for(n), dim3(TPB), 0, stream, n, static_cast<const Id *>(ids), K, scale,
                        g.n_elems, g.n_points, npoel8, reinterpret_cast<const int4 *>(inpoel), etype, const_cast<double *>(g.perm),
                        const_cast<double *>(g.diff_mag), dirty, rejected);
 }
@@ -138,7 +137,7 @@ int launch_scatter_permeability(const GridView &g, uint64_t npoel8, const int32_
                                 int ids_are_int64, int64_t n, const double *dev_K, const double *dev_scale, uint8_t *dirty, int32_t *rejected,
                                 hipStream_t stream) {
     if (n <= 0) return 0;
-    if (n > (int64_t)INT32_MAX * TPB) return -5;
+    if (n > (int64_t)INT32_MAX * TPB) return fail(NIN_ERANGE, "%lld ids are more than one launch takes", (long long)n);
     if (dev_scale) {
         if (ids_are_int64) scatter_variant<true, int64_t>(n, dev_ids, dev_K, dev_scale, g, npoel8, inpoel, etype, dirty, rejected, stream);
         else scatter_variant<true, int32_t>(n, dev_ids, dev_K, dev_scale, g, npoel8, inpoel, etype, dirty, rejected, stream);
@@ -146,34 +145,34 @@ int launch_scatter_permeability(const GridView &g, uint64_t npoel8, const int32_
         if (ids_are_int64) scatter_variant<false, int64_t>(n, dev_ids, dev_K, dev_scale, g, npoel8, inpoel, etype, dirty, rejected, stream);
         else scatter_variant<false, int32_t>(n, dev_ids, dev_K, dev_scale, g, npoel8, inpoel, etype, dirty, rejected, stream);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
-size_t dirty_compact_hist_ints(int32_t n_points) { return (size_t)NK * blocks_for(n_points) + 1; }
+size_t dirty_compact_hist_ints(int32_t n_points) { return (size_t)NK * blocks_for(n_points).x + 1; }
 
 int dirty_compact_tmp_bytes(int32_t n_points, size_t *bytes) {
     *bytes = 0;
     int32_t *none = nullptr;
-    return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, none, none, (int)dirty_compact_hist_ints(n_points), nullptr) == hipSuccess ? 0 : -3;
+    return launch_status(hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, none, none, (int)dirty_compact_hist_ints(n_points), nullptr));
 }
 
 int launch_dirty_compact(int32_t n_points, int single, int clear, uint8_t *dirty, const uint8_t *node_class, const int32_t *rejected,
                          int32_t *hist, int32_t *scanned, void *tmp, size_t tmp_bytes, int32_t *lists, int32_t *hdr, hipStream_t stream) {
     if (n_points <= 0) return 0;
-    const int32_t nblocks = (int32_t)blocks_for(n_points);
+    const int32_t nblocks = (int32_t)blocks_for(n_points).x;
     hipLaunchKernelGGL((nin_dirty_compact_kernel<false>), dim3(nblocks), dim3(TPB), 0, stream, n_points, nblocks, single, 0, dirty, node_class, rejected,
                        hist, lists, hdr);
-    if (hipGetLastError() != hipSuccess) return -3;
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, hist, scanned, (int)dirty_compact_hist_ints(n_points), stream) != hipSuccess) return -3;
+    if (int rc = launch_status()) return rc;
+    if (int rc = launch_status(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, hist, scanned, (int)dirty_compact_hist_ints(n_points), stream))) return rc;
     hipLaunchKernelGGL((nin_dirty_compact_kernel<true>), dim3(nblocks), dim3(TPB), 0, stream, n_points, nblocks, single, clear, dirty, node_class, rejected,
                        scanned, lists, hdr);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_dirty_count(int32_t n_points, const uint8_t *dirty, int32_t *out, hipStream_t stream) {
     if (n_points <= 0) return 0;
-    hipLaunchKernelGGL(nin_dirty_count_kernel, dim3(blocks_for(n_points)), dim3(TPB), 0, stream, n_points, dirty, out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_dirty_count_kernel, blocks_for(n_points), dim3(TPB), 0, stream, n_points, dirty, out);
+    return launch_status();
 }
 
 }  // namespace nin

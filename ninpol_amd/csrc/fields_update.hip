@@ -87,11 +87,10 @@ __global__ __launch_bounds__(TPB) void nin_update_perm_kernel(int32_t E, const d
     if (t < valid) diff_mag[e0 + t] = diff_mag_of(s[9 * t], s[9 * t + 4], s[9 * t + 8]);
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 template <bool SCALED, bool ALIGNED16>
 void launch_variant(int32_t E, const double *K, const double *scale, double *perm, double *diff_mag, hipStream_t stream) {
-    hipLaunchKernelGGL((nin_update_perm_kernel<SCALED, ALIGNED16>), dim3(blocks_for(E)), dim3(TPB), 0, stream, E, K, scale, perm, diff_mag);
+    hipLaunchKernelGGL((nin_update_perm_kernel<SCALED, ALIGNED16>), blocks_for(E), dim3(TPB), 0, stream, E, K, scale, perm, diff_mag);
 }
 
 }  // namespace

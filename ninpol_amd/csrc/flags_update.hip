@@ -113,7 +113,7 @@ void set_variant(int64_t P, const void *src, uint8_t *flags, uint8_t *dirty, hip
 template <class Id, class Src>
 void scatter_variant(int64_t n, const void *ids, const void *src, int32_t P, uint8_t *flags, uint8_t *dirty, int32_t *rejected,
                      hipStream_t stream) {
-    hipLaunchKernelGGL((nin_flags_scatter_kernel<Id, Src>), dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, stream, n,
+    hipLaunchKernelGGL((nin_flags_scatter_kernel<Id, Src>), blocks_for(n, TPB), dim3(TPB), 0, stream, n,
                        static_cast<const Id *>(ids), static_cast<const Src *>(src), P, flags, dirty, rejected);
 }
 
@@ -123,13 +123,13 @@ int launch_set_flags(int32_t n_points, const void *dev_flags, int flags_are_byte
     if (n_points <= 0) return 0;
     if (flags_are_bytes) set_variant<uint8_t>(n_points, dev_flags, flags, dirty, stream);
     else set_variant<double>(n_points, dev_flags, flags, dirty, stream);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_scatter_flags(int32_t n_points, const void *dev_ids, int ids_are_int64, int64_t n, const void *dev_flags, int flags_are_bytes,
                          uint8_t *flags, uint8_t *dirty, int32_t *rejected, hipStream_t stream) {
     if (n <= 0) return 0;
-    if (n > (int64_t)INT32_MAX * TPB) return -5;
+    if (n > (int64_t)INT32_MAX * TPB) return fail(NIN_ERANGE, "%lld ids are more than one launch takes", (long long)n);
     if (ids_are_int64) {
         if (flags_are_bytes) scatter_variant<int64_t, uint8_t>(n, dev_ids, dev_flags, n_points, flags, dirty, rejected, stream);
         else scatter_variant<int64_t, double>(n, dev_ids, dev_flags, n_points, flags, dirty, rejected, stream);
@@ -137,7 +137,7 @@ int launch_scatter_flags(int32_t n_points, const void *dev_ids, int ids_are_int6
         if (flags_are_bytes) scatter_variant<int32_t, uint8_t>(n, dev_ids, dev_flags, n_points, flags, dirty, rejected, stream);
         else scatter_variant<int32_t, double>(n, dev_ids, dev_flags, n_points, flags, dirty, rejected, stream);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

@@ -45,7 +45,6 @@ struct Topo {   // the element tables (utils/point_ordering.yaml via the Grid ct
 };
 
 constexpr int TPB = 256;
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 __global__ void k_ingest_elems(int64_t E, int64_t P, Topo t, const int64_t *__restrict__ conn,
                                const int64_t *__restrict__ types, int32_t *__restrict__ inpoel,
@@ -308,7 +307,7 @@ struct Scope {   // temporaries of the build, freed on every exit path
 #define GB_TRY(expr)                                                                      \
     do {                                                                                  \
         hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(e_); return -3; } \
+        if (e_ != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(e_); return NIN_EHIP; } \
     } while (0)
 
 template <class T>
@@ -452,8 +451,8 @@ int build_grid_on_device(HostGrid &h, DeviceGrid &d, int device, const int64_t *
         GB_TRY(hipMemcpy(conn, connectivity, (size_t)E * 64, hipMemcpyHostToDevice));
         GB_TRY(hipMemcpy(types, element_types, (size_t)E * 8, hipMemcpyHostToDevice));
         GB_TRY(hipMemcpy(x, xyz, (size_t)P * coords_dim * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_ingest_elems, dim3(blocks_for(E)), dim3(TPB), 0, 0, E, P, t, conn, types, inpoel, etype, scal);
-        hipLaunchKernelGGL(k_ingest_coords, dim3(blocks_for(P)), dim3(TPB), 0, 0, P, coords_dim, x, coords);
+        hipLaunchKernelGGL(k_ingest_elems, blocks_for(E), dim3(TPB), 0, 0, E, P, t, conn, types, inpoel, etype, scal);
+        hipLaunchKernelGGL(k_ingest_coords, blocks_for(P), dim3(TPB), 0, 0, P, coords_dim, x, coords);
         int32_t hs[4];
         GB_TRY(hipMemcpy(hs, scal, 16, hipMemcpyDeviceToHost));
         if (hs[0]) return -1;
@@ -465,14 +464,14 @@ int build_grid_on_device(HostGrid &h, DeviceGrid &d, int device, const int64_t *
     int32_t *cnt = nullptr, *esup_ptr = nullptr, *esup = nullptr;
     if ((rc = tmp_alloc(s, &cnt, (size_t)P + 1, err)) || (rc = keep_alloc(d, &esup_ptr, (size_t)P + 1, err))) return rc;
     GB_TRY(hipMemset(cnt, 0, ((size_t)P + 1) * 4));
-    hipLaunchKernelGGL(k_esup_count, dim3(blocks_for(E)), dim3(TPB), 0, 0, E, t, inpoel, etype, cnt);
+    hipLaunchKernelGGL(k_esup_count, blocks_for(E), dim3(TPB), 0, 0, E, t, inpoel, etype, cnt);
     if ((rc = scan_exclusive(s, cnt, esup_ptr, P + 1, err))) return rc;
     int32_t nnz_e = 0;
     GB_TRY(hipMemcpy(&nnz_e, esup_ptr + P, 4, hipMemcpyDeviceToHost));
     if ((rc = keep_alloc(d, &esup, (size_t)nnz_e, err))) return rc;
     GB_TRY(hipMemset(cnt, 0, ((size_t)P + 1) * 4));
-    hipLaunchKernelGGL(k_esup_fill, dim3(blocks_for(E)), dim3(TPB), 0, 0, E, t, inpoel, etype, esup_ptr, cnt, esup);
-    hipLaunchKernelGGL(k_sort_rows, dim3(blocks_for(P)), dim3(TPB), 0, 0, P, esup_ptr, esup, scal + 1);
+    hipLaunchKernelGGL(k_esup_fill, blocks_for(E), dim3(TPB), 0, 0, E, t, inpoel, etype, esup_ptr, cnt, esup);
+    hipLaunchKernelGGL(k_sort_rows, blocks_for(P), dim3(TPB), 0, 0, P, esup_ptr, esup, scal + 1);
     v.esup_ptr = esup_ptr; v.esup = esup;
     d.nnz_e = nnz_e;
     lap("esup");
@@ -480,7 +479,7 @@ int build_grid_on_device(HostGrid &h, DeviceGrid &d, int device, const int64_t *
     // ---- esuel -----------------------------------------------------------------------------------------------
     int32_t *esuel = nullptr;
     if ((rc = tmp_alloc(s, &esuel, (size_t)E * 6, err))) return rc;
-    hipLaunchKernelGGL(k_esuel, dim3(blocks_for(E * 6)), dim3(TPB), 0, 0, E, t, inpoel, etype, esup_ptr, esup, esuel);
+    hipLaunchKernelGGL(k_esuel, blocks_for(E * 6), dim3(TPB), 0, 0, E, t, inpoel, etype, esup_ptr, esup, esuel);
     lap("esuel");
 
     // ---- faces: numbering, inpofa, owner pairs -----------------------------------------------------------
@@ -489,15 +488,15 @@ int build_grid_on_device(HostGrid &h, DeviceGrid &d, int device, const int64_t *
         (rc = tmp_alloc(s, &infael, (size_t)E * 6, err)))
         return rc;
     GB_TRY(hipMemset(own_cnt, 0, ((size_t)E + 1) * 4));
-    hipLaunchKernelGGL(k_own_count, dim3(blocks_for(E)), dim3(TPB), 0, 0, E, t, etype, esuel, own_cnt);
+    hipLaunchKernelGGL(k_own_count, blocks_for(E), dim3(TPB), 0, 0, E, t, etype, esuel, own_cnt);
     if ((rc = scan_exclusive(s, own_cnt, own_start, E + 1, err))) return rc;
     int32_t F32 = 0;
     GB_TRY(hipMemcpy(&F32, own_start + E, 4, hipMemcpyDeviceToHost));
     const int64_t F = F32;
     if (F * 4 >= INT32_MAX) return -5;
     if ((rc = tmp_alloc(s, &inpofa, (size_t)F * 4, err)) || (rc = keep_alloc(d, &face_cells, (size_t)F * 2, err))) return rc;
-    hipLaunchKernelGGL(k_faces_fill, dim3(blocks_for(E)), dim3(TPB), 0, 0, E, t, inpoel, etype, esuel, own_start, infael, inpofa, face_cells);
-    hipLaunchKernelGGL(k_faces_mirror, dim3(blocks_for(E * 6)), dim3(TPB), 0, 0, E, t, etype, esuel, infael);
+    hipLaunchKernelGGL(k_faces_fill, blocks_for(E), dim3(TPB), 0, 0, E, t, inpoel, etype, esuel, own_start, infael, inpofa, face_cells);
+    hipLaunchKernelGGL(k_faces_mirror, blocks_for(E * 6), dim3(TPB), 0, 0, E, t, etype, esuel, infael);
     v.n_faces = (int32_t)F; v.face_cells = face_cells;
     h.n_faces = F;
     lap("infael");
@@ -506,13 +505,13 @@ int build_grid_on_device(HostGrid &h, DeviceGrid &d, int device, const int64_t *
     int32_t *fsup_ptr = nullptr, *fsup = nullptr;
     if ((rc = keep_alloc(d, &fsup_ptr, (size_t)P + 1, err))) return rc;
     GB_TRY(hipMemset(cnt, 0, ((size_t)P + 1) * 4));
-    hipLaunchKernelGGL((k_fsup<false>), dim3(blocks_for(P)), dim3(TPB), 0, 0, P, t, inpoel, etype, esup_ptr, esup, esuel, infael, cnt,
+    hipLaunchKernelGGL((k_fsup<false>), blocks_for(P), dim3(TPB), 0, 0, P, t, inpoel, etype, esup_ptr, esup, esuel, infael, cnt,
                        (const int32_t *)nullptr, (int32_t *)nullptr, scal + 2);
     if ((rc = scan_exclusive(s, cnt, fsup_ptr, P + 1, err))) return rc;
     int32_t nnz_f = 0;
     GB_TRY(hipMemcpy(&nnz_f, fsup_ptr + P, 4, hipMemcpyDeviceToHost));
     if ((rc = keep_alloc(d, &fsup, (size_t)nnz_f, err))) return rc;
-    hipLaunchKernelGGL((k_fsup<true>), dim3(blocks_for(P)), dim3(TPB), 0, 0, P, t, inpoel, etype, esup_ptr, esup, esuel, infael, cnt,
+    hipLaunchKernelGGL((k_fsup<true>), blocks_for(P), dim3(TPB), 0, 0, P, t, inpoel, etype, esup_ptr, esup, esuel, infael, cnt,
                        fsup_ptr, fsup, scal + 2);
     v.fsup_ptr = fsup_ptr; v.fsup = fsup;
     d.nnz_f = nnz_f;
@@ -522,7 +521,7 @@ int build_grid_on_device(HostGrid &h, DeviceGrid &d, int device, const int64_t *
     uint8_t *bfaces = nullptr, *bpoints = nullptr;
     if ((rc = tmp_alloc(s, &bfaces, (size_t)F, err)) || (rc = tmp_alloc(s, &bpoints, (size_t)P, err))) return rc;
     GB_TRY(hipMemset(bpoints, 0, (size_t)P));
-    hipLaunchKernelGGL(k_boundary, dim3(blocks_for(F)), dim3(TPB), 0, 0, F, face_cells, inpofa, bfaces, bpoints, scal + 3);
+    hipLaunchKernelGGL(k_boundary, blocks_for(F), dim3(TPB), 0, 0, F, face_cells, inpofa, bfaces, bpoints, scal + 3);
     lap("esuf");
 
     // ---- geometry ----------------------------------------------------------------------------------------
@@ -530,8 +529,8 @@ int build_grid_on_device(HostGrid &h, DeviceGrid &d, int device, const int64_t *
     if ((rc = keep_alloc(d, &cen, (size_t)E * 3, err)) || (rc = keep_alloc(d, &fc, (size_t)F * 3, err)) ||
         (rc = keep_alloc(d, &fn, (size_t)F * 3, err)) || (rc = tmp_alloc(s, &fa, (size_t)F, err)))
         return rc;
-    hipLaunchKernelGGL(k_centroids, dim3(blocks_for(E)), dim3(TPB), 0, 0, E, (int)h.dim, t, inpoel, etype, coords, cen);
-    hipLaunchKernelGGL(k_faces_geometry, dim3(blocks_for(F)), dim3(TPB), 0, 0, F, (int)h.dim, inpofa, coords, fc, fn, fa);
+    hipLaunchKernelGGL(k_centroids, blocks_for(E), dim3(TPB), 0, 0, E, (int)h.dim, t, inpoel, etype, coords, cen);
+    hipLaunchKernelGGL(k_faces_geometry, blocks_for(F), dim3(TPB), 0, 0, F, (int)h.dim, inpofa, coords, fc, fn, fa);
     v.centroids = cen; v.face_center = fc; v.face_normal = fn;
     GB_TRY(hipDeviceSynchronize());
     lap("geometry");
@@ -638,9 +637,9 @@ __global__ void k_classify(GridView g, int use_group, int force_global, uint8_t 
 
 int launch_classify(const GridView &g, int use_group, int force_global, uint8_t *node_class,
                     unsigned long long *class_max, hipStream_t stream) {
-    hipLaunchKernelGGL(k_classify, dim3(blocks_for(g.n_points)), dim3(TPB), 0, stream, g, use_group, force_global, node_class,
+    hipLaunchKernelGGL(k_classify, blocks_for(g.n_points), dim3(TPB), 0, stream, g, use_group, force_global, node_class,
                        class_max);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

@@ -106,10 +106,10 @@ template <class Id>
 int scatter_variant(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const int32_t *inpofa, const void *ids_,
                     int64_t n, const double *xyz, int cd, double *fa, uint8_t *dirty, int32_t *rejected, hipStream_t stream) {
     const Id *ids = static_cast<const Id *>(ids_);
-    hipLaunchKernelGGL((nin_scatter_points_kernel<Id>), dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, stream, n, ids, xyz, cd, g.n_points,
+    hipLaunchKernelGGL((nin_scatter_points_kernel<Id>), blocks_for(n, TPB), dim3(TPB), 0, stream, n, ids, xyz, cd, g.n_points,
                        const_cast<double *>(g.coords), rejected);
-    if (hipGetLastError() != hipSuccess) return -3;
-    const dim3 grid((unsigned)((n + ENTRIES - 1) / ENTRIES));
+    if (int rc = launch_status()) return rc;
+    const dim3 grid = blocks_for(n, ENTRIES);
     const int4 *poel = reinterpret_cast<const int4 *>(inpoel), *pofa = reinterpret_cast<const int4 *>(inpofa);
     double *cen = const_cast<double *>(g.centroids), *cen4 = const_cast<double *>(g.centroids4), *fc = const_cast<double *>(g.face_center);
     float *fn = const_cast<float *>(g.face_normal);
@@ -119,7 +119,7 @@ int scatter_variant(const GridView &g, uint64_t npoel8, const int32_t *inpoel, c
     else
         hipLaunchKernelGGL((nin_regeom_around_kernel<Id, false>), grid, dim3(TPB), 0, stream, n, ids, g, npoel8, poel, etype, pofa, cen, cen4, fc, fn,
                            fa, dirty);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace
@@ -128,8 +128,8 @@ int launch_scatter_points(const GridView &g, uint64_t npoel8, const int32_t *inp
                           const void *dev_ids, int ids_are_int64, int64_t n, const double *dev_xyz, int coords_dim, double *face_area,
                           uint8_t *dirty, int32_t *rejected, hipStream_t stream) {
     if (n <= 0) return 0;
-    if (coords_dim < 1 || coords_dim > 3) return -5;
-    if (n > (int64_t)INT32_MAX * ENTRIES) return -5;
+    if (coords_dim < 1 || coords_dim > 3) return fail(NIN_ERANGE, "coords_dim is %d, not 1, 2 or 3", coords_dim);
+    if (n > (int64_t)INT32_MAX * ENTRIES) return fail(NIN_ERANGE, "%lld ids are more than one launch takes", (long long)n);
     return ids_are_int64
                ? scatter_variant<int64_t>(g, npoel8, inpoel, etype, inpofa, dev_ids, n, dev_xyz, coords_dim, face_area, dirty, rejected, stream)
                : scatter_variant<int32_t>(g, npoel8, inpoel, etype, inpofa, dev_ids, n, dev_xyz, coords_dim, face_area, dirty, rejected, stream);

@@ -95,32 +95,31 @@ __global__ __launch_bounds__(TPB) void nin_update_faces_kernel(int32_t F, int d,
     store_records_f32(sn, fn + (int64_t)f0 * 3, valid);
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 }  // namespace
 
 int launch_update_coords(const double *dev_xyz, int coords_dim, int64_t n_points, double *coords, hipStream_t stream) {
     if (n_points <= 0) return 0;
     if (coords_dim == 3)
-        return hipMemcpyAsync(coords, dev_xyz, (size_t)n_points * 24, hipMemcpyDeviceToDevice, stream) == hipSuccess ? 0 : -3;
-    hipLaunchKernelGGL(nin_update_pad_coords_kernel, dim3(blocks_for(n_points)), dim3(TPB), 0, stream, n_points, coords_dim, dev_xyz, coords);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+        return launch_status(hipMemcpyAsync(coords, dev_xyz, (size_t)n_points * 24, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(nin_update_pad_coords_kernel, blocks_for(n_points), dim3(TPB), 0, stream, n_points, coords_dim, dev_xyz, coords);
+    return launch_status();
 }
 
 int launch_update_geometry(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const int32_t *inpofa,
                            double *centroids, double *face_center, float *face_normal, double *face_area, hipStream_t stream) {
     if (g.n_elems > 0)
-        hipLaunchKernelGGL(nin_update_cells_kernel, dim3(blocks_for(g.n_elems)), dim3(TPB), 0, stream, g.n_elems, (int)g.dim, g.n_points, npoel8,
+        hipLaunchKernelGGL(nin_update_cells_kernel, blocks_for(g.n_elems), dim3(TPB), 0, stream, g.n_elems, (int)g.dim, g.n_points, npoel8,
                            reinterpret_cast<const int4 *>(inpoel), etype, g.coords, centroids);
     if (g.n_faces > 0) {
         if (g.dim == 3)
-            hipLaunchKernelGGL((nin_update_faces_kernel<true>), dim3(blocks_for(g.n_faces)), dim3(TPB), 0, stream, g.n_faces, 3, g.n_points,
+            hipLaunchKernelGGL((nin_update_faces_kernel<true>), blocks_for(g.n_faces), dim3(TPB), 0, stream, g.n_faces, 3, g.n_points,
                                reinterpret_cast<const int4 *>(inpofa), g.coords, face_center, face_normal, face_area);
         else
-            hipLaunchKernelGGL((nin_update_faces_kernel<false>), dim3(blocks_for(g.n_faces)), dim3(TPB), 0, stream, g.n_faces, (int)g.dim,
+            hipLaunchKernelGGL((nin_update_faces_kernel<false>), blocks_for(g.n_faces), dim3(TPB), 0, stream, g.n_faces, (int)g.dim,
                                g.n_points, reinterpret_cast<const int4 *>(inpofa), g.coords, face_center, face_normal, face_area);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

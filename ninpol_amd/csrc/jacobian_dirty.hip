@@ -35,7 +35,6 @@ constexpr int WAVES = TPB / 64;
 constexpr int NK = kAdjBins;
 static_assert(NK + 2 <= kAdjDirtyHdrInts, "the header of the adjoint's dirty lists is too small for the bins");
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 
 __global__ __launch_bounds__(TPB) void nin_adj_bin_byte_kernel(const int32_t *__restrict__ nodes, int32_t count, int32_t P, uint8_t b,
                                                                 uint8_t *__restrict__ bin_of) {
@@ -126,50 +125,50 @@ __global__ __launch_bounds__(TPB) void nin_mark_dirty_kernel(int64_t m, const Id
 
 int launch_adj_bin_byte(const int32_t *nodes, int32_t count, int32_t n_points, int bin, uint8_t *bin_of, hipStream_t stream) {
     if (count <= 0) return 0;
-    hipLaunchKernelGGL(nin_adj_bin_byte_kernel, dim3(blocks_for(count)), dim3(TPB), 0, stream, nodes, count, n_points, (uint8_t)bin, bin_of);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_adj_bin_byte_kernel, blocks_for(count), dim3(TPB), 0, stream, nodes, count, n_points, (uint8_t)bin, bin_of);
+    return launch_status();
 }
 
-size_t adj_dirty_hist_ints(int32_t n_points) { return (size_t)NK * blocks_for(n_points) + 1; }
+size_t adj_dirty_hist_ints(int32_t n_points) { return (size_t)NK * blocks_for(n_points).x + 1; }
 
 int adj_dirty_tmp_bytes(int32_t n_points, size_t *bytes) {
     *bytes = 0;
     int32_t *none = nullptr;
-    return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, none, none, (int)adj_dirty_hist_ints(n_points), nullptr) == hipSuccess ? 0 : -3;
+    return launch_status(hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, none, none, (int)adj_dirty_hist_ints(n_points), nullptr));
 }
 
 int launch_adj_dirty_compact(int32_t n_points, int clear, uint8_t *dirty, const uint8_t *bin_of, const int32_t *rejected, int32_t *hist,
                              int32_t *scanned, void *tmp, size_t tmp_bytes, int32_t *lists, int32_t *hdr, hipStream_t stream) {
     if (n_points <= 0) return 0;
-    const int32_t nblocks = (int32_t)blocks_for(n_points);
+    const int32_t nblocks = (int32_t)blocks_for(n_points).x;
     hipLaunchKernelGGL((nin_adj_dirty_compact_kernel<false>), dim3(nblocks), dim3(TPB), 0, stream, n_points, nblocks, 0, dirty, bin_of, rejected,
                        hist, lists, hdr);
-    if (hipGetLastError() != hipSuccess) return -3;
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, hist, scanned, (int)adj_dirty_hist_ints(n_points), stream) != hipSuccess) return -3;
+    if (int rc = launch_status()) return rc;
+    if (int rc = launch_status(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, hist, scanned, (int)adj_dirty_hist_ints(n_points), stream))) return rc;
     hipLaunchKernelGGL((nin_adj_dirty_compact_kernel<true>), dim3(nblocks), dim3(TPB), 0, stream, n_points, nblocks, clear, dirty, bin_of, rejected,
                        scanned, lists, hdr);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_jac_seed_rows(const GridView &g, const int32_t *list, int32_t total, const double *u, double *grad_csr, hipStream_t stream) {
     if (total <= 0) return 0;
-    hipLaunchKernelGGL(nin_jac_seed_rows_kernel, dim3((unsigned)(((int64_t)total + TPB / 16 - 1) / (TPB / 16))), dim3(TPB), 0, stream, g.esup_ptr,
+    hipLaunchKernelGGL(nin_jac_seed_rows_kernel, blocks_for(total, TPB / 16), dim3(TPB), 0, stream, g.esup_ptr,
                        g.esup, list, total, u, grad_csr);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_mark_dirty(const GridView &g, uint64_t npoel8, const int32_t *inpoel, const int8_t *etype, const void *dev_ids, int ids_are_int64,
                       int64_t n, int ids_are_cells, uint8_t *dirty, int32_t *rejected, hipStream_t stream) {
     if (n <= 0) return 0;
-    if (n > (int64_t)INT32_MAX * TPB) return -5;
+    if (n > (int64_t)INT32_MAX * TPB) return fail(NIN_ERANGE, "%lld ids are more than one launch takes", (long long)n);
     const int4 *cells = reinterpret_cast<const int4 *>(inpoel);
     if (ids_are_int64)
-        hipLaunchKernelGGL((nin_mark_dirty_kernel<int64_t>), dim3(blocks_for(n)), dim3(TPB), 0, stream, n, static_cast<const int64_t *>(dev_ids),
+        hipLaunchKernelGGL((nin_mark_dirty_kernel<int64_t>), blocks_for(n), dim3(TPB), 0, stream, n, static_cast<const int64_t *>(dev_ids),
                            ids_are_cells ? 1 : 0, g.n_elems, g.n_points, npoel8, cells, etype, dirty, rejected);
     else
-        hipLaunchKernelGGL((nin_mark_dirty_kernel<int32_t>), dim3(blocks_for(n)), dim3(TPB), 0, stream, n, static_cast<const int32_t *>(dev_ids),
+        hipLaunchKernelGGL((nin_mark_dirty_kernel<int32_t>), blocks_for(n), dim3(TPB), 0, stream, n, static_cast<const int32_t *>(dev_ids),
                            ids_are_cells ? 1 : 0, g.n_elems, g.n_points, npoel8, cells, etype, dirty, rejected);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

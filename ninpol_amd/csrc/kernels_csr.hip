@@ -282,7 +282,7 @@ int launch_row_nnz(const GridView &g, const double *data, int32_t *row_nnz, hipS
     if (p_end <= p_begin) return 0;
     hipLaunchKernelGGL(nin_row_nnz_kernel, dim3(grid_for(p_end - p_begin)), dim3(256), 0, stream, g, data, row_nnz, p_begin / 64,
                        (int32_t)(((int64_t)p_end + 63) / 64), p_end);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_compact(const GridView &g, const double *data, const int32_t *new_ptr, int32_t *indices,
@@ -291,26 +291,26 @@ int launch_compact(const GridView &g, const double *data, const int32_t *new_ptr
     if (p_end <= p_begin) return 0;
     hipLaunchKernelGGL(nin_compact_kernel, dim3(grid_for(p_end - p_begin)), dim3(256), 0, stream, g, data, new_ptr, indices, vals,
                        p_begin / 64, (int32_t)(((int64_t)p_end + 63) / 64));
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_pad_centroids(const double *src, int64_t n_elems, double *dst, hipStream_t stream) {
     if (n_elems <= 0) return 0;
     hipLaunchKernelGGL(nin_pad_centroids_kernel, dim3(grid_for(n_elems)), dim3(256), 0, stream, src, n_elems, dst);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_sddmm(const GridView &g, const double *u, const double *v, int32_t k, double *grad, hipStream_t stream) {
     if (g.n_points <= 0) return 0;
     hipLaunchKernelGGL(nin_sddmm_kernel, dim3(grid_for(g.n_points)), dim3(256), 0, stream, g, u, v, k, grad);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_apply_list(const GridView &g, const double *data, const double *u, int32_t k, double *values, const int32_t *list,
                       int32_t count, hipStream_t stream) {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(nin_apply_list_kernel, dim3(grid_for(count)), dim3(256), 0, stream, g, data, u, k, values, list, count);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 // LDS entries per wavefront and nodes per tile for rows of at most `mx_row` entries, `nnz` in all: 64 rows in steps of 64, at most
@@ -331,9 +331,9 @@ static int apply_grid(const GridView &g, int32_t tn) {
 int launch_apply(const GridView &g, const double *data, const double *u, double *values, int32_t mx_row, int64_t nnz, hipStream_t stream) {
     int32_t tn;
     const int32_t cap = apply_cap(mx_row, nnz, g.n_points, &tn);
-    if (allow_dynamic_lds<nin_apply_kernel<1>>((size_t)cap * 4 * 12)) return -3;
+    if (int rc = allow_dynamic_lds<nin_apply_kernel<1>>((size_t)cap * 4 * 12)) return rc;
     hipLaunchKernelGGL(nin_apply_kernel<1>, dim3(apply_grid(g, tn)), dim3(256), (size_t)cap * 4 * 12, stream, g, data, u, 0, 1, values, cap, tn);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 // k fields: four per pass over the weights (the rows of a wavefront are staged once per pass)
@@ -343,19 +343,23 @@ int launch_apply_fields(const GridView &g, const double *data, const double *u, 
     const int32_t cap = apply_cap(mx_row, nnz, g.n_points, &tn);
     const size_t lds = (size_t)cap * 4 * 12;
     const dim3 grid(apply_grid(g, tn));
-    if (allow_dynamic_lds<nin_apply_kernel<1>>(lds) || allow_dynamic_lds<nin_apply_kernel<2>>(lds) || allow_dynamic_lds<nin_apply_kernel<4>>(lds)) return -3;
+    if (int rc = allow_dynamic_lds<nin_apply_kernel<1>>(lds)) return rc;
+    if (int rc = allow_dynamic_lds<nin_apply_kernel<2>>(lds)) return rc;
+    if (int rc = allow_dynamic_lds<nin_apply_kernel<4>>(lds)) return rc;
+    // (not on for_each_chunk: the instantiations are 1, 2 and 4 fields with a k0 / k mask inside the kernel -- three fields run the
+    // four-field kernel -- and a walk over 1 .. 4 would need a kernel this unit does not have)
     for (int32_t k0 = 0; k0 < k; k0 += 4) {
         if (k - k0 >= 3) hipLaunchKernelGGL(nin_apply_kernel<4>, grid, dim3(256), lds, stream, g, data, u, k0, k, values, cap, tn);
         else if (k - k0 == 2) hipLaunchKernelGGL(nin_apply_kernel<2>, grid, dim3(256), lds, stream, g, data, u, k0, k, values, cap, tn);
         else hipLaunchKernelGGL(nin_apply_kernel<1>, grid, dim3(256), lds, stream, g, data, u, k0, k, values, cap, tn);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_iota(int32_t *dst, int32_t n, hipStream_t stream) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(nin_iota_kernel, dim3(grid_for(n)), dim3(256), 0, stream, dst, n);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_transpose_index_fill(const GridView &g, const int32_t *sorted_cells, int32_t nnz, int32_t *cell_ptr, const int32_t *cell_pos,
@@ -363,7 +367,7 @@ int launch_transpose_index_fill(const GridView &g, const int32_t *sorted_cells, 
     hipLaunchKernelGGL(nin_cell_ptr_kernel, dim3(grid_for((int64_t)g.n_elems + 1)), dim3(256), 0, stream, sorted_cells, nnz, g.n_elems, cell_ptr);
     if (nnz > 0)
         hipLaunchKernelGGL(nin_cell_node_kernel, dim3(grid_for(nnz)), dim3(256), 0, stream, g.esup_ptr, g.n_points, cell_pos, nnz, cell_node);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 // k fields: four per pass over the index (the runs of a wavefront are staged once per pass), as launch_apply_fields
@@ -374,9 +378,9 @@ int launch_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int
     const size_t lds = (size_t)cap * 4 * 2 * sizeof(int32_t);
     const int64_t blocks = ((int64_t)(g.n_elems + 63) / 64 + 3) / 4;
     const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks > 256 * 32 ? 256 * 32 : blocks));
-    if (allow_dynamic_lds<nin_apply_transpose_kernel<1>>(lds) || allow_dynamic_lds<nin_apply_transpose_kernel<2>>(lds) ||
-        allow_dynamic_lds<nin_apply_transpose_kernel<4>>(lds))
-        return -3;
+    if (int rc = allow_dynamic_lds<nin_apply_transpose_kernel<1>>(lds)) return rc;
+    if (int rc = allow_dynamic_lds<nin_apply_transpose_kernel<2>>(lds)) return rc;
+    if (int rc = allow_dynamic_lds<nin_apply_transpose_kernel<4>>(lds)) return rc;
     for (int32_t k0 = 0; k0 < k; k0 += 4) {
         if (k - k0 >= 3)
             hipLaunchKernelGGL(nin_apply_transpose_kernel<4>, grid, dim3(256), lds, stream, g.n_elems, g.n_points, cell_ptr, cell_pos, cell_node,
@@ -388,7 +392,7 @@ int launch_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int
             hipLaunchKernelGGL(nin_apply_transpose_kernel<1>, grid, dim3(256), lds, stream, g.n_elems, g.n_points, cell_ptr, cell_pos, cell_node,
                                data, v, k0, k, x, cap);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

@@ -219,7 +219,7 @@ int launch_rpl(const GridView &g, const int32_t *nodes, int32_t count, int add_n
                                                                            //  16 rows per lane: 160 registers, eight wavefronts)
     hipLaunchKernelGGL((nin_gls_team_kernel<RPL, TW>), dim3((unsigned)blocks), dim3(64 * TW), 0, stream, g, nodes, count, add_neumann, out, nws,
                        scratch, (long long)scratch_stride);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace
@@ -236,7 +236,7 @@ int launch_gls_class(const GridView &g, const int32_t *nodes, int32_t count, int
     if (rows_per_lane <= 8) { NIN_RPL(8); }
     if (rows_per_lane <= 16) { NIN_RPL(16); }
 #undef NIN_RPL
-    return -5;  // more than 1024 rows in one node's system
+    return fail(NIN_ERANGE, "%d rows per lane: more than 1024 rows in one node's system", (int)rows_per_lane);
 }
 
 const char *kernel_name_gls() { return "nin_gls_team_kernel"; }

@@ -762,7 +762,7 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
     size_t lds = 0;
     if (LDS) {
         lds = (size_t)bytes;
-        if (allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD, GOP>>(lds)) return -3;
+        if (int rc = allow_dynamic_lds<nin_gls_adjoint_kernel<TW, LDS, TAN, RED, PTS, GRD, GOP>>(lds)) return rc;
         int64_t per_cu = (160 * 1024) / (lds < 1024 ? 1024 : (int64_t)lds);
         if (per_cu > 32 / TW) per_cu = 32 / TW;
         if (per_cu < 1) per_cu = 1;
@@ -772,7 +772,7 @@ int launch_bin(const GridView &g, const int32_t *nodes, int32_t count, int64_t b
     }
     if (blocks > count) blocks = count;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * TW), lds, stream, g, nodes, count, add_neumann, io, scratch, (long long)stride);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 // one bin's nodes through the class of that bin: 1, 2, 4 wavefronts in LDS, 8 over a global-memory slot
@@ -784,19 +784,20 @@ int launch_bin_of(const GridView &g, int bin, const AdjBinRun &r, int add_neuman
         case 1: return launch_bin<2, true, TAN, RED, PTS, GRD, GOP>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
         case 2: return launch_bin<4, true, TAN, RED, PTS, GRD, GOP>(g, r.nodes, r.count, r.bytes, add_neumann, io, nullptr, 0, 0, stream);
         case 3:
-            if (!r.scratch || r.scratch_slots < 1 || r.scratch_stride * 8 < r.bytes) return -1;
+            if (!r.scratch || r.scratch_slots < 1 || r.scratch_stride * 8 < r.bytes)
+                return fail(NIN_EINVAL, "adjoint bin 3 has no scratch slots of %lld bytes", (long long)r.bytes);
             return launch_bin<8, false, TAN, RED, PTS, GRD, GOP>(g, r.nodes, r.count, r.bytes, add_neumann, io, r.scratch, r.scratch_stride, r.scratch_slots,
                                                        stream);
     }
-    return -1;
+    return fail(NIN_EINVAL, "the adjoint kernel has no bin %d", bin);
 }
 
 }  // namespace
 
 int launch_adjoint_bytes(const GridView &g, int64_t *bytes, hipStream_t stream) {
     if (g.n_points <= 0) return 0;
-    hipLaunchKernelGGL(nin_adjoint_bytes_kernel, dim3((unsigned)((g.n_points + 255) / 256)), dim3(256), 0, stream, g, bytes);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_adjoint_bytes_kernel, blocks_for(g.n_points), dim3(256), 0, stream, g, bytes);
+    return launch_status();
 }
 
 int launch_gls_adjoint(const GridView &g, int bin, const AdjBinRun &run, int add_neumann, const double *grad_csr, const double *grad_nws,
@@ -855,9 +856,9 @@ int launch_gls_gradop_factorize(const GridView &g, int bin, const AdjBinRun &run
 int launch_adjoint_gather(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const double *contrib, double *grad_perm,
                           double *grad_diff_mag, hipStream_t stream) {
     if (g.n_elems <= 0) return 0;
-    hipLaunchKernelGGL(nin_adjoint_gather_kernel, dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems, cell_ptr, cell_pos,
+    hipLaunchKernelGGL(nin_adjoint_gather_kernel, blocks_for(g.n_elems), dim3(256), 0, stream, g.n_elems, cell_ptr, cell_pos,
                        contrib, g.perm, grad_perm, grad_diff_mag);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

@@ -786,18 +786,7 @@ int launch_block(const GridView &g, const int32_t *nodes, int32_t count, int32_t
                  double *out, double *nws, int32_t *queue, hipStream_t stream) {
     auto kern = nin_gls_block_kernel<NW, CS>;
     static const int dbg = getenv("NIN_GLS_BLOCK_DEBUG") ? atoi(getenv("NIN_GLS_BLOCK_DEBUG")) : 0;
-    // per instantiation AND per device (the attribute belongs to the (function, device) pair and one process may
-    // drive several GPUs): raise the dynamic-LDS limit once per new maximum
-    static int lds_allowed_dev[64] = {};
-    int dev_id = 0;
-    (void)hipGetDevice(&dev_id);
-    int &lds_allowed = lds_allowed_dev[dev_id & 63];
-    if (lds_allowed == 0) lds_allowed = 48 * 1024;
-    if (lds_bytes > lds_allowed) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-            return -3;
-        lds_allowed = lds_bytes;
-    }
+    if (int rc = allow_dynamic_lds<nin_gls_block_kernel<NW, CS>>((size_t)lds_bytes)) return rc;
     int per_cu = (160 * 1024) / (lds_bytes < 1024 ? 1024 : lds_bytes);
     const int wave_cap = 32 / NW;
     if (per_cu > wave_cap) per_cu = wave_cap;
@@ -809,7 +798,7 @@ int launch_block(const GridView &g, const int32_t *nodes, int32_t count, int32_t
     if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;   // diagnostic: occupancy experiments
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * NW), (size_t)lds_bytes, stream, g, nodes, count, add_neumann,
                        out, nws, queue, dbg);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 template <int NW>
@@ -821,7 +810,7 @@ int launch_block_cs(int cs, const GridView &g, const int32_t *nodes, int32_t cou
         case 3: return launch_block<NW, 3>(g, nodes, count, lds_bytes, add_neumann, out, nws, queue, stream);
         case 4: return launch_block<NW, 4>(g, nodes, count, lds_bytes, add_neumann, out, nws, queue, stream);
     }
-    return -5;
+    return fail(NIN_ERANGE, "the block kernel has no instantiation for %d column slots", cs);
 }
 
 }  // namespace
@@ -835,7 +824,7 @@ int launch_gls_block(const GridView &g, const int32_t *nodes, int32_t count, int
         case 4: return launch_block_cs<4>(col_slots, g, nodes, count, lds_bytes, add_neumann, out, nws, queue, stream);
         case 8: return launch_block_cs<8>(col_slots, g, nodes, count, lds_bytes, add_neumann, out, nws, queue, stream);
     }
-    return -1;
+    return fail(NIN_EINVAL, "the block kernel has no instantiation for %d wavefronts", (int)waves);
 }
 
 const char *kernel_name_gls_block() { return "nin_gls_block_kernel"; }

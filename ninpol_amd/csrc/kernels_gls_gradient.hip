@@ -53,15 +53,15 @@ __global__ __launch_bounds__(256) void nin_node_gradient_kernel(GridView g, long
 
 int launch_corner_flux(const GridView &g, int64_t nnz, int32_t n_fields, const double *grad, double *flux, hipStream_t stream) {
     if (nnz <= 0) return 0;
-    hipLaunchKernelGGL(nin_corner_flux_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, g, (long long)nnz, n_fields, grad, flux);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_corner_flux_kernel, blocks_for(nnz), dim3(256), 0, stream, g, (long long)nnz, n_fields, grad, flux);
+    return launch_status();
 }
 
 int launch_node_gradient(const GridView &g, int64_t nnz, int32_t n_fields, const double *grad, double *node_gradient, hipStream_t stream) {
     if (g.n_points <= 0) return 0;
-    hipLaunchKernelGGL(nin_node_gradient_kernel, dim3((unsigned)((g.n_points + 255) / 256)), dim3(256), 0, stream, g, (long long)nnz, n_fields, grad,
+    hipLaunchKernelGGL(nin_node_gradient_kernel, blocks_for(g.n_points), dim3(256), 0, stream, g, (long long)nnz, n_fields, grad,
                        node_gradient);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

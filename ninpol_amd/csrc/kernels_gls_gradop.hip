@@ -126,22 +126,20 @@ __global__ __launch_bounds__(256) void nin_gradop_gather_kernel(int32_t n_elems,
 template <int NF>
 int apply_chunk(const GridView &g, int64_t nnz, const long long *gop_ptr, const int32_t *pos_node, const double *gop, const double *u,
                 double *grad, hipStream_t stream) {
-    hipLaunchKernelGGL(nin_gradop_apply_kernel<NF>, dim3((unsigned)((3 * nnz + 255) / 256)), dim3(256), 0, stream, g, (long long)nnz, gop_ptr,
-                       pos_node, gop, u, grad);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_gradop_apply_kernel<NF>, blocks_for(3 * nnz), dim3(256), 0, stream, g, (long long)nnz, gop_ptr, pos_node, gop, u, grad);
+    return launch_status();
 }
 
 template <int NF>
 int transpose_chunk(const GridView &g, int64_t nnz, const int32_t *cell_ptr, const int32_t *cell_pos, const long long *gop_ptr,
                     const int32_t *pos_node, const double *gop, const double *gbar, double *dots, double *ubar, hipStream_t stream) {
     if (nnz > 0) {
-        hipLaunchKernelGGL(nin_gradop_dot_kernel<NF>, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, g, (long long)nnz, gop_ptr,
-                           pos_node, gop, gbar, dots);
-        if (hipGetLastError() != hipSuccess) return -3;
+        hipLaunchKernelGGL(nin_gradop_dot_kernel<NF>, blocks_for(nnz), dim3(256), 0, stream, g, (long long)nnz, gop_ptr, pos_node, gop, gbar, dots);
+        if (int rc = launch_status()) return rc;
     }
-    hipLaunchKernelGGL(nin_gradop_gather_kernel<NF>, dim3((unsigned)(((int64_t)g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems,
-                       (long long)nnz, cell_ptr, cell_pos, dots, ubar);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_gradop_gather_kernel<NF>, blocks_for(g.n_elems), dim3(256), 0, stream, g.n_elems, (long long)nnz, cell_ptr, cell_pos,
+                       dots, ubar);
+    return launch_status();
 }
 
 }  // namespace
@@ -150,8 +148,8 @@ int launch_gradop_layout(const GridView &g, int64_t nnz, int64_t *count, void *t
                          hipStream_t stream) {
     if (!tmp) return xjac_pattern_scan(nullptr, tmp_bytes, count, gop_ptr, g.n_points, stream);   // (the size of the scan's scratch alone)
     (void)nnz;
-    hipLaunchKernelGGL(nin_gradop_layout_kernel, dim3((unsigned)(((int64_t)g.n_points + 256) / 256)), dim3(256), 0, stream, g, count, pos_node);
-    if (hipGetLastError() != hipSuccess) return -3;
+    hipLaunchKernelGGL(nin_gradop_layout_kernel, blocks_for((int64_t)g.n_points + 1), dim3(256), 0, stream, g, count, pos_node);
+    if (int rc = launch_status()) return rc;
     return xjac_pattern_scan(tmp, tmp_bytes, count, gop_ptr, g.n_points, stream);
 }
 
@@ -160,19 +158,10 @@ int launch_gradop_apply(const GridView &g, int64_t nnz, const int64_t *gop_ptr_,
     static_assert(sizeof(long long) == sizeof(int64_t), "gop_ptr is read as long long");
     if (nnz <= 0) return 0;
     const long long *gop_ptr = reinterpret_cast<const long long *>(gop_ptr_);
-    for (int32_t t = 0; t < n; t += kGradopChunk) {
-        const double *uc = u + (size_t)t * (size_t)g.n_elems;
-        double *gc = grad + (size_t)t * 3 * (size_t)nnz;
-        int rc = 0;
-        switch (n - t < kGradopChunk ? n - t : kGradopChunk) {
-            case 1: rc = apply_chunk<1>(g, nnz, gop_ptr, pos_node, gop, uc, gc, stream); break;
-            case 2: rc = apply_chunk<2>(g, nnz, gop_ptr, pos_node, gop, uc, gc, stream); break;
-            case 3: rc = apply_chunk<3>(g, nnz, gop_ptr, pos_node, gop, uc, gc, stream); break;
-            default: rc = apply_chunk<4>(g, nnz, gop_ptr, pos_node, gop, uc, gc, stream); break;
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    return for_each_chunk<kGradopChunk>(n, [&](auto nf, int32_t t) {
+        return apply_chunk<decltype(nf)::value>(g, nnz, gop_ptr, pos_node, gop, u + (size_t)t * (size_t)g.n_elems, grad + (size_t)t * 3 * (size_t)nnz,
+                                                stream);
+    });
 }
 
 int launch_gradop_apply_transpose(const GridView &g, int64_t nnz, const int32_t *cell_ptr, const int32_t *cell_pos, const int64_t *gop_ptr_,
@@ -180,19 +169,10 @@ int launch_gradop_apply_transpose(const GridView &g, int64_t nnz, const int32_t 
                                   hipStream_t stream) {
     if (g.n_elems <= 0) return 0;
     const long long *gop_ptr = reinterpret_cast<const long long *>(gop_ptr_);
-    for (int32_t t = 0; t < n; t += kGradopChunk) {
-        const double *gc = gbar + (size_t)t * 3 * (size_t)nnz;
-        double *uc = ubar + (size_t)t * (size_t)g.n_elems;
-        int rc = 0;
-        switch (n - t < kGradopChunk ? n - t : kGradopChunk) {
-            case 1: rc = transpose_chunk<1>(g, nnz, cell_ptr, cell_pos, gop_ptr, pos_node, gop, gc, dots, uc, stream); break;
-            case 2: rc = transpose_chunk<2>(g, nnz, cell_ptr, cell_pos, gop_ptr, pos_node, gop, gc, dots, uc, stream); break;
-            case 3: rc = transpose_chunk<3>(g, nnz, cell_ptr, cell_pos, gop_ptr, pos_node, gop, gc, dots, uc, stream); break;
-            default: rc = transpose_chunk<4>(g, nnz, cell_ptr, cell_pos, gop_ptr, pos_node, gop, gc, dots, uc, stream); break;
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    return for_each_chunk<kGradopChunk>(n, [&](auto nf, int32_t t) {
+        return transpose_chunk<decltype(nf)::value>(g, nnz, cell_ptr, cell_pos, gop_ptr, pos_node, gop, gbar + (size_t)t * 3 * (size_t)nnz, dots,
+                                                    ubar + (size_t)t * (size_t)g.n_elems, stream);
+    });
 }
 
 }  // namespace nin

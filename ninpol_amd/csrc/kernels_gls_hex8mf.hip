@@ -605,8 +605,8 @@ __global__ void k_hex8_desc(GridView g, const int32_t *__restrict__ nodes, int32
 
 int launch_hex8_desc(const GridView &g, const int32_t *nodes, int32_t count, int32_t *desc, hipStream_t stream) {
     if (count <= 0) return 0;
-    hipLaunchKernelGGL(k_hex8_desc, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, g, nodes, count, desc);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(k_hex8_desc, blocks_for(count), dim3(256), 0, stream, g, nodes, count, desc);
+    return launch_status();
 }
 
 int launch_gls_hex8mf(const GridView &g, const int32_t *nodes, const int32_t *desc, int32_t count, int add_neumann,
@@ -638,7 +638,7 @@ int launch_gls_hex8mf(const GridView &g, const int32_t *nodes, const int32_t *de
         }
     }
 #endif
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 // the two-wave kernel in its apply form: values[f][p] = (W . u_f)[p] for the listed cube nodes, neumann_ws as always
@@ -650,7 +650,7 @@ int launch_gls_hex8mf_apply(const GridView &g, const int32_t *nodes, const int32
     if (blocks > 8) blocks &= ~(int64_t)7;
     hipLaunchKernelGGL(nin_gls_hex8w2_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, g, nodes, desc, count, add_neumann,
                        nullptr, nws, queue, u_cells, n_fields, values);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 // (as rocprofv3 prints it: the weights form of the two-wave kernel is the instantiation <false>, the apply form <true>)

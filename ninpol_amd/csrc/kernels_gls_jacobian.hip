@@ -39,15 +39,6 @@ using namespace waveops;
 constexpr int kJacChunk = 4;   // directions per pass over the contribution buffer
 constexpr int kJacAhead = 3;   // 16-byte loads of a row a lane issues before it uses the first (a cube node's row is 2.5 per lane)
 
-// the sum over a row of 16 lanes, in every lane of the row (all 64 lanes active): wave_sum's first four steps
-__device__ __forceinline__ double row16_sum(double v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror
-    return v;
-}
-
 // grad_csr[pos] = u[esup[pos]]: the cotangent whose adjoint launch leaves the Jacobian of W u in the contribution buffer
 __global__ __launch_bounds__(256) void nin_jac_seed_kernel(const int32_t *__restrict__ esup, size_t nnz, const double *__restrict__ u,
                                                           double *__restrict__ grad_csr) {
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(256) void nin_jac_apply_kernel(int32_t n_points, si
     double mine = 0.0;   // lane t of the group writes direction t
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const double s = row16_sum(acc[t]);
+        const double s = group_sum<16>(acc[t]);
         if (lane == t) mine = s;
     }
     if (live && lane < NT) out[(size_t)lane * (size_t)n_points + p] = mine;
@@ -158,48 +149,43 @@ __global__ __launch_bounds__(256) void nin_jac_apply_transpose_kernel(int32_t n_
 }
 
 template <int NT>
-void apply_chunk(const GridView &g, const double *contrib, const double *fold, const double *dperm, const double *ddm, double *out,
-                 hipStream_t stream) {
-    hipLaunchKernelGGL(nin_jac_apply_kernel<NT>, dim3((unsigned)(((int64_t)g.n_points + 15) / 16)), dim3(256), 0, stream, g.n_points,
-                       (size_t)g.n_elems, g.esup_ptr, g.esup, contrib, fold, dperm, ddm, out);
+int apply_chunk(const GridView &g, const double *contrib, const double *fold, const double *dperm, const double *ddm, double *out,
+                hipStream_t stream) {
+    hipLaunchKernelGGL(nin_jac_apply_kernel<NT>, blocks_for(g.n_points, 16), dim3(256), 0, stream, g.n_points, (size_t)g.n_elems, g.esup_ptr,
+                       g.esup, contrib, fold, dperm, ddm, out);
+    return launch_status();
 }
 
 template <int NT>
-void transpose_chunk(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, const double *contrib,
-                     const double *fold, const double *v, double *grad_perm, double *grad_dm, hipStream_t stream) {
-    hipLaunchKernelGGL(nin_jac_apply_transpose_kernel<NT>, dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems,
-                       (size_t)g.n_points, cell_ptr, cell_pos, cell_node, contrib, fold, v, grad_perm, grad_dm);
+int transpose_chunk(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, const double *contrib,
+                    const double *fold, const double *v, double *grad_perm, double *grad_dm, hipStream_t stream) {
+    hipLaunchKernelGGL(nin_jac_apply_transpose_kernel<NT>, blocks_for(g.n_elems), dim3(256), 0, stream, g.n_elems, (size_t)g.n_points,
+                       cell_ptr, cell_pos, cell_node, contrib, fold, v, grad_perm, grad_dm);
+    return launch_status();
 }
 
 }  // namespace
 
 int launch_jac_seed(const GridView &g, int64_t nnz, const double *u, double *grad_csr, hipStream_t stream) {
     if (nnz <= 0) return 0;
-    hipLaunchKernelGGL(nin_jac_seed_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, stream, g.esup, (size_t)nnz, u, grad_csr);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_jac_seed_kernel, blocks_for(nnz), dim3(256), 0, stream, g.esup, (size_t)nnz, u, grad_csr);
+    return launch_status();
 }
 
 int launch_jac_fold(const GridView &g, double *fold, hipStream_t stream) {
     if (g.n_elems <= 0) return 0;
-    hipLaunchKernelGGL(nin_jac_fold_kernel, dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems, g.perm, fold);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(nin_jac_fold_kernel, blocks_for(g.n_elems), dim3(256), 0, stream, g.n_elems, g.perm, fold);
+    return launch_status();
 }
 
 int launch_jac_apply(const GridView &g, const double *contrib, const double *fold, int32_t n, const double *dperm, const double *ddm,
                      double *out, hipStream_t stream) {
     if (g.n_points <= 0) return 0;
     const size_t P = (size_t)g.n_points, E = (size_t)g.n_elems;
-    for (int32_t t0 = 0; t0 < n; t0 += kJacChunk) {
-        const double *dp = dperm + (size_t)t0 * E * 9, *dm = ddm ? ddm + (size_t)t0 * E : nullptr;
-        double *o = out + (size_t)t0 * P;
-        switch (n - t0 < kJacChunk ? n - t0 : kJacChunk) {
-            case 1: apply_chunk<1>(g, contrib, fold, dp, dm, o, stream); break;
-            case 2: apply_chunk<2>(g, contrib, fold, dp, dm, o, stream); break;
-            case 3: apply_chunk<3>(g, contrib, fold, dp, dm, o, stream); break;
-            default: apply_chunk<4>(g, contrib, fold, dp, dm, o, stream); break;
-        }
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return for_each_chunk<kJacChunk>(n, [&](auto nt, int32_t t0) {
+        return apply_chunk<decltype(nt)::value>(g, contrib, fold, dperm + (size_t)t0 * E * 9, ddm ? ddm + (size_t)t0 * E : nullptr,
+                                                out + (size_t)t0 * P, stream);
+    });
 }
 
 int launch_jac_apply_transpose(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
@@ -207,17 +193,10 @@ int launch_jac_apply_transpose(const GridView &g, const int32_t *cell_ptr, const
                                hipStream_t stream) {
     if (g.n_elems <= 0) return 0;
     const size_t P = (size_t)g.n_points, E = (size_t)g.n_elems;
-    for (int32_t t0 = 0; t0 < n; t0 += kJacChunk) {
-        const double *vv = v + (size_t)t0 * P;
-        double *gp = grad_perm + (size_t)t0 * E * 9, *gd = grad_dm ? grad_dm + (size_t)t0 * E : nullptr;
-        switch (n - t0 < kJacChunk ? n - t0 : kJacChunk) {
-            case 1: transpose_chunk<1>(g, cell_ptr, cell_pos, cell_node, contrib, fold, vv, gp, gd, stream); break;
-            case 2: transpose_chunk<2>(g, cell_ptr, cell_pos, cell_node, contrib, fold, vv, gp, gd, stream); break;
-            case 3: transpose_chunk<3>(g, cell_ptr, cell_pos, cell_node, contrib, fold, vv, gp, gd, stream); break;
-            default: transpose_chunk<4>(g, cell_ptr, cell_pos, cell_node, contrib, fold, vv, gp, gd, stream); break;
-        }
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return for_each_chunk<kJacChunk>(n, [&](auto nt, int32_t t0) {
+        return transpose_chunk<decltype(nt)::value>(g, cell_ptr, cell_pos, cell_node, contrib, fold, v + (size_t)t0 * P,
+                                                    grad_perm + (size_t)t0 * E * 9, grad_dm ? grad_dm + (size_t)t0 * E : nullptr, stream);
+    });
 }
 
 }  // namespace nin

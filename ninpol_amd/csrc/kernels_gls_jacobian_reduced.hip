@@ -38,16 +38,6 @@ template <int M> constexpr int kLanes = M == 1 ? 8 : 16;   // lanes per node
 template <int M> constexpr int kWide = M % 2 == 0 ? 2 : 1;  // doubles per load: 2 where every row begins at a 16-byte boundary
 template <int M> constexpr int kGroup = M == 1 ? 8 : 4;     // entries of a cell the transpose has in flight (a hexahedron has 8 nodes)
 
-// the sum over the L lanes of a node (L = 8 or 16, aligned groups), in every one of them (all 64 lanes active): wave_sum's first steps
-template <int L>
-__device__ __forceinline__ double group_sum(double v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    if constexpr (L == 16) v += dpp_mov<0x140>(v);  // row_mirror
-    return v;
-}
-
 template <int M, int NT>
 __global__ __launch_bounds__(256) void nin_jacr_apply_kernel(int32_t n_points, size_t n_elems, const int32_t *__restrict__ esup_ptr,
                                                             const int32_t *__restrict__ esup, const double *__restrict__ R,
@@ -166,50 +156,35 @@ __global__ __launch_bounds__(256) void nin_jacr_apply_transpose_kernel(int32_t n
 }
 
 template <int M, int NT>
-void apply_chunk(const GridView &g, const double *R, const double *dtheta, double *out, hipStream_t stream) {
-    constexpr int nodes = 256 / kLanes<M>;
-    hipLaunchKernelGGL((nin_jacr_apply_kernel<M, NT>), dim3((unsigned)(((int64_t)g.n_points + nodes - 1) / nodes)), dim3(256), 0, stream,
-                       g.n_points, (size_t)g.n_elems, g.esup_ptr, g.esup, R, dtheta, out);
+int apply_chunk(const GridView &g, const double *R, const double *dtheta, double *out, hipStream_t stream) {
+    hipLaunchKernelGGL((nin_jacr_apply_kernel<M, NT>), blocks_for(g.n_points, 256 / kLanes<M>), dim3(256), 0, stream, g.n_points,
+                       (size_t)g.n_elems, g.esup_ptr, g.esup, R, dtheta, out);
+    return launch_status();
 }
 
 template <int M, int NT>
-void transpose_chunk(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, const double *R,
-                     const double *v, double *grad, hipStream_t stream) {
-    hipLaunchKernelGGL((nin_jacr_apply_transpose_kernel<M, NT>), dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems,
-                       (size_t)g.n_points, cell_ptr, cell_pos, cell_node, R, v, grad);
+int transpose_chunk(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, const double *R,
+                    const double *v, double *grad, hipStream_t stream) {
+    hipLaunchKernelGGL((nin_jacr_apply_transpose_kernel<M, NT>), blocks_for(g.n_elems), dim3(256), 0, stream, g.n_elems, (size_t)g.n_points,
+                       cell_ptr, cell_pos, cell_node, R, v, grad);
+    return launch_status();
 }
 
 template <int M>
 int apply_all(const GridView &g, const double *R, int32_t n, const double *dtheta, double *out, hipStream_t stream) {
     const size_t P = (size_t)g.n_points, E = (size_t)g.n_elems;
-    for (int32_t t0 = 0; t0 < n; t0 += kJacrChunk) {
-        const double *d = dtheta + (size_t)t0 * E * M;
-        double *o = out + (size_t)t0 * P;
-        switch (n - t0 < kJacrChunk ? n - t0 : kJacrChunk) {
-            case 1: apply_chunk<M, 1>(g, R, d, o, stream); break;
-            case 2: apply_chunk<M, 2>(g, R, d, o, stream); break;
-            case 3: apply_chunk<M, 3>(g, R, d, o, stream); break;
-            default: apply_chunk<M, 4>(g, R, d, o, stream); break;
-        }
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return for_each_chunk<kJacrChunk>(n, [&](auto nt, int32_t t0) {
+        return apply_chunk<M, decltype(nt)::value>(g, R, dtheta + (size_t)t0 * E * M, out + (size_t)t0 * P, stream);
+    });
 }
 
 template <int M>
 int transpose_all(const GridView &g, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node, const double *R, int32_t n,
                   const double *v, double *grad, hipStream_t stream) {
     const size_t P = (size_t)g.n_points, E = (size_t)g.n_elems;
-    for (int32_t t0 = 0; t0 < n; t0 += kJacrChunk) {
-        const double *vv = v + (size_t)t0 * P;
-        double *o = grad + (size_t)t0 * E * M;
-        switch (n - t0 < kJacrChunk ? n - t0 : kJacrChunk) {
-            case 1: transpose_chunk<M, 1>(g, cell_ptr, cell_pos, cell_node, R, vv, o, stream); break;
-            case 2: transpose_chunk<M, 2>(g, cell_ptr, cell_pos, cell_node, R, vv, o, stream); break;
-            case 3: transpose_chunk<M, 3>(g, cell_ptr, cell_pos, cell_node, R, vv, o, stream); break;
-            default: transpose_chunk<M, 4>(g, cell_ptr, cell_pos, cell_node, R, vv, o, stream); break;
-        }
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return for_each_chunk<kJacrChunk>(n, [&](auto nt, int32_t t0) {
+        return transpose_chunk<M, decltype(nt)::value>(g, cell_ptr, cell_pos, cell_node, R, v + (size_t)t0 * P, grad + (size_t)t0 * E * M, stream);
+    });
 }
 
 }  // namespace
@@ -221,7 +196,7 @@ int launch_jacr_apply(const GridView &g, int32_t M, const double *R, int32_t n, 
         case 3: return apply_all<3>(g, R, n, dtheta, out, stream);
         case 6: return apply_all<6>(g, R, n, dtheta, out, stream);
     }
-    return -1;
+    return fail(NIN_EINVAL, "the reduced Jacobian is built for 1, 3 or 6 parameters per cell, not %d", (int)M);
 }
 
 int launch_jacr_apply_transpose(const GridView &g, int32_t M, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
@@ -232,7 +207,7 @@ int launch_jacr_apply_transpose(const GridView &g, int32_t M, const int32_t *cel
         case 3: return transpose_all<3>(g, cell_ptr, cell_pos, cell_node, R, n, v, grad_theta, stream);
         case 6: return transpose_all<6>(g, cell_ptr, cell_pos, cell_node, R, n, v, grad_theta, stream);
     }
-    return -1;
+    return fail(NIN_EINVAL, "the reduced Jacobian is built for 1, 3 or 6 parameters per cell, not %d", (int)M);
 }
 
 }  // namespace nin

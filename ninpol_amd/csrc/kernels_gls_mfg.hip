@@ -536,18 +536,18 @@ __global__ void k_mfg_desc(GridView g, const int32_t *__restrict__ nodes, int32_
 
 int launch_mfg_desc(const GridView &g, const int32_t *nodes, int32_t count, uint32_t *desc, hipStream_t stream) {
     if (count <= 0) return 0;
-    hipLaunchKernelGGL(k_mfg_desc, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, g, nodes, count, desc);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(k_mfg_desc, blocks_for(count, 64), dim3(64), 0, stream, g, nodes, count, desc);
+    return launch_status();
 }
 
 // `tiles`: n_slots slots of kMfgSlotDoubles doubles (one per resident wavefront); at most n_slots workgroups are launched
 int launch_gls_mfg(const GridView &g, const int32_t *nodes, const uint32_t *desc, int32_t count, int add_neumann, double *out, double *nws,
                    int32_t *queue, double *tiles, int32_t n_slots, hipStream_t stream) {
     if (count <= 0) return 0;
-    if (!tiles || n_slots <= 0) return -1;
+    if (!tiles || n_slots <= 0) return fail(NIN_EINVAL, "the global-memory multifrontal kernel has no tile slots");
     const int64_t blocks = count < n_slots ? count : n_slots;
     hipLaunchKernelGGL(nin_gls_mfg_kernel, dim3((unsigned)blocks), dim3(64), 0, stream, g, nodes, desc, count, add_neumann, out, nws, queue, tiles);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 const char *kernel_name_gls_mfg() { return "nin_gls_mfg_kernel"; }

@@ -945,8 +945,8 @@ __global__ void k_mfw_desc(GridView g, const int32_t *__restrict__ nodes, int32_
 
 int launch_mfw_desc(const GridView &g, const int32_t *nodes, int32_t count, uint32_t *desc, hipStream_t stream) {
     if (count <= 0) return 0;
-    hipLaunchKernelGGL(k_mfw_desc, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, stream, g, nodes, count, desc);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(k_mfw_desc, blocks_for(count, 128), dim3(128), 0, stream, g, nodes, count, desc);
+    return launch_status();
 }
 
 int launch_gls_mfw(const GridView &g, const int32_t *nodes, const uint32_t *desc, int32_t count, int kind, int add_neumann,
@@ -971,7 +971,7 @@ int launch_gls_mfw(const GridView &g, const int32_t *nodes, const uint32_t *desc
     else if (no_strips) NIN_MFW_LAUNCH(kMfwMaxFronts, kMfwMaxDense, true, false, false);
     else NIN_MFW_LAUNCH(kMfwMaxFronts, kMfwMaxDense, true, false, true);
 #undef NIN_MFW_LAUNCH
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 // `kind`: 0 / 1 / 2 = at most 4 / 8 / 12 cells
@@ -985,7 +985,7 @@ int launch_gls_small(const GridView &g, const int32_t *nodes, int32_t count, int
     if (kind == 0) hipLaunchKernelGGL(nin_gls_small_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, g, nodes, count, add_neumann, out, nws);
     else if (kind == 1) hipLaunchKernelGGL(nin_gls_small_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, stream, g, nodes, count, add_neumann, out, nws);
     else hipLaunchKernelGGL(nin_gls_small_kernel<12>, dim3((unsigned)blocks), dim3(256), 0, stream, g, nodes, count, add_neumann, out, nws);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 const char *kernel_name_gls_mfw() { return "nin_gls_mfw_kernel"; }

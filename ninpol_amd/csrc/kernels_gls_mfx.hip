@@ -374,15 +374,15 @@ __global__ void k_mfx_desc(GridView g, const int32_t *__restrict__ nodes, int32_
 
 int launch_mfx_desc(const GridView &g, const int32_t *nodes, int32_t count, uint32_t *desc, hipStream_t stream) {
     if (count <= 0) return 0;
-    hipLaunchKernelGGL(k_mfx_desc, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, g, nodes, count, desc);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(k_mfx_desc, blocks_for(count, 64), dim3(64), 0, stream, g, nodes, count, desc);
+    return launch_status();
 }
 
 // `cls`: the size class of every node of the list (mfx_desc.hpp: mfx_size_class)
 int launch_gls_mfx(const GridView &g, const int32_t *nodes, const uint32_t *desc, int32_t count, int cls, int add_neumann, double *out,
                    double *nws, int32_t *queue, hipStream_t stream) {
     if (count <= 0) return 0;
-    if (cls < 0 || cls > kMfxClasses + 2) return -1;     // (cls == kMfxClasses: the boundary nodes' list, + 1: the small interior class, + 2: (7, 12))
+    if (cls < 0 || cls > kMfxClasses + 2) return fail(NIN_EINVAL, "the wide multifrontal kernel has no size class %d", cls);    // (cls == kMfxClasses: the boundary nodes' list, + 1: the small interior class, + 2: (7, 12))
     int64_t blocks = count;
     // persistent: one wavefront per workgroup, one (class 0: two) per SIMD -- the register file of a SIMD lane belongs to one (two) node(s)
     constexpr int tiles[kMfxClasses + 3] = {6 * 10, 7 * 11, 8 * 13, 9 * 15, 10 * 16, 7 * 11, 4 * 7, 7 * 12};
@@ -400,7 +400,7 @@ int launch_gls_mfx(const GridView &g, const int32_t *nodes, const uint32_t *desc
     else if (cls == 6) NIN_MFX_LAUNCH(4, 7, false);
     else NIN_MFX_LAUNCH(7, 12, false);
 #undef NIN_MFX_LAUNCH
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 const char *kernel_name_gls_mfx() { return "nin_gls_mfx_kernel"; }

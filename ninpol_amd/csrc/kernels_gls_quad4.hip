@@ -355,8 +355,8 @@ __global__ void k_quad4_desc(GridView g, const int32_t *__restrict__ nodes, int3
 
 int launch_quad4_desc(const GridView &g, const int32_t *nodes, int32_t count, int32_t *desc, hipStream_t stream) {
     if (count <= 0) return 0;
-    hipLaunchKernelGGL(k_quad4_desc, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, g, nodes, count, desc);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(k_quad4_desc, blocks_for(count), dim3(256), 0, stream, g, nodes, count, desc);
+    return launch_status();
 }
 
 int launch_gls_quad4(const GridView &g, const int32_t *nodes, const int32_t *desc, int32_t count, int add_neumann, double *out,
@@ -365,7 +365,7 @@ int launch_gls_quad4(const GridView &g, const int32_t *nodes, const int32_t *des
     int64_t blocks = ((int64_t)count + 4 * QNPW - 1) / (4 * QNPW);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(nin_gls_quad4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g, nodes, desc, count, add_neumann, out, nws);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

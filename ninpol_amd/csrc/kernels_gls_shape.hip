@@ -195,21 +195,21 @@ int launch_shape_tangent_geometry(const GridView &g, const int32_t *inpoel, cons
     if (g.n_faces > 0)
         hipLaunchKernelGGL(nin_shape_tangent_face_kernel, dim3((unsigned)((g.n_faces + 255) / 256), ny), dim3(256), 0, stream, g, n_tangents,
                            reinterpret_cast<const int4 *>(inpofa), tangent_points, tangent_face);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_shape_gather(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos, double *cell_bar,
                         const double *face_bar, double *face_slot, double *grad_points, hipStream_t stream) {
     const int4 *rows = reinterpret_cast<const int4 *>(inpofa);
     if (g.n_faces > 0)
-        hipLaunchKernelGGL(nin_shape_face_kernel, dim3((unsigned)((g.n_faces + 255) / 256)), dim3(256), 0, stream, g, rows, face_bar, face_slot);
+        hipLaunchKernelGGL(nin_shape_face_kernel, blocks_for(g.n_faces), dim3(256), 0, stream, g, rows, face_bar, face_slot);
     if (g.n_elems > 0)
-        hipLaunchKernelGGL(nin_shape_cell_kernel, dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems, cell_ptr, cell_pos,
+        hipLaunchKernelGGL(nin_shape_cell_kernel, blocks_for(g.n_elems), dim3(256), 0, stream, g.n_elems, cell_ptr, cell_pos,
                            cell_bar);
     if (g.n_points > 0)
-        hipLaunchKernelGGL(nin_shape_node_kernel, dim3((unsigned)((g.n_points + 255) / 256)), dim3(256), 0, stream, g, rows, cell_bar, face_slot,
+        hipLaunchKernelGGL(nin_shape_node_kernel, blocks_for(g.n_points), dim3(256), 0, stream, g, rows, cell_bar, face_slot,
                            grad_points);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

@@ -244,9 +244,9 @@ template <bool FILL>
 int pattern_pass(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, int force_slow, int64_t *count, const int64_t *block_ptr,
                  int32_t *block_col, hipStream_t stream) {
     if (g.n_points <= 0) return 0;
-    hipLaunchKernelGGL(nin_xjac_pattern_kernel<FILL>, dim3((unsigned)(((int64_t)g.n_points + 3) / 4)), dim3(256), 0, stream, g,
+    hipLaunchKernelGGL(nin_xjac_pattern_kernel<FILL>, blocks_for(g.n_points, 4), dim3(256), 0, stream, g,
                        reinterpret_cast<const int4 *>(inpoel), reinterpret_cast<const int4 *>(inpofa), force_slow, count, block_ptr, block_col);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace
@@ -256,7 +256,7 @@ int launch_xjac_pattern_count(const GridView &g, const int32_t *inpoel, const in
 }
 
 int xjac_pattern_scan(void *tmp, size_t *tmp_bytes, const int64_t *count, int64_t *block_ptr, int32_t n_points, hipStream_t stream) {
-    return hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, count, block_ptr, (int)(n_points + 1), stream) == hipSuccess ? 0 : -3;
+    return launch_status(hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, count, block_ptr, (int)(n_points + 1), stream));
 }
 
 int launch_xjac_pattern_fill(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, int force_slow, const int64_t *block_ptr,
@@ -267,10 +267,10 @@ int launch_xjac_pattern_fill(const GridView &g, const int32_t *inpoel, const int
 int launch_xjac_assemble(const GridView &g, const int32_t *inpoel, const int32_t *inpofa, const double *cell_bar, const double *face_bar,
                          const double *own_bar, const int64_t *block_ptr, const int32_t *block_col, double *values, hipStream_t stream) {
     if (g.n_points <= 0) return 0;
-    hipLaunchKernelGGL(nin_xjac_assemble_kernel, dim3((unsigned)(((int64_t)g.n_points + 7) / 8)), dim3(256), 0, stream, g,
+    hipLaunchKernelGGL(nin_xjac_assemble_kernel, blocks_for(g.n_points, 8), dim3(256), 0, stream, g,
                        reinterpret_cast<const int4 *>(inpoel), reinterpret_cast<const int4 *>(inpofa), cell_bar, face_bar, own_bar, block_ptr,
                        block_col, values);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace nin

@@ -46,15 +46,6 @@ using namespace waveops;
 
 constexpr int kXjacAhead = 2;   // records of a run a lane loads before it uses the first (a cube node's runs are 8 and 12 records: one)
 
-// the sum over a row of 16 lanes, in every lane of the row (all 64 lanes active): wave_sum's first four steps
-__device__ __forceinline__ double row16_sum(double v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror
-    return v;
-}
-
 struct FaceRec {
     double2 a, b, c;   // (fcbar, Nbar)
 };
@@ -153,7 +144,7 @@ __global__ __launch_bounds__(256) void nin_xjac_apply_kernel(GridView g, const d
     double mine = 0.0;   // lane t of the group writes direction t
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const double s = row16_sum(acc[t]);
+        const double s = group_sum<16>(acc[t]);
         if (lane == t) mine = s;
     }
     if (live && lane < NT) out[(size_t)lane * P + p] = mine;
@@ -287,24 +278,28 @@ __global__ __launch_bounds__(256) void nin_xjac_node_kernel(GridView g, const in
 }
 
 template <int NT>
-void apply_chunk(const GridView &g, const double *cell_bar, const double *face_bar, const double *own_bar, const double *dX, const double *dC,
-                 const double *dFN, double *out, hipStream_t stream) {
-    hipLaunchKernelGGL(nin_xjac_apply_kernel<NT>, dim3((unsigned)(((int64_t)g.n_points + 15) / 16)), dim3(256), 0, stream, g, cell_bar, face_bar,
-                       own_bar, dX, dC, dFN, out);
+int apply_chunk(const GridView &g, const double *cell_bar, const double *face_bar, const double *own_bar, const double *dX, const double *dC,
+                const double *dFN, double *out, hipStream_t stream) {
+    hipLaunchKernelGGL(nin_xjac_apply_kernel<NT>, blocks_for(g.n_points, 16), dim3(256), 0, stream, g, cell_bar, face_bar, own_bar, dX, dC, dFN, out);
+    return launch_status();
 }
 
 template <int NT>
-void transpose_chunk(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
-                     const double *cell_bar, const double *face_bar, const double *own_bar, const double *v, double *cell_share,
-                     double *face_slot, double *grad_points, hipStream_t stream) {
+int transpose_chunk(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos, const int32_t *cell_node,
+                    const double *cell_bar, const double *face_bar, const double *own_bar, const double *v, double *cell_share,
+                    double *face_slot, double *grad_points, hipStream_t stream) {
     const int4 *rows = reinterpret_cast<const int4 *>(inpofa);
-    if (g.n_faces > 0)
-        hipLaunchKernelGGL(nin_xjac_face_kernel<NT>, dim3((unsigned)((g.n_faces + 255) / 256)), dim3(256), 0, stream, g, rows, face_bar, v, face_slot);
-    if (g.n_elems > 0)
-        hipLaunchKernelGGL(nin_xjac_cell_kernel<NT>, dim3((unsigned)((g.n_elems + 255) / 256)), dim3(256), 0, stream, g.n_elems, (size_t)g.n_points,
-                           cell_ptr, cell_pos, cell_node, cell_bar, v, cell_share);
-    hipLaunchKernelGGL(nin_xjac_node_kernel<NT>, dim3((unsigned)((g.n_points + 255) / 256)), dim3(256), 0, stream, g, rows, own_bar, cell_share,
-                       face_slot, v, grad_points);
+    if (g.n_faces > 0) {
+        hipLaunchKernelGGL(nin_xjac_face_kernel<NT>, blocks_for(g.n_faces), dim3(256), 0, stream, g, rows, face_bar, v, face_slot);
+        if (int rc = launch_status()) return rc;
+    }
+    if (g.n_elems > 0) {
+        hipLaunchKernelGGL(nin_xjac_cell_kernel<NT>, blocks_for(g.n_elems), dim3(256), 0, stream, g.n_elems, (size_t)g.n_points, cell_ptr, cell_pos,
+                           cell_node, cell_bar, v, cell_share);
+        if (int rc = launch_status()) return rc;
+    }
+    hipLaunchKernelGGL(nin_xjac_node_kernel<NT>, blocks_for(g.n_points), dim3(256), 0, stream, g, rows, own_bar, cell_share, face_slot, v, grad_points);
+    return launch_status();
 }
 
 }  // namespace
@@ -314,19 +309,11 @@ int launch_xjac_apply(const GridView &g, const int32_t *inpoel, const int32_t *i
                       hipStream_t stream) {
     if (g.n_points <= 0) return 0;
     const size_t P = (size_t)g.n_points;
-    for (int32_t t0 = 0; t0 < n; t0 += kXjacApplyChunk) {
-        const int32_t nt = n - t0 < kXjacApplyChunk ? n - t0 : kXjacApplyChunk;
+    return for_each_chunk<kXjacApplyChunk>(n, [&](auto nt, int32_t t0) {
         const double *dx = dX + (size_t)t0 * P * 3;
-        double *o = out + (size_t)t0 * P;
         if (int rc = launch_shape_tangent_geometry(g, inpoel, inpofa, nt, dx, tangent_cell, tangent_face, stream)) return rc;
-        switch (nt) {
-            case 1: apply_chunk<1>(g, cell_bar, face_bar, own_bar, dx, tangent_cell, tangent_face, o, stream); break;
-            case 2: apply_chunk<2>(g, cell_bar, face_bar, own_bar, dx, tangent_cell, tangent_face, o, stream); break;
-            case 3: apply_chunk<3>(g, cell_bar, face_bar, own_bar, dx, tangent_cell, tangent_face, o, stream); break;
-            default: apply_chunk<4>(g, cell_bar, face_bar, own_bar, dx, tangent_cell, tangent_face, o, stream); break;
-        }
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+        return apply_chunk<decltype(nt)::value>(g, cell_bar, face_bar, own_bar, dx, tangent_cell, tangent_face, out + (size_t)t0 * P, stream);
+    });
 }
 
 int launch_xjac_apply_transpose(const GridView &g, const int32_t *inpofa, const int32_t *cell_ptr, const int32_t *cell_pos,
@@ -334,16 +321,10 @@ int launch_xjac_apply_transpose(const GridView &g, const int32_t *inpofa, const 
                                 const double *v, double *cell_share, double *face_slot, double *grad_points, hipStream_t stream) {
     if (g.n_points <= 0) return 0;
     const size_t P = (size_t)g.n_points;
-    static_assert(kXjacTransposeChunk == 2, "the switch below has the transpose chunk's instantiations");
-    for (int32_t t0 = 0; t0 < n; t0 += kXjacTransposeChunk) {
-        const double *vv = v + (size_t)t0 * P;
-        double *gp = grad_points + (size_t)t0 * P * 3;
-        if (n - t0 < 2)
-            transpose_chunk<1>(g, inpofa, cell_ptr, cell_pos, cell_node, cell_bar, face_bar, own_bar, vv, cell_share, face_slot, gp, stream);
-        else
-            transpose_chunk<2>(g, inpofa, cell_ptr, cell_pos, cell_node, cell_bar, face_bar, own_bar, vv, cell_share, face_slot, gp, stream);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return for_each_chunk<kXjacTransposeChunk>(n, [&](auto nt, int32_t t0) {
+        return transpose_chunk<decltype(nt)::value>(g, inpofa, cell_ptr, cell_pos, cell_node, cell_bar, face_bar, own_bar, v + (size_t)t0 * P,
+                                                    cell_share, face_slot, grad_points + (size_t)t0 * P * 3, stream);
+    });
 }
 
 }  // namespace nin

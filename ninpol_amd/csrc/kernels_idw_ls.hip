@@ -229,7 +229,7 @@ int launch_rows(const GridView &g, const int32_t *targets, int32_t n_targets, in
         int64_t blocks = ((int64_t)n_targets + 255) / 256;
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL((nin_rows_targets_kernel<METHOD>), dim3((unsigned)blocks), dim3(256), 0, stream, g, targets, n_targets, out, nws);
-        return hipGetLastError() == hipSuccess ? 0 : -3;
+        return launch_status();
     }
     // LDS per wave: room for 64 rows of the longest length if that is at most 12 KiB of weights + ids (structured meshes); else 18 KiB
     // and as many nodes a tile -- 64, 32 or 16 -- as fit it at 1.25 x the mesh's mean row length (a tile that is longer still takes
@@ -250,10 +250,10 @@ int launch_rows(const GridView &g, const int32_t *targets, int32_t n_targets, in
     int64_t blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const int64_t cap_blocks = 256 * 8;
     if (blocks > cap_blocks) blocks = cap_blocks;
-    if (allow_dynamic_lds<nin_rows_kernel<METHOD>>(dyn)) return -3;
+    if (int rc = allow_dynamic_lds<nin_rows_kernel<METHOD>>(dyn)) return rc;
     hipLaunchKernelGGL((nin_rows_kernel<METHOD>), dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), dyn, stream, g, n_targets,
                        (int32_t)cap, out, nws, tile_begin, tile_end, tn);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace

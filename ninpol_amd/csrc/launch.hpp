@@ -1,26 +1,70 @@
-// launch.hpp -- kernel launchers shared between the .hip translation units and the C ABI (internal)
+// launch.hpp -- kernel launchers shared between the .hip translation units and the C ABI (internal), and the layer they are written in.
+//
+// A launcher (launch_*) returns 0 or a negative NIN_E* code; its launches are asynchronous on `stream`.  It ends -- and, where it
+// launches more than once, follows every launch -- with launch_status(), which reads hipGetLastError() ONCE (the call clears the error)
+// and, on failure, sets the text of nin_last_error() to "launch failed: <HIP's words>" right there and returns NIN_EHIP.  An argument a
+// launcher refuses gets its code and its text through fail() at that place.  So whoever gets a non-zero code from a launcher hands it on
+// as it is: the text stands, and asking HIP a second time would find "no error".
+// blocks_for(n, per_block) is the grid of a kernel with one thread, or one group of lanes, per item and no grid stride; the capped,
+// grid-stride grids (kernels_csr.hip's grid_for / apply_grid, the 256 * 32 caps, the per-XCD grids of the forward kernels) are other
+// expressions and stay where they are.
+// for_each_chunk<MAX>(n, fn) is the walk of a batched product over its n directions, MAX at a time: fn gets the size of the chunk as a
+// compile-time constant (the kernel instantiation) and where the chunk begins, and a non-zero return ends the walk.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
+#include <type_traits>
 
+#include "../../include/ninpol_amd.h"
 #include "device_grid.hpp"
 
 namespace nin {
 
+// sets what nin_last_error() returns (per thread) and hands `code` back (abi_grid.hip); not a dynamic symbol
+__attribute__((visibility("hidden"))) int fail(int code, const char *fmt, ...);
+
+// the status of a launch: 0, or NIN_EHIP with HIP's words for `e` as the text of nin_last_error().  Without an argument: of the launch
+// just made, read -- and thereby cleared -- once
+inline int launch_status(hipError_t e) { return e == hipSuccess ? 0 : fail(NIN_EHIP, "launch failed: %s", hipGetErrorString(e)); }
+inline int launch_status() { return launch_status(hipGetLastError()); }
+
+// ceil(n / per_block) workgroups
+inline dim3 blocks_for(int64_t n, int64_t per_block = 256) { return dim3((unsigned)((n + per_block - 1) / per_block)); }
+
+// fn(std::integral_constant<int, NT>{}, t0) for t0 = 0, MAX, 2 MAX, ... < n with NT = min(MAX, n - t0); stops at the first non-zero
+// return and hands it back, 0 otherwise
+template <int NT, class Fn>
+int call_chunk(int64_t left, Fn &fn, int32_t t0) {
+    if constexpr (NT > 1)
+        if (left < NT) return call_chunk<NT - 1>(left, fn, t0);
+    return fn(std::integral_constant<int, NT>{}, t0);
+}
+template <int MAX, class Fn>
+int for_each_chunk(int32_t n, Fn fn) {
+    for (int64_t t0 = 0; t0 < n; t0 += MAX)
+        if (int rc = call_chunk<MAX>(n - t0, fn, (int32_t)t0)) return rc;
+    return 0;
+}
+
 #ifdef __HIPCC__
-// dynamic LDS beyond the default limit: the attribute belongs to the (kernel, device) pair; raised once per new maximum
+// dynamic LDS beyond the default limit: the attribute belongs to the (kernel, device) pair; raised once per new maximum, which the
+// cache remembers under a lock (two host threads may launch on one grid).  A device the cache has no slot for, or none at all, sets the
+// attribute every time
 template <auto KERN>
 inline int allow_dynamic_lds(size_t bytes) {
     if (bytes <= 48 * 1024) return 0;
-    static size_t allowed[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t &a = allowed[dev & 63];
-    if (bytes > a) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -3;
-        a = bytes;
-    }
+    constexpr int kSlots = 64;
+    static std::mutex lock;
+    static size_t allowed[kSlots] = {};
+    int dev = -1;
+    const bool cached = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kSlots;
+    std::lock_guard<std::mutex> hold(lock);
+    if (cached && bytes <= allowed[dev]) return 0;
+    if (int rc = launch_status(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)))
+        return rc;
+    if (cached) allowed[dev] = bytes;
     return 0;
 }
 #endif
@@ -217,7 +261,7 @@ int launch_jac_apply_transpose(const GridView &g, const int32_t *cell_ptr, const
                                hipStream_t stream);
 
 // the reduced GLS Jacobian applied (kernels_gls_jacobian_reduced.hip), all DEVICE pointers; R [nnz_esup][M] as
-// launch_gls_adjoint_reduced left it, M in {1, 3, 6} (anything else: -1).
+// launch_gls_adjoint_reduced left it, M in {1, 3, 6} (anything else: NIN_EINVAL).
 // launch_jacr_apply: out [n][P] = J_theta . dtheta [n][E][M]; every entry written.
 // launch_jacr_apply_transpose: grad_theta [n][E][M] = J_theta^T . v [n][P], per cell in ascending node id through the transpose index
 int launch_jacr_apply(const GridView &g, int32_t M, const double *R, int32_t n, const double *dtheta, double *out, hipStream_t stream);

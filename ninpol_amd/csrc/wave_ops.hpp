@@ -1,6 +1,6 @@
 // wave_ops.hpp -- the cross-lane primitives of a 64-lane wavefront, once for every kernel (internal, device code only).
-// Moves and fences only: the one piece of floating-point arithmetic here is wave_sum's additions, which no contraction setting can
-// change -- the header is safe in the units built with -ffp-contract=off.
+// Moves and fences only: the one piece of floating-point arithmetic here is the additions of group_sum and of wave_sum on top of it,
+// which no contraction setting can change -- the header is safe in the units built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,13 +25,23 @@ __device__ __forceinline__ uint32_t rl32(uint32_t v, int lane) { return (uint32_
 
 __device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// Sum over the 64 lanes, result in every lane.  All 64 lanes must be active.  (The order of the additions is part of the dense GLS
-// kernels' results; mfwstrips::wave_allsum adds in another order and is not this.)
-__device__ __forceinline__ double wave_sum(double v) {
+// Sum over the aligned group of L lanes (8 or 16) a lane belongs to, result in every lane of the group.  All 64 lanes must be active.
+// The order of these additions is part of the bitwise contract of every product that uses it (the kept Jacobians' apply kernels, and
+// through wave_sum the dense GLS kernels): this is the one place it is written.
+template <int L>
+__device__ __forceinline__ double group_sum(double v) {
+    static_assert(L == 8 || L == 16, "a group is 8 or 16 lanes");
     v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
     v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
     v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror  -> every lane holds its 16-lane row sum
+    if constexpr (L == 16) v += dpp_mov<0x140>(v);  // row_mirror
+    return v;
+}
+
+// Sum over the 64 lanes, result in every lane.  All 64 lanes must be active.  (mfwstrips::wave_allsum adds in another order and is
+// not this.)
+__device__ __forceinline__ double wave_sum(double v) {
+    v = group_sum<16>(v);   // every lane holds its 16-lane row sum
     return (rl64(v, 0) + rl64(v, 16)) + (rl64(v, 32) + rl64(v, 48));
 }
 

@@ -195,6 +195,18 @@ def test_two_calls_agree_and_a_batch_equals_its_fields(op):
         assert op.apply_transpose(v5[f])[0].tobytes() == ta[f].tobytes(), f
 
 
+def test_a_batch_of_seven_equals_its_fields_one_by_one():
+    """a full chunk of four and a chunk of three behind it, both products, on the smallest mesh"""
+    op = get_op("tet")
+    c = op.c
+    seven = lambda x: np.concatenate([x, 0.5 * x, -3.0 * x])[:7]          # noqa: E731  (the module's three fields, and scaled copies)
+    u7, v7 = seven(op.u), seven(op.v)
+    g = op.apply(u7)["grad"]
+    assert g.shape == (7, c.nnz, 3) and g[6].any() and g.tobytes() == np.stack([op.apply(u7[f])["grad"][0] for f in range(7)]).tobytes()
+    t = op.apply_transpose(v7)
+    assert t.shape == (7, c.E) and t[6].any() and t.tobytes() == np.stack([op.apply_transpose(v7[f])[0] for f in range(7)]).tobytes()
+
+
 def test_every_bin_is_populated_on_the_delaunay_mesh():
     plan = get_op("delaunay").c.grid.gls_adjoint_plan()
     assert all(v > 0 for v in plan.values()), plan

@@ -262,6 +262,27 @@ def test_determinism_batching_zero_and_linearity(case):
         assert (2.0 * bp).tobytes() == tp.tobytes() and (not unfolded or (2.0 * bd).tobytes() == td.tobytes())
 
 
+def _seven(x):
+    """seven inputs from the module's N_DIR: the five, and scaled copies of the first two"""
+    return np.concatenate([x, 0.5 * x, -3.0 * x])[:7]
+
+
+def test_a_batch_of_seven_equals_its_members_one_by_one():
+    """a full chunk of four and a chunk of three behind it, both products, on the smallest mesh"""
+    c = get_case("tet")
+    J = c.jac(True)
+    dK, ddm, v = _seven(c.dK), _seven(c.ddm), _seven(c.v)
+    for explicit in (False, True):
+        batch = c.jvp(J, dK, ddm if explicit else None)
+        ones = np.stack([c.jvp(J, dK[t], ddm[t] if explicit else None)[0] for t in range(7)])
+        assert batch.shape == (7, c.P) and batch[6].any() and batch.tobytes() == ones.tobytes(), explicit
+    for unfolded in (False, True):
+        bp, bd = c.vjp(J, v, unfolded)
+        singles = [c.vjp(J, v[t], unfolded) for t in range(7)]
+        assert bp.shape == (7, c.E, 9) and bp[6].any() and bp.tobytes() == np.stack([s[0][0] for s in singles]).tobytes(), unfolded
+        assert not unfolded or bd.tobytes() == np.stack([s[1][0] for s in singles]).tobytes()
+
+
 def test_zero_row_nodes_give_exact_zeros(case):
     c = case
     J = c.jac(True)

@@ -235,6 +235,20 @@ def test_duality_on_the_device(red, k):
 
 
 @pytest.mark.parametrize("k", VARIANTS)
+def test_a_batch_of_seven_equals_its_members_one_by_one(k):
+    """a full chunk of four and a chunk of three behind it, both products, for M = 1, 3 and 6 on the smallest mesh"""
+    r = get_reduced("tet")
+    c = r.c
+    J = r.jac(k, True)
+    seven = lambda x: np.concatenate([x, 0.5 * x, -3.0 * x])[:7]          # noqa: E731  (the module's five, and scaled copies of the first two)
+    dth, v = seven(r.dtheta[k]), seven(c.v)
+    batch = r.jvp(J, dth)
+    assert batch.shape == (7, c.P) and batch[6].any() and batch.tobytes() == np.stack([r.jvp(J, dth[t])[0] for t in range(7)]).tobytes()
+    vb = r.vjp(J, v)
+    assert vb.shape == (7, c.E, r.M(k)) and vb[6].any() and vb.tobytes() == np.stack([r.vjp(J, v[t])[0] for t in range(7)]).tobytes()
+
+
+@pytest.mark.parametrize("k", VARIANTS)
 def test_determinism_batching_zero_and_linearity(red, k):
     r, c = red, red.c
     J = r.jac(k, True)

@@ -219,6 +219,17 @@ def test_every_bin_is_populated_on_the_delaunay_mesh():
     assert sum(plan.values()) == c.P
 
 
+def test_a_batch_of_seven_equals_its_members_one_by_one():
+    """J . dX in chunks of 4 + 3 and J^T . v in chunks of 2 + 2 + 2 + 1, on the smallest mesh"""
+    c = get_case("tet")
+    J = c.jac(True)
+    seven = lambda x: np.concatenate([x, 0.5 * x, -3.0 * x])[:7]          # noqa: E731  (the module's five, and scaled copies of the first two)
+    dXs, vs = seven(c.dXs), seven(c.vs)
+    bj, bv = c.jvp(J, dXs), c.vjp(J, vs)
+    assert bj.shape == (7, c.P) and bj[6].any() and bj.tobytes() == np.stack([c.jvp(J, dXs[t])[0] for t in range(7)]).tobytes()
+    assert bv.shape == (7, c.P, 3) and bv[6].any() and bv.tobytes() == np.stack([c.vjp(J, vs[t])[0] for t in range(7)]).tobytes()
+
+
 def test_bit_for_bit(case):
     c = case
     J = c.jac(True)

@@ -3,9 +3,13 @@
 # tools/sanitize_gradop_driver.hip -- a stand-alone program with its own main -- are compiled with the sanitizers on the HOST side only
 # and linked with the library's other objects as `python -m ninpol_amd.build` left them.  No device is opened, nothing is loaded into
 # Python, and the device code is not instrumented.
-# Usage: bash tools/sanitize_gradop.sh      (exit code 0 = clean)
+# Usage: bash tools/sanitize_gradop.sh [DRIVER.hip]     (exit code 0 = clean)
+# DRIVER.hip: another stand-alone program of tools/ to build and run that way in its place (tools/launch_layer_driver.hip: the launch
+# layer of csrc/launch.hpp, which is header code and so instrumented with the driver)
 set -u -o pipefail
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
+DRIVER="${1:-$ROOT/tools/sanitize_gradop_driver.hip}"
+NAME="$(basename "$DRIVER" .hip)"
 W="${TMPDIR:-/tmp}/nin_sanitize_gradop"
 mkdir -p "$W"
 ROCM="${ROCM_PATH:-/opt/rocm}"
@@ -15,10 +19,10 @@ fail=0
 ( cd "$ROOT" && python -m ninpol_amd.build >/dev/null ) || fail=1
 OBJ="$ROOT/ninpol_amd/csrc/_obj"
 "$HIPCC" --offload-arch=gfx950 -O1 -g -fPIC -std=c++17 -Wno-unknown-pragmas $SAN -c "$ROOT/ninpol_amd/csrc/abi_gradop.hip" -o "$W/abi_gradop.o" || fail=1
-"$HIPCC" --offload-arch=gfx950 -O1 -g -fPIC -std=c++17 -Wno-unknown-pragmas $SAN -c "$ROOT/tools/sanitize_gradop_driver.hip" -o "$W/driver.o" || fail=1
+"$HIPCC" --offload-arch=gfx950 -O1 -g -fPIC -std=c++17 -Wno-unknown-pragmas $SAN -c "$DRIVER" -o "$W/$NAME.o" || fail=1
 others=$(ls "$OBJ"/*.o | grep -v -e /abi_gradop.o)
-"$HIPCC" --offload-arch=gfx950 -fsanitize=address,undefined "$W/driver.o" "$W/abi_gradop.o" $others -L "$ROCM/lib" -lamdhip64 -lgomp \
-    -Wl,-rpath,"$ROCM/lib" -o "$W/sanitize_gradop_driver" || fail=1
-ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 "$W/sanitize_gradop_driver" || fail=1
+"$HIPCC" --offload-arch=gfx950 -fsanitize=address,undefined "$W/$NAME.o" "$W/abi_gradop.o" $others -L "$ROCM/lib" -lamdhip64 -lgomp \
+    -Wl,-rpath,"$ROCM/lib" -o "$W/$NAME" || fail=1
+ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 "$W/$NAME" || fail=1
 echo "== sanitizers: $([ $fail = 0 ] && echo CLEAN || echo FINDINGS)"
 exit $fail
